@@ -17,7 +17,13 @@ weighting restriction, coarsest grid (17^3) iterated to relative residual 0.1 li
 reference's Solver (include/solvers.hpp:324-342; ~85 sweeps, LDS-resident kernel), fp64, zero
 initial guess, hash-noise right-hand side (synthetic). A step is one V-cycle.
 
-One JSON line is printed by rank 0. `roofline` prices the finest-grid smoother launch from HIP
+One JSON line is printed by rank 0. A plain run sets up, warms up, times exactly K cycles and prints
+the headline (`value` V-cycles/s, `ms_per_step`). `--dump-outputs DIR` then also writes the solution
+u after the last timed cycle as DIR/*.npy: the whole array as u.npy when it is at most 48 MB, else a
+fixed sample (seed DUMP_SEED, DUMP_SAMPLE global flat indices, sorted) as u_sample.npy, with its
+indices as u_sample_index.npy.
+
+Everything below is measured only with `--full`. `roofline` prices the finest-grid smoother launch from HIP
 events recorded on the library's own stream INSIDE the timed region:
   achieved = bytes the launch MUST move / launch time.  A streaming Jacobi sweep must move
   24 B per point (read u, read rhs, write u'); the fused pair k_jacobi2 makes ONE pass for two
@@ -30,6 +36,8 @@ events recorded on the library's own stream INSIDE the timed region:
 single (unfused) Jacobi sweeps of the same grid right after the timed region.
 `cpu_baseline` times the CPU oracle (our restatement of the reference algorithm; the
 reference itself has no 3-D path) on the host cores, rank 0, N=1 only.
+`ms_per_step_with_residual_norm` is the marginal cost of one more iteration of mg_solve's loop, and
+`residual_drop_per_cycle` the residual reduction of the benchmarked cycle from the zero guess.
 """
 from __future__ import annotations
 
@@ -47,20 +55,28 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_SEED = 20240607
+DUMP_SAMPLE = 1 << 21          # sampled points of u when the whole array is larger than DUMP_WHOLE_BYTES
+DUMP_WHOLE_BYTES = 48 << 20
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=30, help="timed V-cycles")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed V-cycles before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and per-kernel launch times, streaming sweep, "
+                         "mg_solve's per-iteration cost, residual drop, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed cycles, write the solution u of the last one to DIR/*.npy")
     ap.add_argument("--grid", dest="n", type=int, default=513, help="nodes per side (513 = nominal 512^3)")
     ap.add_argument("--levels", type=int, default=6)
     ap.add_argument("--smoother", choices=["jacobi", "rbgs", "zebra", "zebrax"], default="jacobi",
                     help="zebra / zebrax = zebra line Gauss-Seidel along y / along x (for --aniso-y / --aniso-x >> 1)")
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-cycles", type=int, default=8, help="oracle V-cycles timed for cpu_baseline (~1 s each at 513^3)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--cpu-cycles", type=int, default=8, help="with --full: oracle V-cycles timed for cpu_baseline (~1 s each at 513^3)")
     ap.add_argument("--transport", choices=["rccl", "gloo"], default="rccl",
                     help="N>1 halo transport: rccl = GPU-to-GPU over xGMI (one GPU per rank, the real thing); "
                          "gloo = rehearsal through host memory, ranks may share a GPU (numbers meaningless)")
@@ -86,7 +102,12 @@ def parse(argv=None):
     ap.add_argument("--rehearse", action="store_true",
                     help="plumbing check without a GPU: ranks rendezvous over gloo, plan their slabs, time nothing")
     ap.add_argument("--rehearse-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.dry_rank >= 0 and a.gpus > 1:
+        ap.error("--dump-outputs: a dry run computes nothing meaningful")
+    return a
 
 
 # ------------------------------------------------------------------------------------ launcher
@@ -191,6 +212,34 @@ def hash_rhs(n, dtype, z0=0, nz=None, seed=12345):
             v = (z >> np.uint64(11)).astype(np.float64) * (2.0 / 9007199254740992.0) - 1.0
             out[k] = np.where(inner, v, 0.0)
     return out
+
+
+def dump_outputs(a, s, z0, nz, dist):
+    """--dump-outputs DIR: the solution u after the last timed cycle (what a caller of mg_cycle_async reads back), in the
+    run's dtype. Whole when it is at most DUMP_WHOLE_BYTES, else the points at DUMP_SAMPLE seeded global flat indices
+    (sorted, repeats dropped). On z-slabs every rank contributes its own planes and rank 0 writes the files."""
+    u = s.get_solution().ravel()          # this rank's planes z0 .. z0 + nz - 1
+    plane = a.n * a.n
+    total = a.n * plane
+    lo = z0 * plane
+    idx = None
+    if total * u.itemsize > DUMP_WHOLE_BYTES:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+        u = u[idx[(idx >= lo) & (idx < lo + nz * plane)] - lo]
+    parts = [(lo, u)]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (lo, u))
+    if dist is not None and dist.get_rank() != 0:
+        return
+    vals = np.concatenate([p for _, p in sorted(parts, key=lambda x: x[0])])
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    if idx is None:
+        np.save(os.path.join(a.dump_outputs, "u.npy"), vals.reshape(a.n, a.n, a.n))
+    else:
+        assert vals.size == idx.size
+        np.save(os.path.join(a.dump_outputs, "u_sample.npy"), vals)
+        np.save(os.path.join(a.dump_outputs, "u_sample_index.npy"), idx.astype(np.float64))
 
 
 def rehearse(a, rank, world):
@@ -301,17 +350,21 @@ def main():
     # warmup (untimed)
     s.cycle_async(a.warmup)
     barrier()
-    # timed region: exactly K cycles, finest-level launches bracketed by HIP events
-    s.profile_begin()
+    # timed region: exactly K cycles; with --full the finest-level launches are bracketed by HIP events
+    if a.full:
+        s.profile_begin()
     groups0, sent0 = s.comm_stats()
     t0 = time.perf_counter()
     s.cycle_async(a.steps)
     barrier()
     t1 = time.perf_counter()
     groups1, sent1 = s.comm_stats()
-    _, sm_sweeps = s.profile_end()
-    prof = {k: s.profile_get(getattr(capi, "PROF_" + k)) for k in ("SMOOTH", "SMOOTH_PROLONG", "RESID_RESTRICT", "PROLONG")}
+    if a.full:
+        _, sm_sweeps = s.profile_end()
+        prof = {k: s.profile_get(getattr(capi, "PROF_" + k)) for k in ("SMOOTH", "SMOOTH_PROLONG", "RESID_RESTRICT", "PROLONG")}
     elapsed = t1 - t0
+    if a.dump_outputs:     # before anything else touches u
+        dump_outputs(a, s, z0, nz, dist)
     per_rank_ms = [1e3 * elapsed / a.steps]
     if dist is not None:
         import torch
@@ -323,6 +376,45 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    ms_per_step = 1e3 * elapsed / a.steps
+    cycles_per_s = a.steps / elapsed
+    out = {
+        "metric": f"V-cycles/sec (3D Poisson {a.n}^3 V(2,2)) + finest-grid smoother GB/s vs HBM roofline",
+        "value": cycles_per_s, "unit": "V-cycles/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": f"3D Poisson {a.n}^3 nodes (nominal {a.n - 1}^3), {a.levels}-level V(2,2), "
+                               f"{a.smoother}{' omega=6/7' if a.smoother == 'jacobi' else ''}, full-weighting, "
+                               f"{f'eps={a.aniso_eps}, first {a.semi} coarsenings in x,y only, ' if a.semi or a.aniso_eps != 1.0 else ''}"
+                               f"{f'y-coupling x{a.aniso_y}, ' if a.aniso_y != 1.0 else ''}"
+                               f"{f'x-coupling x{a.aniso_x}, ' if a.aniso_x != 1.0 else ''}"
+                               + (f"20 coarse sweeps, {a.dtype}" if a.semi else
+                                  f"coarse {((a.n - 1) >> (a.levels - 1)) + 1}^3 iterated to rel. residual 0.1, {a.dtype}"),
+                   "parallelism": (f"z-slab x{world}" + ("" if a.transport == "rccl" else " (gloo rehearsal)") + (" (RCCL rehearsal: all ranks on GPU 0, socket transport)" if a.rccl_same_gpu else "")) if world > 1 else "single GPU",
+                   "first_gathered_level": first_gathered},
+        **({"dry_run": f"rank {rank} of {world} WITHOUT communication: one rank's compute schedule, not a result",
+            "dry_run_coarse_sweeps": dry_coarse} if dry else {}),
+        "transport": transport_name, "rccl_ranks": transport_ranks if transport_name == "rccl" else None,
+        "ms_per_step_ranks": per_rank_ms,
+        # what rank 0 posts per cycle: message groups (halo exchanges, gather, scatter: one ncclGroup each) and bytes sent
+        "comm_per_cycle": ({"message_groups": (groups1 - groups0) / a.steps, "bytes_sent": (sent1 - sent0) / a.steps}
+                           if world > 1 else None),
+    }
+
+    if a.full:
+        out.update(full_figures(a, s, capi, world, nz, prof, sm_sweeps, hist, barrier))
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(a)
+    if rank == 0 or dry:
+        print(json.dumps(out))
+    s.close()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_figures(a, s, capi, world, nz, prof, sm_sweeps, hist, barrier):
+    """--full: what the headline does not need, measured after the timed region (these runs overwrite u) and priced from
+    the HIP events recorded inside it."""
     # mg_solve's cycle = this cycle + one finest-grid residual norm: time a few of them for the record
     barrier()
     # (marginal cost of one more iteration of mg_solve's loop: the loop's fixed part -- sum b^2, the first norm and, where the
@@ -346,8 +438,6 @@ def main():
             s.smooth(0, capi.SMOOTH_JACOBI, 1, capi.ARR_U, capi.ARR_RHS)
         stream_ms = s.timer_stop() / 9
 
-    ms_per_step = 1e3 * elapsed / a.steps
-    cycles_per_s = a.steps / elapsed
     esz = 8 if a.dtype == "f64" else 4
     pts_local = nz * a.n * a.n
     sweep_bytes = 3 * esz * pts_local                 # read u, read rhs, write u': what one pass must move
@@ -394,27 +484,7 @@ def main():
                2 * esz * pts_local + esz * pts_c, "prolong"),
     ) if k]
 
-    out = {
-        "metric": f"V-cycles/sec (3D Poisson {a.n}^3 V(2,2)) + finest-grid smoother GB/s vs HBM roofline",
-        "value": cycles_per_s, "unit": "V-cycles/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": f"3D Poisson {a.n}^3 nodes (nominal {a.n - 1}^3), {a.levels}-level V(2,2), "
-                               f"{a.smoother}{' omega=6/7' if a.smoother == 'jacobi' else ''}, full-weighting, "
-                               f"{f'eps={a.aniso_eps}, first {a.semi} coarsenings in x,y only, ' if a.semi or a.aniso_eps != 1.0 else ''}"
-                               f"{f'y-coupling x{a.aniso_y}, ' if a.aniso_y != 1.0 else ''}"
-                               f"{f'x-coupling x{a.aniso_x}, ' if a.aniso_x != 1.0 else ''}"
-                               + (f"20 coarse sweeps, {a.dtype}" if a.semi else
-                                  f"coarse {((a.n - 1) >> (a.levels - 1)) + 1}^3 iterated to rel. residual 0.1, {a.dtype}"),
-                   "parallelism": (f"z-slab x{world}" + ("" if a.transport == "rccl" else " (gloo rehearsal)") + (" (RCCL rehearsal: all ranks on GPU 0, socket transport)" if a.rccl_same_gpu else "")) if world > 1 else "single GPU",
-                   "first_gathered_level": first_gathered},
-        **({"dry_run": f"rank {rank} of {world} WITHOUT communication: one rank's compute schedule, not a result",
-            "dry_run_coarse_sweeps": dry_coarse} if dry else {}),
-        "transport": transport_name, "rccl_ranks": transport_ranks if transport_name == "rccl" else None,
-        "ms_per_step_ranks": per_rank_ms,
-        # what rank 0 posts per cycle: message groups (halo exchanges, gather, scatter: one ncclGroup each) and bytes sent
-        "comm_per_cycle": ({"message_groups": (groups1 - groups0) / a.steps, "bytes_sent": (sent1 - sent0) / a.steps}
-                           if world > 1 else None),
+    return {
         "ms_per_step_with_residual_norm": solve_ms_per_cycle,
         "roofline": {"bound": "hbm",
                      "kernel": ((f"finest-grid fused double {'red-black half-' if a.smoother == 'rbgs' else 'Jacobi '}sweep {pair_kernel} ({a.n}^3, one pass over HBM)" if fused_pair
@@ -443,13 +513,6 @@ def main():
         "device_bytes": s.device_bytes(),
     }
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(a)
-    if rank == 0 or dry:
-        print(json.dumps(out))
-    s.close()
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 def _template_args(name):

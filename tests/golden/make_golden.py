@@ -14,6 +14,8 @@ What it writes (data only -- inputs and expected outputs, never reference source
   fixture_*.txt/.npz   the reference's own result files, copied as data:
                    GeometricMultigrid/test/{MGGS4.txt,x.mtx} (-n 385 -a 1 -w 10 -ml 5 -test 0 -smt 2)
                    WebInterface/{MGGS4.txt,x.mtx}            (-n 145 -a 1 -w 10 -ml 5 -test 1 -smt 1)
+  ref_cli.json     exit code and stdout of oracle/_ref/Multigrid_ref for the command lines the CLI tests check
+                   (`python tests/golden/make_golden.py cli` rewrites only this file)
 """
 import json
 import os
@@ -27,6 +29,11 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 REF_OPS = os.path.join(ROOT, "oracle", "_ref", "ref_ops")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "Multigrid_ref")
+# command lines of the reference's executable whose exit code and stdout tests/test_cli_and_mirror.py compares ours with
+CLI_ARGS = [["--help"], ["-n", "abc"], ["-n", "0"], ["-n"], ["-n", "33", "-ml", "0"], ["-n", "33", "-test", "-1"],
+            ["-n", "33", "-w", "-2"], ["-n", "33", "-ml", "x"],
+            ["-n", "33", "-a", "2.5", "-w", "4", "-ml", "3", "-test", "7", "-smt", "9"]]
 REFDIR = "/root/reference"
 
 
@@ -40,6 +47,25 @@ def run_op(op, n, levels, level, alpha, length, smt, test, u=None, b=None):
         subprocess.run([REF_OPS, op, str(n), str(levels), str(level), repr(alpha), repr(length),
                         str(smt), str(test), fin, fout], check=True)
         return np.fromfile(fout, "<f8")
+
+
+def cli_outputs():
+    """ref_cli.json: exit code and stdout of the reference's executable for CLI_ARGS. The last one starts a solve that
+    reads out of range; only its lines before the run are kept (`head`)."""
+    if not os.path.exists(REF_BIN):
+        sys.exit("build oracle/_ref first: make -C oracle ref")
+    rows = []
+    for args in CLI_ARGS:
+        with tempfile.TemporaryDirectory() as td:
+            p = subprocess.run([REF_BIN, *args], cwd=td, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+        lines = []
+        for line in p.stdout.splitlines():
+            if line.startswith(("Initialization time", "Error:", "Openmp enabled")) and "-smt" in args:
+                break
+            lines.append(line)
+        rows.append(dict(args=args, rc=p.returncode if "-smt" not in args else None, stdout_lines=lines))
+    with open(os.path.join(HERE, "ref_cli.json"), "w") as f:
+        json.dump(rows, f, indent=1)
 
 
 def main():
@@ -118,9 +144,10 @@ def main():
         cnt = int(vals[0])
         assert cnt == vals.size - 1
         np.savez_compressed(os.path.join(HERE, dst), x=vals[1:])
+    cli_outputs()
     for p in os.listdir(HERE):
         os.chmod(os.path.join(HERE, p), 0o644)
 
 
 if __name__ == "__main__":
-    main()
+    cli_outputs() if sys.argv[1:] == ["cli"] else main()

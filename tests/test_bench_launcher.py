@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -47,7 +48,7 @@ def test_bench_dry_rank_runs_one_ranks_schedule_on_one_gpu():
     """--dry-rank R: one process plays rank R of N with no peers (measurement tool). The line must say so, and a middle
     rank's schedule must post the same message groups per cycle as the real transports do (nothing moves)."""
     p = _run(["--gpus", "4", "--dry-rank", "1", "--steps", "3", "--warmup", "1", "--grid", "129", "--levels", "4", "--dist-min-n", "65",
-              "--no-cpu-baseline"])
+              "--full", "--no-cpu-baseline"])
     assert p.returncode == 0, p.stderr
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -66,8 +67,8 @@ def test_bench_launches_real_rccl_ranks_on_one_gpu():
     """`python3 bench.py --gpus 2` as the driver types it, with RCCL as the transport: --rccl-same-gpu puts both ranks on GPU 0
     and gives each a host id of its own, so RCCL accepts them and moves the halos over its socket transport. The line must come
     from two RCCL ranks and show the cycle converging like the single-GPU one."""
-    p = _run(["--gpus", "2", "--rccl-same-gpu", "--steps", "3", "--warmup", "1", "--grid", "257", "--levels", "5", "--no-cpu-baseline",
-              "--launch-timeout", "240"], timeout=400)
+    p = _run(["--gpus", "2", "--rccl-same-gpu", "--steps", "3", "--warmup", "1", "--grid", "257", "--levels", "5", "--full",
+              "--no-cpu-baseline", "--launch-timeout", "240"], timeout=400)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -75,3 +76,38 @@ def test_bench_launches_real_rccl_ranks_on_one_gpu():
     assert out["transport"] == "rccl" and out["rccl_ranks"] == 2 and out["n_gpus"] == 2
     assert len(out["ms_per_step_ranks"]) == 2 and out["comm_per_cycle"]["message_groups"] > 0
     assert 0.15 < out["residual_drop_per_cycle"] < 0.30      # 0.226 on one GPU
+
+
+def test_bench_rejects_zero_steps():
+    p = _run(["--steps", "0", "--warmup", "1"])
+    assert p.returncode == 2 and "--steps must be >= 1" in p.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline only; --dump-outputs writes the solution of the last timed cycle, the same with and
+    without --full (the extra measurements come after it), and that solution is the oracle's after W + K V-cycles."""
+    from oracle import pyoracle as po
+    args = ["--steps", "3", "--warmup", "1", "--grid", "65", "--levels", "3"]
+    p = _run([*args, "--dump-outputs", str(tmp_path / "plain")])
+    assert p.returncode == 0, p.stderr
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["unit"] == "V-cycles/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert "roofline" not in out and "cpu_baseline" not in out
+    u = np.load(tmp_path / "plain" / "u.npy")
+    assert u.shape == (65, 65, 65) and u.dtype == np.float64
+    p = _run([*args, "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert p.returncode == 0, p.stderr
+    assert "roofline" in json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert np.array_equal(np.load(tmp_path / "full" / "u.npy"), u)
+
+    import bench
+    a = bench.parse(args)
+    o = po.Solver(bench.workload_desc(po, a))
+    o.set_rhs(bench.hash_rhs(a.n, np.float64))
+    for _ in range(a.warmup + a.steps):
+        o.cycle()
+    np.testing.assert_allclose(u, o.get_solution(), rtol=1e-12, atol=1e-14)

@@ -20,6 +20,11 @@ G = os.path.join(ROOT, "tests", "golden")
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "Multigrid_ref")
 
 
+def ref_cli(args):
+    """What the reference's executable printed for this command line (tests/golden/ref_cli.json, make_golden.py cli)."""
+    return [r for r in json.load(open(os.path.join(G, "ref_cli.json"))) if r["args"] == list(args)][0]
+
+
 def run_cli(exe, args, cwd):
     p = subprocess.run([exe, *args], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     return p.returncode, p.stdout
@@ -43,10 +48,12 @@ def test_cli_errors_go_to_stdout_and_exit_1(args, expect, tmp_path):
     exe = mgbuild.build_cli()
     rc, out = run_cli(exe, args, tmp_path)
     assert rc == 1 and expect in out
+    ours = [l for l in out.splitlines() if "MI355X extensions" not in l and not l.startswith("  -dim")]
+    ref = ref_cli(args)
+    assert ref["rc"] == rc and ours == ref["stdout_lines"]
     if os.path.exists(REF_BIN):  # the real reference, compiled in the build container
         rc_ref, out_ref = run_cli(REF_BIN, args, tmp_path)
         assert rc_ref == rc
-        ours = [l for l in out.splitlines() if "MI355X extensions" not in l and not l.startswith("  -dim")]
         assert ours == out_ref.splitlines()
 
 
@@ -67,6 +74,7 @@ def test_cli_echo_lines_match_reference(tmp_path):
     assert head == ["Inserted N = 33", "Inserted alpha = 2.5", "Inserted width = 4", "Inserted level = 3",
                     "Inserted test number = 7", "Inserted Smoother number = 9",
                     "Warning: Invalid test case index. Default test case selected."]
+    assert ref_cli(args)["stdout_lines"] == head
     if os.path.exists(REF_BIN):
         _, out_ref = run_cli(REF_BIN, args, tmp_path)
         assert echo_lines(out_ref) == head
@@ -93,11 +101,10 @@ def test_reference_main_cpp_builds_against_the_mirror(tmp_path):
     """SURVEY §8b-2 / INTEGRATION.md B: the reference's OWN src/main.cpp, compiled where it lies, builds
     and links against include/multigrid_hip.hpp + host/utilities.cpp + libmg_hip.so -- including
     Utils::Initialization_for_N (main.cpp:16) and the never-applied BiCGSTAB cycle (main.cpp:56).
-    Container only: the reference does not exist on the GPU box."""
-    if not os.path.exists(mgbuild.REFERENCE_MAIN):
-        pytest.skip("/root/reference is not mounted here")
-    exe = mgbuild.build_reference_main(str(tmp_path / "refmain"))
-    assert exe and os.path.exists(exe)
+    __graft_entry__.build() makes it with oracle/Makefile wherever the reference sources are present."""
+    exe = mgbuild.build_reference_main()
+    if not exe:
+        pytest.skip("oracle/_ref/refmain_mirror was not built (the reference sources were absent at build time)")
     rc, out = run_cli(exe, ["--help"], tmp_path)   # host-only path of the binary: usage + exit(1)
     assert rc == 1 and "Usage: ./Multigrid [OPTIONS]" in out
     rc, out = run_cli(exe, ["-n", "abc"], tmp_path)
@@ -154,7 +161,7 @@ def test_reference_main_cpp_on_the_mirror_reproduces_the_reference_runs(args, ke
     the `-smt 2` (BiCGSTAB -> Jacobi cycle) fixture run."""
     exe = mgbuild.build_reference_main()
     if not exe:
-        pytest.skip("tests/cpp/_build/refmain_mirror was not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/refmain_mirror was not built (the reference sources were absent at build time)")
     rc, out = run_cli(exe, args.split(), tmp_path)
     assert rc == 0, out
     case = [c for c in json.load(open(os.path.join(G, "ref_solve.json"))) if c["key"] == key][0]

@@ -77,7 +77,9 @@ def test_oracle_under_asan_and_ubsan(tmp_path):
 
 CLI_CASES = [["--help"], ["-n", "abc"], ["-n", "0"], ["-n"], ["-n", "33", "-ml", "0"], ["-n", "33", "-test", "-1"],
              ["-n", "33", "-w", "-2"], ["-n", "33", "-ml", "x"], ["-n", "33", "-maxit", "-3"], ["-n", "33", "-smt", "zz"],
-             ["-n", "33", "-a"], ["-a", "2.5", "-w", "3", "-test", "9", "-smt", "7", "-n", "x"]]
+             # a trailing flag without its value is ignored, as in the reference: n = 200 with the default 2 levels is then
+             # refused before any device call (n = 33 would start a solve wherever a GPU is present)
+             ["-n", "200", "-a"], ["-a", "2.5", "-w", "3", "-test", "9", "-smt", "7", "-n", "x"]]
 
 
 def test_cli_parser_under_asan_and_ubsan(tmp_path):

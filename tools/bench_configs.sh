@@ -1,10 +1,11 @@
 #!/bin/bash
-# tools/bench_configs.sh <tag> -- the other BASELINE configurations / extensions on one GPU, one JSON line each under gpurun_out/
+# tools/bench_configs.sh <tag> -- the other BASELINE configurations / extensions on one GPU, one JSON line each under $OUT (default bench_out/)
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-cd "$ROOT"; mkdir -p gpurun_out
+OUT=${OUT:-$ROOT/bench_out}
+cd "$ROOT"; mkdir -p "$OUT"
 TAG=${1:-r02}
-run() { name=$1; shift; python bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" > gpurun_out/${TAG}_bench_$name.json 2> gpurun_out/${TAG}_bench_$name.err || tail -3 gpurun_out/${TAG}_bench_$name.err
-  python - gpurun_out/${TAG}_bench_$name.json $name <<'PY'
+run() { name=$1; shift; python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline "$@" > $OUT/${TAG}_bench_$name.json 2> $OUT/${TAG}_bench_$name.err || tail -3 $OUT/${TAG}_bench_$name.err
+  python - $OUT/${TAG}_bench_$name.json $name <<'PY'
 import json, sys
 try:
     o = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 RE=$1; VAR=$2; shift 2
 for v in "$@"; do
   rm -rf /tmp/kt_$v; cd /tmp && export TMPDIR=/tmp
-  env $VAR=$v rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$v -- python3 $ROOT/bench.py --no-cpu-baseline --steps 6 --warmup 1 $KT_BENCH_ARGS > /dev/null 2>&1
+  env $VAR=$v rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$v -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 6 --warmup 1 $KT_BENCH_ARGS > /dev/null 2>&1
   echo "== $VAR=$v"
   python3 - /tmp/kt_$v "$RE" <<'PY'
 import csv, glob, re, sys, collections
