@@ -1,0 +1,684 @@
+"""The operators of the extensions (3-D, fp32, omega != 1, red-black and zebra line GS, V(nu1,nu2), full weighting, fixed
+coarse sweeps, anisotropic coefficients, semi-coarsening) against an INDEPENDENT reference, tests/npref.py: numpy, written
+from the definitions, computed in long double (float64 above 129^3).
+
+Every other test of these features compares with the CPU oracle (oracle/), and the kernels must match the oracle bit
+for bit; a mistake shared by both would pass all of them. Here:
+  * the oracle against npref, operator by operator, over a generated grid of cases (CPU);
+  * identities that need no reference at all (adjointness of R and P, exactness on multilinear functions, the residual
+    of a quadratic on every level, a vanishing residual on the last colour of a sweep, Jacobi = u + omega D^-1 r, the
+    exact solution as a fixed point of a cycle) on the oracle (CPU);
+  * the same comparisons on the HIP operators, on both sides of every dispatch gate (GPU: OP_ROWS, CYCLE_ROWS).
+
+Error bounds are derived from the operation: a point result may differ from the exact one by c * eps * m, m the sum of
+the magnitudes of the terms that form it (|b| + |A - D| |u| over |D| for a point solve, |b| + |A| |u| for a residual,
+R |f| and P |e| for the transfers), which includes the rounding of the coefficients to the working precision. Results
+of several steps are held to a max-norm bound whose constant is written next to the assert. fp32 results are compared
+with the long-double values through the same bounds: an accuracy check, not fp32 against fp32.
+"""
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from tests import npref as npr
+
+LD = np.longdouble
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+
+def eps_of(dtype):
+    return float(np.finfo(np.float64 if dtype == po.MG_F64 else np.float32).eps)
+
+
+def np_of(dtype):
+    return np.float64 if dtype == po.MG_F64 else np.float32
+
+
+def admissible_levels(n):
+    L = 1
+    while (n - 1) % (1 << L) == 0 and (n - 1) // (1 << L) + 1 >= 3:
+        L += 1
+    return L
+
+
+def check_points(got, ref, mag, eps, c, what):
+    """|got - ref| <= c eps mag at every node"""
+    err = np.abs(np.asarray(got).astype(LD) - ref)
+    bound = c * eps * mag + np.finfo(np.float64).tiny
+    bad = err > bound
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.size} nodes out of bound, first at "
+                           f"{np.argwhere(bad)[0].tolist()}, worst err/bound {float((err / bound).max()):.3g}")
+
+
+def check_max(got, ref, bound, what):
+    err = float(np.abs(np.asarray(got).astype(LD) - ref).max())
+    assert err <= bound, f"{what}: max error {err:.3e} > bound {bound:.3e} ({err / bound:.3g} x)"
+
+
+def sweep_scale(P, l, b, *us):
+    """max over the nodes of |u| + the point-solve magnitude, over every iterate of a sweep"""
+    return max(float((np.abs(P.as_prec(u)) + P.point_solve_mag(u, b, l)).max()) for u in us)
+
+
+# ---- per-operation constants (c in c * eps * magnitude)
+C_POINT = 16    # point solve / damped update: <= 2*dim + 1 terms summed, a division, two roundings of coefficients
+C_RESID = 16    # residual: 2*dim + 1 products summed and one subtraction, coefficient rounding
+C_XFER = 8      # full weighting / interpolation: exact weights, <= 3 additions per axis
+C_LINE = 64     # a line solve, times the line's amplification |D| / (|D| - 2|c_line|) (npref.line_amplification)
+
+
+def line_axis(P, smoother):
+    return P.dim - 2 if smoother == npr.SMOOTH_ZEBRA_Y else P.dim - 1
+
+
+def sweep_bound(P, l, smoother, u_in, u_out, b, eps):
+    """max-norm bound of one sweep: a Gauss-Seidel node reads neighbours that carry their own rounding; with the weights
+    of the new neighbours summing to at most 1/2 of the diagonal (to 1 for the second colour of red-black), the error
+    stays within twice the point bound"""
+    s = sweep_scale(P, l, b, u_in, u_out)
+    if smoother in (npr.SMOOTH_ZEBRA_Y, npr.SMOOTH_ZEBRA_X):
+        return C_LINE * eps * npr.line_amplification(P, l, line_axis(P, smoother)) * s
+    return 2 * C_POINT * eps * s
+
+
+# ======================================================================= the case grid (CPU)
+ANISO = [(1.0, 1.0, 1.0), (1.0, 1.0, 0.01), (1.0, 0.05, 1.0), (30.0, 1.0, 1.0), (1.0, 100.0, 1.0), (0.05, 1.0, 30.0),
+         (100.0, 1.0, 0.05)]
+OMEGA = [1.0, 6.0 / 7.0, 0.8]
+
+
+def _op_cases():
+    out, q = [], 0
+    for dim in (2, 3):
+        for n in (3, 5, 9, 17, 21, 25, 33, 37, 65, 97):
+            Lmax = admissible_levels(n)
+            for dtype in (po.MG_F64, po.MG_F32):
+                if dim == 3 and n == 97 and dtype == po.MG_F32:
+                    continue
+                L = Lmax if (q % 3) else max(1, Lmax - 1)
+                semi = (q % L) if dim == 3 else 0
+                out.append(dict(dim=dim, n=n, levels=L, dtype=dtype, semi_xy=semi, aniso=ANISO[q % len(ANISO)],
+                                omega=OMEGA[q % 3], alpha=(1.0, 0.7, 2.5)[q % 3], length=(1.0, 10.0, 2.0)[(q // 3) % 3]))
+                q += 1
+    return out
+
+
+OP_CASES = _op_cases()
+
+
+def _id(c):
+    return (f"{c['dim']}d-n{c['n']}-L{c['levels']}-{'f64' if c['dtype'] == 0 else 'f32'}-s{c['semi_xy']}"
+            f"-a{'x'.join('%g' % a for a in c['aniso'])}-w{c['omega']:.3g}")
+
+
+def test_case_grid_covers_the_parameter_space():
+    seen = lambda key: {c[key] if key != "aniso" else a for c in OP_CASES for a in (c["aniso"] if key == "aniso" else [0])}
+    assert {3, 5, 9, 17, 21, 25, 33, 37, 65, 97} <= {c["n"] for c in OP_CASES}
+    assert {0.01, 0.05, 30.0, 100.0} <= set(seen("aniso")) and set(OMEGA) <= seen("omega")
+    assert {c["semi_xy"] for c in OP_CASES if c["dim"] == 3} >= {0, 1, 2, 3}
+    assert all(c["levels"] == 1 for c in OP_CASES if c["n"] == 3) and max(c["levels"] for c in OP_CASES) >= 6
+
+
+@pytest.mark.parametrize("case", OP_CASES, ids=[_id(c) for c in OP_CASES])
+def test_geometry_and_coefficients(case):
+    d = po.make_desc(**case)
+    P = npr.Problem(**case)
+    for l in range(case["levels"]):
+        assert po.level_shape(d, l) == P.shape(l), l
+        ca, cd = P.coef(l)
+        ref = ([ca[-1], ca[-2], ca[0]] if P.dim == 3 else [ca[-1], ca[-2]]) + [cd]
+        got = po.level_coef(d, l)
+        got = list(got[:3]) + [got[3]] if P.dim == 3 else [got[0], got[1], got[3]]
+        for g, r in zip(got, ref):    # computed in double by the oracle: a few roundings
+            assert abs(LD(g) - r) <= 8 * np.finfo(np.float64).eps * abs(r), (l, got, ref)
+
+
+@pytest.mark.parametrize("case", OP_CASES, ids=[_id(c) for c in OP_CASES])
+def test_oracle_single_operators_against_npref(case):
+    d = po.make_desc(**case)
+    ops, P = po.Ops(d), npr.Problem(**case)
+    eps, dt = eps_of(case["dtype"]), np_of(case["dtype"])
+    rng = np.random.default_rng(case["n"] * 7 + case["dim"])
+    big = np.prod(P.shape(0)) > 200_000
+    for l in range(case["levels"]):
+        shp = P.shape(l)
+        u, b = rng.standard_normal(shp).astype(dt), rng.standard_normal(shp).astype(dt)
+        w = P.as_prec(u)
+        ref = P.jacobi(u, b, l)
+        check_points(ops.jacobi(l, u, b), ref, np.abs(w) + P.point_solve_mag(u, b, l), eps, C_POINT, f"jacobi l{l}")
+        r, _ = ops.residual(l, u, b)
+        check_points(r, P.residual(u, b, l), np.abs(P.as_prec(b)) + P.apply_A(u, l, absolute=True), eps, C_RESID,
+                     f"residual l{l}")
+        # three Jacobi sweeps: each sweep is non-expansive in the max norm (0 < omega <= 1), so the bounds add up
+        us = [w]
+        for _ in range(3):
+            us.append(P.jacobi(us[-1], b, l))
+        bound = sum(C_POINT * eps * sweep_scale(P, l, b, x) for x in us[:3])
+        check_max(ops.smooth(l, po.SMOOTH_JACOBI, 3, u, b), us[3], bound, f"jacobi x3 l{l}")
+        for sm in (po.SMOOTH_RBGS, po.SMOOTH_ZEBRA_Y, po.SMOOTH_ZEBRA_X) + ((po.SMOOTH_GS_LEX,) if not big else ()):
+            ref = P.smooth(sm, 1, u, b, l)
+            check_max(ops.smooth(l, sm, 1, u, b), ref, sweep_bound(P, l, sm, u, ref, b, eps), f"smoother {sm} l{l}")
+        if l + 1 < case["levels"]:
+            c = rng.standard_normal(P.shape(l + 1)).astype(dt)
+            assert np.array_equal(ops.inject(u).astype(LD), P.inject(u, l)), f"inject l{l}"
+            check_points(ops.restrict_fw(u), P.restrict_fw(u, l), P.restrict_fw(np.abs(w), l), eps, C_XFER, f"fw l{l}")
+            pc = P.prolong(c, l)
+            check_points(ops.prolong_overwrite(c), pc, P.prolong(np.abs(P.as_prec(c)), l), eps, C_XFER, f"prolong l{l}")
+            check_points(ops.prolong_add(c, u), w + pc, np.abs(w) + P.prolong(np.abs(P.as_prec(c)), l), eps, C_XFER,
+                         f"prolong-add l{l}")
+
+
+# ---- whole cycles, COARSE_FIXED
+SMOOTHERS = [po.SMOOTH_JACOBI, po.SMOOTH_RBGS, po.SMOOTH_ZEBRA_Y, po.SMOOTH_ZEBRA_X, po.SMOOTH_GS_LEX]
+NU = [(2, 2), (1, 2), (2, 1), (0, 3), (3, 0)]
+
+
+def _cycle_cases():
+    out, q = [], 0
+    for c in OP_CASES:
+        if c["levels"] < 2 or (c["dim"] == 3 and c["n"] > 65):
+            continue
+        for cyc in (po.CYCLE_V, po.CYCLE_SAWTOOTH):
+            sm = SMOOTHERS[q % len(SMOOTHERS)]
+            if sm == po.SMOOTH_GS_LEX and c["n"] > 33:
+                sm = po.SMOOTH_RBGS
+            nu_pre, nu_post = NU[q % len(NU)]
+            out.append(dict(c, cycle=cyc, smoother=sm, nu_pre=nu_pre, nu_post=nu_post,
+                            restriction=(po.RESTRICT_FULLW, po.RESTRICT_INJECT)[q % 2] if cyc == po.CYCLE_V else po.RESTRICT_INJECT,
+                            coarse_mode=po.COARSE_FIXED, coarse_maxit=(3, 8, 1)[q % 3], outer_pre_gs=0, ncycles=1 + q % 3))
+            q += 1
+    return out
+
+
+CYCLE_CASES = _cycle_cases()
+
+
+def _cid(c):
+    return _id(c) + f"-{'V' if c['cycle'] else 'saw'}-sm{c['smoother']}-nu{c['nu_pre']}{c['nu_post']}-r{c['restriction']}-k{c['ncycles']}"
+
+
+# A cycle of npref at the working precision differs from the exact one by rounding amplified by the coarse solve: the
+# fine residual (|A| |u| ~ |D| |u|) enters a coarse problem whose diagonal is up to 4^(L-1) smaller, each of its sweeps
+# adding r / D_coarse. CYCLE_K * eps * (D_0 / D_{L-1}) * (1 + coarse sweeps) * scale bounds it with a margin of about
+# 10 over the largest ratio seen over the case grid (fp64 and fp32).
+CYCLE_K = 256
+
+
+def cycle_bound(P, eps, coarse_sweeps, scale):
+    amp = float(abs(P.coef(0)[1]) / abs(P.coef(P.L - 1)[1]))
+    return CYCLE_K * eps * amp * (1 + coarse_sweeps) * scale
+
+
+@pytest.mark.parametrize("case", CYCLE_CASES, ids=[_cid(c) for c in CYCLE_CASES])
+def test_oracle_cycles_against_npref(case):
+    kw = {k: v for k, v in case.items() if k != "ncycles"}
+    eps, dt = eps_of(case["dtype"]), np_of(case["dtype"])
+    P = npr.Problem(**kw)
+    s = po.Solver(po.make_desc(**kw))
+    rng = np.random.default_rng(case["n"] + 31 * case["smoother"])
+    b = rng.standard_normal(P.shape(0)).astype(dt)
+    u0 = (0.1 * rng.standard_normal(P.shape(0))).astype(dt)
+    s.set_rhs(b); s.set_solution(u0)
+    u = P.as_prec(u0)
+    for k in range(case["ncycles"]):
+        st = s.cycle()
+        assert st.coarse_iters == case["coarse_maxit"]
+        u = P.cycle(u, b, case["coarse_maxit"])
+        scale = float(np.abs(u).max()) + sweep_scale(P, 0, b, u0)
+        check_max(s.get_solution(), u, cycle_bound(P, eps, case["coarse_maxit"], scale), f"cycle {k}")
+
+
+@pytest.mark.parametrize("cycle", [po.CYCLE_V, po.CYCLE_SAWTOOTH])
+@pytest.mark.parametrize("dim,n,levels,smoother,semi,aniso", [
+    (2, 33, 3, po.SMOOTH_JACOBI, 0, (1.0, 1.0, 1.0)),
+    (3, 17, 3, po.SMOOTH_RBGS, 1, (1.0, 1.0, 0.05)),
+    (3, 17, 3, po.SMOOTH_ZEBRA_Y, 0, (1.0, 30.0, 1.0)),
+])
+def test_oracle_solve_lockstep_against_npref(cycle, dim, n, levels, smoother, semi, aniso):
+    """a whole solve with the iterate-to-tolerance coarse solve (chaotic: SURVEY §7), replayed by npref with the oracle's
+    per-cycle sweep counts; history and solution held to round-off"""
+    kw = dict(dim=dim, n=n, levels=levels, dtype=po.MG_F64, length=1.0, alpha=1.0, cycle=cycle, smoother=smoother,
+              omega=6 / 7 if smoother == po.SMOOTH_JACOBI else 1.0, nu_pre=2, nu_post=2, restriction=po.RESTRICT_FULLW,
+              coarse_mode=po.COARSE_TOL, coarse_tol=0.1, coarse_maxit=500, outer_pre_gs=2, semi_xy=semi, aniso=aniso)
+    P = npr.Problem(**kw)
+    s = po.Solver(po.make_desc(**kw))
+    b = np.random.default_rng(5).standard_normal(P.shape(0))
+    s.set_rhs(b)
+    hist, stats = s.solve(1e-9, 12)
+    counts = [st.coarse_iters for st in stats]
+    u, href = P.solve(np.zeros(P.shape(0)), b, counts, tol=1e-9)
+    assert len(hist) == len(href)
+    # history entries: sums of squares in another order, and iterates within the cycle bound below: relative 1e-9
+    # on entries above 1e-6, absolute 1e-13 below
+    np.testing.assert_allclose(hist, href.astype(float), rtol=1e-9, atol=1e-13)
+    eps = eps_of(po.MG_F64)
+    scale = float(np.abs(u).max()) + float(np.abs(b).max()) / float(abs(P.coef(0)[1]))
+    check_max(s.get_solution(), u, len(counts) * cycle_bound(P, eps, max(counts), scale), "solve")
+
+
+# ======================================================================= identities on the oracle (no reference)
+ID_CASES = [c for c in OP_CASES if c["levels"] >= 2]
+
+
+def _interior_random(rng, shape, dt):
+    a = rng.standard_normal(shape).astype(dt)
+    a[npr.boundary_mask(shape)] = 0
+    return a
+
+
+def _ml(idx, dim):
+    if dim == 2:
+        j, i = idx
+        return 1 + 3 * i - 2 * j + i * j
+    k, j, i = idx
+    return 1 + 3 * i - 2 * j + k + i * j - j * k + i * k + i * j * k / 8
+
+
+@pytest.mark.parametrize("case", ID_CASES, ids=[_id(c) for c in ID_CASES])
+def test_identities_of_the_transfers(case):
+    d = po.make_desc(**case)
+    ops, P = po.Ops(d), npr.Problem(**case)
+    eps, dt = eps_of(case["dtype"]), np_of(case["dtype"])
+    rng = np.random.default_rng(17)
+    for l in range(case["levels"] - 1):
+        fs, cs = P.shape(l), P.shape(l + 1)
+        ncoarsened = P.dim - (1 if P.semi[l] else 0)
+        # adjointness: 2^d <R r, e> = <r, P e> for r, e vanishing on the boundary (2^2 on a semi transition)
+        r, e = _interior_random(rng, fs, dt), _interior_random(rng, cs, dt)
+        Rr = ops.restrict_fw(r).astype(LD)
+        Pe = ops.prolong_overwrite(e).astype(LD)
+        lhs = (2 ** ncoarsened) * np.sum(Rr * e.astype(LD))
+        rhs = np.sum(r.astype(LD) * Pe)
+        mag = np.sum(np.abs(r.astype(LD)) * np.abs(Pe)) * 2 ** ncoarsened
+        assert abs(lhs - rhs) <= 4 * C_XFER * eps * mag, (l, float(lhs), float(rhs))
+        # P and R are exact on multilinear functions (fine index units: coarse node (K, J, I) sits at fine (zs K, 2J, 2I))
+        cidx = np.indices(cs).astype(np.float64)
+        for a in range(P.dim):
+            if not (P.semi[l] and a == 0):
+                cidx[a] *= 2
+        fcoarse = _ml(cidx, P.dim).astype(dt)
+        ffine = _ml(np.indices(fs).astype(np.float64), P.dim).astype(dt)
+        mag_f = P.prolong(np.abs(P.as_prec(fcoarse)), l)
+        check_points(ops.prolong_overwrite(fcoarse), P.as_prec(ffine), mag_f, eps, C_XFER, f"P multilinear l{l}")
+        R = ops.restrict_fw(ffine).astype(LD)
+        inner = ~npr.boundary_mask(cs)
+        check_points(R[inner], P.as_prec(fcoarse)[inner], P.restrict_fw(np.abs(P.as_prec(ffine)), l)[inner], eps, C_XFER,
+                     f"R multilinear l{l}")
+
+
+@pytest.mark.parametrize("case", ID_CASES, ids=[_id(c) for c in ID_CASES])
+def test_identities_of_the_operator_and_smoothers(case):
+    d = po.make_desc(**case)
+    ops, P = po.Ops(d), npr.Problem(**case)
+    eps, dt = eps_of(case["dtype"]), np_of(case["dtype"])
+    rng = np.random.default_rng(23)
+    ax = case["aniso"]
+    for l in range(case["levels"]):
+        shp = P.shape(l)
+        # the residual of u = x^2 + y^2 (+ z^2), b = 0 inside and u on the boundary, is 2 alpha sum(aniso) inside:
+        # pins h and h_z of every level
+        h0 = case["length"] / (case["n"] - 1)
+        hs = [h0 * 2 ** l] * P.dim
+        if P.dim == 3:
+            hs[0] = h0 * 2 ** max(l - case["semi_xy"], 0)
+        idx = np.indices(shp).astype(LD)
+        q = sum((idx[a] * LD(hs[a])) ** 2 for a in range(P.dim))
+        u = q.astype(dt)
+        b = np.where(npr.boundary_mask(shp), u, 0).astype(dt)
+        r, _ = ops.residual(l, u, b)
+        want = np.where(npr.boundary_mask(shp), LD(0), 2 * LD(case["alpha"]) * sum(LD(a) for a in ax[:P.dim]))
+        check_points(r, want, P.apply_A(u, l, absolute=True) + np.abs(P.as_prec(b)), eps, C_RESID,
+                     f"residual of a quadratic l{l}")
+        # Jacobi = u + omega D^-1 r at interior nodes
+        u, b = rng.standard_normal(shp).astype(dt), rng.standard_normal(shp).astype(dt)
+        r, _ = ops.residual(l, u, b)
+        I = (slice(1, -1),) * P.dim
+        got = ops.jacobi(l, u, b).astype(LD)[I]
+        want = P.as_prec(u)[I] + P.omega * r.astype(LD)[I] / P.coef(l)[1]
+        mag = (np.abs(P.as_prec(u)) + P.point_solve_mag(u, b, l))[I]
+        check_points(got, want, mag, eps, 2 * C_POINT, f"jacobi = u + w D^-1 r l{l}")
+        # after a red-black sweep the residual vanishes on colour 1 (and on every boundary node); after a zebra sweep on
+        # the interior rows of the lines of colour 1
+        for sm in (po.SMOOTH_RBGS, po.SMOOTH_ZEBRA_Y, po.SMOOTH_ZEBRA_X):
+            v = ops.smooth(l, sm, 1, u, b)
+            r, _ = ops.residual(l, v, b)
+            mag = np.abs(P.as_prec(b)) + P.apply_A(v, l, absolute=True)
+            if sm == po.SMOOTH_RBGS:
+                where, amp = (npr.parity(shp) == 1) | npr.boundary_mask(shp), 1.0
+            else:
+                la = line_axis(P, sm)
+                where = npr.parity(shp, [a for a in range(P.dim) if a != la]) == 1
+                amp = npr.line_amplification(P, l, la)
+            check_points(r[where], np.zeros(int(where.sum()), LD), mag[where], eps, C_LINE * amp,
+                         f"residual after smoother {sm} on its last colour l{l}")
+
+
+FIXED_POINT_CASES = [dict(c, cycle=cyc, smoother=sm, nu_pre=2, nu_post=2, restriction=po.RESTRICT_FULLW,
+                          coarse_mode=po.COARSE_FIXED, coarse_maxit=4, outer_pre_gs=0)
+                     for i, c in enumerate(ID_CASES[::3]) if not (c["dim"] == 3 and c["n"] > 65)
+                     for cyc, sm in [((po.CYCLE_V, po.CYCLE_SAWTOOTH)[i % 2], SMOOTHERS[i % 4])]]
+
+
+@pytest.mark.parametrize("case", FIXED_POINT_CASES, ids=[_cid(dict(c, ncycles=1)) for c in FIXED_POINT_CASES])
+def test_the_exact_solution_is_a_fixed_point_of_a_cycle(case):
+    """b = A u* built in long double: one cycle from u* leaves u* in place up to the rounding of b and of the residual"""
+    eps, dt = eps_of(case["dtype"]), np_of(case["dtype"])
+    P = npr.Problem(**case)
+    ustar = np.random.default_rng(3).standard_normal(P.shape(0)).astype(dt)
+    b = P.apply_A(ustar, 0).astype(dt)
+    s = po.Solver(po.make_desc(**case))
+    s.set_rhs(b); s.set_solution(ustar)
+    s.cycle()
+    scale = float(np.abs(P.as_prec(ustar)).max())
+    check_max(s.get_solution(), P.as_prec(ustar), cycle_bound(P, eps, case["coarse_maxit"], scale), "fixed point")
+
+
+# ======================================================================= the HIP operators (GPU)
+# Python statements of the dispatch gates (multigrid_prj_amd/csrc): which kernel a shape takes, so that every row below
+# names the side it exercises and the launch counts of mg_profile_get can confirm it.
+def _V(dtype):
+    return 2 if dtype == po.MG_F64 else 4
+
+
+def fast_path_ok(n, dtype):          # mg_jacobi_fast.hip: rows of >= 33, at most one column left over
+    return n >= 33 and n % _V(dtype) <= 1
+
+
+def jacobi2_ok(n, dtype):            # mg_jacobi_fast.hip: rows of exactly 64 ... 512 vectors + the odd column
+    return (n - 1) % _V(dtype) == 0 and (n - 1) // _V(dtype) in (64, 128, 192, 256, 384, 512)
+
+
+def pair_wide_ok(n, nz, dtype):      # mg_pair_wide.hip: rows of 128 / 256 lanes, ny >= 200, nz >= 8
+    return (n - 1) % _V(dtype) == 0 and (n - 1) // _V(dtype) in (128, 256) and n >= 200 and nz >= 8
+
+
+def rr_wide_ok(n, nzc, dtype):       # mg_rr_wide.hip: the same rows, coarse nz >= 4
+    return (n - 1) % _V(dtype) == 0 and (n - 1) // _V(dtype) in (128, 256) and n >= 200 and nzc >= 4
+
+
+def prolong_fast_ok(nc, nf, dtype):  # mg_transfer_fast.hip
+    return nc >= 17 and nf % _V(dtype) == 1
+
+
+def resid_restrict_fast_ok(nf, nc, dtype):  # mg_transfer_fast.hip: + at most 8 column blocks of the coarse row
+    return nc >= 17 and nf % _V(dtype) == 1 and (nc - 1 + 64 * (_V(dtype) // 2) - 1) // (64 * (_V(dtype) // 2)) <= 8
+
+
+def small_fused_ok(nf, nzf):         # mg_small_levels.hip: whole levels up to 129^3, standard coarsening
+    return nf ** 2 * nzf <= 129 ** 3
+
+
+# Single operators through mg_smooth (2 Jacobi sweeps = one fused pair where jacobi2_ok, 1 red-black sweep = the fused
+# sweep where rb_fused_ok == jacobi2_ok), mg_residual, mg_restrict, mg_prolong. `xfer`: also the transfers level 0 <-> 1.
+OP_ROWS = [
+    dict(id="f64-31", gate="fast_path_ok: no (rows < 33): generic kernels", n=31, dtype=po.MG_F64, omega=6 / 7, xfer=True),
+    dict(id="f64-33", gate="fast_path_ok: yes, jacobi2_ok: no (16 vectors)", n=33, dtype=po.MG_F64, omega=0.8, xfer=True),
+    dict(id="f64-129", gate="jacobi2_ok / rb_fused_ok: yes (64 vectors); prolong_fast_ok: yes", n=129, dtype=po.MG_F64,
+         omega=6 / 7, xfer=True),
+    dict(id="f64-131", gate="jacobi2_ok: no (65 vectors), fast_path_ok: yes; prolong_fast_ok: yes", n=131,
+         dtype=po.MG_F64, omega=1.0, xfer=True),
+    dict(id="f64-257", gate="pair_wide_ok: yes (128 lanes)", n=257, dtype=po.MG_F64, omega=6 / 7, xfer=True,
+         fallback="MG_PAIR_WIDE"),
+    dict(id="f64-385", gate="jacobi2_ok: yes (192 vectors), pair_wide_ok: no", n=385, dtype=po.MG_F64, omega=6 / 7,
+         xfer=False),
+    dict(id="f64-513", gate="pair_wide_ok: yes (256 lanes)", n=513, dtype=po.MG_F64, omega=6 / 7, xfer=False),
+    dict(id="f32-35", gate="fast_path_ok: no (35 % 4 == 3); prolong_fast_ok: no", n=35, dtype=po.MG_F32, omega=6 / 7,
+         xfer=True),
+    dict(id="f32-257", gate="jacobi2_ok: yes (64 vectors), pair_wide_ok: no", n=257, dtype=po.MG_F32, omega=0.8,
+         xfer=True),
+    dict(id="f32-513", gate="pair_wide_ok: yes (128 lanes)", n=513, dtype=po.MG_F32, omega=6 / 7, xfer=False),
+]
+
+# Two V(2,2) (or sawtooth) cycles from a random state and a three-cycle mg_solve: reach k_rrw, the prolongation-folding
+# pair, the small-level fused kernels, the fused-norm solve and the zebra kernels, which only the cycle dispatches.
+CYCLE_ROWS = [
+    dict(id="f64-129-jacobi", gate="level 0: jacobi2_ok -> prolongation folded into the post pair, resid_restrict_fast_ok; "
+         "level 1 (65^3): small_fused_ok (jacobi2_ok: no)", n=129, levels=4, dtype=po.MG_F64, smoother=po.SMOOTH_JACOBI,
+         omega=6 / 7, fallbacks=("MG_FUSED_PAIR", "MG_SMALL_FUSED")),
+    dict(id="f64-257-jacobi", gate="pair_wide_ok + rr_wide_ok; fused-norm mg_solve", n=257, levels=5, dtype=po.MG_F64,
+         smoother=po.SMOOTH_JACOBI, omega=0.8, fallbacks=("MG_RR_WIDE",)),
+    dict(id="f64-65-jacobi", gate="level 0: small_fused_ok (unprofiled second cycle)", n=65, levels=3, dtype=po.MG_F64,
+         smoother=po.SMOOTH_JACOBI, omega=6 / 7, outer_pre_gs=2),
+    dict(id="f64-65-rbgs", gate="rb_fused_ok: no, fast_path_ok: yes (colour kernels); resid_restrict_fast_ok", n=65,
+         levels=3, dtype=po.MG_F64, smoother=po.SMOOTH_RBGS, omega=1.0, outer_pre_gs=2),
+    dict(id="f64-129-rbgs", gate="rb_fused_ok: yes, folded prolongation", n=129, levels=4, dtype=po.MG_F64,
+         smoother=po.SMOOTH_RBGS, omega=1.0),
+    dict(id="f32-129-semi-aniso", gate="semi-coarsened transfers (resid_restrict_fast_ok, prolong_fast_ok on semi levels)",
+         n=129, levels=5, dtype=po.MG_F32, smoother=po.SMOOTH_JACOBI, omega=0.8, semi_xy=2, aniso=(1.0, 1.0, 0.05)),
+    dict(id="f64-65-semi-rbgs", gate="semi-coarsened, anisotropic, red-black", n=65, levels=4, dtype=po.MG_F64,
+         smoother=po.SMOOTH_RBGS, omega=1.0, semi_xy=1, aniso=(1.0, 0.5, 0.01)),
+    dict(id="f64-65-zebra-y", gate="zebra kernels (k_zebra_y), red-black coarsest solve", n=65, levels=4, dtype=po.MG_F64,
+         smoother=po.SMOOTH_ZEBRA_Y, omega=1.0, aniso=(1.0, 100.0, 1.0)),
+    dict(id="f32-129-zebra-x-semi", gate="zebra kernels (k_zebra_x) on semi-coarsened levels", n=129, levels=4,
+         dtype=po.MG_F32, smoother=po.SMOOTH_ZEBRA_X, omega=1.0, semi_xy=1, aniso=(100.0, 1.0, 0.05)),
+    dict(id="f32-35-jacobi", gate="fast_path_ok / prolong_fast_ok / resid_restrict_fast_ok: no", n=35, levels=2,
+         dtype=po.MG_F32, smoother=po.SMOOTH_JACOBI, omega=6 / 7),
+    dict(id="f64-65-sawtooth", gate="sawtooth cycle: injection to every level, prolong-overwrite", n=65, levels=3,
+         dtype=po.MG_F64, smoother=po.SMOOTH_JACOBI, omega=1.0, cycle=po.CYCLE_SAWTOOTH, nu_post=3),
+]
+
+
+def _gpu_problem(n, **kw):
+    prec = LD if n <= 129 else np.float64   # long double up to 129^3, float64 above
+    return npr.Problem(n=n, prec=prec, **kw)
+
+
+def run_op_row(row, env_off=()):
+    from multigrid_prj_amd import capi
+    n, dtype = row["n"], row["dtype"]
+    kw = dict(dim=3, n=n, levels=2, dtype=dtype, length=1.0, alpha=1.0, omega=row["omega"])
+    P = _gpu_problem(**kw)
+    eps, dt = eps_of(dtype), np_of(dtype)
+    rng = np.random.default_rng(n)
+    u, b = rng.standard_normal((n,) * 3).astype(dt), rng.standard_normal((n,) * 3).astype(dt)
+    fused = jacobi2_ok(n, dtype) and "MG_FUSED_PAIR" not in env_off
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.set_array(capi.ARR_U, 0, u); s.set_array(capi.ARR_RHS, 0, b)
+        s.profile_begin(); s.smooth(0, capi.SMOOTH_JACOBI, 2, capi.ARR_U, capi.ARR_RHS); s.profile_end()
+        assert s.profile_get(capi.PROF_SMOOTH)[1] == (1 if fused else 2), ("jacobi pair launches", row["gate"])
+        j1 = P.jacobi(u, b, 0)
+        j2 = P.jacobi(j1, b, 0)
+        bound = C_POINT * eps * (sweep_scale(P, 0, b, u) + sweep_scale(P, 0, b, j1))
+        check_max(s.get_array(capi.ARR_U, 0), j2, bound, "two Jacobi sweeps")
+        del j1, j2
+        s.set_array(capi.ARR_U, 0, u)
+        s.profile_begin(); s.smooth(0, capi.SMOOTH_RBGS, 1, capi.ARR_U, capi.ARR_RHS); s.profile_end()
+        assert s.profile_get(capi.PROF_SMOOTH)[1] == (1 if fused else 2), ("red-black launches", row["gate"])
+        ref = P.rbgs(u, b, 0)
+        check_max(s.get_array(capi.ARR_U, 0), ref, sweep_bound(P, 0, npr.SMOOTH_RBGS, u, ref, b, eps), "red-black sweep")
+        del ref
+        s.set_array(capi.ARR_U, 0, u)
+        s.residual(0, capi.ARR_U, capi.ARR_RHS, capi.ARR_TMP)
+        check_points(s.get_array(capi.ARR_TMP, 0), P.residual(u, b, 0),
+                     np.abs(P.as_prec(b)) + P.apply_A(u, 0, absolute=True), eps, C_RESID, "residual")
+        if row["xfer"]:
+            w = P.as_prec(u)
+            s.restrict(0, capi.RESTRICT_FULLW, capi.ARR_U, capi.ARR_RHS)
+            check_points(s.get_array(capi.ARR_RHS, 1), P.restrict_fw(u, 0), P.restrict_fw(np.abs(w), 0), eps, C_XFER, "fw")
+            s.restrict(0, capi.RESTRICT_INJECT, capi.ARR_U, capi.ARR_RHS)
+            assert np.array_equal(s.get_array(capi.ARR_RHS, 1).astype(LD), P.inject(u, 0)), "inject"
+            c = rng.standard_normal(P.shape(1)).astype(dt)
+            pc, pm = P.prolong(c, 0), P.prolong(np.abs(P.as_prec(c)), 0)
+            s.set_array(capi.ARR_E, 1, c)
+            s.prolong(1, False, capi.ARR_E, capi.ARR_E)
+            check_points(s.get_array(capi.ARR_E, 0), pc, pm, eps, C_XFER, "prolong")
+            s.set_array(capi.ARR_U, 0, u); s.set_array(capi.ARR_U, 1, c)
+            s.prolong(1, True, capi.ARR_U, capi.ARR_U)
+            check_points(s.get_array(capi.ARR_U, 0), w + pc, np.abs(w) + pm, eps, C_XFER, "prolong-add")
+
+
+def _cycle_kw(row):
+    return dict(dim=3, n=row["n"], levels=row["levels"], dtype=row["dtype"], length=1.0, alpha=1.0,
+                cycle=row.get("cycle", po.CYCLE_V), smoother=row["smoother"], omega=row["omega"], nu_pre=2,
+                nu_post=row.get("nu_post", 2), restriction=po.RESTRICT_FULLW if row.get("cycle", 1) == po.CYCLE_V
+                else po.RESTRICT_INJECT, coarse_mode=po.COARSE_FIXED, coarse_maxit=8,
+                outer_pre_gs=row.get("outer_pre_gs", 0), semi_xy=row.get("semi_xy", 0),
+                aniso=row.get("aniso", (1.0, 1.0, 1.0)))
+
+
+def expected_launches(row, env_off=()):
+    """finest-level launch kinds of one profiled cycle (mg_solver.cpp: vcycle_rec_t)"""
+    n, dt, sm = row["n"], row["dtype"], row["smoother"]
+    if row.get("cycle", po.CYCLE_V) != po.CYCLE_V:
+        return None
+    semi0 = row.get("semi_xy", 0) > 0
+    j2 = jacobi2_ok(n, dt) and "MG_FUSED_PAIR" not in env_off
+    fold = j2 and not semi0 and sm in (po.SMOOTH_JACOBI, po.SMOOTH_RBGS)
+    nc = (n - 1) // 2 + 1
+    rr = resid_restrict_fast_ok(n, nc, dt)
+    return dict(SMOOTH_PROLONG_pos=fold, PROLONG=0 if fold else 1, RESID_RESTRICT=1 if rr else 2)
+
+
+def run_cycle_row(row, env_off=()):
+    from multigrid_prj_amd import capi
+    kw = _cycle_kw(row)
+    P = _gpu_problem(**kw)
+    eps, dt = eps_of(row["dtype"]), np_of(row["dtype"])
+    rng = np.random.default_rng(row["n"] + 3)
+    b = rng.standard_normal(P.shape(0)).astype(dt)
+    u0 = (0.1 * rng.standard_normal(P.shape(0))).astype(dt)
+    exp = expected_launches(row, env_off)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.set_rhs(b); s.set_solution(u0)
+        u = P.as_prec(u0)
+        for k in range(2):
+            if k == 0:
+                s.profile_begin()
+            st = s.cycle()
+            if k == 0:
+                s.profile_end()
+                got = {kd: s.profile_get(getattr(capi, "PROF_" + kd))[1]
+                       for kd in ("SMOOTH", "SMOOTH_PROLONG", "RESID_RESTRICT", "PROLONG")}
+                if exp is not None:
+                    assert (got["SMOOTH_PROLONG"] > 0) == exp["SMOOTH_PROLONG_pos"], (got, row["gate"])
+                    assert got["PROLONG"] == exp["PROLONG"] and got["RESID_RESTRICT"] == exp["RESID_RESTRICT"], \
+                        (got, exp, row["gate"])
+            assert st.coarse_iters == kw["coarse_maxit"]
+            u = P.cycle(u, b, kw["coarse_maxit"])
+            scale = float(np.abs(u).max()) + sweep_scale(P, 0, b, u0)
+            check_max(s.get_solution(), u, cycle_bound(P, eps, kw["coarse_maxit"], scale), f"cycle {k}")
+        # a short solve (the fused-norm path where the pair takes the norm): history and iterate
+        s.set_solution(np.zeros(P.shape(0), dt))
+        hist, stats = s.solve(1e-30, 3)
+        uref, href = P.solve(np.zeros(P.shape(0)), b, [kw["coarse_maxit"]] * 3)
+        assert len(hist) == len(href) == 4
+        scale = float(np.abs(uref).max()) + float(np.abs(b).max()) / float(abs(P.coef(0)[1]))
+        dmax = 3 * cycle_bound(P, eps, kw["coarse_maxit"], scale)
+        check_max(s.get_solution(), uref, dmax, "solve")
+        # |r| moves by at most the residual's rounding plus |A| times the iterate's error
+        nb = math.sqrt(npr.fsum_sq(b))
+        mag = math.sqrt(npr.fsum_sq(np.abs(P.as_prec(b)) + P.apply_A(uref, 0, absolute=True)))
+        atol = (C_RESID * eps * mag + 2 * float(abs(P.coef(0)[1])) * dmax * math.sqrt(b.size)) / nb
+        np.testing.assert_allclose(hist, href, rtol=1e-9, atol=atol)
+
+
+_CHILD = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+from tests import test_independent_reference as t
+kind, rid, off = sys.argv[2], sys.argv[3], tuple(sys.argv[4].split(","))
+rows = t.OP_ROWS if kind == "op" else t.CYCLE_ROWS
+row = [r for r in rows if r["id"] == rid][0]
+(t.run_op_row if kind == "op" else t.run_cycle_row)(row, off)
+print("child ok")
+"""
+
+
+def _child(kind, row, var):
+    """the other side of a process-wide gate: a fresh child process with the switch off (read once per process)"""
+    env = dict(os.environ, **{var: "0"})
+    p = subprocess.run([sys.executable, "-c", _CHILD, ROOT, kind, row["id"], var], env=env, cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "child ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("row", OP_ROWS, ids=[r["id"] for r in OP_ROWS])
+def test_hip_single_operators_against_npref(row):
+    run_op_row(row)
+    if row.get("fallback"):
+        _child("op", row, row["fallback"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("row", CYCLE_ROWS, ids=[r["id"] for r in CYCLE_ROWS])
+def test_hip_cycles_and_solve_against_npref(row):
+    run_cycle_row(row)
+    for var in row.get("fallbacks", ()):
+        _child("cycle", row, var)
+
+
+GPU_ID_CASES = [dict(dim=3, n=129, levels=3, dtype=po.MG_F64, semi_xy=1, aniso=(1.0, 30.0, 0.05), omega=6 / 7),
+                dict(dim=3, n=257, levels=2, dtype=po.MG_F32, semi_xy=0, aniso=(1.0, 1.0, 1.0), omega=0.8),
+                dict(dim=3, n=65, levels=3, dtype=po.MG_F32, semi_xy=2, aniso=(100.0, 1.0, 0.01), omega=1.0),
+                dict(dim=2, n=129, levels=4, dtype=po.MG_F64, semi_xy=0, aniso=(1.0, 0.05, 1.0), omega=0.8)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", GPU_ID_CASES, ids=[_id(c) for c in GPU_ID_CASES])
+def test_hip_identities(case):
+    """the oracle-free identities on the HIP operators: the residual of a quadratic on every level, the last colour of
+    red-black and zebra sweeps, Jacobi = u + omega D^-1 r, and the adjointness of R and P"""
+    from multigrid_prj_amd import capi
+    P = npr.Problem(length=1.0, alpha=1.0, **case)
+    eps, dt = eps_of(case["dtype"]), np_of(case["dtype"])
+    rng = np.random.default_rng(29)
+    ax = case["aniso"]
+    zsm = capi.SMOOTH_ZEBRA_Y if ax[1] >= ax[0] else capi.SMOOTH_ZEBRA_X
+    with capi.Solver(capi.make_desc(length=1.0, alpha=1.0, smoother=zsm, **case)) as s:
+        for l in range(case["levels"]):
+            shp = P.shape(l)
+            h0 = 1.0 / (case["n"] - 1)
+            hs = [h0 * 2 ** l] * P.dim
+            if P.dim == 3:
+                hs[0] = h0 * 2 ** max(l - case["semi_xy"], 0)
+            idx = np.indices(shp).astype(LD)
+            u = sum((idx[a] * LD(hs[a])) ** 2 for a in range(P.dim)).astype(dt)
+            b = np.where(npr.boundary_mask(shp), u, 0).astype(dt)
+            s.set_array(capi.ARR_E, l, u); s.set_array(capi.ARR_RHS, l, b)
+            s.residual(l, capi.ARR_E, capi.ARR_RHS, capi.ARR_TMP)
+            want = np.where(npr.boundary_mask(shp), LD(0), 2 * sum(LD(a) for a in ax[:P.dim]))
+            check_points(s.get_array(capi.ARR_TMP, l), want, P.apply_A(u, l, absolute=True) + np.abs(P.as_prec(b)),
+                         eps, C_RESID, f"residual of a quadratic l{l}")
+            u, b = rng.standard_normal(shp).astype(dt), rng.standard_normal(shp).astype(dt)
+            s.set_array(capi.ARR_E, l, u); s.set_array(capi.ARR_RHS, l, b)
+            s.residual(l, capi.ARR_E, capi.ARR_RHS, capi.ARR_TMP)
+            r = s.get_array(capi.ARR_TMP, l).astype(LD)
+            s.smooth(l, capi.SMOOTH_JACOBI, 1, capi.ARR_E, capi.ARR_RHS)
+            I = (slice(1, -1),) * P.dim
+            want = P.as_prec(u)[I] + P.omega * r[I] / P.coef(l)[1]
+            check_points(s.get_array(capi.ARR_E, l).astype(LD)[I], want,
+                         (np.abs(P.as_prec(u)) + P.point_solve_mag(u, b, l))[I], eps, 2 * C_POINT, f"jacobi l{l}")
+            for sm in (capi.SMOOTH_RBGS, zsm):
+                s.set_array(capi.ARR_E, l, u)
+                s.smooth(l, sm, 1, capi.ARR_E, capi.ARR_RHS)
+                v = s.get_array(capi.ARR_E, l)
+                s.residual(l, capi.ARR_E, capi.ARR_RHS, capi.ARR_TMP)
+                r = s.get_array(capi.ARR_TMP, l)
+                mag = np.abs(P.as_prec(b)) + P.apply_A(v, l, absolute=True)
+                if sm == capi.SMOOTH_RBGS:
+                    where, amp = (npr.parity(shp) == 1) | npr.boundary_mask(shp), 1.0
+                else:
+                    la = line_axis(P, sm)
+                    where = npr.parity(shp, [a for a in range(P.dim) if a != la]) == 1
+                    amp = npr.line_amplification(P, l, la)
+                check_points(r[where], np.zeros(int(where.sum()), LD), mag[where], eps, C_LINE * amp,
+                             f"last colour of smoother {sm} l{l}")
+            if l + 1 < case["levels"]:
+                nco = P.dim - (1 if P.semi[l] else 0)
+                r, e = _interior_random(rng, shp, dt), _interior_random(rng, P.shape(l + 1), dt)
+                s.set_array(capi.ARR_E, l, r)
+                s.restrict(l, capi.RESTRICT_FULLW, capi.ARR_E, capi.ARR_RHS)
+                Rr = s.get_array(capi.ARR_RHS, l + 1).astype(LD)
+                s.set_array(capi.ARR_E, l + 1, e)
+                s.prolong(l + 1, False, capi.ARR_E, capi.ARR_E)
+                Pe = s.get_array(capi.ARR_E, l).astype(LD)
+                lhs = (2 ** nco) * np.sum(Rr * e.astype(LD))
+                rhs = np.sum(r.astype(LD) * Pe)
+                mag = np.sum(np.abs(r.astype(LD)) * np.abs(Pe)) * 2 ** nco
+                assert abs(lhs - rhs) <= 4 * C_XFER * eps * mag, (l, float(lhs), float(rhs))
