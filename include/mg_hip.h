@@ -128,6 +128,43 @@ int mg_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int
 int mg_solve_lockstep(mg_handle h, double tol, int maxit, const int *coarse_counts, int n_counts,
                       double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
 
+/* Multigrid-preconditioned conjugate gradients (extension; the reference's Krylov option `-smt 2`, BiCGSTAB, is
+ * never applied by its program). Solves A x = b on level 0, b = the RHS array, x0 = the U array (mg_solve's
+ * contract), with flexible CG -- Notay's FCG(1), the Polak-Ribiere beta:
+ *   x0 = b on the Dirichlet nodes;  r0 = b - A x0;  z0 = M r0;  p0 = z0;  gamma0 = z0.r0
+ *   for k = 0, 1, ...:  q = A p;  alpha = gamma / p.q;  x += alpha p;  r -= alpha q;  stop if ||r|| / ||b|| <= tol
+ *                       z = M r;  gamma' = z.r;  beta = -alpha (z.q) / gamma;  gamma = gamma';  p = z + beta p
+ * M r is one outer iteration of mg_solve started from zero on A z = r: desc.outer_pre_gs lexicographic Gauss-Seidel
+ * sweeps, then one mg_cycle of the descriptor's kind. The flexible beta makes every cycle the library builds an
+ * admissible preconditioner (red-black sweeps in the same colour order, the sawtooth, the residual-tested coarse solve
+ * are not symmetric linear operators); with a symmetric M it equals standard PCG in exact arithmetic.
+ * hist[k] = sqrt(r_k.r_k / b.b) with the recursively updated r (hist[0]: after the boundary copy, mg_solve's hist[0]
+ * when U already holds b's boundary values); the loop stops when k > 0 and hist[k] <= tol, after maxit iterations, or
+ * on a breakdown (p.q <= 0, gamma <= 0 or a scalar that is not finite: status 2, x = the last iterate, never NaN).
+ * Dot products accumulate in double for both dtypes, in a fixed order: two runs give the same bits. b.b == 0 or
+ * r0 == 0: nothing to do (status 0, iters 0).
+ * On return U holds x and RHS holds b unchanged; E, TMP, RES and the coarse levels are unspecified (as after mg_solve).
+ * Memory: the first call allocates five more level-0 arrays (z, r, two directions, A p) kept until mg_destroy and
+ * counted by mg_device_bytes from then on -- 5 x 1.1 GB at 513^3 fp64, 5 x 4.4 GB at 1025^3 fp32.
+ * Refused with MG_ERR_BAD_ARG (U untouched): distributed handles (nranks > 1, dry runs included) and a handle with
+ * a stage callback installed. mg_profile_* brackets keep timing the cycles inside. */
+typedef struct mg_krylov_stats {
+    int32_t iters;        /* CG iterations done (= preconditioner applications after the first) */
+    int32_t status;       /* 0 converged, 1 hit maxit, 2 breakdown                               */
+    double  relres;       /* last recursive ||r|| / ||b||                                         */
+    double  relres_true;  /* ||b - A x|| / ||b|| recomputed at exit                               */
+} mg_krylov_stats;
+int mg_pcg_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
+
+/* Kernel-level check of mg_pcg_solve's three vector kernels on level-0 arrays (arrs[] name mg_array slots; the
+ * element-wise formulas are in multigrid_prj_amd/csrc/mg_krylov.hip):
+ *   MG_PCG_K_UPDATE     arrs = {x, p, r, q}:   x += scalar p,  r -= scalar q;       dots[0] = r.r (after)
+ *   MG_PCG_K_DOTS       arrs = {z, r, q}:      dots[0] = z.r,  dots[1] = z.q
+ *   MG_PCG_K_DIRECTION  arrs = {z, p, p', q}:  p' = z + scalar p (0 on Dirichlet nodes), q = A p';  dots[0] = p'.q
+ * Single-GPU handles only; the arrays named must be distinct. */
+enum mg_pcg_kernel_kind { MG_PCG_K_UPDATE = 0, MG_PCG_K_DOTS = 1, MG_PCG_K_DIRECTION = 2 };
+int mg_pcg_kernel(mg_handle h, int kernel, double scalar, const int *arrs, double dots[2]);
+
 /* Debug stage dumps of the sawtooth cycle -- the reference's CREATE_GIF twin
  * (multigrid.hpp:160-316) writes `sol + err` sampled on the level being worked on after every
  * stage: before and after the coarse solve, after each interpolation, after each level's

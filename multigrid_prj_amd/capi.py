@@ -19,6 +19,8 @@ COARSE_TOL, COARSE_FIXED = 0, 1
 ARR_U, ARR_E, ARR_RHS, ARR_TMP, ARR_RES = 0, 1, 2, 3, 4
 MG_COMM_ID_BYTES = 128
 PROF_SMOOTH, PROF_SMOOTH_PROLONG, PROF_RESID_RESTRICT, PROF_PROLONG = 0, 1, 2, 3
+PCG_K_UPDATE, PCG_K_DOTS, PCG_K_DIRECTION = 0, 1, 2
+PCG_CONVERGED, PCG_MAXIT, PCG_BREAKDOWN = 0, 1, 2
 
 
 class MgError(RuntimeError):
@@ -48,6 +50,15 @@ class MgCycleStats(C.Structure):
     _fields_ = [
         ("coarse_iters", C.c_int32), ("coarse_flag", C.c_int32),
         ("coarse_relres", C.c_double), ("fine_sumsq_r", C.c_double),
+    ]
+
+
+class MgKrylovStats(C.Structure):
+    """include/mg_hip.h::mg_krylov_stats (mg_pcg_solve)"""
+
+    _fields_ = [
+        ("iters", C.c_int32), ("status", C.c_int32),
+        ("relres", C.c_double), ("relres_true", C.c_double),
     ]
 
 
@@ -88,6 +99,7 @@ EXPORTS = [
     "mg_level_coefficients", "mg_set_rhs", "mg_set_solution", "mg_get_solution", "mg_set_array",
     "mg_get_array", "mg_zero_array", "mg_smooth", "mg_residual", "mg_sumsq", "mg_restrict",
     "mg_prolong", "mg_correct", "mg_coarse_solve", "mg_coarse_solve_ex", "mg_cycle", "mg_cycle_async", "mg_solve", "mg_solve_lockstep",
+    "mg_pcg_solve", "mg_pcg_kernel",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
 ]
@@ -132,6 +144,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_cycle_async.argtypes = [vp, i]
     L.mg_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
     L.mg_solve_lockstep.argtypes = [vp, C.c_double, i, C.POINTER(i), i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
+    L.mg_pcg_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgKrylovStats)]
+    L.mg_pcg_kernel.argtypes = [vp, i, C.c_double, C.POINTER(i), dp]
     L.mg_set_stage_callback.argtypes = [vp, STAGE_FN, vp]
     L.mg_sync.argtypes = [vp]
     L.mg_timer_start.argtypes = [vp]
@@ -301,6 +315,19 @@ class Solver:
         cnt = (C.c_int * max(len(coarse_counts), 1))(*[int(c) for c in coarse_counts])
         _check(self.lib.mg_solve_lockstep(self.h, tol, maxit, cnt, len(coarse_counts), hist, maxit + 1, C.byref(nh), stats))
         return np.array(hist[:nh.value]), list(stats[:nh.value - 1])
+
+    def pcg_solve(self, tol=1e-11, maxit=1000):
+        """mg_pcg_solve: multigrid-preconditioned flexible CG on level 0 (b = RHS, x0 = U; U holds x on return)
+        -> (hist, MgKrylovStats); hist[k] = ||r_k|| / ||b||"""
+        hist = (C.c_double * (maxit + 1))(); nh = C.c_int(0); st = MgKrylovStats()
+        _check(self.lib.mg_pcg_solve(self.h, tol, maxit, hist, maxit + 1, C.byref(nh), C.byref(st)))
+        return np.array(hist[:min(nh.value, maxit + 1)]), st
+
+    def pcg_kernel(self, kernel, scalar, arrs):
+        """mg_pcg_kernel: one vector kernel of pcg_solve on level-0 arrays (PCG_K_*) -> (dot0, dot1)"""
+        a = (C.c_int * 4)(*(list(arrs) + [0] * (4 - len(arrs)))); dots = (C.c_double * 2)()
+        _check(self.lib.mg_pcg_kernel(self.h, kernel, scalar, a, dots))
+        return dots[0], dots[1]
 
     def set_stage_callback(self, fn):
         """fn(stage, level, array) after every stage of the sawtooth cycle (CREATE_GIF dumps); None removes it"""

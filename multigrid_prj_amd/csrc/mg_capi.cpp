@@ -164,6 +164,19 @@ int mg_solve_lockstep(mg_handle h, double tol, int maxit, const int *coarse_coun
         if (coarse_counts[i] < 0) return bad("mg_solve_lockstep: negative sweep count");
     return guarded([&] { return h->impl->solve(tol, maxit, hist, hist_cap, n_hist, per_cycle, coarse_counts, n_counts); });
 }
+int mg_pcg_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    MG_H(h);
+    if (maxit < 0) return bad("mg_pcg_solve: negative maxit");
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_pcg_solve: bad history buffer");
+    return guarded([&] { return h->impl->pcg_solve(tol, maxit, hist, hist_cap, n_hist, st); });
+}
+int mg_pcg_kernel(mg_handle h, int kernel, double scalar, const int *arrs, double dots[2])
+{
+    MG_H(h);
+    if (!arrs || !dots) return bad("mg_pcg_kernel: null argument");
+    return guarded([&] { return h->impl->pcg_kernel(kernel, scalar, arrs, dots); });
+}
 int mg_set_stage_callback(mg_handle h, mg_stage_fn fn, void *user)
 {
     MG_H(h);

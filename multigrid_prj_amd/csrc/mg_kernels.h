@@ -145,5 +145,41 @@ void launch_coarse_solve(hipStream_t s, const Geom &g, const Coef<T> &c, T omega
                          T *x, T *tmp, const T *rhs, int maxit, double tol, int fixed,
                          CoarseOut *d_out, bool x_is_zero = false);
 
+// ---- flexible conjugate gradients on level 0 (mg_krylov.hip, driven by Solver::pcg_t) ----
+// Scalars of the iteration, resident on the device: the tails write them, the vector kernels read them. bad != 0 (a
+// breakdown: gamma <= 0, p.q <= 0 or a scalar that is not finite) makes every later launch return without writing.
+struct CgScalars {
+    double rr;      // r.r after the last update
+    double gamma;   // z.r
+    double delta;   // z.q
+    double beta;
+    double alpha;
+    double pq;      // p.q
+    int bad;
+    int pad_;
+};
+enum CgTail {
+    CG_TAIL_RR = 0,     // partials of r.r                -> rr
+    CG_TAIL_FIRST = 1,  // partials of z.r, z.q (k = 0)   -> gamma, beta = 0
+    CG_TAIL_BETA = 2,   // partials of z.r, z.q           -> beta = -alpha delta / gamma_old, gamma
+    CG_TAIL_ALPHA = 3   // partials of p.q                -> alpha = gamma / p.q
+};
+int cg_partials_capacity();   // doubles the partials buffer of the three kernels needs
+// x += a p, r -= a q (a = alpha); partials of r.r; returns the number of partials
+template <typename T>
+int launch_cg_update(hipStream_t s, const Geom &g, T *x, const T *p, T *r, const T *q, const CgScalars *sc, double *partials);
+// partials of z.r in [0, nb), of z.q in [nb, 2 nb); returns nb
+template <typename T>
+int launch_cg_dots(hipStream_t s, const Geom &g, const T *z, const T *r, const T *q, const CgScalars *sc, double *partials);
+// pn = z + b p (b = beta; 0 on Dirichlet nodes), q = A pn, partials of pn.q; pn must not alias p
+template <typename T>
+int launch_cg_direction_apply(hipStream_t s, const Geom &g, const Coef<T> &c, const T *z, const T *p, T *pn, T *q,
+                              const CgScalars *sc, double *partials);
+// x = rhs on the Dirichlet nodes, the rest of x untouched
+template <typename T>
+void launch_cg_boundary_copy(hipStream_t s, const Geom &g, T *x, const T *rhs);
+// fixed-order sum of the partials of one launch above + the scalar update `mode` (CgTail), one workgroup
+void launch_cg_tail(hipStream_t s, int mode, const double *partials, int nb, CgScalars *sc);
+
 }  // namespace mg
 #endif

@@ -168,6 +168,11 @@ Solver::~Solver()
     for (auto &L : lv_) if (L.zebra) (void)hipFree(L.zebra);
     for (auto &f : full_) if (f) (void)hipFree(f);
     for (auto &b : stage_base_) if (b) (void)hipFree(b);
+    for (auto &b : kry_) if (b) (void)hipFree(b);
+    if (d_cg_) (void)hipFree(d_cg_);
+    if (d_cg_part_) (void)hipFree(d_cg_part_);
+    if (d_cg_dot_) (void)hipFree(d_cg_dot_);
+    if (h_cg_) (void)hipHostFree(h_cg_);
     delete comm_;
     if (ev_ready_) (void)hipEventDestroy(ev_ready_);
     if (ev_halo_) (void)hipEventDestroy(ev_halo_);
@@ -1773,6 +1778,186 @@ int Solver::timer_stop(double *ms)
     MG_HIP(hipEventElapsedTime(&f, ev0_, ev1_));
     if (ms) *ms = (double)f;
     return MG_OK;
+}
+
+// ---------------------------------------------------------------- multigrid-preconditioned flexible CG (mg_pcg_solve)
+int Solver::krylov_scalars_alloc()
+{
+    if (d_cg_) return MG_OK;
+    const size_t npart = (size_t)cg_partials_capacity();
+    MG_HIP(hipMalloc((void **)&d_cg_, sizeof(CgScalars)));
+    MG_HIP(hipMalloc((void **)&d_cg_part_, sizeof(double) * npart));
+    MG_HIP(hipMalloc((void **)&d_cg_dot_, sizeof(double) * 2));
+    MG_HIP(hipHostMalloc((void **)&h_cg_, sizeof(CgScalars)));
+    bytes_ += sizeof(CgScalars) + sizeof(double) * (npart + 2);
+    return MG_OK;
+}
+
+int Solver::krylov_alloc()
+{
+    MG_TRY(krylov_scalars_alloc());
+    if (kry_[0]) return MG_OK;
+    const size_t nbytes = lv_[0].alloc_elems * esize();
+    for (auto &b : kry_) {
+        MG_HIP(hipMalloc(&b, nbytes));
+        MG_HIP(hipMemsetAsync(b, 0, nbytes, stream_));   // ghost planes and padding columns stay zero from here on
+        bytes_ += nbytes;
+    }
+    return MG_OK;
+}
+
+// z = M r: the cycle code works on level 0's U / RHS slots, so z and r take them for the duration (pointer swap, no copy).
+// The cycle may itself leave its result in the array that was TMP (out-of-place sweeps swap U / TMP): whatever U points
+// at afterwards is z, and TMP keeps the other buffer.
+template <typename T>
+int Solver::precondition_t()
+{
+    Level &L0 = lv_[0];
+    void *const x_base = L0.base[MG_ARR_U], *const b_base = L0.base[MG_ARR_RHS];
+    MG_HIP(hipMemsetAsync(kry_[KZ], 0, L0.alloc_elems * esize(), stream_));
+    L0.base[MG_ARR_U] = kry_[KZ];
+    L0.base[MG_ARR_RHS] = kry_[KR];
+    int rc = MG_OK;
+    if (d_.outer_pre_gs > 0) rc = smooth_t<T>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS);   // `u * GS * GS`
+    if (rc == MG_OK) rc = cycle_enqueue_t<T>();                                                              // `* MGx`
+    kry_[KZ] = L0.base[MG_ARR_U];
+    L0.base[MG_ARR_U] = x_base;
+    L0.base[MG_ARR_RHS] = b_base;
+    return rc;
+}
+
+template <typename T>
+int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    const Coef<T> c = coef_of<T>(L0);
+    auto kp = [&](int k) { return reinterpret_cast<T *>(kry_[k]) + L0.gh * g.plane; };
+    T *const x = ptr<T>(MG_ARR_U, 0);
+    const T *const b = ptr<T>(MG_ARR_RHS, 0);
+    mg_krylov_stats out{0, 0, 0.0, 0.0};
+    int nh = 0;
+    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
+
+    double nb = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    // Dirichlet rows are identity rows carrying the boundary data: x takes b's values there, after which r, z, p and q
+    // vanish on the boundary and the iteration lives on the interior, where A is symmetric positive definite
+    launch_cg_boundary_copy<T>(stream_, g, x, b);
+    MG_HIP(hipGetLastError());
+    launch_residual<T>(stream_, g, c, x, b, kp(KR), d_partials_, d_scal_);   // r0 = b - A x0, r0.r0
+    MG_HIP(hipGetLastError());
+    MG_HIP(hipMemcpyAsync(h_scal_, d_scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    const double rr0 = h_scal_[0];
+    record(std::sqrt(rr0 / nb));
+
+    if (nb == 0.0 || rr0 == 0.0) {
+        out.status = 0;   // nothing to do: b == 0 (x0 = 0 is the answer once its boundary is b's) or x0 solves the system
+    } else if (maxit == 0) {
+        out.status = 1;
+    } else {
+        MG_HIP(hipMemsetAsync(d_cg_, 0, sizeof(CgScalars), stream_));
+        int pc = KP0, pn = KP1;   // p ping-pongs: another workgroup may still read p_k at a neighbour while p_{k+1} is written
+        MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));   // p_{-1} = 0: p_0 = z_0 + 0 p_{-1} = z_0
+        auto direction = [&](int mode) -> int {   // z = M r, gamma, beta, p_{k+1} = z + beta p_k, q = A p_{k+1}, alpha
+            MG_TRY(precondition_t<T>());
+            int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
+            np = launch_cg_direction_apply<T>(stream_, g, c, kp(KZ), kp(pc), kp(pn), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, CG_TAIL_ALPHA, d_cg_part_, np, d_cg_);
+            MG_HIP(hipGetLastError());
+            std::swap(pc, pn);
+            return MG_OK;
+        };
+        MG_TRY(direction(CG_TAIL_FIRST));
+        for (int k = 0; k < maxit; k++) {
+            const int np = launch_cg_update<T>(stream_, g, x, kp(pc), kp(KR), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, CG_TAIL_RR, d_cg_part_, np, d_cg_);
+            MG_HIP(hipGetLastError());
+            MG_HIP(hipMemcpyAsync(h_cg_, d_cg_, sizeof(CgScalars), hipMemcpyDeviceToHost, stream_));
+            MG_HIP(hipStreamSynchronize(stream_));   // the one host synchronisation per iteration: the stopping test
+            if (h_cg_->bad) { out.status = 2; break; }   // the update was skipped: x is the last iterate
+            out.iters = k + 1;
+            const double rel = std::sqrt(h_cg_->rr / nb);
+            record(rel);
+            if (rel <= tol) { out.status = 0; break; }
+            if (k + 1 == maxit) { out.status = 1; break; }
+            MG_TRY(direction(CG_TAIL_BETA));
+        }
+    }
+    double nr = 0;
+    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // the true residual of the returned x
+    out.relres_true = std::sqrt(nr / nb);
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
+int Solver::pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    if (nranks_ > 1) {
+        set_last_error("mg_pcg_solve: distributed handles are not supported (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (stage_fn_) {
+        set_last_error("mg_pcg_solve: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    lock_iters_ = -1;
+    MG_TRY(krylov_alloc());
+    return d_.dtype == MG_F64 ? pcg_t<double>(tol, maxit, hist, hist_cap, n_hist, st)
+                              : pcg_t<float>(tol, maxit, hist, hist_cap, n_hist, st);
+}
+
+template <typename T>
+int Solver::pcg_kernel_t(int kernel, double scalar, const int *a, double *dots)
+{
+    const Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    *h_cg_ = CgScalars{};
+    h_cg_->alpha = h_cg_->beta = scalar;
+    MG_HIP(hipMemcpyAsync(d_cg_, h_cg_, sizeof(CgScalars), hipMemcpyHostToDevice, stream_));
+    int np = 0;
+    if (kernel == MG_PCG_K_UPDATE) {
+        np = launch_cg_update<T>(stream_, g, ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0), ptr<T>(a[3], 0), d_cg_, d_cg_part_);
+        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
+    } else if (kernel == MG_PCG_K_DOTS) {
+        np = launch_cg_dots<T>(stream_, g, ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0), d_cg_, d_cg_part_);
+        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
+        launch_reduce_final(stream_, d_cg_part_ + np, np, d_cg_dot_ + 1);
+    } else {
+        np = launch_cg_direction_apply<T>(stream_, g, coef_of<T>(L0), ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0),
+                                          ptr<T>(a[3], 0), d_cg_, d_cg_part_);
+        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
+    }
+    MG_HIP(hipGetLastError());
+    double h[2] = {0.0, 0.0};
+    MG_HIP(hipMemcpyAsync(h_scal_ + 4, d_cg_dot_, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    h[0] = h_scal_[4];
+    if (kernel == MG_PCG_K_DOTS) h[1] = h_scal_[5];
+    dots[0] = h[0]; dots[1] = h[1];
+    return MG_OK;
+}
+
+int Solver::pcg_kernel(int kernel, double scalar, const int *arrs, double *dots)
+{
+    if (nranks_ > 1) { set_last_error("mg_pcg_kernel: single-GPU handles only"); return MG_ERR_BAD_ARG; }
+    if (kernel < MG_PCG_K_UPDATE || kernel > MG_PCG_K_DIRECTION) { set_last_error("mg_pcg_kernel: unknown kernel"); return MG_ERR_BAD_ARG; }
+    const int na = kernel == MG_PCG_K_DOTS ? 3 : 4;
+    for (int i = 0; i < na; i++) {
+        if (!check_arr(arrs[i], 0, "mg_pcg_kernel")) return MG_ERR_BAD_ARG;
+        for (int j = 0; j < i; j++)
+            if (arrs[i] == arrs[j]) { set_last_error("mg_pcg_kernel: the arrays must be distinct"); return MG_ERR_BAD_ARG; }
+    }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    MG_TRY(krylov_scalars_alloc());
+    return d_.dtype == MG_F64 ? pcg_kernel_t<double>(kernel, scalar, arrs, dots)
+                              : pcg_kernel_t<float>(kernel, scalar, arrs, dots);
 }
 
 }  // namespace mg

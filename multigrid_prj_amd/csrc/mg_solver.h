@@ -11,6 +11,7 @@
 #include "../../include/mg_hip.h"
 #include "mg_comm.h"
 #include "mg_geom.h"
+#include "mg_kernels.h"
 
 namespace mg {
 
@@ -77,6 +78,10 @@ public:
     // lock_counts[i] sweeps (mg_solve_lockstep)
     int solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist,
               mg_cycle_stats *per_cycle, const int *lock_counts = nullptr, int n_lock = 0);
+    // multigrid-preconditioned flexible CG on level 0 (mg_pcg_solve); the Krylov buffers are allocated on the first call
+    int pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
+    // one of the three vector kernels of pcg_solve on level-0 arrays (mg_pcg_kernel)
+    int pcg_kernel(int kernel, double scalar, const int *arrs, double *dots);
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -140,6 +145,11 @@ private:
     template <typename T> int coarse_t(int level, int ax, int ar, bool x_zero = false);
     template <typename T> int coarse_ex_t(int level, int ax, int ar, int smoother, int maxit, double tol, int fixed, bool x_zero = false);
     template <typename T> int cycle_enqueue_t();
+    template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
+    template <typename T> int precondition_t();   // z = M r: one mg_solve outer iteration from zero on (z, r)
+    template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
+    int krylov_scalars_alloc();
+    int krylov_alloc();
     template <typename T> int vcycle_rec_t(int l, bool u_zero = false);
     int cycle_enqueue();
     bool check_arr(int which, int level, const char *fn) const;
@@ -177,6 +187,13 @@ private:
     bool want_pair_norm_ = false, pair_norm_done_ = false;
     int fine_pre_done_ = 0;
     template <typename T> bool pair_norm_ok() const;
+    // Krylov state of pcg_solve (allocated on first use, kept until the handle goes): level-0-shaped buffers z, r, p, p', q
+    // -- z and r take the U / RHS slots of level 0 while the preconditioning cycle runs; device scalars + partial sums
+    enum { KZ = 0, KR = 1, KP0 = 2, KP1 = 3, KQ = 4, NKRY = 5 };
+    void *kry_[NKRY] = {};
+    CgScalars *d_cg_ = nullptr, *h_cg_ = nullptr;
+    double *d_cg_part_ = nullptr;
+    double *d_cg_dot_ = nullptr;    // [2]: sums of the kernel check (mg_pcg_kernel)
     Geom gfull_{};
     void *full_[3] = {nullptr, nullptr, nullptr};
     std::vector<SlabPlan> planT_;
