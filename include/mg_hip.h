@@ -165,6 +165,37 @@ int mg_pcg_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap,
 enum mg_pcg_kernel_kind { MG_PCG_K_UPDATE = 0, MG_PCG_K_DOTS = 1, MG_PCG_K_DIRECTION = 2 };
 int mg_pcg_kernel(mg_handle h, int kernel, double scalar, const int *arrs, double dots[2]);
 
+/* Full multigrid (nested iteration) -- extension, no reference counterpart. Builds the first finest-grid iterate
+ * from the coarsest grid up instead of starting level 0 from whatever U holds:
+ *     RHS(l+1) = R RHS(l) down the hierarchy          (desc.restriction; the coarse boundary is injected, so the
+ *                                                      Dirichlet data travels with the right-hand side)
+ *     U(L-1) = 0 inside, RHS(L-1) on Dirichlet nodes;  coarse solve of A U = RHS   (desc.coarse_* as in a cycle)
+ *     for l = L-2 .. 0:   U(l) = Pi U(l+1) inside, RHS(l) on Dirichlet nodes      (one launch)
+ *                         cycles_per_level V-cycles of the descriptor started on level l
+ * Pi is the FMG interpolation: along every coarsened axis f[2m] = c[m], f[2m+1] = (-c[m-1] + 9 c[m] + 9 c[m+1] -
+ * c[m+2]) / 16, next to a boundary (3 c[0] + 6 c[1] - c[2]) / 8 and its mirror; kept axes (z of a semi-coarsened
+ * transition) are copied. Its O(h^4) error stays below the discretisation error, which mg_prolong's linear
+ * interpolation (right for corrections) does not. On return U(0) holds the FMG iterate -- algebraic error at the level
+ * of the discretisation error after about 8/7 of the work of the cycles run on level 0 -- and RHS(0) is unchanged; the
+ * incoming U(0) is ignored; every other array is unspecified, as after mg_solve. It is the natural first guess of
+ * mg_solve / mg_pcg_solve when a tighter tolerance is wanted. No host synchronisation inside the pass except the one
+ * residual at its end. MG_CYCLE_V only (the levels of a sawtooth cycle hold errors, not solutions), every smoother,
+ * both restrictions, aniso, semi_xy, 2-D and 3-D, both dtypes; levels == 1 is just the coarse solve. MG_ERR_BAD_ARG
+ * with U untouched: MG_CYCLE_SAWTOOTH, cycles_per_level < 1, distributed handles (dry runs included), a stage callback
+ * installed. mg_profile_* brackets keep timing the level-0 cycles inside (cycles on inner levels are not counted). */
+typedef struct mg_fmg_stats {
+    int32_t levels;            /* levels visited (= desc.levels)                                  */
+    int32_t cycles_per_level;
+    int32_t coarse_iters;      /* of the first, true coarse solve (mg_cycle_stats semantics)      */
+    int32_t coarse_flag;
+    double  relres;            /* ||b - A u|| / ||b|| of the result, one residual at the end      */
+} mg_fmg_stats;
+int mg_fmg(mg_handle h, int cycles_per_level, mg_fmg_stats *st);
+/* The interpolation alone, for tests and for callers that drive their own nested iteration:
+ * arr_dst(coarse_level - 1) = Pi arr_src(coarse_level); fine Dirichlet nodes take arr_bnd(coarse_level - 1) bit for bit
+ * (arr_bnd < 0: they are interpolated like every other node). Single-GPU handles only; arr_dst != arr_bnd. */
+int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int arr_bnd);
+
 /* Debug stage dumps of the sawtooth cycle -- the reference's CREATE_GIF twin
  * (multigrid.hpp:160-316) writes `sol + err` sampled on the level being worked on after every
  * stage: before and after the coarse solve, after each interpolation, after each level's

@@ -53,6 +53,15 @@ class MgCycleStats(C.Structure):
     ]
 
 
+class MgFmgStats(C.Structure):
+    """include/mg_hip.h::mg_fmg_stats (mg_fmg)"""
+
+    _fields_ = [
+        ("levels", C.c_int32), ("cycles_per_level", C.c_int32), ("coarse_iters", C.c_int32), ("coarse_flag", C.c_int32),
+        ("relres", C.c_double),
+    ]
+
+
 class MgKrylovStats(C.Structure):
     """include/mg_hip.h::mg_krylov_stats (mg_pcg_solve)"""
 
@@ -99,7 +108,7 @@ EXPORTS = [
     "mg_level_coefficients", "mg_set_rhs", "mg_set_solution", "mg_get_solution", "mg_set_array",
     "mg_get_array", "mg_zero_array", "mg_smooth", "mg_residual", "mg_sumsq", "mg_restrict",
     "mg_prolong", "mg_correct", "mg_coarse_solve", "mg_coarse_solve_ex", "mg_cycle", "mg_cycle_async", "mg_solve", "mg_solve_lockstep",
-    "mg_pcg_solve", "mg_pcg_kernel",
+    "mg_pcg_solve", "mg_pcg_kernel", "mg_fmg", "mg_fmg_prolong",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
 ]
@@ -146,6 +155,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_solve_lockstep.argtypes = [vp, C.c_double, i, C.POINTER(i), i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
     L.mg_pcg_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgKrylovStats)]
     L.mg_pcg_kernel.argtypes = [vp, i, C.c_double, C.POINTER(i), dp]
+    L.mg_fmg.argtypes = [vp, i, C.POINTER(MgFmgStats)]
+    L.mg_fmg_prolong.argtypes = [vp, i, i, i, i]
     L.mg_set_stage_callback.argtypes = [vp, STAGE_FN, vp]
     L.mg_sync.argtypes = [vp]
     L.mg_timer_start.argtypes = [vp]
@@ -328,6 +339,19 @@ class Solver:
         a = (C.c_int * 4)(*(list(arrs) + [0] * (4 - len(arrs)))); dots = (C.c_double * 2)()
         _check(self.lib.mg_pcg_kernel(self.h, kernel, scalar, a, dots))
         return dots[0], dots[1]
+
+    def fmg(self, cycles_per_level=1):
+        """mg_fmg: full multigrid (nested iteration) from the coarsest grid up, cubic interpolation of the solution and
+        cycles_per_level V-cycles per level; U(0) holds the iterate on return (its incoming content is ignored)
+        -> MgFmgStats"""
+        st = MgFmgStats()
+        _check(self.lib.mg_fmg(self.h, cycles_per_level, C.byref(st)))
+        return st
+
+    def fmg_prolong(self, coarse_level, arr_src, arr_dst, arr_bnd=-1):
+        """mg_fmg_prolong: arr_dst(coarse_level - 1) = Pi arr_src(coarse_level), the FMG (cubic) interpolation; fine
+        Dirichlet nodes from arr_bnd (< 0: interpolated too)"""
+        _check(self.lib.mg_fmg_prolong(self.h, coarse_level, arr_src, arr_dst, arr_bnd))
 
     def set_stage_callback(self, fn):
         """fn(stage, level, array) after every stage of the sawtooth cycle (CREATE_GIF dumps); None removes it"""

@@ -177,6 +177,16 @@ int mg_pcg_kernel(mg_handle h, int kernel, double scalar, const int *arrs, doubl
     if (!arrs || !dots) return bad("mg_pcg_kernel: null argument");
     return guarded([&] { return h->impl->pcg_kernel(kernel, scalar, arrs, dots); });
 }
+int mg_fmg(mg_handle h, int cycles_per_level, mg_fmg_stats *st)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->fmg(cycles_per_level, st); });
+}
+int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int arr_bnd)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->fmg_prolong(coarse_level, arr_src, arr_dst, arr_bnd); });
+}
 int mg_set_stage_callback(mg_handle h, mg_stage_fn fn, void *user)
 {
     MG_H(h);

@@ -181,5 +181,12 @@ void launch_cg_boundary_copy(hipStream_t s, const Geom &g, T *x, const T *rhs);
 // fixed-order sum of the partials of one launch above + the scalar update `mode` (CgTail), one workgroup
 void launch_cg_tail(hipStream_t s, int mode, const double *partials, int nb, CgScalars *sc);
 
+// ---- full-multigrid interpolation (mg_fmg.hip, driven by Solver::fmg_t) ----
+// fine = Pi coarse: cubic along every coarsened axis (one-sided quadratic next to a boundary), kept axes copied;
+// bnd != nullptr: fine Dirichlet nodes = bnd[node] instead, in the same launch. Whole (undistributed) levels only.
+template <typename T> bool fmg_prolong_fast_ok(const Geom &gc, const Geom &gf);   // the streaming 3-D form runs (else the gather kernel)
+template <typename T>
+void launch_fmg_prolong(hipStream_t s, const Geom &gc, const Geom &gf, const T *coarse, T *fine, const T *bnd);
+
 }  // namespace mg
 #endif

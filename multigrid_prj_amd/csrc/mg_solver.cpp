@@ -1960,4 +1960,85 @@ int Solver::pcg_kernel(int kernel, double scalar, const int *arrs, double *dots)
                               : pcg_kernel_t<float>(kernel, scalar, arrs, dots);
 }
 
+// ---------------------------------------------------------------- full multigrid (nested iteration), mg_fmg
+// f_{l+1} = R f_l down the hierarchy (the level operators are unscaled and the restrictions inject on the coarse boundary,
+// so this carries the right-hand side and the Dirichlet data), the coarsest-grid solve, then coarse to fine: U(l) = Pi U(l+1)
+// (mg_fmg.hip; Dirichlet nodes from RHS(l)) and cycles_per_level V-cycles started on level l. A cycle started on level l
+// only overwrites U and RHS of the levels below it, which the pass has finished with: no storage of its own.
+template <typename T>
+int Solver::fmg_t(int cycles_per_level, mg_fmg_stats *st)
+{
+    const int L = d_.levels;
+    for (int l = 0; l + 1 < L; l++) MG_TRY(restrict_t<T>(l, d_.restriction, MG_ARR_RHS, MG_ARR_RHS));
+    MG_TRY(zero_array(MG_ARR_U, L - 1));
+    launch_cg_boundary_copy<T>(stream_, lv_[L - 1].g, ptr<T>(MG_ARR_U, L - 1), ptr<T>(MG_ARR_RHS, L - 1));
+    MG_HIP(hipGetLastError());
+    MG_TRY(coarse_level_t<T>(L - 1, MG_ARR_U, MG_ARR_RHS, false));
+    MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));   // of this first, true coarse solve
+    for (int l = L - 2; l >= 0; l--) {
+        launch_fmg_prolong<T>(stream_, lv_[l + 1].g, lv_[l].g, ptr<T>(MG_ARR_U, l + 1), ptr<T>(MG_ARR_U, l), ptr<T>(MG_ARR_RHS, l));
+        MG_HIP(hipGetLastError());
+        for (int k = 0; k < cycles_per_level; k++) MG_TRY(vcycle_rec_t<T>(l));
+    }
+    double nb = 0, nr = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // synchronises: h_coarse_ is valid from here
+    if (st) {
+        st->levels = L;
+        st->cycles_per_level = cycles_per_level;
+        st->coarse_iters = h_coarse_->iters;
+        st->coarse_flag = h_coarse_->flag;
+        st->relres = std::sqrt(nr / nb);
+    }
+    return MG_OK;
+}
+
+int Solver::fmg(int cycles_per_level, mg_fmg_stats *st)
+{
+    if (nranks_ > 1) {
+        set_last_error("mg_fmg: distributed handles are not supported (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (stage_fn_) {
+        set_last_error("mg_fmg: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
+        return MG_ERR_BAD_ARG;
+    }
+    if (d_.cycle != MG_CYCLE_V) {
+        set_last_error("mg_fmg: the descriptor's cycle must be MG_CYCLE_V (the levels of a sawtooth cycle hold errors, not solutions)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (cycles_per_level < 1) {
+        set_last_error("mg_fmg: cycles_per_level must be at least 1");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    lock_iters_ = -1;
+    fine_pre_done_ = 0;
+    return d_.dtype == MG_F64 ? fmg_t<double>(cycles_per_level, st) : fmg_t<float>(cycles_per_level, st);
+}
+
+int Solver::fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)
+{
+    if (nranks_ > 1) { set_last_error("mg_fmg_prolong: single-GPU handles only"); return MG_ERR_BAD_ARG; }
+    if (coarse_level < 1 || coarse_level >= d_.levels || !check_arr(arr_src, coarse_level, "mg_fmg_prolong") ||
+        !check_arr(arr_dst, coarse_level - 1, "mg_fmg_prolong") || (arr_bnd >= 0 && !check_arr(arr_bnd, coarse_level - 1, "mg_fmg_prolong"))) {
+        set_last_error("mg_fmg_prolong: bad level / array");
+        return MG_ERR_BAD_ARG;
+    }
+    if (arr_bnd == arr_dst) { set_last_error("mg_fmg_prolong: arr_bnd must differ from arr_dst"); return MG_ERR_BAD_ARG; }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    const int fl = coarse_level - 1;
+    if (arr_dst == MG_ARR_RHS) lv_[fl].rhs_halo_ok = false;
+    if (d_.dtype == MG_F64)
+        launch_fmg_prolong<double>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<double>(arr_src, coarse_level), ptr<double>(arr_dst, fl),
+                                   arr_bnd >= 0 ? ptr<double>(arr_bnd, fl) : (double *)nullptr);
+    else
+        launch_fmg_prolong<float>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<float>(arr_src, coarse_level), ptr<float>(arr_dst, fl),
+                                  arr_bnd >= 0 ? ptr<float>(arr_bnd, fl) : (float *)nullptr);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
 }  // namespace mg

@@ -82,6 +82,11 @@ public:
     int pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     // one of the three vector kernels of pcg_solve on level-0 arrays (mg_pcg_kernel)
     int pcg_kernel(int kernel, double scalar, const int *arrs, double *dots);
+    // full multigrid (nested iteration): coarsest-grid solve, then per level cubic interpolation of the solution +
+    // cycles_per_level V-cycles started on that level (mg_fmg)
+    int fmg(int cycles_per_level, mg_fmg_stats *st);
+    // arr_dst(l) = Pi arr_src(l + 1), Dirichlet nodes from arr_bnd(l) (< 0: interpolated too) (mg_fmg_prolong)
+    int fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd);
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -148,6 +153,7 @@ private:
     template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     template <typename T> int precondition_t();   // z = M r: one mg_solve outer iteration from zero on (z, r)
     template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
+    template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
     int krylov_scalars_alloc();
     int krylov_alloc();
     template <typename T> int vcycle_rec_t(int l, bool u_zero = false);
