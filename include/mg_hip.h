@@ -196,6 +196,67 @@ int mg_fmg(mg_handle h, int cycles_per_level, mg_fmg_stats *st);
  * (arr_bnd < 0: they are interpolated like every other node). Single-GPU handles only; arr_dst != arr_bnd. */
 int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int arr_bnd);
 
+/* Mixed-precision defect correction (extension, no reference counterpart): an fp64 answer paid for with fp32 cycles.
+ * On a handle created with desc.dtype == MG_F32 the solution u and the right-hand side b of level 0 are kept in fp64
+ * next to the fp32 hierarchy; the residual r = b - A u is evaluated in fp64, the fp32 hierarchy solves A e = r
+ * approximately with inner_cycles of its cycles, and u += e. `maxit` counts corrections:
+ *   u = b on the Dirichlet nodes (fp64, bit for bit);  bb = sum b^2 (all nodes, as mg_solve)
+ *   r = b - A u in fp64 (written as 0 on Dirichlet nodes whatever u holds there);  rr = sum r^2;  hist[0] = sqrt(rr / bb)
+ *   RHS32(0) = (float)(s_0 * r),  s_0 = scale(bb)
+ *   for k = 0, 1, ... :   stop if (k > 0 and hist[k] <= tol) or k == maxit
+ *       U32(0) = 0;  inner_cycles times: desc.outer_pre_gs lexicographic GS sweeps + one mg_cycle   (mg_solve's outer
+ *                                                                                    iteration, as in mg_pcg_solve's M)
+ *       ONE launch:  u += (double)U32 / s_k  (interior; Dirichlet nodes untouched)
+ *                    r  = b - A u  with the corrected u;  rr_new = sum r^2
+ *                    RHS32(0) = (float)(s_{k+1} * r),  s_{k+1} = scale(rr)   (rr of the PREVIOUS residual: known on
+ *                                                                              the host before the launch)
+ *       hist[k+1] = sqrt(rr_new / bb)
+ *   scale(v) = 2^-e with frexp(sqrt(v)) = (m, e); 1.0 when v is 0 or not finite
+ * The scale is a power of two, so multiplying and dividing by it is exact: it changes no digit, it only keeps the fp32
+ * right-hand side near 1 whatever the size of b and however far the residual has fallen. The history of b * 2^p is
+ * bit-identical to that of b, and u is the scaled u bit for bit.
+ * Residual arithmetic: fp64 without contraction, in the row order of mg_residual:
+ *   r = b - (((((((0 + cz u[k-1]) + cy u[j-1]) + cx u[i-1]) + cd u) + cx u[i+1]) + cy u[j+1]) + cz u[k+1])
+ * with mg_level_coefficients(h, 0) (cz terms absent in 2-D); (float) rounds to nearest even; the sums of squares are
+ * accumulated in double in a fixed order: two runs give the same bits. A residual that is exactly zero (b == 0 with
+ * u == 0 included) gives hist[0] = 0, status 0, no correction.
+ * Every cycle the descriptor can describe is admissible (sawtooth or V, every smoother, both restrictions, aniso,
+ * semi_xy, 2-D and 3-D, both coarse modes). On return u64 holds the iterate and b64 is unchanged; every fp32 array of
+ * the handle is unspecified, as after mg_solve. status == 2: the loop stops at the first residual norm that is not
+ * finite (it is the last hist entry) and does NOT take that correction -- the launch writes the corrected u out of place,
+ * so u64 stays the last iterate with a finite norm, never NaN.
+ * One host synchronisation per correction (the stopping test), none inside the inner cycles. mg_profile_* brackets keep
+ * timing the fp32 level-0 launches inside.
+ * Memory: the first mg_mixed_set_* allocates three fp64 level-0 arrays (b64 and two copies of u64, written out of place
+ * and swapped: 3 x 8 bytes per level-0 node, 3 x 1.1 GB at 513^3), kept until mg_destroy and counted by mg_device_bytes
+ * from then on. Host arrays are dense arrays of doubles in the usual layout, whatever desc.dtype says.
+ * MG_ERR_BAD_ARG with u64 untouched: a handle that was not created with MG_F32, inner_cycles < 1, maxit < 0,
+ * mg_mixed_solve before both arrays were set (mg_mixed_get_solution: before the solution was), distributed handles (dry
+ * runs included), a stage callback installed, NULL handle. */
+int mg_mixed_set_rhs(mg_handle h, const double *host_b);
+int mg_mixed_set_solution(mg_handle h, const double *host_u);
+int mg_mixed_get_solution(mg_handle h, double *host_u);
+
+typedef struct mg_mixed_stats {
+    int32_t outer;        /* corrections applied                                        */
+    int32_t cycles;       /* fp32 cycles run = inner_cycles per correction started      */
+    int32_t status;       /* 0 converged, 1 hit maxit, 2 residual norm not finite       */
+    int32_t reserved;
+    double  relres;       /* last hist entry: the TRUE fp64 ||b - A u|| / ||b||         */
+} mg_mixed_stats;
+int mg_mixed_solve(mg_handle h, double tol, int maxit, int inner_cycles,
+                   double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st);
+
+/* Kernel-level check of the two level-0 kernels of mg_mixed_solve (multigrid_prj_amd/csrc/mg_mixed.hip) on the handle's
+ * u64 / b64; arr_e32 / arr_r32 name fp32 level-0 arrays of the handle (mg_array slots):
+ *   MG_MIXED_K_RESIDUAL          arr_r32 = (float)(scale_out * (b64 - A u64)), 0 on Dirichlet nodes; arr_e32 is ignored
+ *   MG_MIXED_K_CORRECT_RESIDUAL  u64 += (double)arr_e32 / scale_in on interior nodes, then the same residual of the
+ *                                corrected u64; arr_e32 != arr_r32
+ * *sumsq_r = sum r^2 (unscaled). Any finite non-zero scale_in is honoured (a power of two is divided by exactly). */
+enum mg_mixed_kernel_kind { MG_MIXED_K_RESIDUAL = 0, MG_MIXED_K_CORRECT_RESIDUAL = 1 };
+int mg_mixed_kernel(mg_handle h, int kernel, double scale_in, double scale_out,
+                    int arr_e32, int arr_r32, double *sumsq_r);
+
 /* Debug stage dumps of the sawtooth cycle -- the reference's CREATE_GIF twin
  * (multigrid.hpp:160-316) writes `sol + err` sampled on the level being worked on after every
  * stage: before and after the coarse solve, after each interpolation, after each level's

@@ -21,6 +21,8 @@ MG_COMM_ID_BYTES = 128
 PROF_SMOOTH, PROF_SMOOTH_PROLONG, PROF_RESID_RESTRICT, PROF_PROLONG = 0, 1, 2, 3
 PCG_K_UPDATE, PCG_K_DOTS, PCG_K_DIRECTION = 0, 1, 2
 PCG_CONVERGED, PCG_MAXIT, PCG_BREAKDOWN = 0, 1, 2
+MIXED_K_RESIDUAL, MIXED_K_CORRECT_RESIDUAL = 0, 1
+MIXED_CONVERGED, MIXED_MAXIT, MIXED_NOT_FINITE = 0, 1, 2
 
 
 class MgError(RuntimeError):
@@ -71,6 +73,15 @@ class MgKrylovStats(C.Structure):
     ]
 
 
+class MgMixedStats(C.Structure):
+    """include/mg_hip.h::mg_mixed_stats (mg_mixed_solve)"""
+
+    _fields_ = [
+        ("outer", C.c_int32), ("cycles", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
+        ("relres", C.c_double),
+    ]
+
+
 def make_desc(dim=2, n=17, levels=2, dtype=MG_F64, length=10.0, alpha=1.0,
               cycle=CYCLE_SAWTOOTH, smoother=SMOOTH_JACOBI, omega=1.0, nu_pre=0, nu_post=5,
               restriction=RESTRICT_INJECT, coarse_mode=COARSE_TOL, coarse_maxit=2000,
@@ -109,6 +120,7 @@ EXPORTS = [
     "mg_get_array", "mg_zero_array", "mg_smooth", "mg_residual", "mg_sumsq", "mg_restrict",
     "mg_prolong", "mg_correct", "mg_coarse_solve", "mg_coarse_solve_ex", "mg_cycle", "mg_cycle_async", "mg_solve", "mg_solve_lockstep",
     "mg_pcg_solve", "mg_pcg_kernel", "mg_fmg", "mg_fmg_prolong",
+    "mg_mixed_set_rhs", "mg_mixed_set_solution", "mg_mixed_get_solution", "mg_mixed_solve", "mg_mixed_kernel",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
 ]
@@ -157,6 +169,11 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_pcg_kernel.argtypes = [vp, i, C.c_double, C.POINTER(i), dp]
     L.mg_fmg.argtypes = [vp, i, C.POINTER(MgFmgStats)]
     L.mg_fmg_prolong.argtypes = [vp, i, i, i, i]
+    L.mg_mixed_set_rhs.argtypes = [vp, vp]
+    L.mg_mixed_set_solution.argtypes = [vp, vp]
+    L.mg_mixed_get_solution.argtypes = [vp, vp]
+    L.mg_mixed_solve.argtypes = [vp, C.c_double, i, i, dp, i, C.POINTER(i), C.POINTER(MgMixedStats)]
+    L.mg_mixed_kernel.argtypes = [vp, i, C.c_double, C.c_double, i, i, dp]
     L.mg_set_stage_callback.argtypes = [vp, STAGE_FN, vp]
     L.mg_sync.argtypes = [vp]
     L.mg_timer_start.argtypes = [vp]
@@ -352,6 +369,36 @@ class Solver:
         """mg_fmg_prolong: arr_dst(coarse_level - 1) = Pi arr_src(coarse_level), the FMG (cubic) interpolation; fine
         Dirichlet nodes from arr_bnd (< 0: interpolated too)"""
         _check(self.lib.mg_fmg_prolong(self.h, coarse_level, arr_src, arr_dst, arr_bnd))
+
+    # -- mixed-precision defect correction: fp64 u / b beside an MG_F32 hierarchy (float64 arrays whatever the handle's dtype)
+    def _host64(self, a):
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != self.level_shape(0):
+            raise ValueError(f"expected shape {self.level_shape(0)}, got {a.shape}")
+        return a
+
+    def mixed_set_rhs(self, b):
+        b = self._host64(b); _check(self.lib.mg_mixed_set_rhs(self.h, b.ctypes.data_as(C.c_void_p)))
+
+    def mixed_set_solution(self, u):
+        u = self._host64(u); _check(self.lib.mg_mixed_set_solution(self.h, u.ctypes.data_as(C.c_void_p)))
+
+    def mixed_get_solution(self):
+        u = np.empty(self.level_shape(0), np.float64)
+        _check(self.lib.mg_mixed_get_solution(self.h, u.ctypes.data_as(C.c_void_p))); return u
+
+    def mixed_solve(self, tol=1e-11, maxit=100, inner_cycles=4):
+        """mg_mixed_solve: fp64 defect correction over the fp32 cycles of this (MG_F32) handle, `maxit` corrections of
+        `inner_cycles` cycles at most -> (hist, MgMixedStats); hist[k] = the true fp64 ||b - A u_k|| / ||b||"""
+        cap = max(maxit, 0) + 1
+        hist = (C.c_double * cap)(); nh = C.c_int(0); st = MgMixedStats()
+        _check(self.lib.mg_mixed_solve(self.h, tol, maxit, inner_cycles, hist, cap, C.byref(nh), C.byref(st)))
+        return np.array(hist[:min(nh.value, cap)]), st
+
+    def mixed_kernel(self, kernel, scale_in, scale_out, arr_e32, arr_r32) -> float:
+        """mg_mixed_kernel: one of the two fp64-in / fp32-out kernels of mixed_solve (MIXED_K_*) -> sum r^2"""
+        s = C.c_double(0)
+        _check(self.lib.mg_mixed_kernel(self.h, kernel, scale_in, scale_out, arr_e32, arr_r32, C.byref(s))); return s.value
 
     def set_stage_callback(self, fn):
         """fn(stage, level, array) after every stage of the sawtooth cycle (CREATE_GIF dumps); None removes it"""

@@ -187,6 +187,35 @@ int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int 
     MG_H(h);
     return guarded([&] { return h->impl->fmg_prolong(coarse_level, arr_src, arr_dst, arr_bnd); });
 }
+int mg_mixed_set_rhs(mg_handle h, const double *host_b)
+{
+    MG_H(h);
+    if (!host_b) return bad("mg_mixed_set_rhs: null argument");
+    return guarded([&] { return h->impl->mixed_set(true, host_b); });
+}
+int mg_mixed_set_solution(mg_handle h, const double *host_u)
+{
+    MG_H(h);
+    if (!host_u) return bad("mg_mixed_set_solution: null argument");
+    return guarded([&] { return h->impl->mixed_set(false, host_u); });
+}
+int mg_mixed_get_solution(mg_handle h, double *host_u)
+{
+    MG_H(h);
+    if (!host_u) return bad("mg_mixed_get_solution: null argument");
+    return guarded([&] { return h->impl->mixed_get_solution(host_u); });
+}
+int mg_mixed_solve(mg_handle h, double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st)
+{
+    MG_H(h);
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_mixed_solve: bad history buffer");
+    return guarded([&] { return h->impl->mixed_solve(tol, maxit, inner_cycles, hist, hist_cap, n_hist, st); });
+}
+int mg_mixed_kernel(mg_handle h, int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->mixed_kernel(kernel, scale_in, scale_out, arr_e32, arr_r32, sumsq_r); });
+}
 int mg_set_stage_callback(mg_handle h, mg_stage_fn fn, void *user)
 {
     MG_H(h);

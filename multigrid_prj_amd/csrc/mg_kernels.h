@@ -188,5 +188,19 @@ template <typename T> bool fmg_prolong_fast_ok(const Geom &gc, const Geom &gf); 
 template <typename T>
 void launch_fmg_prolong(hipStream_t s, const Geom &gc, const Geom &gf, const T *coarse, T *fine, const T *bnd);
 
+// ---- mixed-precision defect correction on level 0 (mg_mixed.hip, driven by Solver::mixed_solve) ----
+// g64 / g32: the fp64 and the fp32 geometry of level 0 (same extents, different pitches); coef = {cx, cy, cz, cd} in fp64.
+// Each launch leaves one partial sum per workgroup in `partials` and returns how many (at most mixed_partials_capacity()).
+int mixed_partials_capacity();
+// r32 = (float)(scale_out * (b - A u)), 0 on Dirichlet nodes; partials of (b - A u)^2
+int launch_mixed_residual(hipStream_t s, const Geom &g64, const Geom &g32, const double coef[4], const double *u, const double *b,
+                          float *r32, double scale_out, double *partials);
+// u_out = u + (double)e32 / scale_in inside, u on Dirichlet nodes; then the same residual of u_out. u_out must not alias u.
+int launch_mixed_correct_residual(hipStream_t s, const Geom &g64, const Geom &g32, const double coef[4], const double *u,
+                                  const float *e32, const double *b, double *u_out, float *r32, double scale_in, double scale_out,
+                                  double *partials);
+// partials of v^2 over all nodes
+int launch_mixed_sumsq(hipStream_t s, const Geom &g64, const double *v, double *partials);
+
 }  // namespace mg
 #endif

@@ -169,6 +169,9 @@ Solver::~Solver()
     for (auto &f : full_) if (f) (void)hipFree(f);
     for (auto &b : stage_base_) if (b) (void)hipFree(b);
     for (auto &b : kry_) if (b) (void)hipFree(b);
+    for (auto &b : mx_) if (b) (void)hipFree(b);
+    if (d_mx_part_) (void)hipFree(d_mx_part_);
+    if (d_mx_sum_) (void)hipFree(d_mx_sum_);
     if (d_cg_) (void)hipFree(d_cg_);
     if (d_cg_part_) (void)hipFree(d_cg_part_);
     if (d_cg_dot_) (void)hipFree(d_cg_dot_);
@@ -392,10 +395,18 @@ int stage_threads()
 int Solver::stage_rows(int which, int level, void *host, bool to_device)
 {
     pair_on_comm_level_ = -1;
-    MG_HIP(hipSetDevice(device_));
     const Level &L = lv_[level];
-    const size_t es = esize(), row = (size_t)L.g.nx * es, prow = (size_t)L.g.pitch * es;
-    const size_t pbytes = (size_t)L.g.plane * es;
+    if (to_device && which == MG_ARR_RHS) lv_[level].rhs_halo_ok = false;
+    char *dev = reinterpret_cast<char *>(L.base[which]) + (size_t)L.gh * (size_t)L.g.plane * esize();      // local plane 0
+    return stage_copy(dev, L.g, esize(), host, to_device);
+}
+
+// dev: local plane 0 of an array of geometry g with elements of es bytes
+int Solver::stage_copy(char *dev, const Geom &g, size_t es, void *host, bool to_device)
+{
+    MG_HIP(hipSetDevice(device_));
+    const size_t row = (size_t)g.nx * es, prow = (size_t)g.pitch * es;
+    const size_t pbytes = (size_t)g.plane * es;
     const size_t want = std::max<size_t>((size_t)64 << 20, 2 * pbytes);   // two halves, each at least one plane
     if (!h_stage_ || h_stage_bytes_ < want) {
         if (h_stage_) { (void)hipHostFree(h_stage_); h_stage_ = nullptr; }
@@ -404,15 +415,13 @@ int Solver::stage_rows(int which, int level, void *host, bool to_device)
     }
     const size_t half = h_stage_bytes_ / 2;
     const int per = (int)std::max<size_t>(1, half / pbytes);  // planes per chunk
-    char *dev = reinterpret_cast<char *>(L.base[which]) + (size_t)L.gh * pbytes;      // local plane 0
-    if (to_device && which == MG_ARR_RHS) lv_[level].rhs_halo_ok = false;
     char *hp = reinterpret_cast<char *>(host);
     // (threads only where there is something to share: a 257^2 array is 0.5 MB, a thread costs ~30 us to start)
-    const int ny = L.g.ny, nthr = (pbytes * (size_t)std::min(per, L.g.nz) >= ((size_t)8 << 20)) ? stage_threads() : 1;
-    const int nchunks = (L.g.nz + per - 1) / per;
+    const int ny = g.ny, nthr = (pbytes * (size_t)std::min(per, g.nz) >= ((size_t)8 << 20)) ? stage_threads() : 1;
+    const int nchunks = (g.nz + per - 1) / per;
     auto half_ptr = [&](int k) { return reinterpret_cast<char *>(h_stage_) + (size_t)(k & 1) * half; };
     auto pack = [&](int k) {        // host rows of chunk k -> its staging half, padding columns zeroed
-        const int z0 = k * per, nzc = std::min(per, L.g.nz - z0);
+        const int z0 = k * per, nzc = std::min(per, g.nz - z0);
         char *st = half_ptr(k);
         parallel_rows((size_t)nzc * ny, nthr, [&](size_t lo, size_t hi) {
             for (size_t r = lo; r < hi; r++) {
@@ -423,14 +432,14 @@ int Solver::stage_rows(int which, int level, void *host, bool to_device)
         });
     };
     auto unpack = [&](int k) {
-        const int z0 = k * per, nzc = std::min(per, L.g.nz - z0);
+        const int z0 = k * per, nzc = std::min(per, g.nz - z0);
         const char *st = half_ptr(k);
         parallel_rows((size_t)nzc * ny, nthr, [&](size_t lo, size_t hi) {
             for (size_t r = lo; r < hi; r++) std::memcpy(hp + ((size_t)z0 * ny + r) * row, st + r * prow, row);
         });
     };
     auto dma = [&](int k) -> int {
-        const int z0 = k * per, nzc = std::min(per, L.g.nz - z0);
+        const int z0 = k * per, nzc = std::min(per, g.nz - z0);
         if (to_device) MG_HIP(hipMemcpyAsync(dev + (size_t)z0 * pbytes, half_ptr(k), (size_t)nzc * pbytes, hipMemcpyHostToDevice, stream_));
         else MG_HIP(hipMemcpyAsync(half_ptr(k), dev + (size_t)z0 * pbytes, (size_t)nzc * pbytes, hipMemcpyDeviceToHost, stream_));
         MG_HIP(hipEventRecord(ev_stage_[k & 1], stream_));
@@ -2038,6 +2047,185 @@ int Solver::fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)
         launch_fmg_prolong<float>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<float>(arr_src, coarse_level), ptr<float>(arr_dst, fl),
                                   arr_bnd >= 0 ? ptr<float>(arr_bnd, fl) : (float *)nullptr);
     MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------- mixed-precision defect correction (mg_mixed_solve)
+// u and b of level 0 in fp64 beside the handle's fp32 hierarchy: r = b - A u in fp64, A e = r solved approximately by
+// inner_cycles of the fp32 cycles, u += e. The fp32 right-hand side is the residual times a power of two that keeps it
+// near 1 (exact both ways); the kernels are in mg_mixed.hip.
+int Solver::mixed_check(const char *fn) const
+{
+    if (d_.dtype != MG_F32) {
+        set_last_error(std::string(fn) + ": the handle has to be created with MG_F32 (the cycles of the mixed-precision solver run in fp32; "
+                                         "this handle is MG_F64)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (nranks_ > 1) {
+        set_last_error(std::string(fn) + ": distributed handles are not supported (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::mixed_alloc()
+{
+    if (mx_[0]) return MG_OK;
+    const Level &L0 = lv_[0];
+    g64_ = L0.g;
+    g64_.pitch = ((L0.g.nx + 15) / 16) * 16;   // rows of doubles padded to 128 B
+    g64_.plane = (long long)g64_.ny * g64_.pitch;
+    mx_alloc_elems_ = (size_t)(g64_.nz + 2) * (size_t)g64_.plane;   // one (zero, unused) ghost plane either side, as every level
+    const size_t nbytes = mx_alloc_elems_ * sizeof(double), npart = (size_t)mixed_partials_capacity();
+    for (auto &b : mx_) {
+        MG_HIP(hipMalloc(&b, nbytes));
+        MG_HIP(hipMemsetAsync(b, 0, nbytes, stream_));   // ghost planes and padding columns stay zero from here on
+        bytes_ += nbytes;
+    }
+    MG_HIP(hipMalloc((void **)&d_mx_part_, sizeof(double) * npart));
+    MG_HIP(hipMalloc((void **)&d_mx_sum_, sizeof(double)));
+    bytes_ += sizeof(double) * (npart + 1);
+    return MG_OK;
+}
+
+int Solver::mixed_set(bool rhs, const double *host)
+{
+    const char *fn = rhs ? "mg_mixed_set_rhs" : "mg_mixed_set_solution";
+    MG_TRY(mixed_check(fn));
+    MG_HIP(hipSetDevice(device_));
+    MG_TRY(mixed_alloc());
+    MG_TRY(stage_copy(reinterpret_cast<char *>(mxptr(rhs ? MXB : MXU)), g64_, sizeof(double), const_cast<double *>(host), true));
+    (rhs ? mx_has_b_ : mx_has_u_) = true;
+    return MG_OK;
+}
+
+int Solver::mixed_get_solution(double *host)
+{
+    MG_TRY(mixed_check("mg_mixed_get_solution"));
+    if (!mx_has_u_) { set_last_error("mg_mixed_get_solution: no solution yet (call mg_mixed_set_solution first)"); return MG_ERR_BAD_ARG; }
+    return stage_copy(reinterpret_cast<char *>(mxptr(MXU)), g64_, sizeof(double), host, false);
+}
+
+// 2^-e with frexp(sqrt(v)) = (m, e): brings a vector of squared norm v to a norm in [0.5, 1)
+static double mixed_scale(double v)
+{
+    if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
+    int e = 0;
+    (void)std::frexp(std::sqrt(v), &e);
+    return std::ldexp(1.0, -e);
+}
+
+int Solver::mixed_inner(int inner_cycles)
+{
+    MG_HIP(hipMemsetAsync(lv_[0].base[MG_ARR_U], 0, lv_[0].alloc_elems * esize(), stream_));
+    for (int c = 0; c < inner_cycles; c++) {
+        if (d_.outer_pre_gs > 0) MG_TRY(smooth_t<float>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS));   // `u * GS * GS`
+        MG_TRY(cycle_enqueue_t<float>());                                                                            // `* MGx`
+    }
+    return MG_OK;
+}
+
+int Solver::mixed_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st)
+{
+    MG_TRY(mixed_check("mg_mixed_solve"));
+    if (stage_fn_) {
+        set_last_error("mg_mixed_solve: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
+        return MG_ERR_BAD_ARG;
+    }
+    if (inner_cycles < 1) { set_last_error("mg_mixed_solve: inner_cycles must be at least 1"); return MG_ERR_BAD_ARG; }
+    if (maxit < 0) { set_last_error("mg_mixed_solve: negative maxit"); return MG_ERR_BAD_ARG; }
+    if (!mx_has_b_ || !mx_has_u_) {
+        set_last_error("mg_mixed_solve: call mg_mixed_set_rhs and mg_mixed_set_solution first");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    lock_iters_ = -1;
+    fine_pre_done_ = 0;
+    Level &L0 = lv_[0];
+    const Geom &g32 = L0.g;
+    const double *const b = mxptr(MXB);
+    mg_mixed_stats out{0, 0, 0, 0, 0.0};
+    int nh = 0;
+    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
+    auto fetch_sum = [&](double *v) -> int {   // the sum the last launch left in d_mx_sum_; synchronises
+        MG_HIP(hipGetLastError());
+        MG_HIP(hipMemcpyAsync(h_scal_ + 6, d_mx_sum_, sizeof(double), hipMemcpyDeviceToHost, stream_));
+        MG_HIP(hipStreamSynchronize(stream_));
+        *v = h_scal_[6];
+        return MG_OK;
+    };
+
+    // u = b on the Dirichlet nodes; b.b over all nodes, as mg_solve
+    launch_cg_boundary_copy<double>(stream_, g64_, mxptr(MXU), b);
+    int np = launch_mixed_sumsq(stream_, g64_, b, d_mx_part_);
+    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+    double bb = 0, rr = 0;
+    MG_TRY(fetch_sum(&bb));
+    double s = mixed_scale(bb);   // the scale RHS32(0) currently carries
+    L0.rhs_halo_ok = false;
+    np = launch_mixed_residual(stream_, g64_, g32, L0.coef, mxptr(MXU), b, ptr<float>(MG_ARR_RHS, 0), s, d_mx_part_);
+    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+    MG_TRY(fetch_sum(&rr));
+    auto relres = [&](double v) { return v == 0.0 ? 0.0 : std::sqrt(v / bb); };
+    record(relres(rr));
+    if (!std::isfinite(rr) || !std::isfinite(out.relres)) {
+        out.status = 2;
+    } else if (rr == 0.0) {
+        out.status = 0;   // nothing to do: u solves the system (b == 0 with u == 0 inside included)
+    } else {
+        for (int k = 0;; k++) {
+            if (k > 0 && out.relres <= tol) { out.status = 0; break; }
+            if (k == maxit) { out.status = 1; break; }
+            MG_TRY(mixed_inner(inner_cycles));
+            out.cycles += inner_cycles;
+            const double s_next = mixed_scale(rr);   // from the PREVIOUS residual: known before the launch
+            np = launch_mixed_correct_residual(stream_, g64_, g32, L0.coef, mxptr(MXU), ptr<float>(MG_ARR_U, 0), b, mxptr(MXU2),
+                                               ptr<float>(MG_ARR_RHS, 0), s, s_next, d_mx_part_);
+            launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+            double rr_new = 0;
+            MG_TRY(fetch_sum(&rr_new));   // the one host synchronisation per correction: the stopping test
+            record(relres(rr_new));
+            if (!std::isfinite(rr_new) || !std::isfinite(out.relres)) { out.status = 2; break; }   // not taken: u64 stays the last iterate
+            std::swap(mx_[MXU], mx_[MXU2]);
+            out.outer = k + 1;
+            rr = rr_new;
+            s = s_next;
+        }
+    }
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
+int Solver::mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r)
+{
+    MG_TRY(mixed_check("mg_mixed_kernel"));
+    if (kernel != MG_MIXED_K_RESIDUAL && kernel != MG_MIXED_K_CORRECT_RESIDUAL) { set_last_error("mg_mixed_kernel: unknown kernel"); return MG_ERR_BAD_ARG; }
+    const bool corr = kernel == MG_MIXED_K_CORRECT_RESIDUAL;
+    if (!check_arr(arr_r32, 0, "mg_mixed_kernel") || (corr && !check_arr(arr_e32, 0, "mg_mixed_kernel"))) return MG_ERR_BAD_ARG;
+    if (corr && arr_e32 == arr_r32) { set_last_error("mg_mixed_kernel: the arrays must be distinct"); return MG_ERR_BAD_ARG; }
+    if (corr && !(scale_in != 0.0 && std::isfinite(scale_in))) { set_last_error("mg_mixed_kernel: scale_in must be finite and not zero"); return MG_ERR_BAD_ARG; }
+    if (!mx_has_b_ || !mx_has_u_) {
+        set_last_error("mg_mixed_kernel: call mg_mixed_set_rhs and mg_mixed_set_solution first");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    Level &L0 = lv_[0];
+    if (arr_r32 == MG_ARR_RHS) L0.rhs_halo_ok = false;
+    int np = 0;
+    if (corr)
+        np = launch_mixed_correct_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), ptr<float>(arr_e32, 0), mxptr(MXB), mxptr(MXU2),
+                                           ptr<float>(arr_r32, 0), scale_in, scale_out, d_mx_part_);
+    else
+        np = launch_mixed_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), mxptr(MXB), ptr<float>(arr_r32, 0), scale_out, d_mx_part_);
+    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+    MG_HIP(hipGetLastError());
+    MG_HIP(hipMemcpyAsync(h_scal_ + 6, d_mx_sum_, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    if (corr) std::swap(mx_[MXU], mx_[MXU2]);
+    if (sumsq_r) *sumsq_r = h_scal_[6];
     return MG_OK;
 }
 

@@ -87,6 +87,12 @@ public:
     int fmg(int cycles_per_level, mg_fmg_stats *st);
     // arr_dst(l) = Pi arr_src(l + 1), Dirichlet nodes from arr_bnd(l) (< 0: interpolated too) (mg_fmg_prolong)
     int fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd);
+    // mixed-precision defect correction: fp64 u / b of level 0 beside an MG_F32 hierarchy (mg_mixed_*); the fp64 arrays are
+    // allocated by the first mixed_set_*
+    int mixed_set(bool rhs, const double *host);
+    int mixed_get_solution(double *host);
+    int mixed_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st);
+    int mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r);
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -154,6 +160,10 @@ private:
     template <typename T> int precondition_t();   // z = M r: one mg_solve outer iteration from zero on (z, r)
     template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
+    int mixed_check(const char *fn) const;      // MG_F32, single-GPU handle
+    int mixed_alloc();
+    int mixed_inner(int inner_cycles);         // U32(0) = 0, then inner_cycles outer iterations of mg_solve on RHS32(0); no sync
+    int stage_copy(char *dev, const Geom &g, size_t es, void *host, bool to_device);   // stage_rows on any level-shaped array
     int krylov_scalars_alloc();
     int krylov_alloc();
     template <typename T> int vcycle_rec_t(int l, bool u_zero = false);
@@ -200,6 +210,15 @@ private:
     CgScalars *d_cg_ = nullptr, *h_cg_ = nullptr;
     double *d_cg_part_ = nullptr;
     double *d_cg_dot_ = nullptr;    // [2]: sums of the kernel check (mg_pcg_kernel)
+    // fp64 outer arrays of mixed_solve (allocated on first use, kept until the handle goes): b64 and two copies of u64 -- the
+    // fused correction + residual launch writes u out of place and the two are swapped, like U / TMP under a sweep
+    enum { MXB = 0, MXU = 1, MXU2 = 2, NMX = 3 };
+    void *mx_[NMX] = {};
+    Geom g64_{};                    // level 0 with the fp64 pitch
+    size_t mx_alloc_elems_ = 0;
+    bool mx_has_b_ = false, mx_has_u_ = false;
+    double *d_mx_part_ = nullptr, *d_mx_sum_ = nullptr;   // per-workgroup partial sums and their total
+    double *mxptr(int k) const { return reinterpret_cast<double *>(mx_[k]) + g64_.plane; }   // local plane 0
     Geom gfull_{};
     void *full_[3] = {nullptr, nullptr, nullptr};
     std::vector<SlabPlan> planT_;

@@ -1,0 +1,451 @@
+"""mg_mixed_solve -- fp64 defect correction over the fp32 multigrid cycles of an MG_F32 handle (include/mg_hip.h).
+
+* kernel level: the two kernels of mg_mixed.hip against the contract restated in numpy, bit for bit, and their sums of
+  squares against long-double sums;
+* the whole solve against an independent loop: numpy fp64 residual, the CPU oracle's fp32 cycles (COARSE_FIXED: a fixed
+  operator, bit-exact with the GPU's cycle) -- u64 bit for bit;
+* what the solver is for: an fp64 residual of 1e-11 where the fp32 handle's own solve stalls above 1e-6, in no more
+  cycles than the fp64 handle needs (one correction of slack);
+* invariance under scaling b by 2^-200 / 2^+200, a dense solve, determinism, isolation, edge cases and refusals.
+
+Not checked here: that the padding columns (x >= nx) of the arrays stay zero -- no entry point of the C ABI reads them;
+the kernels only ever store the first nx elements of a row (masked stores, mg_mixed.hip).
+"""
+import math
+import threading
+
+import numpy as np
+import pytest
+
+from multigrid_prj_amd import capi
+from oracle import pyoracle as po
+from tests.npref import Problem, boundary_mask
+
+pytestmark = pytest.mark.gpu
+
+V22 = dict(cycle=capi.CYCLE_V, smoother=capi.SMOOTH_JACOBI, nu_pre=2, nu_post=2, restriction=capi.RESTRICT_FULLW,
+           outer_pre_gs=0)
+FIXED = dict(coarse_mode=capi.COARSE_FIXED, coarse_maxit=20)
+TOLC = dict(coarse_mode=capi.COARSE_TOL, coarse_maxit=2000, coarse_tol=0.1)
+F32 = dict(dtype=capi.MG_F32)
+
+
+def interior(ndim):
+    return (slice(1, -1),) * ndim
+
+
+def residual64(u, b, coef):
+    """the contract's residual in fp64: r = b - (((((((0 + cz u[k-1]) + cy u[j-1]) + cx u[i-1]) + cd u) + cx u[i+1]) + cy u[j+1])
+    + cz u[k+1]) inside, 0 on Dirichlet nodes; every operation rounded separately"""
+    cx, cy, cz, cd = (np.float64(c) for c in coef)
+    I = interior(u.ndim)
+
+    def nb(axis, off):
+        sl = [slice(1, -1)] * u.ndim
+        sl[axis] = slice(1 + off, u.shape[axis] - 1 + off)
+        return u[tuple(sl)]
+
+    ax_z, ax_y, ax_x = (0, 1, 2) if u.ndim == 3 else (None, 0, 1)
+    s = np.zeros_like(u[I])
+    if u.ndim == 3:
+        s = s + cz * nb(ax_z, -1)
+    s = s + cy * nb(ax_y, -1)
+    s = s + cx * nb(ax_x, -1)
+    s = s + cd * u[I]
+    s = s + cx * nb(ax_x, +1)
+    s = s + cy * nb(ax_y, +1)
+    if u.ndim == 3:
+        s = s + cz * nb(ax_z, +1)
+    r = np.zeros_like(u)
+    r[I] = b[I] - s
+    return r
+
+
+def ld_sumsq(a):
+    a = a.astype(np.longdouble)
+    return float(np.sum(a * a))
+
+
+def scale_of(v):
+    """scale(v) = 2^-e with frexp(sqrt(v)) = (m, e); 1.0 when v is 0 or not finite"""
+    if not (v > 0.0) or not math.isfinite(v):
+        return 1.0
+    return math.ldexp(1.0, -math.frexp(math.sqrt(v))[1])
+
+
+def correct64(u, e32, s_in):
+    un = u.copy()
+    I = interior(u.ndim)
+    un[I] = u[I] + e32[I].astype(np.float64) / np.float64(s_in)
+    return un
+
+
+# ---------------------------------------------------------------- kernel level
+KCASES = [(dim, n) for dim in (2, 3) for n in (17, 97, 129, 385)
+          if not (dim == 3 and n == 385)]   # 385^3 is 57 M points per array: too big for a numpy reference in a unit test
+
+
+@pytest.mark.parametrize("dim,n", KCASES)
+def test_kernels_match_contract(dim, n):
+    rng = np.random.default_rng(n * 10 + dim)
+    kw = dict(dim=dim, n=n, levels=2, length=1.0, alpha=1.0, aniso=(1.0, 0.7, 0.3) if dim == 3 else (1.0, 0.6, 1.0), **F32)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        shape = s.level_shape(0)
+        coef = s.level_coefficients(0)
+        assert coef == po.level_coef(po.make_desc(**dict(kw, dtype=po.MG_F64)), 0)
+        bnd = boundary_mask(shape)
+        u = rng.standard_normal(shape)
+        b = rng.standard_normal(shape) * 1e3
+        e32 = rng.standard_normal(shape).astype(np.float32)
+        other = rng.standard_normal(shape).astype(np.float32)
+        s.mixed_set_rhs(b)
+        s.mixed_set_solution(u)
+        s.set_array(capi.ARR_E, 0, e32)
+        s.set_array(capi.ARR_U, 0, other)
+        # residual alone
+        s_out = 2.0 ** 5
+        ss = s.mixed_kernel(capi.MIXED_K_RESIDUAL, 1.0, s_out, capi.ARR_E, capi.ARR_TMP)
+        r = residual64(u, b, coef)
+        assert np.array_equal(s.get_array(capi.ARR_TMP, 0), (np.float64(s_out) * r).astype(np.float32))
+        np.testing.assert_allclose(ss, ld_sumsq(r), rtol=1e-13)
+        assert np.array_equal(s.mixed_get_solution(), u)
+        assert np.array_equal(s.get_array(capi.ARR_E, 0), e32) and np.array_equal(s.get_array(capi.ARR_U, 0), other)
+        # correction + residual of the corrected u; a power of two (the driver's case), then a scale that is none
+        for s_in, s_out in ((2.0 ** -7, 2.0 ** 5), (0.37, 3.0)):
+            ss = s.mixed_kernel(capi.MIXED_K_CORRECT_RESIDUAL, s_in, s_out, capi.ARR_E, capi.ARR_RES)
+            un = correct64(u, e32, s_in)
+            r = residual64(un, b, coef)
+            got_u = s.mixed_get_solution()
+            assert np.array_equal(got_u[bnd], u[bnd])          # Dirichlet nodes untouched
+            assert np.array_equal(got_u, un)
+            assert np.array_equal(s.get_array(capi.ARR_RES, 0), (np.float64(s_out) * r).astype(np.float32))
+            np.testing.assert_allclose(ss, ld_sumsq(r), rtol=1e-13)
+            assert np.array_equal(s.get_array(capi.ARR_E, 0), e32)
+            u = un
+        # e on the Dirichlet nodes is not looked at: NaN there changes nothing
+        e_nan = e32.copy()
+        e_nan[bnd] = np.nan
+        s.set_array(capi.ARR_E, 0, e_nan)
+        s.mixed_kernel(capi.MIXED_K_CORRECT_RESIDUAL, 2.0 ** 3, 1.0, capi.ARR_E, capi.ARR_RES)
+        un = correct64(u, e32, 2.0 ** 3)
+        assert np.array_equal(s.mixed_get_solution(), un)
+        assert np.array_equal(s.get_array(capi.ARR_RES, 0), residual64(un, b, coef).astype(np.float32))
+
+
+# ---------------------------------------------------------------- whole solve against an independent loop
+SOLVE_CASES = {
+    "2d129-sawtooth": dict(dim=2, n=129, levels=3, length=10.0, alpha=1.0, smoother=capi.SMOOTH_JACOBI, **FIXED),
+    "3d65-v22": dict(dim=3, n=65, levels=4, length=1.0, **V22, omega=6 / 7, **FIXED),
+    "3d65-rb": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, smoother=capi.SMOOTH_RBGS), **FIXED),
+    "3d65-aniso-semi": dict(dim=3, n=65, levels=5, length=1.0, **V22, omega=0.8, aniso=(1.0, 1.0, 0.01), semi_xy=2, **FIXED),
+}
+
+
+def ref_mixed(kw, b, u0, inner_cycles, corrections):
+    """the contract's loop: numpy fp64 residual, the CPU oracle's fp32 hierarchy for the cycles"""
+    coef = po.level_coef(po.make_desc(**dict(kw, dtype=po.MG_F64)), 0)
+    S = po.Solver(po.make_desc(**dict(kw, dtype=po.MG_F32)))
+    pre_gs = kw.get("outer_pre_gs", 2)
+    bnd = boundary_mask(b.shape)
+    u = u0.astype(np.float64).copy()
+    u[bnd] = b[bnd]
+    bb = float(np.sum(b.astype(np.longdouble) ** 2))
+    r = residual64(u, b, coef)
+    rr = ld_sumsq(r)
+    hist = [math.sqrt(rr / bb)]
+    s = scale_of(bb)
+    for _ in range(corrections):
+        S.set_rhs((np.float64(s) * r).astype(np.float32))
+        S.set_solution(np.zeros(b.shape, np.float32))
+        for _c in range(inner_cycles):
+            if pre_gs:
+                S.smooth_fine(po.SMOOTH_GS_LEX, pre_gs)
+            S.cycle()
+        u = correct64(u, S.get_solution(), s)
+        s = scale_of(rr)
+        r = residual64(u, b, coef)
+        rr = ld_sumsq(r)
+        hist.append(math.sqrt(rr / bb))
+    S.close()
+    return np.array(hist), u
+
+
+def random_problem(kw, seed):
+    """random right-hand side with random Dirichlet data"""
+    return np.random.default_rng(seed).standard_normal((kw["n"],) * kw["dim"])
+
+
+@pytest.mark.parametrize("inner_cycles", [1, 4])
+@pytest.mark.parametrize("name", list(SOLVE_CASES))
+def test_solve_matches_independent_loop(name, inner_cycles):
+    kw = SOLVE_CASES[name]
+    b = random_problem(kw, 11)
+    u0 = np.zeros_like(b)
+    href, uref = ref_mixed(kw, b, u0, inner_cycles, 6)
+    with capi.Solver(capi.make_desc(**kw, **F32)) as s:
+        s.mixed_set_rhs(b)
+        s.mixed_set_solution(u0)
+        hist, st = s.mixed_solve(tol=0.0, maxit=6, inner_cycles=inner_cycles)
+        u = s.mixed_get_solution()
+    print(name, inner_cycles, "gpu", " ".join(f"{v:.3e}" for v in hist), "| ref", " ".join(f"{v:.3e}" for v in href))
+    print("max |u - uref| =", np.abs(u - uref).max(), " differing entries:", int((u != uref).sum()))
+    assert (st.status, st.outer, st.cycles) == (capi.MIXED_MAXIT, 6, 6 * inner_cycles) and len(hist) == 7
+    assert st.relres == hist[-1]
+    assert np.array_equal(u, uref)
+    np.testing.assert_allclose(hist, href, rtol=1e-12)
+    assert hist[-1] < hist[0]
+
+
+# ---------------------------------------------------------------- what it is for
+def true_relres(kw, u, b):
+    coef = po.level_coef(po.make_desc(**dict(kw, dtype=po.MG_F64)), 0)
+    return math.sqrt(ld_sumsq(residual64(np.asarray(u, np.float64), b, coef)) / ld_sumsq(b))
+
+
+@pytest.mark.parametrize("name", ["3d65-v22", "3d65-rb"])
+def test_reaches_fp64_tolerance_in_fp64_cycle_count(name):
+    kw = dict(SOLVE_CASES[name], **TOLC)
+    b = random_problem(kw, 3)
+    tol, inner = 1e-11, 4
+    with capi.Solver(capi.make_desc(**kw, **F32)) as s:
+        s.mixed_set_rhs(b)
+        s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(tol, 40, inner)
+        u = s.mixed_get_solution()
+    assert st.status == capi.MIXED_CONVERGED and st.relres <= tol, (st.status, hist)
+    ub = u.copy()
+    ub[boundary_mask(b.shape)] = b[boundary_mask(b.shape)]
+    assert np.array_equal(u, ub)
+    np.testing.assert_allclose(st.relres, true_relres(kw, u, b), rtol=1e-12)
+    with capi.Solver(capi.make_desc(**kw)) as s64:
+        s64.set_rhs(b)
+        u0 = np.zeros_like(b)
+        u0[boundary_mask(b.shape)] = b[boundary_mask(b.shape)]
+        s64.set_solution(u0)
+        h64, _ = s64.solve(tol, 200)
+    n64 = len(h64) - 1
+    print(f"{name}: fp64 mg_solve {n64} cycles (last {h64[-1]:.3e}); mixed {st.cycles} fp32 cycles in {st.outer} corrections "
+          f"(last {st.relres:.3e})")
+    assert h64[-1] <= tol
+    assert st.cycles <= math.ceil(n64 / inner) * inner + inner
+
+
+def test_fp32_solve_alone_stalls():
+    """the reason the feature exists: the fp32 handle's own solve cannot get near an fp64 tolerance"""
+    kw = SOLVE_CASES["3d65-v22"]
+    b = random_problem(kw, 3)
+    with capi.Solver(capi.make_desc(**kw, **F32)) as s:
+        s.set_rhs(b)
+        u0 = np.zeros_like(b)
+        u0[boundary_mask(b.shape)] = b[boundary_mask(b.shape)]
+        s.set_solution(u0)
+        hist, _ = s.solve(1e-11, 40)
+        u32 = s.get_solution()
+    rel = true_relres(kw, u32, b)
+    print("fp32 mg_solve, 65^3 V(2,2):", len(hist) - 1, "cycles, true fp64 relative residual", rel)
+    assert rel > 1e-6
+
+
+# ---------------------------------------------------------------- scale invariance
+@pytest.mark.parametrize("p", [-200, 200])
+def test_scale_invariance(p):
+    kw = SOLVE_CASES["3d65-v22"]
+    b = random_problem(kw, 5)
+    f = math.ldexp(1.0, p)
+    out = []
+    for bb in (b, b * f):
+        with capi.Solver(capi.make_desc(**kw, **F32)) as s:
+            s.mixed_set_rhs(bb)
+            s.mixed_set_solution(np.zeros_like(bb))
+            hist, st = s.mixed_solve(0.0, 6, 3)
+            out.append((hist, s.mixed_get_solution(), st))
+    (h0, u0, st0), (h1, u1, st1) = out
+    assert len(h0) == 7 and h0[-1] < 1e-3 * h0[0]
+    assert np.array_equal(h0, h1)
+    assert np.array_equal(u0 * f, u1)
+    assert (st0.outer, st0.cycles, st0.status) == (st1.outer, st1.cycles, st1.status)
+
+
+# ---------------------------------------------------------------- against a dense solve
+def dense_interior(kw, b):
+    """x on the interior of the dense system A_II x_I = b_I - A_IB b_B; boundary x = b"""
+    P = Problem(**kw, prec=np.float64)
+    ax, cd = P.coef(0)
+    shp = b.shape
+    m = [s - 2 for s in shp]
+    eye = [np.eye(k) for k in m]
+    off = [np.eye(k, k=1) + np.eye(k, k=-1) for k in m]
+    A = float(cd) * np.eye(int(np.prod(m)))
+    for a in range(len(shp)):
+        mats = [off[i] if i == a else eye[i] for i in range(len(shp))]
+        K = mats[0]
+        for M_ in mats[1:]:
+            K = np.kron(K, M_)
+        A += float(ax[a]) * K
+    xb = np.where(boundary_mask(shp), b, 0.0)
+    rhs = (b - np.asarray(P.apply_A(xb, 0), np.float64))[interior(len(shp))].ravel()
+    x = xb.copy()
+    x[interior(len(shp))] = np.linalg.solve(A, rhs).reshape(m)
+    return x
+
+
+@pytest.mark.parametrize("kw", [
+    dict(dim=2, n=33, levels=3, length=10.0, alpha=1.0, smoother=capi.SMOOTH_JACOBI),
+    dict(dim=3, n=17, levels=3, length=1.0, **V22, omega=0.8),
+])
+def test_answer_equals_dense_solve(kw):
+    b = np.random.default_rng(7).standard_normal((kw["n"],) * kw["dim"])
+    xd = dense_interior(kw, b)
+    with capi.Solver(capi.make_desc(**kw, **F32)) as s:
+        s.mixed_set_rhs(b)
+        s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(1e-13, 40, 4)
+        x = s.mixed_get_solution()
+    print("dense check:", kw["dim"], "status", st.status, "corrections", st.outer, "last", st.relres)
+    assert st.status in (capi.MIXED_CONVERGED, capi.MIXED_MAXIT)
+    np.testing.assert_allclose(x, xd, rtol=1e-9, atol=1e-9 * np.abs(xd).max())
+
+
+# ---------------------------------------------------------------- determinism and isolation
+def test_determinism_and_isolation():
+    kw = dict(dim=3, n=65, levels=4, length=1.0, **V22, omega=6 / 7, **TOLC, **F32)
+    rng = np.random.default_rng(4)
+    b = rng.standard_normal((65,) * 3)
+    x0 = rng.standard_normal(b.shape)
+    b32, x32 = b.astype(np.float32), x0.astype(np.float32)
+    with capi.Solver(capi.make_desc(**kw)) as fresh:
+        bytes_fresh = fresh.device_bytes()
+        fresh.set_rhs(b32); fresh.set_solution(x32)
+        h_fresh, _ = fresh.solve(1e-5, 20)
+        u_fresh = fresh.get_solution()
+        assert fresh.device_bytes() == bytes_fresh          # a handle that never called it holds what it held
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        assert s.device_bytes() == bytes_fresh
+        s.mixed_set_rhs(b)
+        grown = s.device_bytes() - bytes_fresh
+        assert grown >= 3 * 8 * b.size                       # b64 and two copies of u64
+        s.mixed_set_solution(x0)
+        assert s.device_bytes() - bytes_fresh == grown
+        h1, st1 = s.mixed_solve(1e-10, 30, 4)
+        u1 = s.mixed_get_solution()
+        s.mixed_set_solution(x0)
+        h2, st2 = s.mixed_solve(1e-10, 30, 4)
+        assert st1.status == capi.MIXED_CONVERGED
+        assert np.array_equal(h1, h2) and np.array_equal(u1, s.mixed_get_solution())
+        assert (st1.outer, st1.cycles, st1.status, st1.relres) == (st2.outer, st2.cycles, st2.status, st2.relres)
+        assert s.device_bytes() - bytes_fresh == grown
+        # the fp32 solve afterwards is the fresh handle's, bit for bit
+        s.set_rhs(b32); s.set_solution(x32)
+        h_mg, _ = s.solve(1e-5, 20)
+        assert np.array_equal(h_mg, h_fresh) and np.array_equal(s.get_solution(), u_fresh)
+
+
+# ---------------------------------------------------------------- edge cases
+def test_edge_cases():
+    kw = dict(dim=2, n=33, levels=3, length=1.0, **V22, omega=0.8, **F32)
+    rng = np.random.default_rng(2)
+    b = rng.standard_normal((33, 33))
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.mixed_set_rhs(b)
+        s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(1e-8, 0, 4)                 # no correction allowed
+        assert (st.status, st.outer, st.cycles) == (capi.MIXED_MAXIT, 0, 0) and len(hist) == 1 and st.relres == hist[0]
+        u = s.mixed_get_solution()
+        assert np.array_equal(u[boundary_mask(b.shape)], b[boundary_mask(b.shape)]) and np.all(u[interior(2)] == 0)
+        s.mixed_set_rhs(np.zeros_like(b))                    # b = 0: u = 0 is the answer
+        s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(1e-8, 10, 4)
+        assert (st.status, st.outer) == (capi.MIXED_CONVERGED, 0) and np.all(hist == 0)
+        assert np.all(s.mixed_get_solution() == 0)
+    # a divergent inner cycle (over-relaxed Jacobi, omega = 1.9): whatever happens, the loop ends, u stays finite and
+    # the status says what happened
+    kw = dict(kw, omega=1.9, nu_pre=1, nu_post=1)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.mixed_set_rhs(b)
+        s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(1e-10, 200, 4)
+        print("omega 1.9: status", st.status, "corrections", st.outer, "entries", len(hist), "last", hist[-1])
+        assert st.status in (capi.MIXED_CONVERGED, capi.MIXED_MAXIT, capi.MIXED_NOT_FINITE)
+        assert np.all(np.isfinite(hist[:-1]))
+        assert np.all(np.isfinite(hist)) or st.status == capi.MIXED_NOT_FINITE
+        assert np.all(np.isfinite(s.mixed_get_solution()))
+
+
+# ---------------------------------------------------------------- refusals
+def test_refusals_on_the_host():
+    kw = dict(dim=2, n=33, levels=3, length=10.0)
+    b = np.random.default_rng(0).standard_normal((33, 33))
+    u0 = np.random.default_rng(1).standard_normal((33, 33))
+    with capi.Solver(capi.make_desc(**kw)) as s64:           # an fp64 handle has no fp32 hierarchy to run the cycles in
+        before = s64.device_bytes()
+        for call in (lambda: s64.mixed_set_rhs(b), lambda: s64.mixed_set_solution(u0), s64.mixed_get_solution,
+                     lambda: s64.mixed_solve(1e-8, 10, 4),
+                     lambda: s64.mixed_kernel(capi.MIXED_K_RESIDUAL, 1.0, 1.0, capi.ARR_E, capi.ARR_TMP)):
+            with pytest.raises(capi.MgError) as e:
+                call()
+            assert e.value.code == -4 and "MG_F32" in str(e.value)
+        assert s64.device_bytes() == before
+    with capi.Solver(capi.make_desc(**kw, **F32)) as s:
+        for call, word in ((lambda: s.mixed_solve(1e-8, 10, 4), "mg_mixed_set_rhs"), (s.mixed_get_solution, "mg_mixed_set_solution")):
+            with pytest.raises(capi.MgError) as e:           # nothing set yet
+                call()
+            assert e.value.code == -4 and word in str(e.value)
+        s.mixed_set_rhs(b)
+        with pytest.raises(capi.MgError) as e:               # only one of the two
+            s.mixed_solve(1e-8, 10, 4)
+        assert e.value.code == -4
+        s.mixed_set_solution(u0)
+        for args, word in (((1e-8, 10, 0), "inner_cycles"), ((1e-8, -1, 4), "maxit")):
+            with pytest.raises(capi.MgError) as e:
+                s.mixed_solve(*args)
+            assert e.value.code == -4 and word in str(e.value)
+            assert np.array_equal(s.mixed_get_solution(), u0)
+        s.set_stage_callback(lambda *a: None)
+        with pytest.raises(capi.MgError) as e:
+            s.mixed_solve(1e-8, 10, 4)
+        assert e.value.code == -4 and "stage callback" in str(e.value)
+        assert np.array_equal(s.mixed_get_solution(), u0)
+        s.set_stage_callback(None)
+        _, st = s.mixed_solve(1e-9, 50, 2)
+        assert st.status == capi.MIXED_CONVERGED
+
+
+def test_refuses_distributed_handle():
+    from tests.thread_ranks import ThreadWorld
+    kw = dict(dim=3, n=33, levels=3, length=1.0, **V22, omega=0.8, dist_min_n=9, **F32)
+    desc = capi.make_desc(**kw)
+    tw = ThreadWorld(2)
+    res = [None, None]
+
+    def rank_main(r):
+        try:
+            z0, nz, _ = capi.plan_slab(desc, 2, r, 0)
+            s = capi.Solver(desc, device=0, rank=r, nranks=2, host_comm=tw.host_comm(r))
+            try:
+                got = []
+                for call in (lambda: s.mixed_set_rhs(np.ones((nz, 33, 33))), lambda: s.mixed_set_solution(np.ones((nz, 33, 33))),
+                             lambda: s.mixed_solve(1e-8, 10, 4)):
+                    try:
+                        call()
+                        got.append("accepted")
+                    except capi.MgError as e:
+                        got.append((e.code, "distributed" in str(e)))
+                res[r] = got
+            finally:
+                s.close()
+        except Exception as e:   # noqa: BLE001 -- reported below
+            res[r] = repr(e)
+
+    th = [threading.Thread(target=rank_main, args=(r,)) for r in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(120)
+    assert res == [[(-4, True)] * 3] * 2, res
+    # the dry-run measurement handle is distributed too
+    with capi.Solver(desc, device=0, rank=0, nranks=2, dry=True) as s:
+        nz = s.level_shape(0)[0]
+        for call in (lambda: s.mixed_set_rhs(np.ones((nz, 33, 33))), lambda: s.mixed_solve(1e-8, 10, 4)):
+            with pytest.raises(capi.MgError) as e:
+                call()
+            assert e.value.code == -4 and "distributed" in str(e.value)
