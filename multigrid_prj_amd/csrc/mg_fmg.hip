@@ -25,7 +25,6 @@
 //                    workgroup marching FMG_ZC planes reads FMG_ZC + 3, so the coarse array (an eighth of the traffic)
 //                    is read (8/5)(19/16) = 1.9 times, mostly out of L2; the fine array is written once with whole
 //                    16-byte non-temporal vectors and the odd last column as one full 128-byte line (mg_jacobi_fast.hip).
-#include <cstdlib>
 
 #include "mg_kernels.h"
 
@@ -248,8 +247,7 @@ template <typename T>
 bool fmg_prolong_fast_ok(const Geom &gc, const Geom &gf)
 {
     constexpr int V = FV<T>::V;
-    const char *e = getenv("MG_FMG_FAST");
-    if (e && e[0] == '0') return false;
+    if (!switches().fmg_fast) return false;
     if (!(gf.dim == 3 && gc.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 && gc.nx >= 17 && gc.ny >= 3 && (gf.nx % V) == 1)) return false;
     if (gf.gz0 != 0 || gc.gz0 != 0 || gf.gnz != gf.nz || gc.gnz != gc.nz) return false;
     return is_semi_transition(gf, gc) ? gf.nz == gc.nz : (gf.nz == 2 * gc.nz - 1 && gc.nz >= 3);

@@ -24,7 +24,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 namespace mg {
 namespace {
@@ -246,11 +245,10 @@ constexpr int J2_TYO = 2;
 // the rule below gives 24 / 8 / 3 there.
 static int j2_nbz(const Geom &g, int tpr, int tyo = 3)   // tyo: output rows per workgroup of the launch (slab rule only)
 {
-    static const int zc_env = [] { const char *e = getenv("MG_J2_ZC"); return e ? atoi(e) : 0; }();
-    static const bool slab_rule = [] { const char *e = getenv("MG_J2_SLAB_RULE"); return !(e && e[0] == '0'); }();
+    const int zc_env = switches().j2_zc;
     int zc = 3;  // the longest march that still leaves enough workgroups (semi-coarsened levels: long in z, few rows)
     if (zc_env > 1) zc = zc_env;
-    else if (slab_rule && g.gnz != g.nz && g.nz >= 8) {
+    else if (g.gnz != g.nz && g.nz >= 8) {
         // A piece of a z-slab (the interior planes of a rank's share of a distributed level): a few dozen to a few hundred planes,
         // where the rule below would cut 60 planes into 20 marches of 3 (5 first-sweep planes per 3 outputs). Measured on one
         // rank's schedule (tools/dry_zc.sh, 513^2 planes): the best chunk count is the one whose workgroups fill a whole
@@ -721,7 +719,7 @@ int launch_residual_fast(hipStream_t s, const Geom &g, const Coef<T> &c, const T
 {
     // the norm-only residual writes nothing, so longer marches (fewer z-halo planes re-read) only help it: 9 planes
     // 0.458 ms at 513^3 against 0.51 with 3, 0.48 with 6, 0.464 with 12 (MG_RES_ZC)
-    static const int res_zc = [] { const char *e = getenv("MG_RES_ZC"); return e ? atoi(e) : 9; }();
+    const int res_zc = switches().res_zc;
     FastGrid f = fast_grid<T>(g, (!r && want_norm && res_zc > 0) ? res_zc : ZC);
     const bool nt = stream_level(g, sizeof(T));
     dim3 gr(f.grid), bl(64 * BW);
@@ -737,8 +735,10 @@ int launch_residual_fast(hipStream_t s, const Geom &g, const Coef<T> &c, const T
 // multiple of the wave size: 64 / 128 / 256 (n = 2^k + 1 grids) and 192 / 384 / 512 (n = 385, 769, 1025 in fp64:
 // the reference's own 385 fixture size, and BASELINE config 4's grid in double precision).
 static bool j2_row_ok(int v) { return v == 64 || v == 128 || v == 192 || v == 256 || v == 384 || v == 512; }
-// 512-thread rows keep two output rows per workgroup (three would need 82 KB of LDS: one workgroup per CU)
-static int j2_tyo_for(int tpr, int wanted) { return tpr > 384 ? 2 : wanted; }
+// Output rows per workgroup where the correction is not folded in: three (5 instead of 4 first-sweep rows per 3 instead of 2
+// outputs, 167 VGPRs, still 3 workgroups/CU: 0.86 -> 0.79 ms per pair at 513^3); 512-thread rows keep two (three would need
+// 82 KB of LDS: one workgroup per CU)
+static int j2_tyo_for(int tpr) { return tpr > 384 ? 2 : 3; }
 
 // fused double sweep: whole (non-distributed) 3-D level whose rows are exactly 64 ... 512 vectors
 // + the odd column; opt out with MG_FUSED_PAIR=0
@@ -746,8 +746,7 @@ template <typename T>
 bool jacobi2_ok(const Geom &g)
 {
     constexpr int V = VecOf<T>::V;
-    static const bool enabled = [] { const char *e = getenv("MG_FUSED_PAIR"); return !(e && e[0] == '0'); }();
-    if (!enabled || g.dim != 3 || g.gz0 != 0 || g.gnz != g.nz || g.ny < 3 || g.nz < 3) return false;
+    if (!switches().fused_pair || g.dim != 3 || g.gz0 != 0 || g.gnz != g.nz || g.ny < 3 || g.nz < 3) return false;
     const int v = (g.nx - 1) / V;
     return (g.nx - 1) % V == 0 && j2_row_ok(v);
 }
@@ -757,11 +756,7 @@ template <typename T>
 bool jacobi2_slab_ok(const Geom &g)
 {
     constexpr int V = VecOf<T>::V;
-    static const bool enabled = [] {
-        const char *e = getenv("MG_FUSED_PAIR"), *f = getenv("MG_FUSED_SLAB");
-        return !(e && e[0] == '0') && !(f && f[0] == '0');
-    }();
-    if (!enabled || g.dim != 3 || g.ny < 3 || g.nz < 6) return false;
+    if (!switches().fused_pair || !switches().fused_slab || g.dim != 3 || g.ny < 3 || g.nz < 6) return false;
     const int v = (g.nx - 1) / V;
     return (g.nx - 1) % V == 0 && j2_row_ok(v);
 }
@@ -774,10 +769,7 @@ int launch_jacobi2(hipStream_t s, const Geom &g, const Coef<T> &c, T omega, cons
     if (pair_wide_ok<T>(g)) return launch_pair_wide<T>(s, g, Geom{}, c, omega, u, (const T *)nullptr, rhs, out, zero_u, false, dup, d_partials);
     const int tpr = (g.nx - 1) / V;
     const int ncopy = dup > 0 ? 2 : 1;   // dup: the same geometry once more, `dup` planes further up, in the same launch
-    // three output rows per workgroup where the correction is not folded in: 5 instead of 4 first-sweep rows
-    // per 3 instead of 2 outputs, 167 VGPRs (still 3 workgroups/CU): 0.86 -> 0.79 ms per pair at 513^3
-    static const int tyo_env = [] { const char *e = getenv("MG_J2_TYO"); return e ? atoi(e) : 3; }();
-    const int tyo = j2_tyo_for(tpr, tyo_env);
+    const int tyo = j2_tyo_for(tpr);
     const int nby = (g.ny + J2_TYO - 1) / J2_TYO, nbz = j2_nbz(g, tpr, tyo == 3 ? 3 : 2);
     const int nblocks = nby * nbz, grid = ((ncopy * nblocks + 7) / 8) * 8;
     const bool damped = (omega != (T)1), nt = stream_level(g, sizeof(T));
@@ -811,8 +803,7 @@ int launch_jacobi2(hipStream_t s, const Geom &g, const Coef<T> &c, T omega, cons
 template <typename T>
 bool rb_fused_ok(const Geom &g)
 {
-    static const bool enabled = [] { const char *e = getenv("MG_FUSED_RB"); return !(e && e[0] == '0'); }();
-    return enabled && jacobi2_ok<T>(g);
+    return switches().fused_rb && jacobi2_ok<T>(g);
 }
 
 // coarse != nullptr: the sweep reads u + P coarse (prolong-add folded in, like launch_jacobi2_corr)
@@ -828,8 +819,7 @@ int launch_rb_fused(hipStream_t s, const Geom &g, const Coef<T> &c, const T *u, 
     if (pair_wide_ok<T>(g)) return launch_pair_wide<T>(s, g, gc, c, (T)1, u, coarse, rhs, out, zero_u, true, dup, d_partials);
     const int tpr = (g.nx - 1) / V;
     const int ncopy = (dup > 0 && !coarse) ? 2 : 1;
-    static const int tyo_env = [] { const char *e = getenv("MG_J2_TYO"); return e ? atoi(e) : 3; }();
-    const int tyo = j2_tyo_for(tpr, tyo_env);
+    const int tyo = j2_tyo_for(tpr);
     const int nby = (g.ny + J2_TYO - 1) / J2_TYO, nbz = j2_nbz(g, tpr, (tyo == 3 && !coarse) ? 3 : 2);
     const int nblocks = nby * nbz, grid = ((ncopy * nblocks + 7) / 8) * 8;
     const int nby3 = (g.ny + 2) / 3, grid3 = ((ncopy * nby3 * nbz + 7) / 8) * 8;
@@ -871,8 +861,7 @@ bool jacobi2_corr_ok(const Geom &gf, const Geom &gc)
 template <typename T>
 bool jacobi2_corr_slab_ok(const Geom &gf, const Geom &gc)
 {
-    static const bool enabled = [] { const char *e = getenv("MG_FUSED_PROLONG_SLAB"); return !(e && e[0] == '0'); }();
-    return enabled && jacobi2_slab_ok<T>(gf) && gc.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 &&
+    return switches().fused_prolong_slab && jacobi2_slab_ok<T>(gf) && gc.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 &&
            gf.gnz == 2 * gc.gnz - 1 && gf.gz0 == 2 * gc.gz0 && (gf.nz == 2 * gc.nz || gf.nz == 2 * gc.nz - 1) && gc.nz >= 2;
 }
 
@@ -886,16 +875,14 @@ void launch_jacobi2_corr(hipStream_t s, const Geom &g, const Geom &gc, const Coe
     const int nby = (g.ny + J2_TYO - 1) / J2_TYO, nbz = j2_nbz(g, tpr, 2);
     const int nblocks = nby * nbz, grid = (((dup > 0 ? 2 : 1) * nblocks + 7) / 8) * 8;
     const bool damped = (omega != (T)1);
-    static const int minw_env = [] { const char *e = getenv("MG_J2C_MINW"); return e ? atoi(e) : 0; }();
     // fp32 (four floats per lane, three coarse values per row) needs 180 VGPRs: held to 168 it spills 12 of them and runs
     // 5.5 ms per launch at 1025^3; at two waves per SIMD, unspilled, 4.8 ms. fp64 fits 163.
-    const int minw = minw_env ? minw_env : (sizeof(T) == 4 ? 2 : 3);
+    constexpr int minw = sizeof(T) == 4 ? 2 : 3;
     // fp32: two floats per lane (rows of 2 * tpr lanes) up to 256-lane rows: 92 instead of 180 VGPRs, 0.590 against 0.618 ms per
     // launch at 513^3; at 1025^3 the row would be a 512-thread workgroup (eight waves on one barrier per plane) and the four-float
-    // kernel at two waves per SIMD wins, 5.12 against 5.49 ms (MG_J2C_V2=0: four floats per lane everywhere)
-    static const bool v2_env = [] { const char *e = getenv("MG_J2C_V2"); return !(e && e[0] == '0'); }();
+    // kernel at two waves per SIMD wins, 5.12 against 5.49 ms
     if constexpr (sizeof(T) == 4) {
-        if (v2_env && 2 * tpr <= 256) {
+        if (2 * tpr <= 256) {
             const int nby2 = (g.ny + 1) / 2, nbz2 = j2_nbz(g, 2 * tpr, 2);
             const int grid2 = (((dup > 0 ? 2 : 1) * nby2 * nbz2 + 7) / 8) * 8;
 #define MG_J2C2(TPR2) \

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include "mg_geom.h"
+#include "mg_switches.h"
 
 namespace mg {
 

@@ -1624,22 +1624,17 @@ void launch_rbgs_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int colo
 template <typename T>
 void launch_gs_lex(hipStream_t s, const Geom &g, const Coef<T> &c, int sweeps, T *u, const T *rhs)
 {
-    static const bool rows = [] { const char *e = getenv("MG_GS_ROWS"); return !(e && e[0] == '0'); }();
     if (g.dim == 3) hipLaunchKernelGGL((k_gs_lex<T, 3>), dim3(1), dim3(SWG), 0, s, g, c, sweeps, u, rhs);
-    else if (rows && g.ny <= SWG && g.nx >= 3 && g.ny >= 3) {  // one thread per row
-        static const int pf = [] { const char *e = getenv("MG_GS_PF"); return e ? atoi(e) : 4; }();
-        static const bool pairs = [] { const char *e = getenv("MG_GS_PAIR"); return !(e && e[0] == '0'); }();
+    else if (switches().gs_rows && g.ny <= SWG && g.nx >= 3 && g.ny >= 3) {  // one thread per row
+        constexpr int GS_PF = 4;   // diagonal steps the off-chain operands are fetched ahead (the kernels were tuned at 4; 8 and 16 could be selected and were never adopted)
+        const bool pairs = switches().gs_pair;
         const dim3 bl(((g.ny + 63) / 64) * 64);
         int left = sweeps;
         while (pairs && left >= 2) {  // two sweeps per wavefront pass
-            hipLaunchKernelGGL((k_gs_lex2d_rows_pair<T, 4>), dim3(1), bl, 0, s, g, c, u, rhs);
+            hipLaunchKernelGGL((k_gs_lex2d_rows_pair<T, GS_PF>), dim3(1), bl, 0, s, g, c, u, rhs);
             left -= 2;
         }
-        if (left > 0) {
-            if (pf == 16) hipLaunchKernelGGL((k_gs_lex2d_rows<T, 16>), dim3(1), bl, 0, s, g, c, left, u, rhs);
-            else if (pf == 8) hipLaunchKernelGGL((k_gs_lex2d_rows<T, 8>), dim3(1), bl, 0, s, g, c, left, u, rhs);
-            else hipLaunchKernelGGL((k_gs_lex2d_rows<T, 4>), dim3(1), bl, 0, s, g, c, left, u, rhs);
-        }
+        if (left > 0) hipLaunchKernelGGL((k_gs_lex2d_rows<T, GS_PF>), dim3(1), bl, 0, s, g, c, left, u, rhs);
     }
     else hipLaunchKernelGGL((k_gs_lex<T, 2>), dim3(1), dim3(SWG), 0, s, g, c, sweeps, u, rhs);
 }
@@ -1780,9 +1775,8 @@ static bool try_launch_coarse_jacobi_rows(hipStream_t s, const Geom &g, const Co
                                           const T *rhs, int maxit, double tol, int fixed, CoarseOut *d_out, int zero_x)
 {
     const size_t total = (size_t)g.nx * g.ny * g.nz;
-    // MG_COARSE_SKIP = sweeps between two norm tests (1 = test after every sweep, the plain loop)
-    static const int skip_env = [] { const char *e = getenv("MG_COARSE_SKIP"); return e ? atoi(e) : 8; }();
-    int skip = skip_env < 1 ? 1 : skip_env;
+    constexpr int COARSE_SKIP = 8;   // sweeps between two norm tests (1 = test after every sweep, the plain loop)
+    int skip = COARSE_SKIP;
     if (3 * total * sizeof(T) > (size_t)150 * 1024) skip = 1;   // no room for the window's first iterate
     // the windowed norm test equals the reference's test per sweep only while the residual norm cannot dip below the tolerance
     // and rise again inside a window: guaranteed for 0 < omega <= 1 (damped Jacobi on this operator is a contraction in the
@@ -1808,17 +1802,14 @@ template <typename T, int DIM>
 static bool try_launch_coarse_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, T omega, T *x, const T *rhs,
                                      int maxit, double tol, int fixed, CoarseOut *d_out, int zero_x)
 {
-    static const bool enabled = [] { const char *e = getenv("MG_COARSE_ROWS"); return !(e && e[0] == '0'); }();
-    if (!enabled || g.ny < 3 || (DIM == 3 && g.nz < 3)) return false;
+    if (!switches().coarse_rows || g.ny < 3 || (DIM == 3 && g.nz < 3)) return false;
     // run length, in measured order of preference (MI355X, one CU): 65^2 -> 8 (504 threads, two
     // waves per SIMD: 52 ms for BASELINE config 1 against 55 ms with 7 and 64 ms with 9);
     // 17^3 -> 5 (675 threads; 8 is 2 % slower per V-cycle at 513^3)
-    static const int pref = [] { const char *e = getenv("MG_COARSE_SEG"); return e ? atoi(e) : 0; }();
     const int W = g.nx - 2, irows = (g.ny - 2) * (DIM == 3 ? g.nz - 2 : 1);
-    const int order2[5] = {pref, 8, 4, 7, 5}, order3[5] = {pref, 5, 4, 8, 7};
+    const int order2[4] = {8, 4, 7, 5}, order3[4] = {5, 4, 8, 7};
     int best = 0;
     for (int seg : (DIM == 3 ? order3 : order2)) {
-        if (seg != 4 && seg != 5 && seg != 7 && seg != 8) continue;
         const int nseg = (W + seg - 1) / seg, threads = nseg * irows;
         if (W < seg || nseg * seg - W > 1 || threads < 128 || threads > (seg >= 7 ? 512 : SWG)) continue;
         best = seg;
@@ -1858,8 +1849,7 @@ template <typename T, int DIM>
 static bool try_launch_coarse_rb(hipStream_t s, const Geom &g, const Coef<T> &c, T *x, const T *rhs, int maxit, double tol,
                                  int fixed, CoarseOut *d_out, int zero_x)
 {
-    static const bool enabled = [] { const char *e = getenv("MG_COARSE_RB_ROWS"); return !(e && e[0] == '0'); }();
-    if (!enabled || g.ny < 3 || (DIM == 3 && g.nz < 3)) return false;
+    if (!switches().coarse_rb_rows || g.ny < 3 || (DIM == 3 && g.nz < 3)) return false;
     const int W = g.nx - 2, irows = (g.ny - 2) * (DIM == 3 ? g.nz - 2 : 1);
     for (int seg : {5, 4}) {   // (runs of 7 / 8 points: the colour selects went through scratch memory; not instantiated)
         const int nseg = (W + seg - 1) / seg, threads = nseg * irows;
@@ -1874,9 +1864,8 @@ template <typename T>
 static bool try_launch_coarse_gs_rows2d(hipStream_t s, const Geom &g, const Coef<T> &c, T *x, const T *rhs, int maxit,
                                         double tol, int fixed, CoarseOut *d_out)
 {
-    static const bool enabled = [] { const char *e = getenv("MG_COARSE_GS_ROWS"); return !(e && e[0] == '0'); }();
     const size_t bytes = 2 * (size_t)g.nx * g.ny * sizeof(T);
-    if (!enabled || g.dim != 2 || g.ny > CGS_THREADS || g.nx < 3 || g.ny < 3 || bytes > (size_t)150 * 1024) return false;
+    if (!switches().coarse_gs_rows || g.dim != 2 || g.ny > CGS_THREADS || g.nx < 3 || g.ny < 3 || bytes > (size_t)150 * 1024) return false;
     auto kern = k_coarse_gs_rows2d<T>;
     static bool attr_set = false;
     if (!attr_set) {

@@ -28,7 +28,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 namespace mg {
 namespace {
@@ -503,23 +502,18 @@ static WidePlan wide_plan(const Geom &g, int nby, int ncopy)
     static const int ncu = [] {
         int dev = 0, n = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        const char *e = getenv("MG_PW_GRID");
-        return std::max(8, ((e ? atoi(e) : n) / 8) * 8);
+        return std::max(8, (n / 8) * 8);
     }();
-    static const int mode = [] { const char *e = getenv("MG_PW_MODE"); return e ? atoi(e) : -1; }();   // 0 ranges, 1 chunks, -1 auto
-    static const int zc_env = [] { const char *e = getenv("MG_PW_ZC"); return e ? atoi(e) : 0; }();
+    const int zc_env = switches().pw_zc;
     const long long total = (long long)ncopy * nby * g.nz;
     const int grid = (int)std::max<long long>(8, (std::min<long long>(ncu, total / 3) / 8) * 8);
-    const double run = (double)total / grid, k = std::max(1.0, std::floor(g.nz / run + 0.5));
-    const bool aligned = std::fabs(k * run - g.nz) <= std::max(2.0, 0.012 * g.nz);
     // measured on one box, same process (tools/ab_modes.sh, 513^3 fp64, ms per launch ranges / chunks): plain pair 0.661 / 0.654,
     // folding pair 0.723 / 0.734, whole cycle 2.43 / 2.39; a slab piece alone on the chip (64 planes: 86 tiles x 2 chunks fill two
     // thirds of it, x 3 one workgroup more than it): 0.111 ms as chunks, 0.089 as ranges. Chunks are nevertheless the default
     // everywhere: a grid of exactly one workgroup per CU, each holding its CU for the whole launch, takes TWICE as long as soon
     // as anything else holds a CU -- RCCL's send / recv kernels, the boundary launch on the communication stream -- while
     // one-chunk workgroups are dispatched to whatever CUs are free. Ranges: MG_PW_MODE=0 (measurements on an otherwise idle GPU).
-    (void)aligned;
-    if (mode == 0) return {grid, 0};
+    if (switches().pw_mode == 0) return {grid, 0};
     // chunks: the count whose last round is fullest; a chunk of zc planes costs zc + 2 plane steps + the prologue
     int best_zc = std::max(1, g.nz);
     double best = 1e30;
@@ -547,11 +541,10 @@ template <typename T>
 bool pair_wide_ok(const Geom &g)
 {
     constexpr int V = WV<T>::V;
-    static const bool enabled = [] { const char *e = getenv("MG_PAIR_WIDE"); return !(e && e[0] == '0'); }();
-    if (g_wide_mode == 0 || (g_wide_mode < 0 && !enabled) || g.dim != 3 || (g.nx - 1) % V != 0) return false;
+    if (g_wide_mode == 0 || (g_wide_mode < 0 && !switches().pair_wide) || g.dim != 3 || (g.nx - 1) % V != 0) return false;
     const int tpr = (g.nx - 1) / V;
     if (tpr != 128 && tpr != 256) return false;
-    static const int min_rows = [] { const char *e = getenv("MG_PW_MIN_NY"); return e ? atoi(e) : 200; }();
+    constexpr int min_rows = 200;   // as rr_wide_ok: enough rows to fill 256 CUs with 1024-thread workgroups
     return g.ny >= min_rows && g.nz >= 8;   // (thin pieces -- the boundary planes of a slab -- stay with k_jacobi2: 17 against 28 us)
 }
 

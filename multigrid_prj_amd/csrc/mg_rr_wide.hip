@@ -23,7 +23,6 @@
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
-#include <cstdlib>
 
 namespace mg {
 namespace {
@@ -306,21 +305,15 @@ __global__ __launch_bounds__(TPR * G) void k_rrw(Geom gf, Geom gc, Coef<T> c, co
 struct RRPlan { int grid, zcc; };
 static RRPlan rr_wide_plan(const Geom &gc, int nby, int ncopy, bool semi)
 {
-    const bool piece = gc.gnz != gc.nz;   // a z-slab piece
     static const int ncu = [] {
         int dev = 0, n = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        const char *e = getenv("MG_RRW_GRID");
-        return std::max(8, ((e ? atoi(e) : n) / 8) * 8);
+        return std::max(8, (n / 8) * 8);
     }();
-    static const int mode = [] { const char *e = getenv("MG_RRW_MODE"); return e ? atoi(e) : -1; }();
-    static const int zcc_env = [] { const char *e = getenv("MG_RRW_ZCC"); return e ? atoi(e) : 0; }();
+    const int zcc_env = switches().rrw_zcc;
     const long long total = (long long)ncopy * nby * gc.nz;
     const int grid = (int)std::max<long long>(8, (std::min<long long>(ncu, total / 2) / 8) * 8);
-    const double run = (double)total / grid, k = std::max(1.0, std::floor(gc.nz / run + 0.5));
-    const bool aligned = std::fabs(k * run - gc.nz) <= std::max(1.0, 0.012 * gc.nz);
-    (void)aligned; (void)piece;
-    if (mode == 0) return {grid, 0};   // ranges only on request (mg_pair_wide.hip: wide_plan says why); whole level 0.543 against 0.525 ms as chunks
+    if (switches().rrw_mode == 0) return {grid, 0};   // ranges only on request (mg_pair_wide.hip: wide_plan says why); whole level 0.543 against 0.525 ms as chunks
     int best_zcc = std::max(1, gc.nz);
     double best = 1e30;
     for (int kk = 1; kk <= gc.nz; kk++) {
@@ -344,8 +337,7 @@ template <typename T>
 bool rr_wide_ok(const Geom &gf, const Geom &gc)
 {
     constexpr int V = RV<T>::V;
-    static const bool enabled = [] { const char *e = getenv("MG_RR_WIDE"); return !(e && e[0] == '0'); }();
-    if (g_rr_wide_mode == 0 || (g_rr_wide_mode < 0 && !enabled) || gf.dim != 3 || (gf.nx - 1) % V != 0 || gf.nx != 2 * gc.nx - 1 || gf.ny != 2 * gc.ny - 1) return false;
+    if (g_rr_wide_mode == 0 || (g_rr_wide_mode < 0 && !switches().rr_wide) || gf.dim != 3 || (gf.nx - 1) % V != 0 || gf.nx != 2 * gc.nx - 1 || gf.ny != 2 * gc.ny - 1) return false;
     const int tpr = (gf.nx - 1) / V;
     return (tpr == 128 || tpr == 256) && gf.ny >= 200 && gc.nz >= 4;   // (single coarse planes -- a slab's boundary pieces -- stay with k_resid_restrict_fw)
 }

@@ -12,7 +12,6 @@
 // (include/solvers.hpp:64-83), Residual (solvers.hpp:265-273), InterpolationClass::interpolate (src/multigrid.cpp:3-27).
 #include "mg_kernels.h"
 
-#include <cstdlib>
 
 namespace mg {
 namespace {
@@ -278,8 +277,7 @@ constexpr int SMALL_CB = 4;
 template <typename T>
 bool small_fused_ok(const Geom &gf, const Geom &gc)
 {
-    static const bool enabled = [] { const char *e = getenv("MG_SMALL_FUSED"); return !(e && e[0] == '0'); }();
-    return enabled && gf.dim == 3 && gc.dim == 3 && gf.gz0 == 0 && gf.gnz == gf.nz && gc.gz0 == 0 && gc.gnz == gc.nz &&
+    return switches().small_fused && gf.dim == 3 && gc.dim == 3 && gf.gz0 == 0 && gf.gnz == gf.nz && gc.gz0 == 0 && gc.gnz == gc.nz &&
            gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 && gf.nz == 2 * gc.nz - 1 && gc.nx >= 3 && gc.ny >= 3 && gc.nz >= 3 &&
            (long long)gf.nx * gf.ny * gf.nz <= 129LL * 129 * 129;
 }

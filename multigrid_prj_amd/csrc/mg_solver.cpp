@@ -204,6 +204,7 @@ int Solver::init()
     if (device_ < 0) MG_HIP(hipGetDevice(&device_));
     if (device_ >= ndev) { set_last_error("device index out of range"); return MG_ERR_BAD_ARG; }
     MG_HIP(hipSetDevice(device_));
+    sw_ = HandleSwitches();
     MG_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     MG_HIP(hipEventCreate(&ev0_));
     MG_HIP(hipEventCreate(&ev1_));
@@ -212,15 +213,12 @@ int Solver::init()
         // the communication stream outranks the main one: the exchange kernels and the boundary pieces behind them are
         // dispatched ahead of the interior launch they run beside (MG_COMM_PRIORITY=0: same priority)
         int prio_least = 0, prio_greatest = 0;
-        const char *pe = getenv("MG_COMM_PRIORITY");
-        if (!(pe && pe[0] == '0') && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) == hipSuccess && prio_greatest != prio_least)
+        if (sw_.comm_priority && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) == hipSuccess && prio_greatest != prio_least)
             MG_HIP(hipStreamCreateWithPriority(&comm_stream_, hipStreamNonBlocking, prio_greatest));
         else
             MG_HIP(hipStreamCreateWithFlags(&comm_stream_, hipStreamNonBlocking));
         MG_HIP(hipEventCreateWithFlags(&ev_ready_, hipEventDisableTiming));
         MG_HIP(hipEventCreateWithFlags(&ev_halo_, hipEventDisableTiming));
-        const char *ov = getenv("MG_OVERLAP");
-        overlap_ = !(ov && ov[0] == '0');
     }
 
     const int epl = (int)(128 / esize());  // elements per 128-byte line
@@ -245,8 +243,7 @@ int Solver::init()
             // Gathered levels: by default EVERY rank holds them and runs them redundantly (same bits everywhere) after an
             // all-gather of the restricted right-hand side -- nobody waits for rank 0 to scatter the correction back, and
             // rank 0 is no longer the one rank with more work. MG_REPLICATE_TAIL=0: rank 0 alone, gather + scatter.
-            replicate_ = [] { const char *e = getenv("MG_REPLICATE_TAIL"); return !(e && e[0] == '0'); }();
-            L.present = L.dist || rank_ == 0 || replicate_;
+            L.present = L.dist || rank_ == 0 || sw_.replicate_tail;
             if (L.dist) {
                 if (l == T_ && rank_ == 0 && T_ == d_.levels - 1) {  // coarsest level still distributed: rank 0 solves it gathered
                     gfull_ = L.g;
@@ -289,15 +286,11 @@ int Solver::init()
             }
         }
         if (!L.dist) L.nz_min = L.g.nz;
-        {
-            // Interior / boundary split with the exchange on the communication stream: two cross-stream waits (6-20 us each on
-            // this chip) and a boundary launch per operation. It pays while the interior launch is longer than the exchange;
-            // on a slab of a few MB (257^3 on 8 ranks: 17 MB per array, interior pair 20 us, halo 1 MB per neighbour) it does
-            // not, and exchange-then-one-launch takes the same time with free communication 13-20 us less per operation.
-            const char *e = getenv("MG_OVERLAP_MIN_MB");   // read per handle (tests switch it between handles of one process)
-            const double min_mb = e ? atof(e) : 32.0;
-            L.overlap = overlap_ && L.dist && (double)L.nz_min * (double)L.g.plane * (double)esize() >= min_mb * 1048576.0;
-        }
+        // Interior / boundary split with the exchange on the communication stream: two cross-stream waits (6-20 us each on
+        // this chip) and a boundary launch per operation. It pays while the interior launch is longer than the exchange;
+        // on a slab of a few MB (257^3 on 8 ranks: 17 MB per array, interior pair 20 us, halo 1 MB per neighbour) it does
+        // not, and exchange-then-one-launch takes the same time with free communication 13-20 us less per operation.
+        L.overlap = sw_.overlap && L.dist && (double)L.nz_min * (double)L.g.plane * (double)esize() >= sw_.overlap_min_mb * 1048576.0;
         L.gh = L.dist ? 2 : 1;
         L.alloc_elems = (size_t)(L.g.nz + 2 * L.gh) * (size_t)L.g.plane;
         if (!L.present) continue;
@@ -383,8 +376,7 @@ void parallel_rows(size_t nrows, int nthreads, F &&fn)
 int stage_threads()
 {
     static const int n = [] {
-        const char *e = getenv("MG_STAGE_THREADS");
-        if (e) return std::max(1, atoi(e));
+        if (switches().stage_threads != -1) return std::max(1, switches().stage_threads);
         const unsigned hc = std::thread::hardware_concurrency();
         return (int)std::max(1u, std::min(8u, hc ? hc / 2 : 4u));
     }();
@@ -546,15 +538,6 @@ int Solver::halo_work_done()
     return MG_OK;
 }
 
-// The boundary pieces of a slab operation (the planes that need the halo) run on the COMMUNICATION stream, right behind
-// the exchange, while the interior piece runs on the main stream: measured on one rank's schedule (tools/dry_ranks.sh) the
-// boundary launch after the interior one cost 14-18 us plus a cross-stream wait per operation, five operations per cycle.
-static bool boundary_on_comm_stream()
-{
-    static const bool e = [] { const char *v = getenv("MG_BOUNDARY_ON_COMM"); return !(v && v[0] == '0'); }();
-    return e;
-}
-
 int Solver::exchange_end()
 {
     MG_HIP(hipStreamWaitEvent(stream_, ev_halo_, 0));
@@ -589,7 +572,7 @@ int Solver::gather_S(int arr)
     const size_t pb = (size_t)stage_g_.plane * esize();
     char *sb = reinterpret_cast<char *>(stage_base_[0]);
     int rc;
-    if (replicate_) {  // all-gather: my staging slab to everybody, everybody's into my full copy of the level
+    if (sw_.replicate_tail) {  // all-gather: my staging slab to everybody, everybody's into my full copy of the level
         char *f = reinterpret_cast<char *>(L.base[arr]);
         MG_HIP(hipMemcpyAsync(f + (size_t)(1 + planS_[rank_].z0) * pb, sb + pb, (size_t)stage_g_.nz * pb, hipMemcpyDeviceToDevice, stream_));
         std::vector<P2POp> ops;
@@ -625,7 +608,7 @@ int Solver::scatter_S(int arr)
     char *sb = reinterpret_cast<char *>(stage_base_[1]);
     auto planes = [&](int r) { return (size_t)planS_[r].nz + (r < nranks_ - 1 ? 1 : 0); };
     int rc;
-    if (replicate_) {  // every rank computed the level: its own planes (+ the upper ghost) are a local copy away
+    if (sw_.replicate_tail) {  // every rank computed the level: its own planes (+ the upper ghost) are a local copy away
         char *f = reinterpret_cast<char *>(L.base[arr]);
         MG_HIP(hipMemcpyAsync(sb + pb, f + (size_t)(1 + planS_[rank_].z0) * pb, planes(rank_) * pb, hipMemcpyDeviceToDevice, stream_));
         return MG_OK;
@@ -700,9 +683,8 @@ int Solver::allreduce(double *dptr, int n)
 template <typename T>
 static Coef<T> coef_of(const Level &L)
 {
-    static const bool fast_div = [] { const char *e = getenv("MG_FAST_DIV"); return !(e && e[0] == '0'); }();
     Coef<T> c = make_coef<T>(L.coef[0], L.coef[1], L.coef[2], L.coef[3]);
-    if (!fast_div) c.win = 0;  // A/B switch: hardware division everywhere
+    if (!switches().fast_div) c.win = 0;  // A/B switch: hardware division everywhere
     return c;
 }
 
@@ -713,22 +695,27 @@ bool Solver::can_skip_zeroing(int level) const
     if (d_.nu_pre <= 0 || level >= d_.levels - 1) return false;
     if (d_.smoother == MG_SMOOTH_JACOBI) return fast_path_ok<T>(lv_[level].g);
     // red-black: the one-pass sweep of an undistributed level (smooth_t takes exactly this branch for it)
-    static const bool rb_zero = [] { const char *e = getenv("MG_RB_ZERO_GUESS"); return !(e && e[0] == '0'); }();
-    return rb_zero && d_.smoother == MG_SMOOTH_RBGS && !lv_[level].dist && rb_fused_ok<T>(lv_[level].g);
+    return d_.smoother == MG_SMOOTH_RBGS && !lv_[level].dist && rb_fused_ok<T>(lv_[level].g);
 }
 
-// true when the V-cycle's prolong-add into `level` can be folded into the first post-smoothing pair
-// (k_jacobi2<CORR>): out = J(J(u + P e)) without ever storing u + P e
-static Geom slab_gate_geom(const Level &L);
-static bool depth2_enabled();
+// Every decision that changes WHICH messages a rank posts must come out the same on all ranks: the gates that look at
+// the slab's thickness are evaluated on the thinnest slab of the level, not on the local one (the last rank owns one
+// plane more, uneven splits differ by a coarse cell).
+static Geom slab_gate_geom(const Level &L)
+{
+    Geom g = L.g;
+    g.nz = L.nz_min;
+    return g;
+}
 
-// the same on two consecutive distributed levels (Jacobi, two ghost planes): every piece of the slab pair folds P e in
+// The three gates of the folded prolongation: the V-cycle's prolong-add into `level` goes into the first post-smoothing pair
+// (k_jacobi2<CORR>), out = J(J(u + P e)) without ever storing u + P e.
+// On two consecutive distributed levels (Jacobi, two ghost planes): every piece of the slab pair folds P e in
 template <typename T>
 bool Solver::can_fold_prolong_slab(int level) const
 {
-    static const bool enabled = [] { const char *e = getenv("MG_FUSED_PROLONG"); return !(e && e[0] == '0'); }();
-    if (!enabled || level + 1 >= d_.levels || !lv_[level].dist || !lv_[level + 1].dist) return false;
-    if (d_.smoother != MG_SMOOTH_JACOBI || d_.nu_post < 2 || !depth2_enabled() || lv_[level + 1].gh < 2 || lv_[level + 1].nz_min < 2) return false;
+    if (!switches().fused_prolong || level + 1 >= d_.levels || !lv_[level].dist || !lv_[level + 1].dist) return false;
+    if (d_.smoother != MG_SMOOTH_JACOBI || d_.nu_post < 2 || !switches().depth2 || lv_[level + 1].gh < 2 || lv_[level + 1].nz_min < 2) return false;
     // the same answer on every rank: the gate looks at the thinnest slabs, whose z-relation holds like everybody's
     Geom gf = slab_gate_geom(lv_[level]), gc = slab_gate_geom(lv_[level + 1]);
     gf.nz = 2 * gc.nz;
@@ -742,12 +729,8 @@ bool Solver::can_fold_prolong_slab(int level) const
 template <typename T>
 bool Solver::can_fold_prolong_replicated(int level) const
 {
-    static const bool enabled = [] {
-        const char *e = getenv("MG_FUSED_PROLONG"), *r = getenv("MG_FUSED_PROLONG_REPLICATED");
-        return !(e && e[0] == '0') && !(r && r[0] == '0');
-    }();
-    if (!enabled || !replicate_ || level + 1 >= d_.levels || !lv_[level].dist || lv_[level + 1].dist || !lv_[level + 1].present) return false;
-    if (d_.smoother != MG_SMOOTH_JACOBI || d_.nu_post < 2 || !depth2_enabled()) return false;
+    if (!switches().fused_prolong || !switches().fused_prolong_replicated || !sw_.replicate_tail || level + 1 >= d_.levels || !lv_[level].dist || lv_[level + 1].dist || !lv_[level + 1].present) return false;
+    if (d_.smoother != MG_SMOOTH_JACOBI || d_.nu_post < 2 || !switches().depth2) return false;
     const Geom &gf = lv_[level].g, &gc = lv_[level + 1].g;
     return jacobi2_slab_ok<T>(slab_gate_geom(lv_[level])) && gc.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 &&
            gf.gnz == 2 * gc.gnz - 1 && gc.gz0 == 0 && gc.gnz == gc.nz && lv_[level].nz_min >= 4;
@@ -756,18 +739,11 @@ bool Solver::can_fold_prolong_replicated(int level) const
 template <typename T>
 bool Solver::can_fold_prolong(int level) const
 {
-    static const bool enabled = [] { const char *e = getenv("MG_FUSED_PROLONG"); return !(e && e[0] == '0'); }();
     const bool sm = (d_.smoother == MG_SMOOTH_JACOBI && d_.nu_post >= 2) ||
                     (d_.smoother == MG_SMOOTH_RBGS && d_.nu_post >= 1 && rb_fused_ok<T>(lv_[level].g));
-    return enabled && sm && level + 1 < d_.levels &&
+    return switches().fused_prolong && sm && level + 1 < d_.levels &&
            lv_[level].present && !lv_[level].dist && lv_[level + 1].present && !lv_[level + 1].dist &&
            jacobi2_corr_ok<T>(lv_[level].g, lv_[level + 1].g);
-}
-
-static bool rb_slab_enabled()
-{
-    static const bool e = [] { const char *v = getenv("MG_FUSED_RB"); return !(v && v[0] == '0'); }();
-    return e;
 }
 
 // Two Jacobi sweeps (or, rb, the two colour passes of one red-black sweep) of U on a z-slab with the fused kernel (depth-1 ghost planes are enough):
@@ -814,22 +790,6 @@ int Solver::pair_on_slab_t(int level, bool rb)
     return MG_OK;
 }
 
-// Every decision that changes WHICH messages a rank posts must come out the same on all ranks: the gates that look at
-// the slab's thickness are evaluated on the thinnest slab of the level, not on the local one (the last rank owns one
-// plane more, uneven splits differ by a coarse cell).
-static Geom slab_gate_geom(const Level &L)
-{
-    Geom g = L.g;
-    g.nz = L.nz_min;
-    return g;
-}
-
-static bool depth2_enabled()
-{
-    static const bool e = [] { const char *v = getenv("MG_DEPTH2"); return !(v && v[0] == '0'); }();
-    return e;
-}
-
 int Solver::refresh_rhs_halo(int level)
 {
     Level &L = lv_[level];
@@ -867,9 +827,7 @@ int Solver::pair_on_slab2_t(int level, bool rb, int corr_level, bool u_halo_ok, 
         else if (rb) launch_rb_fused<T>(st, gs, c, px + off, pr + off, pt + off, (const T *)nullptr, gs, dup);
         else launch_jacobi2<T>(st, gs, c, om, px + off, pr + off, pt + off, false, dup);
     };
-    static const bool one_boundary_launch = [] { const char *e = getenv("MG_MERGE_BOUNDARY"); return !(e && e[0] == '0'); }();
     MG_TRY(refresh_rhs_halo(level));
-    static const bool reuse_halo = [] { const char *e = getenv("MG_REUSE_HALO"); return !(e && e[0] == '0'); }();
     if (norm_partials && !pe) {
         // Solver::solve's speculative pair: the whole slab in ONE wide-tile launch that also sums (rhs - A u)^2 of its input over
         // the owned planes (no interior / boundary split: the thin boundary pieces have no norm variant; the separate residual
@@ -878,13 +836,16 @@ int Solver::pair_on_slab2_t(int level, bool rb, int corr_level, bool u_halo_ok, 
         const int np = rb ? launch_rb_fused<T>(stream_, g, c, px, pr, pt, (const T *)nullptr, g, 0, false, norm_partials)
                           : launch_jacobi2<T>(stream_, g, c, om, px, pr, pt, false, 0, norm_partials);
         if (norm_np) *norm_np = np;
-    } else if (u_halo_ok && reuse_halo) {
+    } else if (u_halo_ok && switches().reuse_halo) {
         fused(g, 0);
     } else if (!L.overlap || g.nz < 8) {
         MG_TRY(exchange(MG_ARR_U, level, 2));
         fused(g, 0);
     } else {
-        const bool on_comm = one_boundary_launch && boundary_on_comm_stream();
+        // The boundary pieces (the planes that need the halo) run on the COMMUNICATION stream, right behind the exchange, while
+        // the interior piece runs on the main stream: measured on one rank's schedule (tools/dry_ranks.sh) the boundary launch
+        // after the interior one cost 14-18 us plus a cross-stream wait per operation, five operations per cycle.
+        const bool on_comm = switches().boundary_on_comm;
         MG_TRY(exchange_begin(MG_ARR_U, level, 2, !on_comm));
         Geom gi = g; gi.nz = g.nz - 4; gi.gz0 = g.gz0 + 2;     // reads u on planes 0 .. nz-1 only
         Geom glo = g; glo.nz = 2;
@@ -895,14 +856,7 @@ int Solver::pair_on_slab2_t(int level, bool rb, int corr_level, bool u_halo_ok, 
         }
         fused(gi, 2 * pl);
         MG_TRY(exchange_end());
-        if (on_comm) {
-        } else if (one_boundary_launch) {    // output planes 0, 1 and nz-2, nz-1 in ONE launch (two were 2 x 15 us at 513^2)
-            fused(glo, 0, g.nz - 2);
-        } else {
-            fused(glo, 0);
-            Geom ghi = g; ghi.nz = 2; ghi.gz0 = g.gz0 + g.nz - 2;
-            fused(ghi, (long long)(g.nz - 2) * pl);
-        }
+        if (!on_comm) fused(glo, 0, g.nz - 2);   // output planes 0, 1 and nz-2, nz-1 in ONE launch (two were 2 x 15 us at 513^2)
     }
     MG_HIP(hipGetLastError());
     std::swap(L.base[MG_ARR_U], L.base[MG_ARR_TMP]);
@@ -928,10 +882,8 @@ int Solver::resid_restrict_on_slab_t(int level, const Geom &gc, T *coarse_rhs)
         launch_resid_restrict_fw<T>(stream_, gf, gc, c, pu, pr, coarse_rhs);
     } else {
         // coarse planes 1 .. nzc-2 read u on owned planes only: they run while the halo moves
-        static const bool one_boundary_launch = [] { const char *e = getenv("MG_MERGE_BOUNDARY"); return !(e && e[0] == '0'); }();
-        const bool on_comm = one_boundary_launch && boundary_on_comm_stream();
-        static const bool early = [] { const char *e = getenv("MG_EARLY_EXCHANGE"); return !(e && e[0] == '0'); }();
-        if (on_comm && early && pair_level == level) {
+        const bool on_comm = switches().boundary_on_comm;
+        if (on_comm && switches().early_exchange && pair_level == level) {
             // The planes to send (0, 1, nz-2, nz-1 of the pair's output) were written by the pair's boundary piece on the
             // communication stream itself: the exchange starts at once, while the pair's interior launch is still running on
             // the main stream; only the boundary piece below needs that launch's planes.
@@ -956,16 +908,8 @@ int Solver::resid_restrict_on_slab_t(int level, const Geom &gc, T *coarse_rhs)
         Geom gfi = gf; gfi.nz = 2 * gci.nz; gfi.gz0 = gf.gz0 + 2;
         launch_resid_restrict_fw<T>(stream_, gfi, gci, c, pu + 2 * gf.plane, pr + 2 * gf.plane, coarse_rhs + gc.plane);
         MG_TRY(exchange_end());
-        if (on_comm) {
-        } else if (one_boundary_launch) {         // first and last coarse plane in ONE launch
+        if (!on_comm)                             // first and last coarse plane in ONE launch
             launch_resid_restrict_fw<T>(stream_, gf0, gc0, c, pu, pr, coarse_rhs, kl, gf.nz - 2 * kl);
-        } else {
-            launch_resid_restrict_fw<T>(stream_, gf0, gc0, c, pu, pr, coarse_rhs);
-            Geom gc1 = gc; gc1.nz = 1; gc1.gz0 = gc.gz0 + kl;
-            Geom gf1 = gf; gf1.nz = gf.nz - 2 * kl; gf1.gz0 = gf.gz0 + 2 * kl;
-            launch_resid_restrict_fw<T>(stream_, gf1, gc1, c, pu + (long long)2 * kl * gf.plane, pr + (long long)2 * kl * gf.plane,
-                                        coarse_rhs + (long long)kl * gc.plane);
-        }
     }
     MG_HIP(hipGetLastError());
     return MG_OK;
@@ -989,7 +933,7 @@ int Solver::smooth_t(int level, int smoother, int sweeps, int ax, int ar, bool x
     case MG_SMOOTH_JACOBI:
         for (int s = 0; s < sweeps; s++) {
             pair_on_comm_level_ = -1;
-            if (L.dist && depth2_enabled() && ax == MG_ARR_U && ar == MG_ARR_RHS && s + 1 < sweeps && jacobi2_slab_ok<T>(slab_gate_geom(L))) {
+            if (L.dist && switches().depth2 && ax == MG_ARR_U && ar == MG_ARR_RHS && s + 1 < sweeps && jacobi2_slab_ok<T>(slab_gate_geom(L))) {
                 if (x_zero && s == 0) {  // zero guess on every rank: no halo of u to fetch at all, only the neighbours' rhs planes
                     MG_TRY(refresh_rhs_halo(level));
                     launch_jacobi2<T>(stream_, L.g, c, (T)d_.omega, ptr<T>(ax, level), ptr<T>(ar, level), ptr<T>(MG_ARR_TMP, level), true);
@@ -1021,12 +965,11 @@ int Solver::smooth_t(int level, int smoother, int sweeps, int ax, int ar, bool x
                 else {  // x_zero: the pair starts from an implicit zero guess (nothing is read for x)
                     // The variant of the wide-tile pair that also sums (rhs - A u)^2 costs 1.5 % over the plain one (0.636 against 0.626 ms
                     // at 513^3, alternating bench runs on one box): level 0's pre-smoothing pair takes it when the outer loop asks
-                    // for the norm (MG_ALWAYS_NORM=1: always, as in the first half of round 3 when it was the faster of the two).
-                    static const bool always_norm = [] { const char *e = getenv("MG_ALWAYS_NORM"); return e && e[0] == '1'; }();
-                    const bool norm = (want_pair_norm_ || always_norm) && level == 0 && s == 0 && !x_zero && ax == MG_ARR_U && ar == MG_ARR_RHS;
+                    // for the norm.
+                    const bool norm = want_pair_norm_ && level == 0 && s == 0 && !x_zero && ax == MG_ARR_U && ar == MG_ARR_RHS;
                     const int np = launch_jacobi2<T>(stream_, L.g, c, (T)d_.omega, ptr<T>(ax, level), ptr<T>(ar, level),
                                                      ptr<T>(MG_ARR_TMP, level), x_zero && s == 0, 0, norm ? d_partials_ : (double *)nullptr);
-                    if (norm && np > 0 && want_pair_norm_) {   // sum r^2 of the pair's input -> d_scal_[0]
+                    if (norm && np > 0) {   // sum r^2 of the pair's input -> d_scal_[0]
                         launch_reduce_final(stream_, d_partials_, np, d_scal_);
                         pair_norm_done_ = true;
                     }
@@ -1052,7 +995,7 @@ int Solver::smooth_t(int level, int smoother, int sweeps, int ax, int ar, bool x
     case MG_SMOOTH_RBGS:
         for (int s = 0; s < sweeps; s++) {
             pair_on_comm_level_ = -1;
-            if (L.dist && depth2_enabled() && ax == MG_ARR_U && ar == MG_ARR_RHS && jacobi2_slab_ok<T>(slab_gate_geom(L)) && rb_slab_enabled()) {
+            if (L.dist && switches().depth2 && ax == MG_ARR_U && ar == MG_ARR_RHS && jacobi2_slab_ok<T>(slab_gate_geom(L)) && switches().fused_rb) {
                 const bool norm = want_pair_norm_ && level == 0 && s == 0 && corr_level < 0;
                 int np = 0;
                 MG_TRY(pair_on_slab2_t<T>(level, true, -1, false, norm ? d_partials_ : (double *)nullptr, &np));   // one-pass red-black sweep on the whole slab, two ghost planes
@@ -1065,7 +1008,7 @@ int Solver::smooth_t(int level, int smoother, int sweeps, int ax, int ar, bool x
                 continue;
             }
             if (L.dist && L.overlap && e_scratch && ax == MG_ARR_U && ar == MG_ARR_RHS &&
-                jacobi2_slab_ok<T>(slab_gate_geom(L)) && rb_slab_enabled()) {  // one-pass red-black sweep on the slab's inner planes
+                jacobi2_slab_ok<T>(slab_gate_geom(L)) && switches().fused_rb) {  // one-pass red-black sweep on the slab's inner planes
                 MG_TRY(pair_on_slab_t<T>(level, true));
                 launches += 1;
                 continue;
@@ -1395,16 +1338,14 @@ int Solver::vcycle_rec_t(int l, bool u_zero)
                          resid_restrict_fast_ok<T>(lv_[l].g, lv_[l + 1].g);
     // distributed level: the coarse slab is the next level's, or the staging slab when the next level is gathered
     const Geom &gc_slab = lv_[l + 1].dist ? lv_[l + 1].g : stage_g_;
-    const bool fuse_rr_slab = mine && lv_[l].dist && d_.restriction == MG_RESTRICT_FULLW && depth2_enabled() &&
+    const bool fuse_rr_slab = mine && lv_[l].dist && d_.restriction == MG_RESTRICT_FULLW && switches().depth2 &&
                               resid_restrict_slab_ok<T>(lv_[l].g, gc_slab);
     const bool prof = profiling_ && l == 0 && mine;
     // launch-bound levels (65^3 and below; rows too narrow for the fused pair): V(2,2) Jacobi with full weighting runs as ONE
     // launch either side of the coarser levels -- J(J(0)) + residual + restriction, and J(J(u + P e)) (mg_small_levels.hip)
-    // levels up to this size take the brick kernels even where the row-wide fused pair would run (MG_SMALL_MAX_N)
-    static const int small_max_n = [] { const char *e = getenv("MG_SMALL_MAX_N"); return e ? atoi(e) : 0; }();
     const bool small = mine && !prof && !stage_fn_ && !lv_[l].dist && lv_[l + 1].present && !lv_[l + 1].dist &&
                        d_.smoother == MG_SMOOTH_JACOBI && d_.nu_pre == 2 && d_.nu_post == 2 && d_.restriction == MG_RESTRICT_FULLW &&
-                       (!jacobi2_ok<T>(lv_[l].g) || lv_[l].g.nx <= small_max_n) && small_fused_ok<T>(lv_[l].g, lv_[l + 1].g);
+                       !jacobi2_ok<T>(lv_[l].g) && small_fused_ok<T>(lv_[l].g, lv_[l + 1].g);
     const bool small_pre = small && u_zero;   // the zero guess is part of the fused kernel's contract
     if (small_pre) {
         lv_[l + 1].rhs_halo_ok = false;
@@ -1569,14 +1510,12 @@ int Solver::cycle_async(int count)
 template <typename T>
 bool Solver::pair_norm_ok() const
 {
-    static const bool enabled = [] { const char *e = getenv("MG_PAIR_NORM"); return !(e && e[0] == '0'); }();
     const Level &L = lv_[0];
-    if (!enabled || d_.cycle != MG_CYCLE_V || d_.levels <= 1 || d_.outer_pre_gs != 0 || stage_fn_ || profiling_ || !L.present) return false;
+    if (!switches().pair_norm || d_.cycle != MG_CYCLE_V || d_.levels <= 1 || d_.outer_pre_gs != 0 || stage_fn_ || profiling_ || !L.present) return false;
     if (L.dist) {   // z-slabs: the Jacobi pair on the whole slab (two ghost planes), wide enough on the thinnest slab of all ranks
-        static const bool slab_enabled = [] { const char *e = getenv("MG_PAIR_NORM_SLAB"); return !(e && e[0] == '0'); }();
         const Geom gs = slab_gate_geom(L);
-        const bool sm = (d_.smoother == MG_SMOOTH_JACOBI && d_.nu_pre == 2) || (d_.smoother == MG_SMOOTH_RBGS && d_.nu_pre >= 1 && rb_slab_enabled());
-        return slab_enabled && sm && depth2_enabled() && jacobi2_slab_ok<T>(gs) && pair_wide_ok<T>(gs);
+        const bool sm = (d_.smoother == MG_SMOOTH_JACOBI && d_.nu_pre == 2) || (d_.smoother == MG_SMOOTH_RBGS && d_.nu_pre >= 1 && switches().fused_rb);
+        return sm && switches().depth2 && jacobi2_slab_ok<T>(gs) && pair_wide_ok<T>(gs);
     }
     const bool sm = (d_.smoother == MG_SMOOTH_JACOBI && d_.nu_pre == 2 && jacobi2_ok<T>(L.g)) ||
                     (d_.smoother == MG_SMOOTH_RBGS && d_.nu_pre >= 1 && rb_fused_ok<T>(L.g));   // red-black: the first sweep carries it

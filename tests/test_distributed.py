@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle as po
+from tests.switch_table import fallbacks
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
@@ -296,6 +297,60 @@ def test_hip_distributed_prolongation_fold_on_slabs(world, n, levels, dtype, tmp
             s.cycle()
         s.solve(0.0, 2)
         assert np.array_equal(res["1"][0], s.get_solution())
+
+
+# FALLBACK rows of mg_switches.def that live in the slab schedule, with the gate each reaches on two ranks of 257^3 over
+# three distributed levels (257^3, 129^3, 65^3: slabs of 128 / 64 / 32 planes) under MG_OVERLAP_MIN_MB=0, and how the
+# message groups per cycle move against the default ("=": the same messages, other streams or launches)
+SLAB_FALLBACKS = {
+    "MG_OVERLAP": "=",            # Level::overlap: exchange, then ONE launch per operation
+    "MG_BOUNDARY_ON_COMM": "=",   # pair_on_slab2_t / resid_restrict_on_slab_t: boundary pieces on the main stream after the interior
+    "MG_EARLY_EXCHANGE": "=",     # resid_restrict_on_slab_t: the exchange behind a pair waits for the main stream
+    "MG_REUSE_HALO": ">",         # pair_on_slab2_t: the folding pair exchanges u once more
+    "MG_DEPTH2": ">",             # smooth_t: one ghost plane, an exchange per sweep of a pair
+    "MG_FUSED_SLAB": ">",         # jacobi2_slab_ok: exchanged single sweeps
+    "MG_FUSED_PAIR": ">",         # jacobi2_slab_ok reads it too: the same on slabs, single sweeps on the gathered levels
+    "MG_FUSED_PROLONG": ">",      # can_fold_prolong_slab: separate prolongation; the pair behind it finds u changed and exchanges it again
+    "MG_FUSED_PROLONG_SLAB": None, "MG_FUSED_PROLONG_REPLICATED": None, "MG_REPLICATE_TAIL": None,   # (cases of their own below)
+}
+
+
+@pytest.fixture(scope="module")
+def slab_default(tmp_path_factory):
+    """the default schedule of that case, one GPU and the oracle: computed once for all switches"""
+    from multigrid_prj_amd import capi
+    tmp = tmp_path_factory.mktemp("slab_default")
+    case, desc, b = _case(tmp, 257, 5, 1, cycles=3)
+    desc["dist_min_n"] = 65
+    case["desc"] = desc
+    u, hists, fg = _run_ranks("hip", 2, case, tmp)
+    assert fg >= 2
+    groups = [float(p["groups_per_cycle"]) for p in _run_ranks.last_parts]
+    with capi.Solver(capi.make_desc(**desc)) as s:
+        s.set_rhs(b)
+        for _ in range(case["cycles"]):
+            s.cycle()
+        s.solve(0.0, 2)
+        assert np.array_equal(u, s.get_solution())
+    u_ref, _ = _oracle(desc, b, case["cycles"])
+    assert np.array_equal(u, u_ref)
+    return case, u, groups
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("var", fallbacks(*[v for v, how in SLAB_FALLBACKS.items() if how]))
+def test_hip_distributed_fallback_switches_keep_the_bits(var, slab_default, tmp_path):
+    """Every slab-schedule switch at 0: same bits as the default schedule (which equals one GPU and the oracle), and the
+    message groups per cycle move the way the switch says."""
+    case, u_default, groups_default = slab_default
+    u, hists, fg = _run_ranks("hip", 2, case, tmp_path, extra_env={var: "0"})
+    groups = [float(p["groups_per_cycle"]) for p in _run_ranks.last_parts]
+    print(var, "= 0: message groups per cycle", groups, "default", groups_default)
+    assert np.array_equal(u, u_default)
+    if SLAB_FALLBACKS[var] == ">":
+        assert all(g > d for g, d in zip(groups, groups_default)), (groups, groups_default)
+    else:
+        assert groups == groups_default, (groups, groups_default)
 
 
 @pytest.mark.gpu

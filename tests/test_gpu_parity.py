@@ -15,6 +15,7 @@ import pytest
 
 from multigrid_prj_amd import capi
 from oracle import pyoracle as po
+from tests.switch_table import fallbacks
 
 pytestmark = pytest.mark.gpu
 
@@ -407,6 +408,28 @@ def test_wide_tile_kernels_dealt_as_balanced_ranges_keep_the_bits(n, dtype, smoo
     p = subprocess.run([sys.executable, "-c", _RANGES_SCRIPT, root, str(n), str(dtype), str(smoother)], env=env, cwd=root,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "ranges ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+
+
+# FALLBACK rows of mg_switches.def whose gates only 2-D Gauss-Seidel reaches (launch_gs_lex: the row wavefront and its
+# two-sweep pass on levels of <= 1024 rows; launch_coarse_solve: k_coarse_gs_rows2d on <= 256 rows), with the bit-exact tests
+# of this file that go through them: -k expressions of a child pytest run with the switch at 0
+GS_2D_FALLBACKS = {
+    "MG_GS_ROWS": "test_smoothers_bit_exact and 2d-n33-L3-f64",
+    "MG_GS_PAIR": "test_smoothers_bit_exact and 2d-n33-L3-f64",
+    "MG_COARSE_GS_ROWS": "test_coarse_solver and 2d-n33-L3-f64",
+}
+
+
+@pytest.mark.parametrize("var", fallbacks(*GS_2D_FALLBACKS))
+def test_2d_gauss_seidel_fallbacks_keep_the_bits(var):
+    """The switch is read once per process: a child pytest process repeats the oracle comparison with the generic kernel."""
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider", os.path.abspath(__file__),
+                        "-k", GS_2D_FALLBACKS[var]], env=dict(os.environ, **{var: "0"}), cwd=root, capture_output=True,
+                       text=True, timeout=600)
+    assert p.returncode == 0 and " passed" in p.stdout and "failed" not in p.stdout, p.stdout[-4000:] + p.stderr[-2000:]
 
 
 def test_config4_as_worded_1025_fp32_seven_level_vcycles_bit_exact():

@@ -26,6 +26,7 @@ import pytest
 
 from oracle import pyoracle as po
 from tests import npref as npr
+from tests.switch_table import fallbacks
 
 LD = np.longdouble
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -423,7 +424,7 @@ OP_ROWS = [
     dict(id="f64-131", gate="jacobi2_ok: no (65 vectors), fast_path_ok: yes; prolong_fast_ok: yes", n=131,
          dtype=po.MG_F64, omega=1.0, xfer=True),
     dict(id="f64-257", gate="pair_wide_ok: yes (128 lanes)", n=257, dtype=po.MG_F64, omega=6 / 7, xfer=True,
-         fallback="MG_PAIR_WIDE"),
+         fallback=fallbacks("MG_PAIR_WIDE")[0]),
     dict(id="f64-385", gate="jacobi2_ok: yes (192 vectors), pair_wide_ok: no", n=385, dtype=po.MG_F64, omega=6 / 7,
          xfer=False),
     dict(id="f64-513", gate="pair_wide_ok: yes (256 lanes)", n=513, dtype=po.MG_F64, omega=6 / 7, xfer=False),
@@ -436,18 +437,25 @@ OP_ROWS = [
 
 # Two V(2,2) (or sawtooth) cycles from a random state and a three-cycle mg_solve: reach k_rrw, the prolongation-folding
 # pair, the small-level fused kernels, the fused-norm solve and the zebra kernels, which only the cycle dispatches.
+# fallbacks: FALLBACK rows of mg_switches.def whose gate this row's shape reaches; each is run once more in a child process
+# with the switch at 0, against the same reference and bound.
+#   f64-129-jacobi  MG_FUSED_PAIR: jacobi2_ok at 129^3 (64 vectors); MG_SMALL_FUSED: small_fused_ok at 65^3; MG_FUSED_PROLONG:
+#                   can_fold_prolong on level 0; MG_FAST_DIV: coef_of on every level; MG_COARSE_ROWS: the coarsest 17^3 is solved
+#                   by k_coarse_jacobi_rows (runs of 5)
+#   f64-257-jacobi  MG_PAIR_WIDE / MG_RR_WIDE: rows of 128 lanes; MG_PAIR_NORM: pair_norm_ok needs pair_wide_ok (the short solve)
+#   f64-129-rbgs    MG_FUSED_RB: rb_fused_ok at 129^3; MG_COARSE_RB_ROWS: red-black on the coarsest 17^3 (k_coarse_rb_rows)
 CYCLE_ROWS = [
     dict(id="f64-129-jacobi", gate="level 0: jacobi2_ok -> prolongation folded into the post pair, resid_restrict_fast_ok; "
          "level 1 (65^3): small_fused_ok (jacobi2_ok: no)", n=129, levels=4, dtype=po.MG_F64, smoother=po.SMOOTH_JACOBI,
-         omega=6 / 7, fallbacks=("MG_FUSED_PAIR", "MG_SMALL_FUSED")),
+         omega=6 / 7, fallbacks=fallbacks("MG_FUSED_PAIR", "MG_SMALL_FUSED", "MG_FUSED_PROLONG", "MG_FAST_DIV", "MG_COARSE_ROWS")),
     dict(id="f64-257-jacobi", gate="pair_wide_ok + rr_wide_ok; fused-norm mg_solve", n=257, levels=5, dtype=po.MG_F64,
-         smoother=po.SMOOTH_JACOBI, omega=0.8, fallbacks=("MG_RR_WIDE",)),
+         smoother=po.SMOOTH_JACOBI, omega=0.8, fallbacks=fallbacks("MG_RR_WIDE", "MG_PAIR_WIDE", "MG_PAIR_NORM")),
     dict(id="f64-65-jacobi", gate="level 0: small_fused_ok (unprofiled second cycle)", n=65, levels=3, dtype=po.MG_F64,
          smoother=po.SMOOTH_JACOBI, omega=6 / 7, outer_pre_gs=2),
     dict(id="f64-65-rbgs", gate="rb_fused_ok: no, fast_path_ok: yes (colour kernels); resid_restrict_fast_ok", n=65,
          levels=3, dtype=po.MG_F64, smoother=po.SMOOTH_RBGS, omega=1.0, outer_pre_gs=2),
     dict(id="f64-129-rbgs", gate="rb_fused_ok: yes, folded prolongation", n=129, levels=4, dtype=po.MG_F64,
-         smoother=po.SMOOTH_RBGS, omega=1.0),
+         smoother=po.SMOOTH_RBGS, omega=1.0, fallbacks=fallbacks("MG_FUSED_RB", "MG_COARSE_RB_ROWS")),
     dict(id="f32-129-semi-aniso", gate="semi-coarsened transfers (resid_restrict_fast_ok, prolong_fast_ok on semi levels)",
          n=129, levels=5, dtype=po.MG_F32, smoother=po.SMOOTH_JACOBI, omega=0.8, semi_xy=2, aniso=(1.0, 1.0, 0.05)),
     dict(id="f64-65-semi-rbgs", gate="semi-coarsened, anisotropic, red-black", n=65, levels=4, dtype=po.MG_F64,
@@ -528,7 +536,9 @@ def expected_launches(row, env_off=()):
         return None
     semi0 = row.get("semi_xy", 0) > 0
     j2 = jacobi2_ok(n, dt) and "MG_FUSED_PAIR" not in env_off
-    fold = j2 and not semi0 and sm in (po.SMOOTH_JACOBI, po.SMOOTH_RBGS)
+    if sm == po.SMOOTH_RBGS and "MG_FUSED_RB" in env_off:   # rb_fused_ok: no -> colour kernels, separate prolongation
+        j2 = False
+    fold = j2 and not semi0 and sm in (po.SMOOTH_JACOBI, po.SMOOTH_RBGS) and "MG_FUSED_PROLONG" not in env_off
     nc = (n - 1) // 2 + 1
     rr = resid_restrict_fast_ok(n, nc, dt)
     return dict(SMOOTH_PROLONG_pos=fold, PROLONG=0 if fold else 1, RESID_RESTRICT=1 if rr else 2)
