@@ -27,6 +27,7 @@
 //                    16-byte non-temporal vectors and the odd last column as one full 128-byte line (mg_jacobi_fast.hip).
 
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 namespace mg {
 namespace {
@@ -98,10 +99,6 @@ __global__ __launch_bounds__(GBX *GBY) void k_fmg_prolong(Geom gc, Geom gf, cons
 }
 
 // ------------------------------------------------------------------------------------------ streaming 3-D form
-template <typename T> struct FV;
-template <> struct FV<double> { static constexpr int V = 2; typedef double vec __attribute__((ext_vector_type(2))); };
-template <> struct FV<float> { static constexpr int V = 4; typedef float vec __attribute__((ext_vector_type(4))); };
-
 constexpr int FMG_W = 8;           // waves per workgroup = coarse rows staged per plane
 constexpr int FMG_R = FMG_W - 3;   // coarse rows a workgroup owns (rows m-1 .. m+2 feed row m)
 constexpr int FMG_ZC = 16;         // coarse planes a workgroup marches
@@ -118,10 +115,10 @@ __device__ __forceinline__ vec rule_vec(vec a, vec b, vec c, vec d, int kind)
 // one fine row: v = the lane's vector, tailv = the odd last column (the same value in every lane)
 template <typename T, bool BND>
 __device__ __forceinline__ void store_row(const Geom &gf, T *__restrict__ fine, const T *__restrict__ bnd, int zf, int yf, int x0,
-                                          bool xin, bool tailwave, int lane, typename FV<T>::vec v, T tailv)
+                                          bool xin, bool tailwave, int lane, typename Vec16<T>::type v, T tailv)
 {
-    constexpr int V = FV<T>::V;
-    typedef typename FV<T>::vec vec;
+    constexpr int V = Vec16<T>::n;
+    typedef typename Vec16<T>::type vec;
     const long long fo = (long long)zf * gf.plane + (long long)yf * gf.pitch;
     if (BND) {
         const bool rowb = zf == 0 || zf == gf.nz - 1 || yf == 0 || yf == gf.ny - 1;   // wave-uniform
@@ -148,8 +145,8 @@ template <typename T, bool SEMI, bool BND>
 __global__ __launch_bounds__(64 * FMG_W) void k_fmg_prolong3d(Geom gc, Geom gf, const T *__restrict__ coarse, T *__restrict__ fine,
                                                               const T *__restrict__ bnd, int nbx)
 {
-    constexpr int V = FV<T>::V, CV = V / 2;
-    typedef typename FV<T>::vec vec;
+    constexpr int V = Vec16<T>::n, CV = V / 2;
+    typedef typename Vec16<T>::type vec;
     __shared__ vec sx[2][FMG_W][64];   // x-passed rows of the plane being staged, double-buffered: one barrier per plane
     __shared__ T st[2][FMG_W];         // their last coarse column (the odd last fine column)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -237,8 +234,6 @@ __global__ __launch_bounds__(64 * FMG_W) void k_fmg_prolong3d(Geom gc, Geom gf, 
     }
 }
 
-bool is_semi_transition(const Geom &gf, const Geom &gc) { return gf.dim == 3 && gf.gnz == gc.gnz && gf.gnz > 1; }
-
 }  // namespace
 
 // whole (undistributed) 3-D levels whose rows are at least a quarter wave wide; MG_FMG_FAST=0 sends everything to the
@@ -246,7 +241,7 @@ bool is_semi_transition(const Geom &gf, const Geom &gc) { return gf.dim == 3 && 
 template <typename T>
 bool fmg_prolong_fast_ok(const Geom &gc, const Geom &gf)
 {
-    constexpr int V = FV<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (!switches().fmg_fast) return false;
     if (!(gf.dim == 3 && gc.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 && gc.nx >= 17 && gc.ny >= 3 && (gf.nx % V) == 1)) return false;
     if (gf.gz0 != 0 || gc.gz0 != 0 || gf.gnz != gf.nz || gc.gnz != gc.nz) return false;
@@ -258,7 +253,7 @@ void launch_fmg_prolong(hipStream_t s, const Geom &gc, const Geom &gf, const T *
 {
     const bool semi = is_semi_transition(gf, gc);
     if (fmg_prolong_fast_ok<T>(gc, gf)) {
-        constexpr int CV = FV<T>::V / 2;
+        constexpr int CV = Vec16<T>::n / 2;
         const int nbx = (gc.nx - 1 + 64 * CV - 1) / (64 * CV);   // lanes cover coarse columns 0 .. nc-2 (the last one only feeds the tail)
         const int nby = (gc.ny + FMG_R - 1) / FMG_R;
         const dim3 gr(nbx * nby, (gc.nz + FMG_ZC - 1) / FMG_ZC), bl(64 * FMG_W);

@@ -11,6 +11,9 @@
 #ifndef MG_GEOM_H
 #define MG_GEOM_H
 
+#include <algorithm>
+#include <cmath>
+
 namespace mg {
 
 struct Geom {
@@ -21,6 +24,9 @@ struct Geom {
     int gz0;          // global z index of local plane 0
     int gnz;          // global number of planes (n in 3-D, 1 in 2-D)
 };
+
+// the transition fine -> coarse keeps z (semi-coarsening): fine plane z <-> coarse plane z
+inline bool is_semi_transition(const Geom &gf, const Geom &gc) { return gf.dim == 3 && gf.gnz == gc.gnz && gf.gnz > 1; }
 
 // off-diagonals (negative) per axis and the diagonal of the level's operator,
 // include/linear_system.hpp:27-28,37-38 of the reference
@@ -123,6 +129,33 @@ __device__ __forceinline__ void div_cd_n_wave(const T (&a)[N], T (&q)[N], const 
     }
 }
 #endif
+
+// ---- how a wide-tile launch (k_pairw, k_rrw: one 1024-thread workgroup per CU) is dealt to the CUs ----------------
+// Work = ncopy copies x nby y-tiles x nz planes. `grid` workgroups (a multiple of 8 for the XCD-aware order) and either
+//  * RANGES (zc = 0; mode 0): the tile-planes are cut into `grid` equal runs, at least min_items_per_wg each, or
+//  * z-CHUNKS of zc planes, one workgroup per chunk: nz is cut into kk = 1 .. kk_max equal chunks and the count whose
+//    last round on ncu CUs is fullest wins, a chunk of zc planes costing planes_per_step * zc + overhead plane steps;
+//    zc_forced > 0 overrides the search.
+// Pure: the callers pass the CU count and their switches (mg_pair_wide.hip: wide_plan has the measurements).
+struct ChunkPlan { int grid, zc; };
+inline ChunkPlan chunk_plan(int nz, int nby, int ncopy, int ncu, int min_items_per_wg, int kk_max, int planes_per_step,
+                            double overhead, int mode, int zc_forced)
+{
+    const long long total = (long long)ncopy * nby * nz;
+    const int grid = (int)std::max<long long>(8, (std::min<long long>(ncu, total / min_items_per_wg) / 8) * 8);
+    if (mode == 0) return {grid, 0};
+    int best_zc = std::max(1, nz);
+    double best = 1e30;
+    for (int kk = 1; kk <= kk_max; kk++) {
+        const int zc = (nz + kk - 1) / kk, nbz = (nz + zc - 1) / zc;
+        const double rounds = std::ceil((double)ncopy * nby * nbz / grid);
+        const double cost = std::max(rounds, 1.0) * (planes_per_step * zc + overhead);
+        if (cost < best - 1e-9) { best = cost; best_zc = zc; }
+    }
+    if (zc_forced > 0) best_zc = zc_forced;
+    const long long items = (long long)ncopy * nby * ((nz + best_zc - 1) / best_zc);
+    return {(int)(((items + 7) / 8) * 8), best_zc};
+}
 
 struct CoarseOut {
     int iters;

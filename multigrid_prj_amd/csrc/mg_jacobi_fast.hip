@@ -21,46 +21,13 @@
 //    CPU restatement the tests compare with.
 // MFMA is not used: there is no contraction here, the kernel is HBM-bound (24 B/point).
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace mg {
 namespace {
-
-template <typename T> struct VecOf;
-template <> struct VecOf<double> { static constexpr int V = 2; typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct VecOf<float> { static constexpr int V = 4; typedef float type __attribute__((ext_vector_type(4))); };
-
-// lane i <- lane i-1 (lane 0 keeps `edge`) : DPP wave_shr:1
-__device__ __forceinline__ float from_prev_lane(float v, float edge)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double from_prev_lane(double v, double edge)
-{
-    int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x138, 0xf, 0xf, false);
-    int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// lane i <- lane i+1 (lane 63 keeps `edge`) : DPP wave_shl:1
-__device__ __forceinline__ float from_next_lane(float v, float edge)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double from_next_lane(double v, double edge)
-{
-    int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x130, 0xf, 0xf, false);
-    int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x130, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_sum64(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 enum { OP_JACOBI = 0, OP_RESIDUAL = 1, OP_RB = 2 };
 
@@ -80,13 +47,12 @@ __global__ __launch_bounds__(64 * BW) void k_sweep3d(Geom g, Coef<T> c, T omega,
                                                      double *__restrict__ partials, int nbx, int nby,
                                                      int nbz)
 {
-    constexpr int V = VecOf<T>::V;
-    typedef typename VecOf<T>::type vec;
+    constexpr int V = Vec16<T>::n;
+    typedef typename Vec16<T>::type vec;
     __shared__ double sh[BW];
 
     const int nblocks = nbx * nby * nbz;
-    const int per = (nblocks + 7) >> 3;
-    const int bid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);  // XCD-aware order
+    const int bid = xcd_block(blockIdx.x, (nblocks + 7) >> 3);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double sq = 0.;
     if (bid < nblocks) {
@@ -140,8 +106,8 @@ __global__ __launch_bounds__(64 * BW) void k_sweep3d(Geom g, Coef<T> c, T omega,
                 T el = 0, er = 0;
                 if (!ZEROU && lane == 0) el = pz[rowoff[r] - 1];
                 if (!ZEROU && lane == 63) er = pz[rowoff[r] + V];
-                const T xm = from_prev_lane(cc[r][V - 1], el);
-                const T xp = from_next_lane(cc[r][0], er);
+                const T xm = lane_from_prev(cc[r][V - 1], el);
+                const T xp = lane_from_next(cc[r][0], er);
                 const vec ym = (r > 0) ? cc[r > 0 ? r - 1 : 0] : hlo;
                 const vec yp = (r < RY - 1) ? cc[r < RY - 1 ? r + 1 : 0] : hhi;
                 const bool rb = zb || ybnd[r];
@@ -215,7 +181,9 @@ __global__ __launch_bounds__(64 * BW) void k_sweep3d(Geom g, Coef<T> c, T omega,
         }
     }
     if (NORM) {
-        sq = wave_sum64(sq);
+        // mg_device.h's block_sum with the wave count known, written out: through the function this kernel's registers and
+        // instruction order change
+        sq = wave_sum(sq);
         if (lane == 0) sh[wv] = sq;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -294,7 +262,7 @@ __global__ __launch_bounds__(TPR, MINW) void k_jacobi2(Geom g, Coef<T> c, T omeg
                                                  const T *__restrict__ rhs_, T *__restrict__ out_, int nby, int nbz,
                                                  const T *__restrict__ coarse, Geom gc, int dup_planes)
 {
-    constexpr int V = VW ? VW : VecOf<T>::V, TYO = TYO_, TYV = TYO + 2;
+    constexpr int V = VW ? VW : Vec16<T>::n, TYO = TYO_, TYV = TYO + 2;
     constexpr int CV = V / 2;  // coarse columns owned by this thread
     static_assert(!CORR || TYO == 2, "the correction assumes two output rows (y0 even)");
     constexpr int LP = TPR * V + 2 * V;  // LDS row: V pad | TPR*V values | tail column | pad
@@ -311,8 +279,7 @@ __global__ __launch_bounds__(TPR, MINW) void k_jacobi2(Geom g, Coef<T> c, T omeg
     // boundary pieces of a z-slab, mg_solver.cpp: pair_on_slab2_t): the workgroups of the second half shift their
     // pointers and the global plane index of local plane 0 -- everything below is unchanged (all of it scalar)
     const int nblocks = nby * nbz, ntotal = dup_planes > 0 ? 2 * nblocks : nblocks;
-    const int per = (ntotal + 7) >> 3;
-    int bid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);         // XCD-aware order
+    int bid = xcd_block(blockIdx.x, (ntotal + 7) >> 3);
     if (bid >= ntotal) return;                                    // whole workgroup
     const bool second = bid >= nblocks;
     if (second) { bid -= nblocks; g.gz0 += dup_planes; }
@@ -547,8 +514,8 @@ __global__ __launch_bounds__(TPR, MINW) void k_jacobi2(Geom g, Coef<T> c, T omeg
                 // (published in the previous step); the row's last thread has the tail column instead
                 const T el = uedge[p & 1][r][wl][1];
                 const T er = tail ? utail[p & 1][r] : uedge[p & 1][r][wr][0];
-                const T xm = from_prev_lane(uc[r][V - 1], el);
-                const T xp = from_next_lane(uc[r][0], er);
+                const T xm = lane_from_prev(uc[r][V - 1], el);
+                const T xp = lane_from_next(uc[r][0], er);
                 const vec ym = (r > 0) ? uc[r > 0 ? r - 1 : 0] : hlo;
                 const vec yp = (r < TYV - 1) ? uc[r < TYV - 1 ? r + 1 : 0] : hhi;
                 const bool rb = zbp || ybnd[r];
@@ -650,7 +617,7 @@ struct FastGrid { int nbx, nby, nbz, grid; };
 template <typename T>
 FastGrid fast_grid(const Geom &g, int zc = ZC)
 {
-    constexpr int V = VecOf<T>::V;
+    constexpr int V = Vec16<T>::n;
     FastGrid f;
     f.nbx = (g.nx / V + 63) / 64;
     f.nby = (g.ny + RY * BW - 1) / (RY * BW);
@@ -668,7 +635,7 @@ FastGrid fast_grid(const Geom &g, int zc = ZC)
 template <typename T>
 bool fast_path_ok(const Geom &g)
 {
-    constexpr int V = VecOf<T>::V;
+    constexpr int V = Vec16<T>::n;
     // 3-D, rows long enough to fill a wave, at most the one boundary column left over
     return g.dim == 3 && g.nx >= 33 && (g.nx % V) <= 1 && g.ny >= 3;
 }
@@ -745,7 +712,7 @@ static int j2_tyo_for(int tpr) { return tpr > 384 ? 2 : 3; }
 template <typename T>
 bool jacobi2_ok(const Geom &g)
 {
-    constexpr int V = VecOf<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (!switches().fused_pair || g.dim != 3 || g.gz0 != 0 || g.gnz != g.nz || g.ny < 3 || g.nz < 3) return false;
     const int v = (g.nx - 1) / V;
     return (g.nx - 1) % V == 0 && j2_row_ok(v);
@@ -755,7 +722,7 @@ bool jacobi2_ok(const Geom &g)
 template <typename T>
 bool jacobi2_slab_ok(const Geom &g)
 {
-    constexpr int V = VecOf<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (!switches().fused_pair || !switches().fused_slab || g.dim != 3 || g.ny < 3 || g.nz < 6) return false;
     const int v = (g.nx - 1) / V;
     return (g.nx - 1) % V == 0 && j2_row_ok(v);
@@ -765,7 +732,7 @@ template <typename T>
 int launch_jacobi2(hipStream_t s, const Geom &g, const Coef<T> &c, T omega, const T *u, const T *rhs, T *out, bool zero_u, int dup,
                    double *d_partials)
 {
-    constexpr int V = VecOf<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (pair_wide_ok<T>(g)) return launch_pair_wide<T>(s, g, Geom{}, c, omega, u, (const T *)nullptr, rhs, out, zero_u, false, dup, d_partials);
     const int tpr = (g.nx - 1) / V;
     const int ncopy = dup > 0 ? 2 : 1;   // dup: the same geometry once more, `dup` planes further up, in the same launch
@@ -814,7 +781,7 @@ template <typename T>
 int launch_rb_fused(hipStream_t s, const Geom &g, const Coef<T> &c, const T *u, const T *rhs, T *out,
                     const T *coarse, const Geom &gc, int dup, bool zero_u, double *d_partials)
 {
-    constexpr int V = VecOf<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (coarse) { dup = 0; zero_u = false; }   // the folding variant only runs on whole levels
     if (pair_wide_ok<T>(g)) return launch_pair_wide<T>(s, g, gc, c, (T)1, u, coarse, rhs, out, zero_u, true, dup, d_partials);
     const int tpr = (g.nx - 1) / V;
@@ -869,7 +836,7 @@ template <typename T>
 void launch_jacobi2_corr(hipStream_t s, const Geom &g, const Geom &gc, const Coef<T> &c, T omega, const T *u,
                          const T *coarse, const T *rhs, T *out, int dup)
 {
-    constexpr int V = VecOf<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (pair_wide_ok<T>(g)) { launch_pair_wide<T>(s, g, gc, c, omega, u, coarse, rhs, out, false, false, dup); return; }
     const int tpr = (g.nx - 1) / V;
     const int nby = (g.ny + J2_TYO - 1) / J2_TYO, nbz = j2_nbz(g, tpr, 2);

@@ -9,6 +9,17 @@
 
 namespace mg {
 
+// compute units of the current device, read once, rounded down to a multiple of 8 (one share per XCD), at least 8
+inline int cu_count_x8()
+{
+    static const int ncu = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return std::max(8, (n / 8) * 8);
+    }();
+    return ncu;
+}
+
 // number of per-block partial sums a reduction launch over `g` may produce
 int reduce_partials_capacity(const Geom &g);
 

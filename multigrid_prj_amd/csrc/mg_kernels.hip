@@ -7,14 +7,14 @@
 //    the reference's order  (k-1),(j-1),(i-1),[c],(i+1),(j+1),(k+1)
 //    (reference src/domain.cpp:36-38, include/solvers.hpp:36-46,70-80,265-273);
 //  * true IEEE division by the diagonal, like `/ m_A.coeffRef(i,i)`;
-//  * norms: per-thread double accumulation -> wave64 shuffle tree -> per-block
-//    partial -> second kernel that adds the partials in a fixed order, so a norm
-//    is reproducible run to run (no float atomics), but its summation order
-//    differs from the reference's serial loop (tolerance 1e-12 relative in tests).
+//  * norms: summed in the fixed order of mg_device.h, so a norm is reproducible run
+//    to run (no float atomics), but its summation order differs from the
+//    reference's serial loop (tolerance 1e-12 relative in tests).
 //
 // Nothing here is a dense contraction: MFMA is deliberately unused; every kernel
 // is priced against the HBM roofline.
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 #include <algorithm>
 
@@ -26,11 +26,6 @@ namespace {
 
 constexpr int BX = 64;  // one wave64 spans 64 consecutive x
 constexpr int BY = 4;   // 4 waves per workgroup, stacked in y
-
-__device__ __forceinline__ long long lidx(const Geom &g, int z, int y, int x)
-{
-    return (long long)z * g.plane + (long long)y * g.pitch + x;
-}
 
 __device__ __forceinline__ bool on_boundary(const Geom &g, int z, int y, int x)
 {
@@ -87,33 +82,6 @@ __device__ __forceinline__ T point_update(const Geom &g, const Coef<T> &c, T ome
         return uc + omega * (jac - uc);
     }
     return jac;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// sum over the workgroup; every thread gets the same value. sh: >= 18 doubles.
-__device__ __forceinline__ double block_sum_bcast(double v, double *sh)
-{
-    const int tid = threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z);
-    const int nthreads = blockDim.x * blockDim.y * blockDim.z;
-    const int nw = (nthreads + 63) >> 6;
-    v = wave_sum(v);
-    if ((tid & 63) == 0) sh[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0;
-        for (int w = 0; w < nw; w++) s += sh[w];
-        sh[17] = s;
-    }
-    __syncthreads();
-    double r = sh[17];
-    __syncthreads();
-    return r;
 }
 
 // ---------------------------------------------------------------- Jacobi (generic)
@@ -371,21 +339,6 @@ __device__ void wg_gs_lex(const Geom &g, const Coef<T> &c, T *u, const T *rhs)
 //                  ahead (their stores happen >= PF+1 barriers after the loads have completed).
 // One barrier per step with only ceil(ny/64) waves resident. Inputs and expression order per
 // point are those of point_update => bit-identical to the serial loop (solvers.hpp:33-48).
-template <typename T>
-__device__ __forceinline__ T gs_prev_lane(T v, T edge);
-template <>
-__device__ __forceinline__ float gs_prev_lane<float>(float v, float edge)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-template <>
-__device__ __forceinline__ double gs_prev_lane<double>(double v, double edge)
-{
-    int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x138, 0xf, 0xf, false);
-    int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
 template <typename T, int PF>
 __global__ __launch_bounds__(SWG) void k_gs_lex2d_rows(Geom g, Coef<T> c, int sweeps, T *u, const T *rhs)
 {
@@ -417,7 +370,7 @@ __global__ __launch_bounds__(SWG) void k_gs_lex2d_rows(Geom g, Coef<T> c, int sw
                 const int d = d0 + j, x = d - y;  // steps past nd-1 find every thread out of range
                 T from_wave = 0;
                 if (lane == 0 && wv > 0) from_wave = mail[(d + 1) & 1][wv - 1];
-                const T upnew = gs_prev_lane<T>(pub, from_wave);
+                const T upnew = lane_from_prev(pub, from_wave);
                 T val = pub;
                 if (rowin && x >= 0 && x < nx) {
                     if (rowb || x == 0 || x == nx - 1) {
@@ -453,21 +406,6 @@ __global__ __launch_bounds__(SWG) void k_gs_lex2d_rows(Geom g, Coef<T> c, int sw
 // and lives in registers: new2(y-1, x2) and new1(y+1, x2) are the neighbouring lanes' results of the
 // previous step (DPP, mailboxes across waves), new2(y, x2-1) and new1(y, x2+1) the thread's own.
 // Sweep 1's values never go to memory: half the steps and half the stores of two separate sweeps.
-template <typename T>
-__device__ __forceinline__ T gs_next_lane(T v, T edge);
-template <>
-__device__ __forceinline__ float gs_next_lane<float>(float v, float edge)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-template <>
-__device__ __forceinline__ double gs_next_lane<double>(double v, double edge)
-{
-    int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x130, 0xf, 0xf, false);
-    int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x130, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
 template <typename T, int PF>
 __global__ __launch_bounds__(SWG) void k_gs_lex2d_rows_pair(Geom g, Coef<T> c, T *u, const T *rhs)
 {
@@ -499,9 +437,9 @@ __global__ __launch_bounds__(SWG) void k_gs_lex2d_rows_pair(Geom g, Coef<T> c, T
             T w1 = 0, w2 = 0, wn = 0;
             if (lane == 0 && wv > 0) { w1 = mail1[(d + 1) & 1][wv - 1]; w2 = mail2[(d + 1) & 1][wv - 1]; }
             if (lane == 63 && wv < nwv - 1) wn = mailn[(d + 1) & 1][wv + 1];
-            const T up1 = gs_prev_lane<T>(pub1, w1);   // new1(y-1, x1)
-            const T up2 = gs_prev_lane<T>(pub2, w2);   // new2(y-1, x2)
-            const T dn2 = gs_next_lane<T>(pub1, wn);   // new1(y+1, x2): thread y+1's sweep-1 result of step d-1
+            const T up1 = lane_from_prev(pub1, w1);   // new1(y-1, x1)
+            const T up2 = lane_from_prev(pub2, w2);   // new2(y-1, x2)
+            const T dn2 = lane_from_next(pub1, wn);   // new1(y+1, x2): thread y+1's sweep-1 result of step d-1
             const T rt2 = pub1;                        // new1(y, x2+1): own sweep-1 result of step d-1
             const T b1 = pb[j];
             T val1 = pub1, val2 = pub2;
@@ -1708,20 +1646,19 @@ void launch_sumsq(hipStream_t s, const Geom &g, const T *v, double *d_partials, 
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(1024), 0, s, d_partials, nb, d_sumsq);
 }
 
-static inline bool is_semi(const Geom &gf, const Geom &gc) { return gf.dim == 3 && gf.gnz == gc.gnz && gf.gnz > 1; }
 
 template <typename T>
 void launch_inject(hipStream_t s, const Geom &gf, const Geom &gc, const T *fine, T *coarse)
 {
     dim3 gr = grid_for(gc.nx, gc.ny, gc.nz), bl(BX, BY, 1);
-    hipLaunchKernelGGL((k_inject<T>), gr, bl, 0, s, gf, gc, is_semi(gf, gc) ? 1 : 0, fine, coarse);
+    hipLaunchKernelGGL((k_inject<T>), gr, bl, 0, s, gf, gc, is_semi_transition(gf, gc) ? 1 : 0, fine, coarse);
 }
 
 template <typename T>
 void launch_restrict_fw(hipStream_t s, const Geom &gf, const Geom &gc, const T *fine, T *coarse)
 {
     dim3 gr = grid_for(gc.nx, gc.ny, gc.nz), bl(BX, BY, 1);
-    if (gc.dim == 3 && is_semi(gf, gc)) hipLaunchKernelGGL((k_restrict_fw<T, 3, false>), gr, bl, 0, s, gf, gc, fine, coarse);
+    if (gc.dim == 3 && is_semi_transition(gf, gc)) hipLaunchKernelGGL((k_restrict_fw<T, 3, false>), gr, bl, 0, s, gf, gc, fine, coarse);
     else if (gc.dim == 3) hipLaunchKernelGGL((k_restrict_fw<T, 3, true>), gr, bl, 0, s, gf, gc, fine, coarse);
     else hipLaunchKernelGGL((k_restrict_fw<T, 2, false>), gr, bl, 0, s, gf, gc, fine, coarse);
 }
@@ -1732,7 +1669,7 @@ void launch_prolong(hipStream_t s, const Geom &gc, const Geom &gf, const T *coar
 {
     if (prolong_fast_ok<T>(gc, gf)) { launch_prolong_fast<T>(s, gc, gf, coarse, fine, add); return; }
     dim3 gr = grid_for(gf.nx, gf.ny, gf.nz), bl(BX, BY, 1);
-    if (gf.dim == 3 && is_semi(gf, gc)) {
+    if (gf.dim == 3 && is_semi_transition(gf, gc)) {
         if (add) hipLaunchKernelGGL((k_prolong<T, 23, true>), gr, bl, 0, s, gc, gf, coarse, fine);
         else hipLaunchKernelGGL((k_prolong<T, 23, false>), gr, bl, 0, s, gc, gf, coarse, fine);
     } else if (gf.dim == 3) {

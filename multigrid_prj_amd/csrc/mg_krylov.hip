@@ -22,6 +22,7 @@
 //   dots: products and sums in double.
 // Zeroing p' on the boundary is what keeps the iteration on the interior whatever the preconditioner leaves there.
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 namespace mg {
 
@@ -30,10 +31,6 @@ namespace {
 constexpr int CG_THREADS = 256;
 constexpr int CG_MAX_BLOCKS = 2048;
 constexpr int TAIL_THREADS = 1024;
-
-template <typename T> struct Vec16;
-template <> struct Vec16<double> { using type = double2; static constexpr int n = 2; };
-template <> struct Vec16<float> { using type = float4; static constexpr int n = 4; };
 
 template <typename T>
 __device__ __forceinline__ void vload(const T *p, T (&v)[Vec16<T>::n])
@@ -59,27 +56,6 @@ __device__ __forceinline__ void vstore_masked(T *p, const T (&v)[Vec16<T>::n], i
 #pragma unroll
     for (int e = 0; e < V; e++)
         if (e < valid) p[e] = v[e];
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// fixed-order workgroup sum; the result is valid in thread 0. sh: one double per wave.
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-    const int nw = blockDim.x >> 6;
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < nw; w++) s += sh[w];
-    __syncthreads();
-    return s;
 }
 
 // one work item = one 16-byte vector of one row: item -> (plane, row, first x)

@@ -23,6 +23,7 @@
 // When s_in is a power of two with a normal reciprocal (what the driver always passes) the division is done as a
 // multiplication by that reciprocal: the same correctly rounded quotient, bit for bit. Any other s_in takes the division.
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 namespace mg {
 
@@ -63,27 +64,6 @@ __device__ __forceinline__ void st4(float *p, const float (&v)[MX_V], int valid)
 #pragma unroll
     for (int e = 0; e < MX_V; e++)
         if (e < valid) p[e] = v[e];
-}
-
-__device__ __forceinline__ double mx_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// fixed-order workgroup sum; the result is valid in thread 0. sh: one double per wave.
-__device__ __forceinline__ double mx_block_sum(double v, double *sh)
-{
-    const int nw = blockDim.x >> 6;
-    v = mx_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < nw; w++) s += sh[w];
-    __syncthreads();
-    return s;
 }
 
 struct MixedCoef {
@@ -184,7 +164,7 @@ __device__ __forceinline__ void mixed_body(const Geom &g, const Geom &g32, const
         if (CORR) st4(un + i64, uc, valid);
         st4(r32 + i32, rv, valid);
     }
-    const double s = mx_block_sum(acc, sh);
+    const double s = block_sum(acc, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -221,7 +201,7 @@ __global__ __launch_bounds__(MX_THREADS) void k_mixed_sumsq(Geom g, const double
         for (int k = 0; k < MX_V; k++)
             if (x0 + k < g.nx) acc += w[k] * w[k];
     }
-    const double s = mx_block_sum(acc, sh);
+    const double s = block_sum(acc, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 

@@ -25,6 +25,7 @@
 // global plane index) are exactly k_jacobi2's, so the launchers of mg_jacobi_fast.hip hand over to this kernel unchanged.
 // MFMA unused: a 7-point stencil is not a contraction; the kernel is bound by HBM traffic (24-25 B per point).
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,10 +41,6 @@ __device__ __forceinline__ double lane_bcast(double v, int l)
     return __hiloint2double(hi, lo);
 }
 
-template <typename T> struct WV;
-template <> struct WV<double> { static constexpr int V = 2; };
-template <> struct WV<float> { static constexpr int V = 4; };
-
 // RB: the pipeline runs red-black Gauss-Seidel instead of Jacobi (see k_jacobi2): phase 1 = red half-sweep (black
 // points copied), phase 2 = black half-sweep on the plane behind -- ONE red-black sweep per pass
 // NORM: the launch also returns sum r^2 of r = rhs - A u (the residual of the INPUT, Residual::apply_iteration_to_vec +
@@ -56,7 +53,7 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
                                                    const T *__restrict__ coarse, Geom gc, int dup_planes,
                                                    double *__restrict__ partials)
 {
-    constexpr int V = WV<T>::V, CV = V / 2, NR = CV + 1;
+    constexpr int V = Vec16<T>::n, CV = V / 2, NR = CV + 1;
     constexpr int R = 2, NROW = G * R, S = NROW - 2;
     constexpr int LP = TPR * V + 2 * V;  // LDS row: V pad | TPR*V values | tail column | pad
     typedef T vec __attribute__((ext_vector_type(V)));
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
     double nsq = 0.;
     const long long per_copy = (long long)nby * g.nz, total = (dup_planes > 0 ? 2 : 1) * per_copy;
     const int nwg = (int)gridDim.x, wper = nwg >> 3;          // the launcher makes the grid a multiple of 8
-    const int wi = (blockIdx.x & 7) * wper + (blockIdx.x >> 3);  // XCD-aware order: an XCD takes consecutive ranges
+    const int wi = xcd_block(blockIdx.x, wper);               // an XCD takes consecutive ranges
     // (chunks: y-neighbouring tiles sit on neighbouring workgroups and march the same planes at the same time, so the halo rows
     // they share are cache hits; ranges keep that only when a range is a whole fraction of a tile's column)
     const int nbz = zc > 0 ? (g.nz + zc - 1) / zc : 0;
@@ -478,6 +475,8 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
     }
     }   // next chunk of this workgroup's range
     if (NORM) {
+        // mg_device.h's block_sum, written out down to the shuffle tree: through the functions the same instructions come out
+        // in another order, and this kernel's instruction stream is kept as it was
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) nsq += __shfl_down(nsq, off, 64);
         if (lane == 0) snorm[t >> 6] = nsq;
@@ -496,37 +495,16 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
 // planes at the same time and share their halo rows in L2, but the last round of chunks is partly empty). Ranges keep the
 // lockstep only when a run is a whole fraction of a tile's column (513^3 on 256 CUs: 86 tiles x 513 planes / 256 = 172.3 planes
 // = a third of a column; 1025^3 fp32: 685 planes = two thirds of one: 3.46 ms as ranges against 3.07 as chunks).
-struct WidePlan { int grid, zc; };
-static WidePlan wide_plan(const Geom &g, int nby, int ncopy)
+static ChunkPlan wide_plan(const Geom &g, int nby, int ncopy)
 {
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return std::max(8, (n / 8) * 8);
-    }();
-    const int zc_env = switches().pw_zc;
-    const long long total = (long long)ncopy * nby * g.nz;
-    const int grid = (int)std::max<long long>(8, (std::min<long long>(ncu, total / 3) / 8) * 8);
     // measured on one box, same process (tools/ab_modes.sh, 513^3 fp64, ms per launch ranges / chunks): plain pair 0.661 / 0.654,
     // folding pair 0.723 / 0.734, whole cycle 2.43 / 2.39; a slab piece alone on the chip (64 planes: 86 tiles x 2 chunks fill two
     // thirds of it, x 3 one workgroup more than it): 0.111 ms as chunks, 0.089 as ranges. Chunks are nevertheless the default
     // everywhere: a grid of exactly one workgroup per CU, each holding its CU for the whole launch, takes TWICE as long as soon
     // as anything else holds a CU -- RCCL's send / recv kernels, the boundary launch on the communication stream -- while
     // one-chunk workgroups are dispatched to whatever CUs are free. Ranges: MG_PW_MODE=0 (measurements on an otherwise idle GPU).
-    if (switches().pw_mode == 0) return {grid, 0};
-    // chunks: the count whose last round is fullest; a chunk of zc planes costs zc + 2 plane steps + the prologue
-    int best_zc = std::max(1, g.nz);
-    double best = 1e30;
-    for (int kk = 1; kk <= std::max(1, g.nz / 4); kk++) {
-        const int zc = (g.nz + kk - 1) / kk, nbz = (g.nz + zc - 1) / zc;
-        const double rounds = std::ceil((double)ncopy * nby * nbz / grid);
-        const double cost = std::max(rounds, 1.0) * (zc + 3.5);
-        if (cost < best - 1e-9) { best = cost; best_zc = zc; }
-    }
-    if (zc_env > 0) best_zc = zc_env;
-    // one workgroup per chunk (the kernel's loop then runs once): the hardware dispatcher deals them
-    const long long items = (long long)ncopy * nby * ((g.nz + best_zc - 1) / best_zc);
-    return {(int)(((items + 7) / 8) * 8), best_zc};
+    // Ranges take at least 3 tile-planes each; a chunk of zc planes costs zc + 2 plane steps + the prologue.
+    return chunk_plan(g.nz, nby, ncopy, cu_count_x8(), 3, std::max(1, g.nz / 4), 1, 3.5, switches().pw_mode, switches().pw_zc);
 }
 
 int g_wide_mode = -1;
@@ -540,7 +518,7 @@ void set_pair_wide(int mode) { g_wide_mode = mode; }
 template <typename T>
 bool pair_wide_ok(const Geom &g)
 {
-    constexpr int V = WV<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (g_wide_mode == 0 || (g_wide_mode < 0 && !switches().pair_wide) || g.dim != 3 || (g.nx - 1) % V != 0) return false;
     const int tpr = (g.nx - 1) / V;
     if (tpr != 128 && tpr != 256) return false;
@@ -552,12 +530,12 @@ template <typename T>
 int launch_pair_wide(hipStream_t s, const Geom &g, const Geom &gc, const Coef<T> &c, T omega, const T *u, const T *coarse,
                      const T *rhs, T *out, bool zero_u, bool rb, int dup, double *d_partials)
 {
-    constexpr int V = WV<T>::V;
+    constexpr int V = Vec16<T>::n;
     const int tpr = (g.nx - 1) / V;
     const int G = 1024 / tpr, S = 2 * G - 2;
     const int nby = (g.ny - 1 + S - 1) / S;
     const int ncopy = dup > 0 ? 2 : 1;
-    const WidePlan plan = wide_plan(g, nby, ncopy);
+    const ChunkPlan plan = wide_plan(g, nby, ncopy);
     const int grid = plan.grid, zc = plan.zc;
     const bool damped = (omega != (T)1) && !rb;
 #define MG_PW(TPR, GG, D, C, Z, RBB) \

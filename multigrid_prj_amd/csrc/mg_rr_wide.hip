@@ -19,6 +19,7 @@
 //     (two register sets alternating with the step's parity: the loop body is instantiated once per parity).
 // Geometry conventions (slab pieces, ghost planes, the second single coarse plane `dup_kc` further up) are k_resid_restrict_fw's.
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -27,17 +28,13 @@
 namespace mg {
 namespace {
 
-template <typename T> struct RV;
-template <> struct RV<double> { static constexpr int V = 2; };
-template <> struct RV<float> { static constexpr int V = 4; };
-
 // SEMI: semi-coarsening transition (z kept): every fine plane is a coarse plane, 9-point weights per plane
 template <typename T, int TPR, int G, bool SEMI>
 __global__ __launch_bounds__(TPR * G) void k_rrw(Geom gf, Geom gc, Coef<T> c, const T *__restrict__ u_,
                                                  const T *__restrict__ rhs_, T *__restrict__ coarse_, int nby,
                                                  int zcc, int dup_kc, int dup_nzf)
 {
-    constexpr int V = RV<T>::V, CV = V / 2;
+    constexpr int V = Vec16<T>::n, CV = V / 2;
     constexpr int R = 2, NROW = G * R, S = NROW - 2;
     constexpr int LP = TPR * V + 2 * V;  // LDS row: V pad | TPR*V values | tail column | pad
     typedef T vec __attribute__((ext_vector_type(V)));
@@ -56,7 +53,7 @@ __global__ __launch_bounds__(TPR * G) void k_rrw(Geom gf, Geom gc, Coef<T> c, co
     const T q = (T)0.25, h = (T)0.5;
     const long long per_copy = (long long)nby * gc.nz, total = (dup_kc > 0 ? 2 : 1) * per_copy;
     const int nwg = (int)gridDim.x, wper = nwg >> 3;             // the launcher makes the grid a multiple of 8
-    const int wi = (blockIdx.x & 7) * wper + (blockIdx.x >> 3);  // XCD-aware order
+    const int wi = xcd_block(blockIdx.x, wper);
     // zcc == 0: ranges. zcc > 0: chunks of zcc coarse planes dealt round-robin with the tile running fastest (k_pairw explains)
     const int nbz = zcc > 0 ? (gc.nz + zcc - 1) / zcc : 0;
     const long long items = (dup_kc > 0 ? 2 : 1) * (long long)nby * nbz;
@@ -302,29 +299,10 @@ __global__ __launch_bounds__(TPR * G) void k_rrw(Geom gf, Geom gc, Coef<T> c, co
 }
 
 // ranges or chunks (mg_pair_wide.hip: wide_plan), in units of coarse planes (two fine planes each unless z is kept)
-struct RRPlan { int grid, zcc; };
-static RRPlan rr_wide_plan(const Geom &gc, int nby, int ncopy, bool semi)
+static ChunkPlan rr_wide_plan(const Geom &gc, int nby, int ncopy, bool semi)
 {
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return std::max(8, (n / 8) * 8);
-    }();
-    const int zcc_env = switches().rrw_zcc;
-    const long long total = (long long)ncopy * nby * gc.nz;
-    const int grid = (int)std::max<long long>(8, (std::min<long long>(ncu, total / 2) / 8) * 8);
-    if (switches().rrw_mode == 0) return {grid, 0};   // ranges only on request (mg_pair_wide.hip: wide_plan says why); whole level 0.543 against 0.525 ms as chunks
-    int best_zcc = std::max(1, gc.nz);
-    double best = 1e30;
-    for (int kk = 1; kk <= gc.nz; kk++) {
-        const int zcc = (gc.nz + kk - 1) / kk, nbz = (gc.nz + zcc - 1) / zcc;
-        const double rounds = std::ceil((double)ncopy * nby * nbz / grid);
-        const double cost = std::max(rounds, 1.0) * ((semi ? 1 : 2) * zcc + 4.5);
-        if (cost < best - 1e-9) { best = cost; best_zcc = zcc; }
-    }
-    if (zcc_env > 0) best_zcc = zcc_env;
-    const long long items = (long long)ncopy * nby * ((gc.nz + best_zcc - 1) / best_zcc);   // one workgroup per chunk
-    return {(int)(((items + 7) / 8) * 8), best_zcc};
+    // ranges (at least 2 tile-planes each) only on request (mg_pair_wide.hip: wide_plan says why); whole level 0.543 against 0.525 ms as chunks
+    return chunk_plan(gc.nz, nby, ncopy, cu_count_x8(), 2, gc.nz, semi ? 1 : 2, 4.5, switches().rrw_mode, switches().rrw_zcc);
 }
 
 int g_rr_wide_mode = -1;
@@ -336,7 +314,7 @@ void set_rr_wide(int mode) { g_rr_wide_mode = mode; }
 template <typename T>
 bool rr_wide_ok(const Geom &gf, const Geom &gc)
 {
-    constexpr int V = RV<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (g_rr_wide_mode == 0 || (g_rr_wide_mode < 0 && !switches().rr_wide) || gf.dim != 3 || (gf.nx - 1) % V != 0 || gf.nx != 2 * gc.nx - 1 || gf.ny != 2 * gc.ny - 1) return false;
     const int tpr = (gf.nx - 1) / V;
     return (tpr == 128 || tpr == 256) && gf.ny >= 200 && gc.nz >= 4;   // (single coarse planes -- a slab's boundary pieces -- stay with k_resid_restrict_fw)
@@ -346,15 +324,15 @@ template <typename T>
 void launch_rr_wide(hipStream_t s, const Geom &gf, const Geom &gc, const Coef<T> &c, const T *u, const T *rhs, T *coarse,
                     int dup_kc, int dup_nzf)
 {
-    constexpr int V = RV<T>::V;
+    constexpr int V = Vec16<T>::n;
     const int tpr = (gf.nx - 1) / V;
     const int G = 1024 / tpr, S = 2 * G - 2;
     const int nby = (gf.ny - 1 + S - 1) / S;
-    const bool semi = gf.gnz == gc.gnz && gf.gnz > 1;
+    const bool semi = is_semi_transition(gf, gc);
     if (gc.nz != 1) dup_kc = 0;
     const int ncopy = dup_kc > 0 ? 2 : 1;
-    const RRPlan plan = rr_wide_plan(gc, nby, ncopy, semi);
-    const int grid = plan.grid, zcc = plan.zcc;
+    const ChunkPlan plan = rr_wide_plan(gc, nby, ncopy, semi);
+    const int grid = plan.grid, zcc = plan.zc;
 #define MG_RRW(TPR, GG, SEMI) \
     hipLaunchKernelGGL((k_rrw<T, TPR, GG, SEMI>), dim3(grid), dim3(TPR * GG), 0, s, gf, gc, c, u, rhs, coarse, nby, zcc, dup_kc, dup_nzf)
     if (tpr == 256) { if (semi) MG_RRW(256, 4, true); else MG_RRW(256, 4, false); }

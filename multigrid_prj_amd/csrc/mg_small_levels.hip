@@ -11,15 +11,10 @@
 // kernels on every hierarchy that has such levels. Reference counterparts: Jacobi_iteration::apply_iteration_to_vec
 // (include/solvers.hpp:64-83), Residual (solvers.hpp:265-273), InterpolationClass::interpolate (src/multigrid.cpp:3-27).
 #include "mg_kernels.h"
-
+#include "mg_device.h"
 
 namespace mg {
 namespace {
-
-__device__ __forceinline__ long long gidx(const Geom &g, int z, int y, int x)
-{
-    return (long long)z * g.plane + (long long)y * g.pitch + x;
-}
 
 // one Jacobi update of a point from its six neighbours (k_sweep3d's expression)
 template <typename T, bool DAMPED>
@@ -68,7 +63,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_small_pre_rr(Geom gf, Geom gc
         const int i = tid + k * SMALL_THREADS;
         const int lx = i % NV, ly = (i / NV) % NV, lz = i / (NV * NV);
         const int x = fx0 - 3 + lx, y = fy0 - 3 + ly, z = fz0 - 3 + lz;
-        bl[k] = (i < NV * NV * NV && inside(z, y, x)) ? rhs[gidx(gf, z, y, x)] : (T)0;
+        bl[k] = (i < NV * NV * NV && inside(z, y, x)) ? rhs[lidx(gf, z, y, x)] : (T)0;
     }
 #pragma unroll
     for (int k = 0; k < IT1; k++) {
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_small_pre_rr(Geom gf, Geom gc
             w = on_bnd(z, y, x) ? b
                                 : jacobi_point<T, DAMPED>(c, omega, b, sv[j], sv[j - NV * NV], sv[j - NV], sv[j - 1], sv[j + 1],
                                                           sv[j + NV], sv[j + NV * NV]);
-            if (lx >= 2 && lx < 2 + FB && ly >= 2 && ly < 2 + FB && lz >= 2 && lz < 2 + FB) u_out[gidx(gf, z, y, x)] = w;
+            if (lx >= 2 && lx < 2 + FB && ly >= 2 && ly < 2 + FB && lz >= 2 && lz < 2 + FB) u_out[lidx(gf, z, y, x)] = w;
         }
         sw[i] = w;
     }
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_small_pre_rr(Geom gf, Geom gc
             }
             val = q * yw[0] + h * yw[1] + q * yw[2];
         }
-        coarse[gidx(gc, K, J, I)] = val;
+        coarse[lidx(gc, K, J, I)] = val;
     }
 }
 
@@ -179,28 +174,28 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_small_prolong_post(Geom gf, G
         const int i = tid + k * SMALL_THREADS;
         const int lx = i % NE, ly = (i / NE) % NE, lz = i / (NE * NE);
         const int x = ex0 + lx, y = ey0 + ly, z = ez0 + lz;
-        el[k] = (i < NE * NE * NE && z >= 0 && z < gc.nz && y >= 0 && y < gc.ny && x >= 0 && x < gc.nx) ? e[gidx(gc, z, y, x)] : (T)0;
+        el[k] = (i < NE * NE * NE && z >= 0 && z < gc.nz && y >= 0 && y < gc.ny && x >= 0 && x < gc.nx) ? e[lidx(gc, z, y, x)] : (T)0;
     }
 #pragma unroll
     for (int k = 0; k < ITW; k++) {
         const int i = tid + k * SMALL_THREADS;
         const int lx = i % NW0, ly = (i / NW0) % NW0, lz = i / (NW0 * NW0);
         const int x = fx0 - 2 + lx, y = fy0 - 2 + ly, z = fz0 - 2 + lz;
-        ul[k] = (i < NW0 * NW0 * NW0 && inside(z, y, x)) ? u[gidx(gf, z, y, x)] : (T)0;
+        ul[k] = (i < NW0 * NW0 * NW0 && inside(z, y, x)) ? u[lidx(gf, z, y, x)] : (T)0;
     }
 #pragma unroll
     for (int k = 0; k < ITV; k++) {
         const int i = tid + k * SMALL_THREADS;
         const int lx = i % NV, ly = (i / NV) % NV, lz = i / (NV * NV);
         const int x = fx0 - 1 + lx, y = fy0 - 1 + ly, z = fz0 - 1 + lz;
-        bv[k] = (i < NV * NV * NV && inside(z, y, x)) ? rhs[gidx(gf, z, y, x)] : (T)0;
+        bv[k] = (i < NV * NV * NV && inside(z, y, x)) ? rhs[lidx(gf, z, y, x)] : (T)0;
     }
 #pragma unroll
     for (int k = 0; k < ITO; k++) {
         const int i = tid + k * SMALL_THREADS;
         const int lx = i % FB, ly = (i / FB) % FB, lz = i / (FB * FB);
         const int x = fx0 + lx, y = fy0 + ly, z = fz0 + lz;
-        bo[k] = (i < FB * FB * FB && inside(z, y, x)) ? rhs[gidx(gf, z, y, x)] : (T)0;
+        bo[k] = (i < FB * FB * FB && inside(z, y, x)) ? rhs[lidx(gf, z, y, x)] : (T)0;
     }
 #pragma unroll
     for (int k = 0; k < ITE; k++) {
@@ -261,7 +256,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void k_small_prolong_post(Geom gf, G
         const int x = fx0 + lx, y = fy0 + ly, z = fz0 + lz;
         if (i >= FB * FB * FB || !inside(z, y, x)) continue;
         const int j = ((lz + 1) * NV + (ly + 1)) * NV + (lx + 1);
-        const long long gi = gidx(gf, z, y, x);
+        const long long gi = lidx(gf, z, y, x);
         const T b = bo[k];
         out[gi] = on_bnd(z, y, x) ? b
                                   : jacobi_point<T, DAMPED>(c, omega, b, sv[j], sv[j - NV * NV], sv[j - NV], sv[j - 1], sv[j + 1],

@@ -13,24 +13,10 @@
 // to the generic k_prolong and to the oracle (same 0.5*(a+b) tree). The odd last fine column is
 // written as one full 128-byte line (see mg_jacobi_fast.hip).
 #include "mg_kernels.h"
+#include "mg_device.h"
 
 namespace mg {
 namespace {
-
-template <typename T> struct PV;
-template <> struct PV<double> { static constexpr int V = 2; typedef double vec __attribute__((ext_vector_type(2))); };
-template <> struct PV<float> { static constexpr int V = 4; typedef float vec __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ float next_lane(float v, float edge)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double next_lane(double v, double edge)
-{
-    int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x130, 0xf, 0xf, false);
-    int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x130, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 
 constexpr int PBW = 4;  // waves per workgroup, stacked over coarse rows
 
@@ -52,8 +38,8 @@ template <typename T, bool ADD, bool SEMI>
 __global__ __launch_bounds__(64 * PBW) void k_prolong3d_fast(Geom gc, Geom gf, const T *__restrict__ coarse,
                                                              T *__restrict__ fine, int nbx, int nby)
 {
-    constexpr int V = PV<T>::V, CV = V / 2;
-    typedef typename PV<T>::vec vec;
+    constexpr int V = Vec16<T>::n, CV = V / 2;
+    typedef typename Vec16<T>::type vec;
     (void)nby;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int bx = blockIdx.x % nbx, by = blockIdx.x / nbx;
@@ -85,7 +71,7 @@ __global__ __launch_bounds__(64 * PBW) void k_prolong3d_fast(Geom gc, Geom gf, c
     }
     T Yn[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) Yn[q] = next_lane(Y[0][q], edge[q]);
+    for (int q = 0; q < 4; q++) Yn[q] = lane_from_next(Y[0][q], edge[q]);
 
     const bool tailwave = (gf.nx % V == 1) && (bx * 64 * V <= gf.nx - 1 - V) && (gf.nx - 1 - V < (bx + 1) * 64 * V);
     // value of the last fine column (x = nx-1, even => coarse column nc-1 = next of the tail lane)
@@ -150,18 +136,6 @@ __global__ __launch_bounds__(64 * PBW) void k_prolong3d_fast(Geom gc, Geom gf, c
 // the oracle's order -- x (q r(x-1) + h r(x) + q r(x+1), r(x-1) from the previous lane by DPP),
 // then y, then z through a three-stage register pipeline -- so the result is bit-identical to
 // k_restrict_fw(k_residual(u)). Coarse boundary nodes inject r(2K,2J,2I).
-__device__ __forceinline__ float prev_lane(float v, float edge)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ double prev_lane(double v, double edge)
-{
-    int lo = __builtin_amdgcn_update_dpp(__double2loint(edge), __double2loint(v), 0x138, 0xf, 0xf, false);
-    int hi = __builtin_amdgcn_update_dpp(__double2hiint(edge), __double2hiint(v), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-
 // One workgroup = CR consecutive coarse rows over their whole width: NW waves side by side in
 // x; each lane evaluates the 2*CR+1 fine residual rows those coarse rows need (neighbouring
 // workgroups recompute the shared odd row: 1.5x residual work for CR = 1, 1.25x for CR = 2).
@@ -171,8 +145,8 @@ __global__ __launch_bounds__(512) void k_resid_restrict_fw(Geom gf, Geom gc, Coe
                                                             const T *__restrict__ rhs_, T *__restrict__ coarse_,
                                                             int nby, int nbz, int zcc, int dup_kc, int dup_nzf)
 {
-    constexpr int V = PV<T>::V, CV = V / 2, NR = 2 * CR + 1;
-    typedef typename PV<T>::vec vec;
+    constexpr int V = Vec16<T>::n, CV = V / 2, NR = 2 * CR + 1;
+    typedef typename Vec16<T>::type vec;
     __shared__ T edge[2][8][NR];  // [slot][wave][row]: last residual element of each wave
     // u on the wave edges, published one plane ahead (as in k_jacobi2): the x-neighbour of a wave's
     // first / last lane is the neighbouring wave's last / first element; only the row's very last
@@ -182,8 +156,7 @@ __global__ __launch_bounds__(512) void k_resid_restrict_fw(Geom gf, Geom gc, Coe
     // dup_kc > 0: the launch covers a second single coarse plane, dup_kc coarse planes (2 dup_kc fine planes) further up,
     // with dup_nzf fine planes: the second half of the workgroups shift pointers and plane indices (all scalar)
     const int nblocks = nby * nbz, ntotal = dup_kc > 0 ? 2 * nblocks : nblocks;
-    const int per = (ntotal + 7) >> 3;
-    int bid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);        // XCD-aware order
+    int bid = xcd_block(blockIdx.x, (ntotal + 7) >> 3);
     if (bid >= ntotal) return;                                    // whole workgroup
     const bool second = bid >= nblocks;
     if (second) { bid -= nblocks; gf.gz0 += 2 * dup_kc; gf.nz = dup_nzf; gc.gz0 += dup_kc; }
@@ -280,8 +253,8 @@ __global__ __launch_bounds__(512) void k_resid_restrict_fw(Geom gf, Geom gc, Coe
 #pragma unroll
         for (int r = 0; r < NR; r++) {
             const T el = elv[r], er = erv[r];
-            const T xm = prev_lane(uc[r][V - 1], el);
-            const T xp = next_lane(uc[r][0], er);
+            const T xm = lane_from_prev(uc[r][V - 1], el);
+            const T xp = lane_from_next(uc[r][0], er);
             const vec ym = (r == 0) ? hlo : uc[r > 0 ? r - 1 : 0];
             const vec yp = (r == NR - 1) ? hhi : uc[r < NR - 1 ? r + 1 : 0];
             const bool rb = zb || ybnd[r];
@@ -317,7 +290,7 @@ __global__ __launch_bounds__(512) void k_resid_restrict_fw(Geom gf, Geom gc, Coe
 #pragma unroll
         for (int r = 0; r < NR; r++) {
             const T from_left_wave = (lane == 0 && wv > 0) ? edge[slot][wv - 1][r] : (T)0;
-            const T rprev = prev_lane(res[r][V - 1], from_left_wave);
+            const T rprev = lane_from_prev(res[r][V - 1], from_left_wave);
 #pragma unroll
             for (int m = 0; m < CV; m++) {
                 const T rleft = (m == 0) ? rprev : res[r][2 * m - 1 > 0 ? 2 * m - 1 : 0];
@@ -366,27 +339,25 @@ __global__ __launch_bounds__(512) void k_resid_restrict_fw(Geom gf, Geom gc, Coe
 
 }  // namespace
 
-static bool transfer_is_semi(const Geom &gf, const Geom &gc) { return gf.dim == 3 && gf.gnz == gc.gnz && gf.gnz > 1; }
-
 template <typename T>
 bool prolong_fast_ok(const Geom &gc, const Geom &gf)
 {
-    constexpr int V = PV<T>::V;
+    constexpr int V = Vec16<T>::n;
     if (!(gf.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 && gc.nx >= 17 && (gf.nx % V) == 1)) return false;
-    if (transfer_is_semi(gf, gc)) return gf.gz0 == gc.gz0 && gf.nz == gc.nz;
+    if (is_semi_transition(gf, gc)) return gf.gz0 == gc.gz0 && gf.nz == gc.nz;
     return gf.gz0 == 2 * gc.gz0 && gf.nz <= 2 * gc.nz && gf.nz >= 2 * gc.nz - 1;
 }
 
 template <typename T>
 void launch_prolong_fast(hipStream_t s, const Geom &gc, const Geom &gf, const T *coarse, T *fine, bool add)
 {
-    constexpr int CV = PV<T>::V / 2;
+    constexpr int CV = Vec16<T>::n / 2;
     // lanes cover coarse columns 0 .. nc-2 (the last coarse column only feeds the tail)
     const int ncol = gc.nx - 1;
     const int nbx = (ncol + 64 * CV - 1) / (64 * CV);
     const int nby = (gc.ny + PBW - 1) / PBW;
     dim3 gr(nbx * nby, gc.nz), bl(64 * PBW);
-    if (transfer_is_semi(gf, gc)) {
+    if (is_semi_transition(gf, gc)) {
         if (add) hipLaunchKernelGGL((k_prolong3d_fast<T, true, true>), gr, bl, 0, s, gc, gf, coarse, fine, nbx, nby);
         else hipLaunchKernelGGL((k_prolong3d_fast<T, false, true>), gr, bl, 0, s, gc, gf, coarse, fine, nbx, nby);
     } else {
@@ -407,8 +378,8 @@ namespace mg {
 template <typename T>
 bool resid_restrict_fast_ok(const Geom &gf, const Geom &gc)
 {
-    constexpr int V = PV<T>::V;
-    const bool zok = transfer_is_semi(gf, gc) ? gf.nz == gc.nz : gf.nz == 2 * gc.nz - 1;
+    constexpr int V = Vec16<T>::n;
+    const bool zok = is_semi_transition(gf, gc) ? gf.nz == gc.nz : gf.nz == 2 * gc.nz - 1;
     return gf.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 && zok &&
            gf.gz0 == 0 && gc.gz0 == 0 && gf.gnz == gf.nz && gc.gnz == gc.nz && gc.nx >= 17 && (gf.nx % V) == 1 &&
            (gc.nx - 1 + 64 * (V / 2) - 1) / (64 * (V / 2)) <= 8;
@@ -419,8 +390,8 @@ bool resid_restrict_fast_ok(const Geom &gf, const Geom &gc)
 template <typename T>
 bool resid_restrict_slab_ok(const Geom &gf, const Geom &gc)
 {
-    constexpr int V = PV<T>::V;
-    const bool semi = transfer_is_semi(gf, gc);
+    constexpr int V = Vec16<T>::n;
+    const bool semi = is_semi_transition(gf, gc);
     const bool zok = semi ? (gf.nz == gc.nz && gf.gz0 == gc.gz0)
                           : (gf.gz0 == 2 * gc.gz0 && (gf.nz == 2 * gc.nz || gf.nz == 2 * gc.nz - 1) && gf.gnz == 2 * gc.gnz - 1);
     return gf.dim == 3 && gf.nx == 2 * gc.nx - 1 && gf.ny == 2 * gc.ny - 1 && zok && gc.nz >= 1 && gc.nx >= 17 && (gf.nx % V) == 1 &&
@@ -432,7 +403,7 @@ void launch_resid_restrict_fw(hipStream_t s, const Geom &gf, const Geom &gc, con
                               const T *rhs, T *coarse, int dup_kc, int dup_nzf)
 {
     if (rr_wide_ok<T>(gf, gc)) { launch_rr_wide<T>(s, gf, gc, c, u, rhs, coarse, dup_kc, dup_nzf); return; }
-    constexpr int CV = PV<T>::V / 2;
+    constexpr int CV = Vec16<T>::n / 2;
     constexpr int CR = 1;                                     // coarse rows per workgroup (2 measured slower again after the mailbox change: 185 VGPRs, 3.28 vs 3.10 ms per cycle)
     const int ncol = gc.nx - 1;                               // coarse columns owned by lanes
     const int nw = (ncol + 64 * CV - 1) / (64 * CV);          // waves side by side in x (<= 8)
@@ -454,7 +425,7 @@ void launch_resid_restrict_fw(hipStream_t s, const Geom &gf, const Geom &gc, con
     const dim3 bl(64 * nw);
 #define MG_RR(SEMI) \
     hipLaunchKernelGGL((k_resid_restrict_fw<T, false, CR, SEMI>), dim3(grid), bl, 0, s, gf, gc, c, u, rhs, coarse, nby, nbz, zcc, dup_kc, dup_nzf)
-    if (transfer_is_semi(gf, gc)) MG_RR(true);
+    if (is_semi_transition(gf, gc)) MG_RR(true);
     else MG_RR(false);
 #undef MG_RR
 }
