@@ -174,6 +174,12 @@ FMG_ROWS = [
          smoother=capi.SMOOTH_JACOBI, omega=6 / 7),
     dict(id="3d-f64-257-jacobi", gate="wide-tile pair on level 0; the cycle started on level 1 (129^3) folds the prolongation",
          dim=3, n=257, levels=5, dtype=capi.MG_F64, smoother=capi.SMOOTH_JACOBI, omega=6 / 7, ks=(1,)),
+    # sweep counts off (2,2): fmg_t starts cycles on inner levels from the interpolated, non-zero iterate (u_zero = false on
+    # level l > 0), and no level may take the V(2,2)-only small-level kernels
+    dict(id="3d-f64-65-jacobi-v12", gate="V(1,2): single pre-sweep, sweep-by-sweep on every small_fused_ok level", dim=3, n=65,
+         levels=3, dtype=capi.MG_F64, smoother=capi.SMOOTH_JACOBI, omega=6 / 7, nu_pre=1, nu_post=2),
+    dict(id="3d-f64-65-rbgs-v11", gate="V(1,1) red-black: colour kernels, one sweep either side", dim=3, n=65, levels=3,
+         dtype=capi.MG_F64, smoother=capi.SMOOTH_RBGS, omega=1.0, nu_pre=1, nu_post=1),
 ]
 
 

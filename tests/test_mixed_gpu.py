@@ -138,6 +138,8 @@ SOLVE_CASES = {
     "3d65-v22": dict(dim=3, n=65, levels=4, length=1.0, **V22, omega=6 / 7, **FIXED),
     "3d65-rb": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, smoother=capi.SMOOTH_RBGS), **FIXED),
     "3d65-aniso-semi": dict(dim=3, n=65, levels=5, length=1.0, **V22, omega=0.8, aniso=(1.0, 1.0, 0.01), semi_xy=2, **FIXED),
+    # sweep counts off (2,2): mixed_inner runs the same cycle driver, from a non-zero state from the second inner cycle on
+    "3d65-v13": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, nu_pre=1, nu_post=3), omega=6 / 7, **FIXED),
 }
 
 

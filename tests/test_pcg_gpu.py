@@ -192,6 +192,9 @@ SOLVE_CASES = {
     "3d65-aniso-semi": dict(dim=3, n=65, levels=5, length=1.0, **V22, omega=0.8, aniso=(1.0, 1.0, 0.01), semi_xy=2, **FIXED),
     "2d97-v22": dict(dim=2, n=97, levels=3, length=1.0, **V22, omega=0.8, **FIXED),
     "2d385-v22": dict(dim=2, n=385, levels=4, length=1.0, **V22, omega=0.8, **FIXED),
+    # sweep counts off (2,2): precondition_t runs the same cycle driver; V(1,1) keeps the preconditioner symmetric, V(3,1) does not
+    "3d65-v11": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, nu_pre=1, nu_post=1), omega=6 / 7, **FIXED),
+    "3d65-v31": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, nu_pre=3, nu_post=1), omega=6 / 7, **FIXED),
 }
 
 

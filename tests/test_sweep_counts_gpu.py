@@ -1,0 +1,245 @@
+"""V(nu_pre, nu_post) cycles other than V(2,2) through the GPU cycle drivers, against the CPU oracle bit for bit.
+
+The driver (mg_solver.cpp: smooth_t, vcycle_rec_t, can_fold_prolong, can_skip_zeroing, pair_norm_ok, Solver::solve) branches
+on the two sweep counts more than on anything else: pairs and odd singles, the prolongation folded into the first
+post-smoothing launch or applied on its own, the zero guess as a flag or as a memset, the small-level kernels that exist for
+V(2,2) only, the residual norm riding on the first pre-smoothing launch of mg_solve. tests/test_independent_reference.py
+pins the oracle to the numpy reference for sweep counts off (2,2) (test_oracle_cycles_against_npref), so the comparison here
+is bit-exact: two cycles from a random state with random Dirichlet data, then a three-cycle mg_solve. Nothing here asserts
+convergence: V(0,n), V(n,0) and red-black with injection need not converge.
+
+The first cycle of every case is profiled and its finest-level launch kinds are compared with expected(), a Python
+statement of vcycle_rec_t's decisions, so that each row proves which branch it ran.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from tests.switch_table import fallbacks
+from tests.test_independent_reference import jacobi2_ok, resid_restrict_fast_ok
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+DEFAULT_NU = [(1, 1), (1, 2), (2, 1), (3, 3), (0, 2), (2, 0), (4, 3)]
+# nu_post = 4 is in no pair of the default set: the two rows whose post-smoothing has the most branches (the folding
+# launch, then a pair / three plain sweeps) add one
+WITH_POST4 = DEFAULT_NU + [(3, 4)]
+
+J67 = dict(smoother=po.SMOOTH_JACOBI, omega=6 / 7)
+J08 = dict(smoother=po.SMOOTH_JACOBI, omega=0.8)
+RB = dict(smoother=po.SMOOTH_RBGS, omega=1.0)
+FW, INJ = dict(restriction=po.RESTRICT_FULLW), dict(restriction=po.RESTRICT_INJECT)
+F64, F32 = dict(dtype=po.MG_F64), dict(dtype=po.MG_F32)
+
+# gate: the branch of mg_solver.cpp the row is there for. nus: the sweep-count pairs it runs (rows of n >= 257 only those
+# their gate names). pair_norm: mg_solve once more in a child process with MG_PAIR_NORM=0.
+ROWS = [
+    dict(id="f64-33", gate="fast_path_ok: yes, jacobi2_ok: no (16 vectors): single sweeps only, separate prolongation",
+         desc=dict(dim=3, n=33, levels=3, **F64, **J67, **FW), nus=DEFAULT_NU),
+    dict(id="f64-65", gate="small_fused_ok shape: any nu != (2,2) must leave the brick kernels of mg_small_levels.hip "
+         "(sweep by sweep, the oracle's bits); (2,2) is the control that takes them in the unprofiled cycles",
+         desc=dict(dim=3, n=65, levels=3, **F64, **J67, **FW), nus=DEFAULT_NU + [(2, 2)]),
+    dict(id="f64-129-j", gate="jacobi2_ok on level 0: pair + single, fold on/off by nu_post >= 2, prolong_t alone at "
+         "nu_post = 0; level 1 (65^3): zero-guess single at nu_pre = 1, real zeroing at nu_pre = 0",
+         desc=dict(dim=3, n=129, levels=4, **F64, **J67, **FW), nus=WITH_POST4),
+    dict(id="f64-129-rb", gate="rb_fused_ok: the one-pass sweep folds at nu_post >= 1, sweeps >= 1 are plain, zero-guess "
+         "first sweep on level 1", desc=dict(dim=3, n=129, levels=4, **F64, **RB, **FW), nus=WITH_POST4),
+    dict(id="f64-129-inj", gate="injection: unfused residual + restriction beside the folded prolongation",
+         desc=dict(dim=3, n=129, levels=3, **F64, **J08, **INJ), nus=DEFAULT_NU),
+    dict(id="f64-257-j", gate="wide-tile pair; level 1 (129^3): zero-guess pair + single at nu_pre = 3, zero-guess single "
+         "at nu_pre = 1; mg_solve takes the separate-norm loop whenever nu_pre != 2 and the pair's norm at nu_pre = 2",
+         desc=dict(dim=3, n=257, levels=5, **F64, **J08, **FW), nus=[(1, 1), (3, 3), (2, 0), (1, 2)], pair_norm=True),
+    dict(id="f64-257-rb", gate="pair_norm_ok for every nu_pre >= 1: Solver::solve leaves left = 0 (nu_pre = 1) and left = 2 "
+         "(nu_pre = 3) sweeps to the cycle; nu_pre = 0: the separate-norm loop",
+         desc=dict(dim=3, n=257, levels=5, **F64, **RB, **FW), nus=[(1, 1), (3, 3), (2, 0), (0, 2)], pair_norm=True),
+    dict(id="f32-257-j", gate="fp32 rows of 64 vectors: the folding pair, then a single (nu_post = 3)",
+         desc=dict(dim=3, n=257, levels=4, **F32, **J67, **FW), nus=[(1, 1), (3, 3), (2, 0)]),
+    # (nu_pre in {1, 3} only: every case of this row holds 1.35e8 unknowns on both sides)
+    dict(id="f32-513-rb", gate="fp32 wide tile with the norm on the first sweep of mg_solve: left = 0 and left = 2",
+         desc=dict(dim=3, n=513, levels=3, **F32, **RB, **FW), nus=[(1, 1), (3, 3)], pair_norm=True),
+    dict(id="f64-65-semi", gate="semi-coarsened transfers with odd sweep counts",
+         desc=dict(dim=3, n=65, levels=4, **F64, **J08, **FW, semi_xy=2, aniso=(1.0, 1.0, 0.05)), nus=DEFAULT_NU),
+    dict(id="f64-65-zy", gate="zebra lines along y: 2 * sweeps colour launches",
+         desc=dict(dim=3, n=65, levels=3, **F64, smoother=po.SMOOTH_ZEBRA_Y, omega=1.0, **FW, aniso=(1.0, 30.0, 1.0)),
+         nus=DEFAULT_NU),
+    dict(id="2d-129", gate="2-D generic kernels: red-black colour launches, separate residual, restriction and prolongation",
+         desc=dict(dim=2, n=129, levels=5, **F64, **RB, **FW), nus=DEFAULT_NU),
+]
+ROW = {r["id"]: r for r in ROWS}
+CASES = [(r["id"], nu) for r in ROWS for nu in r["nus"]]
+
+# the rows and pairs repeated with one FALLBACK switch of mg_switches.def at 0 (one child process per switch)
+FALLBACK_CASES = [("f64-129-j", (3, 3)), ("f64-129-j", (1, 2)), ("f64-129-rb", (1, 1))]
+FALLBACK_VARS = fallbacks("MG_FUSED_PAIR", "MG_FUSED_PROLONG", "MG_FUSED_RB", "MG_SMALL_FUSED", "MG_FAST_DIV")
+
+KINDS = ("SMOOTH", "SMOOTH_PROLONG", "RESID_RESTRICT", "PROLONG")
+
+
+def _id(case):
+    return f"{case[0]}-v{case[1][0]}{case[1][1]}"
+
+
+def case_kw(row, nu):
+    return dict(row["desc"], length=1.0, alpha=1.0, cycle=po.CYCLE_V, nu_pre=nu[0], nu_post=nu[1],
+                coarse_mode=po.COARSE_FIXED, coarse_maxit=8, outer_pre_gs=0)
+
+
+def test_table_covers_every_sweep_count_for_both_point_smoothers():
+    """(CPU) every nu_pre and nu_post in 0..4 is run with Jacobi and with red-black Gauss-Seidel"""
+    for sm in (po.SMOOTH_JACOBI, po.SMOOTH_RBGS):
+        nus = [nu for r in ROWS if r["desc"]["smoother"] == sm for nu in r["nus"]]
+        assert {a for a, _ in nus} >= set(range(5)), (sm, "nu_pre")
+        assert {b for _, b in nus} >= set(range(5)), (sm, "nu_post")
+    for r in ROWS:   # and no row of n >= 257 lost the pairs every row keeps
+        if r["id"] != "f32-513-rb":
+            assert {(1, 1), (3, 3), (2, 0)} <= set(r["nus"]), r["id"]
+    assert all(ROW[rid]["nus"].count(nu) == 1 for rid, nu in FALLBACK_CASES)
+
+
+def expected(row, nu, env_off=()):
+    """finest-level launch kinds of one profiled cycle, from mg_solver.cpp: vcycle_rec_t and smooth_t (level 0 of a
+    one-rank solver; a profiled level 0 never takes the small-level kernels)"""
+    d = row["desc"]
+    n, dt, sm, dim3 = d["n"], d["dtype"], d["smoother"], d["dim"] == 3
+    j2 = dim3 and jacobi2_ok(n, dt) and "MG_FUSED_PAIR" not in env_off
+    rbf = j2 and "MG_FUSED_RB" not in env_off                       # rb_fused_ok
+
+    def launches(s):                                                # smooth_t's count for a call of s sweeps
+        if sm == po.SMOOTH_JACOBI:
+            return (s + 1) // 2 if j2 else s                        # one per full pair + one for the odd sweep
+        if sm == po.SMOOTH_RBGS:
+            return s if rbf else 2 * s                              # one-pass sweeps, else two colour launches
+        return 2 * s                                                # zebra: two colour launches per sweep
+
+    # can_fold_prolong: the smoother's own condition, and jacobi2_corr_ok (jacobi2_ok + a standard coarsening below level 0)
+    sm_ok = (sm == po.SMOOTH_JACOBI and nu[1] >= 2) or (sm == po.SMOOTH_RBGS and nu[1] >= 1 and rbf)
+    fold = sm_ok and j2 and not d.get("semi_xy", 0) and "MG_FUSED_PROLONG" not in env_off
+    rr = dim3 and d["restriction"] == po.RESTRICT_FULLW and resid_restrict_fast_ok(n, (n - 1) // 2 + 1, dt)
+    return dict(SMOOTH=launches(nu[0]) + (0 if fold else launches(nu[1])), SMOOTH_PROLONG=launches(nu[1]) if fold else 0,
+                RESID_RESTRICT=1 if rr else 2, PROLONG=0 if fold else 1)
+
+
+def problem(row):
+    """random right-hand side and initial guess, Dirichlet values included; the same arrays in every process"""
+    d = row["desc"]
+    dt = np.float64 if d["dtype"] == po.MG_F64 else np.float32
+    rng = np.random.default_rng(d["n"] + 7)
+    shape = (d["n"],) * d["dim"]
+    b = rng.standard_normal(shape).astype(dt)
+    u0 = (0.1 * rng.standard_normal(shape)).astype(dt)
+    return b, u0
+
+
+def gpu_run(row, nu, env_off=(), oracle=None):
+    """two cycles (the first one profiled) and a three-cycle mg_solve on the GPU -> (history, solution); with `oracle`
+    (a po.Solver in the same state) every step is compared with it"""
+    from multigrid_prj_amd import capi
+    b, u0 = problem(row)
+    with capi.Solver(capi.make_desc(**case_kw(row, nu))) as s:
+        s.set_rhs(b); s.set_solution(u0)
+        if oracle:
+            oracle.set_rhs(b); oracle.set_solution(u0)
+        del b, u0
+        for k in range(2):
+            if k == 0:
+                s.profile_begin()
+            st = s.cycle()
+            if k == 0:
+                s.profile_end()
+                got = {kd: s.profile_get(getattr(capi, "PROF_" + kd))[1] for kd in KINDS}
+                assert got == expected(row, nu, env_off), (got, expected(row, nu, env_off), row["gate"])
+            assert st.coarse_iters == 8
+            if oracle:
+                oracle.cycle()
+                assert np.array_equal(s.get_solution(), oracle.get_solution()), (f"cycle {k}", row["gate"])
+        hist, _ = s.solve(0.0, 3)
+        u = s.get_solution()
+    assert len(hist) == 4
+    if oracle:
+        ho, _ = oracle.solve(0.0, 3)
+        print(row["id"], nu, "history gpu", hist, "oracle", ho)
+        assert np.array_equal(u, oracle.get_solution()), ("mg_solve", row["gate"])
+        np.testing.assert_allclose(hist, ho, rtol=1e-10 if row["desc"]["dtype"] == po.MG_F64 else 1e-4)
+    return hist, u
+
+
+def run_case(row, nu, env_off=()):
+    o = po.Solver(po.make_desc(**case_kw(row, nu)))
+    try:
+        gpu_run(row, nu, env_off, oracle=o)
+    finally:
+        o.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=_id)
+def test_cycles_and_solve_equal_the_oracle(case):
+    run_case(ROW[case[0]], case[1])
+
+
+_CHILD_FALLBACK = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+from tests import test_sweep_counts_gpu as t
+for rid, nu in t.FALLBACK_CASES:
+    t.run_case(t.ROW[rid], nu, (sys.argv[2],))
+print("child ok")
+"""
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("var", FALLBACK_VARS)
+def test_fallback_switches_keep_the_bits_off_v22(var):
+    """The switch is read once per process: a child process repeats FALLBACK_CASES with it at 0 -- the same oracle
+    comparison, and the launch kinds the fallback path makes."""
+    p = subprocess.run([sys.executable, "-c", _CHILD_FALLBACK, ROOT, var], env=dict(os.environ, **{var: "0"}), cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "child ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+
+
+_CHILD_NORM = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from tests import test_sweep_counts_gpu as t
+row = t.ROW[sys.argv[2]]
+for i, nu in enumerate(row["nus"]):
+    hist, u = t.gpu_run(row, nu)
+    np.save(sys.argv[3] + f"/hist{i}.npy", hist)
+    np.save(sys.argv[3] + f"/u{i}.npy", u)
+print("child ok")
+"""
+
+
+def pair_norm_possible(row, nu):
+    """pair_norm_ok of the rows that set pair_norm (wide-tile level 0, one rank): Jacobi rides the norm on the pair of
+    exactly two pre-smoothing sweeps, red-black on the first sweep of any"""
+    return nu[0] == 2 if row["desc"]["smoother"] == po.SMOOTH_JACOBI else nu[0] >= 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rid", [r["id"] for r in ROWS if r.get("pair_norm")])
+def test_solve_without_the_fused_norm_gives_the_same_history_and_bits(rid, tmp_path):
+    """mg_solve with MG_PAIR_NORM=0 (a child process: the switch is read once) takes the separate-norm loop: as many history
+    entries, each equal to the default run's up to the order of the sum (1e-12 fp64 / 1e-6 fp32) -- and exactly equal where
+    pair_norm_ok is false anyway and the switch must be inert -- and the same iterate bit for bit."""
+    row = ROW[rid]
+    var = fallbacks("MG_PAIR_NORM")[0]
+    p = subprocess.run([sys.executable, "-c", _CHILD_NORM, ROOT, rid, str(tmp_path)], env=dict(os.environ, **{var: "0"}),
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "child ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+    for i, nu in enumerate(row["nus"]):
+        hist, u = gpu_run(row, nu)
+        h0 = np.load(os.path.join(tmp_path, f"hist{i}.npy"))
+        print(rid, nu, "default", hist, "MG_PAIR_NORM=0", h0)
+        assert len(h0) == len(hist)
+        if pair_norm_possible(row, nu):
+            np.testing.assert_allclose(hist, h0, rtol=1e-12 if row["desc"]["dtype"] == po.MG_F64 else 1e-6)
+        else:
+            assert np.array_equal(hist, h0), nu
+        assert np.array_equal(u, np.load(os.path.join(tmp_path, f"u{i}.npy"))), nu
+        del u
