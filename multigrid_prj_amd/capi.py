@@ -324,6 +324,10 @@ class Solver:
     def coarse_solve(self, level, arr_x, arr_rhs) -> MgCycleStats:
         st = MgCycleStats(); _check(self.lib.mg_coarse_solve(self.h, level, arr_x, arr_rhs, C.byref(st))); return st
 
+    def coarse_solve_ex(self, level, arr_x, arr_rhs, smoother, maxit, tol, fixed=False) -> MgCycleStats:
+        st = MgCycleStats()
+        _check(self.lib.mg_coarse_solve_ex(self.h, level, arr_x, arr_rhs, smoother, maxit, tol, int(fixed), C.byref(st))); return st
+
     def cycle(self) -> MgCycleStats:
         st = MgCycleStats(); _check(self.lib.mg_cycle(self.h, C.byref(st))); return st
 

@@ -157,6 +157,83 @@ inline ChunkPlan chunk_plan(int nz, int nby, int ncopy, int ncu, int min_items_p
     return {(int)(((items + 7) / 8) * 8), best_zc};
 }
 
+// ---- which kernel solves the coarsest grid (launch_coarse_solve, mg_kernels.hip) ------------------------------------
+// One workgroup runs the whole Solver::Solve loop; which kernel depends on the shape, the element size, the smoother and
+// omega. Pure: the caller passes its switches (MG_COARSE_ROWS, MG_COARSE_RB_ROWS, MG_COARSE_GS_ROWS) and launches what the
+// plan says; tests/test_coarse_plan_cpu.py sweeps it over every shape a descriptor can make coarsest and
+// tests/coarse_table.py lists what is reachable.
+//  * JACOBI_ROWS / RB_ROWS: a thread owns a run of `seg` interior points of one row. The runs must be full and may share
+//    at most one point per row (`overlap`), 128 <= threads <= 1024 (512 for runs of 7 and 8: registers). The first run
+//    length of the measured order of preference that fits the ROW is taken (2-D: 65^2 -> 8, 504 threads, two waves per
+//    SIMD: 52 ms for BASELINE config 1 against 55 ms with 7 and 64 ms with 9; 3-D: 17^3 -> 5, 675 threads; 8 is 2 % slower
+//    per V-cycle at 513^3); when that one then lacks LDS room no other length is tried. Only these two take the zero
+//    guess as a flag (zero_x); for every other kernel the launcher clears x first (memset).
+//  * skip (Jacobi rows): sweeps between two norm tests. 8 needs a third LDS array (the window's first iterate) and
+//    0 < omega <= 1 (damped Jacobi on this operator is then a contraction in the 2-norm, so the norm cannot dip below
+//    the tolerance and rise again inside a window); otherwise 1, every sweep tested.
+//  * GS_ROWS2D: lexicographic Gauss-Seidel, 2-D, at most 256 rows, two LDS copies.
+//  * LDS: the generic loop, three arrays in LDS, at most 5 points per thread. GLOBAL: the global-memory loop.
+constexpr int COARSE_WG = 1024, COARSE_GS_WG = 256, COARSE_LDS_PT = 5, COARSE_SKIP = 8;
+constexpr long long COARSE_LDS_MAX = 150 * 1024;
+enum CoarseKernel { COARSE_JACOBI_ROWS = 0, COARSE_RB_ROWS = 1, COARSE_GS_ROWS2D = 2, COARSE_LDS = 3, COARSE_GLOBAL = 4 };
+struct CoarsePlan {
+    int kernel;           // CoarseKernel
+    int seg;              // run length (row kernels), 0 otherwise
+    int overlap;          // the last run of a row shares one point with its neighbour
+    int skip;             // Jacobi rows: 8 or 1; 0 otherwise
+    int threads;          // workgroup size as launched
+    long long lds_bytes;  // dynamic LDS
+    int zero_x;           // the kernel takes the zero guess as a flag
+    int memset;           // the launcher clears x before the kernel
+};
+
+inline int coarse_rows_max_threads(int seg) { return seg >= 7 ? COARSE_WG / 2 : COARSE_WG; }
+
+// run length of a row kernel for this shape: the first of `order` whose runs fit; 0 = none
+inline int coarse_rows_seg(int dim, int nx, int ny, int nz, const int *order, int norder)
+{
+    if (ny < 3 || (dim == 3 && nz < 3)) return 0;
+    const int W = nx - 2, irows = (ny - 2) * (dim == 3 ? nz - 2 : 1);
+    for (int k = 0; k < norder; k++) {
+        const int seg = order[k], nseg = (W + seg - 1) / seg, threads = nseg * irows;
+        if (W < seg || nseg * seg - W > 1 || threads < 128 || threads > coarse_rows_max_threads(seg)) continue;
+        return seg;
+    }
+    return 0;
+}
+
+inline CoarsePlan coarse_plan(int dim, int nx, int ny, int nz, int elem_size, int smoother, double omega, bool x_is_zero,
+                              bool whole_level, bool coarse_rows, bool coarse_rb_rows, bool coarse_gs_rows)
+{
+    const long long total = (long long)nx * ny * nz;
+    const int clear = x_is_zero ? 1 : 0;
+    auto rows = [&](int kernel, int seg, int skip, int copies) {
+        const int W = nx - 2, nseg = (W + seg - 1) / seg;
+        const int threads = nseg * (ny - 2) * (dim == 3 ? nz - 2 : 1);
+        return CoarsePlan{kernel, seg, nseg * seg - W, skip, ((threads + 63) / 64) * 64, copies * total * elem_size, clear, 0};
+    };
+    if (smoother == 1 && whole_level && coarse_rows) {  // Jacobi
+        static const int order2[4] = {8, 4, 7, 5}, order3[4] = {5, 4, 8, 7};
+        const int seg = coarse_rows_seg(dim, nx, ny, nz, dim == 3 ? order3 : order2, 4);
+        int skip = COARSE_SKIP;
+        if (3 * total * elem_size > COARSE_LDS_MAX) skip = 1;   // no room for the window's first iterate
+        if (!(omega > 0 && omega <= 1)) skip = 1;
+        const int copies = skip > 1 ? 3 : 2;
+        if (seg && copies * total * elem_size <= COARSE_LDS_MAX) return rows(COARSE_JACOBI_ROWS, seg, skip, copies);
+    }
+    if (smoother == 2 && whole_level && coarse_rb_rows) {  // red-black (runs of 7 / 8 points: the colour selects went through scratch memory)
+        static const int order[2] = {5, 4};
+        const int seg = coarse_rows_seg(dim, nx, ny, nz, order, 2);
+        if (seg && 2 * total * elem_size <= COARSE_LDS_MAX) return rows(COARSE_RB_ROWS, seg, 0, 2);
+    }
+    if (smoother == 0 && coarse_gs_rows && dim == 2 && ny <= COARSE_GS_WG && nx >= 3 && ny >= 3 &&
+        2 * (long long)nx * ny * elem_size <= COARSE_LDS_MAX)
+        return CoarsePlan{COARSE_GS_ROWS2D, 0, 0, 0, COARSE_GS_WG, 2 * (long long)nx * ny * elem_size, 0, clear};
+    if (total <= (long long)COARSE_LDS_PT * COARSE_WG && 3 * total * elem_size <= COARSE_LDS_MAX)
+        return CoarsePlan{COARSE_LDS, 0, 0, 0, COARSE_WG, 3 * total * elem_size, 0, clear};
+    return CoarsePlan{COARSE_GLOBAL, 0, 0, 0, COARSE_WG, 0, 0, clear};
+}
+
 struct CoarseOut {
     int iters;
     int flag;

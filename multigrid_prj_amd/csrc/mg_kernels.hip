@@ -1688,129 +1688,97 @@ void launch_correct(hipStream_t s, const Geom &g, T *u, T *e)
     hipLaunchKernelGGL((k_correct<T>), gr, bl, 0, s, g, u, e);
 }
 
-template <typename T, int DIM, int PT>
-static bool try_launch_coarse_lds(hipStream_t s, const Geom &g, const Coef<T> &c, T omega, int smoother, T *x,
+// ---- coarse solve: mg::coarse_plan (mg_geom.h) decides, the functions below launch what it says -------------------
+static_assert(COARSE_WG == SWG && COARSE_GS_WG == CGS_THREADS, "coarse_plan sizes its workgroups with these");
+
+// LDS above the default limit needs the attribute once per kernel; false: the runtime refused it
+template <typename K>
+static bool coarse_lds_attr(K kern, bool &attr_set)
+{
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)COARSE_LDS_MAX) != hipSuccess) return false;
+        attr_set = true;
+    }
+    return true;
+}
+
+template <typename T, int DIM>
+static bool try_launch_coarse_lds(hipStream_t s, const CoarsePlan &p, const Geom &g, const Coef<T> &c, T omega, int smoother, T *x,
                                   const T *rhs, int maxit, double tol, int fixed, CoarseOut *d_out)
 {
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
-    const size_t bytes = 3 * total * sizeof(T);
-    if (total > (size_t)PT * SWG || bytes > (size_t)150 * 1024) return false;
-    auto kern = k_coarse_solve_lds<T, DIM, PT>;
+    auto kern = k_coarse_solve_lds<T, DIM, COARSE_LDS_PT>;
     static bool attr_set = false;  // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                150 * 1024) != hipSuccess) return false;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(SWG), bytes, s, g, c, omega, smoother, x, rhs, maxit, tol, fixed, d_out);
+    if (!coarse_lds_attr(kern, attr_set)) return false;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(p.threads), (size_t)p.lds_bytes, s, g, c, omega, smoother, x, rhs, maxit, tol, fixed, d_out);
     return true;
 }
 
-
 template <typename T, int DIM, int SEG>
-static bool try_launch_coarse_jacobi_rows(hipStream_t s, const Geom &g, const Coef<T> &c, T omega, T *x,
-                                          const T *rhs, int maxit, double tol, int fixed, CoarseOut *d_out, int zero_x)
+static bool try_launch_coarse_jacobi_rows(hipStream_t s, const CoarsePlan &p, const Geom &g, const Coef<T> &c, T omega, T *x,
+                                          const T *rhs, int maxit, double tol, int fixed, CoarseOut *d_out)
 {
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
-    constexpr int COARSE_SKIP = 8;   // sweeps between two norm tests (1 = test after every sweep, the plain loop)
-    int skip = COARSE_SKIP;
-    if (3 * total * sizeof(T) > (size_t)150 * 1024) skip = 1;   // no room for the window's first iterate
-    // the windowed norm test equals the reference's test per sweep only while the residual norm cannot dip below the tolerance
-    // and rise again inside a window: guaranteed for 0 < omega <= 1 (damped Jacobi on this operator is a contraction in the
-    // 2-norm), not outside that range -- there every sweep is tested
-    if (!(omega > (T)0 && omega <= (T)1)) skip = 1;
-    const size_t bytes = (skip > 1 ? 3 : 2) * total * sizeof(T);
-    const int W = g.nx - 2, nseg = (W + SEG - 1) / SEG;
-    if (W < SEG || nseg * SEG - W > 1) return false;  // full runs, at most one shared point per row
-    const int threads = nseg * (g.ny - 2) * (DIM == 3 ? g.nz - 2 : 1);
-    if (threads < 128 || threads > CoarseRowsThreads<SEG>::value || bytes > (size_t)150 * 1024) return false;
+    static_assert(CoarseRowsThreads<SEG>::value == (SEG >= 7 ? COARSE_WG / 2 : COARSE_WG), "coarse_rows_max_threads");
     auto kern = k_coarse_jacobi_rows<T, DIM, SEG>;
     static bool attr_set = false;  // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                150 * 1024) != hipSuccess) return false;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(((threads + 63) / 64) * 64), bytes, s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, skip, zero_x);
+    if (!coarse_lds_attr(kern, attr_set)) return false;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(p.threads), (size_t)p.lds_bytes, s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, p.skip, p.zero_x);
     return true;
 }
 
-template <typename T, int DIM>
-static bool try_launch_coarse_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, T omega, T *x, const T *rhs,
-                                     int maxit, double tol, int fixed, CoarseOut *d_out, int zero_x)
+// the instantiations are the (DIM, SEG) pairs coarse_plan can return (tests/coarse_table.py: REACHABLE, UNREACHABLE)
+template <typename T>
+static bool try_launch_coarse_jacobi(hipStream_t s, const CoarsePlan &p, const Geom &g, const Coef<T> &c, T omega, T *x, const T *rhs,
+                                     int maxit, double tol, int fixed, CoarseOut *d_out)
 {
-    if (!switches().coarse_rows || g.ny < 3 || (DIM == 3 && g.nz < 3)) return false;
-    // run length, in measured order of preference (MI355X, one CU): 65^2 -> 8 (504 threads, two
-    // waves per SIMD: 52 ms for BASELINE config 1 against 55 ms with 7 and 64 ms with 9);
-    // 17^3 -> 5 (675 threads; 8 is 2 % slower per V-cycle at 513^3)
-    const int W = g.nx - 2, irows = (g.ny - 2) * (DIM == 3 ? g.nz - 2 : 1);
-    const int order2[4] = {8, 4, 7, 5}, order3[4] = {5, 4, 8, 7};
-    int best = 0;
-    for (int seg : (DIM == 3 ? order3 : order2)) {
-        const int nseg = (W + seg - 1) / seg, threads = nseg * irows;
-        if (W < seg || nseg * seg - W > 1 || threads < 128 || threads > (seg >= 7 ? 512 : SWG)) continue;
-        best = seg;
-        break;
+    if (g.dim == 3) {
+        switch (p.seg) {
+        case 4: return try_launch_coarse_jacobi_rows<T, 3, 4>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out);
+        case 5: return try_launch_coarse_jacobi_rows<T, 3, 5>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out);
+        case 7: return try_launch_coarse_jacobi_rows<T, 3, 7>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out);
+        default: return false;
+        }
     }
-    switch (best) {
-    case 4: return try_launch_coarse_jacobi_rows<T, DIM, 4>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, zero_x);
-    case 5: return try_launch_coarse_jacobi_rows<T, DIM, 5>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, zero_x);
-    case 7: return try_launch_coarse_jacobi_rows<T, DIM, 7>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, zero_x);
-    case 8: return try_launch_coarse_jacobi_rows<T, DIM, 8>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, zero_x);
-    default: return false;  // other widths keep the generic LDS kernel
+    switch (p.seg) {
+    case 4: return try_launch_coarse_jacobi_rows<T, 2, 4>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out);
+    case 5: return try_launch_coarse_jacobi_rows<T, 2, 5>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out);
+    case 7: return try_launch_coarse_jacobi_rows<T, 2, 7>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out);
+    case 8: return try_launch_coarse_jacobi_rows<T, 2, 8>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out);
+    default: return false;
     }
 }
 
 template <typename T, int DIM, int SEG>
-static bool try_launch_coarse_rb_rows(hipStream_t s, const Geom &g, const Coef<T> &c, T *x, const T *rhs, int maxit, double tol,
-                                      int fixed, CoarseOut *d_out, int zero_x)
+static bool try_launch_coarse_rb_rows(hipStream_t s, const CoarsePlan &p, const Geom &g, const Coef<T> &c, T *x, const T *rhs, int maxit,
+                                      double tol, int fixed, CoarseOut *d_out)
 {
-    const size_t total = (size_t)g.nx * g.ny * g.nz, bytes = 2 * total * sizeof(T);   // two copies of the iterate
-    const int W = g.nx - 2, nseg = (W + SEG - 1) / SEG;
-    if (W < SEG || nseg * SEG - W > 1) return false;  // full runs, at most one shared point per row
-    const int threads = nseg * (g.ny - 2) * (DIM == 3 ? g.nz - 2 : 1);
-    if (threads < 128 || threads > CoarseRowsThreads<SEG>::value || bytes > (size_t)150 * 1024) return false;
     auto kern = k_coarse_rb_rows<T, DIM, SEG>;
     static bool attr_set = false;  // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                150 * 1024) != hipSuccess) return false;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(((threads + 63) / 64) * 64), bytes, s, g, c, x, rhs, maxit, tol, fixed, d_out, zero_x);
+    if (!coarse_lds_attr(kern, attr_set)) return false;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(p.threads), (size_t)p.lds_bytes, s, g, c, x, rhs, maxit, tol, fixed, d_out, p.zero_x);
     return true;
-}
-
-// red-black coarse solve on the row-segment layout (MG_COARSE_RB_ROWS=0: the generic LDS kernel)
-template <typename T, int DIM>
-static bool try_launch_coarse_rb(hipStream_t s, const Geom &g, const Coef<T> &c, T *x, const T *rhs, int maxit, double tol,
-                                 int fixed, CoarseOut *d_out, int zero_x)
-{
-    if (!switches().coarse_rb_rows || g.ny < 3 || (DIM == 3 && g.nz < 3)) return false;
-    const int W = g.nx - 2, irows = (g.ny - 2) * (DIM == 3 ? g.nz - 2 : 1);
-    for (int seg : {5, 4}) {   // (runs of 7 / 8 points: the colour selects went through scratch memory; not instantiated)
-        const int nseg = (W + seg - 1) / seg, threads = nseg * irows;
-        if (W < seg || nseg * seg - W > 1 || threads < 128 || threads > SWG) continue;
-        if (seg == 5) return try_launch_coarse_rb_rows<T, DIM, 5>(s, g, c, x, rhs, maxit, tol, fixed, d_out, zero_x);
-        return try_launch_coarse_rb_rows<T, DIM, 4>(s, g, c, x, rhs, maxit, tol, fixed, d_out, zero_x);
-    }
-    return false;
 }
 
 template <typename T>
-static bool try_launch_coarse_gs_rows2d(hipStream_t s, const Geom &g, const Coef<T> &c, T *x, const T *rhs, int maxit,
-                                        double tol, int fixed, CoarseOut *d_out)
+static bool try_launch_coarse_rb(hipStream_t s, const CoarsePlan &p, const Geom &g, const Coef<T> &c, T *x, const T *rhs, int maxit,
+                                 double tol, int fixed, CoarseOut *d_out)
 {
-    const size_t bytes = 2 * (size_t)g.nx * g.ny * sizeof(T);
-    if (!switches().coarse_gs_rows || g.dim != 2 || g.ny > CGS_THREADS || g.nx < 3 || g.ny < 3 || bytes > (size_t)150 * 1024) return false;
+    if (g.dim == 3) {
+        if (p.seg == 5) return try_launch_coarse_rb_rows<T, 3, 5>(s, p, g, c, x, rhs, maxit, tol, fixed, d_out);
+        return try_launch_coarse_rb_rows<T, 3, 4>(s, p, g, c, x, rhs, maxit, tol, fixed, d_out);
+    }
+    if (p.seg == 5) return try_launch_coarse_rb_rows<T, 2, 5>(s, p, g, c, x, rhs, maxit, tol, fixed, d_out);
+    return try_launch_coarse_rb_rows<T, 2, 4>(s, p, g, c, x, rhs, maxit, tol, fixed, d_out);
+}
+
+template <typename T>
+static bool try_launch_coarse_gs_rows2d(hipStream_t s, const CoarsePlan &p, const Geom &g, const Coef<T> &c, T *x, const T *rhs,
+                                        int maxit, double tol, int fixed, CoarseOut *d_out)
+{
     auto kern = k_coarse_gs_rows2d<T>;
     static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                150 * 1024) != hipSuccess) return false;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(CGS_THREADS), bytes, s, g, c, x, rhs, maxit, tol, fixed, d_out);
+    if (!coarse_lds_attr(kern, attr_set)) return false;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(p.threads), (size_t)p.lds_bytes, s, g, c, x, rhs, maxit, tol, fixed, d_out);
     return true;
 }
 
@@ -1820,34 +1788,40 @@ void launch_coarse_solve(hipStream_t s, const Geom &g, const Coef<T> &c, T omega
                          CoarseOut *d_out, bool x_is_zero)
 {
     // x_is_zero: the solve starts from the zero guess and the caller has NOT cleared x: the row-segment Jacobi and red-black kernels take the
-    // guess as a flag (a memset launch less per cycle); every other kernel gets its x cleared here
-    if (x_is_zero && smoother == 1 && g.gz0 == 0 && g.gnz == g.nz) {
-        if (g.dim == 3 ? try_launch_coarse_jacobi<T, 3>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, 1)
-                       : try_launch_coarse_jacobi<T, 2>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, 1)) return;
-    }
-    if (x_is_zero && smoother == 2 && g.gz0 == 0 && g.gnz == g.nz) {  // so does the row-segment red-black kernel
-        if (g.dim == 3 ? try_launch_coarse_rb<T, 3>(s, g, c, x, rhs, maxit, tol, fixed, d_out, 1)
-                       : try_launch_coarse_rb<T, 2>(s, g, c, x, rhs, maxit, tol, fixed, d_out, 1)) return;
-    }
-    if (x_is_zero) (void)hipMemsetAsync(x, 0, (size_t)g.nz * (size_t)g.plane * sizeof(T), s);
-    // LDS-resident when the three arrays fit one CU's LDS, global-memory loop otherwise
-    if (smoother == 1 && g.gz0 == 0 && g.gnz == g.nz) {  // Jacobi: the row-segment kernel
-        if (g.dim == 3 ? try_launch_coarse_jacobi<T, 3>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, 0)
-                       : try_launch_coarse_jacobi<T, 2>(s, g, c, omega, x, rhs, maxit, tol, fixed, d_out, 0)) return;
-    }
-    if (smoother == 0 && try_launch_coarse_gs_rows2d<T>(s, g, c, x, rhs, maxit, tol, fixed, d_out)) return;
-    if (smoother == 2 && g.gz0 == 0 && g.gnz == g.nz) {  // red-black: the row-segment kernel
-        if (g.dim == 3 ? try_launch_coarse_rb<T, 3>(s, g, c, x, rhs, maxit, tol, fixed, d_out, 0)
-                       : try_launch_coarse_rb<T, 2>(s, g, c, x, rhs, maxit, tol, fixed, d_out, 0)) return;
-    }
-    if (g.dim == 3) {
-        if (try_launch_coarse_lds<T, 3, 5>(s, g, c, omega, smoother, x, rhs, maxit, tol, fixed, d_out)) return;
-        hipLaunchKernelGGL((k_coarse_solve<T, 3>), dim3(1), dim3(SWG), 0, s, g, c, omega, smoother, x,
-                           tmp, rhs, maxit, tol, fixed, d_out);
-    } else {
-        if (try_launch_coarse_lds<T, 2, 5>(s, g, c, omega, smoother, x, rhs, maxit, tol, fixed, d_out)) return;
-        hipLaunchKernelGGL((k_coarse_solve<T, 2>), dim3(1), dim3(SWG), 0, s, g, c, omega, smoother, x,
-                           tmp, rhs, maxit, tol, fixed, d_out);
+    // guess as a flag (a memset launch less per cycle); every other kernel gets its x cleared here.
+    // A kernel whose LDS attribute the runtime refuses is planned around: its family off, the next choice taken.
+    bool rows = switches().coarse_rows, rb_rows = switches().coarse_rb_rows, gs_rows = switches().coarse_gs_rows, cleared = false;
+    for (;;) {
+        const CoarsePlan p = coarse_plan(g.dim, g.nx, g.ny, g.nz, (int)sizeof(T), smoother, (double)omega, x_is_zero,
+                                         g.gz0 == 0 && g.gnz == g.nz, rows, rb_rows, gs_rows);
+        if (p.memset && !cleared) {
+            (void)hipMemsetAsync(x, 0, (size_t)g.nz * (size_t)g.plane * sizeof(T), s);
+            cleared = true;
+        }
+        switch (p.kernel) {
+        case COARSE_JACOBI_ROWS:
+            if (try_launch_coarse_jacobi<T>(s, p, g, c, omega, x, rhs, maxit, tol, fixed, d_out)) return;
+            rows = false;
+            continue;
+        case COARSE_RB_ROWS:
+            if (try_launch_coarse_rb<T>(s, p, g, c, x, rhs, maxit, tol, fixed, d_out)) return;
+            rb_rows = false;
+            continue;
+        case COARSE_GS_ROWS2D:
+            if (try_launch_coarse_gs_rows2d<T>(s, p, g, c, x, rhs, maxit, tol, fixed, d_out)) return;
+            gs_rows = false;
+            continue;
+        case COARSE_LDS:   // LDS-resident when the three arrays fit one CU's LDS, global-memory loop otherwise
+            if (g.dim == 3 ? try_launch_coarse_lds<T, 3>(s, p, g, c, omega, smoother, x, rhs, maxit, tol, fixed, d_out)
+                           : try_launch_coarse_lds<T, 2>(s, p, g, c, omega, smoother, x, rhs, maxit, tol, fixed, d_out)) return;
+            [[fallthrough]];
+        default:
+            if (g.dim == 3) hipLaunchKernelGGL((k_coarse_solve<T, 3>), dim3(1), dim3(SWG), 0, s, g, c, omega, smoother, x,
+                                               tmp, rhs, maxit, tol, fixed, d_out);
+            else hipLaunchKernelGGL((k_coarse_solve<T, 2>), dim3(1), dim3(SWG), 0, s, g, c, omega, smoother, x,
+                                    tmp, rhs, maxit, tol, fixed, d_out);
+            return;
+        }
     }
 }
 
