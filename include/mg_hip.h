@@ -257,6 +257,64 @@ enum mg_mixed_kernel_kind { MG_MIXED_K_RESIDUAL = 0, MG_MIXED_K_CORRECT_RESIDUAL
 int mg_mixed_kernel(mg_handle h, int kernel, double scale_in, double scale_out,
                     int arr_e32, int arr_r32, double *sumsq_r);
 
+/* Diagonal shift (extension, no reference counterpart): from this call on the handle works on sigma I + A, sigma >= 0 --
+ * the operator of an implicit time step or a screened-Poisson / Helmholtz-type solve. On every level the diagonal becomes
+ * cd0_l + sigma (one fp64 addition, then cast to the working dtype like every coefficient), cd0_l being the diagonal the
+ * handle was created with; off-diagonals and Dirichlet rows (identity) are untouched. mg_level_coefficients reports the
+ * shifted diagonal, and everything works on the shifted operator with no further change of interface: mg_smooth,
+ * mg_residual, mg_coarse_solve(_ex), mg_cycle(_async), mg_solve, mg_solve_lockstep, mg_pcg_solve, mg_pcg_kernel, mg_fmg,
+ * mg_mixed_solve / mg_mixed_kernel (which document themselves in terms of mg_level_coefficients). sigma == 0 restores the
+ * creation state bit for bit; a handle on which this is never called behaves exactly as before. On a zebra handle the
+ * line factors of every level are re-tabulated for the new diagonal after the handle's stream has been synchronised.
+ * MG_ERR_BAD_ARG with the handle unchanged: NULL handle, sigma negative or not finite, distributed handles (dry runs
+ * included). */
+int mg_set_shift(mg_handle h, double sigma);
+int mg_get_shift(mg_handle h, double *sigma);
+
+/* Implicit heat-equation stepper (extension): integrates u_t = -A0 u + f on level 0 with the theta scheme, A0 being the
+ * UNSHIFTED operator of level 0 (desc.alpha is its diffusion constant). The Dirichlet values are those the U array holds
+ * on the Dirichlet nodes: constant over a call, the caller may rewrite them between calls. One step solves, on the
+ * interior rows,
+ *     (1/(theta dt) I + A0) u' = (f + u/dt - (1 - theta) A0 u) / theta
+ * theta = 1: backward Euler, theta = 1/2: Crank-Nicolson. mg_heat_step(h, dt, theta, nsteps, cycles_per_step, st):
+ *   1. mg_set_shift(h, 1.0 / (theta * dt)) -- that expression in fp64 -- unless that is the current shift already. The
+ *      shift STAYS set on return (mg_get_shift tells; mg_residual then evaluates the step's operator).
+ *   2. nsteps times:  RHS(0) = the step's right-hand side built from U(0) (+ f), ONE launch (mg_heat.hip);
+ *                     cycles_per_step times: desc.outer_pre_gs lexicographic GS sweeps + one mg_cycle -- mg_solve's outer
+ *                     iteration, warm-started from u (U is not cleared).
+ *   3. one residual and one sum of squares: st->relres = ||rhs - (sigma I + A0) u|| / ||rhs|| of the LAST step (all
+ *      nodes, as mg_solve; what mg_residual / mg_sumsq on U, RHS return afterwards).
+ * No host synchronisation inside or between the steps: nsteps = 100 enqueues 100 steps back to back; the residual at the
+ * end is the only one. Sawtooth and V-cycle, every smoother, both restrictions, aniso, semi_xy, 2-D and 3-D, both dtypes.
+ * mg_profile_* brackets keep timing the level-0 launches of the cycles inside. On return U holds u after nsteps steps and
+ * RHS(0) the last step's right-hand side; every other array is unspecified, as after mg_solve.
+ * Right-hand-side arithmetic, in the working dtype T, every operation rounded separately (no contraction), the stencil
+ * in the row order of mg_residual with cd0 = the unshifted diagonal of level 0:
+ *   s   = (((((((0 + cz u[k-1]) + cy u[j-1]) + cx u[i-1]) + cd0 u) + cx u[i+1]) + cy u[j+1]) + cz u[k+1])  (cz terms absent in 2-D)
+ *   rhs = ((f + rdt*u) - omt*s) * rth      interior nodes;  without a source (rdt*u - omt*s) * rth
+ *   rhs = u                                Dirichlet nodes, bit for bit
+ *   rdt = (T)(1.0/dt),  omt = (T)(1.0 - theta),  rth = (T)(1.0/theta)   (fp64 on the host, then cast)
+ * theta == 1 takes the stencil-free form rhs = f + rdt*u: for finite data the value of the general expression
+ * (omt = 0, rth = 1).
+ * mg_heat_set_source: f as a dense host array of desc.dtype in the usual layout (its values on Dirichlet nodes are
+ * ignored); NULL: f = 0 again. The first call with an array allocates one more level-0 array, kept until mg_destroy and
+ * counted by mg_device_bytes from then on (1.1 GB at 513^3 fp64); without a source the kernel reads none.
+ * mg_heat_rhs is the assembly kernel alone, for tests and for callers that drive their own steps (mg_set_shift +
+ * mg_heat_rhs + mg_solve is a step solved to a tolerance): arr_dst(0) = the right-hand side of one step built from
+ * arr_u(0); arr_u is not modified and the shift is not touched.
+ * MG_ERR_BAD_ARG, with U and the shift untouched: dt not positive or not finite (or so small that 1/(theta dt) is not
+ * finite), theta outside (0, 1], nsteps < 1, cycles_per_step < 1, arr_dst == arr_u (mg_heat_rhs), distributed handles
+ * (dry runs included), a stage callback installed (mg_heat_step), NULL handle. */
+int mg_heat_set_source(mg_handle h, const void *host_f);
+typedef struct mg_heat_stats {
+    int32_t steps;    /* steps taken                                              */
+    int32_t cycles;   /* cycles run = steps * cycles_per_step                     */
+    double  time;     /* steps * dt                                               */
+    double  relres;   /* ||rhs - (sigma I + A0) u|| / ||rhs|| of the LAST step    */
+} mg_heat_stats;
+int mg_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
+int mg_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst);
+
 /* Debug stage dumps of the sawtooth cycle -- the reference's CREATE_GIF twin
  * (multigrid.hpp:160-316) writes `sol + err` sampled on the level being worked on after every
  * stage: before and after the coarse solve, after each interpolation, after each level's

@@ -82,6 +82,12 @@ class MgMixedStats(C.Structure):
     ]
 
 
+class MgHeatStats(C.Structure):
+    """include/mg_hip.h::mg_heat_stats (mg_heat_step)"""
+
+    _fields_ = [("steps", C.c_int32), ("cycles", C.c_int32), ("time", C.c_double), ("relres", C.c_double)]
+
+
 def make_desc(dim=2, n=17, levels=2, dtype=MG_F64, length=10.0, alpha=1.0,
               cycle=CYCLE_SAWTOOTH, smoother=SMOOTH_JACOBI, omega=1.0, nu_pre=0, nu_post=5,
               restriction=RESTRICT_INJECT, coarse_mode=COARSE_TOL, coarse_maxit=2000,
@@ -121,6 +127,7 @@ EXPORTS = [
     "mg_prolong", "mg_correct", "mg_coarse_solve", "mg_coarse_solve_ex", "mg_cycle", "mg_cycle_async", "mg_solve", "mg_solve_lockstep",
     "mg_pcg_solve", "mg_pcg_kernel", "mg_fmg", "mg_fmg_prolong",
     "mg_mixed_set_rhs", "mg_mixed_set_solution", "mg_mixed_get_solution", "mg_mixed_solve", "mg_mixed_kernel",
+    "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_step", "mg_heat_rhs",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
 ]
@@ -174,6 +181,11 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_mixed_get_solution.argtypes = [vp, vp]
     L.mg_mixed_solve.argtypes = [vp, C.c_double, i, i, dp, i, C.POINTER(i), C.POINTER(MgMixedStats)]
     L.mg_mixed_kernel.argtypes = [vp, i, C.c_double, C.c_double, i, i, dp]
+    L.mg_set_shift.argtypes = [vp, C.c_double]
+    L.mg_get_shift.argtypes = [vp, dp]
+    L.mg_heat_set_source.argtypes = [vp, vp]
+    L.mg_heat_step.argtypes = [vp, C.c_double, C.c_double, i, i, C.POINTER(MgHeatStats)]
+    L.mg_heat_rhs.argtypes = [vp, C.c_double, C.c_double, i, i]
     L.mg_set_stage_callback.argtypes = [vp, STAGE_FN, vp]
     L.mg_sync.argtypes = [vp]
     L.mg_timer_start.argtypes = [vp]
@@ -403,6 +415,32 @@ class Solver:
         """mg_mixed_kernel: one of the two fp64-in / fp32-out kernels of mixed_solve (MIXED_K_*) -> sum r^2"""
         s = C.c_double(0)
         _check(self.lib.mg_mixed_kernel(self.h, kernel, scale_in, scale_out, arr_e32, arr_r32, C.byref(s))); return s.value
+
+    # -- diagonal shift and the implicit heat-equation stepper
+    def set_shift(self, sigma: float):
+        """mg_set_shift: the handle works on sigma I + A from here on (sigma >= 0; 0 restores the creation state)"""
+        _check(self.lib.mg_set_shift(self.h, sigma))
+
+    def get_shift(self) -> float:
+        s = C.c_double(0); _check(self.lib.mg_get_shift(self.h, C.byref(s))); return s.value
+
+    def heat_set_source(self, f):
+        """mg_heat_set_source: the source term f of u_t = -A0 u + f (level-0 array of the handle's dtype); None: f = 0"""
+        if f is None:
+            _check(self.lib.mg_heat_set_source(self.h, None))
+        else:
+            f = self._host(f, 0); _check(self.lib.mg_heat_set_source(self.h, f.ctypes.data_as(C.c_void_p)))
+
+    def heat_step(self, dt, theta=1.0, nsteps=1, cycles_per_step=1) -> MgHeatStats:
+        """mg_heat_step: nsteps theta-scheme steps of u_t = -A0 u + f from U, cycles_per_step cycles each, no host
+        synchronisation in between; U holds the result, the shift 1 / (theta dt) stays set -> MgHeatStats"""
+        st = MgHeatStats()
+        _check(self.lib.mg_heat_step(self.h, dt, theta, nsteps, cycles_per_step, C.byref(st)))
+        return st
+
+    def heat_rhs(self, dt, theta, arr_u=ARR_U, arr_dst=ARR_RHS):
+        """mg_heat_rhs: arr_dst(0) = the right-hand side of one theta-scheme step built from arr_u(0)"""
+        _check(self.lib.mg_heat_rhs(self.h, dt, theta, arr_u, arr_dst))
 
     def set_stage_callback(self, fn):
         """fn(stage, level, array) after every stage of the sawtooth cycle (CREATE_GIF dumps); None removes it"""

@@ -216,6 +216,25 @@ int mg_mixed_kernel(mg_handle h, int kernel, double scale_in, double scale_out, 
     MG_H(h);
     return guarded([&] { return h->impl->mixed_kernel(kernel, scale_in, scale_out, arr_e32, arr_r32, sumsq_r); });
 }
+int mg_set_shift(mg_handle h, double sigma) { MG_H(h); return guarded([&] { return h->impl->set_shift(sigma); }); }
+int mg_get_shift(mg_handle h, double *sigma)
+{
+    MG_H(h);
+    if (!sigma) return bad("mg_get_shift: null argument");
+    *sigma = h->impl->shift();
+    return MG_OK;
+}
+int mg_heat_set_source(mg_handle h, const void *host_f) { MG_H(h); return guarded([&] { return h->impl->heat_set_source(host_f); }); }
+int mg_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->heat_step(dt, theta, nsteps, cycles_per_step, st); });
+}
+int mg_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->heat_rhs(dt, theta, arr_u, arr_dst); });
+}
 int mg_set_stage_callback(mg_handle h, mg_stage_fn fn, void *user)
 {
     MG_H(h);

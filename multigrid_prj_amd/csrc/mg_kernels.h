@@ -214,5 +214,12 @@ int launch_mixed_correct_residual(hipStream_t s, const Geom &g64, const Geom &g3
 // partials of v^2 over all nodes
 int launch_mixed_sumsq(hipStream_t s, const Geom &g64, const double *v, double *partials);
 
+// ---- implicit heat-equation stepper on level 0 (mg_heat.hip, driven by Solver::heat_step) ----
+// out = right-hand side of one theta-scheme step built from u (and the source f; nullptr: f = 0): on interior nodes
+// ((f + u / dt) - (1 - theta) A0 u) / theta with coef0 = {cx, cy, cz, cd0}, the UNSHIFTED operator of the level in fp64
+// (cast to T here); out = u on Dirichlet nodes. out must not alias u or f.
+template <typename T>
+void launch_heat_rhs(hipStream_t s, const Geom &g, const double coef0[4], double dt, double theta, const T *u, const T *f, T *out);
+
 }  // namespace mg
 #endif

@@ -170,6 +170,7 @@ Solver::~Solver()
     for (auto &b : stage_base_) if (b) (void)hipFree(b);
     for (auto &b : kry_) if (b) (void)hipFree(b);
     for (auto &b : mx_) if (b) (void)hipFree(b);
+    if (heat_f_) (void)hipFree(heat_f_);
     if (d_mx_part_) (void)hipFree(d_mx_part_);
     if (d_mx_sum_) (void)hipFree(d_mx_sum_);
     if (d_cg_) (void)hipFree(d_cg_);
@@ -233,6 +234,7 @@ int Solver::init()
         L.g.plane = (long long)L.g.ny * L.g.pitch;
         L.g.gz0 = 0; L.g.gnz = L.g.nz;
         level_coefficients(d_, l, L.coef);
+        L.cd0 = L.coef[3];
         if (nranks_ > 1) {
             SlabPlan p;
             std::string why;
@@ -302,20 +304,10 @@ int Solver::init()
             bytes_ += nbytes;
         }
         if (is_zebra(d_.smoother)) {  // elimination factors of the line solve: along y (cy, ny) or along x (cx, nx)
-            const bool alongx = d_.smoother == MG_SMOOTH_ZEBRA_X;
-            const int nl = alongx ? L.g.nx : L.g.ny;
-            const double cl = alongx ? L.coef[0] : L.coef[1];
-            const size_t nb = 2 * (size_t)nl * esize();
+            const size_t nb = 2 * (size_t)(d_.smoother == MG_SMOOTH_ZEBRA_X ? L.g.nx : L.g.ny) * esize();
             MG_HIP(hipMalloc(&L.zebra, nb));
-            if (d_.dtype == MG_F64) {
-                std::vector<double> f(2 * (size_t)nl);
-                zebra_line_factors<double>(cl, L.coef[3], nl, f.data());
-                MG_HIP(hipMemcpy(L.zebra, f.data(), nb, hipMemcpyHostToDevice));
-            } else {
-                std::vector<float> f(2 * (size_t)nl);
-                zebra_line_factors<float>((float)cl, (float)L.coef[3], nl, f.data());
-                MG_HIP(hipMemcpy(L.zebra, f.data(), nb, hipMemcpyHostToDevice));
-            }
+            const int rc = zebra_tabulate(L);
+            if (rc) return rc;
             bytes_ += nb;
         }
         int cap = reduce_partials_capacity(L.g);
@@ -331,6 +323,25 @@ int Solver::init()
     MG_HIP(hipHostMalloc((void **)&h_fixed_, sizeof(CoarseOut)));
     bytes_ += sizeof(double) * ((size_t)max_partials + 8) + sizeof(CoarseOut);
     MG_HIP(hipStreamSynchronize(stream_));
+    return MG_OK;
+}
+
+// cp(j), den(j) of the level's line solve for its CURRENT diagonal, into the level's table (blocking copy)
+int Solver::zebra_tabulate(Level &L)
+{
+    const bool alongx = d_.smoother == MG_SMOOTH_ZEBRA_X;
+    const int nl = alongx ? L.g.nx : L.g.ny;
+    const double cl = alongx ? L.coef[0] : L.coef[1];
+    const size_t nb = 2 * (size_t)nl * esize();
+    if (d_.dtype == MG_F64) {
+        std::vector<double> f(2 * (size_t)nl);
+        zebra_line_factors<double>(cl, L.coef[3], nl, f.data());
+        MG_HIP(hipMemcpy(L.zebra, f.data(), nb, hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> f(2 * (size_t)nl);
+        zebra_line_factors<float>((float)cl, (float)L.coef[3], nl, f.data());
+        MG_HIP(hipMemcpy(L.zebra, f.data(), nb, hipMemcpyHostToDevice));
+    }
     return MG_OK;
 }
 
@@ -2165,6 +2176,130 @@ int Solver::mixed_kernel(int kernel, double scale_in, double scale_out, int arr_
     MG_HIP(hipStreamSynchronize(stream_));
     if (corr) std::swap(mx_[MXU], mx_[MXU2]);
     if (sumsq_r) *sumsq_r = h_scal_[6];
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------- diagonal shift (mg_set_shift)
+// Every launch rebuilds its Coef from Level::coef (coef_of; mixed_solve hands L0.coef to its fp64 kernels), so the shifted
+// operator needs nothing but the new diagonal -- and new line factors where the smoother is a zebra one, the only data
+// derived from cd when the handle is created.
+int Solver::set_shift(double sigma)
+{
+    if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_last_error("mg_set_shift: sigma must be finite and not negative"); return MG_ERR_BAD_ARG; }
+    if (nranks_ > 1) {
+        set_last_error("mg_set_shift: distributed handles are not supported (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (sigma == shift_) return MG_OK;
+    MG_HIP(hipSetDevice(device_));
+    const bool zebra = is_zebra(d_.smoother);
+    if (zebra) MG_HIP(hipStreamSynchronize(stream_));   // no queued sweep may read a half-written table
+    for (auto &L : lv_) {
+        L.coef[3] = L.cd0 + sigma;
+        if (zebra && L.zebra) MG_TRY(zebra_tabulate(L));
+    }
+    shift_ = sigma;
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------- implicit heat-equation stepper (mg_heat_*)
+// u_t = -A0 u + f by the theta scheme: per step one launch of mg_heat.hip builds the right-hand side from U (+ f) into
+// RHS, then cycles_per_step outer iterations of mg_solve on (1/(theta dt) I + A0) u' = rhs, warm-started from u.
+int Solver::heat_check(const char *fn, double dt, double theta) const
+{
+    if (nranks_ > 1) {
+        set_last_error(std::string(fn) + ": distributed handles are not supported (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (!(dt > 0.0) || !std::isfinite(dt)) { set_last_error(std::string(fn) + ": dt must be positive and finite"); return MG_ERR_BAD_ARG; }
+    if (!(theta > 0.0 && theta <= 1.0)) { set_last_error(std::string(fn) + ": theta must be in (0, 1]"); return MG_ERR_BAD_ARG; }
+    if (!std::isfinite(1.0 / (theta * dt)) || !std::isfinite(1.0 / dt)) {
+        set_last_error(std::string(fn) + ": dt is too small: 1 / (theta dt) is not finite");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::heat_set_source(const void *host)
+{
+    if (nranks_ > 1) {
+        set_last_error("mg_heat_set_source: distributed handles are not supported (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (!host) { heat_has_f_ = false; return MG_OK; }
+    MG_HIP(hipSetDevice(device_));
+    const Level &L0 = lv_[0];
+    if (!heat_f_) {
+        const size_t nbytes = L0.alloc_elems * esize();
+        MG_HIP(hipMalloc(&heat_f_, nbytes));
+        MG_HIP(hipMemsetAsync(heat_f_, 0, nbytes, stream_));   // ghost planes and padding columns stay zero from here on
+        bytes_ += nbytes;
+    }
+    MG_TRY(stage_copy(static_cast<char *>(heat_f_) + (size_t)L0.gh * (size_t)L0.g.plane * esize(), L0.g, esize(), const_cast<void *>(host), true));
+    heat_has_f_ = true;
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::heat_rhs_t(double dt, double theta, int arr_u, int arr_dst)
+{
+    Level &L0 = lv_[0];
+    const double coef0[4] = {L0.coef[0], L0.coef[1], L0.coef[2], L0.cd0};
+    const T *f = heat_has_f_ ? reinterpret_cast<const T *>(heat_f_) + L0.gh * L0.g.plane : (const T *)nullptr;
+    if (arr_dst == MG_ARR_RHS) L0.rhs_halo_ok = false;
+    launch_heat_rhs<T>(stream_, L0.g, coef0, dt, theta, ptr<T>(arr_u, 0), f, ptr<T>(arr_dst, 0));
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::heat_rhs(double dt, double theta, int arr_u, int arr_dst)
+{
+    MG_TRY(heat_check("mg_heat_rhs", dt, theta));
+    if (!check_arr(arr_u, 0, "mg_heat_rhs") || !check_arr(arr_dst, 0, "mg_heat_rhs")) return MG_ERR_BAD_ARG;
+    if (arr_u == arr_dst) { set_last_error("mg_heat_rhs: arr_dst must differ from arr_u"); return MG_ERR_BAD_ARG; }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    return d_.dtype == MG_F64 ? heat_rhs_t<double>(dt, theta, arr_u, arr_dst) : heat_rhs_t<float>(dt, theta, arr_u, arr_dst);
+}
+
+template <typename T>
+int Solver::heat_step_t(double dt, double theta, int nsteps, int cycles_per_step)
+{
+    for (int n = 0; n < nsteps; n++) {
+        MG_TRY(heat_rhs_t<T>(dt, theta, MG_ARR_U, MG_ARR_RHS));
+        for (int c = 0; c < cycles_per_step; c++) {
+            if (d_.outer_pre_gs > 0) MG_TRY(smooth_t<T>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS));   // `u * GS * GS`
+            MG_TRY(cycle_enqueue_t<T>());                                                                            // `* MGx`
+        }
+    }
+    MG_TRY(residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
+    return sumsq_t<T>(0, MG_ARR_RHS);
+}
+
+int Solver::heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
+{
+    MG_TRY(heat_check("mg_heat_step", dt, theta));
+    if (stage_fn_) {
+        set_last_error("mg_heat_step: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
+        return MG_ERR_BAD_ARG;
+    }
+    if (nsteps < 1) { set_last_error("mg_heat_step: nsteps must be at least 1"); return MG_ERR_BAD_ARG; }
+    if (cycles_per_step < 1) { set_last_error("mg_heat_step: cycles_per_step must be at least 1"); return MG_ERR_BAD_ARG; }
+    MG_TRY(set_shift(1.0 / (theta * dt)));
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    lock_iters_ = -1;
+    fine_pre_done_ = 0;
+    MG_TRY(d_.dtype == MG_F64 ? heat_step_t<double>(dt, theta, nsteps, cycles_per_step) : heat_step_t<float>(dt, theta, nsteps, cycles_per_step));
+    // the one host synchronisation of the call: ||rhs - (sigma I + A0) u|| / ||rhs|| of the last step
+    MG_HIP(hipMemcpyAsync(h_scal_, d_scal_, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    if (st) {
+        st->steps = nsteps;
+        st->cycles = nsteps * cycles_per_step;
+        st->time = (double)nsteps * dt;
+        st->relres = h_scal_[0] == 0.0 ? 0.0 : std::sqrt(h_scal_[0] / h_scal_[1]);
+    }
     return MG_OK;
 }
 

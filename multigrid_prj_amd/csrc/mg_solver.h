@@ -40,6 +40,7 @@ struct Level {
     size_t alloc_elems = 0;      // (nz + 2) * plane
     void *base[NUM_ARR] = {};    // allocations (ghost plane first)
     double coef[4] = {};
+    double cd0 = 0;              // coef[3] as created (level_coefficients): coef[3] = cd0 + the handle's shift (mg_set_shift)
     bool present = true;         // false: level not held by this rank (gathered on rank 0)
     bool dist = false;           // true: z-slab of a level distributed over all ranks
     int nz_min = 0;              // thinnest slab of the level over all ranks (== g.nz when the level is not distributed)
@@ -93,6 +94,14 @@ public:
     int mixed_get_solution(double *host);
     int mixed_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st);
     int mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r);
+    // the operator sigma I + A on every level (mg_set_shift): coef[3] = cd0 + sigma, zebra line factors re-tabulated
+    int set_shift(double sigma);
+    double shift() const { return shift_; }
+    // implicit theta-scheme steps of u_t = -A0 u + f on level 0 (mg_heat_*); the source array is allocated by the first
+    // heat_set_source
+    int heat_set_source(const void *host);
+    int heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
+    int heat_rhs(double dt, double theta, int arr_u, int arr_dst);
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -169,6 +178,7 @@ private:
     template <typename T> int vcycle_rec_t(int l, bool u_zero = false);
     int cycle_enqueue();
     bool check_arr(int which, int level, const char *fn) const;
+    int zebra_tabulate(Level &L);   // the level's zebra line factors from its current coefficients -> L.zebra
     size_t esize() const { return d_.dtype == MG_F64 ? 8 : 4; }
 
     mg_desc d_;
@@ -218,6 +228,14 @@ private:
     bool mx_has_b_ = false, mx_has_u_ = false;
     double *d_mx_part_ = nullptr, *d_mx_sum_ = nullptr;   // per-workgroup partial sums and their total
     double *mxptr(int k) const { return reinterpret_cast<double *>(mx_[k]) + g64_.plane; }   // local plane 0
+    // diagonal shift of every level (set_shift) and the stepper's source term f: one more level-0 array (allocated on first
+    // use, kept until the handle goes); heat_has_f_ == false: f = 0, the array is not read
+    double shift_ = 0;
+    int heat_check(const char *fn, double dt, double theta) const;   // single-GPU handle, dt > 0, theta in (0, 1], finite shift
+    template <typename T> int heat_rhs_t(double dt, double theta, int arr_u, int arr_dst);
+    template <typename T> int heat_step_t(double dt, double theta, int nsteps, int cycles_per_step);
+    void *heat_f_ = nullptr;
+    bool heat_has_f_ = false;
     Geom gfull_{};
     void *full_[3] = {nullptr, nullptr, nullptr};
     std::vector<SlabPlan> planT_;
