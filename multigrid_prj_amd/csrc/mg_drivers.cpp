@@ -1,0 +1,578 @@
+// mg_drivers.cpp -- the solve drivers of mg::Solver: everything that calls the cycle from above (mg_solve, mg_pcg_*, mg_fmg*,
+// mg_mixed_*, mg_set_shift, mg_heat_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
+// Reference call structure being replaced by solve(): the outer loop of src/main.cpp:72-116.
+#include "mg_solver.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace mg {
+
+// ---------------------------------------------------------------- what the drivers share
+int Solver::driver_begin(const char *fn, unsigned refuse)
+{
+    if ((refuse & REFUSE_DIST) && nranks_ > 1) {
+        set_last_error(std::string(fn) + ": distributed handles are not supported (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    if ((refuse & REFUSE_STAGE_CB) && stage_fn_) {
+        set_last_error(std::string(fn) + ": a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_HIP(hipSetDevice(device_));
+    pair_on_comm_level_ = -1;
+    lock_iters_ = -1;
+    fine_pre_done_ = 0;
+    return MG_OK;
+}
+
+int Solver::outer_iteration_enqueue()
+{
+    if (d_.outer_pre_gs > 0)                                 // `u * GS * GS` main.cpp:85
+        MG_TRY(d_.dtype == MG_F64 ? smooth_t<double>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS)
+                                  : smooth_t<float>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS));
+    return cycle_enqueue();                                  // `* MGx`
+}
+
+// ---------------------------------------------------------------- mg_solve
+// Outer loop of src/main.cpp:72-116.
+int Solver::solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist,
+                  mg_cycle_stats *per_cycle, const int *lock_counts, int n_lock)
+{
+    MG_HIP(hipSetDevice(device_));
+    double nb = 0, nr = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));                       // Residual ctor, solvers.hpp:237-242
+    const bool fused_norm = !lock_counts && (d_.dtype == MG_F64 ? pair_norm_ok<double>() : pair_norm_ok<float>());
+    if (fused_norm) {
+        // Same loop, same history: entry k is the norm after k cycles. It is computed by the first pre-smoothing pair of cycle
+        // k + 1, which runs before the test; when the test says stop (or maxit is reached) that pair's output is dropped -- it
+        // was written out of place, U still holds the iterate the norm belongs to.
+        Level &L0 = lv_[0];
+        int nh = 0;
+        for (int it = 0; it <= maxit; it++) {
+            void *const base_u = L0.base[MG_ARR_U], *const base_t = L0.base[MG_ARR_TMP];
+            want_pair_norm_ = true; pair_norm_done_ = false;
+            // the speculative launch: the Jacobi pair (both pre-smoothing sweeps), or the first red-black sweep -- ONE out-of-place
+            // launch either way, so the iterate the norm belongs to is still whole when the test says stop
+            const int spec = d_.smoother == MG_SMOOTH_JACOBI ? d_.nu_pre : 1;
+            const int rc = d_.dtype == MG_F64 ? smooth_t<double>(0, d_.smoother, spec, MG_ARR_U, MG_ARR_RHS, false, -1, true)
+                                              : smooth_t<float>(0, d_.smoother, spec, MG_ARR_U, MG_ARR_RHS, false, -1, true);
+            want_pair_norm_ = false;
+            MG_TRY(rc);
+            if (!pair_norm_done_) { set_last_error("mg_solve: the pre-smoothing pair did not deliver the residual norm"); return MG_ERR_HIP; }
+            MG_TRY(fetch_scalars(SC_RR, d_scal_ + SC_RR));
+            nr = h_scal_[SC_RR];
+            if (per_cycle && it > 0) fill_cycle_stats(&per_cycle[it - 1], 0.0);   // the coarse solver's record of the cycle that has just finished
+            const double rel = std::sqrt(nr / nb);
+            if (hist && nh < hist_cap) hist[nh] = rel;
+            nh++;
+            if ((it > 0 && rel <= tol) || it == maxit) {     // main.cpp:88-89 / the loop bound: drop the speculative pair
+                L0.base[MG_ARR_U] = base_u; L0.base[MG_ARR_TMP] = base_t;
+                break;
+            }
+            fine_pre_done_ = spec;
+            const int crc = cycle_enqueue();
+            fine_pre_done_ = 0;
+            MG_TRY(crc);
+            if (per_cycle) MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));
+        }
+        MG_HIP(hipStreamSynchronize(stream_));
+        if (n_hist) *n_hist = nh;
+        return MG_OK;
+    }
+    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));      // main.cpp:73-74
+    int nh = 0;
+    if (hist && nh < hist_cap) hist[nh] = std::sqrt(nr / nb);
+    nh++;
+    for (int it = 0; it < maxit; it++) {
+        lock_iters_ = (lock_counts && it < n_lock) ? lock_counts[it] : -1;
+        const int crc = outer_iteration_enqueue();
+        lock_iters_ = -1;
+        MG_TRY(crc);
+        MG_TRY(fetch_cycle_stats(per_cycle ? &per_cycle[it] : nullptr, true));   // as mg_cycle reports them
+        MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));  // main.cpp:86
+        double rel = std::sqrt(nr / nb);
+        if (hist && nh < hist_cap) hist[nh] = rel;
+        nh++;
+        if (rel <= tol) break;                               // main.cpp:88-89
+    }
+    if (n_hist) *n_hist = nh;
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------- multigrid-preconditioned flexible CG (mg_pcg_solve)
+int Solver::krylov_scalars_alloc()
+{
+    if (d_cg_) return MG_OK;
+    const size_t npart = (size_t)cg_partials_capacity();
+    MG_HIP(hipMalloc((void **)&d_cg_, sizeof(CgScalars)));
+    MG_HIP(hipMalloc((void **)&d_cg_part_, sizeof(double) * npart));
+    MG_HIP(hipMalloc((void **)&d_cg_dot_, sizeof(double) * 2));
+    MG_HIP(hipHostMalloc((void **)&h_cg_, sizeof(CgScalars)));
+    bytes_ += sizeof(CgScalars) + sizeof(double) * (npart + 2);
+    return MG_OK;
+}
+
+int Solver::krylov_alloc()
+{
+    MG_TRY(krylov_scalars_alloc());
+    if (kry_[0]) return MG_OK;
+    const size_t nbytes = lv_[0].alloc_elems * esize();
+    for (auto &b : kry_) MG_TRY(alloc_zeroed(&b, nbytes));
+    return MG_OK;
+}
+
+// z = M r: the cycle code works on level 0's U / RHS slots, so z and r take them for the duration (pointer swap, no copy).
+// The cycle may itself leave its result in the array that was TMP (out-of-place sweeps swap U / TMP): whatever U points
+// at afterwards is z, and TMP keeps the other buffer.
+int Solver::precondition()
+{
+    Level &L0 = lv_[0];
+    void *const x_base = L0.base[MG_ARR_U], *const b_base = L0.base[MG_ARR_RHS];
+    MG_HIP(hipMemsetAsync(kry_[KZ], 0, L0.alloc_elems * esize(), stream_));
+    L0.base[MG_ARR_U] = kry_[KZ];
+    L0.base[MG_ARR_RHS] = kry_[KR];
+    const int rc = outer_iteration_enqueue();
+    kry_[KZ] = L0.base[MG_ARR_U];
+    L0.base[MG_ARR_U] = x_base;
+    L0.base[MG_ARR_RHS] = b_base;
+    return rc;
+}
+
+template <typename T>
+int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    const Coef<T> c = coef_of<T>(L0);
+    auto kp = [&](int k) { return reinterpret_cast<T *>(kry_[k]) + L0.gh * g.plane; };
+    T *const x = ptr<T>(MG_ARR_U, 0);
+    const T *const b = ptr<T>(MG_ARR_RHS, 0);
+    mg_krylov_stats out{0, 0, 0.0, 0.0};
+    int nh = 0;
+    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
+
+    double nb = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    // Dirichlet rows are identity rows carrying the boundary data: x takes b's values there, after which r, z, p and q
+    // vanish on the boundary and the iteration lives on the interior, where A is symmetric positive definite
+    launch_cg_boundary_copy<T>(stream_, g, x, b);
+    MG_HIP(hipGetLastError());
+    launch_residual<T>(stream_, g, c, x, b, kp(KR), d_partials_, d_scal_ + SC_RR);   // r0 = b - A x0, r0.r0
+    MG_HIP(hipGetLastError());
+    MG_TRY(fetch_scalars(SC_RR, d_scal_ + SC_RR));
+    const double rr0 = h_scal_[SC_RR];
+    record(std::sqrt(rr0 / nb));
+
+    if (nb == 0.0 || rr0 == 0.0) {
+        out.status = 0;   // nothing to do: b == 0 (x0 = 0 is the answer once its boundary is b's) or x0 solves the system
+    } else if (maxit == 0) {
+        out.status = 1;
+    } else {
+        MG_HIP(hipMemsetAsync(d_cg_, 0, sizeof(CgScalars), stream_));
+        int pc = KP0, pn = KP1;   // p ping-pongs: another workgroup may still read p_k at a neighbour while p_{k+1} is written
+        MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));   // p_{-1} = 0: p_0 = z_0 + 0 p_{-1} = z_0
+        auto direction = [&](int mode) -> int {   // z = M r, gamma, beta, p_{k+1} = z + beta p_k, q = A p_{k+1}, alpha
+            MG_TRY(precondition());
+            int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
+            np = launch_cg_direction_apply<T>(stream_, g, c, kp(KZ), kp(pc), kp(pn), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, CG_TAIL_ALPHA, d_cg_part_, np, d_cg_);
+            MG_HIP(hipGetLastError());
+            std::swap(pc, pn);
+            return MG_OK;
+        };
+        MG_TRY(direction(CG_TAIL_FIRST));
+        for (int k = 0; k < maxit; k++) {
+            const int np = launch_cg_update<T>(stream_, g, x, kp(pc), kp(KR), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, CG_TAIL_RR, d_cg_part_, np, d_cg_);
+            MG_HIP(hipGetLastError());
+            MG_HIP(hipMemcpyAsync(h_cg_, d_cg_, sizeof(CgScalars), hipMemcpyDeviceToHost, stream_));
+            MG_HIP(hipStreamSynchronize(stream_));   // the one host synchronisation per iteration: the stopping test
+            if (h_cg_->bad) { out.status = 2; break; }   // the update was skipped: x is the last iterate
+            out.iters = k + 1;
+            const double rel = std::sqrt(h_cg_->rr / nb);
+            record(rel);
+            if (rel <= tol) { out.status = 0; break; }
+            if (k + 1 == maxit) { out.status = 1; break; }
+            MG_TRY(direction(CG_TAIL_BETA));
+        }
+    }
+    double nr = 0;
+    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // the true residual of the returned x
+    out.relres_true = std::sqrt(nr / nb);
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
+int Solver::pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    MG_TRY(driver_begin("mg_pcg_solve", REFUSE_DIST | REFUSE_STAGE_CB));
+    MG_TRY(krylov_alloc());
+    return d_.dtype == MG_F64 ? pcg_t<double>(tol, maxit, hist, hist_cap, n_hist, st)
+                              : pcg_t<float>(tol, maxit, hist, hist_cap, n_hist, st);
+}
+
+template <typename T>
+int Solver::pcg_kernel_t(int kernel, double scalar, const int *a, double *dots)
+{
+    const Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    *h_cg_ = CgScalars{};
+    h_cg_->alpha = h_cg_->beta = scalar;
+    MG_HIP(hipMemcpyAsync(d_cg_, h_cg_, sizeof(CgScalars), hipMemcpyHostToDevice, stream_));
+    int np = 0;
+    if (kernel == MG_PCG_K_UPDATE) {
+        np = launch_cg_update<T>(stream_, g, ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0), ptr<T>(a[3], 0), d_cg_, d_cg_part_);
+        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
+    } else if (kernel == MG_PCG_K_DOTS) {
+        np = launch_cg_dots<T>(stream_, g, ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0), d_cg_, d_cg_part_);
+        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
+        launch_reduce_final(stream_, d_cg_part_ + np, np, d_cg_dot_ + 1);
+    } else {
+        np = launch_cg_direction_apply<T>(stream_, g, coef_of<T>(L0), ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0),
+                                          ptr<T>(a[3], 0), d_cg_, d_cg_part_);
+        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
+    }
+    MG_HIP(hipGetLastError());
+    MG_TRY(fetch_scalars(SC_CG_DOT, d_cg_dot_, 2));
+    dots[0] = h_scal_[SC_CG_DOT];
+    dots[1] = kernel == MG_PCG_K_DOTS ? h_scal_[SC_CG_DOT1] : 0.0;
+    return MG_OK;
+}
+
+int Solver::pcg_kernel(int kernel, double scalar, const int *arrs, double *dots)
+{
+    MG_TRY(driver_begin("mg_pcg_kernel", REFUSE_DIST));
+    if (kernel < MG_PCG_K_UPDATE || kernel > MG_PCG_K_DIRECTION) { set_last_error("mg_pcg_kernel: unknown kernel"); return MG_ERR_BAD_ARG; }
+    const int na = kernel == MG_PCG_K_DOTS ? 3 : 4;
+    for (int i = 0; i < na; i++) {
+        if (!check_arr(arrs[i], 0, "mg_pcg_kernel")) return MG_ERR_BAD_ARG;
+        for (int j = 0; j < i; j++)
+            if (arrs[i] == arrs[j]) { set_last_error("mg_pcg_kernel: the arrays must be distinct"); return MG_ERR_BAD_ARG; }
+    }
+    MG_TRY(krylov_scalars_alloc());
+    return d_.dtype == MG_F64 ? pcg_kernel_t<double>(kernel, scalar, arrs, dots)
+                              : pcg_kernel_t<float>(kernel, scalar, arrs, dots);
+}
+
+// ---------------------------------------------------------------- full multigrid (nested iteration), mg_fmg
+// f_{l+1} = R f_l down the hierarchy (the level operators are unscaled and the restrictions inject on the coarse boundary,
+// so this carries the right-hand side and the Dirichlet data), the coarsest-grid solve, then coarse to fine: U(l) = Pi U(l+1)
+// (mg_fmg.hip; Dirichlet nodes from RHS(l)) and cycles_per_level V-cycles started on level l. A cycle started on level l
+// only overwrites U and RHS of the levels below it, which the pass has finished with: no storage of its own.
+template <typename T>
+int Solver::fmg_t(int cycles_per_level, mg_fmg_stats *st)
+{
+    const int L = d_.levels;
+    for (int l = 0; l + 1 < L; l++) MG_TRY(restrict_t<T>(l, d_.restriction, MG_ARR_RHS, MG_ARR_RHS));
+    MG_TRY(zero_array(MG_ARR_U, L - 1));
+    launch_cg_boundary_copy<T>(stream_, lv_[L - 1].g, ptr<T>(MG_ARR_U, L - 1), ptr<T>(MG_ARR_RHS, L - 1));
+    MG_HIP(hipGetLastError());
+    MG_TRY(coarse_level_t<T>(L - 1, MG_ARR_U, MG_ARR_RHS, false));
+    MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));   // of this first, true coarse solve
+    for (int l = L - 2; l >= 0; l--) {
+        launch_fmg_prolong<T>(stream_, lv_[l + 1].g, lv_[l].g, ptr<T>(MG_ARR_U, l + 1), ptr<T>(MG_ARR_U, l), ptr<T>(MG_ARR_RHS, l));
+        MG_HIP(hipGetLastError());
+        for (int k = 0; k < cycles_per_level; k++) MG_TRY(vcycle_rec_t<T>(l));
+    }
+    double nb = 0, nr = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // synchronises: h_coarse_ is valid from here
+    if (st) {
+        st->levels = L;
+        st->cycles_per_level = cycles_per_level;
+        st->coarse_iters = h_coarse_->iters;
+        st->coarse_flag = h_coarse_->flag;
+        st->relres = std::sqrt(nr / nb);
+    }
+    return MG_OK;
+}
+
+int Solver::fmg(int cycles_per_level, mg_fmg_stats *st)
+{
+    MG_TRY(driver_begin("mg_fmg", REFUSE_DIST | REFUSE_STAGE_CB));
+    if (d_.cycle != MG_CYCLE_V) {
+        set_last_error("mg_fmg: the descriptor's cycle must be MG_CYCLE_V (the levels of a sawtooth cycle hold errors, not solutions)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (cycles_per_level < 1) {
+        set_last_error("mg_fmg: cycles_per_level must be at least 1");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? fmg_t<double>(cycles_per_level, st) : fmg_t<float>(cycles_per_level, st);
+}
+
+int Solver::fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)
+{
+    MG_TRY(driver_begin("mg_fmg_prolong", REFUSE_DIST));
+    if (coarse_level < 1 || coarse_level >= d_.levels || !check_arr(arr_src, coarse_level, "mg_fmg_prolong") ||
+        !check_arr(arr_dst, coarse_level - 1, "mg_fmg_prolong") || (arr_bnd >= 0 && !check_arr(arr_bnd, coarse_level - 1, "mg_fmg_prolong"))) {
+        set_last_error("mg_fmg_prolong: bad level / array");
+        return MG_ERR_BAD_ARG;
+    }
+    if (arr_bnd == arr_dst) { set_last_error("mg_fmg_prolong: arr_bnd must differ from arr_dst"); return MG_ERR_BAD_ARG; }
+    const int fl = coarse_level - 1;
+    if (arr_dst == MG_ARR_RHS) lv_[fl].rhs_halo_ok = false;
+    if (d_.dtype == MG_F64)
+        launch_fmg_prolong<double>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<double>(arr_src, coarse_level), ptr<double>(arr_dst, fl),
+                                   arr_bnd >= 0 ? ptr<double>(arr_bnd, fl) : (double *)nullptr);
+    else
+        launch_fmg_prolong<float>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<float>(arr_src, coarse_level), ptr<float>(arr_dst, fl),
+                                  arr_bnd >= 0 ? ptr<float>(arr_bnd, fl) : (float *)nullptr);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------- mixed-precision defect correction (mg_mixed_solve)
+// u and b of level 0 in fp64 beside the handle's fp32 hierarchy: r = b - A u in fp64, A e = r solved approximately by
+// inner_cycles of the fp32 cycles, u += e. The fp32 right-hand side is the residual times a power of two that keeps it
+// near 1 (exact both ways); the kernels are in mg_mixed.hip.
+int Solver::mixed_check(const char *fn, unsigned refuse)
+{
+    if (d_.dtype != MG_F32) {
+        set_last_error(std::string(fn) + ": the handle has to be created with MG_F32 (the cycles of the mixed-precision solver run in fp32; "
+                                         "this handle is MG_F64)");
+        return MG_ERR_BAD_ARG;
+    }
+    return driver_begin(fn, refuse);
+}
+
+int Solver::mixed_alloc()
+{
+    if (mx_[0]) return MG_OK;
+    const Level &L0 = lv_[0];
+    g64_ = L0.g;
+    g64_.pitch = ((L0.g.nx + 15) / 16) * 16;   // rows of doubles padded to 128 B
+    g64_.plane = (long long)g64_.ny * g64_.pitch;
+    mx_alloc_elems_ = (size_t)(g64_.nz + 2) * (size_t)g64_.plane;   // one (zero, unused) ghost plane either side, as every level
+    const size_t nbytes = mx_alloc_elems_ * sizeof(double), npart = (size_t)mixed_partials_capacity();
+    for (auto &b : mx_) MG_TRY(alloc_zeroed(&b, nbytes));
+    MG_HIP(hipMalloc((void **)&d_mx_part_, sizeof(double) * npart));
+    MG_HIP(hipMalloc((void **)&d_mx_sum_, sizeof(double)));
+    bytes_ += sizeof(double) * (npart + 1);
+    return MG_OK;
+}
+
+int Solver::mixed_set(bool rhs, const double *host)
+{
+    const char *fn = rhs ? "mg_mixed_set_rhs" : "mg_mixed_set_solution";
+    MG_TRY(mixed_check(fn));
+    MG_TRY(mixed_alloc());
+    MG_TRY(stage_copy(reinterpret_cast<char *>(mxptr(rhs ? MXB : MXU)), g64_, sizeof(double), const_cast<double *>(host), true));
+    (rhs ? mx_has_b_ : mx_has_u_) = true;
+    return MG_OK;
+}
+
+int Solver::mixed_get_solution(double *host)
+{
+    MG_TRY(mixed_check("mg_mixed_get_solution"));
+    if (!mx_has_u_) { set_last_error("mg_mixed_get_solution: no solution yet (call mg_mixed_set_solution first)"); return MG_ERR_BAD_ARG; }
+    return stage_copy(reinterpret_cast<char *>(mxptr(MXU)), g64_, sizeof(double), host, false);
+}
+
+// 2^-e with frexp(sqrt(v)) = (m, e): brings a vector of squared norm v to a norm in [0.5, 1)
+static double mixed_scale(double v)
+{
+    if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
+    int e = 0;
+    (void)std::frexp(std::sqrt(v), &e);
+    return std::ldexp(1.0, -e);
+}
+
+int Solver::mixed_inner(int inner_cycles)
+{
+    MG_HIP(hipMemsetAsync(lv_[0].base[MG_ARR_U], 0, lv_[0].alloc_elems * esize(), stream_));
+    for (int c = 0; c < inner_cycles; c++) MG_TRY(outer_iteration_enqueue());
+    return MG_OK;
+}
+
+int Solver::mixed_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st)
+{
+    MG_TRY(mixed_check("mg_mixed_solve", REFUSE_DIST | REFUSE_STAGE_CB));
+    if (inner_cycles < 1) { set_last_error("mg_mixed_solve: inner_cycles must be at least 1"); return MG_ERR_BAD_ARG; }
+    if (maxit < 0) { set_last_error("mg_mixed_solve: negative maxit"); return MG_ERR_BAD_ARG; }
+    if (!mx_has_b_ || !mx_has_u_) {
+        set_last_error("mg_mixed_solve: call mg_mixed_set_rhs and mg_mixed_set_solution first");
+        return MG_ERR_BAD_ARG;
+    }
+    Level &L0 = lv_[0];
+    const Geom &g32 = L0.g;
+    const double *const b = mxptr(MXB);
+    mg_mixed_stats out{0, 0, 0, 0, 0.0};
+    int nh = 0;
+    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
+    auto fetch_sum = [&](double *v) -> int {   // the sum the last launch left in d_mx_sum_; synchronises
+        MG_HIP(hipGetLastError());
+        MG_TRY(fetch_scalars(SC_MX_SUM, d_mx_sum_));
+        *v = h_scal_[SC_MX_SUM];
+        return MG_OK;
+    };
+
+    // u = b on the Dirichlet nodes; b.b over all nodes, as mg_solve
+    launch_cg_boundary_copy<double>(stream_, g64_, mxptr(MXU), b);
+    int np = launch_mixed_sumsq(stream_, g64_, b, d_mx_part_);
+    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+    double bb = 0, rr = 0;
+    MG_TRY(fetch_sum(&bb));
+    double s = mixed_scale(bb);   // the scale RHS32(0) currently carries
+    L0.rhs_halo_ok = false;
+    np = launch_mixed_residual(stream_, g64_, g32, L0.coef, mxptr(MXU), b, ptr<float>(MG_ARR_RHS, 0), s, d_mx_part_);
+    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+    MG_TRY(fetch_sum(&rr));
+    auto relres = [&](double v) { return v == 0.0 ? 0.0 : std::sqrt(v / bb); };
+    record(relres(rr));
+    if (!std::isfinite(rr) || !std::isfinite(out.relres)) {
+        out.status = 2;
+    } else if (rr == 0.0) {
+        out.status = 0;   // nothing to do: u solves the system (b == 0 with u == 0 inside included)
+    } else {
+        for (int k = 0;; k++) {
+            if (k > 0 && out.relres <= tol) { out.status = 0; break; }
+            if (k == maxit) { out.status = 1; break; }
+            MG_TRY(mixed_inner(inner_cycles));
+            out.cycles += inner_cycles;
+            const double s_next = mixed_scale(rr);   // from the PREVIOUS residual: known before the launch
+            np = launch_mixed_correct_residual(stream_, g64_, g32, L0.coef, mxptr(MXU), ptr<float>(MG_ARR_U, 0), b, mxptr(MXU2),
+                                               ptr<float>(MG_ARR_RHS, 0), s, s_next, d_mx_part_);
+            launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+            double rr_new = 0;
+            MG_TRY(fetch_sum(&rr_new));   // the one host synchronisation per correction: the stopping test
+            record(relres(rr_new));
+            if (!std::isfinite(rr_new) || !std::isfinite(out.relres)) { out.status = 2; break; }   // not taken: u64 stays the last iterate
+            std::swap(mx_[MXU], mx_[MXU2]);
+            out.outer = k + 1;
+            rr = rr_new;
+            s = s_next;
+        }
+    }
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
+int Solver::mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r)
+{
+    MG_TRY(mixed_check("mg_mixed_kernel"));
+    if (kernel != MG_MIXED_K_RESIDUAL && kernel != MG_MIXED_K_CORRECT_RESIDUAL) { set_last_error("mg_mixed_kernel: unknown kernel"); return MG_ERR_BAD_ARG; }
+    const bool corr = kernel == MG_MIXED_K_CORRECT_RESIDUAL;
+    if (!check_arr(arr_r32, 0, "mg_mixed_kernel") || (corr && !check_arr(arr_e32, 0, "mg_mixed_kernel"))) return MG_ERR_BAD_ARG;
+    if (corr && arr_e32 == arr_r32) { set_last_error("mg_mixed_kernel: the arrays must be distinct"); return MG_ERR_BAD_ARG; }
+    if (corr && !(scale_in != 0.0 && std::isfinite(scale_in))) { set_last_error("mg_mixed_kernel: scale_in must be finite and not zero"); return MG_ERR_BAD_ARG; }
+    if (!mx_has_b_ || !mx_has_u_) {
+        set_last_error("mg_mixed_kernel: call mg_mixed_set_rhs and mg_mixed_set_solution first");
+        return MG_ERR_BAD_ARG;
+    }
+    Level &L0 = lv_[0];
+    if (arr_r32 == MG_ARR_RHS) L0.rhs_halo_ok = false;
+    int np = 0;
+    if (corr)
+        np = launch_mixed_correct_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), ptr<float>(arr_e32, 0), mxptr(MXB), mxptr(MXU2),
+                                           ptr<float>(arr_r32, 0), scale_in, scale_out, d_mx_part_);
+    else
+        np = launch_mixed_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), mxptr(MXB), ptr<float>(arr_r32, 0), scale_out, d_mx_part_);
+    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+    MG_HIP(hipGetLastError());
+    MG_TRY(fetch_scalars(SC_MX_SUM, d_mx_sum_));
+    if (corr) std::swap(mx_[MXU], mx_[MXU2]);
+    if (sumsq_r) *sumsq_r = h_scal_[SC_MX_SUM];
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------- diagonal shift (mg_set_shift)
+// Every launch rebuilds its Coef from Level::coef (coef_of; mixed_solve hands L0.coef to its fp64 kernels), so the shifted
+// operator needs nothing but the new diagonal -- and new line factors where the smoother is a zebra one, the only data
+// derived from cd when the handle is created.
+int Solver::set_shift(double sigma)
+{
+    if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_last_error("mg_set_shift: sigma must be finite and not negative"); return MG_ERR_BAD_ARG; }
+    MG_TRY(driver_begin("mg_set_shift", REFUSE_DIST));
+    if (sigma == shift_) return MG_OK;
+    const bool zebra = is_zebra(d_.smoother);
+    if (zebra) MG_HIP(hipStreamSynchronize(stream_));   // no queued sweep may read a half-written table
+    for (auto &L : lv_) {
+        L.coef[3] = L.cd0 + sigma;
+        if (zebra && L.zebra) MG_TRY(zebra_tabulate(L));
+    }
+    shift_ = sigma;
+    return MG_OK;
+}
+
+// ---------------------------------------------------------------- implicit heat-equation stepper (mg_heat_*)
+// u_t = -A0 u + f by the theta scheme: per step one launch of mg_heat.hip builds the right-hand side from U (+ f) into
+// RHS, then cycles_per_step outer iterations of mg_solve on (1/(theta dt) I + A0) u' = rhs, warm-started from u.
+int Solver::heat_check(const char *fn, double dt, double theta)
+{
+    MG_TRY(driver_begin(fn, REFUSE_DIST));
+    if (!(dt > 0.0) || !std::isfinite(dt)) { set_last_error(std::string(fn) + ": dt must be positive and finite"); return MG_ERR_BAD_ARG; }
+    if (!(theta > 0.0 && theta <= 1.0)) { set_last_error(std::string(fn) + ": theta must be in (0, 1]"); return MG_ERR_BAD_ARG; }
+    if (!std::isfinite(1.0 / (theta * dt)) || !std::isfinite(1.0 / dt)) {
+        set_last_error(std::string(fn) + ": dt is too small: 1 / (theta dt) is not finite");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::heat_set_source(const void *host)
+{
+    MG_TRY(driver_begin("mg_heat_set_source", REFUSE_DIST));
+    if (!host) { heat_has_f_ = false; return MG_OK; }
+    const Level &L0 = lv_[0];
+    if (!heat_f_) MG_TRY(alloc_zeroed(&heat_f_, L0.alloc_elems * esize()));
+    MG_TRY(stage_copy(static_cast<char *>(heat_f_) + (size_t)L0.gh * (size_t)L0.g.plane * esize(), L0.g, esize(), const_cast<void *>(host), true));
+    heat_has_f_ = true;
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::heat_rhs_t(double dt, double theta, int arr_u, int arr_dst)
+{
+    Level &L0 = lv_[0];
+    const double coef0[4] = {L0.coef[0], L0.coef[1], L0.coef[2], L0.cd0};
+    const T *f = heat_has_f_ ? reinterpret_cast<const T *>(heat_f_) + L0.gh * L0.g.plane : (const T *)nullptr;
+    if (arr_dst == MG_ARR_RHS) L0.rhs_halo_ok = false;
+    launch_heat_rhs<T>(stream_, L0.g, coef0, dt, theta, ptr<T>(arr_u, 0), f, ptr<T>(arr_dst, 0));
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::heat_rhs(double dt, double theta, int arr_u, int arr_dst)
+{
+    MG_TRY(heat_check("mg_heat_rhs", dt, theta));
+    if (!check_arr(arr_u, 0, "mg_heat_rhs") || !check_arr(arr_dst, 0, "mg_heat_rhs")) return MG_ERR_BAD_ARG;
+    if (arr_u == arr_dst) { set_last_error("mg_heat_rhs: arr_dst must differ from arr_u"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? heat_rhs_t<double>(dt, theta, arr_u, arr_dst) : heat_rhs_t<float>(dt, theta, arr_u, arr_dst);
+}
+
+template <typename T>
+int Solver::heat_step_t(double dt, double theta, int nsteps, int cycles_per_step)
+{
+    for (int n = 0; n < nsteps; n++) {
+        MG_TRY(heat_rhs_t<T>(dt, theta, MG_ARR_U, MG_ARR_RHS));
+        for (int c = 0; c < cycles_per_step; c++) MG_TRY(outer_iteration_enqueue());
+    }
+    MG_TRY(residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
+    return sumsq_t<T>(0, MG_ARR_RHS);
+}
+
+int Solver::heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
+{
+    MG_TRY(heat_check("mg_heat_step", dt, theta));
+    MG_TRY(driver_begin("mg_heat_step", REFUSE_STAGE_CB));   // a call of its own: a bad dt or theta is reported first
+    if (nsteps < 1) { set_last_error("mg_heat_step: nsteps must be at least 1"); return MG_ERR_BAD_ARG; }
+    if (cycles_per_step < 1) { set_last_error("mg_heat_step: cycles_per_step must be at least 1"); return MG_ERR_BAD_ARG; }
+    MG_TRY(set_shift(1.0 / (theta * dt)));
+    MG_TRY(d_.dtype == MG_F64 ? heat_step_t<double>(dt, theta, nsteps, cycles_per_step) : heat_step_t<float>(dt, theta, nsteps, cycles_per_step));
+    // the one host synchronisation of the call: ||rhs - (sigma I + A0) u|| / ||rhs|| of the last step
+    MG_TRY(fetch_scalars(SC_RR, d_scal_ + SC_RR, 2));   // SC_RR and SC_BB
+    if (st) {
+        st->steps = nsteps;
+        st->cycles = nsteps * cycles_per_step;
+        st->time = (double)nsteps * dt;
+        st->relres = h_scal_[SC_RR] == 0.0 ? 0.0 : std::sqrt(h_scal_[SC_RR] / h_scal_[SC_BB]);
+    }
+    return MG_OK;
+}
+
+}  // namespace mg

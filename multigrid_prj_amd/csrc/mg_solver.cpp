@@ -1,6 +1,6 @@
-// mg_solver.cpp -- grid hierarchy in HBM + stream-ordered cycle drivers.
-// Reference call structure being replaced: SawtoothMGIteration
-// (include/multigrid.hpp:108-145) and the outer loop of src/main.cpp:72-116.
+// mg_solver.cpp -- grid hierarchy in HBM: allocation, staging, communication, the per-operator launch paths and the
+// stream-ordered cycle. The drivers that call the cycle from above are in mg_drivers.cpp.
+// Reference call structure being replaced: SawtoothMGIteration (include/multigrid.hpp:108-145).
 #include "mg_solver.h"
 
 #include <algorithm>
@@ -17,15 +17,6 @@ namespace mg {
 static thread_local std::string g_last_error;
 void set_last_error(const std::string &msg) { g_last_error = msg; }
 const std::string &last_error() { return g_last_error; }
-
-#define MG_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return MG_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
 
 int validate_desc(const mg_desc *d, std::string *why)
 {
@@ -54,7 +45,6 @@ int validate_desc(const mg_desc *d, std::string *why)
     return MG_OK;
 }
 
-static bool is_zebra(int smoother) { return smoother == MG_SMOOTH_ZEBRA_Y || smoother == MG_SMOOTH_ZEBRA_X; }
 // the coarsest-grid solver of a zebra hierarchy smooths with red-black Gauss-Seidel (mg_desc.h)
 static int coarse_smoother_of(int smoother) { return is_zebra(smoother) ? MG_SMOOTH_RBGS : smoother; }
 
@@ -249,12 +239,7 @@ int Solver::init()
             if (L.dist) {
                 if (l == T_ && rank_ == 0 && T_ == d_.levels - 1) {  // coarsest level still distributed: rank 0 solves it gathered
                     gfull_ = L.g;
-                    for (auto &f : full_) {
-                        size_t nbytes = (size_t)(gfull_.nz + 2) * (size_t)gfull_.plane * esize();
-                        MG_HIP(hipMalloc(&f, nbytes));
-                        MG_HIP(hipMemsetAsync(f, 0, nbytes, stream_));
-                        bytes_ += nbytes;
-                    }
+                    for (auto &f : full_) MG_TRY(alloc_zeroed(&f, (size_t)(gfull_.nz + 2) * (size_t)gfull_.plane * esize()));
                     max_partials = std::max(max_partials, reduce_partials_capacity(gfull_));
                 }
                 if (l == T_) {
@@ -280,12 +265,7 @@ int Solver::init()
             }
             stage_g_ = L.g;
             stage_g_.nz = planS_[rank_].nz; stage_g_.gz0 = planS_[rank_].z0;
-            for (auto &b : stage_base_) {
-                size_t nbytes = (size_t)(stage_g_.nz + 2) * (size_t)stage_g_.plane * esize();
-                MG_HIP(hipMalloc(&b, nbytes));
-                MG_HIP(hipMemsetAsync(b, 0, nbytes, stream_));
-                bytes_ += nbytes;
-            }
+            for (auto &b : stage_base_) MG_TRY(alloc_zeroed(&b, (size_t)(stage_g_.nz + 2) * (size_t)stage_g_.plane * esize()));
         }
         if (!L.dist) L.nz_min = L.g.nz;
         // Interior / boundary split with the exchange on the communication stream: two cross-stream waits (6-20 us each on
@@ -298,10 +278,7 @@ int Solver::init()
         if (!L.present) continue;
         for (int a = 0; a < NUM_ARR; a++) {
             if (a == MG_ARR_RES && l > 0) continue;
-            size_t nbytes = L.alloc_elems * esize();
-            MG_HIP(hipMalloc(&L.base[a], nbytes));
-            MG_HIP(hipMemsetAsync(L.base[a], 0, nbytes, stream_));
-            bytes_ += nbytes;
+            MG_TRY(alloc_zeroed(&L.base[a], L.alloc_elems * esize()));
         }
         if (is_zebra(d_.smoother)) {  // elimination factors of the line solve: along y (cy, ny) or along x (cx, nx)
             const size_t nb = 2 * (size_t)(d_.smoother == MG_SMOOTH_ZEBRA_X ? L.g.nx : L.g.ny) * esize();
@@ -314,14 +291,14 @@ int Solver::init()
         if (cap > max_partials) max_partials = cap;
     }
     MG_HIP(hipMalloc((void **)&d_partials_, sizeof(double) * (size_t)max_partials));
-    MG_HIP(hipMalloc((void **)&d_scal_, sizeof(double) * 8));
+    MG_HIP(hipMalloc((void **)&d_scal_, sizeof(double) * SC_COUNT));
     MG_HIP(hipMalloc((void **)&d_coarse_, sizeof(CoarseOut)));
-    MG_HIP(hipMemsetAsync(d_scal_, 0, sizeof(double) * 8, stream_));
+    MG_HIP(hipMemsetAsync(d_scal_, 0, sizeof(double) * SC_COUNT, stream_));
     MG_HIP(hipMemsetAsync(d_coarse_, 0, sizeof(CoarseOut), stream_));
-    MG_HIP(hipHostMalloc((void **)&h_scal_, sizeof(double) * 8));
+    MG_HIP(hipHostMalloc((void **)&h_scal_, sizeof(double) * SC_COUNT));
     MG_HIP(hipHostMalloc((void **)&h_coarse_, sizeof(CoarseOut)));
     MG_HIP(hipHostMalloc((void **)&h_fixed_, sizeof(CoarseOut)));
-    bytes_ += sizeof(double) * ((size_t)max_partials + 8) + sizeof(CoarseOut);
+    bytes_ += sizeof(double) * ((size_t)max_partials + SC_COUNT) + sizeof(CoarseOut);
     MG_HIP(hipStreamSynchronize(stream_));
     return MG_OK;
 }
@@ -345,6 +322,38 @@ int Solver::zebra_tabulate(Level &L)
     return MG_OK;
 }
 
+int Solver::alloc_zeroed(void **p, size_t nbytes)
+{
+    MG_HIP(hipMalloc(p, nbytes));
+    MG_HIP(hipMemsetAsync(*p, 0, nbytes, stream_));
+    bytes_ += nbytes;
+    return MG_OK;
+}
+
+int Solver::fetch_scalars(int slot, const double *dev, int n)
+{
+    MG_HIP(hipMemcpyAsync(h_scal_ + slot, dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    return MG_OK;
+}
+
+void Solver::fill_cycle_stats(mg_cycle_stats *st, double fine_sumsq_r) const
+{
+    st->coarse_iters = h_coarse_->iters;
+    st->coarse_flag = h_coarse_->flag;
+    st->coarse_relres = h_coarse_->relres;
+    st->fine_sumsq_r = fine_sumsq_r;
+}
+
+int Solver::fetch_cycle_stats(mg_cycle_stats *st, bool with_fine)
+{
+    MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));
+    if (with_fine) MG_TRY(fetch_scalars(SC_CYCLE_RR, d_scal_ + SC_CYCLE_RR));
+    else MG_HIP(hipStreamSynchronize(stream_));
+    if (st) fill_cycle_stats(st, with_fine && d_.cycle == MG_CYCLE_SAWTOOTH ? h_scal_[SC_CYCLE_RR] : 0.0);
+    return MG_OK;
+}
+
 bool Solver::check_arr(int which, int level, const char *fn) const
 {
     if (level < 0 || level >= d_.levels || which < 0 || which >= NUM_ARR || !lv_[level].base[which]) {
@@ -352,13 +361,6 @@ bool Solver::check_arr(int which, int level, const char *fn) const
         return false;
     }
     return true;
-}
-
-template <typename T>
-T *Solver::ptr(int which, int level) const
-{
-    const Level &L = lv_[level];
-    return reinterpret_cast<T *>(L.base[which]) + L.gh * L.g.plane;  // skip the lower ghost plane(s)
 }
 
 // Host <-> device copies of a level's array (dense rows on the host, 128-byte-pitched rows on the device)
@@ -487,8 +489,6 @@ int Solver::zero_array(int which, int level)
     MG_HIP(hipMemsetAsync(lv_[level].base[which], 0, lv_[level].alloc_elems * esize(), stream_));
     return MG_OK;
 }
-
-#define MG_TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 int Solver::post(const P2POp *ops, int n, hipStream_t s)
 {
@@ -689,14 +689,6 @@ int Solver::allreduce(double *dptr, int n)
     int rc = comm_->allreduce_sum(dptr, n, stream_);
     if (rc) set_last_error("allreduce failed");
     return rc;
-}
-
-template <typename T>
-static Coef<T> coef_of(const Level &L)
-{
-    Coef<T> c = make_coef<T>(L.coef[0], L.coef[1], L.coef[2], L.coef[3]);
-    if (!switches().fast_div) c.win = 0;  // A/B switch: hardware division everywhere
-    return c;
 }
 
 // true when the first pre-smoothing sweep of `level` can consume an implicit zero guess
@@ -1117,9 +1109,9 @@ int Solver::residual_t(int level, int ax, int ar, int arr_r, bool want_norm)
     MG_TRY(exchange(ax, level));
     launch_residual<T>(stream_, L.g, coef_of<T>(L), ptr<T>(ax, level), ptr<T>(ar, level),
                        arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr, d_partials_,
-                       want_norm ? d_scal_ : (double *)nullptr);
+                       want_norm ? d_scal_ + SC_RR : (double *)nullptr);
     MG_HIP(hipGetLastError());
-    if (want_norm && L.dist) MG_TRY(allreduce(d_scal_, 1));
+    if (want_norm && L.dist) MG_TRY(allreduce(d_scal_ + SC_RR, 1));
     return MG_OK;
 }
 
@@ -1136,9 +1128,8 @@ int Solver::residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq
                                 : residual_t<float>(level, arr_x, arr_rhs, arr_r, true);
     if (rc) return rc;
     if (sumsq_out) {
-        MG_HIP(hipMemcpyAsync(h_scal_, d_scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
-        MG_HIP(hipStreamSynchronize(stream_));
-        *sumsq_out = h_scal_[0];
+        MG_TRY(fetch_scalars(SC_RR, d_scal_ + SC_RR));
+        *sumsq_out = h_scal_[SC_RR];
     }
     return MG_OK;
 }
@@ -1146,9 +1137,9 @@ int Solver::residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq
 template <typename T>
 int Solver::sumsq_t(int level, int arr)
 {
-    launch_sumsq<T>(stream_, lv_[level].g, ptr<T>(arr, level), d_partials_, d_scal_ + 1);
+    launch_sumsq<T>(stream_, lv_[level].g, ptr<T>(arr, level), d_partials_, d_scal_ + SC_BB);
     MG_HIP(hipGetLastError());
-    if (lv_[level].dist) MG_TRY(allreduce(d_scal_ + 1, 1));
+    if (lv_[level].dist) MG_TRY(allreduce(d_scal_ + SC_BB, 1));
     return MG_OK;
 }
 
@@ -1158,9 +1149,8 @@ int Solver::sumsq(int level, int arr, double *out)
     MG_HIP(hipSetDevice(device_));
     int rc = d_.dtype == MG_F64 ? sumsq_t<double>(level, arr) : sumsq_t<float>(level, arr);
     if (rc) return rc;
-    MG_HIP(hipMemcpyAsync(h_scal_ + 1, d_scal_ + 1, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipStreamSynchronize(stream_));
-    *out = h_scal_[1];
+    MG_TRY(fetch_scalars(SC_BB, d_scal_ + SC_BB));
+    *out = h_scal_[SC_BB];
     return MG_OK;
 }
 
@@ -1278,15 +1268,7 @@ int Solver::coarse_solve_ex(int level, int arr_x, int arr_rhs, int smoother, int
     int rc = d_.dtype == MG_F64 ? coarse_ex_t<double>(level, arr_x, arr_rhs, smoother, maxit, tol, fixed)
                                 : coarse_ex_t<float>(level, arr_x, arr_rhs, smoother, maxit, tol, fixed);
     if (rc) return rc;
-    MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipStreamSynchronize(stream_));
-    if (st) {
-        st->coarse_iters = h_coarse_->iters;
-        st->coarse_flag = h_coarse_->flag;
-        st->coarse_relres = h_coarse_->relres;
-        st->fine_sumsq_r = 0;
-    }
-    return MG_OK;
+    return fetch_cycle_stats(st);
 }
 
 // Coarse solve of a coarsest level that is still distributed (few levels, many ranks):
@@ -1448,7 +1430,7 @@ int Solver::cycle_enqueue_t()
     // --- reference sawtooth, include/multigrid.hpp:126-145 ---
     // :127  sol * RES : fine residual into `res`, sum r^2
     MG_TRY(residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, MG_ARR_RES, true));
-    MG_HIP(hipMemcpyAsync(d_scal_ + 2, d_scal_, sizeof(double), hipMemcpyDeviceToDevice, stream_));
+    MG_HIP(hipMemcpyAsync(d_scal_ + SC_CYCLE_RR, d_scal_ + SC_RR, sizeof(double), hipMemcpyDeviceToDevice, stream_));
     // every level's rhs is the fine residual seen through mask() (:113,121) = injection
     int src = MG_ARR_RES;
     for (int l = 0; l + 1 < L; l++) {
@@ -1496,16 +1478,7 @@ int Solver::cycle(mg_cycle_stats *st)
 {
     MG_HIP(hipSetDevice(device_));
     MG_TRY(cycle_enqueue());
-    MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipMemcpyAsync(h_scal_ + 2, d_scal_ + 2, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipStreamSynchronize(stream_));
-    if (st) {
-        st->coarse_iters = h_coarse_->iters;
-        st->coarse_flag = h_coarse_->flag;
-        st->coarse_relres = h_coarse_->relres;
-        st->fine_sumsq_r = (d_.cycle == MG_CYCLE_SAWTOOTH) ? h_scal_[2] : 0.0;
-    }
-    return MG_OK;
+    return fetch_cycle_stats(st, true);   // fine_sumsq_r: the sawtooth cycle's fine sum r^2, 0 after a V-cycle
 }
 
 int Solver::cycle_async(int count)
@@ -1531,79 +1504,6 @@ bool Solver::pair_norm_ok() const
     const bool sm = (d_.smoother == MG_SMOOTH_JACOBI && d_.nu_pre == 2 && jacobi2_ok<T>(L.g)) ||
                     (d_.smoother == MG_SMOOTH_RBGS && d_.nu_pre >= 1 && rb_fused_ok<T>(L.g));   // red-black: the first sweep carries it
     return sm && nranks_ == 1 && pair_wide_ok<T>(L.g);
-}
-
-// Outer loop of src/main.cpp:72-116.
-int Solver::solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist,
-                  mg_cycle_stats *per_cycle, const int *lock_counts, int n_lock)
-{
-    MG_HIP(hipSetDevice(device_));
-    double nb = 0, nr = 0;
-    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));                       // Residual ctor, solvers.hpp:237-242
-    const bool fused_norm = !lock_counts && (d_.dtype == MG_F64 ? pair_norm_ok<double>() : pair_norm_ok<float>());
-    if (fused_norm) {
-        // Same loop, same history: entry k is the norm after k cycles. It is computed by the first pre-smoothing pair of cycle
-        // k + 1, which runs before the test; when the test says stop (or maxit is reached) that pair's output is dropped -- it
-        // was written out of place, U still holds the iterate the norm belongs to.
-        Level &L0 = lv_[0];
-        int nh = 0;
-        for (int it = 0; it <= maxit; it++) {
-            void *const base_u = L0.base[MG_ARR_U], *const base_t = L0.base[MG_ARR_TMP];
-            want_pair_norm_ = true; pair_norm_done_ = false;
-            // the speculative launch: the Jacobi pair (both pre-smoothing sweeps), or the first red-black sweep -- ONE out-of-place
-            // launch either way, so the iterate the norm belongs to is still whole when the test says stop
-            const int spec = d_.smoother == MG_SMOOTH_JACOBI ? d_.nu_pre : 1;
-            const int rc = d_.dtype == MG_F64 ? smooth_t<double>(0, d_.smoother, spec, MG_ARR_U, MG_ARR_RHS, false, -1, true)
-                                              : smooth_t<float>(0, d_.smoother, spec, MG_ARR_U, MG_ARR_RHS, false, -1, true);
-            want_pair_norm_ = false;
-            MG_TRY(rc);
-            if (!pair_norm_done_) { set_last_error("mg_solve: the pre-smoothing pair did not deliver the residual norm"); return MG_ERR_HIP; }
-            MG_HIP(hipMemcpyAsync(h_scal_, d_scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
-            MG_HIP(hipStreamSynchronize(stream_));
-            nr = h_scal_[0];
-            if (per_cycle && it > 0) {                       // the coarse solver's record of the cycle that has just finished
-                mg_cycle_stats &st = per_cycle[it - 1];
-                st.coarse_iters = h_coarse_->iters;
-                st.coarse_flag = h_coarse_->flag;
-                st.coarse_relres = h_coarse_->relres;
-                st.fine_sumsq_r = 0.0;
-            }
-            const double rel = std::sqrt(nr / nb);
-            if (hist && nh < hist_cap) hist[nh] = rel;
-            nh++;
-            if ((it > 0 && rel <= tol) || it == maxit) {     // main.cpp:88-89 / the loop bound: drop the speculative pair
-                L0.base[MG_ARR_U] = base_u; L0.base[MG_ARR_TMP] = base_t;
-                break;
-            }
-            fine_pre_done_ = spec;
-            const int crc = cycle_enqueue();
-            fine_pre_done_ = 0;
-            MG_TRY(crc);
-            if (per_cycle) MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));
-        }
-        MG_HIP(hipStreamSynchronize(stream_));
-        if (n_hist) *n_hist = nh;
-        return MG_OK;
-    }
-    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));      // main.cpp:73-74
-    int nh = 0;
-    if (hist && nh < hist_cap) hist[nh] = std::sqrt(nr / nb);
-    nh++;
-    for (int it = 0; it < maxit; it++) {
-        if (d_.outer_pre_gs > 0)                             // `u * GS * GS` main.cpp:85
-            MG_TRY(smooth(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS));
-        lock_iters_ = (lock_counts && it < n_lock) ? lock_counts[it] : -1;
-        const int crc = cycle(per_cycle ? &per_cycle[it] : nullptr);  // `* MGx`
-        lock_iters_ = -1;
-        MG_TRY(crc);
-        MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));  // main.cpp:86
-        double rel = std::sqrt(nr / nb);
-        if (hist && nh < hist_cap) hist[nh] = rel;
-        nh++;
-        if (rel <= tol) break;                               // main.cpp:88-89
-    }
-    if (n_hist) *n_hist = nh;
-    return MG_OK;
 }
 
 int Solver::set_stage_callback(mg_stage_fn fn, void *user)
@@ -1739,568 +1639,17 @@ int Solver::timer_stop(double *ms)
     return MG_OK;
 }
 
-// ---------------------------------------------------------------- multigrid-preconditioned flexible CG (mg_pcg_solve)
-int Solver::krylov_scalars_alloc()
-{
-    if (d_cg_) return MG_OK;
-    const size_t npart = (size_t)cg_partials_capacity();
-    MG_HIP(hipMalloc((void **)&d_cg_, sizeof(CgScalars)));
-    MG_HIP(hipMalloc((void **)&d_cg_part_, sizeof(double) * npart));
-    MG_HIP(hipMalloc((void **)&d_cg_dot_, sizeof(double) * 2));
-    MG_HIP(hipHostMalloc((void **)&h_cg_, sizeof(CgScalars)));
-    bytes_ += sizeof(CgScalars) + sizeof(double) * (npart + 2);
-    return MG_OK;
-}
-
-int Solver::krylov_alloc()
-{
-    MG_TRY(krylov_scalars_alloc());
-    if (kry_[0]) return MG_OK;
-    const size_t nbytes = lv_[0].alloc_elems * esize();
-    for (auto &b : kry_) {
-        MG_HIP(hipMalloc(&b, nbytes));
-        MG_HIP(hipMemsetAsync(b, 0, nbytes, stream_));   // ghost planes and padding columns stay zero from here on
-        bytes_ += nbytes;
-    }
-    return MG_OK;
-}
-
-// z = M r: the cycle code works on level 0's U / RHS slots, so z and r take them for the duration (pointer swap, no copy).
-// The cycle may itself leave its result in the array that was TMP (out-of-place sweeps swap U / TMP): whatever U points
-// at afterwards is z, and TMP keeps the other buffer.
-template <typename T>
-int Solver::precondition_t()
-{
-    Level &L0 = lv_[0];
-    void *const x_base = L0.base[MG_ARR_U], *const b_base = L0.base[MG_ARR_RHS];
-    MG_HIP(hipMemsetAsync(kry_[KZ], 0, L0.alloc_elems * esize(), stream_));
-    L0.base[MG_ARR_U] = kry_[KZ];
-    L0.base[MG_ARR_RHS] = kry_[KR];
-    int rc = MG_OK;
-    if (d_.outer_pre_gs > 0) rc = smooth_t<T>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS);   // `u * GS * GS`
-    if (rc == MG_OK) rc = cycle_enqueue_t<T>();                                                              // `* MGx`
-    kry_[KZ] = L0.base[MG_ARR_U];
-    L0.base[MG_ARR_U] = x_base;
-    L0.base[MG_ARR_RHS] = b_base;
-    return rc;
-}
-
-template <typename T>
-int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
-{
-    Level &L0 = lv_[0];
-    const Geom &g = L0.g;
-    const Coef<T> c = coef_of<T>(L0);
-    auto kp = [&](int k) { return reinterpret_cast<T *>(kry_[k]) + L0.gh * g.plane; };
-    T *const x = ptr<T>(MG_ARR_U, 0);
-    const T *const b = ptr<T>(MG_ARR_RHS, 0);
-    mg_krylov_stats out{0, 0, 0.0, 0.0};
-    int nh = 0;
-    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
-
-    double nb = 0;
-    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
-    // Dirichlet rows are identity rows carrying the boundary data: x takes b's values there, after which r, z, p and q
-    // vanish on the boundary and the iteration lives on the interior, where A is symmetric positive definite
-    launch_cg_boundary_copy<T>(stream_, g, x, b);
-    MG_HIP(hipGetLastError());
-    launch_residual<T>(stream_, g, c, x, b, kp(KR), d_partials_, d_scal_);   // r0 = b - A x0, r0.r0
-    MG_HIP(hipGetLastError());
-    MG_HIP(hipMemcpyAsync(h_scal_, d_scal_, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipStreamSynchronize(stream_));
-    const double rr0 = h_scal_[0];
-    record(std::sqrt(rr0 / nb));
-
-    if (nb == 0.0 || rr0 == 0.0) {
-        out.status = 0;   // nothing to do: b == 0 (x0 = 0 is the answer once its boundary is b's) or x0 solves the system
-    } else if (maxit == 0) {
-        out.status = 1;
-    } else {
-        MG_HIP(hipMemsetAsync(d_cg_, 0, sizeof(CgScalars), stream_));
-        int pc = KP0, pn = KP1;   // p ping-pongs: another workgroup may still read p_k at a neighbour while p_{k+1} is written
-        MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));   // p_{-1} = 0: p_0 = z_0 + 0 p_{-1} = z_0
-        auto direction = [&](int mode) -> int {   // z = M r, gamma, beta, p_{k+1} = z + beta p_k, q = A p_{k+1}, alpha
-            MG_TRY(precondition_t<T>());
-            int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
-            launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
-            np = launch_cg_direction_apply<T>(stream_, g, c, kp(KZ), kp(pc), kp(pn), kp(KQ), d_cg_, d_cg_part_);
-            launch_cg_tail(stream_, CG_TAIL_ALPHA, d_cg_part_, np, d_cg_);
-            MG_HIP(hipGetLastError());
-            std::swap(pc, pn);
-            return MG_OK;
-        };
-        MG_TRY(direction(CG_TAIL_FIRST));
-        for (int k = 0; k < maxit; k++) {
-            const int np = launch_cg_update<T>(stream_, g, x, kp(pc), kp(KR), kp(KQ), d_cg_, d_cg_part_);
-            launch_cg_tail(stream_, CG_TAIL_RR, d_cg_part_, np, d_cg_);
-            MG_HIP(hipGetLastError());
-            MG_HIP(hipMemcpyAsync(h_cg_, d_cg_, sizeof(CgScalars), hipMemcpyDeviceToHost, stream_));
-            MG_HIP(hipStreamSynchronize(stream_));   // the one host synchronisation per iteration: the stopping test
-            if (h_cg_->bad) { out.status = 2; break; }   // the update was skipped: x is the last iterate
-            out.iters = k + 1;
-            const double rel = std::sqrt(h_cg_->rr / nb);
-            record(rel);
-            if (rel <= tol) { out.status = 0; break; }
-            if (k + 1 == maxit) { out.status = 1; break; }
-            MG_TRY(direction(CG_TAIL_BETA));
-        }
-    }
-    double nr = 0;
-    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // the true residual of the returned x
-    out.relres_true = std::sqrt(nr / nb);
-    if (n_hist) *n_hist = nh;
-    if (st) *st = out;
-    return MG_OK;
-}
-
-int Solver::pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
-{
-    if (nranks_ > 1) {
-        set_last_error("mg_pcg_solve: distributed handles are not supported (single-GPU handles only)");
-        return MG_ERR_BAD_ARG;
-    }
-    if (stage_fn_) {
-        set_last_error("mg_pcg_solve: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
-        return MG_ERR_BAD_ARG;
-    }
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    lock_iters_ = -1;
-    MG_TRY(krylov_alloc());
-    return d_.dtype == MG_F64 ? pcg_t<double>(tol, maxit, hist, hist_cap, n_hist, st)
-                              : pcg_t<float>(tol, maxit, hist, hist_cap, n_hist, st);
-}
-
-template <typename T>
-int Solver::pcg_kernel_t(int kernel, double scalar, const int *a, double *dots)
-{
-    const Level &L0 = lv_[0];
-    const Geom &g = L0.g;
-    *h_cg_ = CgScalars{};
-    h_cg_->alpha = h_cg_->beta = scalar;
-    MG_HIP(hipMemcpyAsync(d_cg_, h_cg_, sizeof(CgScalars), hipMemcpyHostToDevice, stream_));
-    int np = 0;
-    if (kernel == MG_PCG_K_UPDATE) {
-        np = launch_cg_update<T>(stream_, g, ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0), ptr<T>(a[3], 0), d_cg_, d_cg_part_);
-        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
-    } else if (kernel == MG_PCG_K_DOTS) {
-        np = launch_cg_dots<T>(stream_, g, ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0), d_cg_, d_cg_part_);
-        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
-        launch_reduce_final(stream_, d_cg_part_ + np, np, d_cg_dot_ + 1);
-    } else {
-        np = launch_cg_direction_apply<T>(stream_, g, coef_of<T>(L0), ptr<T>(a[0], 0), ptr<T>(a[1], 0), ptr<T>(a[2], 0),
-                                          ptr<T>(a[3], 0), d_cg_, d_cg_part_);
-        launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
-    }
-    MG_HIP(hipGetLastError());
-    double h[2] = {0.0, 0.0};
-    MG_HIP(hipMemcpyAsync(h_scal_ + 4, d_cg_dot_, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipStreamSynchronize(stream_));
-    h[0] = h_scal_[4];
-    if (kernel == MG_PCG_K_DOTS) h[1] = h_scal_[5];
-    dots[0] = h[0]; dots[1] = h[1];
-    return MG_OK;
-}
-
-int Solver::pcg_kernel(int kernel, double scalar, const int *arrs, double *dots)
-{
-    if (nranks_ > 1) { set_last_error("mg_pcg_kernel: single-GPU handles only"); return MG_ERR_BAD_ARG; }
-    if (kernel < MG_PCG_K_UPDATE || kernel > MG_PCG_K_DIRECTION) { set_last_error("mg_pcg_kernel: unknown kernel"); return MG_ERR_BAD_ARG; }
-    const int na = kernel == MG_PCG_K_DOTS ? 3 : 4;
-    for (int i = 0; i < na; i++) {
-        if (!check_arr(arrs[i], 0, "mg_pcg_kernel")) return MG_ERR_BAD_ARG;
-        for (int j = 0; j < i; j++)
-            if (arrs[i] == arrs[j]) { set_last_error("mg_pcg_kernel: the arrays must be distinct"); return MG_ERR_BAD_ARG; }
-    }
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    MG_TRY(krylov_scalars_alloc());
-    return d_.dtype == MG_F64 ? pcg_kernel_t<double>(kernel, scalar, arrs, dots)
-                              : pcg_kernel_t<float>(kernel, scalar, arrs, dots);
-}
-
-// ---------------------------------------------------------------- full multigrid (nested iteration), mg_fmg
-// f_{l+1} = R f_l down the hierarchy (the level operators are unscaled and the restrictions inject on the coarse boundary,
-// so this carries the right-hand side and the Dirichlet data), the coarsest-grid solve, then coarse to fine: U(l) = Pi U(l+1)
-// (mg_fmg.hip; Dirichlet nodes from RHS(l)) and cycles_per_level V-cycles started on level l. A cycle started on level l
-// only overwrites U and RHS of the levels below it, which the pass has finished with: no storage of its own.
-template <typename T>
-int Solver::fmg_t(int cycles_per_level, mg_fmg_stats *st)
-{
-    const int L = d_.levels;
-    for (int l = 0; l + 1 < L; l++) MG_TRY(restrict_t<T>(l, d_.restriction, MG_ARR_RHS, MG_ARR_RHS));
-    MG_TRY(zero_array(MG_ARR_U, L - 1));
-    launch_cg_boundary_copy<T>(stream_, lv_[L - 1].g, ptr<T>(MG_ARR_U, L - 1), ptr<T>(MG_ARR_RHS, L - 1));
-    MG_HIP(hipGetLastError());
-    MG_TRY(coarse_level_t<T>(L - 1, MG_ARR_U, MG_ARR_RHS, false));
-    MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));   // of this first, true coarse solve
-    for (int l = L - 2; l >= 0; l--) {
-        launch_fmg_prolong<T>(stream_, lv_[l + 1].g, lv_[l].g, ptr<T>(MG_ARR_U, l + 1), ptr<T>(MG_ARR_U, l), ptr<T>(MG_ARR_RHS, l));
-        MG_HIP(hipGetLastError());
-        for (int k = 0; k < cycles_per_level; k++) MG_TRY(vcycle_rec_t<T>(l));
-    }
-    double nb = 0, nr = 0;
-    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
-    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // synchronises: h_coarse_ is valid from here
-    if (st) {
-        st->levels = L;
-        st->cycles_per_level = cycles_per_level;
-        st->coarse_iters = h_coarse_->iters;
-        st->coarse_flag = h_coarse_->flag;
-        st->relres = std::sqrt(nr / nb);
-    }
-    return MG_OK;
-}
-
-int Solver::fmg(int cycles_per_level, mg_fmg_stats *st)
-{
-    if (nranks_ > 1) {
-        set_last_error("mg_fmg: distributed handles are not supported (single-GPU handles only)");
-        return MG_ERR_BAD_ARG;
-    }
-    if (stage_fn_) {
-        set_last_error("mg_fmg: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
-        return MG_ERR_BAD_ARG;
-    }
-    if (d_.cycle != MG_CYCLE_V) {
-        set_last_error("mg_fmg: the descriptor's cycle must be MG_CYCLE_V (the levels of a sawtooth cycle hold errors, not solutions)");
-        return MG_ERR_BAD_ARG;
-    }
-    if (cycles_per_level < 1) {
-        set_last_error("mg_fmg: cycles_per_level must be at least 1");
-        return MG_ERR_BAD_ARG;
-    }
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    lock_iters_ = -1;
-    fine_pre_done_ = 0;
-    return d_.dtype == MG_F64 ? fmg_t<double>(cycles_per_level, st) : fmg_t<float>(cycles_per_level, st);
-}
-
-int Solver::fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)
-{
-    if (nranks_ > 1) { set_last_error("mg_fmg_prolong: single-GPU handles only"); return MG_ERR_BAD_ARG; }
-    if (coarse_level < 1 || coarse_level >= d_.levels || !check_arr(arr_src, coarse_level, "mg_fmg_prolong") ||
-        !check_arr(arr_dst, coarse_level - 1, "mg_fmg_prolong") || (arr_bnd >= 0 && !check_arr(arr_bnd, coarse_level - 1, "mg_fmg_prolong"))) {
-        set_last_error("mg_fmg_prolong: bad level / array");
-        return MG_ERR_BAD_ARG;
-    }
-    if (arr_bnd == arr_dst) { set_last_error("mg_fmg_prolong: arr_bnd must differ from arr_dst"); return MG_ERR_BAD_ARG; }
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    const int fl = coarse_level - 1;
-    if (arr_dst == MG_ARR_RHS) lv_[fl].rhs_halo_ok = false;
-    if (d_.dtype == MG_F64)
-        launch_fmg_prolong<double>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<double>(arr_src, coarse_level), ptr<double>(arr_dst, fl),
-                                   arr_bnd >= 0 ? ptr<double>(arr_bnd, fl) : (double *)nullptr);
-    else
-        launch_fmg_prolong<float>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<float>(arr_src, coarse_level), ptr<float>(arr_dst, fl),
-                                  arr_bnd >= 0 ? ptr<float>(arr_bnd, fl) : (float *)nullptr);
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-// ---------------------------------------------------------------- mixed-precision defect correction (mg_mixed_solve)
-// u and b of level 0 in fp64 beside the handle's fp32 hierarchy: r = b - A u in fp64, A e = r solved approximately by
-// inner_cycles of the fp32 cycles, u += e. The fp32 right-hand side is the residual times a power of two that keeps it
-// near 1 (exact both ways); the kernels are in mg_mixed.hip.
-int Solver::mixed_check(const char *fn) const
-{
-    if (d_.dtype != MG_F32) {
-        set_last_error(std::string(fn) + ": the handle has to be created with MG_F32 (the cycles of the mixed-precision solver run in fp32; "
-                                         "this handle is MG_F64)");
-        return MG_ERR_BAD_ARG;
-    }
-    if (nranks_ > 1) {
-        set_last_error(std::string(fn) + ": distributed handles are not supported (single-GPU handles only)");
-        return MG_ERR_BAD_ARG;
-    }
-    return MG_OK;
-}
-
-int Solver::mixed_alloc()
-{
-    if (mx_[0]) return MG_OK;
-    const Level &L0 = lv_[0];
-    g64_ = L0.g;
-    g64_.pitch = ((L0.g.nx + 15) / 16) * 16;   // rows of doubles padded to 128 B
-    g64_.plane = (long long)g64_.ny * g64_.pitch;
-    mx_alloc_elems_ = (size_t)(g64_.nz + 2) * (size_t)g64_.plane;   // one (zero, unused) ghost plane either side, as every level
-    const size_t nbytes = mx_alloc_elems_ * sizeof(double), npart = (size_t)mixed_partials_capacity();
-    for (auto &b : mx_) {
-        MG_HIP(hipMalloc(&b, nbytes));
-        MG_HIP(hipMemsetAsync(b, 0, nbytes, stream_));   // ghost planes and padding columns stay zero from here on
-        bytes_ += nbytes;
-    }
-    MG_HIP(hipMalloc((void **)&d_mx_part_, sizeof(double) * npart));
-    MG_HIP(hipMalloc((void **)&d_mx_sum_, sizeof(double)));
-    bytes_ += sizeof(double) * (npart + 1);
-    return MG_OK;
-}
-
-int Solver::mixed_set(bool rhs, const double *host)
-{
-    const char *fn = rhs ? "mg_mixed_set_rhs" : "mg_mixed_set_solution";
-    MG_TRY(mixed_check(fn));
-    MG_HIP(hipSetDevice(device_));
-    MG_TRY(mixed_alloc());
-    MG_TRY(stage_copy(reinterpret_cast<char *>(mxptr(rhs ? MXB : MXU)), g64_, sizeof(double), const_cast<double *>(host), true));
-    (rhs ? mx_has_b_ : mx_has_u_) = true;
-    return MG_OK;
-}
-
-int Solver::mixed_get_solution(double *host)
-{
-    MG_TRY(mixed_check("mg_mixed_get_solution"));
-    if (!mx_has_u_) { set_last_error("mg_mixed_get_solution: no solution yet (call mg_mixed_set_solution first)"); return MG_ERR_BAD_ARG; }
-    return stage_copy(reinterpret_cast<char *>(mxptr(MXU)), g64_, sizeof(double), host, false);
-}
-
-// 2^-e with frexp(sqrt(v)) = (m, e): brings a vector of squared norm v to a norm in [0.5, 1)
-static double mixed_scale(double v)
-{
-    if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
-    int e = 0;
-    (void)std::frexp(std::sqrt(v), &e);
-    return std::ldexp(1.0, -e);
-}
-
-int Solver::mixed_inner(int inner_cycles)
-{
-    MG_HIP(hipMemsetAsync(lv_[0].base[MG_ARR_U], 0, lv_[0].alloc_elems * esize(), stream_));
-    for (int c = 0; c < inner_cycles; c++) {
-        if (d_.outer_pre_gs > 0) MG_TRY(smooth_t<float>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS));   // `u * GS * GS`
-        MG_TRY(cycle_enqueue_t<float>());                                                                            // `* MGx`
-    }
-    return MG_OK;
-}
-
-int Solver::mixed_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st)
-{
-    MG_TRY(mixed_check("mg_mixed_solve"));
-    if (stage_fn_) {
-        set_last_error("mg_mixed_solve: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
-        return MG_ERR_BAD_ARG;
-    }
-    if (inner_cycles < 1) { set_last_error("mg_mixed_solve: inner_cycles must be at least 1"); return MG_ERR_BAD_ARG; }
-    if (maxit < 0) { set_last_error("mg_mixed_solve: negative maxit"); return MG_ERR_BAD_ARG; }
-    if (!mx_has_b_ || !mx_has_u_) {
-        set_last_error("mg_mixed_solve: call mg_mixed_set_rhs and mg_mixed_set_solution first");
-        return MG_ERR_BAD_ARG;
-    }
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    lock_iters_ = -1;
-    fine_pre_done_ = 0;
-    Level &L0 = lv_[0];
-    const Geom &g32 = L0.g;
-    const double *const b = mxptr(MXB);
-    mg_mixed_stats out{0, 0, 0, 0, 0.0};
-    int nh = 0;
-    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
-    auto fetch_sum = [&](double *v) -> int {   // the sum the last launch left in d_mx_sum_; synchronises
-        MG_HIP(hipGetLastError());
-        MG_HIP(hipMemcpyAsync(h_scal_ + 6, d_mx_sum_, sizeof(double), hipMemcpyDeviceToHost, stream_));
-        MG_HIP(hipStreamSynchronize(stream_));
-        *v = h_scal_[6];
-        return MG_OK;
-    };
-
-    // u = b on the Dirichlet nodes; b.b over all nodes, as mg_solve
-    launch_cg_boundary_copy<double>(stream_, g64_, mxptr(MXU), b);
-    int np = launch_mixed_sumsq(stream_, g64_, b, d_mx_part_);
-    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
-    double bb = 0, rr = 0;
-    MG_TRY(fetch_sum(&bb));
-    double s = mixed_scale(bb);   // the scale RHS32(0) currently carries
-    L0.rhs_halo_ok = false;
-    np = launch_mixed_residual(stream_, g64_, g32, L0.coef, mxptr(MXU), b, ptr<float>(MG_ARR_RHS, 0), s, d_mx_part_);
-    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
-    MG_TRY(fetch_sum(&rr));
-    auto relres = [&](double v) { return v == 0.0 ? 0.0 : std::sqrt(v / bb); };
-    record(relres(rr));
-    if (!std::isfinite(rr) || !std::isfinite(out.relres)) {
-        out.status = 2;
-    } else if (rr == 0.0) {
-        out.status = 0;   // nothing to do: u solves the system (b == 0 with u == 0 inside included)
-    } else {
-        for (int k = 0;; k++) {
-            if (k > 0 && out.relres <= tol) { out.status = 0; break; }
-            if (k == maxit) { out.status = 1; break; }
-            MG_TRY(mixed_inner(inner_cycles));
-            out.cycles += inner_cycles;
-            const double s_next = mixed_scale(rr);   // from the PREVIOUS residual: known before the launch
-            np = launch_mixed_correct_residual(stream_, g64_, g32, L0.coef, mxptr(MXU), ptr<float>(MG_ARR_U, 0), b, mxptr(MXU2),
-                                               ptr<float>(MG_ARR_RHS, 0), s, s_next, d_mx_part_);
-            launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
-            double rr_new = 0;
-            MG_TRY(fetch_sum(&rr_new));   // the one host synchronisation per correction: the stopping test
-            record(relres(rr_new));
-            if (!std::isfinite(rr_new) || !std::isfinite(out.relres)) { out.status = 2; break; }   // not taken: u64 stays the last iterate
-            std::swap(mx_[MXU], mx_[MXU2]);
-            out.outer = k + 1;
-            rr = rr_new;
-            s = s_next;
-        }
-    }
-    if (n_hist) *n_hist = nh;
-    if (st) *st = out;
-    return MG_OK;
-}
-
-int Solver::mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r)
-{
-    MG_TRY(mixed_check("mg_mixed_kernel"));
-    if (kernel != MG_MIXED_K_RESIDUAL && kernel != MG_MIXED_K_CORRECT_RESIDUAL) { set_last_error("mg_mixed_kernel: unknown kernel"); return MG_ERR_BAD_ARG; }
-    const bool corr = kernel == MG_MIXED_K_CORRECT_RESIDUAL;
-    if (!check_arr(arr_r32, 0, "mg_mixed_kernel") || (corr && !check_arr(arr_e32, 0, "mg_mixed_kernel"))) return MG_ERR_BAD_ARG;
-    if (corr && arr_e32 == arr_r32) { set_last_error("mg_mixed_kernel: the arrays must be distinct"); return MG_ERR_BAD_ARG; }
-    if (corr && !(scale_in != 0.0 && std::isfinite(scale_in))) { set_last_error("mg_mixed_kernel: scale_in must be finite and not zero"); return MG_ERR_BAD_ARG; }
-    if (!mx_has_b_ || !mx_has_u_) {
-        set_last_error("mg_mixed_kernel: call mg_mixed_set_rhs and mg_mixed_set_solution first");
-        return MG_ERR_BAD_ARG;
-    }
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    Level &L0 = lv_[0];
-    if (arr_r32 == MG_ARR_RHS) L0.rhs_halo_ok = false;
-    int np = 0;
-    if (corr)
-        np = launch_mixed_correct_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), ptr<float>(arr_e32, 0), mxptr(MXB), mxptr(MXU2),
-                                           ptr<float>(arr_r32, 0), scale_in, scale_out, d_mx_part_);
-    else
-        np = launch_mixed_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), mxptr(MXB), ptr<float>(arr_r32, 0), scale_out, d_mx_part_);
-    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
-    MG_HIP(hipGetLastError());
-    MG_HIP(hipMemcpyAsync(h_scal_ + 6, d_mx_sum_, sizeof(double), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipStreamSynchronize(stream_));
-    if (corr) std::swap(mx_[MXU], mx_[MXU2]);
-    if (sumsq_r) *sumsq_r = h_scal_[6];
-    return MG_OK;
-}
-
-// ---------------------------------------------------------------- diagonal shift (mg_set_shift)
-// Every launch rebuilds its Coef from Level::coef (coef_of; mixed_solve hands L0.coef to its fp64 kernels), so the shifted
-// operator needs nothing but the new diagonal -- and new line factors where the smoother is a zebra one, the only data
-// derived from cd when the handle is created.
-int Solver::set_shift(double sigma)
-{
-    if (!(sigma >= 0.0) || !std::isfinite(sigma)) { set_last_error("mg_set_shift: sigma must be finite and not negative"); return MG_ERR_BAD_ARG; }
-    if (nranks_ > 1) {
-        set_last_error("mg_set_shift: distributed handles are not supported (single-GPU handles only)");
-        return MG_ERR_BAD_ARG;
-    }
-    if (sigma == shift_) return MG_OK;
-    MG_HIP(hipSetDevice(device_));
-    const bool zebra = is_zebra(d_.smoother);
-    if (zebra) MG_HIP(hipStreamSynchronize(stream_));   // no queued sweep may read a half-written table
-    for (auto &L : lv_) {
-        L.coef[3] = L.cd0 + sigma;
-        if (zebra && L.zebra) MG_TRY(zebra_tabulate(L));
-    }
-    shift_ = sigma;
-    return MG_OK;
-}
-
-// ---------------------------------------------------------------- implicit heat-equation stepper (mg_heat_*)
-// u_t = -A0 u + f by the theta scheme: per step one launch of mg_heat.hip builds the right-hand side from U (+ f) into
-// RHS, then cycles_per_step outer iterations of mg_solve on (1/(theta dt) I + A0) u' = rhs, warm-started from u.
-int Solver::heat_check(const char *fn, double dt, double theta) const
-{
-    if (nranks_ > 1) {
-        set_last_error(std::string(fn) + ": distributed handles are not supported (single-GPU handles only)");
-        return MG_ERR_BAD_ARG;
-    }
-    if (!(dt > 0.0) || !std::isfinite(dt)) { set_last_error(std::string(fn) + ": dt must be positive and finite"); return MG_ERR_BAD_ARG; }
-    if (!(theta > 0.0 && theta <= 1.0)) { set_last_error(std::string(fn) + ": theta must be in (0, 1]"); return MG_ERR_BAD_ARG; }
-    if (!std::isfinite(1.0 / (theta * dt)) || !std::isfinite(1.0 / dt)) {
-        set_last_error(std::string(fn) + ": dt is too small: 1 / (theta dt) is not finite");
-        return MG_ERR_BAD_ARG;
-    }
-    return MG_OK;
-}
-
-int Solver::heat_set_source(const void *host)
-{
-    if (nranks_ > 1) {
-        set_last_error("mg_heat_set_source: distributed handles are not supported (single-GPU handles only)");
-        return MG_ERR_BAD_ARG;
-    }
-    if (!host) { heat_has_f_ = false; return MG_OK; }
-    MG_HIP(hipSetDevice(device_));
-    const Level &L0 = lv_[0];
-    if (!heat_f_) {
-        const size_t nbytes = L0.alloc_elems * esize();
-        MG_HIP(hipMalloc(&heat_f_, nbytes));
-        MG_HIP(hipMemsetAsync(heat_f_, 0, nbytes, stream_));   // ghost planes and padding columns stay zero from here on
-        bytes_ += nbytes;
-    }
-    MG_TRY(stage_copy(static_cast<char *>(heat_f_) + (size_t)L0.gh * (size_t)L0.g.plane * esize(), L0.g, esize(), const_cast<void *>(host), true));
-    heat_has_f_ = true;
-    return MG_OK;
-}
-
-template <typename T>
-int Solver::heat_rhs_t(double dt, double theta, int arr_u, int arr_dst)
-{
-    Level &L0 = lv_[0];
-    const double coef0[4] = {L0.coef[0], L0.coef[1], L0.coef[2], L0.cd0};
-    const T *f = heat_has_f_ ? reinterpret_cast<const T *>(heat_f_) + L0.gh * L0.g.plane : (const T *)nullptr;
-    if (arr_dst == MG_ARR_RHS) L0.rhs_halo_ok = false;
-    launch_heat_rhs<T>(stream_, L0.g, coef0, dt, theta, ptr<T>(arr_u, 0), f, ptr<T>(arr_dst, 0));
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::heat_rhs(double dt, double theta, int arr_u, int arr_dst)
-{
-    MG_TRY(heat_check("mg_heat_rhs", dt, theta));
-    if (!check_arr(arr_u, 0, "mg_heat_rhs") || !check_arr(arr_dst, 0, "mg_heat_rhs")) return MG_ERR_BAD_ARG;
-    if (arr_u == arr_dst) { set_last_error("mg_heat_rhs: arr_dst must differ from arr_u"); return MG_ERR_BAD_ARG; }
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    return d_.dtype == MG_F64 ? heat_rhs_t<double>(dt, theta, arr_u, arr_dst) : heat_rhs_t<float>(dt, theta, arr_u, arr_dst);
-}
-
-template <typename T>
-int Solver::heat_step_t(double dt, double theta, int nsteps, int cycles_per_step)
-{
-    for (int n = 0; n < nsteps; n++) {
-        MG_TRY(heat_rhs_t<T>(dt, theta, MG_ARR_U, MG_ARR_RHS));
-        for (int c = 0; c < cycles_per_step; c++) {
-            if (d_.outer_pre_gs > 0) MG_TRY(smooth_t<T>(0, MG_SMOOTH_GS_LEX, d_.outer_pre_gs, MG_ARR_U, MG_ARR_RHS));   // `u * GS * GS`
-            MG_TRY(cycle_enqueue_t<T>());                                                                            // `* MGx`
-        }
-    }
-    MG_TRY(residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
-    return sumsq_t<T>(0, MG_ARR_RHS);
-}
-
-int Solver::heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
-{
-    MG_TRY(heat_check("mg_heat_step", dt, theta));
-    if (stage_fn_) {
-        set_last_error("mg_heat_step: a stage callback is installed (remove it with mg_set_stage_callback(h, NULL, NULL))");
-        return MG_ERR_BAD_ARG;
-    }
-    if (nsteps < 1) { set_last_error("mg_heat_step: nsteps must be at least 1"); return MG_ERR_BAD_ARG; }
-    if (cycles_per_step < 1) { set_last_error("mg_heat_step: cycles_per_step must be at least 1"); return MG_ERR_BAD_ARG; }
-    MG_TRY(set_shift(1.0 / (theta * dt)));
-    MG_HIP(hipSetDevice(device_));
-    pair_on_comm_level_ = -1;
-    lock_iters_ = -1;
-    fine_pre_done_ = 0;
-    MG_TRY(d_.dtype == MG_F64 ? heat_step_t<double>(dt, theta, nsteps, cycles_per_step) : heat_step_t<float>(dt, theta, nsteps, cycles_per_step));
-    // the one host synchronisation of the call: ||rhs - (sigma I + A0) u|| / ||rhs|| of the last step
-    MG_HIP(hipMemcpyAsync(h_scal_, d_scal_, 2 * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    MG_HIP(hipStreamSynchronize(stream_));
-    if (st) {
-        st->steps = nsteps;
-        st->cycles = nsteps * cycles_per_step;
-        st->time = (double)nsteps * dt;
-        st->relres = h_scal_[0] == 0.0 ? 0.0 : std::sqrt(h_scal_[0] / h_scal_[1]);
-    }
-    return MG_OK;
-}
+// The member templates that mg_drivers.cpp calls (mg_solver.h says why they are listed here)
+#define MG_INSTANTIATE_FOR_DRIVERS(T)                                                       \
+    template int Solver::smooth_t<T>(int, int, int, int, int, bool, int, bool, bool);       \
+    template bool Solver::pair_norm_ok<T>() const;                                          \
+    template int Solver::residual_t<T>(int, int, int, int, bool);                           \
+    template int Solver::sumsq_t<T>(int, int);                                              \
+    template int Solver::restrict_t<T>(int, int, int, int);                                 \
+    template int Solver::coarse_level_t<T>(int, int, int, bool);                            \
+    template int Solver::vcycle_rec_t<T>(int, bool);
+MG_INSTANTIATE_FOR_DRIVERS(double)
+MG_INSTANTIATE_FOR_DRIVERS(float)
+#undef MG_INSTANTIATE_FOR_DRIVERS
 
 }  // namespace mg

@@ -1,5 +1,10 @@
-// mg_solver.h -- host-side owner of the HBM-resident grid hierarchy and the
-// stream-ordered cycle drivers behind the C-ABI of include/mg_hip.h.
+// mg_solver.h -- host-side owner of the HBM-resident grid hierarchy behind the C-ABI of include/mg_hip.h. One class, two
+// translation units: mg_solver.cpp holds the hierarchy, the communication, the per-operator launch paths and the cycle
+// (vcycle_rec_t, cycle_enqueue*, cycle); mg_drivers.cpp holds what calls the cycle from above (solve, pcg_*, fmg*, mixed_*,
+// set_shift, heat_*) and the helpers those drivers share.
+// The member templates that mg_drivers.cpp calls and mg_solver.cpp defines (smooth_t, pair_norm_ok, residual_t, sumsq_t,
+// restrict_t, coarse_level_t, vcycle_rec_t) cross the file boundary by ONE mechanism: explicit instantiation definitions
+// for double and float, in one block at the end of mg_solver.cpp.
 #ifndef MG_SOLVER_H
 #define MG_SOLVER_H
 
@@ -12,6 +17,17 @@
 #include "mg_comm.h"
 #include "mg_geom.h"
 #include "mg_kernels.h"
+
+// early returns of the mg_status functions of both translation units
+#define MG_HIP(call)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            mg::set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));           \
+            return MG_ERR_HIP;                                                               \
+        }                                                                                    \
+    } while (0)
+#define MG_TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 namespace mg {
 
@@ -34,6 +50,8 @@ int plan_slab(const mg_desc &d, int nranks, int rank, int level, SlabPlan *out, 
 int plan_stage(const mg_desc &d, int nranks, int rank, SlabPlan *out, std::string *why);
 
 constexpr int NUM_ARR = 5;
+
+inline bool is_zebra(int smoother) { return smoother == MG_SMOOTH_ZEBRA_Y || smoother == MG_SMOOTH_ZEBRA_X; }
 
 struct Level {
     Geom g{};
@@ -120,7 +138,17 @@ public:
     const Level &level(int l) const { return lv_[l]; }
 
 private:
-    template <typename T> T *ptr(int which, int level) const;  // local plane 0
+    template <typename T> T *ptr(int which, int level) const   // local plane 0: skips the lower ghost plane(s)
+    {
+        const Level &L = lv_[level];
+        return reinterpret_cast<T *>(L.base[which]) + L.gh * L.g.plane;
+    }
+    template <typename T> static Coef<T> coef_of(const Level &L)
+    {
+        Coef<T> c = make_coef<T>(L.coef[0], L.coef[1], L.coef[2], L.coef[3]);
+        if (!switches().fast_div) c.win = 0;  // A/B switch: hardware division everywhere
+        return c;
+    }
     // x_zero: the caller knows x == 0 (fresh coarse-level guess): the first Jacobi sweep of a
     // fast-path level then skips reading x (and the caller skips the memset)
     template <typename T> int smooth_t(int level, int smoother, int sweeps, int ax, int ar, bool x_zero = false,
@@ -165,11 +193,27 @@ private:
     template <typename T> int coarse_t(int level, int ax, int ar, bool x_zero = false);
     template <typename T> int coarse_ex_t(int level, int ax, int ar, int smoother, int maxit, double tol, int fixed, bool x_zero = false);
     template <typename T> int cycle_enqueue_t();
+    // ---- shared by the drivers (mg_drivers.cpp)
+    // One outer iteration of mg_solve on (U, RHS) of level 0: outer_pre_gs lexicographic Gauss-Seidel sweeps if asked, then
+    // one cycle. Stream-ordered, no synchronisation.
+    int outer_iteration_enqueue();
+    // Refuses what `refuse` names, then makes the handle's device current and clears the per-call driver state
+    // (pair_on_comm_level_, lock_iters_, fine_pre_done_). Messages start with "<fn>: ".
+    enum : unsigned { REFUSE_DIST = 1u, REFUSE_STAGE_CB = 2u };   // a distributed handle / an installed stage callback
+    int driver_begin(const char *fn, unsigned refuse);
+    // h_scal_[slot .. slot + n) = dev[0 .. n), then waits for the stream
+    int fetch_scalars(int slot, const double *dev, int n = 1);
+    // h_coarse_ = *d_coarse_ (with_fine: and the cycle's fine sum r^2), one wait for the stream, then *st (may be null)
+    int fetch_cycle_stats(mg_cycle_stats *st, bool with_fine = false);
+    void fill_cycle_stats(mg_cycle_stats *st, double fine_sumsq_r) const;   // from h_coarse_ as it stands
+    // *p = nbytes of zeroed device memory (the memset is queued on stream_), counted in bytes_. Level-shaped arrays made
+    // this way keep their ghost planes and padding columns zero: nothing writes them afterwards.
+    int alloc_zeroed(void **p, size_t nbytes);
     template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
-    template <typename T> int precondition_t();   // z = M r: one mg_solve outer iteration from zero on (z, r)
+    int precondition();   // z = M r: one mg_solve outer iteration from zero on (z, r)
     template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
-    int mixed_check(const char *fn) const;      // MG_F32, single-GPU handle
+    int mixed_check(const char *fn, unsigned refuse = REFUSE_DIST);      // MG_F32, then driver_begin(fn, refuse)
     int mixed_alloc();
     int mixed_inner(int inner_cycles);         // U32(0) = 0, then inner_cycles outer iterations of mg_solve on RHS32(0); no sync
     int stage_copy(char *dev, const Geom &g, size_t es, void *host, bool to_device);   // stage_rows on any level-shaped array
@@ -188,9 +232,20 @@ private:
     hipEvent_t ev_stage_[2] = {nullptr, nullptr};   // one per half of the host staging buffer (stage_rows)
     std::vector<Level> lv_;
     double *d_partials_ = nullptr;  // per-block partial sums
-    double *d_scal_ = nullptr;      // [0] sum r^2, [1] sum b^2, [2] cycle's fine sum r^2
+    // Slots of the pinned h_scal_. d_scal_ has the same slots; only the first three are written on the device (the Krylov and
+    // mixed-precision sums have device buffers of their own). A new driver adds a slot here, it does not borrow one.
+    enum ScalSlot {
+        SC_RR = 0,        // sum r^2: residual_t, the norm carried by a pre-smoothing pair (smooth_t hands d_scal_ itself to it)
+        SC_BB = 1,        // sum of squares of an array: sumsq_t (follows SC_RR: heat_step fetches the two in one copy)
+        SC_CYCLE_RR = 2,  // the sawtooth cycle's fine sum r^2 (a copy of SC_RR taken inside the cycle)
+        SC_CG_DOT = 3,    // the two sums of pcg_kernel's check (fetched in one copy)
+        SC_CG_DOT1 = 4,
+        SC_MX_SUM = 5,    // d_mx_sum_: mixed_solve, mixed_kernel
+        SC_COUNT = 8      // the six slots, padded to one 64-byte line
+    };
+    double *d_scal_ = nullptr;      // [SC_COUNT]
     CoarseOut *d_coarse_ = nullptr;
-    double *h_scal_ = nullptr;      // pinned mirrors
+    double *h_scal_ = nullptr;      // pinned mirrors ([SC_COUNT])
     CoarseOut *h_coarse_ = nullptr;
     CoarseOut *h_fixed_ = nullptr;  // pinned: stats reported when the coarse level is swept, not solved
     size_t bytes_ = 0;
@@ -231,7 +286,7 @@ private:
     // diagonal shift of every level (set_shift) and the stepper's source term f: one more level-0 array (allocated on first
     // use, kept until the handle goes); heat_has_f_ == false: f = 0, the array is not read
     double shift_ = 0;
-    int heat_check(const char *fn, double dt, double theta) const;   // single-GPU handle, dt > 0, theta in (0, 1], finite shift
+    int heat_check(const char *fn, double dt, double theta);   // driver_begin(fn, REFUSE_DIST), then dt > 0, theta in (0, 1], finite shift
     template <typename T> int heat_rhs_t(double dt, double theta, int arr_u, int arr_dst);
     template <typename T> int heat_step_t(double dt, double theta, int nsteps, int cycles_per_step);
     void *heat_f_ = nullptr;

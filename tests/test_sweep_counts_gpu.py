@@ -1,6 +1,6 @@
 """V(nu_pre, nu_post) cycles other than V(2,2) through the GPU cycle drivers, against the CPU oracle bit for bit.
 
-The driver (mg_solver.cpp: smooth_t, vcycle_rec_t, can_fold_prolong, can_skip_zeroing, pair_norm_ok, Solver::solve) branches
+The driver (mg_solver.cpp: smooth_t, vcycle_rec_t, can_fold_prolong, can_skip_zeroing, pair_norm_ok; mg_drivers.cpp: Solver::solve) branches
 on the two sweep counts more than on anything else: pairs and odd singles, the prolongation folded into the first
 post-smoothing launch or applied on its own, the zero guess as a flag or as a memset, the small-level kernels that exist for
 V(2,2) only, the residual norm riding on the first pre-smoothing launch of mg_solve. tests/test_independent_reference.py
