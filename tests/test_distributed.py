@@ -106,7 +106,10 @@ def _oracle(desc, b, cycles):
     (3, 65, 4, 1, 2, 1, (2, 2)),    # fp32, three ranks
     (2, 65, 3, 1, 2, 0, (1, 2)),    # sweep counts off (2,2): the model and the oracle agree before anything runs on a GPU
     (3, 65, 4, 1, 2, 0, (3, 1)),
-], ids=["2-65-3-1-2-0", "2-65-4-0-2-0", "3-129-3-1-3-0", "2-65-3-1-2-1", "3-65-4-1-2-1", "2-65-3-1-2-0-v12", "3-65-4-1-2-0-v31"])
+    (2, 161, 4, 1, 3, 0, (2, 2)),   # off 2^k + 1: 161, 81, 41 on slabs of uneven heights, 21^3 gathered
+    (3, 193, 4, 1, 3, 1, (2, 2)),   # 193, 97, 49 on three slabs, fp32
+], ids=["2-65-3-1-2-0", "2-65-4-0-2-0", "3-129-3-1-3-0", "2-65-3-1-2-1", "3-65-4-1-2-1", "2-65-3-1-2-0-v12", "3-65-4-1-2-0-v31",
+        "2-161-4-1-3-0", "3-193-4-1-3-1"])
 def test_slab_decomposition_model_gloo(world, n, levels, restriction, expect_fg, dtype, nu, tmp_path):
     case, desc, b = _case(tmp_path, n, levels, restriction, dtype=dtype, nu=nu)
     u, hists, fg = _run_ranks("model", world, case, tmp_path)
@@ -121,7 +124,10 @@ def test_slab_decomposition_model_gloo(world, n, levels, restriction, expect_fg,
 @pytest.mark.parametrize("world,n,levels,restriction,dtype", [
     (2, 65, 3, 1, 0), (2, 65, 4, 0, 0), (3, 129, 3, 1, 0), (2, 129, 4, 1, 0), (2, 257, 4, 1, 0),
     # fp32 = BASELINE config 4's precision: narrow levels, the fused pair on slabs (n >= 129: 32-float4 rows), 2 and 3 ranks
-    (2, 65, 3, 1, 1), (3, 129, 3, 1, 1), (2, 257, 4, 1, 1), (3, 257, 5, 1, 1)])
+    (2, 65, 3, 1, 1), (3, 129, 3, 1, 1), (2, 257, 4, 1, 1), (3, 257, 5, 1, 1),
+    # grids off 2^k + 1 (tests/size_table.py): 161, 81, 41 and 193, 97, 49 on slabs of uneven heights, rows that are no fused-pair
+    # width (exchanged single sweeps, then the fused residual + restriction on the slab: 64 + 16 lanes, 48 and 24 in fp32)
+    (2, 161, 4, 1, 0), (3, 193, 4, 1, 1)])
 def test_hip_distributed_solver_two_processes_one_gpu(world, n, levels, restriction, dtype, tmp_path):
     from multigrid_prj_amd import capi
     case, desc, b = _case(tmp_path, n, levels, restriction, dtype=dtype)

@@ -180,6 +180,10 @@ FMG_ROWS = [
          levels=3, dtype=capi.MG_F64, smoother=capi.SMOOTH_JACOBI, omega=6 / 7, nu_pre=1, nu_post=2),
     dict(id="3d-f64-65-rbgs-v11", gate="V(1,1) red-black: colour kernels, one sweep either side", dim=3, n=65, levels=3,
          dtype=capi.MG_F64, smoother=capi.SMOOTH_RBGS, omega=1.0, nu_pre=1, nu_post=1),
+    # a grid off 2^k + 1 (97, 49, 25, 13: tests/size_table.py): the one-sided stencils of the cubic interpolation next to the
+    # boundary sit in partial waves (48 and 24 lanes)
+    dict(id="3d-f64-97-jacobi", gate="fmg_prolong_fast_ok 49 -> 97 and 25 -> 49 with rows that are no whole wave", dim=3, n=97,
+         levels=4, dtype=capi.MG_F64, smoother=capi.SMOOTH_JACOBI, omega=6 / 7),
 ]
 
 

@@ -137,7 +137,8 @@ class ShiftedOracle:
         return self.vcycle(u, b) if self.d.cycle == po.CYCLE_V else self.sawtooth(u, b)
 
 
-GRIDS = {"2d65": dict(dim=2, n=65, levels=4, length=10.0, alpha=1.0), "3d33": dict(dim=3, n=33, levels=3, length=1.0, alpha=2.5)}
+GRIDS = {"2d65": dict(dim=2, n=65, levels=4, length=10.0, alpha=1.0), "3d33": dict(dim=3, n=33, levels=3, length=1.0, alpha=2.5),
+         "3d49": dict(dim=3, n=49, levels=3, length=1.0, alpha=2.5)}   # 49, 25, 13: off 2^k + 1 (tests/size_table.py)
 OPCFG = {
     "jacobi-omega1": dict(smoother=capi.SMOOTH_JACOBI, omega=1.0),
     "jacobi-omega0.8": dict(smoother=capi.SMOOTH_JACOBI, omega=0.8),
@@ -361,7 +362,8 @@ def test_fmg_on_the_shifted_operator():
 
 
 # ---------------------------------------------------------------- the stepper
-STEP_GRIDS = {"2d65": dict(dim=2, n=65, levels=4, length=1.0, alpha=1.0), "3d33": dict(dim=3, n=33, levels=3, length=1.0, alpha=1.0)}
+STEP_GRIDS = {"2d65": dict(dim=2, n=65, levels=4, length=1.0, alpha=1.0), "3d33": dict(dim=3, n=33, levels=3, length=1.0, alpha=1.0),
+              "3d49": dict(dim=3, n=49, levels=3, length=1.0, alpha=1.0)}
 STEP_CYCLES = {"v22": dict(V22, omega=0.8), "sawtooth": dict(cycle=capi.CYCLE_SAWTOOTH, smoother=capi.SMOOTH_JACOBI, omega=0.8,
                                                              nu_pre=0, nu_post=3, restriction=capi.RESTRICT_INJECT, outer_pre_gs=2)}
 
@@ -417,10 +419,12 @@ def test_step_against_an_independent_stepper(grid, theta, dtype):
     check_max(got, u, steps * cycle_bound(ref.Ps, eps_of(dtype), FIXED["coarse_maxit"], scale), f"{grid} theta {theta}")
 
 
-# c of the rounding term c * eps * 8 * ||u0||: 8 x the largest error / (eps * 8 * ||u0||) observed over the four cases below on
+# c of the rounding term c * eps * 8 * ||u0||: 8 x the largest error / (eps * 8 * ||u0||) observed over the first four cases below on
 # MI355X. The algebraic term is an upper bound that exceeded the whole error in every case (error - algebraic < 0), so the
 # WHOLE observed error is charged to rounding here, the conservative reading: 8 x 15.6 -> 125.
-PHYSICS_OBSERVED = {"2d65 theta 1": 15.65, "2d65 theta 0.5": 2.28, "3d33 theta 1": 3.65, "3d33 theta 0.5": 0.51}
+# (3d49, added with the grids off 2^k + 1, was measured after the constant was set: 5.48 and 2.83, below the largest)
+PHYSICS_OBSERVED = {"2d65 theta 1": 15.65, "2d65 theta 0.5": 2.28, "3d33 theta 1": 3.65, "3d33 theta 0.5": 0.51,
+                    "3d49 theta 1": 5.48, "3d49 theta 0.5": 2.83}
 PHYSICS_C = 125.0
 PHYSICS_CYCLES = 16
 

@@ -109,7 +109,14 @@ def _op_cases():
     return out
 
 
-OP_CASES = _op_cases()
+# the generated grid, and shapes of the n = m * 2^j + 1 family that the GPU cycle table runs (tests/size_table.py): the
+# oracle is the judge there, so it is pinned here on the same hierarchies (37, 19, 10; 45, 23, 12; 133, 67, 34)
+GRID_CASES = _op_cases()
+ODD_OP_CASES = [dict(dim=3, n=n, levels=3, dtype=dtype, semi_xy=0, aniso=aniso, omega=omega, alpha=1.0, length=1.0)
+                for n, dtype, aniso, omega in [(37, po.MG_F64, ANISO[0], OMEGA[1]), (37, po.MG_F32, ANISO[0], OMEGA[1]),
+                                               (45, po.MG_F64, ANISO[0], OMEGA[1]), (45, po.MG_F32, ANISO[3], OMEGA[2]),
+                                               (133, po.MG_F32, ANISO[0], OMEGA[1])]]
+OP_CASES = GRID_CASES + ODD_OP_CASES
 
 
 def _id(c):
@@ -181,7 +188,7 @@ NU = [(2, 2), (1, 2), (2, 1), (0, 3), (3, 0)]
 
 def _cycle_cases():
     out, q = [], 0
-    for c in OP_CASES:
+    for c in GRID_CASES:
         if c["levels"] < 2 or (c["dim"] == 3 and c["n"] > 65):
             continue
         for cyc in (po.CYCLE_V, po.CYCLE_SAWTOOTH):
@@ -196,7 +203,14 @@ def _cycle_cases():
     return out
 
 
-CYCLE_CASES = _cycle_cases()
+# V(2,2) with full weighting on hierarchies of tests/size_table.py, as tests/test_odd_sizes_gpu.py runs them on the GPU
+ODD_CYCLE_CASES = [dict(dim=3, n=n, levels=levels, dtype=dtype, semi_xy=semi, aniso=aniso, omega=6 / 7 if sm == po.SMOOTH_JACOBI
+                        else 1.0, alpha=1.0, length=1.0, cycle=po.CYCLE_V, smoother=sm, nu_pre=2, nu_post=2,
+                        restriction=po.RESTRICT_FULLW, coarse_mode=po.COARSE_FIXED, coarse_maxit=8, outer_pre_gs=0, ncycles=2)
+                   for n, levels, dtype, semi, aniso, sm in [
+                       (37, 3, po.MG_F64, 0, ANISO[0], po.SMOOTH_JACOBI), (45, 3, po.MG_F32, 0, ANISO[0], po.SMOOTH_RBGS),
+                       (97, 5, po.MG_F64, 0, ANISO[0], po.SMOOTH_JACOBI), (97, 4, po.MG_F32, 1, (1.0, 1.0, 0.25), po.SMOOTH_JACOBI)]]
+CYCLE_CASES = _cycle_cases() + ODD_CYCLE_CASES
 
 
 def _cid(c):
@@ -382,36 +396,9 @@ def test_the_exact_solution_is_a_fixed_point_of_a_cycle(case):
 # ======================================================================= the HIP operators (GPU)
 # Python statements of the dispatch gates (multigrid_prj_amd/csrc): which kernel a shape takes, so that every row below
 # names the side it exercises and the launch counts of mg_profile_get can confirm it.
-def _V(dtype):
-    return 2 if dtype == po.MG_F64 else 4
-
-
-def fast_path_ok(n, dtype):          # mg_jacobi_fast.hip: rows of >= 33, at most one column left over
-    return n >= 33 and n % _V(dtype) <= 1
-
-
-def jacobi2_ok(n, dtype):            # mg_jacobi_fast.hip: rows of exactly 64 ... 512 vectors + the odd column
-    return (n - 1) % _V(dtype) == 0 and (n - 1) // _V(dtype) in (64, 128, 192, 256, 384, 512)
-
-
-def pair_wide_ok(n, nz, dtype):      # mg_pair_wide.hip: rows of 128 / 256 lanes, ny >= 200, nz >= 8
-    return (n - 1) % _V(dtype) == 0 and (n - 1) // _V(dtype) in (128, 256) and n >= 200 and nz >= 8
-
-
-def rr_wide_ok(n, nzc, dtype):       # mg_rr_wide.hip: the same rows, coarse nz >= 4
-    return (n - 1) % _V(dtype) == 0 and (n - 1) // _V(dtype) in (128, 256) and n >= 200 and nzc >= 4
-
-
-def prolong_fast_ok(nc, nf, dtype):  # mg_transfer_fast.hip
-    return nc >= 17 and nf % _V(dtype) == 1
-
-
-def resid_restrict_fast_ok(nf, nc, dtype):  # mg_transfer_fast.hip: + at most 8 column blocks of the coarse row
-    return nc >= 17 and nf % _V(dtype) == 1 and (nc - 1 + 64 * (_V(dtype) // 2) - 1) // (64 * (_V(dtype) // 2)) <= 8
-
-
-def small_fused_ok(nf, nzf):         # mg_small_levels.hip: whole levels up to 129^3, standard coarsening
-    return nf ** 2 * nzf <= 129 ** 3
+# They live in tests/size_table.py, next to the table of odd sizes that is computed from them.
+from tests.size_table import (_V, fast_path_ok, jacobi2_ok, pair_wide_ok, prolong_fast_ok, resid_restrict_fast_ok,  # noqa: E402,F401
+                              rr_wide_ok, small_fused_ok)
 
 
 # Single operators through mg_smooth (2 Jacobi sweeps = one fused pair where jacobi2_ok, 1 red-black sweep = the fused

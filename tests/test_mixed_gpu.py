@@ -140,6 +140,8 @@ SOLVE_CASES = {
     "3d65-aniso-semi": dict(dim=3, n=65, levels=5, length=1.0, **V22, omega=0.8, aniso=(1.0, 1.0, 0.01), semi_xy=2, **FIXED),
     # sweep counts off (2,2): mixed_inner runs the same cycle driver, from a non-zero state from the second inner cycle on
     "3d65-v13": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, nu_pre=1, nu_post=3), omega=6 / 7, **FIXED),
+    # a grid off 2^k + 1 (97, 49, 25, 13, 7: tests/size_table.py): fp32 rows of 24 vectors, 12 lanes in the fused residual + restriction
+    "3d97-v22": dict(dim=3, n=97, levels=5, length=1.0, **V22, omega=6 / 7, **FIXED),
 }
 
 

@@ -195,6 +195,8 @@ SOLVE_CASES = {
     # sweep counts off (2,2): precondition_t runs the same cycle driver; V(1,1) keeps the preconditioner symmetric, V(3,1) does not
     "3d65-v11": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, nu_pre=1, nu_post=1), omega=6 / 7, **FIXED),
     "3d65-v31": dict(dim=3, n=65, levels=4, length=1.0, **dict(V22, nu_pre=3, nu_post=1), omega=6 / 7, **FIXED),
+    # a grid off 2^k + 1 (97, 49, 25, 13, 7: tests/size_table.py): the preconditioner's cycles take the brick kernels on every transition
+    "3d97-v22": dict(dim=3, n=97, levels=5, length=1.0, **V22, omega=6 / 7, **FIXED),
 }
 
 
