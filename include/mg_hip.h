@@ -78,6 +78,39 @@ int mg_set_array(mg_handle h, int which, int level, const void *host);
 int mg_get_array(mg_handle h, int which, int level, void *host);
 int mg_zero_array(mg_handle h, int which, int level);
 
+/* Device-resident array I/O (extension): the same arrays from / into a dense array that already lives in HBM -- a torch
+ * tensor, the output of the caller's own kernels -- ordered against a stream the caller names, with NO host
+ * synchronisation. One streaming kernel (multigrid_prj_amd/csrc/mg_io.hip) converts between the dense layout and the
+ * library's 128-byte-pitched one, and between fp64 and fp32.
+ * Array: `dev` is device memory of the handle's device holding a dense, contiguous array in the host layout above
+ * (a[j*n+i], a[(k*n+j)*n+i]) with the extents mg_set_array uses for that handle and level (a distributed handle: the
+ * rank's own planes). dtype = MG_F64 or MG_F32 is the type of ITS elements and need not be desc.dtype: values are converted
+ * element by element -- double -> float rounds to nearest even (overflow: +-inf, NaN stays NaN), float -> double is exact;
+ * with equal types every bit pattern survives (NaN payloads, -0.0). The address needs only element alignment: a slice
+ * that starts in the middle of a larger buffer is admissible. On a get no byte outside the array is written.
+ * Stream: the caller's hipStream_t passed as void * (this header stays plain C); NULL = the device's default stream. It
+ * must belong to the handle's device and must not be capturing a graph.
+ * Ordering (two events owned by the handle, no timing): the copy runs on the HANDLE's stream
+ *   - after everything already enqueued on `stream` (set: the kernels that produce the array; get: those that still read it)
+ *     and, being on the handle's stream, after everything already enqueued on the handle (a preceding mg_cycle_async);
+ *   - before everything enqueued on `stream` after the call. After a set the caller may therefore overwrite or free the
+ *     array in stream order as soon as the call returns (a caching allocator needs exactly this); after a get, work
+ *     enqueued on `stream` sees the data. Host code synchronises `stream`, or calls mg_sync, before it reads the array.
+ * Side effects are mg_set_array's: ghost planes are not touched, padding columns keep the value zero.
+ * mg_heat_set_source_device and the mg_mixed_*_device calls (declared beside their host twins below) keep every rule of
+ * those twins -- when arrays are allocated, what mg_device_bytes counts, which handles are refused -- with the array
+ * passed as here; the mixed arrays may be MG_F32 (converted exactly into the fp64 u / b, rounded on the way out).
+ * MG_ERR_BAD_ARG, decided before anything is enqueued or allocated, handle and array untouched: NULL handle; unknown
+ * which, level or dtype; NULL dev (except mg_heat_set_source_device: f = 0 again); a pointer that is not aligned to its
+ * element type; a pointer that HIP does not report as device memory of the handle's device (host, managed, another
+ * device); an allocation that ends before the dense array does, or whose extent hipMemGetAddressRange cannot report
+ * (memory of a stream-ordered pool -- hipMallocAsync -- may fall under this: pass memory of hipMalloc, which is what
+ * torch's default caching allocator hands out).
+ * Any other failure (MG_ERR_HIP from a HIP call) leaves the ordering as documented: once the copy is enqueued, the second
+ * hand-over is made before the error is returned. */
+int mg_set_array_device(mg_handle h, int which, int level, const void *dev, int dtype, void *stream);
+int mg_get_array_device(mg_handle h, int which, int level, void *dev, int dtype, void *stream);
+
 /* `x * smoother` `sweeps` times on level l:  A_l x = rhs
  *   MG_SMOOTH_JACOBI -> Jacobi_iteration::apply_iteration_to_vec  solvers.hpp:64-83
  *   MG_SMOOTH_GS_LEX -> Gauss_Seidel_iteration::…                 solvers.hpp:33-48
@@ -236,6 +269,10 @@ int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int 
 int mg_mixed_set_rhs(mg_handle h, const double *host_b);
 int mg_mixed_set_solution(mg_handle h, const double *host_u);
 int mg_mixed_get_solution(mg_handle h, double *host_u);
+/* the same from / into dense device arrays on the caller's stream (see mg_set_array_device) */
+int mg_mixed_set_rhs_device(mg_handle h, const void *dev_b, int dtype, void *stream);
+int mg_mixed_set_solution_device(mg_handle h, const void *dev_u, int dtype, void *stream);
+int mg_mixed_get_solution_device(mg_handle h, void *dev_u, int dtype, void *stream);
 
 typedef struct mg_mixed_stats {
     int32_t outer;        /* corrections applied                                        */
@@ -306,6 +343,8 @@ int mg_get_shift(mg_handle h, double *sigma);
  * finite), theta outside (0, 1], nsteps < 1, cycles_per_step < 1, arr_dst == arr_u (mg_heat_rhs), distributed handles
  * (dry runs included), a stage callback installed (mg_heat_step), NULL handle. */
 int mg_heat_set_source(mg_handle h, const void *host_f);
+/* f from a dense device array on the caller's stream (see mg_set_array_device); dev_f == NULL: f = 0 again */
+int mg_heat_set_source_device(mg_handle h, const void *dev_f, int dtype, void *stream);
 typedef struct mg_heat_stats {
     int32_t steps;    /* steps taken                                              */
     int32_t cycles;   /* cycles run = steps * cycles_per_step                     */

@@ -123,11 +123,12 @@ class MgHostComm(C.Structure):
 EXPORTS = [
     "mg_last_error", "mg_device_count", "mg_create", "mg_destroy", "mg_level_n", "mg_level_nz",
     "mg_level_coefficients", "mg_set_rhs", "mg_set_solution", "mg_get_solution", "mg_set_array",
-    "mg_get_array", "mg_zero_array", "mg_smooth", "mg_residual", "mg_sumsq", "mg_restrict",
+    "mg_get_array", "mg_zero_array", "mg_set_array_device", "mg_get_array_device", "mg_smooth", "mg_residual", "mg_sumsq", "mg_restrict",
     "mg_prolong", "mg_correct", "mg_coarse_solve", "mg_coarse_solve_ex", "mg_cycle", "mg_cycle_async", "mg_solve", "mg_solve_lockstep",
     "mg_pcg_solve", "mg_pcg_kernel", "mg_fmg", "mg_fmg_prolong",
     "mg_mixed_set_rhs", "mg_mixed_set_solution", "mg_mixed_get_solution", "mg_mixed_solve", "mg_mixed_kernel",
-    "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_step", "mg_heat_rhs",
+    "mg_mixed_set_rhs_device", "mg_mixed_set_solution_device", "mg_mixed_get_solution_device",
+    "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_set_source_device", "mg_heat_step", "mg_heat_rhs",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
 ]
@@ -160,6 +161,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_set_array.argtypes = [vp, i, i, vp]
     L.mg_get_array.argtypes = [vp, i, i, vp]
     L.mg_zero_array.argtypes = [vp, i, i]
+    L.mg_set_array_device.argtypes = [vp, i, i, vp, i, vp]
+    L.mg_get_array_device.argtypes = [vp, i, i, vp, i, vp]
     L.mg_smooth.argtypes = [vp, i, i, i, i, i]
     L.mg_residual.argtypes = [vp, i, i, i, i, dp]
     L.mg_sumsq.argtypes = [vp, i, i, dp]
@@ -179,11 +182,15 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_mixed_set_rhs.argtypes = [vp, vp]
     L.mg_mixed_set_solution.argtypes = [vp, vp]
     L.mg_mixed_get_solution.argtypes = [vp, vp]
+    L.mg_mixed_set_rhs_device.argtypes = [vp, vp, i, vp]
+    L.mg_mixed_set_solution_device.argtypes = [vp, vp, i, vp]
+    L.mg_mixed_get_solution_device.argtypes = [vp, vp, i, vp]
     L.mg_mixed_solve.argtypes = [vp, C.c_double, i, i, dp, i, C.POINTER(i), C.POINTER(MgMixedStats)]
     L.mg_mixed_kernel.argtypes = [vp, i, C.c_double, C.c_double, i, i, dp]
     L.mg_set_shift.argtypes = [vp, C.c_double]
     L.mg_get_shift.argtypes = [vp, dp]
     L.mg_heat_set_source.argtypes = [vp, vp]
+    L.mg_heat_set_source_device.argtypes = [vp, vp, i, vp]
     L.mg_heat_step.argtypes = [vp, C.c_double, C.c_double, i, i, C.POINTER(MgHeatStats)]
     L.mg_heat_rhs.argtypes = [vp, C.c_double, C.c_double, i, i]
     L.mg_set_stage_callback.argtypes = [vp, STAGE_FN, vp]
@@ -234,6 +241,35 @@ def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(MG_COMM_ID_BYTES)
     _check(load().mg_comm_unique_id(buf))
     return buf.raw
+
+
+def device_view(obj, shape, writable=False):
+    """(pointer, MG_F64 | MG_F32) of a dense device array that exposes __cuda_array_interface__ (a torch-ROCm tensor does; so
+    does anything else that follows the protocol -- the package itself imports none of them). ValueError, before any
+    library call, unless it is a C-contiguous float64 / float32 array of exactly `shape` with a data pointer (and not
+    read-only where `writable` is asked for)."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise ValueError(f"{type(obj).__name__} has no __cuda_array_interface__: a device array (a torch tensor in HBM) is expected")
+    dtype = {"<f8": MG_F64, "<f4": MG_F32}.get(cai.get("typestr"))
+    if dtype is None:
+        raise ValueError(f"typestr {cai.get('typestr')!r}: only '<f8' and '<f4' device arrays can be copied")
+    got = tuple(int(v) for v in cai.get("shape", ()))
+    if got != tuple(int(v) for v in shape):
+        raise ValueError(f"expected shape {tuple(shape)}, got {got}")
+    strides = cai.get("strides")
+    if strides is not None:
+        want, step = [], 8 if dtype == MG_F64 else 4
+        for extent in reversed(got):
+            want.append(step); step *= extent
+        if tuple(int(v) for v in strides) != tuple(reversed(want)):
+            raise ValueError(f"strides {tuple(strides)} are not C-contiguous (expected {tuple(reversed(want))}): pass a contiguous array")
+    ptr, readonly = cai.get("data", (0, True))
+    if not ptr:
+        raise ValueError("null data pointer")
+    if writable and readonly:
+        raise ValueError("the device array is read-only")
+    return int(ptr), dtype
 
 
 class Solver:
@@ -310,6 +346,22 @@ class Solver:
     def set_rhs(self, b): self.set_array(ARR_RHS, 0, b)
     def set_solution(self, u): self.set_array(ARR_U, 0, u)
     def get_solution(self): return self.get_array(ARR_U, 0)
+
+    # -- the same from / into dense DEVICE arrays (torch tensors in HBM, ...), ordered against the caller's stream: `stream` is
+    # the integer handle of a HIP stream (torch.cuda.current_stream().cuda_stream); 0 = the default stream, torch's default.
+    # No host synchronisation: a set may be followed at once by work on `stream` that overwrites the source, a get by work
+    # on `stream` that reads `out`; host code synchronises the stream (or calls sync()) before it looks at `out`.
+    def set_array_device(self, which, level, obj, stream=0):
+        ptr, dt = device_view(obj, self.level_shape(level))
+        _check(self.lib.mg_set_array_device(self.h, which, level, ptr, dt, stream or None))
+
+    def get_array_device(self, which, level, out, stream=0):
+        ptr, dt = device_view(out, self.level_shape(level), writable=True)
+        _check(self.lib.mg_get_array_device(self.h, which, level, ptr, dt, stream or None))
+
+    def set_rhs_device(self, b, stream=0): self.set_array_device(ARR_RHS, 0, b, stream)
+    def set_solution_device(self, u, stream=0): self.set_array_device(ARR_U, 0, u, stream)
+    def get_solution_device(self, out, stream=0): self.get_array_device(ARR_U, 0, out, stream)
 
     # -- operators
     def smooth(self, level, smoother, sweeps, arr_x, arr_rhs):
@@ -403,6 +455,18 @@ class Solver:
         u = np.empty(self.level_shape(0), np.float64)
         _check(self.lib.mg_mixed_get_solution(self.h, u.ctypes.data_as(C.c_void_p))); return u
 
+    def mixed_set_rhs_device(self, b, stream=0):
+        ptr, dt = device_view(b, self.level_shape(0))
+        _check(self.lib.mg_mixed_set_rhs_device(self.h, ptr, dt, stream or None))
+
+    def mixed_set_solution_device(self, u, stream=0):
+        ptr, dt = device_view(u, self.level_shape(0))
+        _check(self.lib.mg_mixed_set_solution_device(self.h, ptr, dt, stream or None))
+
+    def mixed_get_solution_device(self, out, stream=0):
+        ptr, dt = device_view(out, self.level_shape(0), writable=True)
+        _check(self.lib.mg_mixed_get_solution_device(self.h, ptr, dt, stream or None))
+
     def mixed_solve(self, tol=1e-11, maxit=100, inner_cycles=4):
         """mg_mixed_solve: fp64 defect correction over the fp32 cycles of this (MG_F32) handle, `maxit` corrections of
         `inner_cycles` cycles at most -> (hist, MgMixedStats); hist[k] = the true fp64 ||b - A u_k|| / ||b||"""
@@ -430,6 +494,14 @@ class Solver:
             _check(self.lib.mg_heat_set_source(self.h, None))
         else:
             f = self._host(f, 0); _check(self.lib.mg_heat_set_source(self.h, f.ctypes.data_as(C.c_void_p)))
+
+    def heat_set_source_device(self, f, stream=0):
+        """mg_heat_set_source_device: f from a dense device array on the caller's stream; None: f = 0"""
+        if f is None:
+            _check(self.lib.mg_heat_set_source_device(self.h, None, self.d.dtype, stream or None))
+        else:
+            ptr, dt = device_view(f, self.level_shape(0))
+            _check(self.lib.mg_heat_set_source_device(self.h, ptr, dt, stream or None))
 
     def heat_step(self, dt, theta=1.0, nsteps=1, cycles_per_step=1) -> MgHeatStats:
         """mg_heat_step: nsteps theta-scheme steps of u_t = -A0 u + f from U, cycles_per_step cycles each, no host

@@ -103,6 +103,16 @@ int mg_set_solution(mg_handle h, const void *u) { MG_H(h); return guarded([&] { 
 int mg_get_solution(mg_handle h, void *u) { MG_H(h); return guarded([&] { return h->impl->get_array(MG_ARR_U, 0, u); }); }
 int mg_set_array(mg_handle h, int which, int level, const void *host) { MG_H(h); return guarded([&] { return h->impl->set_array(which, level, host); }); }
 int mg_get_array(mg_handle h, int which, int level, void *host) { MG_H(h); return guarded([&] { return h->impl->get_array(which, level, host); }); }
+int mg_set_array_device(mg_handle h, int which, int level, const void *dev, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->array_device(which, level, const_cast<void *>(dev), dtype, true, static_cast<hipStream_t>(stream)); });
+}
+int mg_get_array_device(mg_handle h, int which, int level, void *dev, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->array_device(which, level, dev, dtype, false, static_cast<hipStream_t>(stream)); });
+}
 int mg_zero_array(mg_handle h, int which, int level) { MG_H(h); return guarded([&] { return h->impl->zero_array(which, level); }); }
 
 int mg_smooth(mg_handle h, int level, int smoother, int sweeps, int arr_x, int arr_rhs)
@@ -205,6 +215,21 @@ int mg_mixed_get_solution(mg_handle h, double *host_u)
     if (!host_u) return bad("mg_mixed_get_solution: null argument");
     return guarded([&] { return h->impl->mixed_get_solution(host_u); });
 }
+int mg_mixed_set_rhs_device(mg_handle h, const void *dev_b, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->mixed_set_device(true, dev_b, dtype, static_cast<hipStream_t>(stream)); });
+}
+int mg_mixed_set_solution_device(mg_handle h, const void *dev_u, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->mixed_set_device(false, dev_u, dtype, static_cast<hipStream_t>(stream)); });
+}
+int mg_mixed_get_solution_device(mg_handle h, void *dev_u, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->mixed_get_solution_device(dev_u, dtype, static_cast<hipStream_t>(stream)); });
+}
 int mg_mixed_solve(mg_handle h, double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st)
 {
     MG_H(h);
@@ -225,6 +250,11 @@ int mg_get_shift(mg_handle h, double *sigma)
     return MG_OK;
 }
 int mg_heat_set_source(mg_handle h, const void *host_f) { MG_H(h); return guarded([&] { return h->impl->heat_set_source(host_f); }); }
+int mg_heat_set_source_device(mg_handle h, const void *dev_f, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->heat_set_source_device(dev_f, dtype, static_cast<hipStream_t>(stream)); });
+}
 int mg_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
 {
     MG_H(h);

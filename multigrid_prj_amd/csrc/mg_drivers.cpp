@@ -372,6 +372,27 @@ int Solver::mixed_get_solution(double *host)
     return stage_copy(reinterpret_cast<char *>(mxptr(MXU)), g64_, sizeof(double), host, false);
 }
 
+// the device twins: every rule of the host calls above; the copy is Solver::device_copy's (no host synchronisation)
+int Solver::mixed_set_device(bool rhs, const void *dense, int dense_dtype, hipStream_t caller)
+{
+    const char *fn = rhs ? "mg_mixed_set_rhs_device" : "mg_mixed_set_solution_device";
+    MG_TRY(mixed_check(fn));
+    if (!mx_[0]) MG_TRY(device_check(fn, dense, dense_dtype, lv_[0].g));   // nothing is allocated for an array that is refused
+    MG_TRY(mixed_alloc());
+    MG_TRY(device_copy(fn, reinterpret_cast<char *>(mxptr(rhs ? MXB : MXU)), g64_, sizeof(double), const_cast<void *>(dense), dense_dtype,
+                       true, caller));
+    (rhs ? mx_has_b_ : mx_has_u_) = true;
+    return MG_OK;
+}
+
+int Solver::mixed_get_solution_device(void *dense, int dense_dtype, hipStream_t caller)
+{
+    const char *fn = "mg_mixed_get_solution_device";
+    MG_TRY(mixed_check(fn));
+    if (!mx_has_u_) { set_last_error("mg_mixed_get_solution_device: no solution yet (call mg_mixed_set_solution first)"); return MG_ERR_BAD_ARG; }
+    return device_copy(fn, reinterpret_cast<char *>(mxptr(MXU)), g64_, sizeof(double), dense, dense_dtype, false, caller);
+}
+
 // 2^-e with frexp(sqrt(v)) = (m, e): brings a vector of squared norm v to a norm in [0.5, 1)
 static double mixed_scale(double v)
 {
@@ -521,6 +542,26 @@ int Solver::heat_set_source(const void *host)
     const Level &L0 = lv_[0];
     if (!heat_f_) MG_TRY(alloc_zeroed(&heat_f_, L0.alloc_elems * esize()));
     MG_TRY(stage_copy(static_cast<char *>(heat_f_) + (size_t)L0.gh * (size_t)L0.g.plane * esize(), L0.g, esize(), const_cast<void *>(host), true));
+    heat_has_f_ = true;
+    return MG_OK;
+}
+
+int Solver::heat_set_source_device(const void *dense, int dense_dtype, hipStream_t caller)
+{
+    const char *fn = "mg_heat_set_source_device";
+    MG_TRY(driver_begin(fn, REFUSE_DIST));
+    if (!dense) {
+        if (dense_dtype != MG_F64 && dense_dtype != MG_F32) { set_last_error(std::string(fn) + ": dtype must be MG_F64 or MG_F32"); return MG_ERR_BAD_ARG; }
+        heat_has_f_ = false;
+        return MG_OK;
+    }
+    const Level &L0 = lv_[0];
+    if (!heat_f_) {
+        MG_TRY(device_check(fn, dense, dense_dtype, L0.g));   // nothing is allocated for an array that is refused
+        MG_TRY(alloc_zeroed(&heat_f_, L0.alloc_elems * esize()));
+    }
+    MG_TRY(device_copy(fn, static_cast<char *>(heat_f_) + (size_t)L0.gh * (size_t)L0.g.plane * esize(), L0.g, esize(),
+                       const_cast<void *>(dense), dense_dtype, true, caller));
     heat_has_f_ = true;
     return MG_OK;
 }

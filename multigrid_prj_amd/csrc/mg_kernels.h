@@ -221,5 +221,12 @@ int launch_mixed_sumsq(hipStream_t s, const Geom &g64, const double *v, double *
 template <typename T>
 void launch_heat_rhs(hipStream_t s, const Geom &g, const double coef0[4], double dt, double theta, const T *u, const T *f, T *out);
 
+// ---- device-resident array I/O (mg_io.hip, driven by Solver::device_copy) ----
+// padded: local plane 0 of a level-shaped array of geometry g with elements P; dense: the caller's dense device array of
+// g.nx * g.ny * g.nz elements D at any element-aligned address. to_padded: padded = (P)dense, padding columns written as
+// zeros; otherwise dense = (D)padded and no byte outside the dense array is written. Ghost planes are not touched.
+template <typename P, typename D>
+void launch_io_copy(hipStream_t s, const Geom &g, P *padded, D *dense, bool to_padded);
+
 }  // namespace mg
 #endif

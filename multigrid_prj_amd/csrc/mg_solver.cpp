@@ -182,6 +182,7 @@ Solver::~Solver()
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     for (hipEvent_t e : ev_stage_) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_io_) if (e) (void)hipEventDestroy(e);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -200,6 +201,7 @@ int Solver::init()
     MG_HIP(hipEventCreate(&ev0_));
     MG_HIP(hipEventCreate(&ev1_));
     for (hipEvent_t &e : ev_stage_) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t &e : ev_io_) MG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (nranks_ > 1) {
         // the communication stream outranks the main one: the exchange kernels and the boundary pieces behind them are
         // dispatched ahead of the interior launch they run beside (MG_COMM_PRIORITY=0: same priority)
@@ -370,6 +372,8 @@ bool Solver::check_arr(int which, int level, const char *fn) const
 // Round 3: the staging buffer has two halves and the row (un)packing runs on a few host threads, so the DMA of one chunk
 // overlaps the packing of the next (1.08 GB at 513^3: 16-19 GB/s up and 8-10 GB/s down before, when chunk k's packing, its DMA
 // and the wait for it ran one after the other on one thread).
+// Measured since on the same array (tools/io_times.py, profiles/io_times.log): see DESIGN.md section 14 for the current figures
+// next to the device-resident path (device_copy below), which is what a caller whose data lives in HBM uses instead.
 namespace {
 // fn(first_row, last_row) over [0, nrows) on up to `nthreads` threads (the calling thread takes the first share)
 template <typename F>
@@ -479,6 +483,78 @@ int Solver::get_array(int which, int level, void *host)
 {
     if (!host || !check_arr(which, level, "mg_get_array")) return MG_ERR_BAD_ARG;
     return stage_rows(which, level, host, false);
+}
+
+// ---- the same copies from / into a dense array that already lives in HBM (mg_*_device) ----
+// Everything that can refuse does so here, before anything is enqueued or allocated: a pointer the kernel could not
+// read or write to the end of the dense array would be an illegal access.
+int Solver::device_check(const char *fn, const void *dense, int dense_dtype, const Geom &g)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (dense_dtype != MG_F64 && dense_dtype != MG_F32) { set_last_error(f + "dtype must be MG_F64 or MG_F32"); return MG_ERR_BAD_ARG; }
+    if (!dense) { set_last_error(f + "null device pointer"); return MG_ERR_BAD_ARG; }
+    const size_t des = dense_dtype == MG_F64 ? 8 : 4;
+    if (reinterpret_cast<uintptr_t>(dense) % des) { set_last_error(f + "the device pointer is not aligned to its element type"); return MG_ERR_BAD_ARG; }
+    MG_HIP(hipSetDevice(device_));
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, dense) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device_) {
+        (void)hipGetLastError();   // a pointer HIP does not know leaves a sticky error behind
+        set_last_error(f + "the pointer is not device memory of the handle's device (host and managed memory, and memory of another "
+                           "device, are refused)");
+        return MG_ERR_BAD_ARG;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(dense)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_last_error(f + "the pointer's allocation is unknown to HIP");
+        return MG_ERR_BAD_ARG;
+    }
+    const size_t need = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz * des;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), p = reinterpret_cast<uintptr_t>(dense);
+    if (p < lo || p - lo > size || size - (p - lo) < need) {
+        set_last_error(f + "the allocation ends before the dense array does: " + std::to_string(need) + " bytes needed, " +
+                       std::to_string(p >= lo && p - lo <= size ? size - (p - lo) : 0) + " left from the pointer on");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::device_copy(const char *fn, char *dev_padded, const Geom &g, size_t es, void *dense, int dense_dtype, bool to_padded,
+                        hipStream_t caller)
+{
+    MG_TRY(device_check(fn, dense, dense_dtype, g));
+    // [0]: the copy starts after everything `caller` holds (the kernels that produce `dense`; for a get, those that still use it)
+    MG_HIP(hipEventRecord(ev_io_[0], caller));
+    MG_HIP(hipStreamWaitEvent(stream_, ev_io_[0], 0));
+    if (es == 8) {
+        if (dense_dtype == MG_F64) launch_io_copy<double, double>(stream_, g, reinterpret_cast<double *>(dev_padded), static_cast<double *>(dense), to_padded);
+        else launch_io_copy<double, float>(stream_, g, reinterpret_cast<double *>(dev_padded), static_cast<float *>(dense), to_padded);
+    } else {
+        if (dense_dtype == MG_F64) launch_io_copy<float, double>(stream_, g, reinterpret_cast<float *>(dev_padded), static_cast<double *>(dense), to_padded);
+        else launch_io_copy<float, float>(stream_, g, reinterpret_cast<float *>(dev_padded), static_cast<float *>(dense), to_padded);
+    }
+    const hipError_t copy_launch = hipGetLastError();
+    // [1]: what `caller` gets from here on runs after the copy (a set: `dense` may be overwritten or freed in stream order; a get:
+    // the data is there). Done whatever the launch reported -- a stale error of the caller's own HIP calls surfaces there too, with
+    // the kernel enqueued all the same -- so that an error return never leaves `caller` unordered against a copy that still runs.
+    const hipError_t rec = hipEventRecord(ev_io_[1], stream_);
+    const hipError_t second_handover = rec == hipSuccess ? hipStreamWaitEvent(caller, ev_io_[1], 0) : rec;
+    MG_HIP(copy_launch);
+    MG_HIP(second_handover);
+    return MG_OK;
+}
+
+int Solver::array_device(int which, int level, void *dense, int dense_dtype, bool to_handle, hipStream_t caller)
+{
+    const char *fn = to_handle ? "mg_set_array_device" : "mg_get_array_device";
+    if (!check_arr(which, level, fn)) return MG_ERR_BAD_ARG;
+    Level &L = lv_[level];
+    char *dev = reinterpret_cast<char *>(L.base[which]) + (size_t)L.gh * (size_t)L.g.plane * esize();      // local plane 0
+    MG_TRY(device_copy(fn, dev, L.g, esize(), dense, dense_dtype, to_handle, caller));   // a refusal leaves the handle as it was
+    pair_on_comm_level_ = -1;                                                            // stage_rows' side effects
+    if (to_handle && which == MG_ARR_RHS) L.rhs_halo_ok = false;
+    return MG_OK;
 }
 
 int Solver::zero_array(int which, int level)

@@ -81,6 +81,9 @@ public:
     int stage_rows(int which, int level, void *host, bool to_device);
     int get_array(int which, int level, void *host);
     int zero_array(int which, int level);
+    // the same arrays from / into a dense DEVICE array of the caller, ordered against the caller's stream, no host
+    // synchronisation (mg_set_array_device / mg_get_array_device)
+    int array_device(int which, int level, void *dense, int dense_dtype, bool to_handle, hipStream_t caller);
 
     int smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs);
     int residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq);
@@ -110,6 +113,8 @@ public:
     // allocated by the first mixed_set_*
     int mixed_set(bool rhs, const double *host);
     int mixed_get_solution(double *host);
+    int mixed_set_device(bool rhs, const void *dense, int dense_dtype, hipStream_t caller);
+    int mixed_get_solution_device(void *dense, int dense_dtype, hipStream_t caller);
     int mixed_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st);
     int mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r);
     // the operator sigma I + A on every level (mg_set_shift): coef[3] = cd0 + sigma, zebra line factors re-tabulated
@@ -118,6 +123,7 @@ public:
     // implicit theta-scheme steps of u_t = -A0 u + f on level 0 (mg_heat_*); the source array is allocated by the first
     // heat_set_source
     int heat_set_source(const void *host);
+    int heat_set_source_device(const void *dense, int dense_dtype, hipStream_t caller);
     int heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
     int heat_rhs(double dt, double theta, int arr_u, int arr_dst);
     int set_stage_callback(mg_stage_fn fn, void *user);
@@ -217,6 +223,14 @@ private:
     int mixed_alloc();
     int mixed_inner(int inner_cycles);         // U32(0) = 0, then inner_cycles outer iterations of mg_solve on RHS32(0); no sync
     int stage_copy(char *dev, const Geom &g, size_t es, void *host, bool to_device);   // stage_rows on any level-shaped array
+    // stage_copy's twin for a dense array in device memory: device_check, then the copy kernel (mg_io.hip) on stream_ between
+    // two event hand-overs with the caller's stream -- it runs after what `caller` holds, and what `caller` gets afterwards
+    // runs after it. dev_padded: local plane 0, elements of es bytes. No host synchronisation.
+    int device_copy(const char *fn, char *dev_padded, const Geom &g, size_t es, void *dense, int dense_dtype, bool to_padded,
+                    hipStream_t caller);
+    // MG_ERR_BAD_ARG unless `dense` is device memory of device_ that holds g.nx * g.ny * g.nz elements of dense_dtype from
+    // there on; enqueues and allocates nothing
+    int device_check(const char *fn, const void *dense, int dense_dtype, const Geom &g);
     int krylov_scalars_alloc();
     int krylov_alloc();
     template <typename T> int vcycle_rec_t(int l, bool u_zero = false);
@@ -230,6 +244,7 @@ private:
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     hipEvent_t ev_stage_[2] = {nullptr, nullptr};   // one per half of the host staging buffer (stage_rows)
+    hipEvent_t ev_io_[2] = {nullptr, nullptr};      // device_copy: [0] caller's stream -> stream_, [1] stream_ -> caller's stream
     std::vector<Level> lv_;
     double *d_partials_ = nullptr;  // per-block partial sums
     // Slots of the pinned h_scal_. d_scal_ has the same slots; only the first three are written on the device (the Krylov and
