@@ -294,6 +294,61 @@ enum mg_mixed_kernel_kind { MG_MIXED_K_RESIDUAL = 0, MG_MIXED_K_CORRECT_RESIDUAL
 int mg_mixed_kernel(mg_handle h, int kernel, double scale_in, double scale_out,
                     int arr_e32, int arr_r32, double *sumsq_r);
 
+/* Fourth-order accurate solves by defect correction (extension, no reference counterpart). The residual is evaluated with
+ * the fourth-order operator sigma I + A4 of level 0, the correction equation (sigma I + A2) e = r is solved approximately by
+ * the handle's own second-order cycles, u += e (Trottenberg et al., Multigrid, section 5.4.1). The fixed point solves the
+ * fourth-order system: its error against the PDE's solution is O(h^4) where mg_solve's is O(h^2).
+ * The operator (level 0 only), from mg_level_coefficients(h, 0) = {cx, cy, cz, cd} and sigma = mg_get_shift: w_a = c_a / 12
+ * in fp64, cast to the working dtype T like every coefficient. Per axis a, with u(-2) .. u(+2) along it and i the node's
+ * index on it (n nodes),
+ *   2 <= i <= n-3:  p_a = ((16*(u(-1) + u(+1))) - (u(-2) + u(+2))) - 30*u
+ *   i == 1:         p_a = ((((10*u_0 - 15*u_1) - 4*u_2) + 14*u_3) - 6*u_4) + u_5     (u_0 the Dirichlet node, u_1 the node)
+ *   i == n-2:       the mirror image, the same order of operations counted from the far boundary
+ *   A4u = ((sigma*u + wz*p_z) + wy*p_y) + wx*p_x       (no z term in 2-D)
+ *   r = b - A4u on interior nodes, r = 0 on Dirichlet nodes whatever u holds there
+ * all in T, every operation rounded separately; the sum of r^2 is accumulated in double in a fixed order (no atomics: two
+ * runs give the same bits). Both stencils are exact for polynomials of degree <= 5 along the axis. Level 0 needs n >= 7 on
+ * every axis; semi_xy, aniso, grids that are not 2^k + 1, 2-D and 3-D, MG_F64 and MG_F32 are all admissible.
+ *
+ * mg_o4_residual:  arr_r(0) = arr_b(0) - (sigma I + A4) arr_u(0); arr_r < 0: norm only; arr_r != arr_u, arr_r != arr_b.
+ * mg_o4_correct_residual (the fused pass of mg_o4_solve, for kernel-level checks): arr_unew = arr_u + arr_e on interior
+ *   nodes, arr_unew = arr_u on Dirichlet nodes (arr_e is not looked at there), arr_r = arr_b - (sigma I + A4) arr_unew in
+ *   the same launch; five distinct level-0 arrays; arr_u and arr_e are not modified.
+ * Both: *sumsq_r = sum r^2 (may be NULL: nothing is fetched and the call does not synchronise).
+ *
+ * mg_o4_solve keeps mg_solve's contract for its arrays: b = RHS(0), first iterate = U(0); on return U(0) holds the answer
+ * and RHS(0) holds b unchanged, every other array is unspecified.
+ *   b4 = RHS(0), u4 = U(0) (device copies); u4 = b4 on Dirichlet nodes; bb = sum b^2 (all nodes, as mg_solve)
+ *   r = b4 - A4 u4 -> RHS(0); hist[0] = sqrt(rr / bb)
+ *   for k = 0, 1, ...: stop if (k > 0 and hist[k] <= tol) or k == maxit
+ *       U(0) = 0; inner_cycles times: desc.outer_pre_gs lexicographic GS sweeps + one mg_cycle (mg_solve's outer iteration)
+ *       ONE launch: u4' = u4 + U(0); RHS(0) = b4 - A4 u4'; rr_new; swap u4 / u4'
+ *       hist[k+1] = sqrt(rr_new / bb)
+ *   U(0) = u4, RHS(0) = b4
+ * One host synchronisation per correction (the stopping test), none inside the inner cycles; mg_profile_* brackets keep
+ * timing the level-0 launches of the cycles inside. Every cycle the descriptor can describe is admissible and the shift is
+ * honoured (the inner cycles work on sigma I + A2 as they do today). The outer iteration contracts by at most
+ * max |1 - A4^/A2^| = 1/3 per correction with an exact inner solve. status: 0 converged, 1 maxit reached, 2 at the first
+ * residual norm that is not finite (the last hist entry) -- that correction is not taken and U holds the last iterate
+ * with a finite norm (the caller's U when the first norm already is not finite). b == 0 with a zero residual gives
+ * hist[0] = 0, status 0 and no correction.
+ * Memory: the first mg_o4_solve allocates three more level-0 arrays (b4 and two copies of u4), kept until mg_destroy and
+ * counted by mg_device_bytes from then on. A call that fails with MG_ERR_HIP after the loop has started (an allocation or a
+ * launch failed) leaves U(0) and RHS(0) unspecified: RHS(0) holds a residual, b is still in the handle's b4.
+ * MG_ERR_BAD_ARG with U untouched: n < 7, inner_cycles < 1, maxit < 0, distributed handles (dry runs included), a stage
+ * callback installed (mg_o4_solve), a bad or repeated array (the two kernel calls), NULL handle. */
+int mg_o4_residual(mg_handle h, int arr_u, int arr_b, int arr_r, double *sumsq_r);
+int mg_o4_correct_residual(mg_handle h, int arr_u, int arr_e, int arr_b, int arr_unew, int arr_r, double *sumsq_r);
+typedef struct mg_o4_stats {
+    int32_t outer;        /* corrections applied                                              */
+    int32_t cycles;       /* cycles run = inner_cycles per correction started                 */
+    int32_t status;       /* 0 converged, 1 hit maxit, 2 residual norm not finite             */
+    int32_t reserved;
+    double  relres;       /* last hist entry: ||b - (sigma I + A4) u|| / ||b||                */
+} mg_o4_stats;
+int mg_o4_solve(mg_handle h, double tol, int maxit, int inner_cycles,
+                double *hist, int hist_cap, int *n_hist, mg_o4_stats *st);
+
 /* Diagonal shift (extension, no reference counterpart): from this call on the handle works on sigma I + A, sigma >= 0 --
  * the operator of an implicit time step or a screened-Poisson / Helmholtz-type solve. On every level the diagonal becomes
  * cd0_l + sigma (one fp64 addition, then cast to the working dtype like every coefficient), cd0_l being the diagonal the

@@ -23,6 +23,7 @@ PCG_K_UPDATE, PCG_K_DOTS, PCG_K_DIRECTION = 0, 1, 2
 PCG_CONVERGED, PCG_MAXIT, PCG_BREAKDOWN = 0, 1, 2
 MIXED_K_RESIDUAL, MIXED_K_CORRECT_RESIDUAL = 0, 1
 MIXED_CONVERGED, MIXED_MAXIT, MIXED_NOT_FINITE = 0, 1, 2
+O4_CONVERGED, O4_MAXIT, O4_NOT_FINITE = 0, 1, 2
 
 
 class MgError(RuntimeError):
@@ -82,6 +83,15 @@ class MgMixedStats(C.Structure):
     ]
 
 
+class MgO4Stats(C.Structure):
+    """include/mg_hip.h::mg_o4_stats (mg_o4_solve)"""
+
+    _fields_ = [
+        ("outer", C.c_int32), ("cycles", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
+        ("relres", C.c_double),
+    ]
+
+
 class MgHeatStats(C.Structure):
     """include/mg_hip.h::mg_heat_stats (mg_heat_step)"""
 
@@ -128,6 +138,7 @@ EXPORTS = [
     "mg_pcg_solve", "mg_pcg_kernel", "mg_fmg", "mg_fmg_prolong",
     "mg_mixed_set_rhs", "mg_mixed_set_solution", "mg_mixed_get_solution", "mg_mixed_solve", "mg_mixed_kernel",
     "mg_mixed_set_rhs_device", "mg_mixed_set_solution_device", "mg_mixed_get_solution_device",
+    "mg_o4_residual", "mg_o4_correct_residual", "mg_o4_solve",
     "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_set_source_device", "mg_heat_step", "mg_heat_rhs",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
@@ -187,6 +198,9 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_mixed_get_solution_device.argtypes = [vp, vp, i, vp]
     L.mg_mixed_solve.argtypes = [vp, C.c_double, i, i, dp, i, C.POINTER(i), C.POINTER(MgMixedStats)]
     L.mg_mixed_kernel.argtypes = [vp, i, C.c_double, C.c_double, i, i, dp]
+    L.mg_o4_residual.argtypes = [vp, i, i, i, dp]
+    L.mg_o4_correct_residual.argtypes = [vp, i, i, i, i, i, dp]
+    L.mg_o4_solve.argtypes = [vp, C.c_double, i, i, dp, i, C.POINTER(i), C.POINTER(MgO4Stats)]
     L.mg_set_shift.argtypes = [vp, C.c_double]
     L.mg_get_shift.argtypes = [vp, dp]
     L.mg_heat_set_source.argtypes = [vp, vp]
@@ -479,6 +493,27 @@ class Solver:
         """mg_mixed_kernel: one of the two fp64-in / fp32-out kernels of mixed_solve (MIXED_K_*) -> sum r^2"""
         s = C.c_double(0)
         _check(self.lib.mg_mixed_kernel(self.h, kernel, scale_in, scale_out, arr_e32, arr_r32, C.byref(s))); return s.value
+
+    # -- fourth-order defect correction on level 0
+    def o4_residual(self, arr_u, arr_b, arr_r=-1) -> float:
+        """mg_o4_residual: arr_r(0) = arr_b(0) - (sigma I + A4) arr_u(0) with the fourth-order operator (arr_r < 0: norm
+        only) -> sum r^2"""
+        s = C.c_double(0); _check(self.lib.mg_o4_residual(self.h, arr_u, arr_b, arr_r, C.byref(s))); return s.value
+
+    def o4_correct_residual(self, arr_u, arr_e, arr_b, arr_unew, arr_r) -> float:
+        """mg_o4_correct_residual: arr_unew = arr_u + arr_e (interior nodes), arr_r = arr_b - (sigma I + A4) arr_unew in
+        one launch; five distinct level-0 arrays -> sum r^2"""
+        s = C.c_double(0)
+        _check(self.lib.mg_o4_correct_residual(self.h, arr_u, arr_e, arr_b, arr_unew, arr_r, C.byref(s))); return s.value
+
+    def o4_solve(self, tol=1e-10, maxit=60, inner_cycles=1):
+        """mg_o4_solve: fourth-order defect correction over this handle's cycles (b = RHS, first iterate = U; U holds the
+        answer on return), `maxit` corrections of `inner_cycles` cycles at most -> (hist, MgO4Stats);
+        hist[k] = ||b - (sigma I + A4) u_k|| / ||b||"""
+        cap = max(maxit, 0) + 1
+        hist = (C.c_double * cap)(); nh = C.c_int(0); st = MgO4Stats()
+        _check(self.lib.mg_o4_solve(self.h, tol, maxit, inner_cycles, hist, cap, C.byref(nh), C.byref(st)))
+        return np.array(hist[:min(nh.value, cap)]), st
 
     # -- diagonal shift and the implicit heat-equation stepper
     def set_shift(self, sigma: float):

@@ -241,6 +241,22 @@ int mg_mixed_kernel(mg_handle h, int kernel, double scale_in, double scale_out, 
     MG_H(h);
     return guarded([&] { return h->impl->mixed_kernel(kernel, scale_in, scale_out, arr_e32, arr_r32, sumsq_r); });
 }
+int mg_o4_residual(mg_handle h, int arr_u, int arr_b, int arr_r, double *sumsq_r)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->o4_residual(arr_u, arr_b, arr_r, sumsq_r); });
+}
+int mg_o4_correct_residual(mg_handle h, int arr_u, int arr_e, int arr_b, int arr_unew, int arr_r, double *sumsq_r)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->o4_correct_residual(arr_u, arr_e, arr_b, arr_unew, arr_r, sumsq_r); });
+}
+int mg_o4_solve(mg_handle h, double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_o4_stats *st)
+{
+    MG_H(h);
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_o4_solve: bad history buffer");
+    return guarded([&] { return h->impl->o4_solve(tol, maxit, inner_cycles, hist, hist_cap, n_hist, st); });
+}
 int mg_set_shift(mg_handle h, double sigma) { MG_H(h); return guarded([&] { return h->impl->set_shift(sigma); }); }
 int mg_get_shift(mg_handle h, double *sigma)
 {

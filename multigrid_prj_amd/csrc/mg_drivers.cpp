@@ -1,5 +1,5 @@
 // mg_drivers.cpp -- the solve drivers of mg::Solver: everything that calls the cycle from above (mg_solve, mg_pcg_*, mg_fmg*,
-// mg_mixed_*, mg_set_shift, mg_heat_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
+// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
 // Reference call structure being replaced by solve(): the outer loop of src/main.cpp:72-116.
 #include "mg_solver.h"
 
@@ -402,7 +402,7 @@ static double mixed_scale(double v)
     return std::ldexp(1.0, -e);
 }
 
-int Solver::mixed_inner(int inner_cycles)
+int Solver::correction_cycles(int inner_cycles)
 {
     MG_HIP(hipMemsetAsync(lv_[0].base[MG_ARR_U], 0, lv_[0].alloc_elems * esize(), stream_));
     for (int c = 0; c < inner_cycles; c++) MG_TRY(outer_iteration_enqueue());
@@ -452,7 +452,7 @@ int Solver::mixed_solve(double tol, int maxit, int inner_cycles, double *hist, i
         for (int k = 0;; k++) {
             if (k > 0 && out.relres <= tol) { out.status = 0; break; }
             if (k == maxit) { out.status = 1; break; }
-            MG_TRY(mixed_inner(inner_cycles));
+            MG_TRY(correction_cycles(inner_cycles));
             out.cycles += inner_cycles;
             const double s_next = mixed_scale(rr);   // from the PREVIOUS residual: known before the launch
             np = launch_mixed_correct_residual(stream_, g64_, g32, L0.coef, mxptr(MXU), ptr<float>(MG_ARR_U, 0), b, mxptr(MXU2),
@@ -499,6 +499,134 @@ int Solver::mixed_kernel(int kernel, double scale_in, double scale_out, int arr_
     if (corr) std::swap(mx_[MXU], mx_[MXU2]);
     if (sumsq_r) *sumsq_r = h_scal_[SC_MX_SUM];
     return MG_OK;
+}
+
+// ---------------------------------------------------------------- fourth-order defect correction (mg_o4_solve)
+// r = b - (sigma I + A4) u with the fourth-order operator of level 0 (mg_o4.hip), (sigma I + A2) e = r solved approximately by
+// inner_cycles of the handle's own cycles, u += e: mixed_solve with another operator in place of another precision. The
+// outer iterate u4 and the right-hand side b4 live beside the hierarchy, whose U(0) / RHS(0) hold e and r meanwhile.
+int Solver::o4_check(const char *fn, unsigned refuse)
+{
+    MG_TRY(driver_begin(fn, refuse));
+    const Geom &g = lv_[0].g;
+    if (g.nx < 7 || g.ny < 7 || (g.dim == 3 && g.gnz < 7)) {
+        set_last_error(std::string(fn) + ": the fourth-order operator needs n >= 7 on every axis of level 0");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::o4_kernel_t(bool corr, int arr_u, int arr_e, int arr_b, int arr_unew, int arr_r, double *sumsq_r)
+{
+    Level &L0 = lv_[0];
+    const double w[3] = {L0.coef[0] / 12.0, L0.coef[1] / 12.0, L0.coef[2] / 12.0};
+    T *const r = arr_r >= 0 ? ptr<T>(arr_r, 0) : (T *)nullptr;
+    if (arr_r == MG_ARR_RHS || (corr && arr_unew == MG_ARR_RHS)) L0.rhs_halo_ok = false;
+    const int np = corr ? launch_o4_correct_residual<T>(stream_, L0.g, w, shift_, ptr<T>(arr_u, 0), ptr<T>(arr_e, 0), ptr<T>(arr_b, 0),
+                                                        ptr<T>(arr_unew, 0), r, d_partials_, o4_partials_cap_)
+                        : launch_o4_residual<T>(stream_, L0.g, w, shift_, ptr<T>(arr_u, 0), ptr<T>(arr_b, 0), r, d_partials_, o4_partials_cap_);
+    launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_O4_SUM);
+    MG_HIP(hipGetLastError());
+    if (sumsq_r) {
+        MG_TRY(fetch_scalars(SC_O4_SUM, d_scal_ + SC_O4_SUM));
+        *sumsq_r = h_scal_[SC_O4_SUM];
+    }
+    return MG_OK;
+}
+
+int Solver::o4_residual(int arr_u, int arr_b, int arr_r, double *sumsq_r)
+{
+    MG_TRY(o4_check("mg_o4_residual", REFUSE_DIST));
+    if (!check_arr(arr_u, 0, "mg_o4_residual") || !check_arr(arr_b, 0, "mg_o4_residual")) return MG_ERR_BAD_ARG;
+    if (arr_r >= 0 && (!check_arr(arr_r, 0, "mg_o4_residual") || arr_r == arr_u || arr_r == arr_b)) {
+        set_last_error("mg_o4_residual: bad output array");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? o4_kernel_t<double>(false, arr_u, -1, arr_b, -1, arr_r, sumsq_r)
+                              : o4_kernel_t<float>(false, arr_u, -1, arr_b, -1, arr_r, sumsq_r);
+}
+
+int Solver::o4_correct_residual(int arr_u, int arr_e, int arr_b, int arr_unew, int arr_r, double *sumsq_r)
+{
+    MG_TRY(o4_check("mg_o4_correct_residual", REFUSE_DIST));
+    const int a[5] = {arr_u, arr_e, arr_b, arr_unew, arr_r};
+    for (int i = 0; i < 5; i++) {
+        if (!check_arr(a[i], 0, "mg_o4_correct_residual")) return MG_ERR_BAD_ARG;
+        for (int j = 0; j < i; j++)
+            if (a[i] == a[j]) { set_last_error("mg_o4_correct_residual: the five arrays must be distinct"); return MG_ERR_BAD_ARG; }
+    }
+    return d_.dtype == MG_F64 ? o4_kernel_t<double>(true, arr_u, arr_e, arr_b, arr_unew, arr_r, sumsq_r)
+                              : o4_kernel_t<float>(true, arr_u, arr_e, arr_b, arr_unew, arr_r, sumsq_r);
+}
+
+template <typename T>
+int Solver::o4_solve_t(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_o4_stats *st)
+{
+    Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    const size_t nbytes = L0.alloc_elems * esize();
+    const double w[3] = {L0.coef[0] / 12.0, L0.coef[1] / 12.0, L0.coef[2] / 12.0};
+    auto op = [&](int k) { return reinterpret_cast<T *>(o4_[k]) + L0.gh * g.plane; };
+    mg_o4_stats out{0, 0, 0, 0, 0.0};
+    int nh = 0;
+    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
+    auto fetch_sum = [&](int np, double *v) -> int {   // the sum of the last launch's partials; synchronises
+        launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_O4_SUM);
+        MG_HIP(hipGetLastError());
+        MG_TRY(fetch_scalars(SC_O4_SUM, d_scal_ + SC_O4_SUM));
+        *v = h_scal_[SC_O4_SUM];
+        return MG_OK;
+    };
+
+    // b4 = RHS(0), u4 = U(0) with b's values on the Dirichlet nodes; b.b over all nodes, as mg_solve
+    double bb = 0, rr = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &bb));
+    MG_HIP(hipMemcpyAsync(o4_[O4B], L0.base[MG_ARR_RHS], nbytes, hipMemcpyDeviceToDevice, stream_));
+    MG_HIP(hipMemcpyAsync(o4_[O4U], L0.base[MG_ARR_U], nbytes, hipMemcpyDeviceToDevice, stream_));
+    launch_cg_boundary_copy<T>(stream_, g, op(O4U), op(O4B));
+    L0.rhs_halo_ok = false;
+    MG_TRY(fetch_sum(launch_o4_residual<T>(stream_, g, w, shift_, op(O4U), op(O4B), ptr<T>(MG_ARR_RHS, 0), d_partials_, o4_partials_cap_), &rr));
+    auto relres = [&](double v) { return v == 0.0 ? 0.0 : std::sqrt(v / bb); };
+    record(relres(rr));
+    bool take_u = true;
+    if (!std::isfinite(rr) || !std::isfinite(out.relres)) {
+        out.status = 2;
+        take_u = false;   // no iterate with a finite norm: U stays what the caller passed
+    } else if (rr == 0.0) {
+        out.status = 0;   // nothing to do: u solves the system (b == 0 with u == 0 inside included)
+    } else {
+        for (int k = 0;; k++) {
+            if (k > 0 && out.relres <= tol) { out.status = 0; break; }
+            if (k == maxit) { out.status = 1; break; }
+            MG_TRY(correction_cycles(inner_cycles));
+            out.cycles += inner_cycles;
+            double rr_new = 0;   // the one host synchronisation per correction: the stopping test
+            MG_TRY(fetch_sum(launch_o4_correct_residual<T>(stream_, g, w, shift_, op(O4U), ptr<T>(MG_ARR_U, 0), op(O4B), op(O4U2),
+                                                           ptr<T>(MG_ARR_RHS, 0), d_partials_, o4_partials_cap_), &rr_new));
+            record(relres(rr_new));
+            if (!std::isfinite(rr_new) || !std::isfinite(out.relres)) { out.status = 2; break; }   // not taken: u4 stays the last iterate
+            std::swap(o4_[O4U], o4_[O4U2]);
+            out.outer = k + 1;
+        }
+    }
+    if (take_u) MG_HIP(hipMemcpyAsync(L0.base[MG_ARR_U], o4_[O4U], nbytes, hipMemcpyDeviceToDevice, stream_));
+    MG_HIP(hipMemcpyAsync(L0.base[MG_ARR_RHS], o4_[O4B], nbytes, hipMemcpyDeviceToDevice, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
+int Solver::o4_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_o4_stats *st)
+{
+    MG_TRY(o4_check("mg_o4_solve", REFUSE_DIST | REFUSE_STAGE_CB));
+    if (inner_cycles < 1) { set_last_error("mg_o4_solve: inner_cycles must be at least 1"); return MG_ERR_BAD_ARG; }
+    if (maxit < 0) { set_last_error("mg_o4_solve: negative maxit"); return MG_ERR_BAD_ARG; }
+    for (auto &b : o4_)   // slot by slot: a call that failed half way leaves the rest to the next one
+        if (!b) MG_TRY(alloc_zeroed(&b, lv_[0].alloc_elems * esize()));
+    return d_.dtype == MG_F64 ? o4_solve_t<double>(tol, maxit, inner_cycles, hist, hist_cap, n_hist, st)
+                              : o4_solve_t<float>(tol, maxit, inner_cycles, hist, hist_cap, n_hist, st);
 }
 
 // ---------------------------------------------------------------- diagonal shift (mg_set_shift)

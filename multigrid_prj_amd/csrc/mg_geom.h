@@ -234,6 +234,15 @@ inline CoarsePlan coarse_plan(int dim, int nx, int ny, int nz, int elem_size, in
     return CoarsePlan{COARSE_GLOBAL, 0, 0, 0, COARSE_WG, 0, 0, clear};
 }
 
+// ---- which level-0 shapes the marching tile of mg_o4.hip takes (launch_o4_*); the plain form takes every other one ----
+// 3-D, and a row holds at least 16 full 16-byte vectors: with fewer, three quarters of a wave's 64 lanes own no node and
+// the one-thread-per-node form has more of the chip at work. Pure; tests/test_o4_cpu.py pins it.
+inline bool o4_march_ok(int dim, int nx, int ny, int nz, int elem_size)
+{
+    const int v = 16 / elem_size;
+    return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
+}
+
 struct CoarseOut {
     int iters;
     int flag;

@@ -221,6 +221,20 @@ int launch_mixed_sumsq(hipStream_t s, const Geom &g64, const double *v, double *
 template <typename T>
 void launch_heat_rhs(hipStream_t s, const Geom &g, const double coef0[4], double dt, double theta, const T *u, const T *f, T *out);
 
+// ---- fourth-order defect correction on level 0 (mg_o4.hip, driven by Solver::o4_solve) ----
+// w = {cx, cy, cz} / 12 of level 0 in fp64 and the handle's shift sigma (both cast to T here). Each launch leaves one partial
+// sum of r^2 per workgroup in `partials` (room for `cap`) and returns how many. The marching tile runs where
+// o4_march_ok (mg_geom.h), the plain form elsewhere.
+// r = b - (sigma I + A4) u on interior nodes, 0 on Dirichlet nodes; r == nullptr: norm only
+template <typename T>
+int launch_o4_residual(hipStream_t s, const Geom &g, const double w[3], double sigma, const T *u, const T *b, T *r,
+                       double *partials, int cap);
+// u_out = u + e on interior nodes, u on Dirichlet nodes (e is not looked at there); then the same residual of u_out.
+// u_out must not alias u.
+template <typename T>
+int launch_o4_correct_residual(hipStream_t s, const Geom &g, const double w[3], double sigma, const T *u, const T *e, const T *b,
+                               T *u_out, T *r, double *partials, int cap);
+
 // ---- device-resident array I/O (mg_io.hip, driven by Solver::device_copy) ----
 // padded: local plane 0 of a level-shaped array of geometry g with elements P; dense: the caller's dense device array of
 // g.nx * g.ny * g.nz elements D at any element-aligned address. to_padded: padded = (P)dense, padding columns written as

@@ -160,6 +160,7 @@ Solver::~Solver()
     for (auto &b : stage_base_) if (b) (void)hipFree(b);
     for (auto &b : kry_) if (b) (void)hipFree(b);
     for (auto &b : mx_) if (b) (void)hipFree(b);
+    for (auto &b : o4_) if (b) (void)hipFree(b);
     if (heat_f_) (void)hipFree(heat_f_);
     if (d_mx_part_) (void)hipFree(d_mx_part_);
     if (d_mx_sum_) (void)hipFree(d_mx_sum_);
@@ -293,6 +294,7 @@ int Solver::init()
         if (cap > max_partials) max_partials = cap;
     }
     MG_HIP(hipMalloc((void **)&d_partials_, sizeof(double) * (size_t)max_partials));
+    o4_partials_cap_ = max_partials;
     MG_HIP(hipMalloc((void **)&d_scal_, sizeof(double) * SC_COUNT));
     MG_HIP(hipMalloc((void **)&d_coarse_, sizeof(CoarseOut)));
     MG_HIP(hipMemsetAsync(d_scal_, 0, sizeof(double) * SC_COUNT, stream_));

@@ -117,6 +117,11 @@ public:
     int mixed_get_solution_device(void *dense, int dense_dtype, hipStream_t caller);
     int mixed_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st);
     int mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r);
+    // fourth-order defect correction on level 0 (mg_o4_*): the residual with sigma I + A4, the correction by the handle's
+    // own cycles; b4 and two copies of u4 are allocated by the first o4_solve
+    int o4_residual(int arr_u, int arr_b, int arr_r, double *sumsq_r);
+    int o4_correct_residual(int arr_u, int arr_e, int arr_b, int arr_unew, int arr_r, double *sumsq_r);
+    int o4_solve(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_o4_stats *st);
     // the operator sigma I + A on every level (mg_set_shift): coef[3] = cd0 + sigma, zebra line factors re-tabulated
     int set_shift(double sigma);
     double shift() const { return shift_; }
@@ -221,7 +226,9 @@ private:
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
     int mixed_check(const char *fn, unsigned refuse = REFUSE_DIST);      // MG_F32, then driver_begin(fn, refuse)
     int mixed_alloc();
-    int mixed_inner(int inner_cycles);         // U32(0) = 0, then inner_cycles outer iterations of mg_solve on RHS32(0); no sync
+    // U(0) = 0, then inner_cycles outer iterations of mg_solve on RHS(0): the approximate solve of the correction equation
+    // of mixed_solve and o4_solve; no synchronisation
+    int correction_cycles(int inner_cycles);
     int stage_copy(char *dev, const Geom &g, size_t es, void *host, bool to_device);   // stage_rows on any level-shaped array
     // stage_copy's twin for a dense array in device memory: device_check, then the copy kernel (mg_io.hip) on stream_ between
     // two event hand-overs with the caller's stream -- it runs after what `caller` holds, and what `caller` gets afterwards
@@ -256,7 +263,8 @@ private:
         SC_CG_DOT = 3,    // the two sums of pcg_kernel's check (fetched in one copy)
         SC_CG_DOT1 = 4,
         SC_MX_SUM = 5,    // d_mx_sum_: mixed_solve, mixed_kernel
-        SC_COUNT = 8      // the six slots, padded to one 64-byte line
+        SC_O4_SUM = 6,    // sum r^2 of the fourth-order residual: o4_solve, o4_residual, o4_correct_residual (written on the device)
+        SC_COUNT = 8      // the seven slots, padded to one 64-byte line
     };
     double *d_scal_ = nullptr;      // [SC_COUNT]
     CoarseOut *d_coarse_ = nullptr;
@@ -298,6 +306,13 @@ private:
     bool mx_has_b_ = false, mx_has_u_ = false;
     double *d_mx_part_ = nullptr, *d_mx_sum_ = nullptr;   // per-workgroup partial sums and their total
     double *mxptr(int k) const { return reinterpret_cast<double *>(mx_[k]) + g64_.plane; }   // local plane 0
+    // outer arrays of o4_solve (allocated on first use, kept until the handle goes): b4 and two copies of u4, level-0 shaped
+    enum { O4B = 0, O4U = 1, O4U2 = 2, NO4 = 3 };
+    void *o4_[NO4] = {};
+    int o4_check(const char *fn, unsigned refuse);   // driver_begin(fn, refuse), then n >= 7 on every axis of level 0
+    int o4_partials_cap_ = 0;                        // room in d_partials_ (set by init)
+    template <typename T> int o4_kernel_t(bool corr, int arr_u, int arr_e, int arr_b, int arr_unew, int arr_r, double *sumsq_r);
+    template <typename T> int o4_solve_t(double tol, int maxit, int inner_cycles, double *hist, int hist_cap, int *n_hist, mg_o4_stats *st);
     // diagonal shift of every level (set_shift) and the stepper's source term f: one more level-0 array (allocated on first
     // use, kept until the handle goes); heat_has_f_ == false: f = 0, the array is not read
     double shift_ = 0;
