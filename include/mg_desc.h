@@ -31,8 +31,15 @@ enum mg_dtype       { MG_F64 = 0, MG_F32 = 1 };
  * x-coupling (aniso[0] >> 1). */
 enum mg_smoother    { MG_SMOOTH_GS_LEX = 0, MG_SMOOTH_JACOBI = 1, MG_SMOOTH_RBGS = 2, MG_SMOOTH_ZEBRA_Y = 3,
                       MG_SMOOTH_ZEBRA_X = 4 };
+/* MG_CYCLE_W / MG_CYCLE_F (EXTENSION): the V-cycle's recursion with a second visit of every level below the one a
+ * cycle is on -- another W-cycle (W) or a V-cycle (F) that continues from the U the first visit left, RHS unchanged. The
+ * coarsest grid is solved once per visit of its parent: a W-cycle makes 2^(levels-2) coarse solves, an F-cycle levels-1.
+ * For a weak coarse-grid correction (injection with red-black sweeps, few coarse sweeps), where the V-cycle stalls or
+ * diverges; about 8/7 -> 4/3 of the V-cycle's fine-grid work in 3-D. Single-GPU handles only. */
 enum mg_cycle_kind  { MG_CYCLE_SAWTOOTH = 0,   /* reference cycle, multigrid.hpp:126-145 */
-                      MG_CYCLE_V        = 1 }; /* standard V(nu_pre,nu_post), extension  */
+                      MG_CYCLE_V        = 1,   /* standard V(nu_pre,nu_post), extension  */
+                      MG_CYCLE_W        = 2,   /* W(nu_pre,nu_post), extension           */
+                      MG_CYCLE_F        = 3 }; /* F(nu_pre,nu_post), extension           */
 enum mg_restriction { MG_RESTRICT_INJECT = 0,  /* reference: aliasing via mask()         */
                       MG_RESTRICT_FULLW  = 1 };/* 9/27-point full weighting, extension   */
 enum mg_coarse_mode { MG_COARSE_TOL   = 0,     /* reference Solver::Solve, solvers.hpp:324-342 */
@@ -49,9 +56,9 @@ typedef struct mg_desc {
     int32_t cycle;        /* enum mg_cycle_kind                                          */
     int32_t smoother;     /* enum mg_smoother, used on every level of the cycle          */
     double  omega;        /* Jacobi damping, 1.0 == reference (undamped)                 */
-    int32_t nu_pre;       /* V-cycle pre-smoothing sweeps (ignored by the sawtooth)      */
+    int32_t nu_pre;       /* V/W/F-cycle pre-smoothing sweeps (ignored by the sawtooth)  */
     int32_t nu_post;      /* post-smoothing sweeps per level (reference: 5)              */
-    int32_t restriction;  /* enum mg_restriction (V-cycle only; sawtooth always injects) */
+    int32_t restriction;  /* enum mg_restriction (V/W/F only; sawtooth always injects)   */
     int32_t coarse_mode;  /* enum mg_coarse_mode                                         */
     int32_t coarse_maxit; /* reference 2000 (or the fixed sweep count)                   */
     int32_t outer_pre_gs; /* lexicographic GS sweeps on the finest grid before each
@@ -87,11 +94,14 @@ static inline void mg_desc_reference_defaults(mg_desc *d, int n, int levels,
 
 /* per-cycle statistics returned by mg_cycle / orc_mg_cycle */
 typedef struct mg_cycle_stats {
-    int32_t coarse_iters;    /* smoother sweeps spent by the coarse solve               */
-    int32_t coarse_flag;     /* Solver::Status(): 1 == hit maxit, 0 == converged        */
-    double  coarse_relres;   /* "Achieved residual on coarse grid" multigrid.hpp:131    */
+    int32_t coarse_iters;    /* smoother sweeps spent by the coarse solve; W / F cycles:
+                                the SUM over the cycle's coarse solves                   */
+    int32_t coarse_flag;     /* Solver::Status(): 1 == hit maxit, 0 == converged; W / F:
+                                the OR over the cycle's coarse solves                    */
+    double  coarse_relres;   /* "Achieved residual on coarse grid" multigrid.hpp:131;
+                                W / F: of the cycle's last coarse solve                  */
     double  fine_sumsq_r;    /* sum r^2 of the fine residual the cycle started from
-                                (sawtooth only; 0 for the V-cycle)                       */
+                                (sawtooth only; 0 for the V, W and F cycles)             */
 } mg_cycle_stats;
 
 #ifdef __cplusplus

@@ -204,7 +204,7 @@ int mg_pcg_kernel(mg_handle h, int kernel, double scalar, const int *arrs, doubl
  *                                                      Dirichlet data travels with the right-hand side)
  *     U(L-1) = 0 inside, RHS(L-1) on Dirichlet nodes;  coarse solve of A U = RHS   (desc.coarse_* as in a cycle)
  *     for l = L-2 .. 0:   U(l) = Pi U(l+1) inside, RHS(l) on Dirichlet nodes      (one launch)
- *                         cycles_per_level V-cycles of the descriptor started on level l
+ *                         cycles_per_level cycles of the descriptor's kind (V, W or F) started on level l
  * Pi is the FMG interpolation: along every coarsened axis f[2m] = c[m], f[2m+1] = (-c[m-1] + 9 c[m] + 9 c[m+1] -
  * c[m+2]) / 16, next to a boundary (3 c[0] + 6 c[1] - c[2]) / 8 and its mirror; kept axes (z of a semi-coarsened
  * transition) are copied. Its O(h^4) error stays below the discretisation error, which mg_prolong's linear
@@ -212,7 +212,7 @@ int mg_pcg_kernel(mg_handle h, int kernel, double scalar, const int *arrs, doubl
  * of the discretisation error after about 8/7 of the work of the cycles run on level 0 -- and RHS(0) is unchanged; the
  * incoming U(0) is ignored; every other array is unspecified, as after mg_solve. It is the natural first guess of
  * mg_solve / mg_pcg_solve when a tighter tolerance is wanted. No host synchronisation inside the pass except the one
- * residual at its end. MG_CYCLE_V only (the levels of a sawtooth cycle hold errors, not solutions), every smoother,
+ * residual at its end. MG_CYCLE_V, _W and _F (the levels of a sawtooth cycle hold errors, not solutions), every smoother,
  * both restrictions, aniso, semi_xy, 2-D and 3-D, both dtypes; levels == 1 is just the coarse solve. MG_ERR_BAD_ARG
  * with U untouched: MG_CYCLE_SAWTOOTH, cycles_per_level < 1, distributed handles (dry runs included), a stage callback
  * installed. mg_profile_* brackets keep timing the level-0 cycles inside (cycles on inner levels are not counted). */
@@ -228,6 +228,34 @@ int mg_fmg(mg_handle h, int cycles_per_level, mg_fmg_stats *st);
  * arr_dst(coarse_level - 1) = Pi arr_src(coarse_level); fine Dirichlet nodes take arr_bnd(coarse_level - 1) bit for bit
  * (arr_bnd < 0: they are interpolated like every other node). Single-GPU handles only; arr_dst != arr_bnd. */
 int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int arr_bnd);
+
+/* W- and F-cycles (extension, mg_desc.h: MG_CYCLE_W, MG_CYCLE_F). With L = desc.levels, one cycle of kind V, W or F started
+ * on level l is
+ *     cyc(l, kind):
+ *       if l == L-1:  coarse solve of A U = RHS (desc.coarse_*);  return
+ *       nu_pre sweeps;  RHS(l+1) = R (RHS(l) - A U(l))  (desc.restriction);  U(l+1) = 0
+ *       cyc(l+1, kind)
+ *       if l+1 < L-1:                      the coarsest grid is solved once per visit of its parent
+ *           kind == W: cyc(l+1, W)         the second visit continues from U(l+1), RHS(l+1) unchanged
+ *           kind == F: cyc(l+1, V)
+ *       U(l) += P U(l+1);  nu_post sweeps
+ * and mg_cycle, mg_solve(_lockstep), mg_pcg_solve, mg_fmg, mg_mixed_solve, mg_heat_step, mg_o4_solve run it wherever they
+ * run "the handle's cycle". mg_cycle_stats of a W / F cycle: coarse_iters is the sum over the cycle's coarse solves (2^(L-2)
+ * of them for W, L-1 for F), coarse_flag the OR, coarse_relres that of the last one; mg_solve_lockstep gives coarse_counts[i]
+ * to every coarse solve of iteration i. Level 0 is visited once per cycle whatever the kind and runs as in a V-cycle. The
+ * levels below a ROOT level that fit one CU's LDS together (Jacobi or red-black, standard coarsening from the root down, no
+ * stage callback) run as ONE launch per visit of the root (MG_SUBCYCLE_LEVEL); mg_subcycle_root says
+ * which. Single-GPU handles only: mg_create_distributed* (dry runs included) answer MG_ERR_INVALID_DESC.
+ *
+ * mg_subcycle: one cyc(level, kind) on U(level), RHS(level), started from the U it holds; kind = MG_CYCLE_V / W / F whatever
+ * desc.cycle says (not on a sawtooth handle). path 0: launch by launch (the cycle driver's own code); path 1: the LDS kernel
+ * rooted at `level` (no second visit), MG_ERR_BAD_ARG when [level, L-1] is not admissible. The two paths give the same bits
+ * with MG_COARSE_FIXED. st as for a W / F cycle. The arrays of the levels below `level` are unspecified afterwards.
+ * MG_ERR_BAD_ARG with U untouched: a sawtooth handle, an unknown kind or path, a level outside [0, L-1], distributed
+ * handles. */
+int mg_subcycle(mg_handle h, int level, int kind, int path, mg_cycle_stats *st);
+/* root level the handle's cycles hand to the LDS kernel, -1: none */
+int mg_subcycle_root(mg_handle h, int *root);
 
 /* Mixed-precision defect correction (extension, no reference counterpart): an fp64 answer paid for with fp32 cycles.
  * On a handle created with desc.dtype == MG_F32 the solution u and the right-hand side b of level 0 are kept in fp64

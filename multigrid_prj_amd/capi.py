@@ -14,6 +14,7 @@ from . import build as _build
 MG_F64, MG_F32 = 0, 1
 SMOOTH_GS_LEX, SMOOTH_JACOBI, SMOOTH_RBGS, SMOOTH_ZEBRA_Y, SMOOTH_ZEBRA_X = 0, 1, 2, 3, 4
 CYCLE_SAWTOOTH, CYCLE_V = 0, 1
+CYCLE_W, CYCLE_F = 2, 3
 RESTRICT_INJECT, RESTRICT_FULLW = 0, 1
 COARSE_TOL, COARSE_FIXED = 0, 1
 ARR_U, ARR_E, ARR_RHS, ARR_TMP, ARR_RES = 0, 1, 2, 3, 4
@@ -135,7 +136,7 @@ EXPORTS = [
     "mg_level_coefficients", "mg_set_rhs", "mg_set_solution", "mg_get_solution", "mg_set_array",
     "mg_get_array", "mg_zero_array", "mg_set_array_device", "mg_get_array_device", "mg_smooth", "mg_residual", "mg_sumsq", "mg_restrict",
     "mg_prolong", "mg_correct", "mg_coarse_solve", "mg_coarse_solve_ex", "mg_cycle", "mg_cycle_async", "mg_solve", "mg_solve_lockstep",
-    "mg_pcg_solve", "mg_pcg_kernel", "mg_fmg", "mg_fmg_prolong",
+    "mg_pcg_solve", "mg_pcg_kernel", "mg_fmg", "mg_fmg_prolong", "mg_subcycle", "mg_subcycle_root",
     "mg_mixed_set_rhs", "mg_mixed_set_solution", "mg_mixed_get_solution", "mg_mixed_solve", "mg_mixed_kernel",
     "mg_mixed_set_rhs_device", "mg_mixed_set_solution_device", "mg_mixed_get_solution_device",
     "mg_o4_residual", "mg_o4_correct_residual", "mg_o4_solve",
@@ -190,6 +191,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_pcg_kernel.argtypes = [vp, i, C.c_double, C.POINTER(i), dp]
     L.mg_fmg.argtypes = [vp, i, C.POINTER(MgFmgStats)]
     L.mg_fmg_prolong.argtypes = [vp, i, i, i, i]
+    L.mg_subcycle.argtypes = [vp, i, i, i, C.POINTER(MgCycleStats)]
+    L.mg_subcycle_root.argtypes = [vp, C.POINTER(i)]
     L.mg_mixed_set_rhs.argtypes = [vp, vp]
     L.mg_mixed_set_solution.argtypes = [vp, vp]
     L.mg_mixed_get_solution.argtypes = [vp, vp]
@@ -441,7 +444,7 @@ class Solver:
 
     def fmg(self, cycles_per_level=1):
         """mg_fmg: full multigrid (nested iteration) from the coarsest grid up, cubic interpolation of the solution and
-        cycles_per_level V-cycles per level; U(0) holds the iterate on return (its incoming content is ignored)
+        cycles_per_level cycles of the descriptor's kind (V, W or F) per level; U(0) holds the iterate on return (its incoming content is ignored)
         -> MgFmgStats"""
         st = MgFmgStats()
         _check(self.lib.mg_fmg(self.h, cycles_per_level, C.byref(st)))
@@ -451,6 +454,15 @@ class Solver:
         """mg_fmg_prolong: arr_dst(coarse_level - 1) = Pi arr_src(coarse_level), the FMG (cubic) interpolation; fine
         Dirichlet nodes from arr_bnd (< 0: interpolated too)"""
         _check(self.lib.mg_fmg_prolong(self.h, coarse_level, arr_src, arr_dst, arr_bnd))
+
+    def subcycle(self, level, kind, path=0) -> MgCycleStats:
+        """mg_subcycle: one cyc(level, kind) (CYCLE_V / _W / _F) on U(level), RHS(level) from the U it holds; path 0: launch
+        by launch, path 1: the one-launch LDS kernel rooted at `level`"""
+        st = MgCycleStats(); _check(self.lib.mg_subcycle(self.h, level, kind, path, C.byref(st))); return st
+
+    def subcycle_root(self) -> int:
+        """mg_subcycle_root: the level the handle's cycles hand to the LDS kernel, -1: none"""
+        r = C.c_int(0); _check(self.lib.mg_subcycle_root(self.h, C.byref(r))); return r.value
 
     # -- mixed-precision defect correction: fp64 u / b beside an MG_F32 hierarchy (float64 arrays whatever the handle's dtype)
     def _host64(self, a):

@@ -192,6 +192,18 @@ int mg_fmg(mg_handle h, int cycles_per_level, mg_fmg_stats *st)
     MG_H(h);
     return guarded([&] { return h->impl->fmg(cycles_per_level, st); });
 }
+int mg_subcycle(mg_handle h, int level, int kind, int path, mg_cycle_stats *st)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->subcycle(level, kind, path, st); });
+}
+int mg_subcycle_root(mg_handle h, int *root)
+{
+    MG_H(h);
+    if (!root) return bad("mg_subcycle_root: null argument");
+    *root = h->impl->subcycle_root();
+    return MG_OK;
+}
 int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int arr_bnd)
 {
     MG_H(h);
@@ -379,6 +391,16 @@ int mg_comm_selftest(size_t bytes)
     });
 }
 
+// the gathered tail of a slab-decomposed hierarchy would be visited repeatedly: a schedule the library does not have
+static int dist_cycle_check(const mg_desc *desc, int nranks, const char *fn)
+{
+    if (nranks > 1 && (desc->cycle == MG_CYCLE_W || desc->cycle == MG_CYCLE_F)) {
+        mg::set_last_error(std::string(fn) + ": MG_CYCLE_W / MG_CYCLE_F run on single-GPU handles only");
+        return MG_ERR_INVALID_DESC;
+    }
+    return MG_OK;
+}
+
 static int create_with_comm(const mg_desc *desc, int device, int rank, int nranks, mg::Comm *comm, mg_handle *out)
 {
     (void)rank; (void)nranks;
@@ -399,6 +421,7 @@ int mg_create_distributed(const mg_desc *desc, int device, int rank, int nranks,
         std::string why;
         int rc = mg::validate_desc(desc, &why);
         if (rc) { mg::set_last_error("mg_create_distributed: " + why); return rc; }
+        if ((rc = dist_cycle_check(desc, nranks, "mg_create_distributed"))) return rc;
         mg::SlabPlan p;
         rc = mg::plan_slab(*desc, nranks, rank, 0, &p, &why);
         if (rc) { mg::set_last_error("mg_create_distributed: " + why); return rc; }
@@ -418,6 +441,7 @@ int mg_create_distributed_hostcomm(const mg_desc *desc, int device, int rank, in
         std::string why;
         int rc = mg::validate_desc(desc, &why);
         if (rc) { mg::set_last_error("mg_create_distributed_hostcomm: " + why); return rc; }
+        if ((rc = dist_cycle_check(desc, nranks, "mg_create_distributed_hostcomm"))) return rc;
         mg::SlabPlan p;
         rc = mg::plan_slab(*desc, nranks, rank, 0, &p, &why);
         if (rc) { mg::set_last_error("mg_create_distributed_hostcomm: " + why); return rc; }
@@ -435,6 +459,7 @@ int mg_create_distributed_dryrun(const mg_desc *desc, int device, int rank, int 
         std::string why;
         int rc = mg::validate_desc(desc, &why);
         if (rc) { mg::set_last_error("mg_create_distributed_dryrun: " + why); return rc; }
+        if ((rc = dist_cycle_check(desc, nranks, "mg_create_distributed_dryrun"))) return rc;
         mg::SlabPlan p;
         rc = mg::plan_slab(*desc, nranks, rank, 0, &p, &why);
         if (rc) { mg::set_last_error("mg_create_distributed_dryrun: " + why); return rc; }

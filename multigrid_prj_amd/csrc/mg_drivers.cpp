@@ -260,7 +260,7 @@ int Solver::pcg_kernel(int kernel, double scalar, const int *arrs, double *dots)
 // ---------------------------------------------------------------- full multigrid (nested iteration), mg_fmg
 // f_{l+1} = R f_l down the hierarchy (the level operators are unscaled and the restrictions inject on the coarse boundary,
 // so this carries the right-hand side and the Dirichlet data), the coarsest-grid solve, then coarse to fine: U(l) = Pi U(l+1)
-// (mg_fmg.hip; Dirichlet nodes from RHS(l)) and cycles_per_level V-cycles started on level l. A cycle started on level l
+// (mg_fmg.hip; Dirichlet nodes from RHS(l)) and cycles_per_level cycles of the descriptor's kind (V, W or F) started on level l. A cycle started on level l
 // only overwrites U and RHS of the levels below it, which the pass has finished with: no storage of its own.
 template <typename T>
 int Solver::fmg_t(int cycles_per_level, mg_fmg_stats *st)
@@ -275,7 +275,7 @@ int Solver::fmg_t(int cycles_per_level, mg_fmg_stats *st)
     for (int l = L - 2; l >= 0; l--) {
         launch_fmg_prolong<T>(stream_, lv_[l + 1].g, lv_[l].g, ptr<T>(MG_ARR_U, l + 1), ptr<T>(MG_ARR_U, l), ptr<T>(MG_ARR_RHS, l));
         MG_HIP(hipGetLastError());
-        for (int k = 0; k < cycles_per_level; k++) MG_TRY(vcycle_rec_t<T>(l));
+        for (int k = 0; k < cycles_per_level; k++) MG_TRY(cycle_from_t<T>(l));   // of the descriptor's kind: V, W or F
     }
     double nb = 0, nr = 0;
     MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
@@ -293,7 +293,7 @@ int Solver::fmg_t(int cycles_per_level, mg_fmg_stats *st)
 int Solver::fmg(int cycles_per_level, mg_fmg_stats *st)
 {
     MG_TRY(driver_begin("mg_fmg", REFUSE_DIST | REFUSE_STAGE_CB));
-    if (d_.cycle != MG_CYCLE_V) {
+    if (!is_vwf(d_.cycle)) {
         set_last_error("mg_fmg: the descriptor's cycle must be MG_CYCLE_V (the levels of a sawtooth cycle hold errors, not solutions)");
         return MG_ERR_BAD_ARG;
     }
@@ -302,6 +302,36 @@ int Solver::fmg(int cycles_per_level, mg_fmg_stats *st)
         return MG_ERR_BAD_ARG;
     }
     return d_.dtype == MG_F64 ? fmg_t<double>(cycles_per_level, st) : fmg_t<float>(cycles_per_level, st);
+}
+
+// ---------------------------------------------------------------- one cyc(level, kind), mg_subcycle
+// The kernel-level check of mg_subcycle.hip and the building block of a caller's own nested iteration: path 0 runs the cycle
+// driver's launches (never the kernel, whatever the handle's root is), path 1 the LDS kernel rooted at `level`.
+int Solver::subcycle(int level, int kind, int path, mg_cycle_stats *st)
+{
+    MG_TRY(driver_begin("mg_subcycle", REFUSE_DIST));
+    if (!is_vwf(d_.cycle)) { set_last_error("mg_subcycle: not on a sawtooth handle (its levels hold errors, not solutions)"); return MG_ERR_BAD_ARG; }
+    if (!is_vwf(kind)) { set_last_error("mg_subcycle: kind must be MG_CYCLE_V, MG_CYCLE_W or MG_CYCLE_F"); return MG_ERR_BAD_ARG; }
+    if (level < 0 || level >= d_.levels) { set_last_error("mg_subcycle: level out of range"); return MG_ERR_BAD_ARG; }
+    if (path != 0 && path != 1) { set_last_error("mg_subcycle: path must be 0 (launches) or 1 (the LDS kernel)"); return MG_ERR_BAD_ARG; }
+    if (path == 1 && (stage_fn_ || subcycle_plan_of(level).root != level)) {
+        set_last_error("mg_subcycle: the LDS kernel does not admit the levels from this one down (mg::subcycle_plan)");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_TRY(stats_begin());
+    const int root_saved = sub_root_;
+    int rc;
+    if (path == 0) {
+        sub_root_ = -1;
+        rc = d_.dtype == MG_F64 ? vcycle_rec_t<double>(level, false, kind) : vcycle_rec_t<float>(level, false, kind);
+        sub_root_ = root_saved;
+    } else {
+        rc = d_.dtype == MG_F64 ? subcycle_launch_t<double>(level, kind, false, false) : subcycle_launch_t<float>(level, kind, false, false);
+    }
+    acc_stats_ = false;
+    MG_TRY(rc);
+    MG_TRY(stats_end());
+    return fetch_cycle_stats(st);
 }
 
 int Solver::fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)

@@ -234,6 +234,64 @@ inline CoarsePlan coarse_plan(int dim, int nx, int ny, int nz, int elem_size, in
     return CoarsePlan{COARSE_GLOBAL, 0, 0, 0, COARSE_WG, 0, 0, clear};
 }
 
+// ---- which levels the one-launch LDS sub-cycle (k_subcycle, mg_subcycle.hip) can hold ---------------------------------------
+// One workgroup runs the whole recursion below a ROOT level out of LDS: for every level l in [root, levels - 1] the arrays
+// u_l, t_l (Jacobi's out-of-place target and the residual) and b_l lie dense (pitch = nx) behind the reduction scratch.
+// Admissible: 1 <= root <= levels - 2 (level 0 keeps its fused pairs, its folded prolongation, the profiling brackets and
+// mg_solve's norm: it always runs by launches), every transition from root downwards coarsens all axes (root >= semi_xy),
+// the smoother is Jacobi or red-black, and everything fits COARSE_LDS_MAX. Pure: nx, ny, nz are the extents of ALL levels
+// of the hierarchy; the caller adds what only it knows (one GPU, no stage callback). off[k][0..2]: byte offsets of u, t, b
+// of level root + k. tests/test_cycle_kinds_cpu.py pins it.
+constexpr int SUBCYCLE_MAX_LEVELS = 8;
+constexpr long long SUBCYCLE_SCRATCH = 256;   // the block sums' 18 doubles, rounded up
+struct SubcyclePlan {
+    int root;             // -1: not admissible
+    int nres;             // resident levels = levels - root
+    long long off[SUBCYCLE_MAX_LEVELS][3];
+    long long lds_bytes;  // dynamic LDS, scratch included
+};
+
+inline SubcyclePlan subcycle_plan(int levels, const int *nx, const int *ny, const int *nz, int semi_xy, int smoother, int elem_size,
+                                  int root)
+{
+    SubcyclePlan p{};
+    p.root = -1;
+    if (root < 1 || root > levels - 2 || levels - root > SUBCYCLE_MAX_LEVELS) return p;
+    if (root < semi_xy) return p;
+    if (smoother != 1 && smoother != 2) return p;   // MG_SMOOTH_JACOBI, MG_SMOOTH_RBGS
+    long long at = SUBCYCLE_SCRATCH;
+    for (int l = root; l < levels; l++) {
+        const long long bytes = (((long long)nx[l] * ny[l] * nz[l] * elem_size + 15) / 16) * 16;
+        for (int a = 0; a < 3; a++) { p.off[l - root][a] = at; at += bytes; }
+    }
+    if (at > COARSE_LDS_MAX) return p;
+    p.root = root;
+    p.nres = levels - root;
+    p.lds_bytes = at;
+    return p;
+}
+
+// the finest admissible root, -1: none
+inline int subcycle_finest_root(int levels, const int *nx, const int *ny, const int *nz, int semi_xy, int smoother, int elem_size)
+{
+    for (int root = 1; root <= levels - 2; root++)
+        if (subcycle_plan(levels, nx, ny, nz, semi_xy, smoother, elem_size, root).root == root) return root;
+    return -1;
+}
+
+// The root W and F handles take by default (MG_SUBCYCLE_LEVEL = -1): the level below the finest admissible root, or that
+// root itself when nothing lies between it and the coarsest level. One workgroup sweeps the finest admissible grid (17^3 in
+// 3-D) more slowly than the chip-wide launches do, and only from the next level down (9^3: one point per thread) does a visit
+// cost less in the kernel than its five or six launches: tools/cycle_kinds_times.py, profiles/cycle_kinds_times.log (W-cycle
+// at 513^3 fp64: 6.13 ms by launches, 5.67 ms rooted at 17^3, 5.39 ms rooted at 9^3; the same order at 1025^3 fp32 and
+// 129^3, Jacobi and red-black). -1: none.
+inline int subcycle_default_root(int levels, const int *nx, const int *ny, const int *nz, int semi_xy, int smoother, int elem_size)
+{
+    const int finest = subcycle_finest_root(levels, nx, ny, nz, semi_xy, smoother, elem_size);
+    if (finest < 0) return -1;
+    return finest + 1 <= levels - 2 ? finest + 1 : finest;
+}
+
 // ---- which level-0 shapes the marching tile of mg_o4.hip takes (launch_o4_*); the plain form takes every other one ----
 // 3-D, and a row holds at least 16 full 16-byte vectors: with fewer, three quarters of a wave's 64 lanes own no node and
 // the one-thread-per-node form has more of the chip at work. Pure; tests/test_o4_cpu.py pins it.

@@ -157,6 +157,36 @@ void launch_coarse_solve(hipStream_t s, const Geom &g, const Coef<T> &c, T omega
                          T *x, T *tmp, const T *rhs, int maxit, double tol, int fixed,
                          CoarseOut *d_out, bool x_is_zero = false);
 
+// ---- the one-launch LDS sub-cycle (mg_subcycle.hip, driven by Solver::subcycle_launch_t) ----
+// One workgroup runs cyc(root, kind) of the V / W / F recursion (mg_desc.h) on the resident levels root .. levels - 1 --
+// followed, when `second` is set, by the second visit of the root its parent makes (W: another W-cycle, F: a V-cycle) --
+// out of LDS as mg::subcycle_plan laid it out. Index k is level root + k.
+template <typename T>
+struct SubcycleArgs {
+    int nres;                                                   // resident levels
+    int nx[SUBCYCLE_MAX_LEVELS], ny[SUBCYCLE_MAX_LEVELS], nz[SUBCYCLE_MAX_LEVELS];
+    int off[SUBCYCLE_MAX_LEVELS][3];                            // byte offsets of u, t, b in dynamic LDS
+    Coef<T> c[SUBCYCLE_MAX_LEVELS];
+    Geom groot;                                                 // the root level as it lies in HBM
+    T omega;
+    int smoother;                                               // 1: Jacobi, 2: red-black
+    int nu_pre, nu_post;
+    int restriction;                                            // enum mg_restriction
+    int kind;                                                   // MG_CYCLE_V / W / F
+    int second;                                                 // the parent's second visit of the root too
+    int u_zero;                                                 // U(root) starts from zero and is not read
+    int maxit, fixed;                                           // the coarsest solve, as launch_coarse_solve takes them
+    double tol;
+    T *u;                                                       // U(root), local plane 0
+    const T *rhs;                                               // RHS(root)
+    CoarseOut *out;                                             // iterations summed, flags or-ed, the last solve's norms
+};
+// false: the runtime refused the kernel its LDS (nothing was launched)
+template <typename T>
+bool launch_subcycle(hipStream_t s, const SubcycleArgs<T> &a, int dim, size_t lds_bytes);
+// acc += cur as mg_cycle_stats reports a W / F cycle (one thread)
+void launch_coarse_accum(hipStream_t s, CoarseOut *acc, const CoarseOut *cur);
+
 // ---- flexible conjugate gradients on level 0 (mg_krylov.hip, driven by Solver::pcg_t) ----
 // Scalars of the iteration, resident on the device: the tails write them, the vector kernels read them. bad != 0 (a
 // breakdown: gamma <= 0, p.q <= 0 or a scalar that is not finite) makes every later launch return without writing.

@@ -27,63 +27,6 @@ namespace {
 constexpr int BX = 64;  // one wave64 spans 64 consecutive x
 constexpr int BY = 4;   // 4 waves per workgroup, stacked in y
 
-__device__ __forceinline__ bool on_boundary(const Geom &g, int z, int y, int x)
-{
-    // reference src/domain.cpp:20-23, extended to the slab-decomposed z axis
-    bool b = (x == 0) | (y == 0) | (x == g.nx - 1) | (y == g.ny - 1);
-    if (g.dim == 3) {
-        int gz = g.gz0 + z;
-        b |= (gz == 0) | (gz == g.gnz - 1);
-    }
-    return b;
-}
-
-template <typename T, int DIM>
-__device__ __forceinline__ T offdiag_sum(const T *u, long long i, int pitch,
-                                         long long plane, const Coef<T> &c)
-{
-    T sum = 0;
-    if (DIM == 3) sum += c.cz * u[i - plane];
-    sum += c.cy * u[i - pitch];
-    sum += c.cx * u[i - 1];
-    sum += c.cx * u[i + 1];
-    sum += c.cy * u[i + pitch];
-    if (DIM == 3) sum += c.cz * u[i + plane];
-    return sum;
-}
-
-template <typename T, int DIM>
-__device__ __forceinline__ T full_sum(const T *u, long long i, int pitch,
-                                      long long plane, const Coef<T> &c)
-{
-    // Residual: diagonal included, in row order (solvers.hpp:269-271)
-    T sum = 0;
-    if (DIM == 3) sum += c.cz * u[i - plane];
-    sum += c.cy * u[i - pitch];
-    sum += c.cx * u[i - 1];
-    sum += c.cd * u[i];
-    sum += c.cx * u[i + 1];
-    sum += c.cy * u[i + pitch];
-    if (DIM == 3) sum += c.cz * u[i + plane];
-    return sum;
-}
-
-template <typename T, int DIM, bool DAMPED>
-__device__ __forceinline__ T point_update(const Geom &g, const Coef<T> &c, T omega,
-                                          const T *u, const T *rhs, int z, int y, int x)
-{
-    long long i = lidx(g, z, y, x);
-    T b = rhs[i];
-    if (on_boundary(g, z, y, x)) return b;  // (b - 0) / 1
-    T sum = offdiag_sum<T, DIM>(u, i, g.pitch, g.plane, c);
-    T jac = div_cd<T>(b - sum, c);
-    if (DAMPED) {
-        T uc = u[i];
-        return uc + omega * (jac - uc);
-    }
-    return jac;
-}
-
 // ---------------------------------------------------------------- Jacobi (generic)
 template <typename T, int DIM, bool DAMPED>
 __global__ __launch_bounds__(BX *BY) void k_jacobi(Geom g, Coef<T> c, T omega,
@@ -193,52 +136,10 @@ __global__ __launch_bounds__(BX *BY) void k_restrict_fw(Geom gf, Geom gc,
     int y = blockIdx.y * BY + threadIdx.y;
     int z = blockIdx.z;
     if (x >= gc.nx || y >= gc.ny) return;
-    int fz = (DIM == 3) ? (WZ ? 2 * (gc.gz0 + z) - gf.gz0 : z) : 0;
-    long long fi = lidx(gf, fz, 2 * y, 2 * x);
-    T out;
-    if (on_boundary(gc, z, y, x)) {
-        out = fine[fi];
-    } else {
-        const T q = (T)0.25, hlf = (T)0.5;
-        T zacc[3];
-#pragma unroll
-        for (int dz = 0; dz < (WZ ? 3 : 1); dz++) {
-            long long oz = WZ ? (long long)(dz - 1) * gf.plane : 0;
-            T yacc[3];
-#pragma unroll
-            for (int dy = 0; dy < 3; dy++) {
-                const T *p = fine + fi + oz + (long long)(dy - 1) * gf.pitch;
-                yacc[dy] = q * p[-1] + hlf * p[0] + q * p[1];
-            }
-            zacc[dz] = q * yacc[0] + hlf * yacc[1] + q * yacc[2];
-        }
-        out = WZ ? q * zacc[0] + hlf * zacc[1] + q * zacc[2] : zacc[0];
-    }
+    const T out = restrict_fw_point<T, DIM, WZ>(gf, gc, fine, z, y, x);
     coarse[lidx(gc, z, y, x)] = out;
 }
 
-// Interpolated value at fine node (zf,yf,xf), built in the reference's phase order
-// (src/multigrid.cpp:3-27; slow axis first, fast axis last) so that every fine node
-// gets bit for bit what the in-place sequential phases produce.
-// DIM == 23: 3-D semi-coarsening (planes map one to one, gzf is then the LOCAL plane index)
-template <typename T, int DIM>
-__device__ __forceinline__ T interp_z(const Geom &gc, const T *__restrict__ c, int gzf, int yc,
-                                      int xc)
-{
-    if (DIM == 2) return c[lidx(gc, 0, yc, xc)];
-    if (DIM == 23) return c[lidx(gc, gzf, yc, xc)];
-    if ((gzf & 1) == 0) return c[lidx(gc, (gzf >> 1) - gc.gz0, yc, xc)];
-    int k0 = ((gzf - 1) >> 1) - gc.gz0;
-    return (T)0.5 * (c[lidx(gc, k0, yc, xc)] + c[lidx(gc, k0 + 1, yc, xc)]);
-}
-template <typename T, int DIM>
-__device__ __forceinline__ T interp_y(const Geom &gc, const T *__restrict__ c, int gzf, int yf,
-                                      int xc)
-{
-    if ((yf & 1) == 0) return interp_z<T, DIM>(gc, c, gzf, yf >> 1, xc);
-    return (T)0.5 * (interp_z<T, DIM>(gc, c, gzf, (yf - 1) >> 1, xc) +
-                     interp_z<T, DIM>(gc, c, gzf, (yf + 1) >> 1, xc));
-}
 template <typename T, int DIM, bool ADD>
 __global__ __launch_bounds__(BX *BY) void k_prolong(Geom gc, Geom gf,
                                                     const T *__restrict__ coarse,
@@ -248,11 +149,7 @@ __global__ __launch_bounds__(BX *BY) void k_prolong(Geom gc, Geom gf,
     int y = blockIdx.y * BY + threadIdx.y;
     int z = blockIdx.z;
     if (x >= gf.nx || y >= gf.ny) return;
-    int gzf = (DIM == 23) ? z : gf.gz0 + z;
-    T v;
-    if ((x & 1) == 0) v = interp_y<T, DIM>(gc, coarse, gzf, y, x >> 1);
-    else v = (T)0.5 * (interp_y<T, DIM>(gc, coarse, gzf, y, (x - 1) >> 1) +
-                       interp_y<T, DIM>(gc, coarse, gzf, y, (x + 1) >> 1));
+    const T v = prolong_point<T, DIM>(gc, gf, coarse, z, y, x);
     long long i = lidx(gf, z, y, x);
     if (ADD) fine[i] += v; else fine[i] = v;
 }
@@ -267,43 +164,6 @@ __global__ __launch_bounds__(BX *BY) void k_correct(Geom g, T *__restrict__ u, T
     long long i = lidx(g, z, y, x);
     u[i] += e[i];
     e[i] = 0;
-}
-
-// ---------------------------------------------------------------- single-workgroup sweeps
-// Device-side sweeps executed by ONE workgroup of 1024 threads (coarsest grid,
-// and the bit-faithful lexicographic GS on any level). Each ends with a barrier.
-constexpr int SWG = 1024;
-
-template <typename T, int DIM, bool DAMPED>
-__device__ void wg_jacobi(const Geom &g, const Coef<T> &c, T omega, const T *u, const T *rhs,
-                          T *out)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    for (long long q = threadIdx.x; q < total; q += SWG) {
-        int z = (int)(q / npl);
-        int rem = (int)(q - (long long)z * npl);
-        int y = rem / g.nx, x = rem - y * g.nx;
-        out[lidx(g, z, y, x)] = point_update<T, DIM, DAMPED>(g, c, omega, u, rhs, z, y, x);
-    }
-    __syncthreads();
-}
-
-template <typename T, int DIM>
-__device__ void wg_rbgs(const Geom &g, const Coef<T> &c, T *u, const T *rhs)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    for (int colour = 0; colour < 2; colour++) {
-        for (long long q = threadIdx.x; q < total; q += SWG) {
-            int z = (int)(q / npl);
-            int rem = (int)(q - (long long)z * npl);
-            int y = rem / g.nx, x = rem - y * g.nx;
-            if (((x + y + g.gz0 + z) & 1) != colour) continue;
-            u[lidx(g, z, y, x)] = point_update<T, DIM, false>(g, c, (T)1, u, rhs, z, y, x);
-        }
-        __syncthreads();
-    }
 }
 
 // Lexicographic Gauss-Seidel (solvers.hpp:33-48) as anti-diagonal wavefronts:
@@ -480,43 +340,6 @@ __global__ __launch_bounds__(SWG) void k_gs_lex2d_rows_pair(Geom g, Coef<T> c, T
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
         }
     }
-}
-
-template <typename T, int DIM>
-__device__ double wg_residual_sumsq(const Geom &g, const Coef<T> &c, const T *u, const T *rhs,
-                                    double *sh)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    double sq = 0.;
-    for (long long q = threadIdx.x; q < total; q += SWG) {
-        int z = (int)(q / npl);
-        int rem = (int)(q - (long long)z * npl);
-        int y = rem / g.nx, x = rem - y * g.nx;
-        long long i = lidx(g, z, y, x);
-        T sum;
-        if (on_boundary(g, z, y, x)) sum = (T)1 * u[i];
-        else sum = full_sum<T, DIM>(u, i, g.pitch, g.plane, c);
-        T res = rhs[i] - sum;
-        sq += (double)res * (double)res;
-    }
-    return block_sum_bcast(sq, sh);
-}
-
-template <typename T>
-__device__ double wg_sumsq(const Geom &g, const T *v, double *sh)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    double sq = 0.;
-    for (long long q = threadIdx.x; q < total; q += SWG) {
-        int z = (int)(q / npl);
-        int rem = (int)(q - (long long)z * npl);
-        int y = rem / g.nx, x = rem - y * g.nx;
-        double t = (double)v[lidx(g, z, y, x)];
-        sq += t * t;
-    }
-    return block_sum_bcast(sq, sh);
 }
 
 template <typename T, int DIM>

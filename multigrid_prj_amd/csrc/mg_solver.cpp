@@ -32,7 +32,7 @@ int validate_desc(const mg_desc *d, std::string *why)
     if ((d->n - 1) / step + 1 < 3) return fail("coarsest grid would have fewer than 3 nodes per side");
     if (d->dtype != MG_F64 && d->dtype != MG_F32) return fail("dtype must be MG_F64 or MG_F32");
     if (d->smoother < MG_SMOOTH_GS_LEX || d->smoother > MG_SMOOTH_ZEBRA_X) return fail("unknown smoother");
-    if (d->cycle != MG_CYCLE_SAWTOOTH && d->cycle != MG_CYCLE_V) return fail("unknown cycle kind");
+    if (d->cycle != MG_CYCLE_SAWTOOTH && !is_vwf(d->cycle)) return fail("unknown cycle kind");
     if (d->restriction != MG_RESTRICT_INJECT && d->restriction != MG_RESTRICT_FULLW) return fail("unknown restriction");
     if (d->coarse_mode != MG_COARSE_TOL && d->coarse_mode != MG_COARSE_FIXED) return fail("unknown coarse mode");
     if (!(d->length > 0) || !(d->alpha > 0)) return fail("length and alpha must be positive");
@@ -175,6 +175,7 @@ Solver::~Solver()
     if (d_partials_) (void)hipFree(d_partials_);
     if (d_scal_) (void)hipFree(d_scal_);
     if (d_coarse_) (void)hipFree(d_coarse_);
+    if (d_coarse_acc_) (void)hipFree(d_coarse_acc_);
     if (h_scal_) (void)hipHostFree(h_scal_);
     if (h_coarse_) (void)hipHostFree(h_coarse_);
     if (h_fixed_) (void)hipHostFree(h_fixed_);
@@ -299,6 +300,22 @@ int Solver::init()
     MG_HIP(hipMalloc((void **)&d_coarse_, sizeof(CoarseOut)));
     MG_HIP(hipMemsetAsync(d_scal_, 0, sizeof(double) * SC_COUNT, stream_));
     MG_HIP(hipMemsetAsync(d_coarse_, 0, sizeof(CoarseOut), stream_));
+    MG_HIP(hipMalloc((void **)&d_coarse_acc_, sizeof(CoarseOut)));
+    MG_HIP(hipMemsetAsync(d_coarse_acc_, 0, sizeof(CoarseOut), stream_));
+    // The LDS sub-cycle (mg_subcycle.hip). MG_SUBCYCLE_LEVEL = -1: W and F handles give it subcycle_default_root (the
+    // fastest of tools/cycle_kinds_times.py), V handles keep their launches; k >= 1: root k for every kind when admissible.
+    sub_root_ = -1;
+    if (nranks_ == 1 && is_vwf(d_.cycle)) {
+        if (sw_.subcycle_level == -1) {
+            if (d_.cycle != MG_CYCLE_V) {
+                int nx[16], ny[16], nz[16];
+                for (int l = 0; l < d_.levels; l++) { nx[l] = lv_[l].g.nx; ny[l] = lv_[l].g.ny; nz[l] = lv_[l].g.nz; }
+                sub_root_ = subcycle_default_root(d_.levels, nx, ny, nz, d_.semi_xy, d_.smoother, (int)esize());
+            }
+        } else if (sw_.subcycle_level >= 1 && sw_.subcycle_level < d_.levels && subcycle_plan_of(sw_.subcycle_level).root >= 0) {
+            sub_root_ = sw_.subcycle_level;
+        }
+    }
     MG_HIP(hipHostMalloc((void **)&h_scal_, sizeof(double) * SC_COUNT));
     MG_HIP(hipHostMalloc((void **)&h_coarse_, sizeof(CoarseOut)));
     MG_HIP(hipHostMalloc((void **)&h_fixed_, sizeof(CoarseOut)));
@@ -1377,7 +1394,7 @@ int Solver::coarse_level_t(int l, int ax, int ar, bool x_zero)
     if (x_zero && ((big && d_.coarse_mode == MG_COARSE_FIXED) || L.dist)) { MG_TRY(zero_array(ax, l)); x_zero = false; }
     if (big && d_.coarse_mode == MG_COARSE_FIXED) {
         MG_TRY(smooth_t<T>(l, coarse_smoother_of(d_.smoother), d_.coarse_maxit, ax, ar, false, -1,
-                           d_.cycle == MG_CYCLE_V));
+                           is_vwf(d_.cycle)));
         h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
         h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;  // not evaluated on this path
         MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
@@ -1396,14 +1413,20 @@ int Solver::coarse_level_t(int l, int ax, int ar, bool x_zero)
 // 0..T_ are distributed (halo exchanges happen inside smooth_t / residual_t / restrict_t /
 // prolong_t), the residual of level T_ is gathered on rank 0, which runs the deeper levels
 // alone and scatters the prolonged correction back.
+// kind W / F (single GPU): the same level code, the child visited twice (visit_child_t); a second visit enters with
+// u_zero == false, so the zero-guess shortcuts (small_pre, the flag of the first sweep) apply to first visits only.
 template <typename T>
-int Solver::vcycle_rec_t(int l, bool u_zero)
+int Solver::vcycle_rec_t(int l, bool u_zero, int kind)
 {
     const int L = d_.levels;
     const bool mine = lv_[l].present;
     bool fold = false;  // prolong-add folded into the post-smoothing pair
     bool fold_slab = false;  // ... on the pieces of a slab: u itself stays as the residual + restriction saw it
-    if (l == L - 1) return coarse_level_t<T>(l, MG_ARR_U, MG_ARR_RHS, u_zero);
+    if (l == L - 1) {
+        MG_TRY(coarse_level_t<T>(l, MG_ARR_U, MG_ARR_RHS, u_zero));
+        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
+        return MG_OK;
+    }
     // fused residual + full weighting when both levels live whole on this rank
     const bool fuse_rr = mine && d_.restriction == MG_RESTRICT_FULLW && !lv_[l].dist && lv_[l + 1].present &&
                          resid_restrict_fast_ok<T>(lv_[l].g, lv_[l + 1].g);
@@ -1423,9 +1446,7 @@ int Solver::vcycle_rec_t(int l, bool u_zero)
         launch_small_pre_rr<T>(stream_, lv_[l].g, lv_[l + 1].g, coef_of<T>(lv_[l]), (T)d_.omega, ptr<T>(MG_ARR_RHS, l),
                                ptr<T>(MG_ARR_U, l), ptr<T>(MG_ARR_RHS, l + 1));
         MG_HIP(hipGetLastError());
-        const bool skip0 = can_skip_zeroing<T>(l + 1) || l + 1 == L - 1;   // the coarsest-grid solver takes the zero guess as a flag
-        if (!skip0) MG_TRY(zero_array(MG_ARR_U, l + 1));
-        MG_TRY(vcycle_rec_t<T>(l + 1, skip0));
+        MG_TRY(visit_child_t<T>(l + 1, kind));
     } else if (mine) {
         if (l == 0 && fine_pre_done_ > 0) {   // Solver::solve ran (the first sweeps of) this level's pre-smoothing with the norm
             const int left = d_.nu_pre - fine_pre_done_;
@@ -1450,9 +1471,7 @@ int Solver::vcycle_rec_t(int l, bool u_zero)
         if (prof) MG_TRY(prof_end(l, MG_PROF_RESID_RESTRICT, 1, fuse_rr_slab ? 1 : 2));
         MG_TRY(gather_S(MG_ARR_RHS));
         if (lv_[l + 1].present) {
-            const bool skip0 = can_skip_zeroing<T>(l + 1) || l + 1 == L - 1;
-            if (!skip0) MG_TRY(zero_array(MG_ARR_U, l + 1));
-            MG_TRY(vcycle_rec_t<T>(l + 1, skip0));
+            MG_TRY(visit_child_t<T>(l + 1, kind));
         }
         if (fuse_rr_slab && can_fold_prolong_replicated<T>(l)) {
             fold = fold_slab = true;   // the post-smoothing pair reads the correction from the replicated level's own array
@@ -1475,9 +1494,7 @@ int Solver::vcycle_rec_t(int l, bool u_zero)
             MG_TRY(restrict_t<T>(l, d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
         }
         if (prof) MG_TRY(prof_end(l, MG_PROF_RESID_RESTRICT, 1, (fuse_rr || fuse_rr_slab) ? 1 : 2));   // the slab-fused form is ONE segment (exchange + interior + boundary launches), like the pair
-        const bool skip0 = can_skip_zeroing<T>(l + 1) || l + 1 == L - 1;   // the coarsest-grid solver takes the zero guess as a flag
-        if (!skip0) MG_TRY(zero_array(MG_ARR_U, l + 1));
-        MG_TRY(vcycle_rec_t<T>(l + 1, skip0));
+        MG_TRY(visit_child_t<T>(l + 1, kind));
         fold_slab = can_fold_prolong_slab<T>(l);
         fold = can_fold_prolong<T>(l) || fold_slab;
         if (!fold && !small) {
@@ -1498,13 +1515,100 @@ int Solver::vcycle_rec_t(int l, bool u_zero)
     return MG_OK;
 }
 
+template <typename T>
+int Solver::visit_child_t(int l1, int kind)
+{
+    const int L = d_.levels;
+    if (l1 == sub_root_ && !stage_fn_) return subcycle_launch_t<T>(l1, kind, true, true);
+    const bool skip0 = can_skip_zeroing<T>(l1) || l1 == L - 1;   // the coarsest-grid solver takes the zero guess as a flag
+    if (!skip0) MG_TRY(zero_array(MG_ARR_U, l1));
+    MG_TRY(vcycle_rec_t<T>(l1, skip0, kind));
+    if (l1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(vcycle_rec_t<T>(l1, false, MG_CYCLE_W));   // continues from U(l1), RHS(l1) unchanged
+    if (l1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(vcycle_rec_t<T>(l1, false, MG_CYCLE_V));
+    return MG_OK;
+}
+
+SubcyclePlan Solver::subcycle_plan_of(int root) const
+{
+    int nx[16], ny[16], nz[16];
+    for (int l = 0; l < d_.levels; l++) { nx[l] = lv_[l].g.nx; ny[l] = lv_[l].g.ny; nz[l] = lv_[l].g.nz; }
+    if (nranks_ > 1) { SubcyclePlan p{}; p.root = -1; return p; }
+    return subcycle_plan(d_.levels, nx, ny, nz, d_.semi_xy, d_.smoother, (int)esize(), root);
+}
+
+// cyc(root, kind) -- and with `second` the parent's second visit of the root -- in ONE launch (mg_subcycle.hip). The
+// kernel's CoarseOut lands in d_coarse_ like a coarse solve's.
+template <typename T>
+int Solver::subcycle_launch_t(int root, int kind, bool second, bool u_zero)
+{
+    pair_on_comm_level_ = -1;
+    const SubcyclePlan p = subcycle_plan_of(root);
+    if (p.root != root) { set_last_error("the LDS sub-cycle does not admit this root level"); return MG_ERR_BAD_ARG; }
+    SubcycleArgs<T> a{};
+    a.nres = p.nres;
+    for (int k = 0; k < p.nres; k++) {
+        const Level &Lk = lv_[root + k];
+        a.nx[k] = Lk.g.nx; a.ny[k] = Lk.g.ny; a.nz[k] = Lk.g.nz;
+        for (int w = 0; w < 3; w++) a.off[k][w] = (int)p.off[k][w];
+        a.c[k] = coef_of<T>(Lk);
+    }
+    a.groot = lv_[root].g;
+    a.omega = (T)d_.omega;
+    a.smoother = d_.smoother;
+    a.nu_pre = d_.nu_pre; a.nu_post = d_.nu_post;
+    a.restriction = d_.restriction;
+    a.kind = kind;
+    a.second = second ? 1 : 0;
+    a.u_zero = u_zero ? 1 : 0;
+    a.maxit = lock_iters_ >= 0 ? lock_iters_ : d_.coarse_maxit;
+    a.fixed = (lock_iters_ >= 0 || d_.coarse_mode == MG_COARSE_FIXED) ? 1 : 0;
+    a.tol = d_.coarse_tol;
+    a.u = ptr<T>(MG_ARR_U, root);
+    a.rhs = ptr<T>(MG_ARR_RHS, root);
+    a.out = d_coarse_;
+    if (!launch_subcycle<T>(stream_, a, d_.dim, (size_t)p.lds_bytes)) {
+        set_last_error("the LDS sub-cycle kernel was refused its shared memory");
+        return MG_ERR_HIP;
+    }
+    MG_HIP(hipGetLastError());
+    if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
+    return MG_OK;
+}
+
+int Solver::stats_begin()
+{
+    MG_HIP(hipMemsetAsync(d_coarse_acc_, 0, sizeof(CoarseOut), stream_));
+    acc_stats_ = true;
+    return MG_OK;
+}
+
+int Solver::stats_end()
+{
+    acc_stats_ = false;
+    MG_HIP(hipMemcpyAsync(d_coarse_, d_coarse_acc_, sizeof(CoarseOut), hipMemcpyDeviceToDevice, stream_));
+    return MG_OK;
+}
+
+// One cycle of the descriptor's kind started on level l. W and F make several coarse solves: their statistics are summed on
+// the device (launch_coarse_accum) and d_coarse_ holds the sum afterwards, so every reader of d_coarse_ works unchanged.
+template <typename T>
+int Solver::cycle_from_t(int l)
+{
+    if (d_.cycle == MG_CYCLE_V) return vcycle_rec_t<T>(l);
+    MG_TRY(stats_begin());
+    const int rc = vcycle_rec_t<T>(l, false, d_.cycle);
+    acc_stats_ = false;
+    MG_TRY(rc);
+    return stats_end();
+}
+
 // Enqueues one cycle; no host synchronisation inside (RCCL transport).
 template <typename T>
 int Solver::cycle_enqueue_t()
 {
     pair_on_comm_level_ = -1;
     const int L = d_.levels;
-    if (d_.cycle == MG_CYCLE_V) return vcycle_rec_t<T>(0);
+    if (is_vwf(d_.cycle)) return cycle_from_t<T>(0);
     // --- reference sawtooth, include/multigrid.hpp:126-145 ---
     // :127  sol * RES : fine residual into `res`, sum r^2
     MG_TRY(residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, MG_ARR_RES, true));
@@ -1573,7 +1677,7 @@ template <typename T>
 bool Solver::pair_norm_ok() const
 {
     const Level &L = lv_[0];
-    if (!switches().pair_norm || d_.cycle != MG_CYCLE_V || d_.levels <= 1 || d_.outer_pre_gs != 0 || stage_fn_ || profiling_ || !L.present) return false;
+    if (!switches().pair_norm || !is_vwf(d_.cycle) || d_.levels <= 1 || d_.outer_pre_gs != 0 || stage_fn_ || profiling_ || !L.present) return false;
     if (L.dist) {   // z-slabs: the Jacobi pair on the whole slab (two ghost planes), wide enough on the thinnest slab of all ranks
         const Geom gs = slab_gate_geom(L);
         const bool sm = (d_.smoother == MG_SMOOTH_JACOBI && d_.nu_pre == 2) || (d_.smoother == MG_SMOOTH_RBGS && d_.nu_pre >= 1 && switches().fused_rb);
@@ -1725,7 +1829,9 @@ int Solver::timer_stop(double *ms)
     template int Solver::sumsq_t<T>(int, int);                                              \
     template int Solver::restrict_t<T>(int, int, int, int);                                 \
     template int Solver::coarse_level_t<T>(int, int, int, bool);                            \
-    template int Solver::vcycle_rec_t<T>(int, bool);
+    template int Solver::vcycle_rec_t<T>(int, bool, int); \
+    template int Solver::cycle_from_t<T>(int); \
+    template int Solver::subcycle_launch_t<T>(int, int, bool, bool);
 MG_INSTANTIATE_FOR_DRIVERS(double)
 MG_INSTANTIATE_FOR_DRIVERS(float)
 #undef MG_INSTANTIATE_FOR_DRIVERS

@@ -1,9 +1,9 @@
 // mg_solver.h -- host-side owner of the HBM-resident grid hierarchy behind the C-ABI of include/mg_hip.h. One class, two
 // translation units: mg_solver.cpp holds the hierarchy, the communication, the per-operator launch paths and the cycle
-// (vcycle_rec_t, cycle_enqueue*, cycle); mg_drivers.cpp holds what calls the cycle from above (solve, pcg_*, fmg*, mixed_*,
-// set_shift, heat_*) and the helpers those drivers share.
+// (vcycle_rec_t for the V, W and F kinds, visit_child_t, subcycle_launch_t, cycle_from_t, cycle_enqueue*, cycle); mg_drivers.cpp
+// holds what calls the cycle from above (solve, pcg_*, fmg*, subcycle, mixed_*, set_shift, heat_*) and the helpers those drivers share.
 // The member templates that mg_drivers.cpp calls and mg_solver.cpp defines (smooth_t, pair_norm_ok, residual_t, sumsq_t,
-// restrict_t, coarse_level_t, vcycle_rec_t) cross the file boundary by ONE mechanism: explicit instantiation definitions
+// restrict_t, coarse_level_t, vcycle_rec_t, cycle_from_t, subcycle_launch_t) cross the file boundary by ONE mechanism: explicit instantiation definitions
 // for double and float, in one block at the end of mg_solver.cpp.
 #ifndef MG_SOLVER_H
 #define MG_SOLVER_H
@@ -52,6 +52,8 @@ int plan_stage(const mg_desc &d, int nranks, int rank, SlabPlan *out, std::strin
 constexpr int NUM_ARR = 5;
 
 inline bool is_zebra(int smoother) { return smoother == MG_SMOOTH_ZEBRA_Y || smoother == MG_SMOOTH_ZEBRA_X; }
+// the cycles of the V-cycle's recursion (every level holds a solution, not an error): V, W and F
+inline bool is_vwf(int cycle) { return cycle == MG_CYCLE_V || cycle == MG_CYCLE_W || cycle == MG_CYCLE_F; }
 
 struct Level {
     Geom g{};
@@ -109,6 +111,10 @@ public:
     int fmg(int cycles_per_level, mg_fmg_stats *st);
     // arr_dst(l) = Pi arr_src(l + 1), Dirichlet nodes from arr_bnd(l) (< 0: interpolated too) (mg_fmg_prolong)
     int fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd);
+    // one cyc(level, kind) on U(level), RHS(level): launch by launch (path 0) or by the LDS kernel rooted there (path 1)
+    int subcycle(int level, int kind, int path, mg_cycle_stats *st);
+    // root level the handle's cycles hand to the LDS kernel, -1: none
+    int subcycle_root() const { return stage_fn_ ? -1 : sub_root_; }
     // mixed-precision defect correction: fp64 u / b of level 0 beside an MG_F32 hierarchy (mg_mixed_*); the fp64 arrays are
     // allocated by the first mixed_set_*
     int mixed_set(bool rhs, const double *host);
@@ -240,7 +246,20 @@ private:
     int device_check(const char *fn, const void *dense, int dense_dtype, const Geom &g);
     int krylov_scalars_alloc();
     int krylov_alloc();
-    template <typename T> int vcycle_rec_t(int l, bool u_zero = false);
+    // cyc(l, kind) of mg_desc.h; kind V is the V-cycle, launch for launch what it was before W and F existed
+    template <typename T> int vcycle_rec_t(int l, bool u_zero = false, int kind = MG_CYCLE_V);
+    // what a level does with its child l1: U(l1) = 0, cyc(l1, kind) and the second visit W / F make -- by launches, or by
+    // one launch of the LDS kernel when l1 is the handle's sub-cycle root
+    template <typename T> int visit_child_t(int l1, int kind);
+    // one cycle of the descriptor's kind (V / W / F) started on level l, the W / F statistics accumulated into d_coarse_
+    template <typename T> int cycle_from_t(int l);
+    template <typename T> int subcycle_launch_t(int root, int kind, bool second, bool u_zero);
+    SubcyclePlan subcycle_plan_of(int root) const;   // mg::subcycle_plan on this handle's hierarchy (single GPU)
+    int sub_root_ = -1;               // level the cycles hand to the LDS kernel (MG_SUBCYCLE_LEVEL, init()); -1: none
+    CoarseOut *d_coarse_acc_ = nullptr;   // W / F: the cycle's coarse solves summed up (launch_coarse_accum)
+    bool acc_stats_ = false;          // a W / F cycle is being enqueued: every coarse solve is added to d_coarse_acc_
+    int stats_begin();                // clears d_coarse_acc_, sets acc_stats_
+    int stats_end();                  // d_coarse_ = d_coarse_acc_, clears acc_stats_
     int cycle_enqueue();
     bool check_arr(int which, int level, const char *fn) const;
     int zebra_tabulate(Level &L);   // the level's zebra line factors from its current coefficients -> L.zebra

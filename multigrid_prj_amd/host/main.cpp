@@ -26,7 +26,7 @@ int main(int argc, char **argv)
     d.omega = opt.omega;
     if (opt.fp32) d.dtype = MG_F32;
     if (opt.vcycle) {
-        d.cycle = MG_CYCLE_V;
+        d.cycle = opt.cycle_kind;   // MG_CYCLE_V / _W / _F
         d.nu_pre = opt.nu1;
         d.nu_post = opt.nu2 >= 0 ? opt.nu2 : 2;
         d.outer_pre_gs = 0;

@@ -35,7 +35,7 @@ void usage()
               << "  -smt, you can choose your favourite smoother" << std::endl
               << "  --help, Display this help message" << std::endl
               << "MI355X extensions:" << std::endl
-              << "  -dim 2|3, -cycle saw|v, -omega W, -nu1 K, -nu2 K, -rbgs, -zebra, -zebrax, -anisox A, -anisoy A, -fw, -coarse_fixed K, -fp32, -maxit K, -cold, -eps E, -semi K" << std::endl;
+              << "  -dim 2|3, -cycle saw|v|w|f, -omega W, -nu1 K, -nu2 K, -rbgs, -zebra, -zebrax, -anisox A, -anisoy A, -fw, -coarse_fixed K, -fp32, -maxit K, -cold, -eps E, -semi K" << std::endl;
 }
 
 }  // namespace
@@ -90,7 +90,11 @@ void Utils::parse_command_line(int argc, char **argv, Options &o)
         }
         // ---- extensions ----
         else if (a == "-dim" && has_value) { o.dim = std::atoi(argv[i + 1]); if (o.dim != 2 && o.dim != 3) fail("-dim must be 2 or 3"); }
-        else if (a == "-cycle" && has_value) { o.vcycle = std::string(argv[i + 1]) == "v"; }
+        else if (a == "-cycle" && has_value) {
+            const std::string k = argv[i + 1];
+            o.vcycle = k == "v" || k == "w" || k == "f";   // every other spelling: the reference's sawtooth
+            o.cycle_kind = k == "w" ? 2 : k == "f" ? 3 : 1;
+        }
         else if (a == "-omega" && has_value) { o.omega = std::atof(argv[i + 1]); }
         else if (a == "-nu1" && has_value) { o.nu1 = std::atoi(argv[i + 1]); }
         else if (a == "-nu2" && has_value) { o.nu2 = std::atoi(argv[i + 1]); }
