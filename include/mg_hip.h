@@ -437,6 +437,75 @@ typedef struct mg_heat_stats {
 int mg_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
 int mg_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst);
 
+/* ---- lowest eigenpairs by multigrid-preconditioned LOBPCG ----
+ * mg_eig_solve finds the nev smallest eigenpairs of sigma I + A on the interior nodes of level 0, (sigma I + A) x =
+ * lambda x with x = 0 on Dirichlet nodes -- the operator of mg_level_coefficients(h, 0): aniso, the current shift
+ * (mg_set_shift) and grids that are not 2^k + 1 included -- by LOBPCG (Knyazev 2001) on a block of m >= nev vectors.
+ * The preconditioner is M = one outer iteration of mg_solve from zero (outer_pre_gs sweeps + one cycle of the
+ * descriptor's kind), exactly mg_pcg_solve's.
+ *
+ * Each iteration: R_j = AX_j - theta_j X_j and relres_j = ||R_j|| / (|theta_j| ||X_j||); the columns with relres > tol are
+ * active (soft locking: the others stay in the Rayleigh-Ritz basis but get no W and no P); W_j = M R_j for the active
+ * columns, 0 on Dirichlet nodes; S = [X, W, P]; G = S^T S and H = S^T A S in double on the device; on the host in fp64 the
+ * m smallest eigenpairs of H c = theta G c (scaling by diag(G)^-1/2, Cholesky, cyclic Jacobi -- csrc/mg_dense.h); then
+ * X' = S Cx, P' = [W, P] Cp (X' without its X part), AX' and AP' likewise, in place. P is absent in the first iteration,
+ * after a restart -- a Cholesky pivot of the scaled G below 1e-10: P is dropped for that iteration and `restarts`
+ * counts it -- and in an iteration whose active set holds a column the previous one did not (a column that came back
+ * from the locked set has no P). The solve stops when columns 0 .. nev-1 all have relres <= tol; hist[k] is the largest
+ * of those nev values at iteration k (n_hist may exceed hist_cap: only hist_cap entries are written). With tol below
+ * the dtype's rounding floor, about eps_T |cd| / lambda_1, the loop runs to maxit.
+ *
+ * On return: lambda[0 .. m) ascending and relres[0 .. m), both recomputed from a fresh A X of the returned vectors (one
+ * apply, one Gram, one Rayleigh-Ritz rotation of the block), not the running recurrences; the X columns are orthonormal
+ * in the Euclidean inner product over the nodes of level 0 and exactly 0 on Dirichlet nodes.
+ * status: 0 converged, 1 maxit reached, 2 a Gram entry or norm is not finite or the block is rank-deficient (X is then
+ * the last block that was whole).
+ *
+ * State: the block lives in the handle -- six families of m level-0 arrays (enum mg_eig_family), allocated by the first
+ * call (or by mg_eig_set_vector), re-sized by a call with another m, kept until mg_destroy and counted by
+ * mg_device_bytes, beside a few MB of partial sums. A second call warm-starts from the X it finds. Columns nobody has
+ * set hold the default start: a hash (splitmix64) of the node's global index and the column, uniform in [-1, 1), which
+ * has no grid symmetry. mg_eig_set_vector(MG_EIG_X, j, ...) with j beyond the current block grows the block to j + 1.
+ * U(0) and RHS(0) are preserved bit for bit (the preconditioner works by swapping pointers into their slots); E, TMP,
+ * RES and the coarse levels are unspecified afterwards, as after mg_solve. Two host synchronisations per iteration: the
+ * stopping test / active set, and the dense problem. Two runs give the same bits.
+ *
+ * MG_ERR_BAD_ARG with nothing touched: m outside [1, MG_EIG_MAX_BLOCK], nev outside [1, m], m above the number of
+ * interior nodes, tol not positive and finite, maxit < 0, a bad history buffer, NULL lambda / relres, distributed handles
+ * (dry runs included), a stage callback installed, an unknown family, j outside the block, NULL handle. The device
+ * variants follow every rule of mg_set_array_device. */
+#define MG_EIG_MAX_BLOCK 8
+enum mg_eig_family { MG_EIG_X = 0, MG_EIG_AX = 1, MG_EIG_W = 2, MG_EIG_AW = 3, MG_EIG_P = 4, MG_EIG_AP = 5 };
+typedef struct mg_eig_stats {
+    int32_t iters;      /* LOBPCG iterations done                                        */
+    int32_t status;     /* 0 converged, 1 hit maxit, 2 a Gram entry / norm not finite    */
+    int32_t cycles;     /* preconditioner applications (= active columns summed over iterations) */
+    int32_t restarts;   /* iterations that dropped P because the basis Gram matrix was not safely positive definite */
+    double  max_relres; /* max over the first nev columns of the returned relres         */
+} mg_eig_stats;
+int mg_eig_solve(mg_handle h, int m, int nev, double tol, int maxit,
+                 double *lambda /*m*/, double *relres /*m*/,
+                 double *hist, int hist_cap, int *n_hist, mg_eig_stats *st);
+int mg_eig_set_vector(mg_handle h, int family, int j, const void *host);   /* dense, desc.dtype, usual layout */
+int mg_eig_get_vector(mg_handle h, int family, int j, void *host);
+int mg_eig_set_vector_device(mg_handle h, int family, int j, const void *dev, int dtype, void *stream);
+int mg_eig_get_vector_device(mg_handle h, int family, int j, void *dev, int dtype, void *stream);
+int mg_eig_block(mg_handle h, int *m);   /* block size currently allocated, 0: none */
+
+/* Kernel-level check of the two block kernels of mg_eig.hip on the handle's block of m = mg_eig_block columns.
+ * APPLY_GRAM: the first nw W columns and np P columns (np = 0 or nw) are active. AW_j = A W_j (row order of the
+ *             residual kernel, in T; W_j := 0 on Dirichlet nodes). G, H (s x s row-major doubles, s = m + nw + np) over
+ *             S = [X, W, P], AS = [AX, AW, AP]: G_ab = S_a . S_b and H_ab = S_a . AS_b for a <= b, both mirrored into
+ *             the lower triangle (H is symmetric when AS really is A S). Products and sums in double, fixed order.
+ * COMBINE:    coef = Cx (s x m) followed by Cp ((nw+np) x nw), row-major doubles; theta (m doubles). In place:
+ *             X' = S Cx, AX' = AS Cx, P' = [W, P] Cp, AP' = [AW, AP] Cp; each element starts at 0.0 in double, adds
+ *             (double) S_i * C_ij in the column order of S with every product and sum rounded, and is rounded once to T.
+ *             R into the W family's first m columns: r = ax' - (T) theta_j * x', in T. sums[j] = sum r_j^2 (m doubles).
+ * MG_ERR_BAD_ARG: no block, nw outside [0, m], np not 0 or nw, a NULL output, distributed handles. */
+enum mg_eig_kernel_kind { MG_EIG_K_APPLY_GRAM = 0, MG_EIG_K_COMBINE = 1 };
+int mg_eig_kernel(mg_handle h, int kernel, int nw, int np, const double *coef, const double *theta,
+                  double *G, double *H, double *sums);
+
 /* Debug stage dumps of the sawtooth cycle -- the reference's CREATE_GIF twin
  * (multigrid.hpp:160-316) writes `sol + err` sampled on the level being worked on after every
  * stage: before and after the coarse solve, after each interpolation, after each level's

@@ -194,6 +194,18 @@ public:
     mg_handle get() const { return h_; }
     size_t fine_n() const { return n0_; }
 
+    // mg_eig_solve on this hierarchy: the nev smallest eigenvalues of level 0's operator on a block of m vectors (the
+    // vectors stay in the handle: mg_eig_get_vector(get(), MG_EIG_X, j, ...)); relres (may be null) gets the m residuals
+    std::vector<double> eigenvalues(int m, int nev, double tol = 1e-8, int maxit = 200, std::vector<double> *relres = nullptr,
+                                    mg_eig_stats *stats = nullptr)
+    {
+        std::vector<double> lambda(m > 0 ? m : 1), rel(m > 0 ? m : 1);
+        mg_check(mg_eig_solve(h_, m, nev, tol, maxit, lambda.data(), rel.data(), nullptr, 0, nullptr, stats));
+        lambda.resize(m); rel.resize(m);
+        if (relres) *relres = rel;
+        return lambda;
+    }
+
     // level entries of a fine-size host vector (addressed like Domain::mask) <-> device array
     template <class Vector>
     void upload(int arr, int level, const Vector &v)

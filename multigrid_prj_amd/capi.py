@@ -25,6 +25,10 @@ PCG_CONVERGED, PCG_MAXIT, PCG_BREAKDOWN = 0, 1, 2
 MIXED_K_RESIDUAL, MIXED_K_CORRECT_RESIDUAL = 0, 1
 MIXED_CONVERGED, MIXED_MAXIT, MIXED_NOT_FINITE = 0, 1, 2
 O4_CONVERGED, O4_MAXIT, O4_NOT_FINITE = 0, 1, 2
+EIG_MAX_BLOCK = 8
+EIG_X, EIG_AX, EIG_W, EIG_AW, EIG_P, EIG_AP = 0, 1, 2, 3, 4, 5
+EIG_K_APPLY_GRAM, EIG_K_COMBINE = 0, 1
+EIG_CONVERGED, EIG_MAXIT, EIG_NOT_FINITE = 0, 1, 2
 
 
 class MgError(RuntimeError):
@@ -99,6 +103,13 @@ class MgHeatStats(C.Structure):
     _fields_ = [("steps", C.c_int32), ("cycles", C.c_int32), ("time", C.c_double), ("relres", C.c_double)]
 
 
+class MgEigStats(C.Structure):
+    """include/mg_hip.h::mg_eig_stats (mg_eig_solve)"""
+
+    _fields_ = [("iters", C.c_int32), ("status", C.c_int32), ("cycles", C.c_int32), ("restarts", C.c_int32),
+                ("max_relres", C.c_double)]
+
+
 def make_desc(dim=2, n=17, levels=2, dtype=MG_F64, length=10.0, alpha=1.0,
               cycle=CYCLE_SAWTOOTH, smoother=SMOOTH_JACOBI, omega=1.0, nu_pre=0, nu_post=5,
               restriction=RESTRICT_INJECT, coarse_mode=COARSE_TOL, coarse_maxit=2000,
@@ -141,6 +152,8 @@ EXPORTS = [
     "mg_mixed_set_rhs_device", "mg_mixed_set_solution_device", "mg_mixed_get_solution_device",
     "mg_o4_residual", "mg_o4_correct_residual", "mg_o4_solve",
     "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_set_source_device", "mg_heat_step", "mg_heat_rhs",
+    "mg_eig_solve", "mg_eig_set_vector", "mg_eig_get_vector", "mg_eig_set_vector_device", "mg_eig_get_vector_device",
+    "mg_eig_block", "mg_eig_kernel",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
 ]
@@ -210,6 +223,13 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_heat_set_source_device.argtypes = [vp, vp, i, vp]
     L.mg_heat_step.argtypes = [vp, C.c_double, C.c_double, i, i, C.POINTER(MgHeatStats)]
     L.mg_heat_rhs.argtypes = [vp, C.c_double, C.c_double, i, i]
+    L.mg_eig_solve.argtypes = [vp, i, i, C.c_double, i, dp, dp, dp, i, C.POINTER(i), C.POINTER(MgEigStats)]
+    L.mg_eig_set_vector.argtypes = [vp, i, i, vp]
+    L.mg_eig_get_vector.argtypes = [vp, i, i, vp]
+    L.mg_eig_set_vector_device.argtypes = [vp, i, i, vp, i, vp]
+    L.mg_eig_get_vector_device.argtypes = [vp, i, i, vp, i, vp]
+    L.mg_eig_block.argtypes = [vp, C.POINTER(i)]
+    L.mg_eig_kernel.argtypes = [vp, i, i, i, dp, dp, dp, dp, dp]
     L.mg_set_stage_callback.argtypes = [vp, STAGE_FN, vp]
     L.mg_sync.argtypes = [vp]
     L.mg_timer_start.argtypes = [vp]
@@ -560,6 +580,54 @@ class Solver:
     def heat_rhs(self, dt, theta, arr_u=ARR_U, arr_dst=ARR_RHS):
         """mg_heat_rhs: arr_dst(0) = the right-hand side of one theta-scheme step built from arr_u(0)"""
         _check(self.lib.mg_heat_rhs(self.h, dt, theta, arr_u, arr_dst))
+
+    # -- lowest eigenpairs of sigma I + A on level 0 (multigrid-preconditioned LOBPCG)
+    def eig_solve(self, m, nev=None, tol=1e-8, maxit=200):
+        """mg_eig_solve: the nev (default m) smallest eigenpairs on a block of m vectors, warm-started from the X columns the
+        handle holds -> (lambda[m], relres[m], hist, MgEigStats); the vectors come from eig_get_vector(EIG_X, j)"""
+        nev = m if nev is None else nev
+        cap = max(maxit, 0) + 1
+        lam = (C.c_double * max(m, 1))(); rel = (C.c_double * max(m, 1))()
+        hist = (C.c_double * cap)(); nh = C.c_int(0); st = MgEigStats()
+        _check(self.lib.mg_eig_solve(self.h, m, nev, tol, maxit, lam, rel, hist, cap, C.byref(nh), C.byref(st)))
+        return np.array(lam[:m]), np.array(rel[:m]), np.array(hist[:min(nh.value, cap)]), st
+
+    def eig_set_vector(self, family, j, a):
+        """mg_eig_set_vector: column j of a family (EIG_*) from a level-0 host array; EIG_X columns beyond the block grow it"""
+        a = self._host(a, 0); _check(self.lib.mg_eig_set_vector(self.h, family, j, a.ctypes.data_as(C.c_void_p)))
+
+    def eig_get_vector(self, family, j):
+        a = np.empty(self.level_shape(0), self.np)
+        _check(self.lib.mg_eig_get_vector(self.h, family, j, a.ctypes.data_as(C.c_void_p))); return a
+
+    def eig_set_vector_device(self, family, j, obj, stream=0):
+        ptr, dt = device_view(obj, self.level_shape(0))
+        _check(self.lib.mg_eig_set_vector_device(self.h, family, j, ptr, dt, stream or None))
+
+    def eig_get_vector_device(self, family, j, out, stream=0):
+        ptr, dt = device_view(out, self.level_shape(0), writable=True)
+        _check(self.lib.mg_eig_get_vector_device(self.h, family, j, ptr, dt, stream or None))
+
+    def eig_block(self) -> int:
+        """mg_eig_block: the block size currently allocated, 0: none"""
+        m = C.c_int(0); _check(self.lib.mg_eig_block(self.h, C.byref(m))); return m.value
+
+    def eig_kernel_gram(self, nw, np_):
+        """mg_eig_kernel(EIG_K_APPLY_GRAM): AW = A W on the first nw W columns, then (G, H) over [X, W, P]"""
+        s = self.eig_block() + nw + np_
+        G = np.zeros((s, s)); H = np.zeros((s, s)); dp = C.POINTER(C.c_double)
+        _check(self.lib.mg_eig_kernel(self.h, EIG_K_APPLY_GRAM, nw, np_, None, None, G.ctypes.data_as(dp), H.ctypes.data_as(dp), None))
+        return G, H
+
+    def eig_kernel_combine(self, nw, np_, cx, cp, theta):
+        """mg_eig_kernel(EIG_K_COMBINE): the in-place block update with Cx (s x m), Cp ((nw + np) x nw), theta (m) -> sums r^2"""
+        m = self.eig_block(); dp = C.POINTER(C.c_double)
+        coef = np.concatenate([np.ascontiguousarray(cx, np.float64).ravel(), np.ascontiguousarray(cp, np.float64).ravel()])
+        th = np.ascontiguousarray(theta, np.float64); sums = np.zeros(m)
+        assert coef.size == (m + nw + np_) * m + (nw + np_) * nw and th.size == m
+        _check(self.lib.mg_eig_kernel(self.h, EIG_K_COMBINE, nw, np_, coef.ctypes.data_as(dp), th.ctypes.data_as(dp), None, None,
+                                      sums.ctypes.data_as(dp)))
+        return sums
 
     def set_stage_callback(self, fn):
         """fn(stage, level, array) after every stage of the sawtooth cycle (CREATE_GIF dumps); None removes it"""

@@ -293,6 +293,45 @@ int mg_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst)
     MG_H(h);
     return guarded([&] { return h->impl->heat_rhs(dt, theta, arr_u, arr_dst); });
 }
+int mg_eig_solve(mg_handle h, int m, int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap,
+                 int *n_hist, mg_eig_stats *st)
+{
+    MG_H(h);
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_eig_solve: bad history buffer");
+    return guarded([&] { return h->impl->eig_solve(m, nev, tol, maxit, lambda, relres, hist, hist_cap, n_hist, st); });
+}
+int mg_eig_set_vector(mg_handle h, int family, int j, const void *host)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->eig_vector(family, j, const_cast<void *>(host), true); });
+}
+int mg_eig_get_vector(mg_handle h, int family, int j, void *host)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->eig_vector(family, j, host, false); });
+}
+int mg_eig_set_vector_device(mg_handle h, int family, int j, const void *dev, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->eig_vector_device(family, j, const_cast<void *>(dev), dtype, true, static_cast<hipStream_t>(stream)); });
+}
+int mg_eig_get_vector_device(mg_handle h, int family, int j, void *dev, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->eig_vector_device(family, j, dev, dtype, false, static_cast<hipStream_t>(stream)); });
+}
+int mg_eig_block(mg_handle h, int *m)
+{
+    MG_H(h);
+    if (!m) return bad("mg_eig_block: null argument");
+    *m = h->impl->eig_block();
+    return MG_OK;
+}
+int mg_eig_kernel(mg_handle h, int kernel, int nw, int np, const double *coef, const double *theta, double *G, double *H, double *sums)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->eig_kernel(kernel, nw, np, coef, theta, G, H, sums); });
+}
 int mg_set_stage_callback(mg_handle h, mg_stage_fn fn, void *user)
 {
     MG_H(h);

@@ -1,7 +1,8 @@
 // mg_drivers.cpp -- the solve drivers of mg::Solver: everything that calls the cycle from above (mg_solve, mg_pcg_*, mg_fmg*,
-// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
+// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*, mg_eig_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
 // Reference call structure being replaced by solve(): the outer loop of src/main.cpp:72-116.
 #include "mg_solver.h"
+#include "mg_dense.h"
 
 #include <algorithm>
 #include <cmath>
@@ -125,15 +126,15 @@ int Solver::krylov_alloc()
 // z = M r: the cycle code works on level 0's U / RHS slots, so z and r take them for the duration (pointer swap, no copy).
 // The cycle may itself leave its result in the array that was TMP (out-of-place sweeps swap U / TMP): whatever U points
 // at afterwards is z, and TMP keeps the other buffer.
-int Solver::precondition()
+int Solver::precondition(void **z, void *r)
 {
     Level &L0 = lv_[0];
     void *const x_base = L0.base[MG_ARR_U], *const b_base = L0.base[MG_ARR_RHS];
-    MG_HIP(hipMemsetAsync(kry_[KZ], 0, L0.alloc_elems * esize(), stream_));
-    L0.base[MG_ARR_U] = kry_[KZ];
-    L0.base[MG_ARR_RHS] = kry_[KR];
+    MG_HIP(hipMemsetAsync(*z, 0, L0.alloc_elems * esize(), stream_));
+    L0.base[MG_ARR_U] = *z;
+    L0.base[MG_ARR_RHS] = r;
     const int rc = outer_iteration_enqueue();
-    kry_[KZ] = L0.base[MG_ARR_U];
+    *z = L0.base[MG_ARR_U];
     L0.base[MG_ARR_U] = x_base;
     L0.base[MG_ARR_RHS] = b_base;
     return rc;
@@ -173,7 +174,7 @@ int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist
         int pc = KP0, pn = KP1;   // p ping-pongs: another workgroup may still read p_k at a neighbour while p_{k+1} is written
         MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));   // p_{-1} = 0: p_0 = z_0 + 0 p_{-1} = z_0
         auto direction = [&](int mode) -> int {   // z = M r, gamma, beta, p_{k+1} = z + beta p_k, q = A p_{k+1}, alpha
-            MG_TRY(precondition());
+            MG_TRY(precondition(&kry_[KZ], kry_[KR]));
             int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
             launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
             np = launch_cg_direction_apply<T>(stream_, g, c, kp(KZ), kp(pc), kp(pn), kp(KQ), d_cg_, d_cg_part_);
@@ -772,6 +773,307 @@ int Solver::heat_step(double dt, double theta, int nsteps, int cycles_per_step, 
         st->relres = h_scal_[SC_RR] == 0.0 ? 0.0 : std::sqrt(h_scal_[SC_RR] / h_scal_[SC_BB]);
     }
     return MG_OK;
+}
+
+// ---------------------------------------------------------------- lowest eigenpairs by LOBPCG (mg_eig_*), DESIGN.md section 17
+// The block: six families of eig_m_ level-0 arrays. The preconditioner takes a residual column (W family) as RHS and a free
+// column of the AW family as z, by pointer; the families are tables of pointers, so a column "moves" by swapping entries.
+int Solver::eig_resize(int m)
+{
+    if (!d_eig_part_) {
+        const size_t npart = (size_t)EIG_MAX_LAUNCHES * 2 * EIG_GRAM_ROWS * EIG_GRAM_COLS * EIG_MAX_BLOCKS;
+        const size_t nout = (size_t)EIG_MAX_LAUNCHES * 2 * EIG_GRAM_ROWS * EIG_GRAM_COLS;
+        MG_HIP(hipMalloc((void **)&d_eig_part_, sizeof(double) * npart));
+        MG_HIP(hipMalloc((void **)&d_eig_out_, sizeof(double) * nout));
+        MG_HIP(hipMalloc((void **)&d_eig_coef_, sizeof(double) * EIG_HOST_DOUBLES));
+        MG_HIP(hipHostMalloc((void **)&h_eig_, sizeof(double) * EIG_HOST_DOUBLES));
+        bytes_ += sizeof(double) * (npart + nout + EIG_HOST_DOUBLES);
+    }
+    const size_t nbytes = lv_[0].alloc_elems * esize();
+    for (int j = eig_m_; j < m; j++) {          // grow: new columns, X holding the default start vector
+        for (int f = 0; f < EIG_FAMILIES; f++) MG_TRY(alloc_zeroed(&eig_[f][j], nbytes));
+        char *x = reinterpret_cast<char *>(eig_[MG_EIG_X][j]) + (size_t)lv_[0].gh * (size_t)lv_[0].g.plane * esize();
+        if (d_.dtype == MG_F64) launch_eig_fill<double>(stream_, lv_[0].g, reinterpret_cast<double *>(x), j);
+        else launch_eig_fill<float>(stream_, lv_[0].g, reinterpret_cast<float *>(x), j);
+        MG_HIP(hipGetLastError());
+        eig_m_ = j + 1;
+    }
+    if (m < eig_m_) {                           // shrink: the columns beyond m go
+        MG_HIP(hipStreamSynchronize(stream_));
+        for (int j = m; j < eig_m_; j++)
+            for (int f = 0; f < EIG_FAMILIES; f++) {
+                MG_HIP(hipFree(eig_[f][j]));
+                eig_[f][j] = nullptr;
+                bytes_ -= nbytes;
+            }
+        eig_m_ = m;
+    }
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::eig_gram_t(int mode, int nw, int np, double *G, double *H)
+{
+    const Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    const Coef<T> c = coef_of<T>(L0);
+    const int m = eig_m_;
+    auto col = [&](int fam, int j) { return reinterpret_cast<T *>(eig_[fam][j]) + L0.gh * g.plane; };
+    // S and AS in column order; `interior`: the column is read as 0 on Dirichlet nodes (what the apply is about to make of it)
+    T *sp[3 * MG_EIG_MAX_BLOCK], *asp[3 * MG_EIG_MAX_BLOCK];
+    bool interior[3 * MG_EIG_MAX_BLOCK], applied[3 * MG_EIG_MAX_BLOCK];
+    int s = 0;
+    for (int j = 0; j < m; j++, s++) { sp[s] = col(MG_EIG_X, j); asp[s] = col(MG_EIG_AX, j); interior[s] = applied[s] = mode == EIG_GRAM_X; }
+    if (mode != EIG_GRAM_X) {
+        for (int j = 0; j < nw; j++, s++) { sp[s] = col(MG_EIG_W, j); asp[s] = col(MG_EIG_AW, j); interior[s] = applied[s] = true; }
+        for (int j = 0; j < np; j++, s++) { sp[s] = col(MG_EIG_P, j); asp[s] = col(MG_EIG_AP, j); interior[s] = applied[s] = false; }
+    }
+    // column blocks of at most EIG_GRAM_COLS columns of ONE family, each against the rows above and on the diagonal in chunks
+    // of EIG_GRAM_ROWS; the first chunk of a block carries the apply
+    struct Tile { int r0, na, c0, nb; } tiles[EIG_MAX_LAUNCHES];
+    constexpr int TILE = 2 * EIG_GRAM_ROWS * EIG_GRAM_COLS;
+    int nt = 0, nblocks = 0;
+    const int fam_begin[4] = {0, m, m + (mode == EIG_GRAM_X ? 0 : nw), s};
+    for (int f = 0; f < 3; f++) {
+        if (f == 0 && mode == EIG_GRAM_ITER) continue;   // X^T X = I and X^T A X = diag(theta): the caller has filled them in
+        for (int c0 = fam_begin[f]; c0 < fam_begin[f + 1]; c0 += EIG_GRAM_COLS) {
+            const int nb = std::min(EIG_GRAM_COLS, fam_begin[f + 1] - c0);
+            for (int r0 = 0; r0 < c0 + nb; r0 += EIG_GRAM_ROWS) {
+                if (nt == EIG_MAX_LAUNCHES) { set_last_error("mg_eig: more Gram tiles than the partial-sum buffer holds"); return MG_ERR_HIP; }
+                EigGramArgs<T> a{};
+                a.na = std::min(EIG_GRAM_ROWS, c0 + nb - r0);
+                a.nb = nb;
+                for (int r = 0; r < a.na; r++) {
+                    a.row[r] = sp[r0 + r];
+                    if (interior[r0 + r]) a.row_interior |= 1u << r;
+                }
+                for (int j = 0; j < nb; j++) { a.col[j] = sp[c0 + j]; a.acol[j] = asp[c0 + j]; }
+                // the kernel loads all EIG_GRAM_ROWS rows and EIG_GRAM_COLS columns without a branch: the unused ones repeat a used one
+                for (int r = a.na; r < EIG_GRAM_ROWS; r++) a.row[r] = a.row[0];
+                for (int j = nb; j < EIG_GRAM_COLS; j++) { a.col[j] = a.col[0]; a.acol[j] = a.acol[0]; }
+                a.col_interior = interior[c0] ? 1 : 0;
+                nblocks = launch_eig_gram<T>(stream_, g, c, a, applied[c0] && r0 == 0, d_eig_part_ + (size_t)nt * TILE * EIG_MAX_BLOCKS);
+                tiles[nt++] = Tile{r0, a.na, c0, nb};
+            }
+        }
+    }
+    MG_HIP(hipGetLastError());
+    if (nt == 0) return MG_OK;
+    // every tile left TILE * nblocks partials at a stride of TILE * EIG_MAX_BLOCKS: one reduction launch per tile
+    for (int t = 0; t < nt; t++)
+        launch_eig_reduce(stream_, d_eig_part_ + (size_t)t * TILE * EIG_MAX_BLOCKS, nblocks, TILE, d_eig_out_ + (size_t)t * TILE);
+    MG_HIP(hipGetLastError());
+    MG_HIP(hipMemcpyAsync(h_eig_, d_eig_out_, sizeof(double) * (size_t)nt * TILE, hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    for (int t = 0; t < nt; t++)
+        for (int r = 0; r < tiles[t].na; r++)
+            for (int j = 0; j < tiles[t].nb; j++) {
+                const int a = tiles[t].r0 + r, b = tiles[t].c0 + j;
+                if (a > b) continue;
+                G[a * s + b] = G[b * s + a] = h_eig_[t * TILE + r * EIG_GRAM_COLS + j];
+                H[a * s + b] = H[b * s + a] = h_eig_[t * TILE + TILE / 2 + r * EIG_GRAM_COLS + j];
+            }
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::eig_combine_t(int nw, int np, const double *coef, const double *theta, double *sums)
+{
+    const Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    const int m = eig_m_, s = m + nw + np;
+    auto col = [&](int fam, int j) { return reinterpret_cast<T *>(eig_[fam][j]) + L0.gh * g.plane; };
+    EigCombineArgs<T> a{};
+    a.m = m; a.nw = nw; a.np = np;
+    int k = 0;
+    for (int j = 0; j < m; j++, k++) { a.s[k] = col(MG_EIG_X, j); a.as[k] = col(MG_EIG_AX, j); }
+    for (int j = 0; j < nw; j++, k++) { a.s[k] = col(MG_EIG_W, j); a.as[k] = col(MG_EIG_AW, j); }
+    for (int j = 0; j < np; j++, k++) { a.s[k] = col(MG_EIG_P, j); a.as[k] = col(MG_EIG_AP, j); }
+    for (int j = 0; j < m; j++) {
+        a.x[j] = col(MG_EIG_X, j); a.ax[j] = col(MG_EIG_AX, j); a.r[j] = col(MG_EIG_W, j);
+        a.p[j] = col(MG_EIG_P, j); a.ap[j] = col(MG_EIG_AP, j);
+    }
+    const int ncoef = s * m + (nw + np) * nw;   // <= 24 * 8 + 16 * 8
+    for (int i = 0; i < ncoef; i++) h_eig_[i] = coef[i];
+    for (int j = 0; j < m; j++) h_eig_[ncoef + j] = theta[j];
+    MG_HIP(hipMemcpyAsync(d_eig_coef_, h_eig_, sizeof(double) * (size_t)(ncoef + m), hipMemcpyHostToDevice, stream_));
+    const int nblocks = launch_eig_combine<T>(stream_, g, a, d_eig_coef_, d_eig_coef_ + ncoef, d_eig_part_);
+    launch_eig_reduce(stream_, d_eig_part_, nblocks, m, d_eig_out_);
+    MG_HIP(hipGetLastError());
+    MG_HIP(hipMemcpyAsync(h_eig_ + ncoef + m, d_eig_out_, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    for (int j = 0; j < m; j++) sums[j] = h_eig_[ncoef + m + j];
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::eig_t(int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap, int *n_hist,
+                  mg_eig_stats *st)
+{
+    constexpr int SMAX = 3 * MG_EIG_MAX_BLOCK;
+    const int m = eig_m_;
+    mg_eig_stats out{0, 1, 0, 0, 0.0};
+    double G[SMAX * SMAX], H[SMAX * SMAX], C[SMAX * MG_EIG_MAX_BLOCK + 2 * MG_EIG_MAX_BLOCK * MG_EIG_MAX_BLOCK];
+    double theta[MG_EIG_MAX_BLOCK], sums[MG_EIG_MAX_BLOCK], rel[MG_EIG_MAX_BLOCK];
+    int nh = 0;
+    // Rayleigh-Ritz on X alone from a fresh A X (X need not be orthonormal): X, AX rotated, theta, R in the W family, rel
+    auto ritz_x = [&]() -> int {
+        MG_TRY(eig_gram_t<T>(EIG_GRAM_X, 0, 0, G, H));
+        if (dense_rayleigh_ritz(m, m, G, H, DENSE_PIVOT_MIN, theta, C) != DENSE_OK) return 1;
+        MG_TRY(eig_combine_t<T>(0, 0, C, theta, sums));
+        for (int j = 0; j < m; j++) rel[j] = std::sqrt(sums[j]) / std::fabs(theta[j]);   // ||x_j|| = 1
+        return MG_OK;
+    };
+    auto all_finite = [&]() {
+        for (int j = 0; j < m; j++)
+            if (!std::isfinite(rel[j])) return false;
+        return true;
+    };
+    int rc = ritz_x();
+    if (rc < 0) return rc;
+    bool whole = rc == 0 && all_finite();
+    if (!whole) out.status = 2;
+    int act_prev[MG_EIG_MAX_BLOCK], n_prev = 0;   // the columns P belongs to (P column k goes with X column act_prev[k])
+    while (whole) {
+        double worst = 0;
+        for (int j = 0; j < nev; j++) worst = std::max(worst, rel[j]);
+        if (hist && nh < hist_cap) hist[nh] = worst;
+        nh++;
+        if (worst <= tol) { out.status = 0; break; }
+        if (out.iters == maxit) { out.status = 1; break; }
+        int act[MG_EIG_MAX_BLOCK], nw = 0;
+        for (int j = 0; j < m; j++)
+            if (rel[j] > tol) act[nw++] = j;
+        // P of the active columns, compacted to the front of its family; none when a column has no P
+        int np = n_prev > 0 ? nw : 0;
+        for (int k = 0; k < nw && np; k++) {
+            int from = -1;
+            for (int q = 0; q < n_prev; q++)
+                if (act_prev[q] == act[k]) from = q;
+            if (from < 0) { np = 0; break; }
+            if (from != k) {   // from > k: act and act_prev both ascend
+                std::swap(eig_[MG_EIG_P][k], eig_[MG_EIG_P][from]);
+                std::swap(eig_[MG_EIG_AP][k], eig_[MG_EIG_AP][from]);
+                std::swap(act_prev[k], act_prev[from]);
+            }
+        }
+        // W_k = M R_{act[k]}: the residual column is the right-hand side, a free AW column takes the result; afterwards the
+        // result is W column k and the buffer R_k lay in (a finished or locked column's: act[k] >= k) is the free AW column
+        for (int k = 0; k < nw; k++) {
+            void *z = eig_[MG_EIG_AW][k];
+            MG_TRY(precondition(&z, eig_[MG_EIG_W][act[k]]));
+            eig_[MG_EIG_AW][k] = eig_[MG_EIG_W][k];
+            eig_[MG_EIG_W][k] = z;
+            out.cycles++;
+        }
+        int status = DENSE_RANK;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            const int s = m + nw + np;
+            if (attempt == 0) {
+                for (int i = 0; i < s * s; i++) G[i] = H[i] = 0.0;
+                for (int j = 0; j < m; j++) { G[j * s + j] = 1.0; H[j * s + j] = theta[j]; }
+                MG_TRY(eig_gram_t<T>(EIG_GRAM_ITER, nw, np, G, H));
+            }
+            status = dense_rayleigh_ritz(s, m, G, H, DENSE_PIVOT_MIN, theta, C);
+            if (status == DENSE_OK || np == 0) break;
+            // the basis with P is not safely positive definite: the same iteration without P (the leading block of G, H)
+            const int s2 = m + nw;
+            for (int i = 0; i < s2; i++)
+                for (int j = 0; j < s2; j++) { G[i * s2 + j] = G[i * s + j]; H[i * s2 + j] = H[i * s + j]; }
+            np = 0;
+            out.restarts++;
+        }
+        if (status != DENSE_OK) { out.status = 2; whole = false; break; }
+        {
+            const int s = m + nw + np;
+            double *Cp = C + s * m;   // P' = X' without its X part, for the active columns
+            for (int r = 0; r < nw + np; r++)
+                for (int k = 0; k < nw; k++) Cp[r * nw + k] = C[(m + r) * m + act[k]];
+            MG_TRY(eig_combine_t<T>(nw, np, C, theta, sums));
+        }
+        for (int j = 0; j < m; j++) rel[j] = std::sqrt(sums[j]) / std::fabs(theta[j]);
+        for (int k = 0; k < nw; k++) act_prev[k] = act[k];
+        n_prev = nw;
+        out.iters++;
+        if (!all_finite()) { out.status = 2; whole = false; break; }
+    }
+    // what is returned: Ritz values and residuals of the returned block from a fresh A X
+    rc = ritz_x();
+    if (rc < 0) return rc;
+    if (rc != 0 || !all_finite()) {
+        out.status = 2;
+        for (int j = 0; j < m; j++) theta[j] = rel[j] = std::nan("");
+    }
+    for (int j = 0; j < m; j++) { lambda[j] = theta[j]; relres[j] = rel[j]; }
+    out.max_relres = 0;
+    for (int j = 0; j < nev; j++) out.max_relres = rel[j] > out.max_relres || std::isnan(rel[j]) ? rel[j] : out.max_relres;
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
+int Solver::eig_solve(int m, int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap,
+                      int *n_hist, mg_eig_stats *st)
+{
+    const Geom &g = lv_[0].g;
+    const long long interior = (long long)(g.nx - 2) * (g.ny - 2) * (g.dim == 3 ? g.gnz - 2 : 1);
+    if (m < 1 || m > MG_EIG_MAX_BLOCK || nev < 1 || nev > m || m > interior || !(tol > 0.0) || !std::isfinite(tol) || maxit < 0 ||
+        !lambda || !relres) {
+        set_last_error("mg_eig_solve: need 1 <= nev <= m <= min(MG_EIG_MAX_BLOCK, interior nodes), a positive finite tol, maxit >= 0 and "
+                       "lambda / relres arrays");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_TRY(driver_begin("mg_eig_solve", REFUSE_DIST | REFUSE_STAGE_CB));
+    MG_TRY(eig_resize(m));
+    return d_.dtype == MG_F64 ? eig_t<double>(nev, tol, maxit, lambda, relres, hist, hist_cap, n_hist, st)
+                              : eig_t<float>(nev, tol, maxit, lambda, relres, hist, hist_cap, n_hist, st);
+}
+
+int Solver::eig_check(const char *fn, int family, int j, bool may_grow)
+{
+    MG_TRY(driver_begin(fn, REFUSE_DIST));
+    const int limit = may_grow && family == MG_EIG_X ? MG_EIG_MAX_BLOCK : eig_m_;
+    if (family < 0 || family >= EIG_FAMILIES || j < 0 || j >= limit) {
+        set_last_error(std::string(fn) + ": no such family / column (MG_EIG_X columns up to MG_EIG_MAX_BLOCK - 1 can be set, every "
+                                         "other access lies inside the allocated block, see mg_eig_block)");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::eig_vector(int family, int j, void *host, bool to_handle)
+{
+    const char *fn = to_handle ? "mg_eig_set_vector" : "mg_eig_get_vector";
+    MG_TRY(eig_check(fn, family, j, to_handle));
+    if (!host) { set_last_error(std::string(fn) + ": null argument"); return MG_ERR_BAD_ARG; }
+    if (j >= eig_m_) MG_TRY(eig_resize(j + 1));
+    const Level &L0 = lv_[0];
+    char *dev = reinterpret_cast<char *>(eig_[family][j]) + (size_t)L0.gh * (size_t)L0.g.plane * esize();
+    return stage_copy(dev, L0.g, esize(), host, to_handle);
+}
+
+int Solver::eig_vector_device(int family, int j, void *dense, int dense_dtype, bool to_handle, hipStream_t caller)
+{
+    const char *fn = to_handle ? "mg_eig_set_vector_device" : "mg_eig_get_vector_device";
+    MG_TRY(eig_check(fn, family, j, to_handle));
+    const Level &L0 = lv_[0];
+    MG_TRY(device_check(fn, dense, dense_dtype, L0.g));   // every refusal comes before the block grows
+    if (j >= eig_m_) MG_TRY(eig_resize(j + 1));
+    char *dev = reinterpret_cast<char *>(eig_[family][j]) + (size_t)L0.gh * (size_t)L0.g.plane * esize();
+    return device_copy(fn, dev, L0.g, esize(), dense, dense_dtype, to_handle, caller);
+}
+
+int Solver::eig_kernel(int kernel, int nw, int np, const double *coef, const double *theta, double *G, double *H, double *sums)
+{
+    MG_TRY(driver_begin("mg_eig_kernel", REFUSE_DIST));
+    const bool gram = kernel == MG_EIG_K_APPLY_GRAM;
+    if ((!gram && kernel != MG_EIG_K_COMBINE) || eig_m_ == 0 || nw < 0 || nw > eig_m_ || (np != 0 && np != nw) ||
+        (gram ? (!G || !H) : (!coef || !theta || !sums))) {
+        set_last_error("mg_eig_kernel: unknown kernel, no block (mg_eig_block), nw outside [0, m], np not 0 or nw, or a null argument");
+        return MG_ERR_BAD_ARG;
+    }
+    if (gram) return d_.dtype == MG_F64 ? eig_gram_t<double>(EIG_GRAM_FULL, nw, np, G, H) : eig_gram_t<float>(EIG_GRAM_FULL, nw, np, G, H);
+    return d_.dtype == MG_F64 ? eig_combine_t<double>(nw, np, coef, theta, sums) : eig_combine_t<float>(nw, np, coef, theta, sums);
 }
 
 }  // namespace mg

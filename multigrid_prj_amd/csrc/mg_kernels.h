@@ -223,6 +223,44 @@ void launch_cg_boundary_copy(hipStream_t s, const Geom &g, T *x, const T *rhs);
 // fixed-order sum of the partials of one launch above + the scalar update `mode` (CgTail), one workgroup
 void launch_cg_tail(hipStream_t s, int mode, const double *partials, int nb, CgScalars *sc);
 
+// ---- block kernels of the LOBPCG eigensolver on level 0 (mg_eig.hip, driven by Solver::eig_t) ----
+constexpr int EIG_GRAM_ROWS = 12;      // one Gram tile: up to 12 row vectors ...
+constexpr int EIG_GRAM_COLS = 4;       // ... against up to 4 column vectors and their images under A
+constexpr int EIG_MAX_BLOCKS = 1024;   // workgroups of a launch = partial sums per accumulator
+constexpr int EIG_MAX_COLS = 8;        // MG_EIG_MAX_BLOCK
+template <typename T>
+struct EigGramArgs {
+    const T *row[EIG_GRAM_ROWS];
+    T *col[EIG_GRAM_COLS];             // b
+    T *acol[EIG_GRAM_COLS];            // A b: read, or with the apply written (col is then set to 0 on Dirichlet nodes)
+    int na, nb;                        // rows / columns in use; the entries beyond them must repeat a used pointer (the kernel
+                                       // loads all of them without a branch and ignores what it got)
+    unsigned row_interior;             // bit r: row r is read as 0 on Dirichlet nodes whatever it holds there (the W family)
+    int col_interior;                  // the same for the columns of a launch without the apply
+};
+// One tile: partials[(r * EIG_GRAM_COLS + j) * nblocks + block] of row[r] . col[j], and EIG_GRAM_ROWS * EIG_GRAM_COLS
+// entries further on the same of row[r] . acol[j]. apply: acol[j] = A col[j] is made (and stored) instead of read.
+// Every array is level-shaped with a ghost plane either side (the apply reads the neighbours of boundary nodes too and
+// zeroes them afterwards). Returns nblocks.
+template <typename T>
+int launch_eig_gram(hipStream_t s, const Geom &g, const Coef<T> &c, const EigGramArgs<T> &a, bool apply, double *partials);
+template <typename T>
+struct EigCombineArgs {
+    const T *s[3 * EIG_MAX_COLS], *as[3 * EIG_MAX_COLS];   // S = [X, W, P] and AS = [AX, AW, AP] in column order
+    T *x[EIG_MAX_COLS], *ax[EIG_MAX_COLS], *r[EIG_MAX_COLS], *p[EIG_MAX_COLS], *ap[EIG_MAX_COLS];   // outputs (they alias inputs)
+    int m, nw, np;
+};
+// x_j = S Cx, ax_j = AS Cx (j < m), p_j = [W, P] Cp, ap_j = [AW, AP] Cp (j < nw), r_j = ax_j - theta_j x_j; coef (device) =
+// Cx (s x m) followed by Cp ((nw + np) x nw), row-major; partials[j * nblocks + block] of r_j^2. Returns nblocks.
+template <typename T>
+int launch_eig_combine(hipStream_t s, const Geom &g, const EigCombineArgs<T> &a, const double *coef, const double *theta,
+                       double *partials);
+// out[k] = the sum of partials[k * nb .. (k + 1) * nb) in a fixed order, k < nsums
+void launch_eig_reduce(hipStream_t s, const double *partials, int nb, int nsums, double *out);
+// the default start vector of column `column`: a hash of the node's global index, uniform in [-1, 1), 0 on Dirichlet nodes
+template <typename T>
+void launch_eig_fill(hipStream_t s, const Geom &g, T *x, int column);
+
 // ---- full-multigrid interpolation (mg_fmg.hip, driven by Solver::fmg_t) ----
 // fine = Pi coarse: cubic along every coarsened axis (one-sided quadratic next to a boundary), kept axes copied;
 // bnd != nullptr: fine Dirichlet nodes = bnd[node] instead, in the same launch. Whole (undistributed) levels only.

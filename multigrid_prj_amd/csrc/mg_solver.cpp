@@ -162,6 +162,12 @@ Solver::~Solver()
     for (auto &b : mx_) if (b) (void)hipFree(b);
     for (auto &b : o4_) if (b) (void)hipFree(b);
     if (heat_f_) (void)hipFree(heat_f_);
+    for (auto &fam : eig_)
+        for (auto &b : fam) if (b) (void)hipFree(b);
+    if (d_eig_part_) (void)hipFree(d_eig_part_);
+    if (d_eig_out_) (void)hipFree(d_eig_out_);
+    if (d_eig_coef_) (void)hipFree(d_eig_coef_);
+    if (h_eig_) (void)hipHostFree(h_eig_);
     if (d_mx_part_) (void)hipFree(d_mx_part_);
     if (d_mx_sum_) (void)hipFree(d_mx_sum_);
     if (d_cg_) (void)hipFree(d_cg_);

@@ -1,7 +1,7 @@
 // mg_solver.h -- host-side owner of the HBM-resident grid hierarchy behind the C-ABI of include/mg_hip.h. One class, two
 // translation units: mg_solver.cpp holds the hierarchy, the communication, the per-operator launch paths and the cycle
 // (vcycle_rec_t for the V, W and F kinds, visit_child_t, subcycle_launch_t, cycle_from_t, cycle_enqueue*, cycle); mg_drivers.cpp
-// holds what calls the cycle from above (solve, pcg_*, fmg*, subcycle, mixed_*, set_shift, heat_*) and the helpers those drivers share.
+// holds what calls the cycle from above (solve, pcg_*, fmg*, subcycle, mixed_*, set_shift, heat_*, eig_*) and the helpers those drivers share.
 // The member templates that mg_drivers.cpp calls and mg_solver.cpp defines (smooth_t, pair_norm_ok, residual_t, sumsq_t,
 // restrict_t, coarse_level_t, vcycle_rec_t, cycle_from_t, subcycle_launch_t) cross the file boundary by ONE mechanism: explicit instantiation definitions
 // for double and float, in one block at the end of mg_solver.cpp.
@@ -137,6 +137,14 @@ public:
     int heat_set_source_device(const void *dense, int dense_dtype, hipStream_t caller);
     int heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
     int heat_rhs(double dt, double theta, int arr_u, int arr_dst);
+    // lowest eigenpairs of sigma I + A on level 0 by multigrid-preconditioned LOBPCG (mg_eig_*); the block of 6 m level-0
+    // arrays is allocated on first use and kept until the handle goes
+    int eig_solve(int m, int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap, int *n_hist,
+                  mg_eig_stats *st);
+    int eig_vector(int family, int j, void *host, bool to_handle);
+    int eig_vector_device(int family, int j, void *dense, int dense_dtype, bool to_handle, hipStream_t caller);
+    int eig_block() const { return eig_m_; }
+    int eig_kernel(int kernel, int nw, int np, const double *coef, const double *theta, double *G, double *H, double *sums);
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -227,7 +235,9 @@ private:
     // this way keep their ghost planes and padding columns zero: nothing writes them afterwards.
     int alloc_zeroed(void **p, size_t nbytes);
     template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
-    int precondition();   // z = M r: one mg_solve outer iteration from zero on (z, r)
+    // *z = M r: one mg_solve outer iteration from zero with the buffers *z and r in level 0's U / RHS slots. The cycle may leave
+    // its result in the buffer that was TMP: *z is whatever U points at afterwards, and TMP keeps the other buffer.
+    int precondition(void **z, void *r);
     template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
     int mixed_check(const char *fn, unsigned refuse = REFUSE_DIST);      // MG_F32, then driver_begin(fn, refuse)
@@ -340,6 +350,21 @@ private:
     template <typename T> int heat_step_t(double dt, double theta, int nsteps, int cycles_per_step);
     void *heat_f_ = nullptr;
     bool heat_has_f_ = false;
+    // block of eig_solve: eig_[family][column] (enum mg_eig_family), level-0-shaped; the per-workgroup partial sums of up to
+    // EIG_MAX_LAUNCHES Gram tiles, their totals, the coefficients of the combine (device) and a pinned mirror of the last two
+    enum { EIG_FAMILIES = 6, EIG_MAX_LAUNCHES = 9, EIG_HOST_DOUBLES = 2048 };
+    enum EigGramMode { EIG_GRAM_X = 0, EIG_GRAM_ITER = 1, EIG_GRAM_FULL = 2 };
+    void *eig_[EIG_FAMILIES][MG_EIG_MAX_BLOCK] = {};
+    int eig_m_ = 0;
+    double *d_eig_part_ = nullptr, *d_eig_out_ = nullptr, *d_eig_coef_ = nullptr, *h_eig_ = nullptr;
+    int eig_check(const char *fn, int family, int j, bool may_grow);   // driver_begin + the family / column rules
+    int eig_resize(int m);
+    // G, H (s x s, s = m or m + nw + np) of the block. EIG_GRAM_X: S = [X], AX = A X made on the way (X := 0 on Dirichlet
+    // nodes); EIG_GRAM_ITER: S = [X, W, P], AW made, the X x X block left as the caller filled it; EIG_GRAM_FULL: every block
+    template <typename T> int eig_gram_t(int mode, int nw, int np, double *G, double *H);
+    template <typename T> int eig_combine_t(int nw, int np, const double *coef, const double *theta, double *sums);
+    template <typename T> int eig_t(int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap,
+                                    int *n_hist, mg_eig_stats *st);
     Geom gfull_{};
     void *full_[3] = {nullptr, nullptr, nullptr};
     std::vector<SlabPlan> planT_;

@@ -123,6 +123,20 @@ int main(int argc, char **argv)
         mg_destroy(h);
         return 1;
     }
+    // -eig m: the m smallest eigenvalues of the operator just solved with, by mg_eig_solve (tolerance 1e-8, 1e-3 in fp32);
+    // printed after the report below
+    std::vector<double> eig_lambda(static_cast<size_t>(opt.eig)), eig_relres(static_cast<size_t>(opt.eig));
+    mg_eig_stats eig_st{};
+    if (opt.eig > 0) {
+        try {
+            MultiGrid::mg_check(mg_eig_solve(h, opt.eig, opt.eig, opt.fp32 ? 1e-3 : 1e-8, 500, eig_lambda.data(), eig_relres.data(),
+                                             nullptr, 0, nullptr, &eig_st));
+        } catch (const MultiGrid::HipError &e) {
+            std::cout << "Error: " << e.what() << std::endl;
+            mg_destroy(h);
+            return 1;
+        }
+    }
 
     // the reference stops its clock after the iteration loop (main.cpp:114); tearing the device
     // hierarchy down corresponds to its destructors at scope exit, after the report
@@ -132,6 +146,12 @@ int main(int argc, char **argv)
     std::cout << "||Solving elapsed time: " << solve_time.count() << " sec<br>" << std::endl;
     std::cout << "Tol: " << TOL << "<br>" << std::endl;
     std::cout << "Max iter: " << MaxIter << "<br>" << std::endl;
+
+    if (opt.eig > 0) {
+        std::cout << "Eigenvalues: " << eig_st.iters << " LOBPCG iterations, " << eig_st.cycles << " cycles, status " << eig_st.status << std::endl;
+        std::cout.precision(15);
+        for (int j = 0; j < opt.eig; j++) std::cout << "eig " << j << " " << eig_lambda[j] << " " << eig_relres[j] << std::endl;
+    }
 
     Utils::saveVectorOnFile(hist, "MGGS4.txt");
     Utils::saveVectorOnFile(u, "x.mtx");

@@ -35,7 +35,7 @@ void usage()
               << "  -smt, you can choose your favourite smoother" << std::endl
               << "  --help, Display this help message" << std::endl
               << "MI355X extensions:" << std::endl
-              << "  -dim 2|3, -cycle saw|v|w|f, -omega W, -nu1 K, -nu2 K, -rbgs, -zebra, -zebrax, -anisox A, -anisoy A, -fw, -coarse_fixed K, -fp32, -maxit K, -cold, -eps E, -semi K" << std::endl;
+              << "  -dim 2|3, -cycle saw|v|w|f, -omega W, -nu1 K, -nu2 K, -rbgs, -zebra, -zebrax, -anisox A, -anisoy A, -fw, -coarse_fixed K, -fp32, -maxit K, -cold, -eps E, -semi K, -eig M" << std::endl;
 }
 
 }  // namespace
@@ -110,6 +110,7 @@ void Utils::parse_command_line(int argc, char **argv, Options &o)
         else if (a == "-fw") { o.full_weighting = true; }
         else if (a == "-fp32") { o.fp32 = true; }
         else if (a == "-cold") { o.cold = true; }
+        else if (a == "-eig" && has_value) { o.eig = std::atoi(argv[i + 1]); if (o.eig < 1 || o.eig > 8) fail("-eig must be in 1..8"); }
     }
 }
 

@@ -36,6 +36,7 @@ struct Options {
     int semi = 0;
     int cycle_kind = 1;   // with vcycle: MG_CYCLE_V (-cycle v), MG_CYCLE_W (w) or MG_CYCLE_F (f)
     int nu1 = 2, nu2 = -1, coarse_fixed = -1, maxit = 1000;
+    int eig = 0;   // -eig m: after the run, the m smallest eigenvalues of the operator (mg_eig_solve); 0: none
 };
 
 // Parses argv like the reference's Initialization_for_N (same echo lines, same `Error: …`
