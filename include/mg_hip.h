@@ -377,6 +377,70 @@ typedef struct mg_o4_stats {
 int mg_o4_solve(mg_handle h, double tol, int maxit, int inner_cycles,
                 double *hist, int hist_cap, int *n_hist, mg_o4_stats *st);
 
+/* Variable-coefficient diffusion (extension, no reference counterpart): sigma u - div(a(x) grad u) with a nodal coefficient
+ * field a >= a_min > 0 -- heterogeneous conduction, porous-media pressure, variable-density projection. On every level l,
+ * at interior nodes,
+ *   (L u)_i = sigma u_i + sum over axes a of (-c_a / 2) [ (a_i + a_i+)(u_i - u_i+) + (a_i + a_i-)(u_i - u_i-) ]
+ * with c_a the off-diagonals of mg_level_coefficients(h, l) and sigma = mg_get_shift: desc.alpha, aniso, semi_xy, grids that
+ * are not 2^k + 1 and the shift keep their meaning; Dirichlet rows are identity rows; a == 1 is the handle's constant
+ * operator up to rounding. Face coefficients are ARITHMETIC means of the two nodal values (a harmonic mean saves Krylov
+ * iterations on jumps and costs six divisions per node per sweep); the coefficient of level l + 1 is the FULL-WEIGHTED
+ * coefficient of level l (injected on the coarse boundary, semi transitions as mg_restrict handles them) -- injection
+ * diverges on a jump that does not lie on the coarse grids.
+ * Arithmetic, in the working dtype T, every operation rounded separately (no contraction), w_a = (T)(-c_a / 2), the
+ * neighbours q in the row order of mg_residual, z-, y-, x-, x+, y+, z+ (no z terms in 2-D):
+ *   s = 0, d = (T)sigma;  per neighbour on axis a:  g = w_a*(a_i + a_q);  s = s + g*u_q;  d = d + g
+ *   residual     r = b - (d*u_i - s) on interior nodes, r = b - u on Dirichlet nodes (mg_residual's convention)
+ *   point solve  ps = (b + s) / d, an IEEE division
+ *   Jacobi       out of place: u' = ps when desc.omega == 1, else u_i + omega*(ps - u_i); Dirichlet nodes take b
+ *   red-black    in place, colour (i + j + k) & 1, colour 0 first; Dirichlet nodes take b with their colour
+ *   the sum of r^2 (all nodes) is accumulated in double in a fixed order, no atomics: two runs give the same bits.
+ *
+ * mg_vc_set_coefficient: a as a dense host array of desc.dtype in the usual layout (level 0); a value that is not finite
+ *   and > 0 is refused. The FIRST set call allocates one more level-shaped array per level, kept until mg_destroy and
+ *   counted by mg_device_bytes from then on (8/7 of a level-0 array in 3-D); every set call re-restricts all levels.
+ * mg_vc_set_coefficient_device: the same from a dense device array on the caller's stream, every rule of
+ *   mg_set_array_device (dtype conversion included); positive finite values are a PRECONDITION, nothing looks at them.
+ * mg_vc_get_coefficient: the coefficient of any level as a dense host array.
+ * mg_vc_residual: arr_r(level) = arr_rhs - L arr_x; arr_r < 0: norm only; *sumsq_r = sum r^2 (may be NULL: no fetch, no
+ *   synchronisation); arr_r != arr_x, arr_r != arr_rhs.
+ * mg_vc_smooth: `sweeps` sweeps of MG_SMOOTH_JACOBI (desc.omega) or MG_SMOOTH_RBGS; the result is in arr_x (a Jacobi sweep
+ *   writes MG_ARR_TMP and the two are swapped, as mg_smooth does: neither array may be MG_ARR_TMP).
+ * mg_vc_coarse_solve: mg_coarse_solve's loop (desc.coarse_mode, coarse_maxit, coarse_tol, the handle's smoother) in one
+ *   workgroup with the vc sweep and the vc residual; any level.
+ * mg_vc_cycle: cyc(0, desc.cycle) exactly as the W / F block above words it -- nu_pre sweeps; RHS(l+1) = R (RHS(l) - L U(l))
+ *   with desc.restriction; U(l+1) = 0; the recursion; the second visit for W and F; U(l) += P U(l+1); nu_post sweeps -- every
+ *   sweep, residual and the coarse solve by the vc kernels, the transfers by the handle's own; launch by launch (no fused
+ *   pairs, no LDS sub-cycle, no folded prolongation). A coarsest level too big for one workgroup in MG_COARSE_FIXED mode
+ *   runs coarse_maxit chip-wide sweeps, as mg_cycle does. mg_cycle_stats have the W / F semantics of mg_desc.h.
+ * mg_vc_solve: mg_solve's loop and history contract on L: U = RHS on the Dirichlet nodes first, hist[0] the initial
+ *   relative residual over all nodes, one mg_vc_cycle per iteration. desc.outer_pre_gs is IGNORED (the lexicographic sweep
+ *   has no variable-coefficient form).
+ * mg_vc_pcg_solve: mg_pcg_solve's algorithm, statuses and history word for word with A -> L and M r = one mg_vc_cycle from
+ *   zero. The cycle alone stalls on coefficient jumps that the coarse grids do not resolve; this is the solver for them.
+ * mg_vc_direction (the direction kernel of mg_vc_pcg_solve alone, for kernel-level checks and measurements, as mg_pcg_kernel):
+ *   arr_pn = arr_z + (T)beta * arr_p on interior nodes, 0 on Dirichlet nodes; arr_q = L arr_pn by the contract above with
+ *   u = arr_pn (q = d*pn_i - s), 0 on Dirichlet nodes; *pq = the sum of pn*q in double (may be NULL: no fetch, no
+ *   synchronisation). Four distinct level-0 arrays; arr_z and arr_p are not modified.
+ * mg_vc_set_form (tests and measurement tools): form 1 runs the one-thread-per-node kernels on every level, form 0 (the
+ *   default) the marching tile where the level's shape admits it (3-D, at least 16 full 16-byte vectors per row).
+ * On return of the three drivers U(0) holds the iterate and RHS(0) is unchanged; every other array is unspecified.
+ * MG_ERR_BAD_ARG with U untouched: no coefficient set (every call but the two set calls); a sawtooth handle or a stage
+ * callback installed (cycle, solve, pcg_solve); a handle smoother other than Jacobi or red-black (cycle, solve, pcg_solve,
+ * coarse_solve); an unknown smoother in mg_vc_smooth; distributed handles (dry runs included); bad arrays or levels; NULL
+ * handle. No other entry point changes behaviour, and a handle that never calls mg_vc_* allocates nothing new. */
+int mg_vc_set_coefficient(mg_handle h, const void *host_a);
+int mg_vc_set_coefficient_device(mg_handle h, const void *dev_a, int dtype, void *stream);
+int mg_vc_get_coefficient(mg_handle h, int level, void *host_a);
+int mg_vc_set_form(mg_handle h, int form);
+int mg_vc_residual(mg_handle h, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
+int mg_vc_smooth(mg_handle h, int level, int smoother, int sweeps, int arr_x, int arr_rhs);
+int mg_vc_coarse_solve(mg_handle h, int level, int arr_x, int arr_rhs, mg_cycle_stats *st);
+int mg_vc_cycle(mg_handle h, mg_cycle_stats *st);
+int mg_vc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
+int mg_vc_pcg_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
+int mg_vc_direction(mg_handle h, double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq);
+
 /* Diagonal shift (extension, no reference counterpart): from this call on the handle works on sigma I + A, sigma >= 0 --
  * the operator of an implicit time step or a screened-Poisson / Helmholtz-type solve. On every level the diagonal becomes
  * cd0_l + sigma (one fp64 addition, then cast to the working dtype like every coefficient), cd0_l being the diagonal the

@@ -151,6 +151,8 @@ EXPORTS = [
     "mg_mixed_set_rhs", "mg_mixed_set_solution", "mg_mixed_get_solution", "mg_mixed_solve", "mg_mixed_kernel",
     "mg_mixed_set_rhs_device", "mg_mixed_set_solution_device", "mg_mixed_get_solution_device",
     "mg_o4_residual", "mg_o4_correct_residual", "mg_o4_solve",
+    "mg_vc_set_coefficient", "mg_vc_set_coefficient_device", "mg_vc_get_coefficient", "mg_vc_set_form", "mg_vc_residual", "mg_vc_smooth",
+    "mg_vc_coarse_solve", "mg_vc_cycle", "mg_vc_solve", "mg_vc_pcg_solve", "mg_vc_direction",
     "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_set_source_device", "mg_heat_step", "mg_heat_rhs",
     "mg_eig_solve", "mg_eig_set_vector", "mg_eig_get_vector", "mg_eig_set_vector_device", "mg_eig_get_vector_device",
     "mg_eig_block", "mg_eig_kernel",
@@ -217,6 +219,17 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_o4_residual.argtypes = [vp, i, i, i, dp]
     L.mg_o4_correct_residual.argtypes = [vp, i, i, i, i, i, dp]
     L.mg_o4_solve.argtypes = [vp, C.c_double, i, i, dp, i, C.POINTER(i), C.POINTER(MgO4Stats)]
+    L.mg_vc_set_coefficient.argtypes = [vp, vp]
+    L.mg_vc_set_coefficient_device.argtypes = [vp, vp, i, vp]
+    L.mg_vc_get_coefficient.argtypes = [vp, i, vp]
+    L.mg_vc_set_form.argtypes = [vp, i]
+    L.mg_vc_residual.argtypes = [vp, i, i, i, i, dp]
+    L.mg_vc_smooth.argtypes = [vp, i, i, i, i, i]
+    L.mg_vc_coarse_solve.argtypes = [vp, i, i, i, C.POINTER(MgCycleStats)]
+    L.mg_vc_cycle.argtypes = [vp, C.POINTER(MgCycleStats)]
+    L.mg_vc_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
+    L.mg_vc_pcg_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgKrylovStats)]
+    L.mg_vc_direction.argtypes = [vp, C.c_double, i, i, i, i, dp]
     L.mg_set_shift.argtypes = [vp, C.c_double]
     L.mg_get_shift.argtypes = [vp, dp]
     L.mg_heat_set_source.argtypes = [vp, vp]
@@ -554,6 +567,53 @@ class Solver:
 
     def get_shift(self) -> float:
         s = C.c_double(0); _check(self.lib.mg_get_shift(self.h, C.byref(s))); return s.value
+
+    # -- variable-coefficient diffusion sigma u - div(a grad u) (mg_vc_*, include/mg_hip.h)
+    def vc_set_coefficient(self, a):
+        """mg_vc_set_coefficient: the nodal coefficient a > 0 of level 0 (coarser levels: its full weighting)"""
+        a = self._host(a, 0); _check(self.lib.mg_vc_set_coefficient(self.h, a.ctypes.data_as(C.c_void_p)))
+
+    def vc_set_coefficient_device(self, a, stream=0):
+        """mg_vc_set_coefficient_device: the same from a dense device array on the caller's stream"""
+        ptr, dt = device_view(a, self.level_shape(0))
+        _check(self.lib.mg_vc_set_coefficient_device(self.h, ptr, dt, stream or None))
+
+    def vc_get_coefficient(self, level):
+        a = np.empty(self.level_shape(level), self.np)
+        _check(self.lib.mg_vc_get_coefficient(self.h, level, a.ctypes.data_as(C.c_void_p))); return a
+
+    def vc_set_form(self, form):
+        """mg_vc_set_form (tests and measurement tools): 1 = the plain kernels on every level, 0 = the default"""
+        _check(self.lib.mg_vc_set_form(self.h, int(form)))
+
+    def vc_residual(self, level, arr_x, arr_rhs, arr_r=-1) -> float:
+        s = C.c_double(0); _check(self.lib.mg_vc_residual(self.h, level, arr_x, arr_rhs, arr_r, C.byref(s))); return s.value
+
+    def vc_smooth(self, level, smoother, sweeps, arr_x, arr_rhs):
+        _check(self.lib.mg_vc_smooth(self.h, level, smoother, sweeps, arr_x, arr_rhs))
+
+    def vc_coarse_solve(self, level, arr_x, arr_rhs) -> MgCycleStats:
+        st = MgCycleStats(); _check(self.lib.mg_vc_coarse_solve(self.h, level, arr_x, arr_rhs, C.byref(st))); return st
+
+    def vc_cycle(self) -> MgCycleStats:
+        st = MgCycleStats(); _check(self.lib.mg_vc_cycle(self.h, C.byref(st))); return st
+
+    def vc_solve(self, tol=1e-11, maxit=1000):
+        """mg_vc_solve -> (hist, per-cycle MgCycleStats)"""
+        hist = (C.c_double * (maxit + 1))(); nh = C.c_int(0)
+        stats = (MgCycleStats * max(maxit, 1))()
+        _check(self.lib.mg_vc_solve(self.h, tol, maxit, hist, maxit + 1, C.byref(nh), stats))
+        return np.array(hist[:nh.value]), list(stats[:nh.value - 1])
+
+    def vc_pcg_solve(self, tol=1e-11, maxit=1000):
+        """mg_vc_pcg_solve: flexible CG on L preconditioned by one mg_vc_cycle -> (hist, MgKrylovStats)"""
+        hist = (C.c_double * (maxit + 1))(); nh = C.c_int(0); st = MgKrylovStats()
+        _check(self.lib.mg_vc_pcg_solve(self.h, tol, maxit, hist, maxit + 1, C.byref(nh), C.byref(st)))
+        return np.array(hist[:min(nh.value, maxit + 1)]), st
+
+    def vc_direction(self, beta, arr_z, arr_p, arr_pn, arr_q) -> float:
+        """mg_vc_direction: arr_pn = arr_z + beta arr_p, arr_q = L arr_pn (both 0 on Dirichlet nodes) -> sum pn.q"""
+        s = C.c_double(0); _check(self.lib.mg_vc_direction(self.h, beta, arr_z, arr_p, arr_pn, arr_q, C.byref(s))); return s.value
 
     def heat_set_source(self, f):
         """mg_heat_set_source: the source term f of u_t = -A0 u + f (level-0 array of the handle's dtype); None: f = 0"""

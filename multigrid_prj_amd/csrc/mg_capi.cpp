@@ -269,6 +269,48 @@ int mg_o4_solve(mg_handle h, double tol, int maxit, int inner_cycles, double *hi
     if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_o4_solve: bad history buffer");
     return guarded([&] { return h->impl->o4_solve(tol, maxit, inner_cycles, hist, hist_cap, n_hist, st); });
 }
+int mg_vc_set_coefficient(mg_handle h, const void *host_a) { MG_H(h); return guarded([&] { return h->impl->vc_set_coefficient(host_a); }); }
+int mg_vc_set_coefficient_device(mg_handle h, const void *dev_a, int dtype, void *stream)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->vc_set_coefficient_device(dev_a, dtype, static_cast<hipStream_t>(stream)); });
+}
+int mg_vc_get_coefficient(mg_handle h, int level, void *host_a) { MG_H(h); return guarded([&] { return h->impl->vc_get_coefficient(level, host_a); }); }
+int mg_vc_set_form(mg_handle h, int form) { MG_H(h); return guarded([&] { return h->impl->vc_set_form(form); }); }
+int mg_vc_residual(mg_handle h, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->vc_residual(level, arr_x, arr_rhs, arr_r, sumsq_r); });
+}
+int mg_vc_smooth(mg_handle h, int level, int smoother, int sweeps, int arr_x, int arr_rhs)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->vc_smooth(level, smoother, sweeps, arr_x, arr_rhs); });
+}
+int mg_vc_coarse_solve(mg_handle h, int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->vc_coarse_solve(level, arr_x, arr_rhs, st); });
+}
+int mg_vc_cycle(mg_handle h, mg_cycle_stats *st) { MG_H(h); return guarded([&] { return h->impl->vc_cycle(st); }); }
+int mg_vc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    MG_H(h);
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_vc_solve: bad history buffer");
+    return guarded([&] { return h->impl->vc_solve(tol, maxit, hist, hist_cap, n_hist, per_cycle); });
+}
+int mg_vc_pcg_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    MG_H(h);
+    if (maxit < 0) return bad("mg_vc_pcg_solve: negative maxit");
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_vc_pcg_solve: bad history buffer");
+    return guarded([&] { return h->impl->vc_pcg_solve(tol, maxit, hist, hist_cap, n_hist, st); });
+}
+int mg_vc_direction(mg_handle h, double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->vc_direction(beta, arr_z, arr_p, arr_pn, arr_q, pq); });
+}
 int mg_set_shift(mg_handle h, double sigma) { MG_H(h); return guarded([&] { return h->impl->set_shift(sigma); }); }
 int mg_get_shift(mg_handle h, double *sigma)
 {

@@ -1,5 +1,5 @@
 // mg_drivers.cpp -- the solve drivers of mg::Solver: everything that calls the cycle from above (mg_solve, mg_pcg_*, mg_fmg*,
-// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*, mg_eig_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
+// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*, mg_eig_*, mg_vc_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
 // Reference call structure being replaced by solve(): the outer loop of src/main.cpp:72-116.
 #include "mg_solver.h"
 #include "mg_dense.h"
@@ -126,14 +126,14 @@ int Solver::krylov_alloc()
 // z = M r: the cycle code works on level 0's U / RHS slots, so z and r take them for the duration (pointer swap, no copy).
 // The cycle may itself leave its result in the array that was TMP (out-of-place sweeps swap U / TMP): whatever U points
 // at afterwards is z, and TMP keeps the other buffer.
-int Solver::precondition(void **z, void *r)
+int Solver::precondition(void **z, void *r, bool vc)
 {
     Level &L0 = lv_[0];
     void *const x_base = L0.base[MG_ARR_U], *const b_base = L0.base[MG_ARR_RHS];
     MG_HIP(hipMemsetAsync(*z, 0, L0.alloc_elems * esize(), stream_));
     L0.base[MG_ARR_U] = *z;
     L0.base[MG_ARR_RHS] = r;
-    const int rc = outer_iteration_enqueue();
+    const int rc = vc ? vc_cycle_enqueue() : outer_iteration_enqueue();
     *z = L0.base[MG_ARR_U];
     L0.base[MG_ARR_U] = x_base;
     L0.base[MG_ARR_RHS] = b_base;
@@ -1074,6 +1074,366 @@ int Solver::eig_kernel(int kernel, int nw, int np, const double *coef, const dou
     }
     if (gram) return d_.dtype == MG_F64 ? eig_gram_t<double>(EIG_GRAM_FULL, nw, np, G, H) : eig_gram_t<float>(EIG_GRAM_FULL, nw, np, G, H);
     return d_.dtype == MG_F64 ? eig_combine_t<double>(nw, np, coef, theta, sums) : eig_combine_t<float>(nw, np, coef, theta, sums);
+}
+
+// ---------------------------------------------------------------- variable-coefficient diffusion (mg_vc_*), DESIGN.md section 18
+// L = sigma I - div(a grad .) with a nodal coefficient array per level (Level::vc_a; level l + 1 is the full-weighted level
+// l). The kernels are in mg_vc.hip; the transfers are the handle's own. Everything goes launch by launch: no fused pairs,
+// no LDS sub-cycle, no folded prolongation -- those kernels carry the constant stencil in registers.
+int Solver::vc_check(const char *fn, unsigned need)
+{
+    MG_TRY(driver_begin(fn, REFUSE_DIST | ((need & VC_NEED_CYCLE) ? REFUSE_STAGE_CB : 0u)));
+    if (!vc_set_) { set_last_error(std::string(fn) + ": no coefficient set (call mg_vc_set_coefficient first)"); return MG_ERR_BAD_ARG; }
+    if ((need & VC_NEED_CYCLE) && !is_vwf(d_.cycle)) {
+        set_last_error(std::string(fn) + ": not on a sawtooth handle (the cycle must be MG_CYCLE_V, MG_CYCLE_W or MG_CYCLE_F)");
+        return MG_ERR_BAD_ARG;
+    }
+    if ((need & (VC_NEED_CYCLE | VC_NEED_SMOOTHER)) && d_.smoother != MG_SMOOTH_JACOBI && d_.smoother != MG_SMOOTH_RBGS) {
+        set_last_error(std::string(fn) + ": the handle's smoother must be MG_SMOOTH_JACOBI or MG_SMOOTH_RBGS");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::vc_alloc()
+{
+    for (auto &L : lv_)   // slot by slot: a call that failed half way leaves the rest to the next one
+        if (!L.vc_a) MG_TRY(alloc_zeroed(&L.vc_a, L.alloc_elems * esize()));
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::vc_restrict_all_t()
+{
+    for (int l = 0; l + 1 < d_.levels; l++) launch_restrict_fw<T>(stream_, lv_[l].g, lv_[l + 1].g, vcptr<T>(l), vcptr<T>(l + 1));
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::vc_set_coefficient(const void *host)
+{
+    MG_TRY(driver_begin("mg_vc_set_coefficient", REFUSE_DIST));
+    if (!host) { set_last_error("mg_vc_set_coefficient: null array"); return MG_ERR_BAD_ARG; }
+    const Geom &g = lv_[0].g;
+    const size_t n = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz;
+    bool ok = true;
+    if (d_.dtype == MG_F64) { const double *a = static_cast<const double *>(host); for (size_t i = 0; i < n && ok; i++) ok = a[i] > 0.0 && std::isfinite(a[i]); }
+    else { const float *a = static_cast<const float *>(host); for (size_t i = 0; i < n && ok; i++) ok = a[i] > 0.0f && std::isfinite(a[i]); }
+    if (!ok) { set_last_error("mg_vc_set_coefficient: every value must be finite and > 0"); return MG_ERR_BAD_ARG; }
+    MG_TRY(vc_alloc());
+    MG_TRY(stage_copy(reinterpret_cast<char *>(lv_[0].vc_a) + (size_t)lv_[0].gh * (size_t)g.plane * esize(), g, esize(),
+                      const_cast<void *>(host), true));
+    MG_TRY(d_.dtype == MG_F64 ? vc_restrict_all_t<double>() : vc_restrict_all_t<float>());
+    vc_set_ = true;
+    return MG_OK;
+}
+
+int Solver::vc_set_coefficient_device(const void *dense, int dense_dtype, hipStream_t caller)
+{
+    const char *fn = "mg_vc_set_coefficient_device";
+    MG_TRY(driver_begin(fn, REFUSE_DIST));
+    const Geom &g = lv_[0].g;
+    MG_TRY(device_check(fn, dense, dense_dtype, g));   // nothing is allocated for an array that is refused
+    MG_TRY(vc_alloc());
+    MG_TRY(device_copy(fn, reinterpret_cast<char *>(lv_[0].vc_a) + (size_t)lv_[0].gh * (size_t)g.plane * esize(), g, esize(),
+                       const_cast<void *>(dense), dense_dtype, true, caller));
+    MG_TRY(d_.dtype == MG_F64 ? vc_restrict_all_t<double>() : vc_restrict_all_t<float>());
+    vc_set_ = true;
+    return MG_OK;
+}
+
+int Solver::vc_get_coefficient(int level, void *host)
+{
+    MG_TRY(vc_check("mg_vc_get_coefficient", 0));
+    if (!host || level < 0 || level >= d_.levels) { set_last_error("mg_vc_get_coefficient: bad level / null array"); return MG_ERR_BAD_ARG; }
+    const Level &L = lv_[level];
+    return stage_copy(reinterpret_cast<char *>(L.vc_a) + (size_t)L.gh * (size_t)L.g.plane * esize(), L.g, esize(), host, false);
+}
+
+int Solver::vc_set_form(int form)
+{
+    if (form != 0 && form != 1) { set_last_error("mg_vc_set_form: form must be 0 (default) or 1 (the plain kernels everywhere)"); return MG_ERR_BAD_ARG; }
+    vc_plain_ = form == 1;
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::vc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
+{
+    Level &L = lv_[level];
+    if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
+    const int np = launch_vc_residual<T>(stream_, L.g, L.coef, shift_, ptr<T>(ax, level), vcptr<T>(level), ptr<T>(ar, level),
+                                         arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr, d_partials_, o4_partials_cap_, vc_plain_);
+    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_VC_SUM);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::vc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
+{
+    MG_TRY(vc_check("mg_vc_residual", 0));
+    if (!check_arr(arr_x, level, "mg_vc_residual") || !check_arr(arr_rhs, level, "mg_vc_residual")) return MG_ERR_BAD_ARG;
+    if (arr_r >= 0 && (!check_arr(arr_r, level, "mg_vc_residual") || arr_r == arr_x || arr_r == arr_rhs)) {
+        set_last_error("mg_vc_residual: bad output array");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_TRY(d_.dtype == MG_F64 ? vc_residual_t<double>(level, arr_x, arr_rhs, arr_r, true) : vc_residual_t<float>(level, arr_x, arr_rhs, arr_r, true));
+    if (sumsq_r) {
+        MG_TRY(fetch_scalars(SC_VC_SUM, d_scal_ + SC_VC_SUM));
+        *sumsq_r = h_scal_[SC_VC_SUM];
+    }
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::vc_smooth_t(int level, int smoother, int sweeps, int ax, int ar)
+{
+    Level &L = lv_[level];
+    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
+    for (int s = 0; s < sweeps; s++) {
+        if (smoother == MG_SMOOTH_JACOBI) {   // out of place into TMP, then the two pointers are swapped (as smooth_t)
+            launch_vc_jacobi<T>(stream_, L.g, L.coef, shift_, (T)d_.omega, ptr<T>(ax, level), vcptr<T>(level), ptr<T>(ar, level),
+                                ptr<T>(MG_ARR_TMP, level), vc_plain_);
+            std::swap(L.base[ax], L.base[MG_ARR_TMP]);
+        } else {
+            for (int colour = 0; colour < 2; colour++)
+                launch_vc_rb_colour<T>(stream_, L.g, L.coef, shift_, colour, ptr<T>(ax, level), vcptr<T>(level), ptr<T>(ar, level));
+        }
+    }
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::vc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs)
+{
+    MG_TRY(vc_check("mg_vc_smooth", 0));
+    if (!check_arr(arr_x, level, "mg_vc_smooth") || !check_arr(arr_rhs, level, "mg_vc_smooth")) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs || sweeps < 0 ||
+        (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS)) {
+        set_last_error("mg_vc_smooth: bad array / sweeps, or a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? vc_smooth_t<double>(level, smoother, sweeps, arr_x, arr_rhs)
+                              : vc_smooth_t<float>(level, smoother, sweeps, arr_x, arr_rhs);
+}
+
+template <typename T>
+int Solver::vc_coarse_t(int level, int ax, int ar)
+{
+    Level &L = lv_[level];
+    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
+    launch_vc_coarse<T>(stream_, L.g, L.coef, shift_, (T)d_.omega, d_.smoother, ptr<T>(ax, level), ptr<T>(MG_ARR_TMP, level),
+                        ptr<T>(ar, level), vcptr<T>(level), d_.coarse_maxit, d_.coarse_tol, d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0,
+                        d_coarse_);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::vc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
+{
+    MG_TRY(vc_check("mg_vc_coarse_solve", VC_NEED_SMOOTHER));
+    if (!check_arr(arr_x, level, "mg_vc_coarse_solve") || !check_arr(arr_rhs, level, "mg_vc_coarse_solve")) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs) { set_last_error("mg_vc_coarse_solve: bad array"); return MG_ERR_BAD_ARG; }
+    MG_TRY(d_.dtype == MG_F64 ? vc_coarse_t<double>(level, arr_x, arr_rhs) : vc_coarse_t<float>(level, arr_x, arr_rhs));
+    return fetch_cycle_stats(st);
+}
+
+// cyc(l, kind) of mg_desc.h with the vc kernels, launch by launch
+template <typename T>
+int Solver::vc_cycle_rec_t(int l, int kind)
+{
+    const int L = d_.levels;
+    if (l == L - 1) {
+        const long long pts = (long long)lv_[l].g.nx * lv_[l].g.ny * lv_[l].g.gnz;
+        if (pts > 32768 && d_.coarse_mode == MG_COARSE_FIXED) {   // too big for one workgroup: chip-wide sweeps, as coarse_level_t
+            MG_TRY(vc_smooth_t<T>(l, d_.smoother, d_.coarse_maxit, MG_ARR_U, MG_ARR_RHS));
+            h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
+            h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;   // not evaluated on this path
+            MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
+        } else {
+            MG_TRY(vc_coarse_t<T>(l, MG_ARR_U, MG_ARR_RHS));
+        }
+        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
+        return MG_OK;
+    }
+    MG_TRY(vc_smooth_t<T>(l, d_.smoother, d_.nu_pre, MG_ARR_U, MG_ARR_RHS));
+    MG_TRY(vc_residual_t<T>(l, MG_ARR_U, MG_ARR_RHS, MG_ARR_TMP, false));
+    MG_TRY(restrict_t<T>(l, d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
+    MG_TRY(zero_array(MG_ARR_U, l + 1));
+    MG_TRY(vc_cycle_rec_t<T>(l + 1, kind));
+    if (l + 1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(vc_cycle_rec_t<T>(l + 1, MG_CYCLE_W));   // continues from U(l + 1), RHS(l + 1) unchanged
+    if (l + 1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(vc_cycle_rec_t<T>(l + 1, MG_CYCLE_V));
+    MG_TRY(prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U));
+    return vc_smooth_t<T>(l, d_.smoother, d_.nu_post, MG_ARR_U, MG_ARR_RHS);
+}
+
+template <typename T>
+int Solver::vc_cycle_enqueue_t()
+{
+    if (d_.cycle == MG_CYCLE_V) return vc_cycle_rec_t<T>(0, MG_CYCLE_V);
+    MG_TRY(stats_begin());   // W and F make several coarse solves: summed on the device, as cycle_from_t
+    const int rc = vc_cycle_rec_t<T>(0, d_.cycle);
+    acc_stats_ = false;
+    MG_TRY(rc);
+    return stats_end();
+}
+
+int Solver::vc_cycle_enqueue() { return d_.dtype == MG_F64 ? vc_cycle_enqueue_t<double>() : vc_cycle_enqueue_t<float>(); }
+
+int Solver::vc_cycle(mg_cycle_stats *st)
+{
+    MG_TRY(vc_check("mg_vc_cycle", VC_NEED_CYCLE));
+    MG_TRY(vc_cycle_enqueue());
+    return fetch_cycle_stats(st);
+}
+
+// mg_solve's loop and history on L; desc.outer_pre_gs is ignored (the lexicographic sweep has no vc form)
+template <typename T>
+int Solver::vc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    double nb = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    launch_cg_boundary_copy<T>(stream_, lv_[0].g, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0));   // U = RHS on the Dirichlet nodes
+    MG_HIP(hipGetLastError());
+    int nh = 0;
+    auto norm = [&]() -> int {
+        MG_TRY(vc_residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
+        MG_TRY(fetch_scalars(SC_VC_SUM, d_scal_ + SC_VC_SUM));
+        const double rel = std::sqrt(h_scal_[SC_VC_SUM] / nb);
+        if (hist && nh < hist_cap) hist[nh] = rel;
+        nh++;
+        return MG_OK;
+    };
+    MG_TRY(norm());
+    for (int it = 0; it < maxit; it++) {
+        MG_TRY(vc_cycle_enqueue());
+        MG_TRY(fetch_cycle_stats(per_cycle ? &per_cycle[it] : nullptr));
+        MG_TRY(norm());
+        if (std::sqrt(h_scal_[SC_VC_SUM] / nb) <= tol) break;
+    }
+    if (n_hist) *n_hist = nh;
+    return MG_OK;
+}
+
+int Solver::vc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    MG_TRY(vc_check("mg_vc_solve", VC_NEED_CYCLE));
+    if (maxit < 0) { set_last_error("mg_vc_solve: negative maxit"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? vc_solve_t<double>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
+                              : vc_solve_t<float>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
+}
+
+// pcg_t with A -> L and M r = one vc cycle from zero
+template <typename T>
+int Solver::vc_pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    Level &L0 = lv_[0];
+    const Geom &g = L0.g;
+    auto kp = [&](int k) { return reinterpret_cast<T *>(kry_[k]) + L0.gh * g.plane; };
+    T *const x = ptr<T>(MG_ARR_U, 0);
+    const T *const b = ptr<T>(MG_ARR_RHS, 0);
+    mg_krylov_stats out{0, 0, 0.0, 0.0};
+    int nh = 0;
+    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
+    auto residual_sum = [&](T *r, double *v) -> int {   // r = b - L x (r may be null), *v = r.r; synchronises
+        const int np = launch_vc_residual<T>(stream_, g, L0.coef, shift_, ptr<T>(MG_ARR_U, 0), vcptr<T>(0), b, r, d_partials_,
+                                             o4_partials_cap_, vc_plain_);
+        launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_VC_SUM);
+        MG_HIP(hipGetLastError());
+        MG_TRY(fetch_scalars(SC_VC_SUM, d_scal_ + SC_VC_SUM));
+        *v = h_scal_[SC_VC_SUM];
+        return MG_OK;
+    };
+
+    double nb = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    launch_cg_boundary_copy<T>(stream_, g, x, b);   // as pcg_t: afterwards r, z, p and q vanish on the boundary
+    MG_HIP(hipGetLastError());
+    double rr0 = 0;
+    MG_TRY(residual_sum(kp(KR), &rr0));
+    record(std::sqrt(rr0 / nb));
+
+    if (nb == 0.0 || rr0 == 0.0) {
+        out.status = 0;
+    } else if (maxit == 0) {
+        out.status = 1;
+    } else {
+        MG_HIP(hipMemsetAsync(d_cg_, 0, sizeof(CgScalars), stream_));
+        int pc = KP0, pn = KP1;
+        MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));
+        auto direction = [&](int mode) -> int {
+            MG_TRY(precondition(&kry_[KZ], kry_[KR], true));
+            int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
+            np = launch_vc_cg_direction<T>(stream_, g, L0.coef, shift_, kp(KZ), kp(pc), vcptr<T>(0), kp(pn), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, CG_TAIL_ALPHA, d_cg_part_, np, d_cg_);
+            MG_HIP(hipGetLastError());
+            std::swap(pc, pn);
+            return MG_OK;
+        };
+        MG_TRY(direction(CG_TAIL_FIRST));
+        for (int k = 0; k < maxit; k++) {
+            const int np = launch_cg_update<T>(stream_, g, ptr<T>(MG_ARR_U, 0), kp(pc), kp(KR), kp(KQ), d_cg_, d_cg_part_);
+            launch_cg_tail(stream_, CG_TAIL_RR, d_cg_part_, np, d_cg_);
+            MG_HIP(hipGetLastError());
+            MG_HIP(hipMemcpyAsync(h_cg_, d_cg_, sizeof(CgScalars), hipMemcpyDeviceToHost, stream_));
+            MG_HIP(hipStreamSynchronize(stream_));   // the one host synchronisation per iteration: the stopping test
+            if (h_cg_->bad) { out.status = 2; break; }
+            out.iters = k + 1;
+            const double rel = std::sqrt(h_cg_->rr / nb);
+            record(rel);
+            if (rel <= tol) { out.status = 0; break; }
+            if (k + 1 == maxit) { out.status = 1; break; }
+            MG_TRY(direction(CG_TAIL_BETA));
+        }
+    }
+    double nr = 0;
+    MG_TRY(residual_sum((T *)nullptr, &nr));   // the true residual of the returned x
+    out.relres_true = std::sqrt(nr / nb);
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
+// the direction kernel alone on level-0 arrays (mg_vc_direction): kernel-level checks and measurements, as mg_pcg_kernel
+template <typename T>
+int Solver::vc_direction_t(double beta, const int *a, double *pq)
+{
+    const Level &L0 = lv_[0];
+    *h_cg_ = CgScalars{};
+    h_cg_->alpha = h_cg_->beta = beta;
+    MG_HIP(hipMemcpyAsync(d_cg_, h_cg_, sizeof(CgScalars), hipMemcpyHostToDevice, stream_));
+    const int np = launch_vc_cg_direction<T>(stream_, L0.g, L0.coef, shift_, ptr<T>(a[0], 0), ptr<T>(a[1], 0), vcptr<T>(0), ptr<T>(a[2], 0),
+                                             ptr<T>(a[3], 0), d_cg_, d_cg_part_);
+    launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
+    MG_HIP(hipGetLastError());
+    if (pq) {
+        MG_TRY(fetch_scalars(SC_CG_DOT, d_cg_dot_, 1));
+        *pq = h_scal_[SC_CG_DOT];
+    }
+    return MG_OK;
+}
+
+int Solver::vc_direction(double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq)
+{
+    MG_TRY(vc_check("mg_vc_direction", 0));
+    const int a[4] = {arr_z, arr_p, arr_pn, arr_q};
+    for (int i = 0; i < 4; i++) {
+        if (!check_arr(a[i], 0, "mg_vc_direction")) return MG_ERR_BAD_ARG;
+        for (int j = 0; j < i; j++)
+            if (a[i] == a[j]) { set_last_error("mg_vc_direction: the arrays must be distinct"); return MG_ERR_BAD_ARG; }
+    }
+    if (arr_pn == MG_ARR_RHS || arr_q == MG_ARR_RHS) lv_[0].rhs_halo_ok = false;
+    MG_TRY(krylov_scalars_alloc());
+    return d_.dtype == MG_F64 ? vc_direction_t<double>(beta, a, pq) : vc_direction_t<float>(beta, a, pq);
+}
+
+int Solver::vc_pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    MG_TRY(vc_check("mg_vc_pcg_solve", VC_NEED_CYCLE));
+    MG_TRY(krylov_alloc());
+    return d_.dtype == MG_F64 ? vc_pcg_t<double>(tol, maxit, hist, hist_cap, n_hist, st)
+                              : vc_pcg_t<float>(tol, maxit, hist, hist_cap, n_hist, st);
 }
 
 }  // namespace mg

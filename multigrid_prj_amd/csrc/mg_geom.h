@@ -301,6 +301,15 @@ inline bool o4_march_ok(int dim, int nx, int ny, int nz, int elem_size)
     return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
 }
 
+// ---- which levels the marching tile of mg_vc.hip takes (residual and Jacobi sweep of mg_vc_*); the plain form takes every
+// other one, and every red-black colour pass. The shape test of o4_march_ok: the tile is the same one with radius 1, and a
+// row with fewer than 16 full vectors leaves three quarters of a wave idle. Pure; tests/test_vc_cpu.py pins it.
+inline bool vc_march_ok(int dim, int nx, int ny, int nz, int elem_size)
+{
+    const int v = 16 / elem_size;
+    return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
+}
+
 struct CoarseOut {
     int iters;
     int flag;

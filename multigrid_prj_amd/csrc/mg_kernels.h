@@ -303,6 +303,29 @@ template <typename T>
 int launch_o4_correct_residual(hipStream_t s, const Geom &g, const double w[3], double sigma, const T *u, const T *e, const T *b,
                                T *u_out, T *r, double *partials, int cap);
 
+// ---- variable-coefficient operator (mg_vc.hip, driven by Solver::vc_*) ----
+// coef = {cx, cy, cz, cd} of the level in fp64 (cd is not used: the diagonal is built from a), sigma the handle's shift; a:
+// the level's coefficient array (level-shaped, ghost planes and padding zero). plain: never the marching tile.
+// r = b - L u (r == nullptr: norm only); one partial sum of r^2 per workgroup in `partials` (room for `cap`), returns how many
+template <typename T>
+int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, const T *u, const T *a, const T *b, T *r,
+                       double *partials, int cap, bool plain);
+// one Jacobi sweep, out of place (out must not alias u)
+template <typename T>
+void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, T omega, const T *u, const T *a, const T *b,
+                      T *out, bool plain);
+// one colour pass of red-black Gauss-Seidel, in place
+template <typename T>
+void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int colour, T *u, const T *a, const T *b);
+// launch_coarse_solve's loop with the vc sweep (smoother 1: Jacobi, 2: red-black) and the vc residual, one workgroup
+template <typename T>
+void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, T omega, int smoother, T *x, T *tmp,
+                      const T *rhs, const T *a, int maxit, double tol, int fixed, CoarseOut *d_out);
+// launch_cg_direction_apply with q = L pn; partials of pn.q (at most cg_partials_capacity() / 2), returns how many
+template <typename T>
+int launch_vc_cg_direction(hipStream_t s, const Geom &g, const double coef[4], double sigma, const T *z, const T *p, const T *a, T *pn,
+                           T *q, const CgScalars *sc, double *partials);
+
 // ---- device-resident array I/O (mg_io.hip, driven by Solver::device_copy) ----
 // padded: local plane 0 of a level-shaped array of geometry g with elements P; dense: the caller's dense device array of
 // g.nx * g.ny * g.nz elements D at any element-aligned address. to_padded: padded = (P)dense, padding columns written as

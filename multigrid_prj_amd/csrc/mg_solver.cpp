@@ -162,6 +162,7 @@ Solver::~Solver()
     for (auto &b : mx_) if (b) (void)hipFree(b);
     for (auto &b : o4_) if (b) (void)hipFree(b);
     if (heat_f_) (void)hipFree(heat_f_);
+    for (auto &L : lv_) if (L.vc_a) (void)hipFree(L.vc_a);
     for (auto &fam : eig_)
         for (auto &b : fam) if (b) (void)hipFree(b);
     if (d_eig_part_) (void)hipFree(d_eig_part_);
@@ -1834,6 +1835,7 @@ int Solver::timer_stop(double *ms)
     template int Solver::residual_t<T>(int, int, int, int, bool);                           \
     template int Solver::sumsq_t<T>(int, int);                                              \
     template int Solver::restrict_t<T>(int, int, int, int);                                 \
+    template int Solver::prolong_t<T>(int, int, int, int);                                  \
     template int Solver::coarse_level_t<T>(int, int, int, bool);                            \
     template int Solver::vcycle_rec_t<T>(int, bool, int); \
     template int Solver::cycle_from_t<T>(int); \

@@ -3,7 +3,7 @@
 // (vcycle_rec_t for the V, W and F kinds, visit_child_t, subcycle_launch_t, cycle_from_t, cycle_enqueue*, cycle); mg_drivers.cpp
 // holds what calls the cycle from above (solve, pcg_*, fmg*, subcycle, mixed_*, set_shift, heat_*, eig_*) and the helpers those drivers share.
 // The member templates that mg_drivers.cpp calls and mg_solver.cpp defines (smooth_t, pair_norm_ok, residual_t, sumsq_t,
-// restrict_t, coarse_level_t, vcycle_rec_t, cycle_from_t, subcycle_launch_t) cross the file boundary by ONE mechanism: explicit instantiation definitions
+// restrict_t, prolong_t, coarse_level_t, vcycle_rec_t, cycle_from_t, subcycle_launch_t) cross the file boundary by ONE mechanism: explicit instantiation definitions
 // for double and float, in one block at the end of mg_solver.cpp.
 #ifndef MG_SOLVER_H
 #define MG_SOLVER_H
@@ -70,6 +70,7 @@ struct Level {
                                  // (MG_OVERLAP_MIN_MB, decided on the thinnest slab: the same answer on every rank)
     bool rhs_halo_ok = false;    // distributed level: the RHS array's first ghost planes hold the neighbours' planes
     void *zebra = nullptr;       // MG_SMOOTH_ZEBRA_Y / _X: cp(j), den(j) of the line solve (2 * ny or 2 * nx values, device)
+    void *vc_a = nullptr;        // mg_vc_*: the level's diffusion coefficient, level-shaped like base[] (allocated by the first set)
 };
 
 class Solver {
@@ -145,6 +146,19 @@ public:
     int eig_vector_device(int family, int j, void *dense, int dense_dtype, bool to_handle, hipStream_t caller);
     int eig_block() const { return eig_m_; }
     int eig_kernel(int kernel, int nw, int np, const double *coef, const double *theta, double *G, double *H, double *sums);
+    // variable-coefficient diffusion -div(a grad u) + sigma u (mg_vc_*): one coefficient array per level, allocated by the
+    // first vc_set_coefficient*; level l + 1 is the full-weighted level l
+    int vc_set_coefficient(const void *host);
+    int vc_set_coefficient_device(const void *dense, int dense_dtype, hipStream_t caller);
+    int vc_get_coefficient(int level, void *host);
+    int vc_set_form(int form);   // tests and measurement tools: 1 = the plain kernels on every level, 0 = the default
+    int vc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
+    int vc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs);
+    int vc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st);
+    int vc_cycle(mg_cycle_stats *st);
+    int vc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
+    int vc_pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
+    int vc_direction(double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq);   // the direction kernel alone
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -237,7 +251,8 @@ private:
     template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     // *z = M r: one mg_solve outer iteration from zero with the buffers *z and r in level 0's U / RHS slots. The cycle may leave
     // its result in the buffer that was TMP: *z is whatever U points at afterwards, and TMP keeps the other buffer.
-    int precondition(void **z, void *r);
+    // vc: the cycle is vc_cycle_enqueue's (mg_vc_pcg_solve) and no Gauss-Seidel sweeps come before it
+    int precondition(void **z, void *r, bool vc = false);
     template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
     int mixed_check(const char *fn, unsigned refuse = REFUSE_DIST);      // MG_F32, then driver_begin(fn, refuse)
@@ -293,7 +308,8 @@ private:
         SC_CG_DOT1 = 4,
         SC_MX_SUM = 5,    // d_mx_sum_: mixed_solve, mixed_kernel
         SC_O4_SUM = 6,    // sum r^2 of the fourth-order residual: o4_solve, o4_residual, o4_correct_residual (written on the device)
-        SC_COUNT = 8      // the seven slots, padded to one 64-byte line
+        SC_VC_SUM = 7,    // sum r^2 of the variable-coefficient residual: vc_residual, vc_solve, vc_pcg_solve (written on the device)
+        SC_COUNT = 8      // the eight slots: one 64-byte line
     };
     double *d_scal_ = nullptr;      // [SC_COUNT]
     CoarseOut *d_coarse_ = nullptr;
@@ -350,6 +366,22 @@ private:
     template <typename T> int heat_step_t(double dt, double theta, int nsteps, int cycles_per_step);
     void *heat_f_ = nullptr;
     bool heat_has_f_ = false;
+    // variable-coefficient drivers (mg_vc_*): Level::vc_a of every level, valid once vc_set_ is true
+    bool vc_set_ = false, vc_plain_ = false;
+    enum : unsigned { VC_NEED_CYCLE = 1u, VC_NEED_SMOOTHER = 2u };   // what vc_check asks of the descriptor beyond a coefficient
+    int vc_check(const char *fn, unsigned need);   // driver_begin, a coefficient is set, the cycle / smoother the vc drivers run
+    int vc_alloc();
+    template <typename T> T *vcptr(int level) const { return reinterpret_cast<T *>(lv_[level].vc_a) + lv_[level].gh * lv_[level].g.plane; }
+    template <typename T> int vc_restrict_all_t();   // vc_a(l + 1) = full weighting of vc_a(l), every transition
+    template <typename T> int vc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_VC_SUM]
+    template <typename T> int vc_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
+    template <typename T> int vc_coarse_t(int level, int ax, int ar);
+    template <typename T> int vc_cycle_rec_t(int l, int kind);
+    template <typename T> int vc_cycle_enqueue_t();
+    int vc_cycle_enqueue();
+    template <typename T> int vc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
+    template <typename T> int vc_direction_t(double beta, const int *arrs, double *pq);
+    template <typename T> int vc_pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     // block of eig_solve: eig_[family][column] (enum mg_eig_family), level-0-shaped; the per-workgroup partial sums of up to
     // EIG_MAX_LAUNCHES Gram tiles, their totals, the coefficients of the combine (device) and a pinned mirror of the last two
     enum { EIG_FAMILIES = 6, EIG_MAX_LAUNCHES = 9, EIG_HOST_DOUBLES = 2048 };

@@ -1,0 +1,444 @@
+"""Variable-coefficient diffusion on the GPU (mg_vc_*, multigrid_prj_amd/csrc/mg_vc.hip) against tests/vc_ref.py:
+the kernels bit for bit (plain form and marching tile), the coarse coefficients, a == 1 against the constant-coefficient
+kernels, the coarse solve, one cycle against the long-double reference, convergence on the fields of DESIGN.md section 18,
+and the contracts of the C ABI."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from multigrid_prj_amd import capi
+from tests import npref
+from tests import vc_ref as vr
+
+pytestmark = pytest.mark.gpu
+
+NP = {capi.MG_F64: np.float64, capi.MG_F32: np.float32}
+DTYPES = pytest.mark.parametrize("dtype", [capi.MG_F64, capi.MG_F32], ids=["f64", "f32"])
+U, E, RHS, TMP, RES = capi.ARR_U, capi.ARR_E, capi.ARR_RHS, capi.ARR_TMP, capi.ARR_RES
+JAC, RB = capi.SMOOTH_JACOBI, capi.SMOOTH_RBGS
+LD = np.longdouble
+
+# (dim, n, levels, extra): 9, 17 plain; 33, 35 march in fp64; 65, 67 march in both (35: odd last column, not 2^k + 1;
+# 67: a partial last vector in fp32; 34: an even row in fp64); 2-D always plain
+CASES = [
+    (3, 9, 2, {}), (3, 17, 2, {}), (3, 33, 2, {}), (3, 35, 2, {}), (3, 34, 1, {}), (3, 65, 2, {}), (3, 67, 2, {}),
+    (2, 17, 2, {}), (2, 130, 1, {}),
+    (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}), (3, 17, 3, {"semi_xy": 1}),
+]
+
+
+def case_id(c):
+    dim, n, levels, extra = c
+    return f"{dim}d{n}" + "".join("-" + k for k in extra)
+
+
+def desc_kw(dim, n, levels, extra, dtype, **more):
+    kw = dict(dim=dim, n=n, levels=levels, length=1.0, alpha=1.3, dtype=dtype, cycle=capi.CYCLE_V, smoother=RB, nu_pre=2, nu_post=2,
+              restriction=capi.RESTRICT_FULLW, outer_pre_gs=0, coarse_mode=capi.COARSE_FIXED, coarse_maxit=6)
+    kw.update(extra); kw.update(more)
+    return kw
+
+
+def problem_of(s, kw, prec, sigma=0.0):
+    """the reference of a handle's descriptor in `prec`, with the handle's own level coefficients"""
+    P = vr.VCProblem(prec=prec, sigma=sigma, **{k: v for k, v in kw.items() if k != "dtype"})
+    P.use_handle_coefs([s.level_coefficients(l) for l in range(kw["levels"])])
+    return P
+
+
+def random_a(shape, seed):
+    return np.exp(np.random.default_rng(seed).standard_normal(shape))
+
+
+def sumsq(r):
+    return npref.fsum_sq(r)
+
+
+# ---------------------------------------------------------------- 1. the kernels, bit for bit
+@DTYPES
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_kernels_bit_for_bit(case, dtype):
+    """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7) and one red-black sweep on levels 0 and 1, sigma 0
+    and 500; where the marching tile takes the level the plain form is run too (mg_vc_set_form) against the same numbers"""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    rng = np.random.default_rng(100 * dim + n)
+    forms_seen = set()
+    for omega in (1.0, 6.0 / 7.0):
+        kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
+        with capi.Solver(capi.make_desc(**kw)) as s:
+            s.vc_set_coefficient(random_a(s.level_shape(0), n).astype(T))
+            for sigma in (0.0, 500.0):
+                s.set_shift(sigma)
+                P = problem_of(s, kw, T, sigma)
+                P.a = [s.vc_get_coefficient(l) for l in range(levels)]
+                for l in range(min(levels, 2)):
+                    shape = s.level_shape(l)
+                    u, b, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
+                    r_ref, jac_ref, rb_ref = P.residual(u, b, l), P.jacobi(u, b, l), P.rbgs(u, b, l)
+                    assert r_ref.dtype == T and jac_ref.dtype == T and rb_ref.dtype == T
+                    march = dim == 3 and vr.march_side(3, shape[-1], np.dtype(T).itemsize) and min(shape) >= 7
+                    for form in ((0, 1) if march else (0,)):
+                        s.vc_set_form(form)
+                        forms_seen.add("march" if march and form == 0 else "plain")
+                        tag = (l, sigma, omega, form)
+                        s.set_array(E, l, u); s.set_array(RHS, l, b); s.set_array(TMP, l, other)   # RES exists on level 0 only
+                        ss = s.vc_residual(l, E, RHS, TMP)
+                        got = s.get_array(TMP, l)
+                        assert np.array_equal(got, r_ref), (tag, int((got != r_ref).sum()))
+                        assert ss == pytest.approx(sumsq(r_ref), rel=1e-13) and s.vc_residual(l, E, RHS, -1) == ss
+                        assert np.array_equal(s.get_array(E, l), u) and np.array_equal(s.get_array(RHS, l), b)
+                        s.set_array(U, l, u)
+                        s.vc_smooth(l, JAC, 1, U, RHS)
+                        got = s.get_array(U, l)
+                        assert np.array_equal(got, jac_ref), (tag, int((got != jac_ref).sum()))
+                        s.set_array(U, l, u)
+                        s.vc_smooth(l, RB, 1, U, RHS)
+                        got = s.get_array(U, l)
+                        assert np.array_equal(got, rb_ref), (tag, int((got != rb_ref).sum()))
+                        assert np.array_equal(s.get_array(RHS, l), b)
+                        assert np.array_equal(s.vc_get_coefficient(l), P.a[l])
+                    s.vc_set_form(0)
+    want = {"march", "plain"} if dim == 3 and vr.march_side(3, n, np.dtype(T).itemsize) else {"plain"}
+    assert forms_seen == want
+
+
+@DTYPES
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)})], ids=case_id)
+def test_direction_kernel_bit_for_bit(case, dtype):
+    """p' = z + beta p and q = L p', both 0 on Dirichlet nodes whatever z and p hold there; p'.q to rel 1e-13"""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    kw = desc_kw(dim, n, levels, extra, dtype)
+    rng = np.random.default_rng(n + 7)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        shape = s.level_shape(0)
+        s.vc_set_coefficient(random_a(shape, n).astype(T))
+        bm = vr.boundary_mask(shape)
+        for sigma, beta in ((0.0, 0.0), (500.0, -0.37)):
+            s.set_shift(sigma)
+            P = problem_of(s, kw, T, sigma)
+            P.a = [s.vc_get_coefficient(0)]
+            z, p, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
+            pn = z + T(beta) * p
+            pn[bm] = 0
+            q = P.apply_A(pn, 0)
+            q[bm] = 0
+            s.set_array(U, 0, z); s.set_array(E, 0, p); s.set_array(RES, 0, other); s.set_array(RHS, 0, other)
+            pq = s.vc_direction(beta, U, E, RES, RHS)
+            assert np.array_equal(s.get_array(RES, 0), pn) and np.array_equal(s.get_array(RHS, 0), q)
+            assert np.array_equal(s.get_array(U, 0), z) and np.array_equal(s.get_array(E, 0), p)
+            want = float(np.sum(pn.astype(np.float64) * q.astype(np.float64)))
+            assert pq == pytest.approx(want, rel=1e-13, abs=1e-13 * float(np.sum(abs(pn.astype(np.float64) * q.astype(np.float64)))))
+
+
+# ---------------------------------------------------------------- 2. the coarse coefficients
+@DTYPES
+@pytest.mark.parametrize("case", [(3, 17, 4, {}), (3, 35, 2, {}), (3, 17, 4, {"semi_xy": 2}), (2, 33, 5, {})], ids=case_id)
+def test_coarse_coefficients_are_full_weighted(case, dtype):
+    """level l + 1 is, bit for bit, what mg_restrict(FULLW) makes of level l uploaded into an array slot; a second set
+    re-restricts"""
+    dim, n, levels, extra = case
+    kw = desc_kw(dim, n, levels, extra, dtype)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        for seed in (1, 2):
+            a0 = random_a(s.level_shape(0), seed).astype(s.np)
+            s.vc_set_coefficient(a0)
+            assert np.array_equal(s.vc_get_coefficient(0), a0)
+            for l in range(levels - 1):
+                s.set_array(E, l, s.vc_get_coefficient(l))
+                s.restrict(l, capi.RESTRICT_FULLW, E, TMP)
+                coarse = s.vc_get_coefficient(l + 1)
+                assert np.array_equal(coarse, s.get_array(TMP, l + 1)), l
+                assert coarse.min() >= a0.min() * (1 - 1e-6) and coarse.max() <= a0.max() * (1 + 1e-6)
+
+
+@DTYPES
+@pytest.mark.parametrize("src", [torch.float64, torch.float32], ids=["from64", "from32"])
+def test_device_set_equals_host_set(src, dtype):
+    kw = desc_kw(3, 33, 3, {}, dtype)
+    with capi.Solver(capi.make_desc(**kw)) as host, capi.Solver(capi.make_desc(**kw)) as dev:
+        a0 = random_a(host.level_shape(0), 7)
+        t = torch.from_numpy(a0).to(device="cuda", dtype=src)
+        dev.vc_set_coefficient_device(t)
+        dev.sync()
+        host.vc_set_coefficient(t.cpu().numpy().astype(host.np))   # the conversion the copy kernel makes
+        for l in range(3):
+            assert np.array_equal(dev.vc_get_coefficient(l), host.vc_get_coefficient(l)), l
+
+
+# ---------------------------------------------------------------- 3. a == 1 is the constant operator
+@DTYPES
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 33, 2, {}), (3, 65, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)})],
+                         ids=case_id)
+def test_unit_coefficient_agrees_with_the_constant_kernels(case, dtype):
+    """vc_residual / one vc_smooth sweep against mg_residual / mg_smooth within 8 eps_T of npref's rounding magnitudes
+    (apply_A(absolute=True), point_solve_mag): what tests/test_independent_reference.py holds the constant kernels to"""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    eps = float(np.finfo(T).eps)
+    kw = desc_kw(dim, n, levels, extra, dtype, omega=6.0 / 7.0)
+    P = npref.Problem(**{k: v for k, v in kw.items() if k != "dtype"})
+    rng = np.random.default_rng(n)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.vc_set_coefficient(np.ones(s.level_shape(0), T))
+        for l in range(levels):
+            shape = s.level_shape(l)
+            assert np.array_equal(s.vc_get_coefficient(l), np.ones(shape, T))
+            u, b = (rng.standard_normal(shape).astype(T) for _ in range(2))
+            s.set_array(E, l, u); s.set_array(RHS, l, b)
+            s.residual(l, E, RHS, TMP); r_const = s.get_array(TMP, l).astype(LD)
+            s.vc_residual(l, E, RHS, TMP); r_vc = s.get_array(TMP, l).astype(LD)
+            bound = 8 * eps * np.asarray(abs(P.as_prec(b)) + P.apply_A(u, l, absolute=True))
+            assert (abs(r_vc - r_const) <= bound).all(), (l, float((abs(r_vc - r_const) / bound).max()))
+            bound = 8 * eps * np.asarray(abs(P.as_prec(u)) + P.point_solve_mag(u, b, l))
+            for sm in (JAC, RB):
+                s.set_array(U, l, u); s.smooth(l, sm, 1, U, RHS); x_const = s.get_array(U, l).astype(LD)
+                s.set_array(U, l, u); s.vc_smooth(l, sm, 1, U, RHS); x_vc = s.get_array(U, l).astype(LD)
+                assert (abs(x_vc - x_const) <= bound).all(), (l, sm, float((abs(x_vc - x_const) / bound).max()))
+
+
+# ---------------------------------------------------------------- 4. the coarse solve
+@DTYPES
+@pytest.mark.parametrize("smoother,omega", [(JAC, 6.0 / 7.0), (JAC, 1.0), (RB, 1.0)], ids=["jacobi67", "jacobi1", "rb"])
+@pytest.mark.parametrize("dim,n", [(3, 9), (2, 17)])
+def test_coarse_solve_fixed_bit_for_bit(dim, n, smoother, omega, dtype):
+    T = NP[dtype]
+    kw = desc_kw(dim, n, 1, {}, dtype, smoother=smoother, omega=omega, coarse_maxit=7)   # odd: the Jacobi result is moved back
+    rng = np.random.default_rng(n)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        shape = s.level_shape(0)
+        s.vc_set_coefficient(random_a(shape, 3).astype(T))
+        for sigma in (0.0, 500.0):
+            s.set_shift(sigma)
+            P = problem_of(s, kw, T, sigma)
+            P.a = [s.vc_get_coefficient(0)]
+            u, b = (rng.standard_normal(shape).astype(T) for _ in range(2))
+            ref, iters, flag, relres, _ = P.coarse_loop(u, b, 0, 7, 0.0, True)
+            s.set_array(U, 0, u); s.set_array(RHS, 0, b)
+            st = s.vc_coarse_solve(0, U, RHS)
+            assert np.array_equal(s.get_array(U, 0), ref) and np.array_equal(s.get_array(RHS, 0), b)
+            assert (st.coarse_iters, st.coarse_flag) == (7, 0) and st.coarse_relres == pytest.approx(relres, rel=1e-12)
+
+
+@DTYPES
+@pytest.mark.parametrize("smoother,omega", [(JAC, 6.0 / 7.0), (RB, 1.0)], ids=["jacobi67", "rb"])
+@pytest.mark.parametrize("dim,n", [(3, 9), (2, 17)])
+def test_coarse_solve_to_tolerance(dim, n, smoother, omega, dtype):
+    T = NP[dtype]
+    tol = 3e-3
+    rng = np.random.default_rng(n + 1)
+    for maxit in (2000, 5):   # converges / runs out of sweeps
+        kw = desc_kw(dim, n, 1, {}, dtype, smoother=smoother, omega=omega, coarse_mode=capi.COARSE_TOL, coarse_maxit=maxit, coarse_tol=tol)
+        with capi.Solver(capi.make_desc(**kw)) as s:
+            shape = s.level_shape(0)
+            s.vc_set_coefficient(random_a(shape, 4).astype(T))
+            P = problem_of(s, kw, LD)
+            P.a = [s.vc_get_coefficient(0).astype(LD)]
+            b = rng.standard_normal(shape).astype(T)
+            _, iters, flag, relres, tested = P.coarse_loop(np.zeros(shape), b, 0, maxit, tol, False)
+            assert min(abs(t / tol - 1.0) for t in tested) > 1e-6   # no stopping decision of the reference is a near tie
+            s.zero_array(U, 0); s.set_array(RHS, 0, b)
+            st = s.vc_coarse_solve(0, U, RHS)
+            assert abs(st.coarse_iters - iters) <= 1 and st.coarse_flag == flag
+            assert st.coarse_flag == 1 or st.coarse_relres <= tol
+            assert np.array_equal(s.get_array(RHS, 0), b)
+
+
+# ---------------------------------------------------------------- 5. one cycle
+CYCLE_KINDS = {"v22-rb": dict(cycle=capi.CYCLE_V, smoother=RB, nu_pre=2, nu_post=2),
+               "w11-jacobi": dict(cycle=capi.CYCLE_W, smoother=JAC, omega=6.0 / 7.0, nu_pre=1, nu_post=1)}
+
+
+@functools.lru_cache(maxsize=None)
+def cycle_references(n, levels, kind, dtype):
+    """one cycle from the same u, b, a by vc_ref in the working dtype and in long double -> (u_T, u_LD, the inputs)"""
+    kw = desc_kw(3, n, levels, {}, dtype, **CYCLE_KINDS[kind])
+    T = NP[dtype]
+    rng = np.random.default_rng(n)
+    shape = (n, n, n)
+    a0, u0, b = random_a(shape, 9).astype(T), rng.standard_normal(shape).astype(T), rng.standard_normal(shape).astype(T)
+    out = []
+    for prec in (T, LD):
+        P = vr.VCProblem(prec=prec, **{k: v for k, v in kw.items() if k != "dtype"})
+        P.set_a(a0)
+        out.append(P.vcycle(P.as_prec(u0), P.as_prec(b), kw["coarse_maxit"]))
+    return out[0], out[1], (a0, u0, b), kw
+
+
+@DTYPES
+@pytest.mark.parametrize("kind", list(CYCLE_KINDS))
+@pytest.mark.parametrize("n,levels", [(17, 3), (33, 4)])
+def test_one_cycle_against_long_double(n, levels, kind, dtype):
+    """mg_vc_cycle against the long-double reference cycle. Tolerance: 4 x the largest difference between vc_ref run in the
+    working dtype and in long double on the same input (computed here, from the reference alone). That difference, measured
+    on the CPU (max norm; u, b standard normal, a = exp(N(0,1))):
+        n = 17  V(2,2) red-black   fp64 4.2e-16   fp32 2.2e-07      W(1,1) Jacobi 6/7   fp64 6.9e-16   fp32 2.4e-07
+        n = 33  V(2,2) red-black   fp64 1.1e-15   fp32 4.0e-07      W(1,1) Jacobi 6/7   fp64 7.5e-16   fp32 4.0e-07"""
+    u_T, u_LD, (a0, u0, b), kw = cycle_references(n, levels, kind, dtype)
+    tol = 4 * float(abs(u_T.astype(LD) - u_LD).max())
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.vc_set_coefficient(a0); s.set_solution(u0); s.set_rhs(b)
+        st = s.vc_cycle()
+        got = s.get_solution().astype(LD)
+        err = float(abs(got - u_LD).max())
+        print(f"n={n} {kind} {NP[dtype].__name__}: |gpu - ld| = {err:.3e}, tolerance = {tol:.3e}")
+        assert err <= tol
+        assert np.array_equal(s.get_array(RHS, 0), b)
+        visits = 1 if kw["cycle"] == capi.CYCLE_V else 2 ** (levels - 2)
+        assert st.coarse_iters == visits * kw["coarse_maxit"] and st.coarse_flag == 0
+
+
+# ---------------------------------------------------------------- 6. / 7. convergence (fp64, n = 33, 5 levels, red-black V(2,2), 50 coarse sweeps)
+CONV = dict(dim=3, n=33, levels=5, length=1.0, alpha=1.0, dtype=capi.MG_F64, cycle=capi.CYCLE_V, smoother=RB, nu_pre=2, nu_post=2,
+            restriction=capi.RESTRICT_FULLW, outer_pre_gs=0, coarse_mode=capi.COARSE_FIXED, coarse_maxit=50)
+
+
+@functools.lru_cache(maxsize=None)
+def conv_reference(field):
+    P = vr.convergence_problem()
+    b, b0 = vr.convergence_rhs(P.shape(0)), vr.convergence_rhs(P.shape(0), zero_boundary=True)
+    if field == "smooth":
+        P.set_a(vr.field_smooth(33))
+        return b, P.cycle_history(np.zeros_like(b), b, 7, 50)[1]
+    P.set_a(vr.field_jump_offgrid(33))
+    return b, P.cycle_history(np.zeros_like(b), b, 25, 50)[1], b0, P.fcg(np.zeros_like(b), b0, 1e-8, 40, 50)[1]
+
+
+def test_smooth_field_history():
+    b, ref = conv_reference("smooth")
+    with capi.Solver(capi.make_desc(**CONV)) as s:
+        s.vc_set_coefficient(vr.field_smooth(33)); s.set_rhs(b); s.set_solution(np.zeros_like(b))
+        hist, stats = s.vc_solve(0.0, 7)
+        print("gpu", hist, "reference", ref)
+        assert len(hist) == 8 and len(stats) == 7 and all(st.coarse_iters == 50 for st in stats)
+        assert hist == pytest.approx(ref, rel=1e-6)
+        assert hist[-1] / hist[-2] <= 0.2
+        assert np.array_equal(s.get_array(RHS, 0), b)
+
+
+def test_jumps_need_the_krylov_wrapper():
+    b, ref, b0, ref_fcg = conv_reference("jump")
+    with capi.Solver(capi.make_desc(**CONV)) as s:
+        s.vc_set_coefficient(vr.field_jump_offgrid(33)); s.set_rhs(b); s.set_solution(np.zeros_like(b))
+        hist, _ = s.vc_solve(0.0, 25)
+        print("cycle alone: gpu", hist[-1], "reference", ref[-1])
+        assert ref[-1] > 1e-2 and hist[-1] == pytest.approx(ref[-1], rel=1e-6) and hist[-1] > 1e-2
+        assert np.array_equal(s.get_array(RHS, 0), b)
+        s.set_rhs(b0); s.set_solution(np.zeros_like(b0))
+        h, st = s.vc_pcg_solve(1e-8, 60)
+        print("fcg: gpu", st.iters, h[-1], st.relres_true, "reference", len(ref_fcg) - 1, ref_fcg[-1])
+        assert st.status == 0 and st.iters <= len(ref_fcg) - 1 + 2
+        assert st.relres_true <= 2e-8
+        assert np.array_equal(s.get_array(RHS, 0), b0)
+
+
+# ---------------------------------------------------------------- 8. contracts
+def refused(call, word):
+    with pytest.raises(capi.MgError) as e:
+        call()
+    assert e.value.code == -4 and word in str(e.value), str(e.value)
+
+
+def test_refusals_leave_u_untouched():
+    rng = np.random.default_rng(5)
+    base = desc_kw(3, 17, 3, {}, capi.MG_F64)
+
+    def drivers(s):
+        return [lambda: s.vc_cycle(), lambda: s.vc_solve(1e-8, 3), lambda: s.vc_pcg_solve(1e-8, 3)]
+
+    # no coefficient set
+    with capi.Solver(capi.make_desc(**base)) as s:
+        u0 = rng.standard_normal(s.level_shape(0)); s.set_solution(u0); s.set_rhs(u0)
+        before = s.device_bytes()
+        for call in drivers(s) + [lambda: s.vc_residual(0, U, RHS, RES), lambda: s.vc_smooth(0, JAC, 1, U, RHS),
+                                  lambda: s.vc_coarse_solve(2, U, RHS), lambda: s.vc_get_coefficient(0)]:
+            refused(call, "no coefficient")
+        # a coefficient that is not finite and > 0
+        for bad in (0.0, -1.0, np.nan, np.inf):
+            a = np.ones(s.level_shape(0)); a[3, 4, 5] = bad
+            refused(lambda: s.vc_set_coefficient(a), "finite and > 0")
+        assert s.device_bytes() == before and np.array_equal(s.get_solution(), u0)
+        # bad arrays, levels and smoothers
+        s.vc_set_coefficient(np.ones(s.level_shape(0)))
+        for call in (lambda: s.vc_residual(3, U, RHS, RES), lambda: s.vc_residual(0, U, RHS, U), lambda: s.vc_residual(0, 7, RHS, RES),
+                     lambda: s.vc_smooth(0, JAC, 1, U, U), lambda: s.vc_smooth(0, JAC, 1, TMP, RHS), lambda: s.vc_smooth(-1, RB, 1, U, RHS),
+                     lambda: s.vc_smooth(0, capi.SMOOTH_GS_LEX, 1, U, RHS), lambda: s.vc_smooth(0, capi.SMOOTH_ZEBRA_X, 1, U, RHS),
+                     lambda: s.vc_smooth(0, 99, 1, U, RHS), lambda: s.vc_coarse_solve(2, U, TMP), lambda: s.vc_coarse_solve(5, U, RHS),
+                     lambda: s.vc_get_coefficient(3)):
+            with pytest.raises(capi.MgError) as e:
+                call()
+            assert e.value.code == -4
+        # a stage callback
+        s.set_stage_callback(lambda *a: None)
+        for call in drivers(s):
+            refused(call, "stage callback")
+        s.set_stage_callback(None)
+        assert np.array_equal(s.get_solution(), u0)
+    # a sawtooth handle; a smoother the vc kernels do not have
+    for more, word, extra_calls in ((dict(cycle=capi.CYCLE_SAWTOOTH), "sawtooth", 0), (dict(smoother=capi.SMOOTH_GS_LEX), "smoother", 1),
+                                    (dict(smoother=capi.SMOOTH_ZEBRA_Y), "smoother", 1)):
+        with capi.Solver(capi.make_desc(**dict(base, **more))) as s:
+            u0 = rng.standard_normal(s.level_shape(0)); s.set_solution(u0); s.set_rhs(u0)
+            s.vc_set_coefficient(np.ones(s.level_shape(0)))
+            for call in drivers(s) + [lambda: s.vc_coarse_solve(2, U, RHS)] * extra_calls:
+                refused(call, word)
+            assert np.array_equal(s.get_solution(), u0)
+    # distributed handles, the dry-run measurement handle included
+    with capi.Solver(capi.make_desc(**base), device=0, rank=0, nranks=2, dry=True) as s:
+        u0 = rng.standard_normal(s.level_shape(0)); s.set_solution(u0)
+        before = s.device_bytes()
+        t = torch.ones(s.level_shape(0), dtype=torch.float64, device="cuda")
+        for call in drivers(s) + [lambda: s.vc_set_coefficient(np.ones(s.level_shape(0))), lambda: s.vc_set_coefficient_device(t),
+                                  lambda: s.vc_residual(0, U, RHS, RES), lambda: s.vc_smooth(0, RB, 1, U, RHS),
+                                  lambda: s.vc_coarse_solve(2, U, RHS), lambda: s.vc_get_coefficient(0)]:
+            refused(call, "distributed")
+        assert np.array_equal(s.get_solution(), u0) and s.device_bytes() == before
+    # NULL handle
+    L = capi.load()
+    assert L.mg_vc_cycle(None, None) == -4 and L.mg_vc_set_coefficient(None, None) == -4 and L.mg_vc_pcg_solve(None, 0.0, 1, None, 0, None, None) == -4
+
+
+@DTYPES
+def test_memory_determinism_and_isolation(dtype):
+    T = NP[dtype]
+    kw = desc_kw(3, 33, 4, {}, dtype, smoother=JAC, omega=6.0 / 7.0)
+    rng = np.random.default_rng(8)
+    with capi.Solver(capi.make_desc(**kw)) as s, capi.Solver(capi.make_desc(**kw)) as sib, capi.Solver(capi.make_desc(**kw)) as plain:
+        shape = s.level_shape(0)
+        a0, b = random_a(shape, 2).astype(T), rng.standard_normal(shape).astype(T)
+        b[vr.boundary_mask(shape)] = 0
+        # the first set allocates one level-shaped array per level, nothing afterwards
+        before = s.device_bytes()
+        s.vc_set_coefficient(a0)
+        es, line = np.dtype(T).itemsize, 128 // np.dtype(T).itemsize
+        want = sum((s.level_nz(l) + 2) * s.level_n(l) * (-(-s.level_n(l) // line) * line) * es for l in range(4))
+        assert s.device_bytes() - before == want
+        s.vc_set_coefficient(a0); s.vc_set_coefficient_device(torch.from_numpy(a0).cuda()); s.sync()
+        assert s.device_bytes() - before == want
+        runs = []
+        for k in range(2):
+            s.set_rhs(b); s.set_solution(np.zeros_like(b))
+            hist, _ = s.vc_solve(0.0, 3)
+            u_solve = s.get_solution()
+            assert np.array_equal(s.get_array(RHS, 0), b)
+            if k == 0:
+                assert s.device_bytes() - before == want   # the cycle and the solve allocate nothing (the Krylov buffers come later)
+            s.set_solution(np.zeros_like(b))
+            h2, st = s.vc_pcg_solve(1e-30, 4)
+            assert np.array_equal(s.get_array(RHS, 0), b)
+            runs.append((hist, u_solve, h2, s.get_solution()))
+        for x, y in zip(*runs):
+            assert np.array_equal(x, y)   # two runs give the same bits
+        # a handle that never set a coefficient: mg_cycle gives the same bits whether or not a sibling used mg_vc_*
+        outs = []
+        for h in (plain, sib):
+            if h is sib:
+                s.vc_cycle()
+            h.set_rhs(b); h.set_solution(np.zeros_like(b))
+            h.cycle(); h.cycle()
+            outs.append(h.get_solution())
+        assert np.array_equal(outs[0], outs[1])
+        assert plain.device_bytes() == sib.device_bytes() == before
