@@ -441,6 +441,67 @@ int mg_vc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, 
 int mg_vc_pcg_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
 int mg_vc_direction(mg_handle h, double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq);
 
+/* Neumann faces (extension, no reference counterpart): the handle's constant operator -- alpha, aniso, semi_xy, grids that
+ * are not 2^k + 1 and the shift of mg_set_shift keep their meaning -- with zero-flux walls or symmetry planes on any of the
+ * 2*dim faces of the box. x is the fast index i, y is j, z is k; LO is index 0 and HI index n-1 of the host layout. */
+enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 8, MG_FACE_ZLO = 16, MG_FACE_ZHI = 32 };
+/* The mask is the set of NEUMANN faces; 0 (the default) means all Dirichlet. A node is a DIRICHLET NODE if it lies on at
+ * least one face that is not in the mask: its row is the identity row with mg_residual's and mg_smooth's conventions (the
+ * residual is b - u, the sweeps take b, red-black with the node's colour). Every other node is an unknown: the interior
+ * nodes and the nodes that lie only on Neumann faces, the edges and corners between Neumann faces included. At an unknown on
+ * the LO face of an axis the missing neighbour u(i-) is the mirror image u(i+), likewise on HI, each axis on its own; no
+ * ghost value is stored or read. Arithmetic in the working dtype T, every operation rounded separately, the coefficients
+ * of mg_level_coefficients(h, l):
+ *   residual     sum = cz u(z-) + cy u(y-) + cx u(x-) + cd u_i + cx u(x+) + cy u(y+) + cz u(z+), added left to right (no z terms
+ *                in 2-D); r = b - sum; the sum of r^2 over all nodes in double in a fixed order, no atomics
+ *   point solve  the same sum without the diagonal term; ps = (b - sum) / cd, the IEEE quotient
+ *   Jacobi       out of place: u' = ps when desc.omega == 1, else u_i + omega*(ps - u_i)
+ *   red-black    in place, colour (i + j + k) & 1, colour 0 first
+ * With mask 0 these are mg_residual's and mg_smooth's results bit for bit.
+ * INHOMOGENEOUS FLUX is the caller's business: for an outward normal derivative g on a Neumann face of axis a, add
+ * -2 h_a c_a g = +(2 alpha aniso_a / h_a) g to b at that face's nodes (c_a the level-0 off-diagonal, h_a the mesh width; at
+ * an edge or corner between Neumann faces one term per face). The discretisation stays second-order accurate.
+ *
+ * mg_bc_set_faces / mg_bc_get_faces: set and read the mask. Nothing is allocated and the mask may be changed at any time;
+ *   z bits on a 2-D handle are MG_ERR_BAD_ARG.
+ * mg_bc_residual, mg_bc_smooth, mg_bc_coarse_solve: the argument lists and aliasing rules of mg_vc_residual, mg_vc_smooth and
+ *   mg_vc_coarse_solve.
+ * mg_bc_restrict: MG_RESTRICT_INJECT is mg_restrict's injection. MG_RESTRICT_FULLW at a coarse unknown is mg_restrict's
+ *   9-/27-point full weighting in its order of operations with fine indices that fall outside the grid mirrored
+ *   (2x-1 < 0 -> 2x+1, 2x+1 > nx_f-1 -> 2x-1, per axis); coarse Dirichlet nodes are injected; semi transitions keep z.
+ *   Mask 0 equals mg_restrict bit for bit. (Injecting at coarse nodes of a Neumann face, which mg_restrict would do, makes
+ *   the red-black cycle diverge: DESIGN.md section 19.)
+ * mg_bc_cycle: cyc(0, desc.cycle) exactly as mg_vc_cycle words it, with the sweeps, the residual, the restriction
+ *   (desc.restriction) and the coarse solve of this operator and mg_prolong(add = 1); launch by launch. A coarsest level too big
+ *   for one workgroup in MG_COARSE_FIXED mode runs coarse_maxit chip-wide sweeps, as mg_cycle does.
+ * mg_bc_solve: mg_solve's loop and history contract on this operator: U = RHS on the Dirichlet nodes first, hist[0] the
+ *   initial relative residual over all nodes, one mg_bc_cycle per iteration. desc.outer_pre_gs is IGNORED.
+ *   THE SINGULAR CASE -- all 2*dim faces Neumann and the current shift 0: the constants are the null space. mg_bc_solve then
+ *   projects RHS(0) (mg_bc_project) before anything else, so hist is relative to the projected right-hand side, and projects
+ *   U(0) after the last cycle; RHS(0) holds the PROJECTED right-hand side on return. In every other combination RHS(0) is
+ *   unchanged.
+ * mg_bc_project: c = (sum w_i v_i) / (sum w_i) in double in a fixed order, then v_i -= (T)c on every node; *mean = c (may be
+ *   NULL). w_i is the product over the axes of 1/2 for each Neumann face the node lies on, else 1: diag(w) L is symmetric,
+ *   so w spans the left null space of the singular operator, and the mirrored full weighting keeps a compatible right-hand
+ *   side compatible from level to level (R^T w_coarse = w_fine / 2^dim). Synchronises.
+ * mg_bc_set_form (tests and measurement tools): form 1 runs the one-thread-per-node kernels on every level, form 0 (the
+ *   default) the marching tile where the level's shape admits it (3-D, at least 16 full 16-byte vectors per row).
+ * MG_ERR_BAD_ARG with U untouched: a sawtooth handle or a stage callback installed (cycle, solve); a handle smoother other
+ * than Jacobi or red-black (cycle, solve, coarse_solve); an unknown smoother in mg_bc_smooth; distributed handles (dry runs
+ * included); bad arrays, levels or masks; NULL handle. No other entry point changes behaviour, and the family allocates
+ * nothing. Not combined with mg_vc_*, mg_o4_*, mg_heat_step, mg_fmg, mg_eig_solve, mg_mixed_solve or mg_pcg_solve, which
+ * keep treating every face as Dirichlet; mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
+int mg_bc_set_faces(mg_handle h, int mask);
+int mg_bc_get_faces(mg_handle h, int *mask);
+int mg_bc_set_form(mg_handle h, int form);
+int mg_bc_residual(mg_handle h, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
+int mg_bc_smooth(mg_handle h, int level, int smoother, int sweeps, int arr_x, int arr_rhs);
+int mg_bc_restrict(mg_handle h, int fine_level, int kind, int arr_src, int arr_dst);
+int mg_bc_coarse_solve(mg_handle h, int level, int arr_x, int arr_rhs, mg_cycle_stats *st);
+int mg_bc_project(mg_handle h, int level, int arr, double *mean);
+int mg_bc_cycle(mg_handle h, mg_cycle_stats *st);
+int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
+
 /* Diagonal shift (extension, no reference counterpart): from this call on the handle works on sigma I + A, sigma >= 0 --
  * the operator of an implicit time step or a screened-Poisson / Helmholtz-type solve. On every level the diagonal becomes
  * cd0_l + sigma (one fp64 addition, then cast to the working dtype like every coefficient), cd0_l being the diagonal the

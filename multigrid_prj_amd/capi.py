@@ -16,6 +16,7 @@ SMOOTH_GS_LEX, SMOOTH_JACOBI, SMOOTH_RBGS, SMOOTH_ZEBRA_Y, SMOOTH_ZEBRA_X = 0, 1
 CYCLE_SAWTOOTH, CYCLE_V = 0, 1
 CYCLE_W, CYCLE_F = 2, 3
 RESTRICT_INJECT, RESTRICT_FULLW = 0, 1
+FACE_XLO, FACE_XHI, FACE_YLO, FACE_YHI, FACE_ZLO, FACE_ZHI = 1, 2, 4, 8, 16, 32   # enum mg_face: the Neumann faces of mg_bc_*
 COARSE_TOL, COARSE_FIXED = 0, 1
 ARR_U, ARR_E, ARR_RHS, ARR_TMP, ARR_RES = 0, 1, 2, 3, 4
 MG_COMM_ID_BYTES = 128
@@ -153,6 +154,8 @@ EXPORTS = [
     "mg_o4_residual", "mg_o4_correct_residual", "mg_o4_solve",
     "mg_vc_set_coefficient", "mg_vc_set_coefficient_device", "mg_vc_get_coefficient", "mg_vc_set_form", "mg_vc_residual", "mg_vc_smooth",
     "mg_vc_coarse_solve", "mg_vc_cycle", "mg_vc_solve", "mg_vc_pcg_solve", "mg_vc_direction",
+    "mg_bc_set_faces", "mg_bc_get_faces", "mg_bc_set_form", "mg_bc_residual", "mg_bc_smooth", "mg_bc_restrict", "mg_bc_coarse_solve",
+    "mg_bc_project", "mg_bc_cycle", "mg_bc_solve",
     "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_set_source_device", "mg_heat_step", "mg_heat_rhs",
     "mg_eig_solve", "mg_eig_set_vector", "mg_eig_get_vector", "mg_eig_set_vector_device", "mg_eig_get_vector_device",
     "mg_eig_block", "mg_eig_kernel",
@@ -230,6 +233,16 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_vc_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
     L.mg_vc_pcg_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgKrylovStats)]
     L.mg_vc_direction.argtypes = [vp, C.c_double, i, i, i, i, dp]
+    L.mg_bc_set_faces.argtypes = [vp, i]
+    L.mg_bc_get_faces.argtypes = [vp, C.POINTER(i)]
+    L.mg_bc_set_form.argtypes = [vp, i]
+    L.mg_bc_residual.argtypes = [vp, i, i, i, i, dp]
+    L.mg_bc_smooth.argtypes = [vp, i, i, i, i, i]
+    L.mg_bc_restrict.argtypes = [vp, i, i, i, i]
+    L.mg_bc_coarse_solve.argtypes = [vp, i, i, i, C.POINTER(MgCycleStats)]
+    L.mg_bc_project.argtypes = [vp, i, i, dp]
+    L.mg_bc_cycle.argtypes = [vp, C.POINTER(MgCycleStats)]
+    L.mg_bc_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
     L.mg_set_shift.argtypes = [vp, C.c_double]
     L.mg_get_shift.argtypes = [vp, dp]
     L.mg_heat_set_source.argtypes = [vp, vp]
@@ -614,6 +627,44 @@ class Solver:
     def vc_direction(self, beta, arr_z, arr_p, arr_pn, arr_q) -> float:
         """mg_vc_direction: arr_pn = arr_z + beta arr_p, arr_q = L arr_pn (both 0 on Dirichlet nodes) -> sum pn.q"""
         s = C.c_double(0); _check(self.lib.mg_vc_direction(self.h, beta, arr_z, arr_p, arr_pn, arr_q, C.byref(s))); return s.value
+
+    # -- Neumann faces: the constant operator with zero-flux walls on the faces of a mask (mg_bc_*, include/mg_hip.h)
+    def bc_set_faces(self, mask):
+        """mg_bc_set_faces: the set of Neumann faces (FACE_* bits), 0 = all Dirichlet"""
+        _check(self.lib.mg_bc_set_faces(self.h, int(mask)))
+
+    def bc_get_faces(self) -> int:
+        m = C.c_int(0); _check(self.lib.mg_bc_get_faces(self.h, C.byref(m))); return m.value
+
+    def bc_set_form(self, form):
+        """mg_bc_set_form (tests and measurement tools): 1 = the plain kernels on every level, 0 = the default"""
+        _check(self.lib.mg_bc_set_form(self.h, int(form)))
+
+    def bc_residual(self, level, arr_x, arr_rhs, arr_r=-1) -> float:
+        s = C.c_double(0); _check(self.lib.mg_bc_residual(self.h, level, arr_x, arr_rhs, arr_r, C.byref(s))); return s.value
+
+    def bc_smooth(self, level, smoother, sweeps, arr_x, arr_rhs):
+        _check(self.lib.mg_bc_smooth(self.h, level, smoother, sweeps, arr_x, arr_rhs))
+
+    def bc_restrict(self, fine_level, kind, arr_src, arr_dst):
+        _check(self.lib.mg_bc_restrict(self.h, fine_level, kind, arr_src, arr_dst))
+
+    def bc_coarse_solve(self, level, arr_x, arr_rhs) -> MgCycleStats:
+        st = MgCycleStats(); _check(self.lib.mg_bc_coarse_solve(self.h, level, arr_x, arr_rhs, C.byref(st))); return st
+
+    def bc_project(self, level, arr) -> float:
+        """mg_bc_project: subtracts the w-weighted mean from every node and returns it"""
+        m = C.c_double(0); _check(self.lib.mg_bc_project(self.h, level, arr, C.byref(m))); return m.value
+
+    def bc_cycle(self) -> MgCycleStats:
+        st = MgCycleStats(); _check(self.lib.mg_bc_cycle(self.h, C.byref(st))); return st
+
+    def bc_solve(self, tol=1e-11, maxit=1000):
+        """mg_bc_solve -> (hist, per-cycle MgCycleStats)"""
+        hist = (C.c_double * (maxit + 1))(); nh = C.c_int(0)
+        stats = (MgCycleStats * max(maxit, 1))()
+        _check(self.lib.mg_bc_solve(self.h, tol, maxit, hist, maxit + 1, C.byref(nh), stats))
+        return np.array(hist[:nh.value]), list(stats[:nh.value - 1])
 
     def heat_set_source(self, f):
         """mg_heat_set_source: the source term f of u_t = -A0 u + f (level-0 array of the handle's dtype); None: f = 0"""

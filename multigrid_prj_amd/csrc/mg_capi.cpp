@@ -311,6 +311,42 @@ int mg_vc_direction(mg_handle h, double beta, int arr_z, int arr_p, int arr_pn, 
     MG_H(h);
     return guarded([&] { return h->impl->vc_direction(beta, arr_z, arr_p, arr_pn, arr_q, pq); });
 }
+int mg_bc_set_faces(mg_handle h, int mask) { MG_H(h); return guarded([&] { return h->impl->bc_set_faces(mask); }); }
+int mg_bc_get_faces(mg_handle h, int *mask)
+{
+    MG_H(h);
+    if (!mask) return bad("mg_bc_get_faces: null output");
+    return h->impl->bc_get_faces(mask);
+}
+int mg_bc_set_form(mg_handle h, int form) { MG_H(h); return guarded([&] { return h->impl->bc_set_form(form); }); }
+int mg_bc_residual(mg_handle h, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->bc_residual(level, arr_x, arr_rhs, arr_r, sumsq_r); });
+}
+int mg_bc_smooth(mg_handle h, int level, int smoother, int sweeps, int arr_x, int arr_rhs)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->bc_smooth(level, smoother, sweeps, arr_x, arr_rhs); });
+}
+int mg_bc_restrict(mg_handle h, int fine_level, int kind, int arr_src, int arr_dst)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->bc_restrict(fine_level, kind, arr_src, arr_dst); });
+}
+int mg_bc_coarse_solve(mg_handle h, int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->bc_coarse_solve(level, arr_x, arr_rhs, st); });
+}
+int mg_bc_project(mg_handle h, int level, int arr, double *mean) { MG_H(h); return guarded([&] { return h->impl->bc_project(level, arr, mean); }); }
+int mg_bc_cycle(mg_handle h, mg_cycle_stats *st) { MG_H(h); return guarded([&] { return h->impl->bc_cycle(st); }); }
+int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    MG_H(h);
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_bc_solve: bad history buffer");
+    return guarded([&] { return h->impl->bc_solve(tol, maxit, hist, hist_cap, n_hist, per_cycle); });
+}
 int mg_set_shift(mg_handle h, double sigma) { MG_H(h); return guarded([&] { return h->impl->set_shift(sigma); }); }
 int mg_get_shift(mg_handle h, double *sigma)
 {

@@ -1,5 +1,5 @@
 // mg_drivers.cpp -- the solve drivers of mg::Solver: everything that calls the cycle from above (mg_solve, mg_pcg_*, mg_fmg*,
-// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*, mg_eig_*, mg_vc_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
+// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*, mg_eig_*, mg_vc_*, mg_bc_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
 // Reference call structure being replaced by solve(): the outer loop of src/main.cpp:72-116.
 #include "mg_solver.h"
 #include "mg_dense.h"
@@ -1434,6 +1434,270 @@ int Solver::vc_pcg_solve(double tol, int maxit, double *hist, int hist_cap, int 
     MG_TRY(krylov_alloc());
     return d_.dtype == MG_F64 ? vc_pcg_t<double>(tol, maxit, hist, hist_cap, n_hist, st)
                               : vc_pcg_t<float>(tol, maxit, hist, hist_cap, n_hist, st);
+}
+
+// ---------------------------------------------------------------- Neumann faces (mg_bc_*), DESIGN.md section 19
+// The handle's constant operator with zero-flux walls on the faces of a mask (enum mg_face): nodes that lie only on Neumann
+// faces are unknowns whose missing neighbours are mirror images. The kernels are in mg_bc.hip -- the restriction too, because
+// injecting at coarse nodes of a Neumann face makes the cycle diverge; the prolongation is the handle's own. Everything goes
+// launch by launch, as the mg_vc_* drivers do. Nothing is allocated: the state is the mask.
+int Solver::bc_check(const char *fn, unsigned need)
+{
+    MG_TRY(driver_begin(fn, REFUSE_DIST | ((need & BC_NEED_CYCLE) ? REFUSE_STAGE_CB : 0u)));
+    if ((need & BC_NEED_CYCLE) && !is_vwf(d_.cycle)) {
+        set_last_error(std::string(fn) + ": not on a sawtooth handle (the cycle must be MG_CYCLE_V, MG_CYCLE_W or MG_CYCLE_F)");
+        return MG_ERR_BAD_ARG;
+    }
+    if ((need & (BC_NEED_CYCLE | BC_NEED_SMOOTHER)) && d_.smoother != MG_SMOOTH_JACOBI && d_.smoother != MG_SMOOTH_RBGS) {
+        set_last_error(std::string(fn) + ": the handle's smoother must be MG_SMOOTH_JACOBI or MG_SMOOTH_RBGS");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::bc_set_faces(int mask)
+{
+    MG_TRY(driver_begin("mg_bc_set_faces", REFUSE_DIST));
+    if (mask < 0 || mask > 63) { set_last_error("mg_bc_set_faces: the mask must be a combination of the six MG_FACE_* bits"); return MG_ERR_BAD_ARG; }
+    if (d_.dim == 2 && (mask & (MG_FACE_ZLO | MG_FACE_ZHI))) { set_last_error("mg_bc_set_faces: a 2-D handle has no z faces"); return MG_ERR_BAD_ARG; }
+    bc_mask_ = mask;
+    return MG_OK;
+}
+
+int Solver::bc_get_faces(int *mask) const
+{
+    if (!mask) return MG_ERR_BAD_ARG;
+    *mask = bc_mask_;
+    return MG_OK;
+}
+
+int Solver::bc_set_form(int form)
+{
+    if (form != 0 && form != 1) { set_last_error("mg_bc_set_form: form must be 0 (default) or 1 (the plain kernels everywhere)"); return MG_ERR_BAD_ARG; }
+    bc_plain_ = form == 1;
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::bc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
+{
+    Level &L = lv_[level];
+    if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
+    const int np = launch_bc_residual<T>(stream_, L.g, coef_of<T>(L), bc_mask_, ptr<T>(ax, level), ptr<T>(ar, level),
+                                         arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr, d_partials_, o4_partials_cap_, bc_plain_);
+    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_BC_SUM);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::bc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
+{
+    MG_TRY(bc_check("mg_bc_residual", 0));
+    if (!check_arr(arr_x, level, "mg_bc_residual") || !check_arr(arr_rhs, level, "mg_bc_residual")) return MG_ERR_BAD_ARG;
+    if (arr_r >= 0 && (!check_arr(arr_r, level, "mg_bc_residual") || arr_r == arr_x || arr_r == arr_rhs)) {
+        set_last_error("mg_bc_residual: bad output array");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_TRY(d_.dtype == MG_F64 ? bc_residual_t<double>(level, arr_x, arr_rhs, arr_r, true) : bc_residual_t<float>(level, arr_x, arr_rhs, arr_r, true));
+    if (sumsq_r) {
+        MG_TRY(fetch_scalars(SC_BC_SUM, d_scal_ + SC_BC_SUM));
+        *sumsq_r = h_scal_[SC_BC_SUM];
+    }
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::bc_smooth_t(int level, int smoother, int sweeps, int ax, int ar)
+{
+    Level &L = lv_[level];
+    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
+    const Coef<T> c = coef_of<T>(L);
+    for (int s = 0; s < sweeps; s++) {
+        if (smoother == MG_SMOOTH_JACOBI) {   // out of place into TMP, then the two pointers are swapped (as smooth_t)
+            launch_bc_jacobi<T>(stream_, L.g, c, bc_mask_, (T)d_.omega, ptr<T>(ax, level), ptr<T>(ar, level), ptr<T>(MG_ARR_TMP, level),
+                                bc_plain_);
+            std::swap(L.base[ax], L.base[MG_ARR_TMP]);
+        } else {
+            for (int colour = 0; colour < 2; colour++)
+                launch_bc_rb_colour<T>(stream_, L.g, c, bc_mask_, colour, ptr<T>(ax, level), ptr<T>(ar, level));
+        }
+    }
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::bc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs)
+{
+    MG_TRY(bc_check("mg_bc_smooth", 0));
+    if (!check_arr(arr_x, level, "mg_bc_smooth") || !check_arr(arr_rhs, level, "mg_bc_smooth")) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs || sweeps < 0 ||
+        (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS)) {
+        set_last_error("mg_bc_smooth: bad array / sweeps, or a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? bc_smooth_t<double>(level, smoother, sweeps, arr_x, arr_rhs)
+                              : bc_smooth_t<float>(level, smoother, sweeps, arr_x, arr_rhs);
+}
+
+template <typename T>
+int Solver::bc_restrict_t(int fl, int kind, int as, int ad)
+{
+    if (ad == MG_ARR_RHS) lv_[fl + 1].rhs_halo_ok = false;
+    if (kind == MG_RESTRICT_FULLW)
+        launch_bc_restrict_fw<T>(stream_, lv_[fl].g, lv_[fl + 1].g, bc_mask_, ptr<T>(as, fl), ptr<T>(ad, fl + 1));
+    else
+        launch_inject<T>(stream_, lv_[fl].g, lv_[fl + 1].g, ptr<T>(as, fl), ptr<T>(ad, fl + 1));
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::bc_restrict(int fine_level, int kind, int arr_src, int arr_dst)
+{
+    MG_TRY(bc_check("mg_bc_restrict", 0));
+    if (fine_level < 0 || fine_level + 1 >= d_.levels || !check_arr(arr_src, fine_level, "mg_bc_restrict") ||
+        !check_arr(arr_dst, fine_level + 1, "mg_bc_restrict") || (kind != MG_RESTRICT_INJECT && kind != MG_RESTRICT_FULLW)) {
+        set_last_error("mg_bc_restrict: bad level / array / kind");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? bc_restrict_t<double>(fine_level, kind, arr_src, arr_dst)
+                              : bc_restrict_t<float>(fine_level, kind, arr_src, arr_dst);
+}
+
+template <typename T>
+int Solver::bc_coarse_t(int level, int ax, int ar)
+{
+    Level &L = lv_[level];
+    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
+    launch_bc_coarse<T>(stream_, L.g, coef_of<T>(L), bc_mask_, (T)d_.omega, d_.smoother, ptr<T>(ax, level), ptr<T>(MG_ARR_TMP, level),
+                        ptr<T>(ar, level), d_.coarse_maxit, d_.coarse_tol, d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, d_coarse_);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::bc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
+{
+    MG_TRY(bc_check("mg_bc_coarse_solve", BC_NEED_SMOOTHER));
+    if (!check_arr(arr_x, level, "mg_bc_coarse_solve") || !check_arr(arr_rhs, level, "mg_bc_coarse_solve")) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs) { set_last_error("mg_bc_coarse_solve: bad array"); return MG_ERR_BAD_ARG; }
+    MG_TRY(d_.dtype == MG_F64 ? bc_coarse_t<double>(level, arr_x, arr_rhs) : bc_coarse_t<float>(level, arr_x, arr_rhs));
+    return fetch_cycle_stats(st);
+}
+
+// c = (sum w v) / (sum w), v -= (T)c. sum w is the product over the axes of (nodes - half a node per Neumann face): exact in double.
+template <typename T>
+int Solver::bc_project_t(int level, int arr, double *mean)
+{
+    Level &L = lv_[level];
+    if (arr == MG_ARR_RHS) L.rhs_halo_ok = false;
+    const Geom &g = L.g;
+    const int np = launch_bc_wsum<T>(stream_, g, bc_mask_, ptr<T>(arr, level), d_partials_, o4_partials_cap_);
+    launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_BC_SUM);
+    MG_HIP(hipGetLastError());
+    MG_TRY(fetch_scalars(SC_BC_SUM, d_scal_ + SC_BC_SUM));
+    auto halves = [&](int lo, int hi) { return 0.5 * (((bc_mask_ & lo) ? 1 : 0) + ((bc_mask_ & hi) ? 1 : 0)); };
+    double sw = ((double)g.nx - halves(MG_FACE_XLO, MG_FACE_XHI)) * ((double)g.ny - halves(MG_FACE_YLO, MG_FACE_YHI));
+    if (g.dim == 3) sw *= (double)g.gnz - halves(MG_FACE_ZLO, MG_FACE_ZHI);
+    const double c = h_scal_[SC_BC_SUM] / sw;
+    launch_bc_shift<T>(stream_, g, (T)c, ptr<T>(arr, level));
+    MG_HIP(hipGetLastError());
+    if (mean) *mean = c;
+    return MG_OK;
+}
+
+int Solver::bc_project(int level, int arr, double *mean)
+{
+    MG_TRY(bc_check("mg_bc_project", 0));
+    if (!check_arr(arr, level, "mg_bc_project")) return MG_ERR_BAD_ARG;
+    return d_.dtype == MG_F64 ? bc_project_t<double>(level, arr, mean) : bc_project_t<float>(level, arr, mean);
+}
+
+// cyc(l, kind) of mg_desc.h with the bc kernels, launch by launch
+template <typename T>
+int Solver::bc_cycle_rec_t(int l, int kind)
+{
+    const int L = d_.levels;
+    if (l == L - 1) {
+        const long long pts = (long long)lv_[l].g.nx * lv_[l].g.ny * lv_[l].g.gnz;
+        if (pts > 32768 && d_.coarse_mode == MG_COARSE_FIXED) {   // too big for one workgroup: chip-wide sweeps, as coarse_level_t
+            MG_TRY(bc_smooth_t<T>(l, d_.smoother, d_.coarse_maxit, MG_ARR_U, MG_ARR_RHS));
+            h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
+            h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;   // not evaluated on this path
+            MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
+        } else {
+            MG_TRY(bc_coarse_t<T>(l, MG_ARR_U, MG_ARR_RHS));
+        }
+        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
+        return MG_OK;
+    }
+    MG_TRY(bc_smooth_t<T>(l, d_.smoother, d_.nu_pre, MG_ARR_U, MG_ARR_RHS));
+    MG_TRY(bc_residual_t<T>(l, MG_ARR_U, MG_ARR_RHS, MG_ARR_TMP, false));
+    MG_TRY(bc_restrict_t<T>(l, d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
+    MG_TRY(zero_array(MG_ARR_U, l + 1));
+    MG_TRY(bc_cycle_rec_t<T>(l + 1, kind));
+    if (l + 1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(bc_cycle_rec_t<T>(l + 1, MG_CYCLE_W));   // continues from U(l + 1), RHS(l + 1) unchanged
+    if (l + 1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(bc_cycle_rec_t<T>(l + 1, MG_CYCLE_V));
+    MG_TRY(prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U));
+    return bc_smooth_t<T>(l, d_.smoother, d_.nu_post, MG_ARR_U, MG_ARR_RHS);
+}
+
+template <typename T>
+int Solver::bc_cycle_enqueue_t()
+{
+    if (d_.cycle == MG_CYCLE_V) return bc_cycle_rec_t<T>(0, MG_CYCLE_V);
+    MG_TRY(stats_begin());   // W and F make several coarse solves: summed on the device, as cycle_from_t
+    const int rc = bc_cycle_rec_t<T>(0, d_.cycle);
+    acc_stats_ = false;
+    MG_TRY(rc);
+    return stats_end();
+}
+
+int Solver::bc_cycle_enqueue() { return d_.dtype == MG_F64 ? bc_cycle_enqueue_t<double>() : bc_cycle_enqueue_t<float>(); }
+
+int Solver::bc_cycle(mg_cycle_stats *st)
+{
+    MG_TRY(bc_check("mg_bc_cycle", BC_NEED_CYCLE));
+    MG_TRY(bc_cycle_enqueue());
+    return fetch_cycle_stats(st);
+}
+
+// mg_solve's loop and history on this operator; desc.outer_pre_gs is ignored. All faces Neumann and no shift: the constants
+// are the null space, RHS(0) is projected onto the range first (it stays projected) and U(0) is projected at the end.
+template <typename T>
+int Solver::bc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    const bool singular = bc_singular();
+    if (singular) MG_TRY(bc_project_t<T>(0, MG_ARR_RHS, nullptr));
+    double nb = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    launch_bc_dirichlet_copy<T>(stream_, lv_[0].g, bc_mask_, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0));   // U = RHS on the Dirichlet nodes
+    MG_HIP(hipGetLastError());
+    int nh = 0;
+    auto norm = [&]() -> int {
+        MG_TRY(bc_residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
+        MG_TRY(fetch_scalars(SC_BC_SUM, d_scal_ + SC_BC_SUM));
+        const double rel = std::sqrt(h_scal_[SC_BC_SUM] / nb);
+        if (hist && nh < hist_cap) hist[nh] = rel;
+        nh++;
+        return MG_OK;
+    };
+    MG_TRY(norm());
+    for (int it = 0; it < maxit; it++) {
+        MG_TRY(bc_cycle_enqueue());
+        MG_TRY(fetch_cycle_stats(per_cycle ? &per_cycle[it] : nullptr));
+        MG_TRY(norm());
+        if (std::sqrt(h_scal_[SC_BC_SUM] / nb) <= tol) break;
+    }
+    if (singular) MG_TRY(bc_project_t<T>(0, MG_ARR_U, nullptr));
+    if (n_hist) *n_hist = nh;
+    return MG_OK;
+}
+
+int Solver::bc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    MG_TRY(bc_check("mg_bc_solve", BC_NEED_CYCLE));
+    if (maxit < 0) { set_last_error("mg_bc_solve: negative maxit"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? bc_solve_t<double>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
+                              : bc_solve_t<float>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
 }
 
 }  // namespace mg

@@ -310,6 +310,15 @@ inline bool vc_march_ok(int dim, int nx, int ny, int nz, int elem_size)
     return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
 }
 
+// ---- which levels the marching tile of mg_bc.hip takes (residual and Jacobi sweep of mg_bc_*); the plain form takes every
+// other one, every red-black colour pass and the restriction. vc_march_ok's shape rule: the same tile with one marched
+// field instead of two. Pure; tests/test_bc_cpu.py pins it.
+inline bool bc_march_ok(int dim, int nx, int ny, int nz, int elem_size)
+{
+    const int v = 16 / elem_size;
+    return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
+}
+
 struct CoarseOut {
     int iters;
     int flag;

@@ -326,6 +326,36 @@ template <typename T>
 int launch_vc_cg_direction(hipStream_t s, const Geom &g, const double coef[4], double sigma, const T *z, const T *p, const T *a, T *pn,
                            T *q, const CgScalars *sc, double *partials);
 
+// ---- the constant operator with Neumann faces (mg_bc.hip, driven by Solver::bc_*) ----
+// c: the level's Coef (shift included); mask: the Neumann faces (enum mg_face), 0 = the existing kernels' results bit for
+// bit. plain: never the marching tile.
+// r = b - L u (r == nullptr: norm only); one partial sum of r^2 per workgroup in `partials` (room for `cap`), returns how many
+template <typename T>
+int launch_bc_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, const T *u, const T *b, T *r, double *partials, int cap,
+                       bool plain);
+// one Jacobi sweep, out of place (out must not alias u)
+template <typename T>
+void launch_bc_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, T omega, const T *u, const T *b, T *out, bool plain);
+// one colour pass of red-black Gauss-Seidel, in place
+template <typename T>
+void launch_bc_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, int colour, T *u, const T *b);
+// full weighting with fine neighbours mirrored on the Neumann faces, coarse Dirichlet nodes injected
+template <typename T>
+void launch_bc_restrict_fw(hipStream_t s, const Geom &gf, const Geom &gc, int mask, const T *fine, T *coarse);
+// launch_coarse_solve's loop with the bc sweep (smoother 1: Jacobi, 2: red-black) and the bc residual, one workgroup
+template <typename T>
+void launch_bc_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, T omega, int smoother, T *x, T *tmp, const T *rhs,
+                      int maxit, double tol, int fixed, CoarseOut *d_out);
+// partial sums of w v, w = 1/2 per Neumann face the node lies on (room for `cap`), returns how many
+template <typename T>
+int launch_bc_wsum(hipStream_t s, const Geom &g, int mask, const T *v, double *partials, int cap);
+// v -= cval on every node
+template <typename T>
+void launch_bc_shift(hipStream_t s, const Geom &g, T cval, T *v);
+// x = rhs on the Dirichlet nodes of the mask
+template <typename T>
+void launch_bc_dirichlet_copy(hipStream_t s, const Geom &g, int mask, T *x, const T *rhs);
+
 // ---- device-resident array I/O (mg_io.hip, driven by Solver::device_copy) ----
 // padded: local plane 0 of a level-shaped array of geometry g with elements P; dense: the caller's dense device array of
 // g.nx * g.ny * g.nz elements D at any element-aligned address. to_padded: padded = (P)dense, padding columns written as

@@ -159,6 +159,17 @@ public:
     int vc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     int vc_pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     int vc_direction(double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq);   // the direction kernel alone
+    // the constant operator with Neumann faces (mg_bc_*): a face mask (enum mg_face), nothing allocated
+    int bc_set_faces(int mask);
+    int bc_get_faces(int *mask) const;
+    int bc_set_form(int form);   // tests and measurement tools: 1 = the plain kernels on every level, 0 = the default
+    int bc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
+    int bc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs);
+    int bc_restrict(int fine_level, int kind, int arr_src, int arr_dst);
+    int bc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st);
+    int bc_project(int level, int arr, double *mean);
+    int bc_cycle(mg_cycle_stats *st);
+    int bc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -309,6 +320,7 @@ private:
         SC_MX_SUM = 5,    // d_mx_sum_: mixed_solve, mixed_kernel
         SC_O4_SUM = 6,    // sum r^2 of the fourth-order residual: o4_solve, o4_residual, o4_correct_residual (written on the device)
         SC_VC_SUM = 7,    // sum r^2 of the variable-coefficient residual: vc_residual, vc_solve, vc_pcg_solve (written on the device)
+        SC_BC_SUM = SC_VC_SUM,   // mg_bc_*: sum r^2 or sum w v; shares the slot (every call fetches its sum before another family runs)
         SC_COUNT = 8      // the eight slots: one 64-byte line
     };
     double *d_scal_ = nullptr;      // [SC_COUNT]
@@ -382,6 +394,21 @@ private:
     template <typename T> int vc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     template <typename T> int vc_direction_t(double beta, const int *arrs, double *pq);
     template <typename T> int vc_pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
+    // Neumann-face drivers (mg_bc_*): the mask of Neumann faces, 0 = all Dirichlet
+    int bc_mask_ = 0;
+    bool bc_plain_ = false;
+    enum : unsigned { BC_NEED_CYCLE = 1u, BC_NEED_SMOOTHER = 2u };   // what bc_check asks of the descriptor
+    int bc_check(const char *fn, unsigned need);   // driver_begin, the cycle / smoother the bc drivers run
+    bool bc_singular() const { return bc_mask_ == (d_.dim == 3 ? 63 : 15) && shift_ == 0.0; }   // all faces Neumann, no shift: constants are the null space
+    template <typename T> int bc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_BC_SUM]
+    template <typename T> int bc_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
+    template <typename T> int bc_restrict_t(int fl, int kind, int as, int ad);
+    template <typename T> int bc_coarse_t(int level, int ax, int ar);
+    template <typename T> int bc_project_t(int level, int arr, double *mean);   // synchronises: the mean is fetched
+    template <typename T> int bc_cycle_rec_t(int l, int kind);
+    template <typename T> int bc_cycle_enqueue_t();
+    int bc_cycle_enqueue();
+    template <typename T> int bc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     // block of eig_solve: eig_[family][column] (enum mg_eig_family), level-0-shaped; the per-workgroup partial sums of up to
     // EIG_MAX_LAUNCHES Gram tiles, their totals, the coefficients of the combine (device) and a pinned mirror of the last two
     enum { EIG_FAMILIES = 6, EIG_MAX_LAUNCHES = 9, EIG_HOST_DOUBLES = 2048 };
