@@ -502,6 +502,70 @@ int mg_bc_project(mg_handle h, int level, int arr, double *mean);
 int mg_bc_cycle(mg_handle h, mg_cycle_stats *st);
 int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
 
+/* Nonlinear solves by the full approximation scheme, FAS (extension, no reference counterpart): the semilinear problem
+ *     N(u) = (sigma I + A) u + gamma g(u) = f
+ * with the handle's constant operator -- alpha, aniso, semi_xy, grids that are not 2^k + 1 and the shift of mg_set_shift keep
+ * their meaning --, all faces Dirichlet, and a pointwise reaction g; gamma is the same on every level. The cycle is the
+ * smoothing / restriction / prolongation recursion on the nonlinear problem itself: no global linearisation, no Jacobian. */
+enum mg_fas_kind { MG_FAS_CUBIC = 0 /* g = u^3 */, MG_FAS_EXP = 1 /* g = exp(u) */ };
+typedef struct mg_fas_stats {
+    int32_t status;   /* 0 converged, 1 hit maxit, 2 a norm that is not finite (it is the last hist entry; U is unspecified) */
+    int32_t cycles;   /* cycles done = n_hist - 1                                                                            */
+    double  norm0;    /* hist[0]                                                                                             */
+    double  norm;     /* the last norm                                                                                       */
+} mg_fas_stats;
+/* Arithmetic in the working dtype T, every operation rounded separately, the coefficients of mg_level_coefficients(h, l),
+ * G = (T)gamma. At interior nodes:
+ *   reaction     MG_FAS_CUBIC: q = u*u; g = q*u; gp = (T)3 * q.  MG_FAS_EXP: g = gp = exp(u) (the device library's exp / expf)
+ *   residual     sum = cz u(z-) + cy u(y-) + cx u(x-) + cd u_i + cx u(x+) + cy u(y+) + cz u(z+), added left to right (no z terms
+ *                in 2-D); r = b - (sum + G*g). Dirichlet nodes: r = b - u. The sum of r^2 over all nodes in double in a fixed
+ *                order, no atomics
+ *   point solve  s = the same sum without the diagonal term; num = (b - s) - G*(g - gp*u); den = cd + G*gp; ps = num / den,
+ *                the IEEE quotient -- one Newton step on the node's own equation, no inner iteration. Dirichlet nodes take b.
+ *                NOTHING GUARDS den: the supported regime is gamma g' >= 0 (monotone); other signs are the caller's risk
+ *                and end in status 2 of mg_fas_solve when a norm stops being finite.
+ *   Jacobi       out of place: u' = ps when desc.omega == 1, else u_i + omega*(ps - u_i)
+ *   red-black    in place, colour (i + j + k) & 1, colour 0 first
+ * With gamma == 0 these are mg_residual's and mg_smooth's results bit for bit, for both kinds.
+ *
+ * mg_fas_set_reaction / mg_fas_get_reaction: the kind and gamma (default MG_FAS_CUBIC, 0). Nothing is allocated and the
+ *   reaction may change at any time.
+ * mg_fas_residual, mg_fas_smooth, mg_fas_coarse_solve: the argument lists and aliasing rules of mg_vc_residual, mg_vc_smooth
+ *   and mg_vc_coarse_solve; the coarse solve is mg_coarse_solve's loop on the nonlinear residual and point solve.
+ * mg_fas_coarse_rhs(l): the FAS transition l -> l+1 in one launch, after the residual of level l is in TMP(l). Per coarse
+ *   node: uc = U(l) at the even fine node (the iterate goes down by INJECTION), written to U(l+1) and to E(l+1), the kept
+ *   copy; rc = the full weighting of TMP(l) in mg_restrict's order of operations, or its injection with MG_RESTRICT_INJECT
+ *   (desc.restriction); RHS(l+1) = rc + (sum_c + G*g(uc)), sum_c the residual's sum with the coefficients of level l+1 and the
+ *   coarse neighbours read from U(l). Coarse Dirichlet nodes: RHS(l+1) = uc. Semi transitions keep z as mg_restrict does.
+ * mg_fas_correct(l): E(l+1) = U(l+1) - E(l+1) rounded in T, then U(l) += P E(l+1) by mg_prolong(add = 1); E(l+1) holds the
+ *   coarse correction afterwards.
+ * mg_fas_cycle: cyc(0, desc.cycle) exactly as mg_vc_cycle words it, with these differences: the transition and the correction
+ *   are the two calls above, so U(l+1) starts from the injected iterate instead of 0, and a second visit (W, F) continues
+ *   from U(l+1) with RHS(l+1) and E(l+1) unchanged; the coarsest level runs mg_fas_coarse_solve. Launch by launch.
+ * mg_fas_solve: U = RHS on the Dirichlet nodes first; hist[k] = sqrt(sum r^2) over all nodes after k cycles -- ABSOLUTE
+ *   norms, because b = 0 is an ordinary nonlinear problem; stops when hist[k] <= max(atol, rtol * hist[0]) (k = 0 included) or
+ *   k == maxit; at the first norm that is not finite it stops with status 2. One host synchronisation per cycle.
+ *   desc.outer_pre_gs is IGNORED. FAS CONVERGES LOCALLY: the starting iterate in U is the caller's (DESIGN.md section 20 has
+ *   a case that diverges from u = 0); there is no line search and no nested iteration.
+ * mg_fas_set_form (tests and measurement tools): form 1 runs the one-thread-per-node kernels on every level, form 0 (the
+ *   default) the marching tile where the level's shape admits it (3-D, at least 16 full 16-byte vectors per row).
+ * MG_ERR_BAD_ARG with nothing changed: an unknown kind or a gamma that is not finite; a smoother other than Jacobi or
+ * red-black (mg_fas_smooth's argument; the handle's for cycle, solve, coarse_solve); a sawtooth handle or a stage callback
+ * installed (cycle, solve); distributed handles (dry runs included); bad arrays or levels and the aliasing mg_vc_residual /
+ * mg_vc_smooth reject; negative or non-finite tolerances, maxit < 0; NULL handle. No other entry point changes behaviour, and
+ * the family allocates nothing. Not combined with mg_vc_*, mg_bc_*, mg_o4_*, mg_fmg, mg_mixed_solve or mg_heat_step;
+ * mg_set_shift(1/dt) + mg_fas_solve is one implicit reaction-diffusion step. */
+int mg_fas_set_reaction(mg_handle h, int kind, double gamma);
+int mg_fas_get_reaction(mg_handle h, int *kind, double *gamma);
+int mg_fas_set_form(mg_handle h, int form);
+int mg_fas_residual(mg_handle h, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
+int mg_fas_smooth(mg_handle h, int level, int smoother, int sweeps, int arr_x, int arr_rhs);
+int mg_fas_coarse_rhs(mg_handle h, int fine_level);
+int mg_fas_correct(mg_handle h, int fine_level);
+int mg_fas_coarse_solve(mg_handle h, int level, int arr_x, int arr_rhs, mg_cycle_stats *st);
+int mg_fas_cycle(mg_handle h, mg_cycle_stats *st);
+int mg_fas_solve(mg_handle h, double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st);
+
 /* Diagonal shift (extension, no reference counterpart): from this call on the handle works on sigma I + A, sigma >= 0 --
  * the operator of an implicit time step or a screened-Poisson / Helmholtz-type solve. On every level the diagonal becomes
  * cd0_l + sigma (one fp64 addition, then cast to the working dtype like every coefficient), cd0_l being the diagonal the

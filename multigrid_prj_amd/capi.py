@@ -17,6 +17,7 @@ CYCLE_SAWTOOTH, CYCLE_V = 0, 1
 CYCLE_W, CYCLE_F = 2, 3
 RESTRICT_INJECT, RESTRICT_FULLW = 0, 1
 FACE_XLO, FACE_XHI, FACE_YLO, FACE_YHI, FACE_ZLO, FACE_ZHI = 1, 2, 4, 8, 16, 32   # enum mg_face: the Neumann faces of mg_bc_*
+FAS_CUBIC, FAS_EXP = 0, 1   # enum mg_fas_kind: the reaction g of mg_fas_* (u^3, exp(u))
 COARSE_TOL, COARSE_FIXED = 0, 1
 ARR_U, ARR_E, ARR_RHS, ARR_TMP, ARR_RES = 0, 1, 2, 3, 4
 MG_COMM_ID_BYTES = 128
@@ -68,6 +69,15 @@ class MgFmgStats(C.Structure):
     _fields_ = [
         ("levels", C.c_int32), ("cycles_per_level", C.c_int32), ("coarse_iters", C.c_int32), ("coarse_flag", C.c_int32),
         ("relres", C.c_double),
+    ]
+
+
+class MgFasStats(C.Structure):
+    """include/mg_hip.h::mg_fas_stats (mg_fas_solve)"""
+
+    _fields_ = [
+        ("status", C.c_int32), ("cycles", C.c_int32),
+        ("norm0", C.c_double), ("norm", C.c_double),
     ]
 
 
@@ -156,6 +166,8 @@ EXPORTS = [
     "mg_vc_coarse_solve", "mg_vc_cycle", "mg_vc_solve", "mg_vc_pcg_solve", "mg_vc_direction",
     "mg_bc_set_faces", "mg_bc_get_faces", "mg_bc_set_form", "mg_bc_residual", "mg_bc_smooth", "mg_bc_restrict", "mg_bc_coarse_solve",
     "mg_bc_project", "mg_bc_cycle", "mg_bc_solve",
+    "mg_fas_set_reaction", "mg_fas_get_reaction", "mg_fas_set_form", "mg_fas_residual", "mg_fas_smooth", "mg_fas_coarse_rhs", "mg_fas_correct",
+    "mg_fas_coarse_solve", "mg_fas_cycle", "mg_fas_solve",
     "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_set_source_device", "mg_heat_step", "mg_heat_rhs",
     "mg_eig_solve", "mg_eig_set_vector", "mg_eig_get_vector", "mg_eig_set_vector_device", "mg_eig_get_vector_device",
     "mg_eig_block", "mg_eig_kernel",
@@ -243,6 +255,16 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_bc_project.argtypes = [vp, i, i, dp]
     L.mg_bc_cycle.argtypes = [vp, C.POINTER(MgCycleStats)]
     L.mg_bc_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
+    L.mg_fas_set_reaction.argtypes = [vp, i, C.c_double]
+    L.mg_fas_get_reaction.argtypes = [vp, C.POINTER(i), dp]
+    L.mg_fas_set_form.argtypes = [vp, i]
+    L.mg_fas_residual.argtypes = [vp, i, i, i, i, dp]
+    L.mg_fas_smooth.argtypes = [vp, i, i, i, i, i]
+    L.mg_fas_coarse_rhs.argtypes = [vp, i]
+    L.mg_fas_correct.argtypes = [vp, i]
+    L.mg_fas_coarse_solve.argtypes = [vp, i, i, i, C.POINTER(MgCycleStats)]
+    L.mg_fas_cycle.argtypes = [vp, C.POINTER(MgCycleStats)]
+    L.mg_fas_solve.argtypes = [vp, C.c_double, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgFasStats)]
     L.mg_set_shift.argtypes = [vp, C.c_double]
     L.mg_get_shift.argtypes = [vp, dp]
     L.mg_heat_set_source.argtypes = [vp, vp]
@@ -665,6 +687,45 @@ class Solver:
         stats = (MgCycleStats * max(maxit, 1))()
         _check(self.lib.mg_bc_solve(self.h, tol, maxit, hist, maxit + 1, C.byref(nh), stats))
         return np.array(hist[:nh.value]), list(stats[:nh.value - 1])
+
+    # -- nonlinear solves by the full approximation scheme: (sigma I + A) u + gamma g(u) = f (mg_fas_*, include/mg_hip.h)
+    def fas_set_reaction(self, kind, gamma):
+        """mg_fas_set_reaction: g = u^3 (FAS_CUBIC) or exp(u) (FAS_EXP) and its factor gamma"""
+        _check(self.lib.mg_fas_set_reaction(self.h, int(kind), float(gamma)))
+
+    def fas_get_reaction(self):
+        """-> (kind, gamma)"""
+        k = C.c_int(0); g = C.c_double(0); _check(self.lib.mg_fas_get_reaction(self.h, C.byref(k), C.byref(g))); return k.value, g.value
+
+    def fas_set_form(self, form):
+        """mg_fas_set_form (tests and measurement tools): 1 = the plain kernels on every level, 0 = the default"""
+        _check(self.lib.mg_fas_set_form(self.h, int(form)))
+
+    def fas_residual(self, level, arr_x, arr_rhs, arr_r=-1) -> float:
+        s = C.c_double(0); _check(self.lib.mg_fas_residual(self.h, level, arr_x, arr_rhs, arr_r, C.byref(s))); return s.value
+
+    def fas_smooth(self, level, smoother, sweeps, arr_x, arr_rhs):
+        _check(self.lib.mg_fas_smooth(self.h, level, smoother, sweeps, arr_x, arr_rhs))
+
+    def fas_coarse_rhs(self, fine_level):
+        """mg_fas_coarse_rhs: TMP(l), U(l) -> U, E, RHS of level l + 1"""
+        _check(self.lib.mg_fas_coarse_rhs(self.h, fine_level))
+
+    def fas_correct(self, fine_level):
+        """mg_fas_correct: U(l) += P (U(l+1) - E(l+1)); E(l+1) holds the difference afterwards"""
+        _check(self.lib.mg_fas_correct(self.h, fine_level))
+
+    def fas_coarse_solve(self, level, arr_x, arr_rhs) -> MgCycleStats:
+        st = MgCycleStats(); _check(self.lib.mg_fas_coarse_solve(self.h, level, arr_x, arr_rhs, C.byref(st))); return st
+
+    def fas_cycle(self) -> MgCycleStats:
+        st = MgCycleStats(); _check(self.lib.mg_fas_cycle(self.h, C.byref(st))); return st
+
+    def fas_solve(self, rtol=1e-10, atol=0.0, maxit=50):
+        """mg_fas_solve -> (hist of absolute residual norms, MgFasStats)"""
+        hist = (C.c_double * (maxit + 1))(); nh = C.c_int(0); st = MgFasStats()
+        _check(self.lib.mg_fas_solve(self.h, rtol, atol, maxit, hist, maxit + 1, C.byref(nh), C.byref(st)))
+        return np.array(hist[:nh.value]), st
 
     def heat_set_source(self, f):
         """mg_heat_set_source: the source term f of u_t = -A0 u + f (level-0 array of the handle's dtype); None: f = 0"""

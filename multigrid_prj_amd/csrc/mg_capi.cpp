@@ -347,6 +347,33 @@ int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, 
     if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_bc_solve: bad history buffer");
     return guarded([&] { return h->impl->bc_solve(tol, maxit, hist, hist_cap, n_hist, per_cycle); });
 }
+int mg_fas_set_reaction(mg_handle h, int kind, double gamma) { MG_H(h); return guarded([&] { return h->impl->fas_set_reaction(kind, gamma); }); }
+int mg_fas_get_reaction(mg_handle h, int *kind, double *gamma) { MG_H(h); return h->impl->fas_get_reaction(kind, gamma); }
+int mg_fas_set_form(mg_handle h, int form) { MG_H(h); return guarded([&] { return h->impl->fas_set_form(form); }); }
+int mg_fas_residual(mg_handle h, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->fas_residual(level, arr_x, arr_rhs, arr_r, sumsq_r); });
+}
+int mg_fas_smooth(mg_handle h, int level, int smoother, int sweeps, int arr_x, int arr_rhs)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->fas_smooth(level, smoother, sweeps, arr_x, arr_rhs); });
+}
+int mg_fas_coarse_rhs(mg_handle h, int fine_level) { MG_H(h); return guarded([&] { return h->impl->fas_coarse_rhs(fine_level); }); }
+int mg_fas_correct(mg_handle h, int fine_level) { MG_H(h); return guarded([&] { return h->impl->fas_correct(fine_level); }); }
+int mg_fas_coarse_solve(mg_handle h, int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->fas_coarse_solve(level, arr_x, arr_rhs, st); });
+}
+int mg_fas_cycle(mg_handle h, mg_cycle_stats *st) { MG_H(h); return guarded([&] { return h->impl->fas_cycle(st); }); }
+int mg_fas_solve(mg_handle h, double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st)
+{
+    MG_H(h);
+    if (hist_cap < 0 || (hist_cap > 0 && !hist)) return bad("mg_fas_solve: bad history buffer");
+    return guarded([&] { return h->impl->fas_solve(rtol, atol, maxit, hist, hist_cap, n_hist, st); });
+}
 int mg_set_shift(mg_handle h, double sigma) { MG_H(h); return guarded([&] { return h->impl->set_shift(sigma); }); }
 int mg_get_shift(mg_handle h, double *sigma)
 {

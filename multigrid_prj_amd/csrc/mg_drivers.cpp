@@ -1,5 +1,5 @@
 // mg_drivers.cpp -- the solve drivers of mg::Solver: everything that calls the cycle from above (mg_solve, mg_pcg_*, mg_fmg*,
-// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*, mg_eig_*, mg_vc_*, mg_bc_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
+// mg_mixed_*, mg_o4_*, mg_set_shift, mg_heat_*, mg_eig_*, mg_vc_*, mg_bc_*, mg_fas_*) and the helpers they share. The hierarchy and the cycle itself are in mg_solver.cpp.
 // Reference call structure being replaced by solve(): the outer loop of src/main.cpp:72-116.
 #include "mg_solver.h"
 #include "mg_dense.h"
@@ -1698,6 +1698,259 @@ int Solver::bc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_h
     if (maxit < 0) { set_last_error("mg_bc_solve: negative maxit"); return MG_ERR_BAD_ARG; }
     return d_.dtype == MG_F64 ? bc_solve_t<double>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
                               : bc_solve_t<float>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
+}
+
+// ---------------------------------------------------------------- the full approximation scheme (mg_fas_*), DESIGN.md section 20
+// N(u) = (sigma I + A) u + gamma g(u) with the handle's constant operator, all faces Dirichlet, gamma the same on every level.
+// The cycle is mg_vc_cycle's recursion on the nonlinear problem itself: the coarse level starts from the INJECTED iterate (kept
+// in E), its right-hand side is R r + N_c(injected iterate), and the correction is the difference to the kept copy. The
+// kernels are in mg_fas.hip; everything goes launch by launch. Nothing is allocated: the state is the kind and gamma.
+int Solver::fas_check(const char *fn, unsigned need)
+{
+    MG_TRY(driver_begin(fn, REFUSE_DIST | ((need & FAS_NEED_CYCLE) ? REFUSE_STAGE_CB : 0u)));
+    if ((need & FAS_NEED_CYCLE) && !is_vwf(d_.cycle)) {
+        set_last_error(std::string(fn) + ": not on a sawtooth handle (the cycle must be MG_CYCLE_V, MG_CYCLE_W or MG_CYCLE_F)");
+        return MG_ERR_BAD_ARG;
+    }
+    if ((need & (FAS_NEED_CYCLE | FAS_NEED_SMOOTHER)) && d_.smoother != MG_SMOOTH_JACOBI && d_.smoother != MG_SMOOTH_RBGS) {
+        set_last_error(std::string(fn) + ": the handle's smoother must be MG_SMOOTH_JACOBI or MG_SMOOTH_RBGS");
+        return MG_ERR_BAD_ARG;
+    }
+    return MG_OK;
+}
+
+int Solver::fas_set_reaction(int kind, double gamma)
+{
+    MG_TRY(driver_begin("mg_fas_set_reaction", REFUSE_DIST));
+    if (kind != MG_FAS_CUBIC && kind != MG_FAS_EXP) { set_last_error("mg_fas_set_reaction: the kind must be MG_FAS_CUBIC or MG_FAS_EXP"); return MG_ERR_BAD_ARG; }
+    if (!std::isfinite(gamma)) { set_last_error("mg_fas_set_reaction: gamma must be finite"); return MG_ERR_BAD_ARG; }
+    fas_kind_ = kind;
+    fas_gamma_ = gamma;
+    return MG_OK;
+}
+
+int Solver::fas_get_reaction(int *kind, double *gamma) const
+{
+    if (kind) *kind = fas_kind_;
+    if (gamma) *gamma = fas_gamma_;
+    return MG_OK;
+}
+
+int Solver::fas_set_form(int form)
+{
+    if (form != 0 && form != 1) { set_last_error("mg_fas_set_form: form must be 0 (default) or 1 (the plain kernels everywhere)"); return MG_ERR_BAD_ARG; }
+    fas_plain_ = form == 1;
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::fas_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
+{
+    Level &L = lv_[level];
+    if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
+    const int np = launch_fas_residual<T>(stream_, L.g, coef_of<T>(L), fas_kind_, (T)fas_gamma_, ptr<T>(ax, level), ptr<T>(ar, level),
+                                          arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr, d_partials_, o4_partials_cap_, fas_plain_);
+    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_FAS_SUM);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::fas_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
+{
+    MG_TRY(fas_check("mg_fas_residual", 0));
+    if (!check_arr(arr_x, level, "mg_fas_residual") || !check_arr(arr_rhs, level, "mg_fas_residual")) return MG_ERR_BAD_ARG;
+    if (arr_r >= 0 && (!check_arr(arr_r, level, "mg_fas_residual") || arr_r == arr_x || arr_r == arr_rhs)) {
+        set_last_error("mg_fas_residual: bad output array");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_TRY(d_.dtype == MG_F64 ? fas_residual_t<double>(level, arr_x, arr_rhs, arr_r, true) : fas_residual_t<float>(level, arr_x, arr_rhs, arr_r, true));
+    if (sumsq_r) {
+        MG_TRY(fetch_scalars(SC_FAS_SUM, d_scal_ + SC_FAS_SUM));
+        *sumsq_r = h_scal_[SC_FAS_SUM];
+    }
+    return MG_OK;
+}
+
+template <typename T>
+int Solver::fas_smooth_t(int level, int smoother, int sweeps, int ax, int ar)
+{
+    Level &L = lv_[level];
+    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
+    const Coef<T> c = coef_of<T>(L);
+    const T G = (T)fas_gamma_;
+    for (int s = 0; s < sweeps; s++) {
+        if (smoother == MG_SMOOTH_JACOBI) {   // out of place into TMP, then the two pointers are swapped (as smooth_t)
+            launch_fas_jacobi<T>(stream_, L.g, c, fas_kind_, G, (T)d_.omega, ptr<T>(ax, level), ptr<T>(ar, level), ptr<T>(MG_ARR_TMP, level),
+                                 fas_plain_);
+            std::swap(L.base[ax], L.base[MG_ARR_TMP]);
+        } else {
+            for (int colour = 0; colour < 2; colour++)
+                launch_fas_rb_colour<T>(stream_, L.g, c, fas_kind_, G, colour, ptr<T>(ax, level), ptr<T>(ar, level));
+        }
+    }
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::fas_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs)
+{
+    MG_TRY(fas_check("mg_fas_smooth", 0));
+    if (!check_arr(arr_x, level, "mg_fas_smooth") || !check_arr(arr_rhs, level, "mg_fas_smooth")) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs || sweeps < 0 ||
+        (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS)) {
+        set_last_error("mg_fas_smooth: bad array / sweeps, or a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? fas_smooth_t<double>(level, smoother, sweeps, arr_x, arr_rhs)
+                              : fas_smooth_t<float>(level, smoother, sweeps, arr_x, arr_rhs);
+}
+
+// TMP(fl) holds the residual of level fl: U, E and RHS of level fl + 1 in one launch
+template <typename T>
+int Solver::fas_coarse_rhs_t(int fl)
+{
+    lv_[fl + 1].rhs_halo_ok = false;
+    launch_fas_coarse_rhs<T>(stream_, lv_[fl].g, lv_[fl + 1].g, coef_of<T>(lv_[fl + 1]), fas_kind_, (T)fas_gamma_,
+                             d_.restriction == MG_RESTRICT_INJECT, ptr<T>(MG_ARR_U, fl), ptr<T>(MG_ARR_TMP, fl), ptr<T>(MG_ARR_U, fl + 1),
+                             ptr<T>(MG_ARR_E, fl + 1), ptr<T>(MG_ARR_RHS, fl + 1));
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::fas_coarse_rhs(int fine_level)
+{
+    MG_TRY(fas_check("mg_fas_coarse_rhs", 0));
+    if (fine_level < 0 || fine_level + 1 >= d_.levels) { set_last_error("mg_fas_coarse_rhs: bad level"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? fas_coarse_rhs_t<double>(fine_level) : fas_coarse_rhs_t<float>(fine_level);
+}
+
+// E(fl + 1) = U(fl + 1) - E(fl + 1), then U(fl) += P E(fl + 1): E(fl + 1) holds the coarse correction afterwards
+template <typename T>
+int Solver::fas_correct_t(int fl)
+{
+    launch_fas_diff<T>(stream_, lv_[fl + 1].g, ptr<T>(MG_ARR_U, fl + 1), ptr<T>(MG_ARR_E, fl + 1));
+    MG_HIP(hipGetLastError());
+    return prolong_t<T>(fl + 1, 1, MG_ARR_E, MG_ARR_U);
+}
+
+int Solver::fas_correct(int fine_level)
+{
+    MG_TRY(fas_check("mg_fas_correct", 0));
+    if (fine_level < 0 || fine_level + 1 >= d_.levels) { set_last_error("mg_fas_correct: bad level"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? fas_correct_t<double>(fine_level) : fas_correct_t<float>(fine_level);
+}
+
+template <typename T>
+int Solver::fas_coarse_t(int level, int ax, int ar)
+{
+    Level &L = lv_[level];
+    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
+    launch_fas_coarse<T>(stream_, L.g, coef_of<T>(L), fas_kind_, (T)fas_gamma_, (T)d_.omega, d_.smoother, ptr<T>(ax, level),
+                         ptr<T>(MG_ARR_TMP, level), ptr<T>(ar, level), d_.coarse_maxit, d_.coarse_tol,
+                         d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, d_coarse_);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+int Solver::fas_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
+{
+    MG_TRY(fas_check("mg_fas_coarse_solve", FAS_NEED_SMOOTHER));
+    if (!check_arr(arr_x, level, "mg_fas_coarse_solve") || !check_arr(arr_rhs, level, "mg_fas_coarse_solve")) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs) { set_last_error("mg_fas_coarse_solve: bad array"); return MG_ERR_BAD_ARG; }
+    MG_TRY(d_.dtype == MG_F64 ? fas_coarse_t<double>(level, arr_x, arr_rhs) : fas_coarse_t<float>(level, arr_x, arr_rhs));
+    return fetch_cycle_stats(st);
+}
+
+// cyc(l, kind) of mg_desc.h on the nonlinear problem, launch by launch
+template <typename T>
+int Solver::fas_cycle_rec_t(int l, int kind)
+{
+    const int L = d_.levels;
+    if (l == L - 1) {
+        const long long pts = (long long)lv_[l].g.nx * lv_[l].g.ny * lv_[l].g.gnz;
+        if (pts > 32768 && d_.coarse_mode == MG_COARSE_FIXED) {   // too big for one workgroup: chip-wide sweeps, as coarse_level_t
+            MG_TRY(fas_smooth_t<T>(l, d_.smoother, d_.coarse_maxit, MG_ARR_U, MG_ARR_RHS));
+            h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
+            h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;   // not evaluated on this path
+            MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
+        } else {
+            MG_TRY(fas_coarse_t<T>(l, MG_ARR_U, MG_ARR_RHS));
+        }
+        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
+        return MG_OK;
+    }
+    MG_TRY(fas_smooth_t<T>(l, d_.smoother, d_.nu_pre, MG_ARR_U, MG_ARR_RHS));
+    MG_TRY(fas_residual_t<T>(l, MG_ARR_U, MG_ARR_RHS, MG_ARR_TMP, false));
+    MG_TRY(fas_coarse_rhs_t<T>(l));   // U(l + 1) = E(l + 1) = the injected iterate, RHS(l + 1)
+    MG_TRY(fas_cycle_rec_t<T>(l + 1, kind));
+    if (l + 1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(fas_cycle_rec_t<T>(l + 1, MG_CYCLE_W));   // continues from U(l + 1); RHS(l + 1), E(l + 1) unchanged
+    if (l + 1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(fas_cycle_rec_t<T>(l + 1, MG_CYCLE_V));
+    MG_TRY(fas_correct_t<T>(l));
+    return fas_smooth_t<T>(l, d_.smoother, d_.nu_post, MG_ARR_U, MG_ARR_RHS);
+}
+
+template <typename T>
+int Solver::fas_cycle_enqueue_t()
+{
+    if (d_.cycle == MG_CYCLE_V) return fas_cycle_rec_t<T>(0, MG_CYCLE_V);
+    MG_TRY(stats_begin());   // W and F make several coarse solves: summed on the device, as cycle_from_t
+    const int rc = fas_cycle_rec_t<T>(0, d_.cycle);
+    acc_stats_ = false;
+    MG_TRY(rc);
+    return stats_end();
+}
+
+int Solver::fas_cycle_enqueue() { return d_.dtype == MG_F64 ? fas_cycle_enqueue_t<double>() : fas_cycle_enqueue_t<float>(); }
+
+int Solver::fas_cycle(mg_cycle_stats *st)
+{
+    MG_TRY(fas_check("mg_fas_cycle", FAS_NEED_CYCLE));
+    MG_TRY(fas_cycle_enqueue());
+    return fetch_cycle_stats(st);
+}
+
+// hist[k] = sqrt(sum r^2) after k cycles, ABSOLUTE (b = 0 is an ordinary nonlinear problem); one synchronisation per cycle
+template <typename T>
+int Solver::fas_solve_t(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st)
+{
+    launch_bc_dirichlet_copy<T>(stream_, lv_[0].g, 0, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0));   // U = RHS on the Dirichlet nodes
+    MG_HIP(hipGetLastError());
+    int nh = 0, status = 1;
+    double first = 0, last = 0;
+    auto norm = [&]() -> int {
+        MG_TRY(fas_residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
+        MG_TRY(fetch_scalars(SC_FAS_SUM, d_scal_ + SC_FAS_SUM));
+        last = std::sqrt(h_scal_[SC_FAS_SUM]);
+        if (nh == 0) first = last;
+        if (hist && nh < hist_cap) hist[nh] = last;
+        nh++;
+        return MG_OK;
+    };
+    // 0 converged, 2 not finite, -1 go on
+    auto verdict = [&]() { return !std::isfinite(last) ? 2 : (last <= std::max(atol, rtol * first) ? 0 : -1); };
+    MG_TRY(norm());
+    int v = verdict();
+    int it = 0;
+    for (; v < 0 && it < maxit; it++) {
+        MG_TRY(fas_cycle_enqueue());
+        MG_TRY(norm());
+        v = verdict();
+    }
+    if (v >= 0) status = v;
+    if (n_hist) *n_hist = nh;
+    if (st) { st->status = status; st->cycles = it; st->norm0 = first; st->norm = last; }
+    return MG_OK;
+}
+
+int Solver::fas_solve(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st)
+{
+    MG_TRY(fas_check("mg_fas_solve", FAS_NEED_CYCLE));
+    if (!(rtol >= 0) || !(atol >= 0) || !std::isfinite(rtol) || !std::isfinite(atol) || maxit < 0) {
+        set_last_error("mg_fas_solve: the tolerances must be finite and >= 0, maxit >= 0");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? fas_solve_t<double>(rtol, atol, maxit, hist, hist_cap, n_hist, st)
+                              : fas_solve_t<float>(rtol, atol, maxit, hist, hist_cap, n_hist, st);
 }
 
 }  // namespace mg

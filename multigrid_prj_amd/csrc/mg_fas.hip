@@ -1,0 +1,564 @@
+// mg_fas.hip -- kernels of the SEMILINEAR operator N(u) = (sigma I + A) u + gamma g(u) of the full approximation scheme
+// (mg_fas_*, include/mg_hip.h; drivers: Solver::fas_* in mg_drivers.cpp). The linear part is the
+// handle's constant operator (alpha, aniso, semi_xy, odd sizes, the shift of mg_set_shift), all faces Dirichlet; the reaction
+// g is pointwise, so every kernel is the 7-point stream of the constant operator plus a few flops on the centre value.
+//
+//   k_fas_plain<T, DIM, KIND, OP, SAVE>  OP = residual (stored with SAVE, else norm only) / Jacobi sweep (out of place) / one
+//                                        red-black colour pass (in place): one thread per node, grid-stride, every shape
+//   k_fas_march<T, KIND, OP, SAVE>       the residual and the Jacobi sweep on 3-D levels with rows long enough to fill a wave
+//                                        (fas_march_ok, mg_geom.h): k_bc_march's tile (mg_bc.hip) with one marched field
+//   k_fas_coarse_rhs<T, DIM, WZ, KIND>   the FAS transition l -> l+1 in one launch: U(l+1) = E(l+1) = U(l) injected,
+//                                        RHS(l+1) = R TMP(l) + N_c(U(l) injected), the coarse neighbours read from U(l)
+//   k_fas_diff<T>                        e = x - e (the coarse correction U(l+1) - E(l+1), into E(l+1))
+//   k_fas_coarse<T, DIM, KIND>           the Solver::Solve loop of k_coarse_solve (mg_kernels.hip) in one workgroup
+//
+// Arithmetic contract (compiled with -ffp-contract=off; tests/fas_ref.py restates it in numpy), all in T, every operation
+// rounded separately, c = the level's Coef (mg_level_coefficients: shift and aniso included), G = (T)gamma:
+//   reaction     MG_FAS_CUBIC: q = u*u; g = q*u; gp = (T)3 * q.   MG_FAS_EXP: g = gp = exp(u) (the device library's exp / expf)
+//   residual     sum = full_sum's expression (z-, y-, x-, d, x+, y+, z+); r = b - (sum + G*g); Dirichlet nodes: r = b - u;
+//                the sum of r^2 over ALL nodes in double, fixed order, no atomics
+//   point solve  s = offdiag_sum's expression; num = (b - s) - G*(g - gp*u); den = cd + G*gp; ps = num / den (the IEEE
+//                quotient: one Newton step on the node's own equation); Dirichlet nodes take b. Nothing guards den.
+//   Jacobi       u' = ps (omega == 1) or u_i + omega * (ps - u_i)
+//   red-black    in place, colour (i + j + gz) & 1, colour 0 first; Dirichlet nodes take b with their colour
+// With gamma == 0 num = b - s and den = cd, and the correctly rounded quotient is div_cd's: mg_residual's and mg_smooth's bits.
+#include "mg_kernels.h"
+#include "mg_device.h"
+
+#include <algorithm>
+
+namespace mg {
+namespace {
+
+constexpr int FAS_THREADS = 256, FAS_MAX_BLOCKS = 2048;
+constexpr int FBW = 4, FRY = 2;   // waves per workgroup / rows per wave of the marching tile
+enum { FAS_RES = 0, FAS_JAC = 1, FAS_RB = 2 };
+enum { FAS_CUBIC = 0, FAS_EXP = 1 };   // enum mg_fas_kind
+
+__device__ __forceinline__ double fas_exp(double x) { return exp(x); }
+__device__ __forceinline__ float fas_exp(float x) { return expf(x); }
+
+// g(u) and g'(u)
+template <typename T, int KIND>
+__device__ __forceinline__ void fas_react(T u, T &gv, T &gp)
+{
+    if (KIND == FAS_CUBIC) {
+        const T q = u * u;
+        gv = q * u;
+        gp = (T)3 * q;
+    } else {
+        gv = gp = fas_exp(u);
+    }
+}
+
+// the point solve from the off-diagonal sum s, the centre value and the right-hand side
+template <typename T, int KIND>
+__device__ __forceinline__ T fas_newton(const Coef<T> &c, T G, T s, T ui, T bi)
+{
+    T gv, gp;
+    fas_react<T, KIND>(ui, gv, gp);
+    const T num = (bi - s) - G * (gv - gp * ui);
+    const T den = c.cd + G * gp;
+    return num / den;
+}
+
+template <typename T, int DIM, int KIND>
+__device__ __forceinline__ T fas_point_res(const Geom &g, const Coef<T> &c, T G, const T *u, const T *b, int z, int y, int x)
+{
+    const long long i = lidx(g, z, y, x);
+    T sum;
+    if (on_boundary(g, z, y, x)) {
+        sum = (T)1 * u[i];
+    } else {
+        T gv, gp;
+        fas_react<T, KIND>(u[i], gv, gp);
+        sum = full_sum<T, DIM>(u, i, g.pitch, g.plane, c) + G * gv;
+    }
+    return b[i] - sum;
+}
+
+template <typename T, int DIM, int KIND>
+__device__ __forceinline__ T fas_point_solve(const Geom &g, const Coef<T> &c, T G, T omega, bool damped, const T *u, const T *b,
+                                             int z, int y, int x)
+{
+    const long long i = lidx(g, z, y, x);
+    const T bi = b[i];
+    if (on_boundary(g, z, y, x)) return bi;
+    const T s = offdiag_sum<T, DIM>(u, i, g.pitch, g.plane, c);
+    const T ui = u[i];
+    const T ps = fas_newton<T, KIND>(c, G, s, ui, bi);
+    if (damped) return ui + omega * (ps - ui);
+    return ps;
+}
+
+// ---------------------------------------------------------------- the plain form
+// out: r (FAS_RES with SAVE), u' (FAS_JAC, must not alias u) or u itself (FAS_RB: the other colour is only read)
+template <typename T, int DIM, int KIND, int OP, bool SAVE>
+__global__ __launch_bounds__(FAS_THREADS) void k_fas_plain(Geom g, Coef<T> c, T G, T omega, int colour, const T *u,
+                                                           const T *__restrict__ b, T *out, double *__restrict__ partials)
+{
+    __shared__ double sh[FAS_THREADS / 64];
+    const int hx = OP == FAS_RB ? (g.nx + 1) / 2 : g.nx;   // nodes of a row this launch visits
+    const long long nitems = (long long)hx * g.ny * g.nz;
+    const bool damped = OP == FAS_JAC && omega != (T)1;
+    double acc = 0.;
+    for (long long it = (long long)blockIdx.x * FAS_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * FAS_THREADS) {
+        const long long row = it / hx;
+        int x = (int)(it - row * hx);
+        const int y = (int)(row % g.ny), z = (int)(row / g.ny);
+        if (OP == FAS_RB) {
+            x = 2 * x + ((y + g.gz0 + z + colour) & 1);   // the x parity that has (x + y + gz) & 1 == colour
+            if (x >= g.nx) continue;
+        }
+        if (OP == FAS_RES) {
+            const T res = fas_point_res<T, DIM, KIND>(g, c, G, u, b, z, y, x);
+            acc += (double)res * (double)res;
+            if (SAVE) out[lidx(g, z, y, x)] = res;
+        } else {
+            out[lidx(g, z, y, x)] = fas_point_solve<T, DIM, KIND>(g, c, G, omega, damped, u, b, z, y, x);
+        }
+    }
+    if (OP == FAS_RES) {
+        const double s = block_sum(acc, sh);
+        if (threadIdx.x == 0) partials[blockIdx.x] = s;
+    }
+}
+
+// ---------------------------------------------------------------- the marching tile (3-D)
+// k_bc_march's tile: a lane owns one aligned 16-byte vector of x, a wave covers 64 vectors of FRY = 2 rows, FBW = 4 waves are
+// stacked in y and the workgroup marches zc planes with the planes z-1, z, z+1 of u in registers. The reaction term is
+// computed from the centre value the lane holds: no load and no branch is added in the interior; Dirichlet nodes are a select.
+template <typename T, int KIND, int OP, bool SAVE>
+__global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, T omega, const T *__restrict__ u,
+                                                        const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
+                                                        int nbx, int nby, int nbz, int zc)
+{
+    constexpr int V = Vec16<T>::n;
+    constexpr bool STORE = OP == FAS_JAC || SAVE;
+    typedef typename Vec16<T>::type vec;
+    __shared__ double sh[FBW];
+
+    const int nblocks = nbx * nby * nbz;
+    const int bid = xcd_block(blockIdx.x, (nblocks + 7) >> 3);
+    if (bid >= nblocks) {   // the whole workgroup
+        if (OP == FAS_RES && threadIdx.x == 0) partials[blockIdx.x] = 0.;
+        return;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int bx = bid % nbx, by = (bid / nbx) % nby, bz = bid / (nbx * nby);
+    const int x0 = V * (bx * 64 + lane);
+    const int x0c = min(x0, g.pitch - V);   // clamped for loads: every lane stays active
+    const bool xfull = x0 + V <= g.nx;      // the lane's vector lies inside the row
+    const int yb = (by * FBW + wv) * FRY;
+    const int z0 = bz * zc, zend = min(z0 + zc, g.nz);
+    // one column left over: the wave that holds the row's last full vector writes it as a full line
+    const bool tail1 = g.nx % V == 1 && g.nx > V;
+    const bool tailwave = tail1 && (bx * 64 * V <= g.nx - 1 - V) && (g.nx - 1 - V < (bx + 1) * 64 * V);
+    const int part = (!tail1 && !xfull && x0 < g.nx) ? g.nx - x0 : 0;   // elements of a partial last vector stored one by one
+    const int nown = xfull ? V : part;                                  // elements of the vector this lane stores and sums
+    const bool damped = OP == FAS_JAC && omega != (T)1;
+
+    long long rowoff[FRY];
+    bool yin[FRY], ybnd[FRY];
+#pragma unroll
+    for (int r = 0; r < FRY; r++) {
+        const int y = yb + r;
+        yin[r] = y < g.ny;
+        const int yc = min(y, g.ny - 1);
+        ybnd[r] = yc == 0 || yc == g.ny - 1;
+        rowoff[r] = (long long)yc * g.pitch + x0c;
+    }
+    const long long off_lo = (long long)min(max(yb - 1, 0), g.ny - 1) * g.pitch + x0c;
+    const long long off_hi = (long long)min(yb + FRY, g.ny - 1) * g.pitch + x0c;
+    const bool edge_l = lane == 0 && x0c > 0, edge_r = lane == 63 && x0c + V < g.pitch;
+
+    vec uzm[FRY], ucc[FRY], uzp[FRY];
+    const T *pu = u + (long long)z0 * g.plane;
+#pragma unroll
+    for (int r = 0; r < FRY; r++) {
+        uzm[r] = *(const vec *)(pu - g.plane + rowoff[r]);   // z0 == 0: the ghost plane, never used (plane 0 is Dirichlet)
+        ucc[r] = *(const vec *)(pu + rowoff[r]);
+    }
+    double acc = 0.;
+    for (int z = z0; z < zend; z++, pu += g.plane) {
+        const long long zo = (long long)z * g.plane;
+        vec bv[FRY];
+#pragma unroll
+        for (int r = 0; r < FRY; r++) {
+            uzp[r] = *(const vec *)(pu + g.plane + rowoff[r]);
+            bv[r] = __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r]));
+        }
+        const vec ulo = *(const vec *)(pu + off_lo), uhi = *(const vec *)(pu + off_hi);
+        const int gz = g.gz0 + z;
+        const bool zbnd = gz == 0 || gz == g.gnz - 1;
+#pragma unroll
+        for (int r = 0; r < FRY; r++) {
+            T uel = 0, uer = 0;
+            if (edge_l) uel = pu[rowoff[r] - 1];
+            if (edge_r) uer = pu[rowoff[r] + V];
+            const T uxm = lane_from_prev(ucc[r][V - 1], uel), uxp = lane_from_next(ucc[r][0], uer);
+            const vec uym = (r > 0) ? ucc[r > 0 ? r - 1 : 0] : ulo, uyp = (r < FRY - 1) ? ucc[r < FRY - 1 ? r + 1 : 0] : uhi;
+            const bool rbnd = zbnd || ybnd[r];
+            vec res;
+#pragma unroll
+            for (int e = 0; e < V; e++) {
+                const T ui = ucc[r][e], bi = bv[r][e];
+                const T ul = (e == 0) ? uxm : ucc[r][e > 0 ? e - 1 : 0];
+                const T ur = (e == V - 1) ? uxp : ucc[r][e < V - 1 ? e + 1 : 0];
+                const bool dn = rbnd || x0 + e == 0 || x0 + e == g.nx - 1;
+                T sum = 0;
+                sum += c.cz * uzm[r][e];
+                sum += c.cy * uym[e];
+                sum += c.cx * ul;
+                if (OP == FAS_RES) sum += c.cd * ui;
+                sum += c.cx * ur;
+                sum += c.cy * uyp[e];
+                sum += c.cz * uzp[r][e];
+                if (OP == FAS_RES) {
+                    T gv, gp;
+                    fas_react<T, KIND>(ui, gv, gp);
+                    res[e] = dn ? bi - ui : bi - (sum + G * gv);
+                } else {
+                    const T ps = fas_newton<T, KIND>(c, G, sum, ui, bi);
+                    res[e] = dn ? bi : (damped ? ui + omega * (ps - ui) : ps);
+                }
+            }
+            if (yin[r]) {
+                if (OP == FAS_RES) {
+#pragma unroll
+                    for (int e = 0; e < V; e++)
+                        if (e < nown) acc += (double)res[e] * (double)res[e];
+                }
+                T *const po = out + zo + rowoff[r];
+                if (xfull) {
+                    if (STORE) __builtin_nontemporal_store(res, (vec *)po);
+                } else if (part) {
+#pragma unroll
+                    for (int e = 0; e < V; e++)
+                        if (STORE && e < part) po[e] = res[e];
+                }
+                if (tailwave && lane >= 56) {
+                    // column nx-1 (a Dirichlet node) as one full 128-byte line: value + zero padding
+                    const int j = lane - 56;
+                    constexpr int LINE = 128 / (int)sizeof(T);
+                    const int xs = g.nx - 1 + V * j;
+                    const int line_end = ((g.nx - 1) / LINE + 1) * LINE;
+                    const long long ro = zo + (rowoff[r] - x0c);
+                    if (xs < line_end) {
+                        vec tv = (vec)(0);
+                        if (j == 0) {
+                            const T bt = b[ro + g.nx - 1];
+                            if (OP == FAS_RES) {
+                                const T rt = bt - (T)1 * u[ro + g.nx - 1];
+                                acc += (double)rt * (double)rt;
+                                tv[0] = rt;
+                            } else {
+                                tv[0] = bt;
+                            }
+                        }
+                        if (STORE) __builtin_nontemporal_store(tv, (vec *)(out + ro + xs));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < FRY; r++) { uzm[r] = ucc[r]; ucc[r] = uzp[r]; }
+    }
+    if (OP == FAS_RES) {
+        const double s = block_sum(acc, sh);
+        if (threadIdx.x == 0) partials[blockIdx.x] = s;
+    }
+}
+
+// ---------------------------------------------------------------- the FAS transition l -> l+1
+// uf = U(l), rf = TMP(l) (the residual of level l); per coarse node: uc = uf at the even fine node -> uco and eco;
+// rc = restrict_fw_point(rf) (inject: rf at the even fine node); rhsc = rc + (full_sum_c(uc) + G*g(uc)) with the coarse
+// neighbours read from uf at distance 2 (z: 1 on a semi transition); coarse Dirichlet nodes: rhsc = uc. cc: Coef of level l+1.
+template <typename T, int DIM, bool WZ, int KIND>
+__global__ __launch_bounds__(FAS_THREADS) void k_fas_coarse_rhs(Geom gf, Geom gc, Coef<T> cc, T G, int inject, const T *__restrict__ uf,
+                                                                const T *__restrict__ rf, T *__restrict__ uco, T *__restrict__ eco,
+                                                                T *__restrict__ rhsc)
+{
+    const long long nitems = (long long)gc.nx * gc.ny * gc.nz;
+    for (long long it = (long long)blockIdx.x * FAS_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * FAS_THREADS) {
+        const long long row = it / gc.nx;
+        const int x = (int)(it - row * gc.nx), y = (int)(row % gc.ny), z = (int)(row / gc.ny);
+        const int fz = (DIM == 3) ? (WZ ? 2 * (gc.gz0 + z) - gf.gz0 : z) : 0;
+        const long long fi = lidx(gf, fz, 2 * y, 2 * x), ci = lidx(gc, z, y, x);
+        const T uc = uf[fi];
+        T rhs;
+        if (on_boundary(gc, z, y, x)) {
+            rhs = uc;
+        } else {
+            const T rc = inject ? rf[fi] : restrict_fw_point<T, DIM, WZ>(gf, gc, rf, z, y, x);
+            const long long sy = 2 * (long long)gf.pitch, sz = WZ ? 2 * gf.plane : gf.plane;
+            T gv, gp;
+            fas_react<T, KIND>(uc, gv, gp);
+            T sum = 0;
+            if (DIM == 3) sum += cc.cz * uf[fi - sz];
+            sum += cc.cy * uf[fi - sy];
+            sum += cc.cx * uf[fi - 2];
+            sum += cc.cd * uc;
+            sum += cc.cx * uf[fi + 2];
+            sum += cc.cy * uf[fi + sy];
+            if (DIM == 3) sum += cc.cz * uf[fi + sz];
+            rhs = rc + (sum + G * gv);
+        }
+        uco[ci] = uc;
+        eco[ci] = uc;
+        rhsc[ci] = rhs;
+    }
+}
+
+// e = x - e on every node
+template <typename T>
+__global__ __launch_bounds__(FAS_THREADS) void k_fas_diff(Geom g, const T *__restrict__ x_, T *__restrict__ e)
+{
+    const long long nitems = (long long)g.nx * g.ny * g.nz;
+    for (long long it = (long long)blockIdx.x * FAS_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * FAS_THREADS) {
+        const long long row = it / g.nx;
+        const int x = (int)(it - row * g.nx), y = (int)(row % g.ny), z = (int)(row / g.ny);
+        const long long i = lidx(g, z, y, x);
+        e[i] = x_[i] - e[i];
+    }
+}
+
+// ---------------------------------------------------------------- the coarsest-grid solve: one workgroup
+template <typename T, int DIM, int KIND>
+__device__ void wg_fas_jacobi(const Geom &g, const Coef<T> &c, T G, T omega, bool damped, const T *u, const T *rhs, T *out)
+{
+    const int npl = g.nx * g.ny;
+    const long long total = (long long)npl * g.nz;
+    for (long long q = threadIdx.x; q < total; q += SWG) {
+        const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
+        const int y = rem / g.nx, x = rem - y * g.nx;
+        out[lidx(g, z, y, x)] = fas_point_solve<T, DIM, KIND>(g, c, G, omega, damped, u, rhs, z, y, x);
+    }
+    __syncthreads();
+}
+
+template <typename T, int DIM, int KIND>
+__device__ void wg_fas_rbgs(const Geom &g, const Coef<T> &c, T G, T *u, const T *rhs)
+{
+    const int npl = g.nx * g.ny;
+    const long long total = (long long)npl * g.nz;
+    for (int colour = 0; colour < 2; colour++) {
+        for (long long q = threadIdx.x; q < total; q += SWG) {
+            const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
+            const int y = rem / g.nx, x = rem - y * g.nx;
+            if (((x + y + g.gz0 + z) & 1) != colour) continue;
+            u[lidx(g, z, y, x)] = fas_point_solve<T, DIM, KIND>(g, c, G, (T)1, false, u, rhs, z, y, x);
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T, int DIM, int KIND>
+__device__ double wg_fas_residual_sumsq(const Geom &g, const Coef<T> &c, T G, const T *u, const T *rhs, double *sh)
+{
+    const int npl = g.nx * g.ny;
+    const long long total = (long long)npl * g.nz;
+    double sq = 0.;
+    for (long long q = threadIdx.x; q < total; q += SWG) {
+        const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
+        const int y = rem / g.nx, x = rem - y * g.nx;
+        const T res = fas_point_res<T, DIM, KIND>(g, c, G, u, rhs, z, y, x);
+        sq += (double)res * (double)res;
+    }
+    return block_sum_bcast(sq, sh);
+}
+
+// k_coarse_solve's loop (Solver::Solve with maxit, tol, fixed) with the nonlinear sweep and the nonlinear residual
+template <typename T, int DIM, int KIND>
+__global__ __launch_bounds__(SWG) void k_fas_coarse(Geom g, Coef<T> c, T G, T omega, int smoother, T *x, T *tmp, const T *rhs,
+                                                    int maxit, double tol, int fixed, CoarseOut *out)
+{
+    __shared__ double sh[18];
+    T *cur = x, *oth = tmp;
+    const bool damped = (omega != (T)1);
+    auto sweep = [&]() {
+        if (smoother == 1) {
+            wg_fas_jacobi<T, DIM, KIND>(g, c, G, omega, damped, cur, rhs, oth);
+            T *t = cur; cur = oth; oth = t;
+        } else {
+            wg_fas_rbgs<T, DIM, KIND>(g, c, G, cur, rhs);
+        }
+    };
+    const double nb = wg_sumsq<T>(g, rhs, sh);
+    int iters = 0, flag = 0;
+    double nr;
+    if (fixed) {
+        for (int s = 0; s < maxit; s++) sweep();
+        iters = maxit;
+        nr = wg_fas_residual_sumsq<T, DIM, KIND>(g, c, G, cur, rhs, sh);
+    } else {
+        int counter = maxit;
+        nr = wg_fas_residual_sumsq<T, DIM, KIND>(g, c, G, cur, rhs, sh);
+        while (sqrt(nr / nb) > tol) {   // NaN (zero rhs) compares false, as in k_coarse_solve
+            if (counter > 0) {
+                sweep();
+                counter -= 1;
+                iters++;
+                nr = wg_fas_residual_sumsq<T, DIM, KIND>(g, c, G, cur, rhs, sh);
+            } else {
+                flag = 1;
+                break;
+            }
+        }
+    }
+    if (cur != x) {   // odd number of Jacobi sweeps: move the result back into x
+        const int npl = g.nx * g.ny;
+        const long long total = (long long)npl * g.nz;
+        for (long long q = threadIdx.x; q < total; q += SWG) {
+            const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
+            const int y = rem / g.nx, xx = rem - y * g.nx;
+            const long long i = lidx(g, z, y, xx);
+            x[i] = cur[i];
+        }
+    }
+    if (threadIdx.x == 0) {
+        out->iters = iters;
+        out->flag = flag;
+        out->relres = sqrt(nr / nb);
+        out->sumsq_rhs = nb;
+        out->sumsq_r = nr;
+    }
+}
+
+// ---------------------------------------------------------------- launchers
+int fas_plain_grid(long long items, int cap)
+{
+    const long long nb = std::min<long long>(FAS_MAX_BLOCKS, (items + FAS_THREADS - 1) / FAS_THREADS);
+    return (int)std::max<long long>(1, std::min<long long>(nb, cap));
+}
+
+struct FasMarchGrid { int nbx, nby, nbz, zc, grid; };
+
+template <typename T>
+FasMarchGrid fas_march_grid(const Geom &g)
+{
+    constexpr int V = Vec16<T>::n;
+    // vectors a row needs lanes for: the full ones, and a partial last one unless it is the single tail column
+    const int nvec = std::max(1, g.nx / V + (g.nx % V > 1 ? 1 : 0));
+    FasMarchGrid m;
+    m.nbx = (nvec + 63) / 64;
+    m.nby = (g.ny + FRY * FBW - 1) / (FRY * FBW);
+    // a chunk of zc planes loads zc + 2: long chunks while they still fill the chip, never shorter than 4
+    m.zc = 16;
+    while (m.zc > 4 && (long long)m.nbx * m.nby * ((g.nz + m.zc - 1) / m.zc) < 2048) m.zc >>= 1;
+    m.nbz = (g.nz + m.zc - 1) / m.zc;
+    m.grid = ((m.nbx * m.nby * m.nbz + 7) / 8) * 8;
+    return m;
+}
+
+// whole levels only: mg_fas_* refuse distributed handles before they get here
+template <typename T>
+bool fas_march_takes(const Geom &g, bool plain)
+{
+    return !plain && fas_march_ok(g.dim, g.nx, g.ny, g.nz, (int)sizeof(T)) && g.gz0 == 0 && g.gnz == g.nz;
+}
+
+}  // namespace
+
+template <typename T>
+int launch_fas_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, const T *u, const T *b, T *r, double *partials,
+                        int cap, bool plain)
+{
+    if (fas_march_takes<T>(g, plain)) {
+        const FasMarchGrid m = fas_march_grid<T>(g);
+        if (m.grid <= cap) {
+            const dim3 gr(m.grid), bl(64 * FBW);
+#define MG_FAS(KIND, SAVE) hipLaunchKernelGGL((k_fas_march<T, KIND, FAS_RES, SAVE>), gr, bl, 0, s, g, c, G, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc)
+            if (kind == FAS_CUBIC) { if (r) MG_FAS(FAS_CUBIC, true); else MG_FAS(FAS_CUBIC, false); }
+            else { if (r) MG_FAS(FAS_EXP, true); else MG_FAS(FAS_EXP, false); }
+#undef MG_FAS
+            return m.grid;
+        }
+    }
+    const int nb = fas_plain_grid((long long)g.nx * g.ny * g.nz, cap);
+    const dim3 gr(nb), bl(FAS_THREADS);
+#define MG_FAS(DIM, KIND, SAVE) hipLaunchKernelGGL((k_fas_plain<T, DIM, KIND, FAS_RES, SAVE>), gr, bl, 0, s, g, c, G, (T)1, 0, u, b, r, partials)
+#define MG_FAS_K(DIM) \
+    if (kind == FAS_CUBIC) { if (r) MG_FAS(DIM, FAS_CUBIC, true); else MG_FAS(DIM, FAS_CUBIC, false); } \
+    else { if (r) MG_FAS(DIM, FAS_EXP, true); else MG_FAS(DIM, FAS_EXP, false); }
+    if (g.dim == 3) { MG_FAS_K(3) } else { MG_FAS_K(2) }
+#undef MG_FAS_K
+#undef MG_FAS
+    return nb;
+}
+
+template <typename T>
+void launch_fas_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, const T *u, const T *b, T *out, bool plain)
+{
+    if (fas_march_takes<T>(g, plain)) {
+        const FasMarchGrid m = fas_march_grid<T>(g);
+        const dim3 gr(m.grid), bl(64 * FBW);
+        if (kind == FAS_CUBIC)
+            hipLaunchKernelGGL((k_fas_march<T, FAS_CUBIC, FAS_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+        else
+            hipLaunchKernelGGL((k_fas_march<T, FAS_EXP, FAS_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+        return;
+    }
+    const dim3 gr(fas_plain_grid((long long)g.nx * g.ny * g.nz, FAS_MAX_BLOCKS)), bl(FAS_THREADS);
+#define MG_FAS(DIM, KIND) hipLaunchKernelGGL((k_fas_plain<T, DIM, KIND, FAS_JAC, false>), gr, bl, 0, s, g, c, G, omega, 0, u, b, out, (double *)nullptr)
+    if (g.dim == 3) { if (kind == FAS_CUBIC) MG_FAS(3, FAS_CUBIC); else MG_FAS(3, FAS_EXP); }
+    else { if (kind == FAS_CUBIC) MG_FAS(2, FAS_CUBIC); else MG_FAS(2, FAS_EXP); }
+#undef MG_FAS
+}
+
+template <typename T>
+void launch_fas_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int colour, T *u, const T *b)
+{
+    const dim3 gr(fas_plain_grid((long long)((g.nx + 1) / 2) * g.ny * g.nz, FAS_MAX_BLOCKS)), bl(FAS_THREADS);
+#define MG_FAS(DIM, KIND) hipLaunchKernelGGL((k_fas_plain<T, DIM, KIND, FAS_RB, false>), gr, bl, 0, s, g, c, G, (T)1, colour, u, b, u, (double *)nullptr)
+    if (g.dim == 3) { if (kind == FAS_CUBIC) MG_FAS(3, FAS_CUBIC); else MG_FAS(3, FAS_EXP); }
+    else { if (kind == FAS_CUBIC) MG_FAS(2, FAS_CUBIC); else MG_FAS(2, FAS_EXP); }
+#undef MG_FAS
+}
+
+template <typename T>
+void launch_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const Coef<T> &cc, int kind, T G, bool inject, const T *uf,
+                           const T *rf, T *uc, T *ec, T *rhsc)
+{
+    const dim3 gr(fas_plain_grid((long long)gc.nx * gc.ny * gc.nz, FAS_MAX_BLOCKS)), bl(FAS_THREADS);
+    const int inj = inject ? 1 : 0;
+#define MG_FAS(DIM, WZ, KIND) hipLaunchKernelGGL((k_fas_coarse_rhs<T, DIM, WZ, KIND>), gr, bl, 0, s, gf, gc, cc, G, inj, uf, rf, uc, ec, rhsc)
+#define MG_FAS_K(DIM, WZ) if (kind == FAS_CUBIC) MG_FAS(DIM, WZ, FAS_CUBIC); else MG_FAS(DIM, WZ, FAS_EXP);
+    if (gc.dim == 3 && is_semi_transition(gf, gc)) { MG_FAS_K(3, false) }
+    else if (gc.dim == 3) { MG_FAS_K(3, true) }
+    else { MG_FAS_K(2, false) }
+#undef MG_FAS_K
+#undef MG_FAS
+}
+
+template <typename T>
+void launch_fas_diff(hipStream_t s, const Geom &g, const T *x, T *e)
+{
+    const int nb = fas_plain_grid((long long)g.nx * g.ny * g.nz, FAS_MAX_BLOCKS);
+    hipLaunchKernelGGL((k_fas_diff<T>), dim3(nb), dim3(FAS_THREADS), 0, s, g, x, e);
+}
+
+template <typename T>
+void launch_fas_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, int smoother, T *x, T *tmp, const T *rhs,
+                       int maxit, double tol, int fixed, CoarseOut *d_out)
+{
+#define MG_FAS(DIM, KIND) hipLaunchKernelGGL((k_fas_coarse<T, DIM, KIND>), dim3(1), dim3(SWG), 0, s, g, c, G, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out)
+    if (g.dim == 3) { if (kind == FAS_CUBIC) MG_FAS(3, FAS_CUBIC); else MG_FAS(3, FAS_EXP); }
+    else { if (kind == FAS_CUBIC) MG_FAS(2, FAS_CUBIC); else MG_FAS(2, FAS_EXP); }
+#undef MG_FAS
+}
+
+#define MG_FAS_INST(T)                                                                                                                    \
+    template int launch_fas_residual<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, const T *, const T *, T *, double *, int, bool); \
+    template void launch_fas_jacobi<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, T, const T *, const T *, T *, bool);           \
+    template void launch_fas_rb_colour<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, int, T *, const T *);                       \
+    template void launch_fas_coarse_rhs<T>(hipStream_t, const Geom &, const Geom &, const Coef<T> &, int, T, bool, const T *, const T *,  \
+                                           T *, T *, T *);                                                                                \
+    template void launch_fas_diff<T>(hipStream_t, const Geom &, const T *, T *);                                                          \
+    template void launch_fas_coarse<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, T, int, T *, T *, const T *, int, double, int, \
+                                       CoarseOut *);
+MG_FAS_INST(double)
+MG_FAS_INST(float)
+#undef MG_FAS_INST
+
+}  // namespace mg

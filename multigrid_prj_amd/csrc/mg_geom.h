@@ -319,6 +319,15 @@ inline bool bc_march_ok(int dim, int nx, int ny, int nz, int elem_size)
     return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
 }
 
+// ---- which levels the marching tile of mg_fas.hip takes (residual and Jacobi sweep of mg_fas_*); the plain form takes every
+// other one, every red-black colour pass and the FAS transition. bc_march_ok's shape rule: the same tile, the reaction term
+// on the centre value. Pure; tests/test_fas_cpu.py pins it.
+inline bool fas_march_ok(int dim, int nx, int ny, int nz, int elem_size)
+{
+    const int v = 16 / elem_size;
+    return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
+}
+
 struct CoarseOut {
     int iters;
     int flag;

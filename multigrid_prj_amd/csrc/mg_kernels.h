@@ -356,6 +356,31 @@ void launch_bc_shift(hipStream_t s, const Geom &g, T cval, T *v);
 template <typename T>
 void launch_bc_dirichlet_copy(hipStream_t s, const Geom &g, int mask, T *x, const T *rhs);
 
+// ---- the semilinear operator (sigma I + A) u + gamma g(u) of the full approximation scheme (mg_fas.hip, Solver::fas_*) ----
+// c: the level's Coef (shift included); kind: enum mg_fas_kind; G = (T)gamma, 0 = the constant kernels' results bit for bit.
+// plain: never the marching tile.
+// r = b - N(u) (r == nullptr: norm only); one partial sum of r^2 per workgroup in `partials` (room for `cap`), returns how many
+template <typename T>
+int launch_fas_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, const T *u, const T *b, T *r, double *partials,
+                        int cap, bool plain);
+// one Jacobi sweep of linearised point solves, out of place (out must not alias u)
+template <typename T>
+void launch_fas_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, const T *u, const T *b, T *out, bool plain);
+// one colour pass of red-black Gauss-Seidel with the linearised point solve, in place
+template <typename T>
+void launch_fas_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int colour, T *u, const T *b);
+// the FAS transition: uc = ec = uf injected, rhsc = R rf + N_c(uf injected) (cc: Coef of the coarse level; inject: R is the injection)
+template <typename T>
+void launch_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const Coef<T> &cc, int kind, T G, bool inject, const T *uf,
+                           const T *rf, T *uc, T *ec, T *rhsc);
+// e = x - e on every node
+template <typename T>
+void launch_fas_diff(hipStream_t s, const Geom &g, const T *x, T *e);
+// launch_coarse_solve's loop with the nonlinear sweep (smoother 1: Jacobi, 2: red-black) and the nonlinear residual, one workgroup
+template <typename T>
+void launch_fas_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, int smoother, T *x, T *tmp, const T *rhs,
+                       int maxit, double tol, int fixed, CoarseOut *d_out);
+
 // ---- device-resident array I/O (mg_io.hip, driven by Solver::device_copy) ----
 // padded: local plane 0 of a level-shaped array of geometry g with elements P; dense: the caller's dense device array of
 // g.nx * g.ny * g.nz elements D at any element-aligned address. to_padded: padded = (P)dense, padding columns written as

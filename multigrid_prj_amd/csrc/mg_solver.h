@@ -170,6 +170,17 @@ public:
     int bc_project(int level, int arr, double *mean);
     int bc_cycle(mg_cycle_stats *st);
     int bc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
+    // the semilinear operator (sigma I + A) u + gamma g(u) by the full approximation scheme (mg_fas_*): a kind and gamma, nothing allocated
+    int fas_set_reaction(int kind, double gamma);
+    int fas_get_reaction(int *kind, double *gamma) const;
+    int fas_set_form(int form);   // tests and measurement tools: 1 = the plain kernels on every level, 0 = the default
+    int fas_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
+    int fas_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs);
+    int fas_coarse_rhs(int fine_level);
+    int fas_correct(int fine_level);
+    int fas_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st);
+    int fas_cycle(mg_cycle_stats *st);
+    int fas_solve(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st);
     int set_stage_callback(mg_stage_fn fn, void *user);
     int sync();
     int timer_start();
@@ -321,6 +332,7 @@ private:
         SC_O4_SUM = 6,    // sum r^2 of the fourth-order residual: o4_solve, o4_residual, o4_correct_residual (written on the device)
         SC_VC_SUM = 7,    // sum r^2 of the variable-coefficient residual: vc_residual, vc_solve, vc_pcg_solve (written on the device)
         SC_BC_SUM = SC_VC_SUM,   // mg_bc_*: sum r^2 or sum w v; shares the slot (every call fetches its sum before another family runs)
+        SC_FAS_SUM = SC_VC_SUM,  // mg_fas_*: sum r^2; shares the slot in the same way
         SC_COUNT = 8      // the eight slots: one 64-byte line
     };
     double *d_scal_ = nullptr;      // [SC_COUNT]
@@ -409,6 +421,21 @@ private:
     template <typename T> int bc_cycle_enqueue_t();
     int bc_cycle_enqueue();
     template <typename T> int bc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
+    // full-approximation-scheme drivers (mg_fas_*): the reaction gamma g(u), g of enum mg_fas_kind
+    int fas_kind_ = MG_FAS_CUBIC;
+    double fas_gamma_ = 0.0;
+    bool fas_plain_ = false;
+    enum : unsigned { FAS_NEED_CYCLE = 1u, FAS_NEED_SMOOTHER = 2u };   // what fas_check asks of the descriptor
+    int fas_check(const char *fn, unsigned need);   // driver_begin, the cycle / smoother the fas drivers run
+    template <typename T> int fas_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_FAS_SUM]
+    template <typename T> int fas_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
+    template <typename T> int fas_coarse_rhs_t(int fl);
+    template <typename T> int fas_correct_t(int fl);
+    template <typename T> int fas_coarse_t(int level, int ax, int ar);
+    template <typename T> int fas_cycle_rec_t(int l, int kind);
+    template <typename T> int fas_cycle_enqueue_t();
+    int fas_cycle_enqueue();
+    template <typename T> int fas_solve_t(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st);
     // block of eig_solve: eig_[family][column] (enum mg_eig_family), level-0-shaped; the per-workgroup partial sums of up to
     // EIG_MAX_LAUNCHES Gram tiles, their totals, the coefficients of the combine (device) and a pinned mirror of the last two
     enum { EIG_FAMILIES = 6, EIG_MAX_LAUNCHES = 9, EIG_HOST_DOUBLES = 2048 };
