@@ -5,17 +5,18 @@
 // axis; no ghost value is stored or read. The prolongation does not depend on the faces; the restriction does (injecting
 // at coarse nodes of a Neumann face makes the cycle diverge), so it lives here too.
 //
-//   k_bc_plain<T, DIM, OP, SAVE>   OP = residual (stored with SAVE, else norm only) / Jacobi sweep (out of place) / one
-//                                  red-black colour pass (in place): one thread per node, grid-stride, every shape
+//   BcOp<T>                        the point operator (Coef and the mask): res<DIM> and solve<DIM> of the contract below. The
+//                                  plain form (residual / Jacobi sweep / one red-black colour pass, every shape) and the
+//                                  coarsest-grid solve are mg_opfamily.h's k_op_plain<BcOp<T>, DIM, OP, SAVE> and
+//                                  k_op_coarse<BcOp<T>, DIM>
 //   k_bc_march<T, OP, SAVE>        the residual and the Jacobi sweep on 3-D levels with rows long enough to fill a wave
 //                                  (bc_march_ok, mg_geom.h)
 //   k_bc_restrict<T, DIM, WZ>      full weighting with mirrored fine neighbours, coarse Dirichlet nodes injected
-//   k_bc_coarse<T, DIM>            the Solver::Solve loop of k_coarse_solve (mg_kernels.hip) in one workgroup
 //   k_bc_wsum<T> / k_bc_shift<T>   sum of w v (w = 1/2 per Neumann face the node lies on) / v -= c on every node
 //   k_bc_dirichlet_copy<T>         x = rhs on the Dirichlet nodes
 //
 // The marching tile is k_vc_march's (mg_vc.hip) with ONE marched field: a lane owns one aligned 16-byte vector of x, a wave
-// covers 64 vectors of BRY = 2 rows, BBW = 4 waves are stacked in y and the workgroup marches zc planes with the planes
+// covers 64 vectors of MRY = 2 rows, MBW = 4 waves are stacked in y and the workgroup marches zc planes with the planes
 // z-1, z, z+1 of u in registers. x-neighbours are the neighbouring lanes' values (whole-wave DPP shifts; the two edge
 // lanes load theirs), y-neighbours the wave's other row or two halo rows that hit L1 / L2. The mirror is a select on values
 // the lane holds anyway: the element at x = 0 takes its right neighbour for the left one, row 0 takes row 1 for the halo
@@ -35,17 +36,11 @@
 //   restriction  restrict_fw_point's expression (x, then y inside the z planes, weights q, hlf, q) with fine indices outside
 //                the grid mirrored; coarse Dirichlet nodes injected
 // With mask 0 every one of these is the existing kernel's expression: the results are the same bits.
-#include "mg_kernels.h"
-#include "mg_device.h"
-
-#include <algorithm>
+#include "mg_opfamily.h"
 
 namespace mg {
 namespace {
 
-constexpr int BC_THREADS = 256, BC_MAX_BLOCKS = 2048;
-constexpr int BBW = 4, BRY = 2;   // waves per workgroup / rows per wave of the marching tile
-enum { BC_RES = 0, BC_JAC = 1, BC_RB = 2 };
 enum { FXLO = 1, FXHI = 2, FYLO = 4, FYHI = 8, FZLO = 16, FZHI = 32 };   // enum mg_face
 
 // the faces node (z, y, x) lies on, as mg_face bits
@@ -119,54 +114,42 @@ __device__ __forceinline__ T bc_point_solve(const Geom &g, const Coef<T> &c, int
     return ps;
 }
 
-// ---------------------------------------------------------------- the plain form
-// out: r (BC_RES with SAVE), u' (BC_JAC, must not alias u) or u itself (BC_RB: the other colour is only read)
-template <typename T, int DIM, int OP, bool SAVE>
-__global__ __launch_bounds__(BC_THREADS) void k_bc_plain(Geom g, Coef<T> c, int mask, T omega, int colour, const T *u,
-                                                         const T *__restrict__ b, T *out, double *__restrict__ partials)
-{
-    __shared__ double sh[BC_THREADS / 64];
-    const int hx = OP == BC_RB ? (g.nx + 1) / 2 : g.nx;   // nodes of a row this launch visits
-    const long long nitems = (long long)hx * g.ny * g.nz;
-    const bool damped = OP == BC_JAC && omega != (T)1;
-    double acc = 0.;
-    for (long long it = (long long)blockIdx.x * BC_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * BC_THREADS) {
-        const long long row = it / hx;
-        int x = (int)(it - row * hx);
-        const int y = (int)(row % g.ny), z = (int)(row / g.ny);
-        if (OP == BC_RB) {
-            x = 2 * x + ((y + g.gz0 + z + colour) & 1);   // the x parity that has (x + y + gz) & 1 == colour
-            if (x >= g.nx) continue;
-        }
-        if (OP == BC_RES) {
-            const T res = bc_point_res<T, DIM>(g, c, mask, u, b, z, y, x);
-            acc += (double)res * (double)res;
-            if (SAVE) out[lidx(g, z, y, x)] = res;
-        } else {
-            out[lidx(g, z, y, x)] = bc_point_solve<T, DIM>(g, c, mask, omega, damped, u, b, z, y, x);
-        }
+// the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h). The two point functions stay free
+// functions because the marching tile calls them too, for the odd last column.
+template <typename T>
+struct BcOp {
+    typedef T type;
+    Coef<T> c;
+    int mask;
+
+    template <int DIM>
+    __device__ __forceinline__ T res(const Geom &g, const T *u, const T *b, int z, int y, int x) const
+    {
+        return bc_point_res<T, DIM>(g, c, mask, u, b, z, y, x);
     }
-    if (OP == BC_RES) {
-        const double s = block_sum(acc, sh);
-        if (threadIdx.x == 0) partials[blockIdx.x] = s;
+
+    template <int DIM>
+    __device__ __forceinline__ T solve(const Geom &g, T omega, bool damped, const T *u, const T *b, int z, int y, int x) const
+    {
+        return bc_point_solve<T, DIM>(g, c, mask, omega, damped, u, b, z, y, x);
     }
-}
+};
 
 // ---------------------------------------------------------------- the marching tile (3-D)
 template <typename T, int OP, bool SAVE>
-__global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int mask, T omega, const T *__restrict__ u,
+__global__ __launch_bounds__(64 * MBW) void k_bc_march(Geom g, Coef<T> c, int mask, T omega, const T *__restrict__ u,
                                                        const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
                                                        int nbx, int nby, int nbz, int zc)
 {
     constexpr int V = Vec16<T>::n;
-    constexpr bool STORE = OP == BC_JAC || SAVE;
+    constexpr bool STORE = OP == OP_JAC || SAVE;
     typedef typename Vec16<T>::type vec;
-    __shared__ double sh[BBW];
+    __shared__ double sh[MBW];
 
     const int nblocks = nbx * nby * nbz;
     const int bid = xcd_block(blockIdx.x, (nblocks + 7) >> 3);
     if (bid >= nblocks) {   // the whole workgroup
-        if (OP == BC_RES && threadIdx.x == 0) partials[blockIdx.x] = 0.;
+        if (OP == OP_RES && threadIdx.x == 0) partials[blockIdx.x] = 0.;
         return;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -174,21 +157,21 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
     const int x0 = V * (bx * 64 + lane);
     const int x0c = min(x0, g.pitch - V);   // clamped for loads: every lane stays active
     const bool xfull = x0 + V <= g.nx;      // the lane's vector lies inside the row
-    const int yb = (by * BBW + wv) * BRY;
+    const int yb = (by * MBW + wv) * MRY;
     const int z0 = bz * zc, zend = min(z0 + zc, g.nz);
     // one column left over: the wave that holds the row's last full vector writes it as a full line
     const bool tail1 = g.nx % V == 1 && g.nx > V;
     const bool tailwave = tail1 && (bx * 64 * V <= g.nx - 1 - V) && (g.nx - 1 - V < (bx + 1) * 64 * V);
     const int part = (!tail1 && !xfull && x0 < g.nx) ? g.nx - x0 : 0;   // elements of a partial last vector stored one by one
     const int nown = xfull ? V : part;                                  // elements of the vector this lane stores and sums
-    const bool damped = OP == BC_JAC && omega != (T)1;
+    const bool damped = OP == OP_JAC && omega != (T)1;
     const int dir = ~mask;   // the Dirichlet faces
 
-    long long rowoff[BRY];
-    bool yin[BRY];
-    int yface[BRY];
+    long long rowoff[MRY];
+    bool yin[MRY];
+    int yface[MRY];
 #pragma unroll
-    for (int r = 0; r < BRY; r++) {
+    for (int r = 0; r < MRY; r++) {
         const int y = yb + r;
         yin[r] = y < g.ny;
         const int yc = min(y, g.ny - 1);
@@ -196,22 +179,22 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
         rowoff[r] = (long long)yc * g.pitch + x0c;
     }
     const long long off_lo = (long long)min(max(yb - 1, 0), g.ny - 1) * g.pitch + x0c;
-    const long long off_hi = (long long)min(yb + BRY, g.ny - 1) * g.pitch + x0c;
+    const long long off_hi = (long long)min(yb + MRY, g.ny - 1) * g.pitch + x0c;
     const bool edge_l = lane == 0 && x0c > 0, edge_r = lane == 63 && x0c + V < g.pitch;
 
-    vec uzm[BRY], ucc[BRY], uzp[BRY];
+    vec uzm[MRY], ucc[MRY], uzp[MRY];
     const T *pu = u + (long long)z0 * g.plane;
 #pragma unroll
-    for (int r = 0; r < BRY; r++) {
+    for (int r = 0; r < MRY; r++) {
         uzm[r] = *(const vec *)(pu - g.plane + rowoff[r]);
         ucc[r] = *(const vec *)(pu + rowoff[r]);
     }
     double acc = 0.;
     for (int z = z0; z < zend; z++, pu += g.plane) {
         const long long zo = (long long)z * g.plane;
-        vec bv[BRY];
+        vec bv[MRY];
 #pragma unroll
-        for (int r = 0; r < BRY; r++) {
+        for (int r = 0; r < MRY; r++) {
             uzp[r] = *(const vec *)(pu + g.plane + rowoff[r]);
             bv[r] = __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r]));
         }
@@ -219,12 +202,12 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
         const int gz = g.gz0 + z;
         const int zface = (gz == 0 ? FZLO : 0) | (gz == g.gnz - 1 ? FZHI : 0);
 #pragma unroll
-        for (int r = 0; r < BRY; r++) {
+        for (int r = 0; r < MRY; r++) {
             T uel = 0, uer = 0;
             if (edge_l) uel = pu[rowoff[r] - 1];
             if (edge_r) uer = pu[rowoff[r] + V];
             const T uxm = lane_from_prev(ucc[r][V - 1], uel), uxp = lane_from_next(ucc[r][0], uer);
-            const vec uym0 = (r > 0) ? ucc[r > 0 ? r - 1 : 0] : ulo, uyp0 = (r < BRY - 1) ? ucc[r < BRY - 1 ? r + 1 : 0] : uhi;
+            const vec uym0 = (r > 0) ? ucc[r > 0 ? r - 1 : 0] : ulo, uyp0 = (r < MRY - 1) ? ucc[r < MRY - 1 ? r + 1 : 0] : uhi;
             // the mirror in y and z: values the lane holds anyway
             const vec uym = (yface[r] & FYLO) ? uyp0 : uym0, uyp = (yface[r] & FYHI) ? uym0 : uyp0;
             const vec uzl = (zface & FZLO) ? uzp[r] : uzm[r], uzh = (zface & FZHI) ? uzm[r] : uzp[r];
@@ -244,14 +227,14 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
                 sum += c.cz * uzl[e];
                 sum += c.cy * uym[e];
                 sum += c.cx * ul;
-                if (OP == BC_RES) sum += c.cd * ui;
+                if (OP == OP_RES) sum += c.cd * ui;
                 sum += c.cx * ur;
                 sum += c.cy * uyp[e];
                 sum += c.cz * uzh[e];
-                if (OP == BC_RES) res[e] = dn[e] ? bi - ui : bi - sum;
+                if (OP == OP_RES) res[e] = dn[e] ? bi - ui : bi - sum;
                 else num[e] = bi - sum;
             }
-            if (OP == BC_JAC) {
+            if (OP == OP_JAC) {
                 div_cd_n_wave<T, V>(num, ps, c);
 #pragma unroll
                 for (int e = 0; e < V; e++) {
@@ -260,7 +243,7 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
                 }
             }
             if (yin[r]) {
-                if (OP == BC_RES) {
+                if (OP == OP_RES) {
 #pragma unroll
                     for (int e = 0; e < V; e++)
                         if (e < nown) acc += (double)res[e] * (double)res[e];
@@ -284,7 +267,7 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
                     if (xs < line_end) {
                         vec tv = (vec)(0);
                         if (j == 0) {
-                            if (OP == BC_RES) {
+                            if (OP == OP_RES) {
                                 const T rt = bc_point_res<T, 3>(g, c, mask, u, b, z, yb + r, g.nx - 1);
                                 acc += (double)rt * (double)rt;
                                 tv[0] = rt;
@@ -298,9 +281,9 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
             }
         }
 #pragma unroll
-        for (int r = 0; r < BRY; r++) { uzm[r] = ucc[r]; ucc[r] = uzp[r]; }
+        for (int r = 0; r < MRY; r++) { uzm[r] = ucc[r]; ucc[r] = uzp[r]; }
     }
-    if (OP == BC_RES) {
+    if (OP == OP_RES) {
         const double s = block_sum(acc, sh);
         if (threadIdx.x == 0) partials[blockIdx.x] = s;
     }
@@ -309,10 +292,10 @@ __global__ __launch_bounds__(64 * BBW) void k_bc_march(Geom g, Coef<T> c, int ma
 // ---------------------------------------------------------------- restriction with mirrored fine neighbours
 // WZ: weights along z too (3-D standard coarsening); otherwise 9-point weights per plane (2-D, semi transitions)
 template <typename T, int DIM, bool WZ>
-__global__ __launch_bounds__(BC_THREADS) void k_bc_restrict(Geom gf, Geom gc, int mask, const T *__restrict__ fine, T *__restrict__ coarse)
+__global__ __launch_bounds__(OP_THREADS) void k_bc_restrict(Geom gf, Geom gc, int mask, const T *__restrict__ fine, T *__restrict__ coarse)
 {
     const long long nitems = (long long)gc.nx * gc.ny * gc.nz;
-    for (long long it = (long long)blockIdx.x * BC_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * BC_THREADS) {
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
         const long long row = it / gc.nx;
         const int x = (int)(it - row * gc.nx), y = (int)(row % gc.ny), z = (int)(row / gc.ny);
         const int gzf = (DIM == 3 && WZ) ? 2 * (gc.gz0 + z) : 0;   // global fine plane
@@ -347,12 +330,12 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_restrict(Geom gf, Geom gc, in
 
 // ---------------------------------------------------------------- the weighted sum, the shift, the Dirichlet copy
 template <typename T>
-__global__ __launch_bounds__(BC_THREADS) void k_bc_wsum(Geom g, int mask, const T *__restrict__ v, double *__restrict__ partials)
+__global__ __launch_bounds__(OP_THREADS) void k_bc_wsum(Geom g, int mask, const T *__restrict__ v, double *__restrict__ partials)
 {
-    __shared__ double sh[BC_THREADS / 64];
+    __shared__ double sh[OP_THREADS / 64];
     const long long nitems = (long long)g.nx * g.ny * g.nz;
     double acc = 0.;
-    for (long long it = (long long)blockIdx.x * BC_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * BC_THREADS) {
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
         const long long row = it / g.nx;
         const int x = (int)(it - row * g.nx), y = (int)(row % g.ny), z = (int)(row / g.ny);
         const int nf = __popc((unsigned)(bc_faces(g, z, y, x) & mask));   // 0 .. 3: at most one face per axis
@@ -364,10 +347,10 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_wsum(Geom g, int mask, const 
 }
 
 template <typename T>
-__global__ __launch_bounds__(BC_THREADS) void k_bc_shift(Geom g, T cval, T *__restrict__ v)
+__global__ __launch_bounds__(OP_THREADS) void k_bc_shift(Geom g, T cval, T *__restrict__ v)
 {
     const long long nitems = (long long)g.nx * g.ny * g.nz;
-    for (long long it = (long long)blockIdx.x * BC_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * BC_THREADS) {
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
         const long long row = it / g.nx;
         const int x = (int)(it - row * g.nx), y = (int)(row % g.ny), z = (int)(row / g.ny);
         const long long i = lidx(g, z, y, x);
@@ -376,10 +359,10 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_shift(Geom g, T cval, T *__re
 }
 
 template <typename T>
-__global__ __launch_bounds__(BC_THREADS) void k_bc_dirichlet_copy(Geom g, int mask, T *__restrict__ x_, const T *__restrict__ rhs)
+__global__ __launch_bounds__(OP_THREADS) void k_bc_dirichlet_copy(Geom g, int mask, T *__restrict__ x_, const T *__restrict__ rhs)
 {
     const long long nitems = (long long)g.nx * g.ny * g.nz;
-    for (long long it = (long long)blockIdx.x * BC_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * BC_THREADS) {
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
         const long long row = it / g.nx;
         const int x = (int)(it - row * g.nx), y = (int)(row % g.ny), z = (int)(row / g.ny);
         if (bc_faces(g, z, y, x) & ~mask) {
@@ -389,191 +372,47 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_dirichlet_copy(Geom g, int ma
     }
 }
 
-// ---------------------------------------------------------------- the coarsest-grid solve: one workgroup
-template <typename T, int DIM>
-__device__ void wg_bc_jacobi(const Geom &g, const Coef<T> &c, int mask, T omega, bool damped, const T *u, const T *rhs, T *out)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    for (long long q = threadIdx.x; q < total; q += SWG) {
-        const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-        const int y = rem / g.nx, x = rem - y * g.nx;
-        out[lidx(g, z, y, x)] = bc_point_solve<T, DIM>(g, c, mask, omega, damped, u, rhs, z, y, x);
-    }
-    __syncthreads();
-}
-
-template <typename T, int DIM>
-__device__ void wg_bc_rbgs(const Geom &g, const Coef<T> &c, int mask, T *u, const T *rhs)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    for (int colour = 0; colour < 2; colour++) {
-        for (long long q = threadIdx.x; q < total; q += SWG) {
-            const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-            const int y = rem / g.nx, x = rem - y * g.nx;
-            if (((x + y + g.gz0 + z) & 1) != colour) continue;
-            u[lidx(g, z, y, x)] = bc_point_solve<T, DIM>(g, c, mask, (T)1, false, u, rhs, z, y, x);
-        }
-        __syncthreads();
-    }
-}
-
-template <typename T, int DIM>
-__device__ double wg_bc_residual_sumsq(const Geom &g, const Coef<T> &c, int mask, const T *u, const T *rhs, double *sh)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    double sq = 0.;
-    for (long long q = threadIdx.x; q < total; q += SWG) {
-        const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-        const int y = rem / g.nx, x = rem - y * g.nx;
-        const T res = bc_point_res<T, DIM>(g, c, mask, u, rhs, z, y, x);
-        sq += (double)res * (double)res;
-    }
-    return block_sum_bcast(sq, sh);
-}
-
-// k_coarse_solve's loop (Solver::Solve with maxit, tol, fixed) with the bc sweep and the bc residual
-template <typename T, int DIM>
-__global__ __launch_bounds__(SWG) void k_bc_coarse(Geom g, Coef<T> c, int mask, T omega, int smoother, T *x, T *tmp, const T *rhs,
-                                                   int maxit, double tol, int fixed, CoarseOut *out)
-{
-    __shared__ double sh[18];
-    T *cur = x, *oth = tmp;
-    const bool damped = (omega != (T)1);
-    auto sweep = [&]() {
-        if (smoother == 1) {
-            wg_bc_jacobi<T, DIM>(g, c, mask, omega, damped, cur, rhs, oth);
-            T *t = cur; cur = oth; oth = t;
-        } else {
-            wg_bc_rbgs<T, DIM>(g, c, mask, cur, rhs);
-        }
-    };
-    const double nb = wg_sumsq<T>(g, rhs, sh);
-    int iters = 0, flag = 0;
-    double nr;
-    if (fixed) {
-        for (int s = 0; s < maxit; s++) sweep();
-        iters = maxit;
-        nr = wg_bc_residual_sumsq<T, DIM>(g, c, mask, cur, rhs, sh);
-    } else {
-        int counter = maxit;
-        nr = wg_bc_residual_sumsq<T, DIM>(g, c, mask, cur, rhs, sh);
-        while (sqrt(nr / nb) > tol) {   // NaN (zero rhs) compares false, as in k_coarse_solve
-            if (counter > 0) {
-                sweep();
-                counter -= 1;
-                iters++;
-                nr = wg_bc_residual_sumsq<T, DIM>(g, c, mask, cur, rhs, sh);
-            } else {
-                flag = 1;
-                break;
-            }
-        }
-    }
-    if (cur != x) {   // odd number of Jacobi sweeps: move the result back into x
-        const int npl = g.nx * g.ny;
-        const long long total = (long long)npl * g.nz;
-        for (long long q = threadIdx.x; q < total; q += SWG) {
-            const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-            const int y = rem / g.nx, xx = rem - y * g.nx;
-            const long long i = lidx(g, z, y, xx);
-            x[i] = cur[i];
-        }
-    }
-    if (threadIdx.x == 0) {
-        out->iters = iters;
-        out->flag = flag;
-        out->relres = sqrt(nr / nb);
-        out->sumsq_rhs = nb;
-        out->sumsq_r = nr;
-    }
-}
-
 // ---------------------------------------------------------------- launchers
-int bc_plain_grid(long long items, int cap)
-{
-    const long long nb = std::min<long long>(BC_MAX_BLOCKS, (items + BC_THREADS - 1) / BC_THREADS);
-    return (int)std::max<long long>(1, std::min<long long>(nb, cap));
-}
-
-struct BcMarchGrid { int nbx, nby, nbz, zc, grid; };
-
-template <typename T>
-BcMarchGrid bc_march_grid(const Geom &g)
-{
-    constexpr int V = Vec16<T>::n;
-    // vectors a row needs lanes for: the full ones, and a partial last one unless it is the single tail column
-    const int nvec = std::max(1, g.nx / V + (g.nx % V > 1 ? 1 : 0));
-    BcMarchGrid m;
-    m.nbx = (nvec + 63) / 64;
-    m.nby = (g.ny + BRY * BBW - 1) / (BRY * BBW);
-    // a chunk of zc planes loads zc + 2: long chunks while they still fill the chip, never shorter than 4
-    m.zc = 16;
-    while (m.zc > 4 && (long long)m.nbx * m.nby * ((g.nz + m.zc - 1) / m.zc) < 2048) m.zc >>= 1;
-    m.nbz = (g.nz + m.zc - 1) / m.zc;
-    m.grid = ((m.nbx * m.nby * m.nbz + 7) / 8) * 8;
-    return m;
-}
-
-// whole levels only: mg_bc_* refuse distributed handles before they get here
-template <typename T>
-bool bc_march_takes(const Geom &g, bool plain)
-{
-    return !plain && bc_march_ok(g.dim, g.nx, g.ny, g.nz, (int)sizeof(T)) && g.gz0 == 0 && g.gnz == g.nz;
-}
-
 }  // namespace
 
 template <typename T>
 int launch_bc_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, const T *u, const T *b, T *r, double *partials, int cap,
                        bool plain)
 {
-    if (bc_march_takes<T>(g, plain)) {
-        const BcMarchGrid m = bc_march_grid<T>(g);
+    if (march_takes<T>(g, plain)) {
+        const MarchGrid m = march_grid<T>(g);
         if (m.grid <= cap) {
-            const dim3 gr(m.grid), bl(64 * BBW);
-            if (r) hipLaunchKernelGGL((k_bc_march<T, BC_RES, true>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
-            else hipLaunchKernelGGL((k_bc_march<T, BC_RES, false>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
+            const dim3 gr(m.grid), bl(64 * MBW);
+            if (r) hipLaunchKernelGGL((k_bc_march<T, OP_RES, true>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
+            else hipLaunchKernelGGL((k_bc_march<T, OP_RES, false>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
             return m.grid;
         }
     }
-    const int nb = bc_plain_grid((long long)g.nx * g.ny * g.nz, cap);
-    const dim3 gr(nb), bl(BC_THREADS);
-#define MG_BC(DIM, SAVE) hipLaunchKernelGGL((k_bc_plain<T, DIM, BC_RES, SAVE>), gr, bl, 0, s, g, c, mask, (T)1, 0, u, b, r, partials)
-    if (g.dim == 3) { if (r) MG_BC(3, true); else MG_BC(3, false); }
-    else { if (r) MG_BC(2, true); else MG_BC(2, false); }
-#undef MG_BC
-    return nb;
+    return plain_residual(s, g, BcOp<T>{c, mask}, u, b, r, partials, cap);
 }
 
 template <typename T>
 void launch_bc_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, T omega, const T *u, const T *b, T *out, bool plain)
 {
-    if (bc_march_takes<T>(g, plain)) {
-        const BcMarchGrid m = bc_march_grid<T>(g);
-        hipLaunchKernelGGL((k_bc_march<T, BC_JAC, false>), dim3(m.grid), dim3(64 * BBW), 0, s, g, c, mask, omega, u, b, out,
+    if (march_takes<T>(g, plain)) {
+        const MarchGrid m = march_grid<T>(g);
+        hipLaunchKernelGGL((k_bc_march<T, OP_JAC, false>), dim3(m.grid), dim3(64 * MBW), 0, s, g, c, mask, omega, u, b, out,
                            (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
         return;
     }
-    const dim3 gr(bc_plain_grid((long long)g.nx * g.ny * g.nz, BC_MAX_BLOCKS)), bl(BC_THREADS);
-    if (g.dim == 3) hipLaunchKernelGGL((k_bc_plain<T, 3, BC_JAC, false>), gr, bl, 0, s, g, c, mask, omega, 0, u, b, out, (double *)nullptr);
-    else hipLaunchKernelGGL((k_bc_plain<T, 2, BC_JAC, false>), gr, bl, 0, s, g, c, mask, omega, 0, u, b, out, (double *)nullptr);
+    plain_jacobi(s, g, BcOp<T>{c, mask}, omega, u, b, out);
 }
 
 template <typename T>
 void launch_bc_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, int colour, T *u, const T *b)
 {
-    const dim3 gr(bc_plain_grid((long long)((g.nx + 1) / 2) * g.ny * g.nz, BC_MAX_BLOCKS)), bl(BC_THREADS);
-    if (g.dim == 3) hipLaunchKernelGGL((k_bc_plain<T, 3, BC_RB, false>), gr, bl, 0, s, g, c, mask, (T)1, colour, u, b, u, (double *)nullptr);
-    else hipLaunchKernelGGL((k_bc_plain<T, 2, BC_RB, false>), gr, bl, 0, s, g, c, mask, (T)1, colour, u, b, u, (double *)nullptr);
+    plain_rb_colour(s, g, BcOp<T>{c, mask}, colour, u, b);
 }
 
 template <typename T>
 void launch_bc_restrict_fw(hipStream_t s, const Geom &gf, const Geom &gc, int mask, const T *fine, T *coarse)
 {
-    const dim3 gr(bc_plain_grid((long long)gc.nx * gc.ny * gc.nz, BC_MAX_BLOCKS)), bl(BC_THREADS);
+    const dim3 gr(plain_grid((long long)gc.nx * gc.ny * gc.nz, OP_MAX_BLOCKS)), bl(OP_THREADS);
     if (gc.dim == 3 && is_semi_transition(gf, gc)) hipLaunchKernelGGL((k_bc_restrict<T, 3, false>), gr, bl, 0, s, gf, gc, mask, fine, coarse);
     else if (gc.dim == 3) hipLaunchKernelGGL((k_bc_restrict<T, 3, true>), gr, bl, 0, s, gf, gc, mask, fine, coarse);
     else hipLaunchKernelGGL((k_bc_restrict<T, 2, false>), gr, bl, 0, s, gf, gc, mask, fine, coarse);
@@ -583,30 +422,29 @@ template <typename T>
 void launch_bc_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, T omega, int smoother, T *x, T *tmp, const T *rhs,
                       int maxit, double tol, int fixed, CoarseOut *d_out)
 {
-    if (g.dim == 3) hipLaunchKernelGGL((k_bc_coarse<T, 3>), dim3(1), dim3(SWG), 0, s, g, c, mask, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
-    else hipLaunchKernelGGL((k_bc_coarse<T, 2>), dim3(1), dim3(SWG), 0, s, g, c, mask, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
+    coarse_solve(s, g, BcOp<T>{c, mask}, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
 }
 
 template <typename T>
 int launch_bc_wsum(hipStream_t s, const Geom &g, int mask, const T *v, double *partials, int cap)
 {
-    const int nb = bc_plain_grid((long long)g.nx * g.ny * g.nz, cap);
-    hipLaunchKernelGGL((k_bc_wsum<T>), dim3(nb), dim3(BC_THREADS), 0, s, g, mask, v, partials);
+    const int nb = plain_grid((long long)g.nx * g.ny * g.nz, cap);
+    hipLaunchKernelGGL((k_bc_wsum<T>), dim3(nb), dim3(OP_THREADS), 0, s, g, mask, v, partials);
     return nb;
 }
 
 template <typename T>
 void launch_bc_shift(hipStream_t s, const Geom &g, T cval, T *v)
 {
-    const int nb = bc_plain_grid((long long)g.nx * g.ny * g.nz, BC_MAX_BLOCKS);
-    hipLaunchKernelGGL((k_bc_shift<T>), dim3(nb), dim3(BC_THREADS), 0, s, g, cval, v);
+    const int nb = plain_grid((long long)g.nx * g.ny * g.nz, OP_MAX_BLOCKS);
+    hipLaunchKernelGGL((k_bc_shift<T>), dim3(nb), dim3(OP_THREADS), 0, s, g, cval, v);
 }
 
 template <typename T>
 void launch_bc_dirichlet_copy(hipStream_t s, const Geom &g, int mask, T *x, const T *rhs)
 {
-    const int nb = bc_plain_grid((long long)g.nx * g.ny * g.nz, BC_MAX_BLOCKS);
-    hipLaunchKernelGGL((k_bc_dirichlet_copy<T>), dim3(nb), dim3(BC_THREADS), 0, s, g, mask, x, rhs);
+    const int nb = plain_grid((long long)g.nx * g.ny * g.nz, OP_MAX_BLOCKS);
+    hipLaunchKernelGGL((k_bc_dirichlet_copy<T>), dim3(nb), dim3(OP_THREADS), 0, s, g, mask, x, rhs);
 }
 
 #define MG_BC_INST(T)                                                                                                                   \

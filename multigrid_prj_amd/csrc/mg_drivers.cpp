@@ -133,19 +133,22 @@ int Solver::precondition(void **z, void *r, bool vc)
     MG_HIP(hipMemsetAsync(*z, 0, L0.alloc_elems * esize(), stream_));
     L0.base[MG_ARR_U] = *z;
     L0.base[MG_ARR_RHS] = r;
-    const int rc = vc ? vc_cycle_enqueue() : outer_iteration_enqueue();
+    const int rc = vc ? fam_cycle_enqueue<VcFam>() : outer_iteration_enqueue();
     *z = L0.base[MG_ARR_U];
     L0.base[MG_ARR_U] = x_base;
     L0.base[MG_ARR_RHS] = b_base;
     return rc;
 }
 
-template <typename T>
-int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+// The flexible CG iteration of mg_pcg_solve and mg_vc_pcg_solve on level 0. What the two operators do differently comes in:
+// residual_sum(r, v): r = b - A x (r may be null), *v = r.r, fetched (it synchronises); direction_apply(z, p, pn, q): pn = z +
+// beta p, q = A pn, returns the number of partial sums of pn.q; vc: precondition()'s flag.
+template <typename T, class ResidualSum, class DirectionApply>
+int Solver::pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply direction_apply, double tol, int maxit, double *hist,
+                       int hist_cap, int *n_hist, mg_krylov_stats *st)
 {
     Level &L0 = lv_[0];
     const Geom &g = L0.g;
-    const Coef<T> c = coef_of<T>(L0);
     auto kp = [&](int k) { return reinterpret_cast<T *>(kry_[k]) + L0.gh * g.plane; };
     T *const x = ptr<T>(MG_ARR_U, 0);
     const T *const b = ptr<T>(MG_ARR_RHS, 0);
@@ -159,10 +162,8 @@ int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist
     // vanish on the boundary and the iteration lives on the interior, where A is symmetric positive definite
     launch_cg_boundary_copy<T>(stream_, g, x, b);
     MG_HIP(hipGetLastError());
-    launch_residual<T>(stream_, g, c, x, b, kp(KR), d_partials_, d_scal_ + SC_RR);   // r0 = b - A x0, r0.r0
-    MG_HIP(hipGetLastError());
-    MG_TRY(fetch_scalars(SC_RR, d_scal_ + SC_RR));
-    const double rr0 = h_scal_[SC_RR];
+    double rr0 = 0;
+    MG_TRY(residual_sum(kp(KR), &rr0));   // r0 = b - A x0, r0.r0
     record(std::sqrt(rr0 / nb));
 
     if (nb == 0.0 || rr0 == 0.0) {
@@ -174,10 +175,10 @@ int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist
         int pc = KP0, pn = KP1;   // p ping-pongs: another workgroup may still read p_k at a neighbour while p_{k+1} is written
         MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));   // p_{-1} = 0: p_0 = z_0 + 0 p_{-1} = z_0
         auto direction = [&](int mode) -> int {   // z = M r, gamma, beta, p_{k+1} = z + beta p_k, q = A p_{k+1}, alpha
-            MG_TRY(precondition(&kry_[KZ], kry_[KR]));
+            MG_TRY(precondition(&kry_[KZ], kry_[KR], vc));
             int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
             launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
-            np = launch_cg_direction_apply<T>(stream_, g, c, kp(KZ), kp(pc), kp(pn), kp(KQ), d_cg_, d_cg_part_);
+            np = direction_apply(kp(KZ), kp(pc), kp(pn), kp(KQ));
             launch_cg_tail(stream_, CG_TAIL_ALPHA, d_cg_part_, np, d_cg_);
             MG_HIP(hipGetLastError());
             std::swap(pc, pn);
@@ -200,11 +201,31 @@ int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist
         }
     }
     double nr = 0;
-    MG_TRY(residual(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // the true residual of the returned x
+    MG_TRY(residual_sum((T *)nullptr, &nr));   // the true residual of the returned x
     out.relres_true = std::sqrt(nr / nb);
     if (n_hist) *n_hist = nh;
     if (st) *st = out;
     return MG_OK;
+}
+
+// A = the handle's constant operator, M r = one mg_solve outer iteration from zero; the sum of the residual comes out of
+// launch_residual in SC_RR
+template <typename T>
+int Solver::pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
+{
+    const Level &L0 = lv_[0];
+    const Coef<T> c = coef_of<T>(L0);
+    auto residual_sum = [&](T *r, double *v) -> int {
+        launch_residual<T>(stream_, L0.g, c, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0), r, d_partials_, d_scal_ + SC_RR);
+        MG_HIP(hipGetLastError());
+        MG_TRY(fetch_scalars(SC_RR, d_scal_ + SC_RR));
+        *v = h_scal_[SC_RR];
+        return MG_OK;
+    };
+    auto direction_apply = [&](const T *z, const T *p, T *pn, T *q) {
+        return launch_cg_direction_apply<T>(stream_, L0.g, c, z, p, pn, q, d_cg_, d_cg_part_);
+    };
+    return pcg_body_t<T>(false, residual_sum, direction_apply, tol, maxit, hist, hist_cap, n_hist, st);
 }
 
 int Solver::pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
@@ -1076,25 +1097,336 @@ int Solver::eig_kernel(int kernel, int nw, int np, const double *coef, const dou
     return d_.dtype == MG_F64 ? eig_combine_t<double>(nw, np, coef, theta, sums) : eig_combine_t<float>(nw, np, coef, theta, sums);
 }
 
-// ---------------------------------------------------------------- variable-coefficient diffusion (mg_vc_*), DESIGN.md section 18
-// L = sigma I - div(a grad .) with a nodal coefficient array per level (Level::vc_a; level l + 1 is the full-weighted level
-// l). The kernels are in mg_vc.hip; the transfers are the handle's own. Everything goes launch by launch: no fused pairs,
-// no LDS sub-cycle, no folded prolongation -- those kernels carry the constant stencil in registers.
-int Solver::vc_check(const char *fn, unsigned need)
+// ---------------------------------------------------------------- operator families (mg_vc_*, mg_bc_*, mg_fas_*), DESIGN.md sections 18 - 20
+// Three operators that take the place of the handle's constant stencil in the smoother, the residual and the coarsest-grid
+// solve. They share one driver skeleton, the fam_* templates below; a family is a policy F<T> that supplies exactly what
+// differs: the four launches (with the family's plain flag), the precondition of the check, and what the cycle does on the
+// way down to level l + 1 and back up. Everything goes launch by launch: no fused pairs, no LDS sub-cycle, no folded
+// prolongation -- those kernels carry the constant stencil in registers.
+//
+// vc (section 18): L = sigma I - div(a grad .) with a nodal coefficient array per level (Level::vc_a; level l + 1 is the
+// full-weighted level l). The kernels are in mg_vc.hip; the transfers are the handle's own.
+template <typename T>
+struct Solver::VcFam {
+    typedef T type;
+    static int ready(Solver &s, const char *fn)
+    {
+        if (!s.vc_set_) { set_last_error(std::string(fn) + ": no coefficient set (call mg_vc_set_coefficient first)"); return MG_ERR_BAD_ARG; }
+        return MG_OK;
+    }
+    static int residual(Solver &s, int l, const T *x, const T *b, T *r)
+    {
+        const Level &L = s.lv_[l];
+        return launch_vc_residual<T>(s.stream_, L.g, L.coef, s.shift_, x, s.vcptr<T>(l), b, r, s.d_partials_, s.o4_partials_cap_, s.vc_plain_);
+    }
+    static void jacobi(Solver &s, int l, const T *x, const T *b, T *out)
+    {
+        const Level &L = s.lv_[l];
+        launch_vc_jacobi<T>(s.stream_, L.g, L.coef, s.shift_, (T)s.d_.omega, x, s.vcptr<T>(l), b, out, s.vc_plain_);
+    }
+    static void rb_colour(Solver &s, int l, int colour, T *x, const T *b)
+    {
+        const Level &L = s.lv_[l];
+        launch_vc_rb_colour<T>(s.stream_, L.g, L.coef, s.shift_, colour, x, s.vcptr<T>(l), b);
+    }
+    static void coarse(Solver &s, int l, T *x, T *tmp, const T *b)
+    {
+        const Level &L = s.lv_[l];
+        launch_vc_coarse<T>(s.stream_, L.g, L.coef, s.shift_, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.vcptr<T>(l), s.d_.coarse_maxit,
+                            s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
+    }
+    static int down(Solver &s, int l)
+    {
+        MG_TRY(s.restrict_t<T>(l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
+        return s.zero_array(MG_ARR_U, l + 1);
+    }
+    static int up(Solver &s, int l) { return s.prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U); }
+    // mg_vc_solve: nothing to project; U = RHS on the Dirichlet nodes
+    static int solve_begin(Solver &) { return MG_OK; }
+    static int solve_end(Solver &) { return MG_OK; }
+    static void dirichlet_copy(Solver &s) { launch_cg_boundary_copy<T>(s.stream_, s.lv_[0].g, s.ptr<T>(MG_ARR_U, 0), s.ptr<T>(MG_ARR_RHS, 0)); }
+};
+
+// bc (section 19): the handle's constant operator with zero-flux walls on the faces of a mask (enum mg_face): nodes that lie
+// only on Neumann faces are unknowns whose missing neighbours are mirror images. The kernels are in mg_bc.hip -- the
+// restriction too, because injecting at coarse nodes of a Neumann face makes the cycle diverge; the prolongation is the
+// handle's own. Nothing is allocated: the state is the mask.
+template <typename T>
+struct Solver::BcFam {
+    typedef T type;
+    static int ready(Solver &, const char *) { return MG_OK; }
+    static int residual(Solver &s, int l, const T *x, const T *b, T *r)
+    {
+        const Level &L = s.lv_[l];
+        return launch_bc_residual<T>(s.stream_, L.g, coef_of<T>(L), s.bc_mask_, x, b, r, s.d_partials_, s.o4_partials_cap_, s.bc_plain_);
+    }
+    static void jacobi(Solver &s, int l, const T *x, const T *b, T *out)
+    {
+        const Level &L = s.lv_[l];
+        launch_bc_jacobi<T>(s.stream_, L.g, coef_of<T>(L), s.bc_mask_, (T)s.d_.omega, x, b, out, s.bc_plain_);
+    }
+    static void rb_colour(Solver &s, int l, int colour, T *x, const T *b)
+    {
+        const Level &L = s.lv_[l];
+        launch_bc_rb_colour<T>(s.stream_, L.g, coef_of<T>(L), s.bc_mask_, colour, x, b);
+    }
+    static void coarse(Solver &s, int l, T *x, T *tmp, const T *b)
+    {
+        const Level &L = s.lv_[l];
+        launch_bc_coarse<T>(s.stream_, L.g, coef_of<T>(L), s.bc_mask_, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.d_.coarse_maxit,
+                            s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
+    }
+    static int down(Solver &s, int l)
+    {
+        MG_TRY(s.bc_restrict_t<T>(l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
+        return s.zero_array(MG_ARR_U, l + 1);
+    }
+    static int up(Solver &s, int l) { return s.prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U); }
+    // mg_bc_solve with all faces Neumann and no shift: the constants are the null space, RHS(0) is projected onto the range
+    // first (it stays projected) and U(0) is projected at the end
+    static int solve_begin(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(0, MG_ARR_RHS, nullptr) : MG_OK; }
+    static int solve_end(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(0, MG_ARR_U, nullptr) : MG_OK; }
+    static void dirichlet_copy(Solver &s)
+    {
+        launch_bc_dirichlet_copy<T>(s.stream_, s.lv_[0].g, s.bc_mask_, s.ptr<T>(MG_ARR_U, 0), s.ptr<T>(MG_ARR_RHS, 0));
+    }
+};
+
+// fas (section 20): N(u) = (sigma I + A) u + gamma g(u) with the handle's constant operator, all faces Dirichlet, gamma the
+// same on every level. The cycle is the same recursion on the nonlinear problem itself: the coarse level starts from the
+// INJECTED iterate (kept in E), its right-hand side is R r + N_c(injected iterate), and the correction is the difference to
+// the kept copy. The kernels are in mg_fas.hip. Nothing is allocated: the state is the kind and gamma.
+template <typename T>
+struct Solver::FasFam {
+    typedef T type;
+    static int ready(Solver &, const char *) { return MG_OK; }
+    static int residual(Solver &s, int l, const T *x, const T *b, T *r)
+    {
+        const Level &L = s.lv_[l];
+        return launch_fas_residual<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, x, b, r, s.d_partials_, s.o4_partials_cap_,
+                                      s.fas_plain_);
+    }
+    static void jacobi(Solver &s, int l, const T *x, const T *b, T *out)
+    {
+        const Level &L = s.lv_[l];
+        launch_fas_jacobi<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, (T)s.d_.omega, x, b, out, s.fas_plain_);
+    }
+    static void rb_colour(Solver &s, int l, int colour, T *x, const T *b)
+    {
+        const Level &L = s.lv_[l];
+        launch_fas_rb_colour<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, colour, x, b);
+    }
+    static void coarse(Solver &s, int l, T *x, T *tmp, const T *b)
+    {
+        const Level &L = s.lv_[l];
+        launch_fas_coarse<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, (T)s.d_.omega, s.d_.smoother, x, tmp, b,
+                             s.d_.coarse_maxit, s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
+    }
+    static int down(Solver &s, int l) { return s.fas_coarse_rhs_t<T>(l); }   // U(l + 1) = E(l + 1) = the injected iterate, RHS(l + 1)
+    static int up(Solver &s, int l) { return s.fas_correct_t<T>(l); }
+};
+
+template <template <typename> class F>
+int Solver::fam_check(const char *fn, unsigned need)
 {
-    MG_TRY(driver_begin(fn, REFUSE_DIST | ((need & VC_NEED_CYCLE) ? REFUSE_STAGE_CB : 0u)));
-    if (!vc_set_) { set_last_error(std::string(fn) + ": no coefficient set (call mg_vc_set_coefficient first)"); return MG_ERR_BAD_ARG; }
-    if ((need & VC_NEED_CYCLE) && !is_vwf(d_.cycle)) {
+    MG_TRY(driver_begin(fn, REFUSE_DIST | ((need & FAM_NEED_CYCLE) ? REFUSE_STAGE_CB : 0u)));
+    MG_TRY(F<double>::ready(*this, fn));   // the precondition looks at handle state only: the same for either element type
+    if ((need & FAM_NEED_CYCLE) && !is_vwf(d_.cycle)) {
         set_last_error(std::string(fn) + ": not on a sawtooth handle (the cycle must be MG_CYCLE_V, MG_CYCLE_W or MG_CYCLE_F)");
         return MG_ERR_BAD_ARG;
     }
-    if ((need & (VC_NEED_CYCLE | VC_NEED_SMOOTHER)) && d_.smoother != MG_SMOOTH_JACOBI && d_.smoother != MG_SMOOTH_RBGS) {
+    if ((need & (FAM_NEED_CYCLE | FAM_NEED_SMOOTHER)) && d_.smoother != MG_SMOOTH_JACOBI && d_.smoother != MG_SMOOTH_RBGS) {
         set_last_error(std::string(fn) + ": the handle's smoother must be MG_SMOOTH_JACOBI or MG_SMOOTH_RBGS");
         return MG_ERR_BAD_ARG;
     }
     return MG_OK;
 }
 
+int Solver::set_form(const char *fn, int form, bool *plain)
+{
+    if (form != 0 && form != 1) { set_last_error(std::string(fn) + ": form must be 0 (default) or 1 (the plain kernels everywhere)"); return MG_ERR_BAD_ARG; }
+    *plain = form == 1;
+    return MG_OK;
+}
+
+template <class F>
+int Solver::fam_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
+{
+    typedef typename F::type T;
+    Level &L = lv_[level];
+    if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
+    const int np = F::residual(*this, level, ptr<T>(ax, level), ptr<T>(ar, level), arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr);
+    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_FAM_SUM);
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+// residual -> reduce -> fetch -> value; synchronises
+template <class F>
+int Solver::fam_residual_sum_t(int level, int ax, int ar, int arr_r, double *sumsq_r)
+{
+    MG_TRY(fam_residual_t<F>(level, ax, ar, arr_r, true));
+    MG_TRY(fetch_scalars(SC_FAM_SUM, d_scal_ + SC_FAM_SUM));
+    *sumsq_r = h_scal_[SC_FAM_SUM];
+    return MG_OK;
+}
+
+template <template <typename> class F>
+int Solver::fam_residual(const char *fn, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
+{
+    MG_TRY(fam_check<F>(fn, 0));
+    if (!check_arr(arr_x, level, fn) || !check_arr(arr_rhs, level, fn)) return MG_ERR_BAD_ARG;
+    if (arr_r >= 0 && (!check_arr(arr_r, level, fn) || arr_r == arr_x || arr_r == arr_rhs)) {
+        set_last_error(std::string(fn) + ": bad output array");
+        return MG_ERR_BAD_ARG;
+    }
+    if (!sumsq_r)   // the sum stays on the device: no synchronisation
+        return d_.dtype == MG_F64 ? fam_residual_t<F<double>>(level, arr_x, arr_rhs, arr_r, true) : fam_residual_t<F<float>>(level, arr_x, arr_rhs, arr_r, true);
+    return d_.dtype == MG_F64 ? fam_residual_sum_t<F<double>>(level, arr_x, arr_rhs, arr_r, sumsq_r)
+                              : fam_residual_sum_t<F<float>>(level, arr_x, arr_rhs, arr_r, sumsq_r);
+}
+
+template <class F>
+int Solver::fam_smooth_t(int level, int smoother, int sweeps, int ax, int ar)
+{
+    typedef typename F::type T;
+    Level &L = lv_[level];
+    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
+    for (int s = 0; s < sweeps; s++) {
+        if (smoother == MG_SMOOTH_JACOBI) {   // out of place into TMP, then the two pointers are swapped (as smooth_t)
+            F::jacobi(*this, level, ptr<T>(ax, level), ptr<T>(ar, level), ptr<T>(MG_ARR_TMP, level));
+            std::swap(L.base[ax], L.base[MG_ARR_TMP]);
+        } else {
+            for (int colour = 0; colour < 2; colour++) F::rb_colour(*this, level, colour, ptr<T>(ax, level), ptr<T>(ar, level));
+        }
+    }
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+template <template <typename> class F>
+int Solver::fam_smooth(const char *fn, int level, int smoother, int sweeps, int arr_x, int arr_rhs)
+{
+    MG_TRY(fam_check<F>(fn, 0));
+    if (!check_arr(arr_x, level, fn) || !check_arr(arr_rhs, level, fn)) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs || sweeps < 0 ||
+        (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS)) {
+        set_last_error(std::string(fn) + ": bad array / sweeps, or a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? fam_smooth_t<F<double>>(level, smoother, sweeps, arr_x, arr_rhs)
+                              : fam_smooth_t<F<float>>(level, smoother, sweeps, arr_x, arr_rhs);
+}
+
+template <class F>
+int Solver::fam_coarse_t(int level, int ax, int ar)
+{
+    typedef typename F::type T;
+    if (ax == MG_ARR_RHS) lv_[level].rhs_halo_ok = false;
+    F::coarse(*this, level, ptr<T>(ax, level), ptr<T>(MG_ARR_TMP, level), ptr<T>(ar, level));
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+template <template <typename> class F>
+int Solver::fam_coarse_solve(const char *fn, int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
+{
+    MG_TRY(fam_check<F>(fn, FAM_NEED_SMOOTHER));
+    if (!check_arr(arr_x, level, fn) || !check_arr(arr_rhs, level, fn)) return MG_ERR_BAD_ARG;
+    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs) { set_last_error(std::string(fn) + ": bad array"); return MG_ERR_BAD_ARG; }
+    MG_TRY(d_.dtype == MG_F64 ? fam_coarse_t<F<double>>(level, arr_x, arr_rhs) : fam_coarse_t<F<float>>(level, arr_x, arr_rhs));
+    return fetch_cycle_stats(st);
+}
+
+// cyc(l, kind) of mg_desc.h with the family's kernels, launch by launch
+template <class F>
+int Solver::fam_cycle_rec_t(int l, int kind)
+{
+    const int L = d_.levels;
+    if (l == L - 1) {
+        const long long pts = (long long)lv_[l].g.nx * lv_[l].g.ny * lv_[l].g.gnz;
+        if (pts > 32768 && d_.coarse_mode == MG_COARSE_FIXED) {   // too big for one workgroup: chip-wide sweeps, as coarse_level_t
+            MG_TRY(fam_smooth_t<F>(l, d_.smoother, d_.coarse_maxit, MG_ARR_U, MG_ARR_RHS));
+            h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
+            h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;   // not evaluated on this path
+            MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
+        } else {
+            MG_TRY(fam_coarse_t<F>(l, MG_ARR_U, MG_ARR_RHS));
+        }
+        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
+        return MG_OK;
+    }
+    MG_TRY(fam_smooth_t<F>(l, d_.smoother, d_.nu_pre, MG_ARR_U, MG_ARR_RHS));
+    MG_TRY(fam_residual_t<F>(l, MG_ARR_U, MG_ARR_RHS, MG_ARR_TMP, false));
+    MG_TRY(F::down(*this, l));   // TMP(l) -> RHS(l + 1) and the start U(l + 1)
+    MG_TRY(fam_cycle_rec_t<F>(l + 1, kind));
+    if (l + 1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(fam_cycle_rec_t<F>(l + 1, MG_CYCLE_W));   // continues from U(l + 1); RHS(l + 1) (fas: and E(l + 1)) unchanged
+    if (l + 1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(fam_cycle_rec_t<F>(l + 1, MG_CYCLE_V));
+    MG_TRY(F::up(*this, l));
+    return fam_smooth_t<F>(l, d_.smoother, d_.nu_post, MG_ARR_U, MG_ARR_RHS);
+}
+
+template <class F>
+int Solver::fam_cycle_enqueue_t()
+{
+    if (d_.cycle == MG_CYCLE_V) return fam_cycle_rec_t<F>(0, MG_CYCLE_V);
+    MG_TRY(stats_begin());   // W and F make several coarse solves: summed on the device, as cycle_from_t
+    const int rc = fam_cycle_rec_t<F>(0, d_.cycle);
+    acc_stats_ = false;
+    MG_TRY(rc);
+    return stats_end();
+}
+
+template <template <typename> class F>
+int Solver::fam_cycle_enqueue() { return d_.dtype == MG_F64 ? fam_cycle_enqueue_t<F<double>>() : fam_cycle_enqueue_t<F<float>>(); }
+
+template <template <typename> class F>
+int Solver::fam_cycle(const char *fn, mg_cycle_stats *st)
+{
+    MG_TRY(fam_check<F>(fn, FAM_NEED_CYCLE));
+    MG_TRY(fam_cycle_enqueue<F>());
+    return fetch_cycle_stats(st);
+}
+
+// mg_solve's loop and history on the family's operator (vc, bc); desc.outer_pre_gs is ignored (the lexicographic sweep has
+// no such form)
+template <class F>
+int Solver::fam_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    MG_TRY(F::solve_begin(*this));
+    double nb = 0, rr = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    F::dirichlet_copy(*this);   // U = RHS on the Dirichlet nodes
+    MG_HIP(hipGetLastError());
+    int nh = 0;
+    auto norm = [&]() -> int {
+        MG_TRY(fam_residual_sum_t<F>(0, MG_ARR_U, MG_ARR_RHS, -1, &rr));
+        if (hist && nh < hist_cap) hist[nh] = std::sqrt(rr / nb);
+        nh++;
+        return MG_OK;
+    };
+    MG_TRY(norm());
+    for (int it = 0; it < maxit; it++) {
+        MG_TRY(fam_cycle_enqueue_t<F>());
+        MG_TRY(fetch_cycle_stats(per_cycle ? &per_cycle[it] : nullptr));
+        MG_TRY(norm());
+        if (std::sqrt(rr / nb) <= tol) break;
+    }
+    MG_TRY(F::solve_end(*this));
+    if (n_hist) *n_hist = nh;
+    return MG_OK;
+}
+
+template <template <typename> class F>
+int Solver::fam_solve(const char *fn, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
+{
+    MG_TRY(fam_check<F>(fn, FAM_NEED_CYCLE));
+    if (maxit < 0) { set_last_error(std::string(fn) + ": negative maxit"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? fam_solve_t<F<double>>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
+                              : fam_solve_t<F<float>>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
+}
+
+// ---------------------------------------------------------------- what only mg_vc_* has
 int Solver::vc_alloc()
 {
     for (auto &L : lv_)   // slot by slot: a call that failed half way leaves the rest to the next one
@@ -1144,255 +1476,40 @@ int Solver::vc_set_coefficient_device(const void *dense, int dense_dtype, hipStr
 
 int Solver::vc_get_coefficient(int level, void *host)
 {
-    MG_TRY(vc_check("mg_vc_get_coefficient", 0));
+    MG_TRY(fam_check<VcFam>("mg_vc_get_coefficient", 0));
     if (!host || level < 0 || level >= d_.levels) { set_last_error("mg_vc_get_coefficient: bad level / null array"); return MG_ERR_BAD_ARG; }
     const Level &L = lv_[level];
     return stage_copy(reinterpret_cast<char *>(L.vc_a) + (size_t)L.gh * (size_t)L.g.plane * esize(), L.g, esize(), host, false);
 }
 
-int Solver::vc_set_form(int form)
-{
-    if (form != 0 && form != 1) { set_last_error("mg_vc_set_form: form must be 0 (default) or 1 (the plain kernels everywhere)"); return MG_ERR_BAD_ARG; }
-    vc_plain_ = form == 1;
-    return MG_OK;
-}
-
-template <typename T>
-int Solver::vc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
-{
-    Level &L = lv_[level];
-    if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
-    const int np = launch_vc_residual<T>(stream_, L.g, L.coef, shift_, ptr<T>(ax, level), vcptr<T>(level), ptr<T>(ar, level),
-                                         arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr, d_partials_, o4_partials_cap_, vc_plain_);
-    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_VC_SUM);
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::vc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
-{
-    MG_TRY(vc_check("mg_vc_residual", 0));
-    if (!check_arr(arr_x, level, "mg_vc_residual") || !check_arr(arr_rhs, level, "mg_vc_residual")) return MG_ERR_BAD_ARG;
-    if (arr_r >= 0 && (!check_arr(arr_r, level, "mg_vc_residual") || arr_r == arr_x || arr_r == arr_rhs)) {
-        set_last_error("mg_vc_residual: bad output array");
-        return MG_ERR_BAD_ARG;
-    }
-    MG_TRY(d_.dtype == MG_F64 ? vc_residual_t<double>(level, arr_x, arr_rhs, arr_r, true) : vc_residual_t<float>(level, arr_x, arr_rhs, arr_r, true));
-    if (sumsq_r) {
-        MG_TRY(fetch_scalars(SC_VC_SUM, d_scal_ + SC_VC_SUM));
-        *sumsq_r = h_scal_[SC_VC_SUM];
-    }
-    return MG_OK;
-}
-
-template <typename T>
-int Solver::vc_smooth_t(int level, int smoother, int sweeps, int ax, int ar)
-{
-    Level &L = lv_[level];
-    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
-    for (int s = 0; s < sweeps; s++) {
-        if (smoother == MG_SMOOTH_JACOBI) {   // out of place into TMP, then the two pointers are swapped (as smooth_t)
-            launch_vc_jacobi<T>(stream_, L.g, L.coef, shift_, (T)d_.omega, ptr<T>(ax, level), vcptr<T>(level), ptr<T>(ar, level),
-                                ptr<T>(MG_ARR_TMP, level), vc_plain_);
-            std::swap(L.base[ax], L.base[MG_ARR_TMP]);
-        } else {
-            for (int colour = 0; colour < 2; colour++)
-                launch_vc_rb_colour<T>(stream_, L.g, L.coef, shift_, colour, ptr<T>(ax, level), vcptr<T>(level), ptr<T>(ar, level));
-        }
-    }
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::vc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs)
-{
-    MG_TRY(vc_check("mg_vc_smooth", 0));
-    if (!check_arr(arr_x, level, "mg_vc_smooth") || !check_arr(arr_rhs, level, "mg_vc_smooth")) return MG_ERR_BAD_ARG;
-    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs || sweeps < 0 ||
-        (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS)) {
-        set_last_error("mg_vc_smooth: bad array / sweeps, or a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS");
-        return MG_ERR_BAD_ARG;
-    }
-    return d_.dtype == MG_F64 ? vc_smooth_t<double>(level, smoother, sweeps, arr_x, arr_rhs)
-                              : vc_smooth_t<float>(level, smoother, sweeps, arr_x, arr_rhs);
-}
-
-template <typename T>
-int Solver::vc_coarse_t(int level, int ax, int ar)
-{
-    Level &L = lv_[level];
-    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
-    launch_vc_coarse<T>(stream_, L.g, L.coef, shift_, (T)d_.omega, d_.smoother, ptr<T>(ax, level), ptr<T>(MG_ARR_TMP, level),
-                        ptr<T>(ar, level), vcptr<T>(level), d_.coarse_maxit, d_.coarse_tol, d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0,
-                        d_coarse_);
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::vc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
-{
-    MG_TRY(vc_check("mg_vc_coarse_solve", VC_NEED_SMOOTHER));
-    if (!check_arr(arr_x, level, "mg_vc_coarse_solve") || !check_arr(arr_rhs, level, "mg_vc_coarse_solve")) return MG_ERR_BAD_ARG;
-    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs) { set_last_error("mg_vc_coarse_solve: bad array"); return MG_ERR_BAD_ARG; }
-    MG_TRY(d_.dtype == MG_F64 ? vc_coarse_t<double>(level, arr_x, arr_rhs) : vc_coarse_t<float>(level, arr_x, arr_rhs));
-    return fetch_cycle_stats(st);
-}
-
-// cyc(l, kind) of mg_desc.h with the vc kernels, launch by launch
-template <typename T>
-int Solver::vc_cycle_rec_t(int l, int kind)
-{
-    const int L = d_.levels;
-    if (l == L - 1) {
-        const long long pts = (long long)lv_[l].g.nx * lv_[l].g.ny * lv_[l].g.gnz;
-        if (pts > 32768 && d_.coarse_mode == MG_COARSE_FIXED) {   // too big for one workgroup: chip-wide sweeps, as coarse_level_t
-            MG_TRY(vc_smooth_t<T>(l, d_.smoother, d_.coarse_maxit, MG_ARR_U, MG_ARR_RHS));
-            h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
-            h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;   // not evaluated on this path
-            MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
-        } else {
-            MG_TRY(vc_coarse_t<T>(l, MG_ARR_U, MG_ARR_RHS));
-        }
-        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
-        return MG_OK;
-    }
-    MG_TRY(vc_smooth_t<T>(l, d_.smoother, d_.nu_pre, MG_ARR_U, MG_ARR_RHS));
-    MG_TRY(vc_residual_t<T>(l, MG_ARR_U, MG_ARR_RHS, MG_ARR_TMP, false));
-    MG_TRY(restrict_t<T>(l, d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
-    MG_TRY(zero_array(MG_ARR_U, l + 1));
-    MG_TRY(vc_cycle_rec_t<T>(l + 1, kind));
-    if (l + 1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(vc_cycle_rec_t<T>(l + 1, MG_CYCLE_W));   // continues from U(l + 1), RHS(l + 1) unchanged
-    if (l + 1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(vc_cycle_rec_t<T>(l + 1, MG_CYCLE_V));
-    MG_TRY(prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U));
-    return vc_smooth_t<T>(l, d_.smoother, d_.nu_post, MG_ARR_U, MG_ARR_RHS);
-}
-
-template <typename T>
-int Solver::vc_cycle_enqueue_t()
-{
-    if (d_.cycle == MG_CYCLE_V) return vc_cycle_rec_t<T>(0, MG_CYCLE_V);
-    MG_TRY(stats_begin());   // W and F make several coarse solves: summed on the device, as cycle_from_t
-    const int rc = vc_cycle_rec_t<T>(0, d_.cycle);
-    acc_stats_ = false;
-    MG_TRY(rc);
-    return stats_end();
-}
-
-int Solver::vc_cycle_enqueue() { return d_.dtype == MG_F64 ? vc_cycle_enqueue_t<double>() : vc_cycle_enqueue_t<float>(); }
-
-int Solver::vc_cycle(mg_cycle_stats *st)
-{
-    MG_TRY(vc_check("mg_vc_cycle", VC_NEED_CYCLE));
-    MG_TRY(vc_cycle_enqueue());
-    return fetch_cycle_stats(st);
-}
-
-// mg_solve's loop and history on L; desc.outer_pre_gs is ignored (the lexicographic sweep has no vc form)
-template <typename T>
-int Solver::vc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
-{
-    double nb = 0;
-    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
-    launch_cg_boundary_copy<T>(stream_, lv_[0].g, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0));   // U = RHS on the Dirichlet nodes
-    MG_HIP(hipGetLastError());
-    int nh = 0;
-    auto norm = [&]() -> int {
-        MG_TRY(vc_residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
-        MG_TRY(fetch_scalars(SC_VC_SUM, d_scal_ + SC_VC_SUM));
-        const double rel = std::sqrt(h_scal_[SC_VC_SUM] / nb);
-        if (hist && nh < hist_cap) hist[nh] = rel;
-        nh++;
-        return MG_OK;
-    };
-    MG_TRY(norm());
-    for (int it = 0; it < maxit; it++) {
-        MG_TRY(vc_cycle_enqueue());
-        MG_TRY(fetch_cycle_stats(per_cycle ? &per_cycle[it] : nullptr));
-        MG_TRY(norm());
-        if (std::sqrt(h_scal_[SC_VC_SUM] / nb) <= tol) break;
-    }
-    if (n_hist) *n_hist = nh;
-    return MG_OK;
-}
-
+int Solver::vc_set_form(int form) { return set_form("mg_vc_set_form", form, &vc_plain_); }
+int Solver::vc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r) { return fam_residual<VcFam>("mg_vc_residual", level, arr_x, arr_rhs, arr_r, sumsq_r); }
+int Solver::vc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs) { return fam_smooth<VcFam>("mg_vc_smooth", level, smoother, sweeps, arr_x, arr_rhs); }
+int Solver::vc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st) { return fam_coarse_solve<VcFam>("mg_vc_coarse_solve", level, arr_x, arr_rhs, st); }
+int Solver::vc_cycle(mg_cycle_stats *st) { return fam_cycle<VcFam>("mg_vc_cycle", st); }
 int Solver::vc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
 {
-    MG_TRY(vc_check("mg_vc_solve", VC_NEED_CYCLE));
-    if (maxit < 0) { set_last_error("mg_vc_solve: negative maxit"); return MG_ERR_BAD_ARG; }
-    return d_.dtype == MG_F64 ? vc_solve_t<double>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
-                              : vc_solve_t<float>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
+    return fam_solve<VcFam>("mg_vc_solve", tol, maxit, hist, hist_cap, n_hist, per_cycle);
 }
 
-// pcg_t with A -> L and M r = one vc cycle from zero
+// pcg_body_t with A -> L and M r = one vc cycle from zero; the sum of the residual goes through launch_reduce_final into
+// the families' slot
 template <typename T>
 int Solver::vc_pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
 {
-    Level &L0 = lv_[0];
-    const Geom &g = L0.g;
-    auto kp = [&](int k) { return reinterpret_cast<T *>(kry_[k]) + L0.gh * g.plane; };
-    T *const x = ptr<T>(MG_ARR_U, 0);
-    const T *const b = ptr<T>(MG_ARR_RHS, 0);
-    mg_krylov_stats out{0, 0, 0.0, 0.0};
-    int nh = 0;
-    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
-    auto residual_sum = [&](T *r, double *v) -> int {   // r = b - L x (r may be null), *v = r.r; synchronises
-        const int np = launch_vc_residual<T>(stream_, g, L0.coef, shift_, ptr<T>(MG_ARR_U, 0), vcptr<T>(0), b, r, d_partials_,
-                                             o4_partials_cap_, vc_plain_);
-        launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_VC_SUM);
+    const Level &L0 = lv_[0];
+    auto residual_sum = [&](T *r, double *v) -> int {
+        const int np = VcFam<T>::residual(*this, 0, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0), r);
+        launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_FAM_SUM);
         MG_HIP(hipGetLastError());
-        MG_TRY(fetch_scalars(SC_VC_SUM, d_scal_ + SC_VC_SUM));
-        *v = h_scal_[SC_VC_SUM];
+        MG_TRY(fetch_scalars(SC_FAM_SUM, d_scal_ + SC_FAM_SUM));
+        *v = h_scal_[SC_FAM_SUM];
         return MG_OK;
     };
-
-    double nb = 0;
-    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
-    launch_cg_boundary_copy<T>(stream_, g, x, b);   // as pcg_t: afterwards r, z, p and q vanish on the boundary
-    MG_HIP(hipGetLastError());
-    double rr0 = 0;
-    MG_TRY(residual_sum(kp(KR), &rr0));
-    record(std::sqrt(rr0 / nb));
-
-    if (nb == 0.0 || rr0 == 0.0) {
-        out.status = 0;
-    } else if (maxit == 0) {
-        out.status = 1;
-    } else {
-        MG_HIP(hipMemsetAsync(d_cg_, 0, sizeof(CgScalars), stream_));
-        int pc = KP0, pn = KP1;
-        MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));
-        auto direction = [&](int mode) -> int {
-            MG_TRY(precondition(&kry_[KZ], kry_[KR], true));
-            int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
-            launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
-            np = launch_vc_cg_direction<T>(stream_, g, L0.coef, shift_, kp(KZ), kp(pc), vcptr<T>(0), kp(pn), kp(KQ), d_cg_, d_cg_part_);
-            launch_cg_tail(stream_, CG_TAIL_ALPHA, d_cg_part_, np, d_cg_);
-            MG_HIP(hipGetLastError());
-            std::swap(pc, pn);
-            return MG_OK;
-        };
-        MG_TRY(direction(CG_TAIL_FIRST));
-        for (int k = 0; k < maxit; k++) {
-            const int np = launch_cg_update<T>(stream_, g, ptr<T>(MG_ARR_U, 0), kp(pc), kp(KR), kp(KQ), d_cg_, d_cg_part_);
-            launch_cg_tail(stream_, CG_TAIL_RR, d_cg_part_, np, d_cg_);
-            MG_HIP(hipGetLastError());
-            MG_HIP(hipMemcpyAsync(h_cg_, d_cg_, sizeof(CgScalars), hipMemcpyDeviceToHost, stream_));
-            MG_HIP(hipStreamSynchronize(stream_));   // the one host synchronisation per iteration: the stopping test
-            if (h_cg_->bad) { out.status = 2; break; }
-            out.iters = k + 1;
-            const double rel = std::sqrt(h_cg_->rr / nb);
-            record(rel);
-            if (rel <= tol) { out.status = 0; break; }
-            if (k + 1 == maxit) { out.status = 1; break; }
-            MG_TRY(direction(CG_TAIL_BETA));
-        }
-    }
-    double nr = 0;
-    MG_TRY(residual_sum((T *)nullptr, &nr));   // the true residual of the returned x
-    out.relres_true = std::sqrt(nr / nb);
-    if (n_hist) *n_hist = nh;
-    if (st) *st = out;
-    return MG_OK;
+    auto direction_apply = [&](const T *z, const T *p, T *pn, T *q) {
+        return launch_vc_cg_direction<T>(stream_, L0.g, L0.coef, shift_, z, p, vcptr<T>(0), pn, q, d_cg_, d_cg_part_);
+    };
+    return pcg_body_t<T>(true, residual_sum, direction_apply, tol, maxit, hist, hist_cap, n_hist, st);
 }
 
 // the direction kernel alone on level-0 arrays (mg_vc_direction): kernel-level checks and measurements, as mg_pcg_kernel
@@ -1416,7 +1533,7 @@ int Solver::vc_direction_t(double beta, const int *a, double *pq)
 
 int Solver::vc_direction(double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq)
 {
-    MG_TRY(vc_check("mg_vc_direction", 0));
+    MG_TRY(fam_check<VcFam>("mg_vc_direction", 0));
     const int a[4] = {arr_z, arr_p, arr_pn, arr_q};
     for (int i = 0; i < 4; i++) {
         if (!check_arr(a[i], 0, "mg_vc_direction")) return MG_ERR_BAD_ARG;
@@ -1430,31 +1547,13 @@ int Solver::vc_direction(double beta, int arr_z, int arr_p, int arr_pn, int arr_
 
 int Solver::vc_pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st)
 {
-    MG_TRY(vc_check("mg_vc_pcg_solve", VC_NEED_CYCLE));
+    MG_TRY(fam_check<VcFam>("mg_vc_pcg_solve", FAM_NEED_CYCLE));
     MG_TRY(krylov_alloc());
     return d_.dtype == MG_F64 ? vc_pcg_t<double>(tol, maxit, hist, hist_cap, n_hist, st)
                               : vc_pcg_t<float>(tol, maxit, hist, hist_cap, n_hist, st);
 }
 
-// ---------------------------------------------------------------- Neumann faces (mg_bc_*), DESIGN.md section 19
-// The handle's constant operator with zero-flux walls on the faces of a mask (enum mg_face): nodes that lie only on Neumann
-// faces are unknowns whose missing neighbours are mirror images. The kernels are in mg_bc.hip -- the restriction too, because
-// injecting at coarse nodes of a Neumann face makes the cycle diverge; the prolongation is the handle's own. Everything goes
-// launch by launch, as the mg_vc_* drivers do. Nothing is allocated: the state is the mask.
-int Solver::bc_check(const char *fn, unsigned need)
-{
-    MG_TRY(driver_begin(fn, REFUSE_DIST | ((need & BC_NEED_CYCLE) ? REFUSE_STAGE_CB : 0u)));
-    if ((need & BC_NEED_CYCLE) && !is_vwf(d_.cycle)) {
-        set_last_error(std::string(fn) + ": not on a sawtooth handle (the cycle must be MG_CYCLE_V, MG_CYCLE_W or MG_CYCLE_F)");
-        return MG_ERR_BAD_ARG;
-    }
-    if ((need & (BC_NEED_CYCLE | BC_NEED_SMOOTHER)) && d_.smoother != MG_SMOOTH_JACOBI && d_.smoother != MG_SMOOTH_RBGS) {
-        set_last_error(std::string(fn) + ": the handle's smoother must be MG_SMOOTH_JACOBI or MG_SMOOTH_RBGS");
-        return MG_ERR_BAD_ARG;
-    }
-    return MG_OK;
-}
-
+// ---------------------------------------------------------------- what only mg_bc_* has
 int Solver::bc_set_faces(int mask)
 {
     MG_TRY(driver_begin("mg_bc_set_faces", REFUSE_DIST));
@@ -1471,74 +1570,6 @@ int Solver::bc_get_faces(int *mask) const
     return MG_OK;
 }
 
-int Solver::bc_set_form(int form)
-{
-    if (form != 0 && form != 1) { set_last_error("mg_bc_set_form: form must be 0 (default) or 1 (the plain kernels everywhere)"); return MG_ERR_BAD_ARG; }
-    bc_plain_ = form == 1;
-    return MG_OK;
-}
-
-template <typename T>
-int Solver::bc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
-{
-    Level &L = lv_[level];
-    if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
-    const int np = launch_bc_residual<T>(stream_, L.g, coef_of<T>(L), bc_mask_, ptr<T>(ax, level), ptr<T>(ar, level),
-                                         arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr, d_partials_, o4_partials_cap_, bc_plain_);
-    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_BC_SUM);
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::bc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
-{
-    MG_TRY(bc_check("mg_bc_residual", 0));
-    if (!check_arr(arr_x, level, "mg_bc_residual") || !check_arr(arr_rhs, level, "mg_bc_residual")) return MG_ERR_BAD_ARG;
-    if (arr_r >= 0 && (!check_arr(arr_r, level, "mg_bc_residual") || arr_r == arr_x || arr_r == arr_rhs)) {
-        set_last_error("mg_bc_residual: bad output array");
-        return MG_ERR_BAD_ARG;
-    }
-    MG_TRY(d_.dtype == MG_F64 ? bc_residual_t<double>(level, arr_x, arr_rhs, arr_r, true) : bc_residual_t<float>(level, arr_x, arr_rhs, arr_r, true));
-    if (sumsq_r) {
-        MG_TRY(fetch_scalars(SC_BC_SUM, d_scal_ + SC_BC_SUM));
-        *sumsq_r = h_scal_[SC_BC_SUM];
-    }
-    return MG_OK;
-}
-
-template <typename T>
-int Solver::bc_smooth_t(int level, int smoother, int sweeps, int ax, int ar)
-{
-    Level &L = lv_[level];
-    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
-    const Coef<T> c = coef_of<T>(L);
-    for (int s = 0; s < sweeps; s++) {
-        if (smoother == MG_SMOOTH_JACOBI) {   // out of place into TMP, then the two pointers are swapped (as smooth_t)
-            launch_bc_jacobi<T>(stream_, L.g, c, bc_mask_, (T)d_.omega, ptr<T>(ax, level), ptr<T>(ar, level), ptr<T>(MG_ARR_TMP, level),
-                                bc_plain_);
-            std::swap(L.base[ax], L.base[MG_ARR_TMP]);
-        } else {
-            for (int colour = 0; colour < 2; colour++)
-                launch_bc_rb_colour<T>(stream_, L.g, c, bc_mask_, colour, ptr<T>(ax, level), ptr<T>(ar, level));
-        }
-    }
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::bc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs)
-{
-    MG_TRY(bc_check("mg_bc_smooth", 0));
-    if (!check_arr(arr_x, level, "mg_bc_smooth") || !check_arr(arr_rhs, level, "mg_bc_smooth")) return MG_ERR_BAD_ARG;
-    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs || sweeps < 0 ||
-        (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS)) {
-        set_last_error("mg_bc_smooth: bad array / sweeps, or a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS");
-        return MG_ERR_BAD_ARG;
-    }
-    return d_.dtype == MG_F64 ? bc_smooth_t<double>(level, smoother, sweeps, arr_x, arr_rhs)
-                              : bc_smooth_t<float>(level, smoother, sweeps, arr_x, arr_rhs);
-}
-
 template <typename T>
 int Solver::bc_restrict_t(int fl, int kind, int as, int ad)
 {
@@ -1553,7 +1584,7 @@ int Solver::bc_restrict_t(int fl, int kind, int as, int ad)
 
 int Solver::bc_restrict(int fine_level, int kind, int arr_src, int arr_dst)
 {
-    MG_TRY(bc_check("mg_bc_restrict", 0));
+    MG_TRY(fam_check<BcFam>("mg_bc_restrict", 0));
     if (fine_level < 0 || fine_level + 1 >= d_.levels || !check_arr(arr_src, fine_level, "mg_bc_restrict") ||
         !check_arr(arr_dst, fine_level + 1, "mg_bc_restrict") || (kind != MG_RESTRICT_INJECT && kind != MG_RESTRICT_FULLW)) {
         set_last_error("mg_bc_restrict: bad level / array / kind");
@@ -1561,26 +1592,6 @@ int Solver::bc_restrict(int fine_level, int kind, int arr_src, int arr_dst)
     }
     return d_.dtype == MG_F64 ? bc_restrict_t<double>(fine_level, kind, arr_src, arr_dst)
                               : bc_restrict_t<float>(fine_level, kind, arr_src, arr_dst);
-}
-
-template <typename T>
-int Solver::bc_coarse_t(int level, int ax, int ar)
-{
-    Level &L = lv_[level];
-    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
-    launch_bc_coarse<T>(stream_, L.g, coef_of<T>(L), bc_mask_, (T)d_.omega, d_.smoother, ptr<T>(ax, level), ptr<T>(MG_ARR_TMP, level),
-                        ptr<T>(ar, level), d_.coarse_maxit, d_.coarse_tol, d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, d_coarse_);
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::bc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
-{
-    MG_TRY(bc_check("mg_bc_coarse_solve", BC_NEED_SMOOTHER));
-    if (!check_arr(arr_x, level, "mg_bc_coarse_solve") || !check_arr(arr_rhs, level, "mg_bc_coarse_solve")) return MG_ERR_BAD_ARG;
-    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs) { set_last_error("mg_bc_coarse_solve: bad array"); return MG_ERR_BAD_ARG; }
-    MG_TRY(d_.dtype == MG_F64 ? bc_coarse_t<double>(level, arr_x, arr_rhs) : bc_coarse_t<float>(level, arr_x, arr_rhs));
-    return fetch_cycle_stats(st);
 }
 
 // c = (sum w v) / (sum w), v -= (T)c. sum w is the product over the axes of (nodes - half a node per Neumann face): exact in double.
@@ -1591,13 +1602,13 @@ int Solver::bc_project_t(int level, int arr, double *mean)
     if (arr == MG_ARR_RHS) L.rhs_halo_ok = false;
     const Geom &g = L.g;
     const int np = launch_bc_wsum<T>(stream_, g, bc_mask_, ptr<T>(arr, level), d_partials_, o4_partials_cap_);
-    launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_BC_SUM);
+    launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_FAM_SUM);
     MG_HIP(hipGetLastError());
-    MG_TRY(fetch_scalars(SC_BC_SUM, d_scal_ + SC_BC_SUM));
+    MG_TRY(fetch_scalars(SC_FAM_SUM, d_scal_ + SC_FAM_SUM));
     auto halves = [&](int lo, int hi) { return 0.5 * (((bc_mask_ & lo) ? 1 : 0) + ((bc_mask_ & hi) ? 1 : 0)); };
     double sw = ((double)g.nx - halves(MG_FACE_XLO, MG_FACE_XHI)) * ((double)g.ny - halves(MG_FACE_YLO, MG_FACE_YHI));
     if (g.dim == 3) sw *= (double)g.gnz - halves(MG_FACE_ZLO, MG_FACE_ZHI);
-    const double c = h_scal_[SC_BC_SUM] / sw;
+    const double c = h_scal_[SC_FAM_SUM] / sw;
     launch_bc_shift<T>(stream_, g, (T)c, ptr<T>(arr, level));
     MG_HIP(hipGetLastError());
     if (mean) *mean = c;
@@ -1606,119 +1617,22 @@ int Solver::bc_project_t(int level, int arr, double *mean)
 
 int Solver::bc_project(int level, int arr, double *mean)
 {
-    MG_TRY(bc_check("mg_bc_project", 0));
+    MG_TRY(fam_check<BcFam>("mg_bc_project", 0));
     if (!check_arr(arr, level, "mg_bc_project")) return MG_ERR_BAD_ARG;
     return d_.dtype == MG_F64 ? bc_project_t<double>(level, arr, mean) : bc_project_t<float>(level, arr, mean);
 }
 
-// cyc(l, kind) of mg_desc.h with the bc kernels, launch by launch
-template <typename T>
-int Solver::bc_cycle_rec_t(int l, int kind)
-{
-    const int L = d_.levels;
-    if (l == L - 1) {
-        const long long pts = (long long)lv_[l].g.nx * lv_[l].g.ny * lv_[l].g.gnz;
-        if (pts > 32768 && d_.coarse_mode == MG_COARSE_FIXED) {   // too big for one workgroup: chip-wide sweeps, as coarse_level_t
-            MG_TRY(bc_smooth_t<T>(l, d_.smoother, d_.coarse_maxit, MG_ARR_U, MG_ARR_RHS));
-            h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
-            h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;   // not evaluated on this path
-            MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
-        } else {
-            MG_TRY(bc_coarse_t<T>(l, MG_ARR_U, MG_ARR_RHS));
-        }
-        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
-        return MG_OK;
-    }
-    MG_TRY(bc_smooth_t<T>(l, d_.smoother, d_.nu_pre, MG_ARR_U, MG_ARR_RHS));
-    MG_TRY(bc_residual_t<T>(l, MG_ARR_U, MG_ARR_RHS, MG_ARR_TMP, false));
-    MG_TRY(bc_restrict_t<T>(l, d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
-    MG_TRY(zero_array(MG_ARR_U, l + 1));
-    MG_TRY(bc_cycle_rec_t<T>(l + 1, kind));
-    if (l + 1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(bc_cycle_rec_t<T>(l + 1, MG_CYCLE_W));   // continues from U(l + 1), RHS(l + 1) unchanged
-    if (l + 1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(bc_cycle_rec_t<T>(l + 1, MG_CYCLE_V));
-    MG_TRY(prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U));
-    return bc_smooth_t<T>(l, d_.smoother, d_.nu_post, MG_ARR_U, MG_ARR_RHS);
-}
-
-template <typename T>
-int Solver::bc_cycle_enqueue_t()
-{
-    if (d_.cycle == MG_CYCLE_V) return bc_cycle_rec_t<T>(0, MG_CYCLE_V);
-    MG_TRY(stats_begin());   // W and F make several coarse solves: summed on the device, as cycle_from_t
-    const int rc = bc_cycle_rec_t<T>(0, d_.cycle);
-    acc_stats_ = false;
-    MG_TRY(rc);
-    return stats_end();
-}
-
-int Solver::bc_cycle_enqueue() { return d_.dtype == MG_F64 ? bc_cycle_enqueue_t<double>() : bc_cycle_enqueue_t<float>(); }
-
-int Solver::bc_cycle(mg_cycle_stats *st)
-{
-    MG_TRY(bc_check("mg_bc_cycle", BC_NEED_CYCLE));
-    MG_TRY(bc_cycle_enqueue());
-    return fetch_cycle_stats(st);
-}
-
-// mg_solve's loop and history on this operator; desc.outer_pre_gs is ignored. All faces Neumann and no shift: the constants
-// are the null space, RHS(0) is projected onto the range first (it stays projected) and U(0) is projected at the end.
-template <typename T>
-int Solver::bc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
-{
-    const bool singular = bc_singular();
-    if (singular) MG_TRY(bc_project_t<T>(0, MG_ARR_RHS, nullptr));
-    double nb = 0;
-    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
-    launch_bc_dirichlet_copy<T>(stream_, lv_[0].g, bc_mask_, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0));   // U = RHS on the Dirichlet nodes
-    MG_HIP(hipGetLastError());
-    int nh = 0;
-    auto norm = [&]() -> int {
-        MG_TRY(bc_residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
-        MG_TRY(fetch_scalars(SC_BC_SUM, d_scal_ + SC_BC_SUM));
-        const double rel = std::sqrt(h_scal_[SC_BC_SUM] / nb);
-        if (hist && nh < hist_cap) hist[nh] = rel;
-        nh++;
-        return MG_OK;
-    };
-    MG_TRY(norm());
-    for (int it = 0; it < maxit; it++) {
-        MG_TRY(bc_cycle_enqueue());
-        MG_TRY(fetch_cycle_stats(per_cycle ? &per_cycle[it] : nullptr));
-        MG_TRY(norm());
-        if (std::sqrt(h_scal_[SC_BC_SUM] / nb) <= tol) break;
-    }
-    if (singular) MG_TRY(bc_project_t<T>(0, MG_ARR_U, nullptr));
-    if (n_hist) *n_hist = nh;
-    return MG_OK;
-}
-
+int Solver::bc_set_form(int form) { return set_form("mg_bc_set_form", form, &bc_plain_); }
+int Solver::bc_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r) { return fam_residual<BcFam>("mg_bc_residual", level, arr_x, arr_rhs, arr_r, sumsq_r); }
+int Solver::bc_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs) { return fam_smooth<BcFam>("mg_bc_smooth", level, smoother, sweeps, arr_x, arr_rhs); }
+int Solver::bc_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st) { return fam_coarse_solve<BcFam>("mg_bc_coarse_solve", level, arr_x, arr_rhs, st); }
+int Solver::bc_cycle(mg_cycle_stats *st) { return fam_cycle<BcFam>("mg_bc_cycle", st); }
 int Solver::bc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle)
 {
-    MG_TRY(bc_check("mg_bc_solve", BC_NEED_CYCLE));
-    if (maxit < 0) { set_last_error("mg_bc_solve: negative maxit"); return MG_ERR_BAD_ARG; }
-    return d_.dtype == MG_F64 ? bc_solve_t<double>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
-                              : bc_solve_t<float>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
+    return fam_solve<BcFam>("mg_bc_solve", tol, maxit, hist, hist_cap, n_hist, per_cycle);
 }
 
-// ---------------------------------------------------------------- the full approximation scheme (mg_fas_*), DESIGN.md section 20
-// N(u) = (sigma I + A) u + gamma g(u) with the handle's constant operator, all faces Dirichlet, gamma the same on every level.
-// The cycle is mg_vc_cycle's recursion on the nonlinear problem itself: the coarse level starts from the INJECTED iterate (kept
-// in E), its right-hand side is R r + N_c(injected iterate), and the correction is the difference to the kept copy. The
-// kernels are in mg_fas.hip; everything goes launch by launch. Nothing is allocated: the state is the kind and gamma.
-int Solver::fas_check(const char *fn, unsigned need)
-{
-    MG_TRY(driver_begin(fn, REFUSE_DIST | ((need & FAS_NEED_CYCLE) ? REFUSE_STAGE_CB : 0u)));
-    if ((need & FAS_NEED_CYCLE) && !is_vwf(d_.cycle)) {
-        set_last_error(std::string(fn) + ": not on a sawtooth handle (the cycle must be MG_CYCLE_V, MG_CYCLE_W or MG_CYCLE_F)");
-        return MG_ERR_BAD_ARG;
-    }
-    if ((need & (FAS_NEED_CYCLE | FAS_NEED_SMOOTHER)) && d_.smoother != MG_SMOOTH_JACOBI && d_.smoother != MG_SMOOTH_RBGS) {
-        set_last_error(std::string(fn) + ": the handle's smoother must be MG_SMOOTH_JACOBI or MG_SMOOTH_RBGS");
-        return MG_ERR_BAD_ARG;
-    }
-    return MG_OK;
-}
-
+// ---------------------------------------------------------------- what only mg_fas_* has
 int Solver::fas_set_reaction(int kind, double gamma)
 {
     MG_TRY(driver_begin("mg_fas_set_reaction", REFUSE_DIST));
@@ -1736,75 +1650,6 @@ int Solver::fas_get_reaction(int *kind, double *gamma) const
     return MG_OK;
 }
 
-int Solver::fas_set_form(int form)
-{
-    if (form != 0 && form != 1) { set_last_error("mg_fas_set_form: form must be 0 (default) or 1 (the plain kernels everywhere)"); return MG_ERR_BAD_ARG; }
-    fas_plain_ = form == 1;
-    return MG_OK;
-}
-
-template <typename T>
-int Solver::fas_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
-{
-    Level &L = lv_[level];
-    if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
-    const int np = launch_fas_residual<T>(stream_, L.g, coef_of<T>(L), fas_kind_, (T)fas_gamma_, ptr<T>(ax, level), ptr<T>(ar, level),
-                                          arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr, d_partials_, o4_partials_cap_, fas_plain_);
-    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_FAS_SUM);
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::fas_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r)
-{
-    MG_TRY(fas_check("mg_fas_residual", 0));
-    if (!check_arr(arr_x, level, "mg_fas_residual") || !check_arr(arr_rhs, level, "mg_fas_residual")) return MG_ERR_BAD_ARG;
-    if (arr_r >= 0 && (!check_arr(arr_r, level, "mg_fas_residual") || arr_r == arr_x || arr_r == arr_rhs)) {
-        set_last_error("mg_fas_residual: bad output array");
-        return MG_ERR_BAD_ARG;
-    }
-    MG_TRY(d_.dtype == MG_F64 ? fas_residual_t<double>(level, arr_x, arr_rhs, arr_r, true) : fas_residual_t<float>(level, arr_x, arr_rhs, arr_r, true));
-    if (sumsq_r) {
-        MG_TRY(fetch_scalars(SC_FAS_SUM, d_scal_ + SC_FAS_SUM));
-        *sumsq_r = h_scal_[SC_FAS_SUM];
-    }
-    return MG_OK;
-}
-
-template <typename T>
-int Solver::fas_smooth_t(int level, int smoother, int sweeps, int ax, int ar)
-{
-    Level &L = lv_[level];
-    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
-    const Coef<T> c = coef_of<T>(L);
-    const T G = (T)fas_gamma_;
-    for (int s = 0; s < sweeps; s++) {
-        if (smoother == MG_SMOOTH_JACOBI) {   // out of place into TMP, then the two pointers are swapped (as smooth_t)
-            launch_fas_jacobi<T>(stream_, L.g, c, fas_kind_, G, (T)d_.omega, ptr<T>(ax, level), ptr<T>(ar, level), ptr<T>(MG_ARR_TMP, level),
-                                 fas_plain_);
-            std::swap(L.base[ax], L.base[MG_ARR_TMP]);
-        } else {
-            for (int colour = 0; colour < 2; colour++)
-                launch_fas_rb_colour<T>(stream_, L.g, c, fas_kind_, G, colour, ptr<T>(ax, level), ptr<T>(ar, level));
-        }
-    }
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::fas_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs)
-{
-    MG_TRY(fas_check("mg_fas_smooth", 0));
-    if (!check_arr(arr_x, level, "mg_fas_smooth") || !check_arr(arr_rhs, level, "mg_fas_smooth")) return MG_ERR_BAD_ARG;
-    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs || sweeps < 0 ||
-        (smoother != MG_SMOOTH_JACOBI && smoother != MG_SMOOTH_RBGS)) {
-        set_last_error("mg_fas_smooth: bad array / sweeps, or a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS");
-        return MG_ERR_BAD_ARG;
-    }
-    return d_.dtype == MG_F64 ? fas_smooth_t<double>(level, smoother, sweeps, arr_x, arr_rhs)
-                              : fas_smooth_t<float>(level, smoother, sweeps, arr_x, arr_rhs);
-}
-
 // TMP(fl) holds the residual of level fl: U, E and RHS of level fl + 1 in one launch
 template <typename T>
 int Solver::fas_coarse_rhs_t(int fl)
@@ -1819,7 +1664,7 @@ int Solver::fas_coarse_rhs_t(int fl)
 
 int Solver::fas_coarse_rhs(int fine_level)
 {
-    MG_TRY(fas_check("mg_fas_coarse_rhs", 0));
+    MG_TRY(fam_check<FasFam>("mg_fas_coarse_rhs", 0));
     if (fine_level < 0 || fine_level + 1 >= d_.levels) { set_last_error("mg_fas_coarse_rhs: bad level"); return MG_ERR_BAD_ARG; }
     return d_.dtype == MG_F64 ? fas_coarse_rhs_t<double>(fine_level) : fas_coarse_rhs_t<float>(fine_level);
 }
@@ -1835,79 +1680,16 @@ int Solver::fas_correct_t(int fl)
 
 int Solver::fas_correct(int fine_level)
 {
-    MG_TRY(fas_check("mg_fas_correct", 0));
+    MG_TRY(fam_check<FasFam>("mg_fas_correct", 0));
     if (fine_level < 0 || fine_level + 1 >= d_.levels) { set_last_error("mg_fas_correct: bad level"); return MG_ERR_BAD_ARG; }
     return d_.dtype == MG_F64 ? fas_correct_t<double>(fine_level) : fas_correct_t<float>(fine_level);
 }
 
-template <typename T>
-int Solver::fas_coarse_t(int level, int ax, int ar)
-{
-    Level &L = lv_[level];
-    if (ax == MG_ARR_RHS) L.rhs_halo_ok = false;
-    launch_fas_coarse<T>(stream_, L.g, coef_of<T>(L), fas_kind_, (T)fas_gamma_, (T)d_.omega, d_.smoother, ptr<T>(ax, level),
-                         ptr<T>(MG_ARR_TMP, level), ptr<T>(ar, level), d_.coarse_maxit, d_.coarse_tol,
-                         d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, d_coarse_);
-    MG_HIP(hipGetLastError());
-    return MG_OK;
-}
-
-int Solver::fas_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st)
-{
-    MG_TRY(fas_check("mg_fas_coarse_solve", FAS_NEED_SMOOTHER));
-    if (!check_arr(arr_x, level, "mg_fas_coarse_solve") || !check_arr(arr_rhs, level, "mg_fas_coarse_solve")) return MG_ERR_BAD_ARG;
-    if (arr_x == MG_ARR_TMP || arr_rhs == MG_ARR_TMP || arr_x == arr_rhs) { set_last_error("mg_fas_coarse_solve: bad array"); return MG_ERR_BAD_ARG; }
-    MG_TRY(d_.dtype == MG_F64 ? fas_coarse_t<double>(level, arr_x, arr_rhs) : fas_coarse_t<float>(level, arr_x, arr_rhs));
-    return fetch_cycle_stats(st);
-}
-
-// cyc(l, kind) of mg_desc.h on the nonlinear problem, launch by launch
-template <typename T>
-int Solver::fas_cycle_rec_t(int l, int kind)
-{
-    const int L = d_.levels;
-    if (l == L - 1) {
-        const long long pts = (long long)lv_[l].g.nx * lv_[l].g.ny * lv_[l].g.gnz;
-        if (pts > 32768 && d_.coarse_mode == MG_COARSE_FIXED) {   // too big for one workgroup: chip-wide sweeps, as coarse_level_t
-            MG_TRY(fas_smooth_t<T>(l, d_.smoother, d_.coarse_maxit, MG_ARR_U, MG_ARR_RHS));
-            h_fixed_->iters = d_.coarse_maxit; h_fixed_->flag = 0;
-            h_fixed_->relres = 0; h_fixed_->sumsq_rhs = 0; h_fixed_->sumsq_r = 0;   // not evaluated on this path
-            MG_HIP(hipMemcpyAsync(d_coarse_, h_fixed_, sizeof(CoarseOut), hipMemcpyHostToDevice, stream_));
-        } else {
-            MG_TRY(fas_coarse_t<T>(l, MG_ARR_U, MG_ARR_RHS));
-        }
-        if (acc_stats_) { launch_coarse_accum(stream_, d_coarse_acc_, d_coarse_); MG_HIP(hipGetLastError()); }
-        return MG_OK;
-    }
-    MG_TRY(fas_smooth_t<T>(l, d_.smoother, d_.nu_pre, MG_ARR_U, MG_ARR_RHS));
-    MG_TRY(fas_residual_t<T>(l, MG_ARR_U, MG_ARR_RHS, MG_ARR_TMP, false));
-    MG_TRY(fas_coarse_rhs_t<T>(l));   // U(l + 1) = E(l + 1) = the injected iterate, RHS(l + 1)
-    MG_TRY(fas_cycle_rec_t<T>(l + 1, kind));
-    if (l + 1 < L - 1 && kind == MG_CYCLE_W) MG_TRY(fas_cycle_rec_t<T>(l + 1, MG_CYCLE_W));   // continues from U(l + 1); RHS(l + 1), E(l + 1) unchanged
-    if (l + 1 < L - 1 && kind == MG_CYCLE_F) MG_TRY(fas_cycle_rec_t<T>(l + 1, MG_CYCLE_V));
-    MG_TRY(fas_correct_t<T>(l));
-    return fas_smooth_t<T>(l, d_.smoother, d_.nu_post, MG_ARR_U, MG_ARR_RHS);
-}
-
-template <typename T>
-int Solver::fas_cycle_enqueue_t()
-{
-    if (d_.cycle == MG_CYCLE_V) return fas_cycle_rec_t<T>(0, MG_CYCLE_V);
-    MG_TRY(stats_begin());   // W and F make several coarse solves: summed on the device, as cycle_from_t
-    const int rc = fas_cycle_rec_t<T>(0, d_.cycle);
-    acc_stats_ = false;
-    MG_TRY(rc);
-    return stats_end();
-}
-
-int Solver::fas_cycle_enqueue() { return d_.dtype == MG_F64 ? fas_cycle_enqueue_t<double>() : fas_cycle_enqueue_t<float>(); }
-
-int Solver::fas_cycle(mg_cycle_stats *st)
-{
-    MG_TRY(fas_check("mg_fas_cycle", FAS_NEED_CYCLE));
-    MG_TRY(fas_cycle_enqueue());
-    return fetch_cycle_stats(st);
-}
+int Solver::fas_set_form(int form) { return set_form("mg_fas_set_form", form, &fas_plain_); }
+int Solver::fas_residual(int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r) { return fam_residual<FasFam>("mg_fas_residual", level, arr_x, arr_rhs, arr_r, sumsq_r); }
+int Solver::fas_smooth(int level, int smoother, int sweeps, int arr_x, int arr_rhs) { return fam_smooth<FasFam>("mg_fas_smooth", level, smoother, sweeps, arr_x, arr_rhs); }
+int Solver::fas_coarse_solve(int level, int arr_x, int arr_rhs, mg_cycle_stats *st) { return fam_coarse_solve<FasFam>("mg_fas_coarse_solve", level, arr_x, arr_rhs, st); }
+int Solver::fas_cycle(mg_cycle_stats *st) { return fam_cycle<FasFam>("mg_fas_cycle", st); }
 
 // hist[k] = sqrt(sum r^2) after k cycles, ABSOLUTE (b = 0 is an ordinary nonlinear problem); one synchronisation per cycle
 template <typename T>
@@ -1918,9 +1700,9 @@ int Solver::fas_solve_t(double rtol, double atol, int maxit, double *hist, int h
     int nh = 0, status = 1;
     double first = 0, last = 0;
     auto norm = [&]() -> int {
-        MG_TRY(fas_residual_t<T>(0, MG_ARR_U, MG_ARR_RHS, -1, true));
-        MG_TRY(fetch_scalars(SC_FAS_SUM, d_scal_ + SC_FAS_SUM));
-        last = std::sqrt(h_scal_[SC_FAS_SUM]);
+        double rr = 0;
+        MG_TRY(fam_residual_sum_t<FasFam<T>>(0, MG_ARR_U, MG_ARR_RHS, -1, &rr));
+        last = std::sqrt(rr);
         if (nh == 0) first = last;
         if (hist && nh < hist_cap) hist[nh] = last;
         nh++;
@@ -1932,7 +1714,7 @@ int Solver::fas_solve_t(double rtol, double atol, int maxit, double *hist, int h
     int v = verdict();
     int it = 0;
     for (; v < 0 && it < maxit; it++) {
-        MG_TRY(fas_cycle_enqueue());
+        MG_TRY(fam_cycle_enqueue_t<FasFam<T>>());
         MG_TRY(norm());
         v = verdict();
     }
@@ -1944,7 +1726,7 @@ int Solver::fas_solve_t(double rtol, double atol, int maxit, double *hist, int h
 
 int Solver::fas_solve(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st)
 {
-    MG_TRY(fas_check("mg_fas_solve", FAS_NEED_CYCLE));
+    MG_TRY(fam_check<FasFam>("mg_fas_solve", FAM_NEED_CYCLE));
     if (!(rtol >= 0) || !(atol >= 0) || !std::isfinite(rtol) || !std::isfinite(atol) || maxit < 0) {
         set_last_error("mg_fas_solve: the tolerances must be finite and >= 0, maxit >= 0");
         return MG_ERR_BAD_ARG;

@@ -3,14 +3,15 @@
 // handle's constant operator (alpha, aniso, semi_xy, odd sizes, the shift of mg_set_shift), all faces Dirichlet; the reaction
 // g is pointwise, so every kernel is the 7-point stream of the constant operator plus a few flops on the centre value.
 //
-//   k_fas_plain<T, DIM, KIND, OP, SAVE>  OP = residual (stored with SAVE, else norm only) / Jacobi sweep (out of place) / one
-//                                        red-black colour pass (in place): one thread per node, grid-stride, every shape
+//   FasOp<T, KIND>                       the point operator (Coef and G): res<DIM> and solve<DIM> of the contract below. The plain
+//                                        form (residual / Jacobi sweep / one red-black colour pass, every shape) and the
+//                                        coarsest-grid solve are mg_opfamily.h's k_op_plain<FasOp<T, KIND>, DIM, OP, SAVE> and
+//                                        k_op_coarse<FasOp<T, KIND>, DIM>
 //   k_fas_march<T, KIND, OP, SAVE>       the residual and the Jacobi sweep on 3-D levels with rows long enough to fill a wave
 //                                        (fas_march_ok, mg_geom.h): k_bc_march's tile (mg_bc.hip) with one marched field
 //   k_fas_coarse_rhs<T, DIM, WZ, KIND>   the FAS transition l -> l+1 in one launch: U(l+1) = E(l+1) = U(l) injected,
 //                                        RHS(l+1) = R TMP(l) + N_c(U(l) injected), the coarse neighbours read from U(l)
 //   k_fas_diff<T>                        e = x - e (the coarse correction U(l+1) - E(l+1), into E(l+1))
-//   k_fas_coarse<T, DIM, KIND>           the Solver::Solve loop of k_coarse_solve (mg_kernels.hip) in one workgroup
 //
 // Arithmetic contract (compiled with -ffp-contract=off; tests/fas_ref.py restates it in numpy), all in T, every operation
 // rounded separately, c = the level's Coef (mg_level_coefficients: shift and aniso included), G = (T)gamma:
@@ -22,17 +23,11 @@
 //   Jacobi       u' = ps (omega == 1) or u_i + omega * (ps - u_i)
 //   red-black    in place, colour (i + j + gz) & 1, colour 0 first; Dirichlet nodes take b with their colour
 // With gamma == 0 num = b - s and den = cd, and the correctly rounded quotient is div_cd's: mg_residual's and mg_smooth's bits.
-#include "mg_kernels.h"
-#include "mg_device.h"
-
-#include <algorithm>
+#include "mg_opfamily.h"
 
 namespace mg {
 namespace {
 
-constexpr int FAS_THREADS = 256, FAS_MAX_BLOCKS = 2048;
-constexpr int FBW = 4, FRY = 2;   // waves per workgroup / rows per wave of the marching tile
-enum { FAS_RES = 0, FAS_JAC = 1, FAS_RB = 2 };
 enum { FAS_CUBIC = 0, FAS_EXP = 1 };   // enum mg_fas_kind
 
 __device__ __forceinline__ double fas_exp(double x) { return exp(x); }
@@ -62,86 +57,60 @@ __device__ __forceinline__ T fas_newton(const Coef<T> &c, T G, T s, T ui, T bi)
     return num / den;
 }
 
-template <typename T, int DIM, int KIND>
-__device__ __forceinline__ T fas_point_res(const Geom &g, const Coef<T> &c, T G, const T *u, const T *b, int z, int y, int x)
-{
-    const long long i = lidx(g, z, y, x);
-    T sum;
-    if (on_boundary(g, z, y, x)) {
-        sum = (T)1 * u[i];
-    } else {
-        T gv, gp;
-        fas_react<T, KIND>(u[i], gv, gp);
-        sum = full_sum<T, DIM>(u, i, g.pitch, g.plane, c) + G * gv;
-    }
-    return b[i] - sum;
-}
+// the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h)
+template <typename T, int KIND>
+struct FasOp {
+    typedef T type;
+    Coef<T> c;
+    T G;
 
-template <typename T, int DIM, int KIND>
-__device__ __forceinline__ T fas_point_solve(const Geom &g, const Coef<T> &c, T G, T omega, bool damped, const T *u, const T *b,
-                                             int z, int y, int x)
-{
-    const long long i = lidx(g, z, y, x);
-    const T bi = b[i];
-    if (on_boundary(g, z, y, x)) return bi;
-    const T s = offdiag_sum<T, DIM>(u, i, g.pitch, g.plane, c);
-    const T ui = u[i];
-    const T ps = fas_newton<T, KIND>(c, G, s, ui, bi);
-    if (damped) return ui + omega * (ps - ui);
-    return ps;
-}
-
-// ---------------------------------------------------------------- the plain form
-// out: r (FAS_RES with SAVE), u' (FAS_JAC, must not alias u) or u itself (FAS_RB: the other colour is only read)
-template <typename T, int DIM, int KIND, int OP, bool SAVE>
-__global__ __launch_bounds__(FAS_THREADS) void k_fas_plain(Geom g, Coef<T> c, T G, T omega, int colour, const T *u,
-                                                           const T *__restrict__ b, T *out, double *__restrict__ partials)
-{
-    __shared__ double sh[FAS_THREADS / 64];
-    const int hx = OP == FAS_RB ? (g.nx + 1) / 2 : g.nx;   // nodes of a row this launch visits
-    const long long nitems = (long long)hx * g.ny * g.nz;
-    const bool damped = OP == FAS_JAC && omega != (T)1;
-    double acc = 0.;
-    for (long long it = (long long)blockIdx.x * FAS_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * FAS_THREADS) {
-        const long long row = it / hx;
-        int x = (int)(it - row * hx);
-        const int y = (int)(row % g.ny), z = (int)(row / g.ny);
-        if (OP == FAS_RB) {
-            x = 2 * x + ((y + g.gz0 + z + colour) & 1);   // the x parity that has (x + y + gz) & 1 == colour
-            if (x >= g.nx) continue;
-        }
-        if (OP == FAS_RES) {
-            const T res = fas_point_res<T, DIM, KIND>(g, c, G, u, b, z, y, x);
-            acc += (double)res * (double)res;
-            if (SAVE) out[lidx(g, z, y, x)] = res;
+    template <int DIM>
+    __device__ __forceinline__ T res(const Geom &g, const T *u, const T *b, int z, int y, int x) const
+    {
+        const long long i = lidx(g, z, y, x);
+        T sum;
+        if (on_boundary(g, z, y, x)) {
+            sum = (T)1 * u[i];
         } else {
-            out[lidx(g, z, y, x)] = fas_point_solve<T, DIM, KIND>(g, c, G, omega, damped, u, b, z, y, x);
+            T gv, gp;
+            fas_react<T, KIND>(u[i], gv, gp);
+            sum = full_sum<T, DIM>(u, i, g.pitch, g.plane, c) + G * gv;
         }
+        return b[i] - sum;
     }
-    if (OP == FAS_RES) {
-        const double s = block_sum(acc, sh);
-        if (threadIdx.x == 0) partials[blockIdx.x] = s;
+
+    template <int DIM>
+    __device__ __forceinline__ T solve(const Geom &g, T omega, bool damped, const T *u, const T *b, int z, int y, int x) const
+    {
+        const long long i = lidx(g, z, y, x);
+        const T bi = b[i];
+        if (on_boundary(g, z, y, x)) return bi;
+        const T s = offdiag_sum<T, DIM>(u, i, g.pitch, g.plane, c);
+        const T ui = u[i];
+        const T ps = fas_newton<T, KIND>(c, G, s, ui, bi);
+        if (damped) return ui + omega * (ps - ui);
+        return ps;
     }
-}
+};
 
 // ---------------------------------------------------------------- the marching tile (3-D)
-// k_bc_march's tile: a lane owns one aligned 16-byte vector of x, a wave covers 64 vectors of FRY = 2 rows, FBW = 4 waves are
+// k_bc_march's tile: a lane owns one aligned 16-byte vector of x, a wave covers 64 vectors of MRY = 2 rows, MBW = 4 waves are
 // stacked in y and the workgroup marches zc planes with the planes z-1, z, z+1 of u in registers. The reaction term is
 // computed from the centre value the lane holds: no load and no branch is added in the interior; Dirichlet nodes are a select.
 template <typename T, int KIND, int OP, bool SAVE>
-__global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, T omega, const T *__restrict__ u,
+__global__ __launch_bounds__(64 * MBW) void k_fas_march(Geom g, Coef<T> c, T G, T omega, const T *__restrict__ u,
                                                         const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
                                                         int nbx, int nby, int nbz, int zc)
 {
     constexpr int V = Vec16<T>::n;
-    constexpr bool STORE = OP == FAS_JAC || SAVE;
+    constexpr bool STORE = OP == OP_JAC || SAVE;
     typedef typename Vec16<T>::type vec;
-    __shared__ double sh[FBW];
+    __shared__ double sh[MBW];
 
     const int nblocks = nbx * nby * nbz;
     const int bid = xcd_block(blockIdx.x, (nblocks + 7) >> 3);
     if (bid >= nblocks) {   // the whole workgroup
-        if (OP == FAS_RES && threadIdx.x == 0) partials[blockIdx.x] = 0.;
+        if (OP == OP_RES && threadIdx.x == 0) partials[blockIdx.x] = 0.;
         return;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -149,19 +118,19 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
     const int x0 = V * (bx * 64 + lane);
     const int x0c = min(x0, g.pitch - V);   // clamped for loads: every lane stays active
     const bool xfull = x0 + V <= g.nx;      // the lane's vector lies inside the row
-    const int yb = (by * FBW + wv) * FRY;
+    const int yb = (by * MBW + wv) * MRY;
     const int z0 = bz * zc, zend = min(z0 + zc, g.nz);
     // one column left over: the wave that holds the row's last full vector writes it as a full line
     const bool tail1 = g.nx % V == 1 && g.nx > V;
     const bool tailwave = tail1 && (bx * 64 * V <= g.nx - 1 - V) && (g.nx - 1 - V < (bx + 1) * 64 * V);
     const int part = (!tail1 && !xfull && x0 < g.nx) ? g.nx - x0 : 0;   // elements of a partial last vector stored one by one
     const int nown = xfull ? V : part;                                  // elements of the vector this lane stores and sums
-    const bool damped = OP == FAS_JAC && omega != (T)1;
+    const bool damped = OP == OP_JAC && omega != (T)1;
 
-    long long rowoff[FRY];
-    bool yin[FRY], ybnd[FRY];
+    long long rowoff[MRY];
+    bool yin[MRY], ybnd[MRY];
 #pragma unroll
-    for (int r = 0; r < FRY; r++) {
+    for (int r = 0; r < MRY; r++) {
         const int y = yb + r;
         yin[r] = y < g.ny;
         const int yc = min(y, g.ny - 1);
@@ -169,22 +138,22 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
         rowoff[r] = (long long)yc * g.pitch + x0c;
     }
     const long long off_lo = (long long)min(max(yb - 1, 0), g.ny - 1) * g.pitch + x0c;
-    const long long off_hi = (long long)min(yb + FRY, g.ny - 1) * g.pitch + x0c;
+    const long long off_hi = (long long)min(yb + MRY, g.ny - 1) * g.pitch + x0c;
     const bool edge_l = lane == 0 && x0c > 0, edge_r = lane == 63 && x0c + V < g.pitch;
 
-    vec uzm[FRY], ucc[FRY], uzp[FRY];
+    vec uzm[MRY], ucc[MRY], uzp[MRY];
     const T *pu = u + (long long)z0 * g.plane;
 #pragma unroll
-    for (int r = 0; r < FRY; r++) {
+    for (int r = 0; r < MRY; r++) {
         uzm[r] = *(const vec *)(pu - g.plane + rowoff[r]);   // z0 == 0: the ghost plane, never used (plane 0 is Dirichlet)
         ucc[r] = *(const vec *)(pu + rowoff[r]);
     }
     double acc = 0.;
     for (int z = z0; z < zend; z++, pu += g.plane) {
         const long long zo = (long long)z * g.plane;
-        vec bv[FRY];
+        vec bv[MRY];
 #pragma unroll
-        for (int r = 0; r < FRY; r++) {
+        for (int r = 0; r < MRY; r++) {
             uzp[r] = *(const vec *)(pu + g.plane + rowoff[r]);
             bv[r] = __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r]));
         }
@@ -192,12 +161,12 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
         const int gz = g.gz0 + z;
         const bool zbnd = gz == 0 || gz == g.gnz - 1;
 #pragma unroll
-        for (int r = 0; r < FRY; r++) {
+        for (int r = 0; r < MRY; r++) {
             T uel = 0, uer = 0;
             if (edge_l) uel = pu[rowoff[r] - 1];
             if (edge_r) uer = pu[rowoff[r] + V];
             const T uxm = lane_from_prev(ucc[r][V - 1], uel), uxp = lane_from_next(ucc[r][0], uer);
-            const vec uym = (r > 0) ? ucc[r > 0 ? r - 1 : 0] : ulo, uyp = (r < FRY - 1) ? ucc[r < FRY - 1 ? r + 1 : 0] : uhi;
+            const vec uym = (r > 0) ? ucc[r > 0 ? r - 1 : 0] : ulo, uyp = (r < MRY - 1) ? ucc[r < MRY - 1 ? r + 1 : 0] : uhi;
             const bool rbnd = zbnd || ybnd[r];
             vec res;
 #pragma unroll
@@ -210,11 +179,11 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
                 sum += c.cz * uzm[r][e];
                 sum += c.cy * uym[e];
                 sum += c.cx * ul;
-                if (OP == FAS_RES) sum += c.cd * ui;
+                if (OP == OP_RES) sum += c.cd * ui;
                 sum += c.cx * ur;
                 sum += c.cy * uyp[e];
                 sum += c.cz * uzp[r][e];
-                if (OP == FAS_RES) {
+                if (OP == OP_RES) {
                     T gv, gp;
                     fas_react<T, KIND>(ui, gv, gp);
                     res[e] = dn ? bi - ui : bi - (sum + G * gv);
@@ -224,7 +193,7 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
                 }
             }
             if (yin[r]) {
-                if (OP == FAS_RES) {
+                if (OP == OP_RES) {
 #pragma unroll
                     for (int e = 0; e < V; e++)
                         if (e < nown) acc += (double)res[e] * (double)res[e];
@@ -248,7 +217,7 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
                         vec tv = (vec)(0);
                         if (j == 0) {
                             const T bt = b[ro + g.nx - 1];
-                            if (OP == FAS_RES) {
+                            if (OP == OP_RES) {
                                 const T rt = bt - (T)1 * u[ro + g.nx - 1];
                                 acc += (double)rt * (double)rt;
                                 tv[0] = rt;
@@ -262,9 +231,9 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
             }
         }
 #pragma unroll
-        for (int r = 0; r < FRY; r++) { uzm[r] = ucc[r]; ucc[r] = uzp[r]; }
+        for (int r = 0; r < MRY; r++) { uzm[r] = ucc[r]; ucc[r] = uzp[r]; }
     }
-    if (OP == FAS_RES) {
+    if (OP == OP_RES) {
         const double s = block_sum(acc, sh);
         if (threadIdx.x == 0) partials[blockIdx.x] = s;
     }
@@ -275,12 +244,12 @@ __global__ __launch_bounds__(64 * FBW) void k_fas_march(Geom g, Coef<T> c, T G, 
 // rc = restrict_fw_point(rf) (inject: rf at the even fine node); rhsc = rc + (full_sum_c(uc) + G*g(uc)) with the coarse
 // neighbours read from uf at distance 2 (z: 1 on a semi transition); coarse Dirichlet nodes: rhsc = uc. cc: Coef of level l+1.
 template <typename T, int DIM, bool WZ, int KIND>
-__global__ __launch_bounds__(FAS_THREADS) void k_fas_coarse_rhs(Geom gf, Geom gc, Coef<T> cc, T G, int inject, const T *__restrict__ uf,
+__global__ __launch_bounds__(OP_THREADS) void k_fas_coarse_rhs(Geom gf, Geom gc, Coef<T> cc, T G, int inject, const T *__restrict__ uf,
                                                                 const T *__restrict__ rf, T *__restrict__ uco, T *__restrict__ eco,
                                                                 T *__restrict__ rhsc)
 {
     const long long nitems = (long long)gc.nx * gc.ny * gc.nz;
-    for (long long it = (long long)blockIdx.x * FAS_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * FAS_THREADS) {
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
         const long long row = it / gc.nx;
         const int x = (int)(it - row * gc.nx), y = (int)(row % gc.ny), z = (int)(row / gc.ny);
         const int fz = (DIM == 3) ? (WZ ? 2 * (gc.gz0 + z) - gf.gz0 : z) : 0;
@@ -312,10 +281,10 @@ __global__ __launch_bounds__(FAS_THREADS) void k_fas_coarse_rhs(Geom gf, Geom gc
 
 // e = x - e on every node
 template <typename T>
-__global__ __launch_bounds__(FAS_THREADS) void k_fas_diff(Geom g, const T *__restrict__ x_, T *__restrict__ e)
+__global__ __launch_bounds__(OP_THREADS) void k_fas_diff(Geom g, const T *__restrict__ x_, T *__restrict__ e)
 {
     const long long nitems = (long long)g.nx * g.ny * g.nz;
-    for (long long it = (long long)blockIdx.x * FAS_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * FAS_THREADS) {
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
         const long long row = it / g.nx;
         const int x = (int)(it - row * g.nx), y = (int)(row % g.ny), z = (int)(row / g.ny);
         const long long i = lidx(g, z, y, x);
@@ -323,139 +292,14 @@ __global__ __launch_bounds__(FAS_THREADS) void k_fas_diff(Geom g, const T *__res
     }
 }
 
-// ---------------------------------------------------------------- the coarsest-grid solve: one workgroup
-template <typename T, int DIM, int KIND>
-__device__ void wg_fas_jacobi(const Geom &g, const Coef<T> &c, T G, T omega, bool damped, const T *u, const T *rhs, T *out)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    for (long long q = threadIdx.x; q < total; q += SWG) {
-        const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-        const int y = rem / g.nx, x = rem - y * g.nx;
-        out[lidx(g, z, y, x)] = fas_point_solve<T, DIM, KIND>(g, c, G, omega, damped, u, rhs, z, y, x);
-    }
-    __syncthreads();
-}
-
-template <typename T, int DIM, int KIND>
-__device__ void wg_fas_rbgs(const Geom &g, const Coef<T> &c, T G, T *u, const T *rhs)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    for (int colour = 0; colour < 2; colour++) {
-        for (long long q = threadIdx.x; q < total; q += SWG) {
-            const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-            const int y = rem / g.nx, x = rem - y * g.nx;
-            if (((x + y + g.gz0 + z) & 1) != colour) continue;
-            u[lidx(g, z, y, x)] = fas_point_solve<T, DIM, KIND>(g, c, G, (T)1, false, u, rhs, z, y, x);
-        }
-        __syncthreads();
-    }
-}
-
-template <typename T, int DIM, int KIND>
-__device__ double wg_fas_residual_sumsq(const Geom &g, const Coef<T> &c, T G, const T *u, const T *rhs, double *sh)
-{
-    const int npl = g.nx * g.ny;
-    const long long total = (long long)npl * g.nz;
-    double sq = 0.;
-    for (long long q = threadIdx.x; q < total; q += SWG) {
-        const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-        const int y = rem / g.nx, x = rem - y * g.nx;
-        const T res = fas_point_res<T, DIM, KIND>(g, c, G, u, rhs, z, y, x);
-        sq += (double)res * (double)res;
-    }
-    return block_sum_bcast(sq, sh);
-}
-
-// k_coarse_solve's loop (Solver::Solve with maxit, tol, fixed) with the nonlinear sweep and the nonlinear residual
-template <typename T, int DIM, int KIND>
-__global__ __launch_bounds__(SWG) void k_fas_coarse(Geom g, Coef<T> c, T G, T omega, int smoother, T *x, T *tmp, const T *rhs,
-                                                    int maxit, double tol, int fixed, CoarseOut *out)
-{
-    __shared__ double sh[18];
-    T *cur = x, *oth = tmp;
-    const bool damped = (omega != (T)1);
-    auto sweep = [&]() {
-        if (smoother == 1) {
-            wg_fas_jacobi<T, DIM, KIND>(g, c, G, omega, damped, cur, rhs, oth);
-            T *t = cur; cur = oth; oth = t;
-        } else {
-            wg_fas_rbgs<T, DIM, KIND>(g, c, G, cur, rhs);
-        }
-    };
-    const double nb = wg_sumsq<T>(g, rhs, sh);
-    int iters = 0, flag = 0;
-    double nr;
-    if (fixed) {
-        for (int s = 0; s < maxit; s++) sweep();
-        iters = maxit;
-        nr = wg_fas_residual_sumsq<T, DIM, KIND>(g, c, G, cur, rhs, sh);
-    } else {
-        int counter = maxit;
-        nr = wg_fas_residual_sumsq<T, DIM, KIND>(g, c, G, cur, rhs, sh);
-        while (sqrt(nr / nb) > tol) {   // NaN (zero rhs) compares false, as in k_coarse_solve
-            if (counter > 0) {
-                sweep();
-                counter -= 1;
-                iters++;
-                nr = wg_fas_residual_sumsq<T, DIM, KIND>(g, c, G, cur, rhs, sh);
-            } else {
-                flag = 1;
-                break;
-            }
-        }
-    }
-    if (cur != x) {   // odd number of Jacobi sweeps: move the result back into x
-        const int npl = g.nx * g.ny;
-        const long long total = (long long)npl * g.nz;
-        for (long long q = threadIdx.x; q < total; q += SWG) {
-            const int z = (int)(q / npl), rem = (int)(q - (long long)z * npl);
-            const int y = rem / g.nx, xx = rem - y * g.nx;
-            const long long i = lidx(g, z, y, xx);
-            x[i] = cur[i];
-        }
-    }
-    if (threadIdx.x == 0) {
-        out->iters = iters;
-        out->flag = flag;
-        out->relres = sqrt(nr / nb);
-        out->sumsq_rhs = nb;
-        out->sumsq_r = nr;
-    }
-}
-
 // ---------------------------------------------------------------- launchers
-int fas_plain_grid(long long items, int cap)
+// launch(op) with op = the point operator of the reaction `kind`: the launches of mg_opfamily.h take their template arguments
+// from its type
+template <typename T, typename Launch>
+auto with_fas_op(int kind, const Coef<T> &c, T G, Launch &&launch)
 {
-    const long long nb = std::min<long long>(FAS_MAX_BLOCKS, (items + FAS_THREADS - 1) / FAS_THREADS);
-    return (int)std::max<long long>(1, std::min<long long>(nb, cap));
-}
-
-struct FasMarchGrid { int nbx, nby, nbz, zc, grid; };
-
-template <typename T>
-FasMarchGrid fas_march_grid(const Geom &g)
-{
-    constexpr int V = Vec16<T>::n;
-    // vectors a row needs lanes for: the full ones, and a partial last one unless it is the single tail column
-    const int nvec = std::max(1, g.nx / V + (g.nx % V > 1 ? 1 : 0));
-    FasMarchGrid m;
-    m.nbx = (nvec + 63) / 64;
-    m.nby = (g.ny + FRY * FBW - 1) / (FRY * FBW);
-    // a chunk of zc planes loads zc + 2: long chunks while they still fill the chip, never shorter than 4
-    m.zc = 16;
-    while (m.zc > 4 && (long long)m.nbx * m.nby * ((g.nz + m.zc - 1) / m.zc) < 2048) m.zc >>= 1;
-    m.nbz = (g.nz + m.zc - 1) / m.zc;
-    m.grid = ((m.nbx * m.nby * m.nbz + 7) / 8) * 8;
-    return m;
-}
-
-// whole levels only: mg_fas_* refuse distributed handles before they get here
-template <typename T>
-bool fas_march_takes(const Geom &g, bool plain)
-{
-    return !plain && fas_march_ok(g.dim, g.nx, g.ny, g.nz, (int)sizeof(T)) && g.gz0 == 0 && g.gnz == g.nz;
+    if (kind == FAS_CUBIC) return launch(FasOp<T, FAS_CUBIC>{c, G});
+    return launch(FasOp<T, FAS_EXP>{c, G});
 }
 
 }  // namespace
@@ -464,63 +308,46 @@ template <typename T>
 int launch_fas_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, const T *u, const T *b, T *r, double *partials,
                         int cap, bool plain)
 {
-    if (fas_march_takes<T>(g, plain)) {
-        const FasMarchGrid m = fas_march_grid<T>(g);
+    if (march_takes<T>(g, plain)) {
+        const MarchGrid m = march_grid<T>(g);
         if (m.grid <= cap) {
-            const dim3 gr(m.grid), bl(64 * FBW);
-#define MG_FAS(KIND, SAVE) hipLaunchKernelGGL((k_fas_march<T, KIND, FAS_RES, SAVE>), gr, bl, 0, s, g, c, G, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc)
+            const dim3 gr(m.grid), bl(64 * MBW);
+#define MG_FAS(KIND, SAVE) hipLaunchKernelGGL((k_fas_march<T, KIND, OP_RES, SAVE>), gr, bl, 0, s, g, c, G, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc)
             if (kind == FAS_CUBIC) { if (r) MG_FAS(FAS_CUBIC, true); else MG_FAS(FAS_CUBIC, false); }
             else { if (r) MG_FAS(FAS_EXP, true); else MG_FAS(FAS_EXP, false); }
 #undef MG_FAS
             return m.grid;
         }
     }
-    const int nb = fas_plain_grid((long long)g.nx * g.ny * g.nz, cap);
-    const dim3 gr(nb), bl(FAS_THREADS);
-#define MG_FAS(DIM, KIND, SAVE) hipLaunchKernelGGL((k_fas_plain<T, DIM, KIND, FAS_RES, SAVE>), gr, bl, 0, s, g, c, G, (T)1, 0, u, b, r, partials)
-#define MG_FAS_K(DIM) \
-    if (kind == FAS_CUBIC) { if (r) MG_FAS(DIM, FAS_CUBIC, true); else MG_FAS(DIM, FAS_CUBIC, false); } \
-    else { if (r) MG_FAS(DIM, FAS_EXP, true); else MG_FAS(DIM, FAS_EXP, false); }
-    if (g.dim == 3) { MG_FAS_K(3) } else { MG_FAS_K(2) }
-#undef MG_FAS_K
-#undef MG_FAS
-    return nb;
+    return with_fas_op(kind, c, G, [&](auto op) { return plain_residual(s, g, op, u, b, r, partials, cap); });
 }
 
 template <typename T>
 void launch_fas_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, const T *u, const T *b, T *out, bool plain)
 {
-    if (fas_march_takes<T>(g, plain)) {
-        const FasMarchGrid m = fas_march_grid<T>(g);
-        const dim3 gr(m.grid), bl(64 * FBW);
+    if (march_takes<T>(g, plain)) {
+        const MarchGrid m = march_grid<T>(g);
+        const dim3 gr(m.grid), bl(64 * MBW);
         if (kind == FAS_CUBIC)
-            hipLaunchKernelGGL((k_fas_march<T, FAS_CUBIC, FAS_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+            hipLaunchKernelGGL((k_fas_march<T, FAS_CUBIC, OP_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
         else
-            hipLaunchKernelGGL((k_fas_march<T, FAS_EXP, FAS_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+            hipLaunchKernelGGL((k_fas_march<T, FAS_EXP, OP_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
         return;
     }
-    const dim3 gr(fas_plain_grid((long long)g.nx * g.ny * g.nz, FAS_MAX_BLOCKS)), bl(FAS_THREADS);
-#define MG_FAS(DIM, KIND) hipLaunchKernelGGL((k_fas_plain<T, DIM, KIND, FAS_JAC, false>), gr, bl, 0, s, g, c, G, omega, 0, u, b, out, (double *)nullptr)
-    if (g.dim == 3) { if (kind == FAS_CUBIC) MG_FAS(3, FAS_CUBIC); else MG_FAS(3, FAS_EXP); }
-    else { if (kind == FAS_CUBIC) MG_FAS(2, FAS_CUBIC); else MG_FAS(2, FAS_EXP); }
-#undef MG_FAS
+    with_fas_op(kind, c, G, [&](auto op) { plain_jacobi(s, g, op, omega, u, b, out); });
 }
 
 template <typename T>
 void launch_fas_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int colour, T *u, const T *b)
 {
-    const dim3 gr(fas_plain_grid((long long)((g.nx + 1) / 2) * g.ny * g.nz, FAS_MAX_BLOCKS)), bl(FAS_THREADS);
-#define MG_FAS(DIM, KIND) hipLaunchKernelGGL((k_fas_plain<T, DIM, KIND, FAS_RB, false>), gr, bl, 0, s, g, c, G, (T)1, colour, u, b, u, (double *)nullptr)
-    if (g.dim == 3) { if (kind == FAS_CUBIC) MG_FAS(3, FAS_CUBIC); else MG_FAS(3, FAS_EXP); }
-    else { if (kind == FAS_CUBIC) MG_FAS(2, FAS_CUBIC); else MG_FAS(2, FAS_EXP); }
-#undef MG_FAS
+    with_fas_op(kind, c, G, [&](auto op) { plain_rb_colour(s, g, op, colour, u, b); });
 }
 
 template <typename T>
 void launch_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const Coef<T> &cc, int kind, T G, bool inject, const T *uf,
                            const T *rf, T *uc, T *ec, T *rhsc)
 {
-    const dim3 gr(fas_plain_grid((long long)gc.nx * gc.ny * gc.nz, FAS_MAX_BLOCKS)), bl(FAS_THREADS);
+    const dim3 gr(plain_grid((long long)gc.nx * gc.ny * gc.nz, OP_MAX_BLOCKS)), bl(OP_THREADS);
     const int inj = inject ? 1 : 0;
 #define MG_FAS(DIM, WZ, KIND) hipLaunchKernelGGL((k_fas_coarse_rhs<T, DIM, WZ, KIND>), gr, bl, 0, s, gf, gc, cc, G, inj, uf, rf, uc, ec, rhsc)
 #define MG_FAS_K(DIM, WZ) if (kind == FAS_CUBIC) MG_FAS(DIM, WZ, FAS_CUBIC); else MG_FAS(DIM, WZ, FAS_EXP);
@@ -534,18 +361,15 @@ void launch_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const 
 template <typename T>
 void launch_fas_diff(hipStream_t s, const Geom &g, const T *x, T *e)
 {
-    const int nb = fas_plain_grid((long long)g.nx * g.ny * g.nz, FAS_MAX_BLOCKS);
-    hipLaunchKernelGGL((k_fas_diff<T>), dim3(nb), dim3(FAS_THREADS), 0, s, g, x, e);
+    const int nb = plain_grid((long long)g.nx * g.ny * g.nz, OP_MAX_BLOCKS);
+    hipLaunchKernelGGL((k_fas_diff<T>), dim3(nb), dim3(OP_THREADS), 0, s, g, x, e);
 }
 
 template <typename T>
 void launch_fas_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, int smoother, T *x, T *tmp, const T *rhs,
                        int maxit, double tol, int fixed, CoarseOut *d_out)
 {
-#define MG_FAS(DIM, KIND) hipLaunchKernelGGL((k_fas_coarse<T, DIM, KIND>), dim3(1), dim3(SWG), 0, s, g, c, G, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out)
-    if (g.dim == 3) { if (kind == FAS_CUBIC) MG_FAS(3, FAS_CUBIC); else MG_FAS(3, FAS_EXP); }
-    else { if (kind == FAS_CUBIC) MG_FAS(2, FAS_CUBIC); else MG_FAS(2, FAS_EXP); }
-#undef MG_FAS
+    with_fas_op(kind, c, G, [&](auto op) { coarse_solve(s, g, op, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out); });
 }
 
 #define MG_FAS_INST(T)                                                                                                                    \

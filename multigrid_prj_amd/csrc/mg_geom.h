@@ -292,41 +292,21 @@ inline int subcycle_default_root(int levels, const int *nx, const int *ny, const
     return finest + 1 <= levels - 2 ? finest + 1 : finest;
 }
 
-// ---- which level-0 shapes the marching tile of mg_o4.hip takes (launch_o4_*); the plain form takes every other one ----
+// ---- which shapes the marching tiles take; the plain forms take every other one ----
 // 3-D, and a row holds at least 16 full 16-byte vectors: with fewer, three quarters of a wave's 64 lanes own no node and
-// the one-thread-per-node form has more of the chip at work. Pure; tests/test_o4_cpu.py pins it.
-inline bool o4_march_ok(int dim, int nx, int ny, int nz, int elem_size)
+// the one-thread-per-node form has more of the chip at work. One rule for the four files that have such a tile: level 0 of
+// mg_o4.hip (launch_o4_*, radius 2), and the residual and the Jacobi sweep of mg_vc.hip (two marched fields), mg_bc.hip and
+// mg_fas.hip (one) on every level, where every red-black colour pass and every transfer is plain too. Pure; each name is
+// pinned by its family's tests/test_{o4,vc,bc,fas}_cpu.py.
+inline bool march_ok(int dim, int nx, int ny, int nz, int elem_size)
 {
     const int v = 16 / elem_size;
     return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
 }
-
-// ---- which levels the marching tile of mg_vc.hip takes (residual and Jacobi sweep of mg_vc_*); the plain form takes every
-// other one, and every red-black colour pass. The shape test of o4_march_ok: the tile is the same one with radius 1, and a
-// row with fewer than 16 full vectors leaves three quarters of a wave idle. Pure; tests/test_vc_cpu.py pins it.
-inline bool vc_march_ok(int dim, int nx, int ny, int nz, int elem_size)
-{
-    const int v = 16 / elem_size;
-    return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
-}
-
-// ---- which levels the marching tile of mg_bc.hip takes (residual and Jacobi sweep of mg_bc_*); the plain form takes every
-// other one, every red-black colour pass and the restriction. vc_march_ok's shape rule: the same tile with one marched
-// field instead of two. Pure; tests/test_bc_cpu.py pins it.
-inline bool bc_march_ok(int dim, int nx, int ny, int nz, int elem_size)
-{
-    const int v = 16 / elem_size;
-    return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
-}
-
-// ---- which levels the marching tile of mg_fas.hip takes (residual and Jacobi sweep of mg_fas_*); the plain form takes every
-// other one, every red-black colour pass and the FAS transition. bc_march_ok's shape rule: the same tile, the reaction term
-// on the centre value. Pure; tests/test_fas_cpu.py pins it.
-inline bool fas_march_ok(int dim, int nx, int ny, int nz, int elem_size)
-{
-    const int v = 16 / elem_size;
-    return dim == 3 && nx / v >= 16 && ny >= 7 && nz >= 7;
-}
+inline bool o4_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return march_ok(dim, nx, ny, nz, elem_size); }
+inline bool vc_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return march_ok(dim, nx, ny, nz, elem_size); }
+inline bool bc_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return march_ok(dim, nx, ny, nz, elem_size); }
+inline bool fas_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return march_ok(dim, nx, ny, nz, elem_size); }
 
 struct CoarseOut {
     int iters;

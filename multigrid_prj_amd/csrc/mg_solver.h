@@ -271,9 +271,13 @@ private:
     // this way keep their ghost planes and padding columns zero: nothing writes them afterwards.
     int alloc_zeroed(void **p, size_t nbytes);
     template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
+    // pcg_t's and vc_pcg_t's iteration; the two callables are the operator's residual with its sum and its direction kernel
+    template <typename T, class ResidualSum, class DirectionApply>
+    int pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply direction_apply, double tol, int maxit, double *hist, int hist_cap,
+                   int *n_hist, mg_krylov_stats *st);
     // *z = M r: one mg_solve outer iteration from zero with the buffers *z and r in level 0's U / RHS slots. The cycle may leave
     // its result in the buffer that was TMP: *z is whatever U points at afterwards, and TMP keeps the other buffer.
-    // vc: the cycle is vc_cycle_enqueue's (mg_vc_pcg_solve) and no Gauss-Seidel sweeps come before it
+    // vc: the cycle is mg_vc_cycle's (mg_vc_pcg_solve) and no Gauss-Seidel sweeps come before it
     int precondition(void **z, void *r, bool vc = false);
     template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
@@ -330,9 +334,8 @@ private:
         SC_CG_DOT1 = 4,
         SC_MX_SUM = 5,    // d_mx_sum_: mixed_solve, mixed_kernel
         SC_O4_SUM = 6,    // sum r^2 of the fourth-order residual: o4_solve, o4_residual, o4_correct_residual (written on the device)
-        SC_VC_SUM = 7,    // sum r^2 of the variable-coefficient residual: vc_residual, vc_solve, vc_pcg_solve (written on the device)
-        SC_BC_SUM = SC_VC_SUM,   // mg_bc_*: sum r^2 or sum w v; shares the slot (every call fetches its sum before another family runs)
-        SC_FAS_SUM = SC_VC_SUM,  // mg_fas_*: sum r^2; shares the slot in the same way
+        SC_FAM_SUM = 7,   // mg_vc_*, mg_bc_*, mg_fas_*: sum r^2 of the family's residual, or bc_project's sum w v (written on the
+                          // device; every call fetches its sum before another family runs)
         SC_COUNT = 8      // the eight slots: one 64-byte line
     };
     double *d_scal_ = nullptr;      // [SC_COUNT]
@@ -390,51 +393,49 @@ private:
     template <typename T> int heat_step_t(double dt, double theta, int nsteps, int cycles_per_step);
     void *heat_f_ = nullptr;
     bool heat_has_f_ = false;
+    // ---- operator families (mg_vc_*, mg_bc_*, mg_fas_*): one driver skeleton, the fam_* templates, over a policy F<T> per
+    // family (defined in mg_drivers.cpp) that supplies what differs: the residual / Jacobi / red-black colour / coarse launches
+    // with the family's plain flag, the precondition of the check, and the cycle's hooks on the way down and up
+    template <typename T> struct VcFam;
+    template <typename T> struct BcFam;
+    template <typename T> struct FasFam;
+    enum : unsigned { FAM_NEED_CYCLE = 1u, FAM_NEED_SMOOTHER = 2u };   // what fam_check asks of the descriptor beyond F's own precondition
+    template <template <typename> class F> int fam_check(const char *fn, unsigned need);   // driver_begin, F::ready, the cycle / smoother the family drivers run
+    int set_form(const char *fn, int form, bool *plain);   // mg_*_set_form
+    template <class F> int fam_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_FAM_SUM]
+    template <class F> int fam_residual_sum_t(int level, int ax, int ar, int arr_r, double *sumsq_r);   // ... and fetched: synchronises
+    template <class F> int fam_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
+    template <class F> int fam_coarse_t(int level, int ax, int ar);
+    template <class F> int fam_cycle_rec_t(int l, int kind);
+    template <class F> int fam_cycle_enqueue_t();
+    template <class F> int fam_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);   // vc, bc
+    template <template <typename> class F> int fam_cycle_enqueue();   // by the handle's dtype
+    // the public mg_<family>_<fn>: fam_check, the argument checks (messages start with fn), then the template by dtype
+    template <template <typename> class F> int fam_residual(const char *fn, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
+    template <template <typename> class F> int fam_smooth(const char *fn, int level, int smoother, int sweeps, int arr_x, int arr_rhs);
+    template <template <typename> class F> int fam_coarse_solve(const char *fn, int level, int arr_x, int arr_rhs, mg_cycle_stats *st);
+    template <template <typename> class F> int fam_cycle(const char *fn, mg_cycle_stats *st);
+    template <template <typename> class F>
+    int fam_solve(const char *fn, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     // variable-coefficient drivers (mg_vc_*): Level::vc_a of every level, valid once vc_set_ is true
     bool vc_set_ = false, vc_plain_ = false;
-    enum : unsigned { VC_NEED_CYCLE = 1u, VC_NEED_SMOOTHER = 2u };   // what vc_check asks of the descriptor beyond a coefficient
-    int vc_check(const char *fn, unsigned need);   // driver_begin, a coefficient is set, the cycle / smoother the vc drivers run
     int vc_alloc();
     template <typename T> T *vcptr(int level) const { return reinterpret_cast<T *>(lv_[level].vc_a) + lv_[level].gh * lv_[level].g.plane; }
     template <typename T> int vc_restrict_all_t();   // vc_a(l + 1) = full weighting of vc_a(l), every transition
-    template <typename T> int vc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_VC_SUM]
-    template <typename T> int vc_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
-    template <typename T> int vc_coarse_t(int level, int ax, int ar);
-    template <typename T> int vc_cycle_rec_t(int l, int kind);
-    template <typename T> int vc_cycle_enqueue_t();
-    int vc_cycle_enqueue();
-    template <typename T> int vc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     template <typename T> int vc_direction_t(double beta, const int *arrs, double *pq);
     template <typename T> int vc_pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     // Neumann-face drivers (mg_bc_*): the mask of Neumann faces, 0 = all Dirichlet
     int bc_mask_ = 0;
     bool bc_plain_ = false;
-    enum : unsigned { BC_NEED_CYCLE = 1u, BC_NEED_SMOOTHER = 2u };   // what bc_check asks of the descriptor
-    int bc_check(const char *fn, unsigned need);   // driver_begin, the cycle / smoother the bc drivers run
     bool bc_singular() const { return bc_mask_ == (d_.dim == 3 ? 63 : 15) && shift_ == 0.0; }   // all faces Neumann, no shift: constants are the null space
-    template <typename T> int bc_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_BC_SUM]
-    template <typename T> int bc_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
     template <typename T> int bc_restrict_t(int fl, int kind, int as, int ad);
-    template <typename T> int bc_coarse_t(int level, int ax, int ar);
     template <typename T> int bc_project_t(int level, int arr, double *mean);   // synchronises: the mean is fetched
-    template <typename T> int bc_cycle_rec_t(int l, int kind);
-    template <typename T> int bc_cycle_enqueue_t();
-    int bc_cycle_enqueue();
-    template <typename T> int bc_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     // full-approximation-scheme drivers (mg_fas_*): the reaction gamma g(u), g of enum mg_fas_kind
     int fas_kind_ = MG_FAS_CUBIC;
     double fas_gamma_ = 0.0;
     bool fas_plain_ = false;
-    enum : unsigned { FAS_NEED_CYCLE = 1u, FAS_NEED_SMOOTHER = 2u };   // what fas_check asks of the descriptor
-    int fas_check(const char *fn, unsigned need);   // driver_begin, the cycle / smoother the fas drivers run
-    template <typename T> int fas_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_FAS_SUM]
-    template <typename T> int fas_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
     template <typename T> int fas_coarse_rhs_t(int fl);
     template <typename T> int fas_correct_t(int fl);
-    template <typename T> int fas_coarse_t(int level, int ax, int ar);
-    template <typename T> int fas_cycle_rec_t(int l, int kind);
-    template <typename T> int fas_cycle_enqueue_t();
-    int fas_cycle_enqueue();
     template <typename T> int fas_solve_t(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st);
     // block of eig_solve: eig_[family][column] (enum mg_eig_family), level-0-shaped; the per-workgroup partial sums of up to
     // EIG_MAX_LAUNCHES Gram tiles, their totals, the coefficients of the combine (device) and a pinned mirror of the last two

@@ -291,6 +291,36 @@ def test_one_cycle_against_long_double(n, levels, kind, dtype):
         assert st.coarse_iters == visits * kw["coarse_maxit"] and st.coarse_flag == 0
 
 
+@DTYPES
+@pytest.mark.parametrize("smoother,omega", [(JAC, 6.0 / 7.0), (RB, 1.0)], ids=["jacobi67", "rb"])
+def test_big_coarsest_level_is_smoothed_chip_wide(smoother, omega, dtype):
+    """n = 65 on 2 levels: the coarsest level has 33^3 = 35937 > 32768 nodes, too many for the one-workgroup coarse kernel, so
+    with MG_COARSE_FIXED the cycle runs coarse_maxit chip-wide sweeps there. One mg_vc_cycle equals, bit for bit, the same
+    steps made through the public entry points on a second handle, and the statistics report the fixed sweeps."""
+    T = NP[dtype]
+    kw = desc_kw(3, 65, 2, {}, dtype, smoother=smoother, omega=omega, coarse_maxit=3)
+    rng = np.random.default_rng(65)
+    with capi.Solver(capi.make_desc(**kw)) as s, capi.Solver(capi.make_desc(**kw)) as m:
+        shape = s.level_shape(0)
+        assert int(np.prod(s.level_shape(1))) == 33 ** 3 > 32768
+        a0, u0, b = random_a(shape, 11).astype(T), rng.standard_normal(shape).astype(T), rng.standard_normal(shape).astype(T)
+        for h in (s, m):
+            h.vc_set_coefficient(a0); h.set_solution(u0); h.set_rhs(b)
+        st = s.vc_cycle()
+        m.vc_smooth(0, smoother, kw["nu_pre"], U, RHS)
+        m.vc_residual(0, U, RHS, TMP)
+        m.restrict(0, kw["restriction"], TMP, RHS)
+        m.zero_array(U, 1)
+        m.vc_smooth(1, smoother, kw["coarse_maxit"], U, RHS)
+        m.prolong(1, True, U, U)
+        m.vc_smooth(0, smoother, kw["nu_post"], U, RHS)
+        got, want = s.get_solution(), m.get_solution()
+        assert np.isfinite(want).all() and not np.array_equal(want, u0)
+        assert np.array_equal(got, want), int((got != want).sum())
+        assert np.array_equal(s.get_array(U, 1), m.get_array(U, 1)) and np.array_equal(s.get_array(RHS, 0), b)
+        assert (st.coarse_iters, st.coarse_flag) == (3, 0)
+
+
 # ---------------------------------------------------------------- 6. / 7. convergence (fp64, n = 33, 5 levels, red-black V(2,2), 50 coarse sweeps)
 CONV = dict(dim=3, n=33, levels=5, length=1.0, alpha=1.0, dtype=capi.MG_F64, cycle=capi.CYCLE_V, smoother=RB, nu_pre=2, nu_post=2,
             restriction=capi.RESTRICT_FULLW, outer_pre_gs=0, coarse_mode=capi.COARSE_FIXED, coarse_maxit=50)
