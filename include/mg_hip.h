@@ -626,6 +626,44 @@ typedef struct mg_heat_stats {
 int mg_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
 int mg_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst);
 
+/* ---- implicit time steps on the operator families (extension) ----
+ * mg_vc_heat_*, mg_bc_heat_* and mg_fas_heat_* are mg_heat_step / mg_heat_rhs for u_t = -N0(u) + f, with N0 the family's
+ * operator on level 0 WITHOUT the handle's shift:
+ *   vc    N0(u) = -div(a grad u)          (a of mg_vc_set_coefficient; Dirichlet nodes: the box boundary)
+ *   bc    N0(u) = A0 u with mirrored neighbours at the unknowns on the faces of the mask (mg_bc_set_faces; Dirichlet nodes:
+ *                 the nodes on a face that is NOT in the mask)
+ *   fas   N0(u) = A0 u + gamma g(u)       (mg_fas_set_reaction; Dirichlet nodes: the box boundary)
+ * f is the source of mg_heat_set_source[_device]: a handle holds ONE source, shared by mg_heat_step and these three
+ * steppers. One theta step solves, on the unknowns,
+ *     (1/(theta dt)) u' + N0(u') = (f + u/dt - (1 - theta) N0(u)) / theta
+ * which holds for the nonlinear N0 as it stands (theta = 1: backward Euler, 1/2: the trapezoidal rule).
+ * mg_X_heat_step(h, dt, theta, nsteps, cycles_per_step, st) is mg_heat_step with step 2's launch replaced by the family's
+ * right-hand side launch and its outer iteration by ONE mg_X_cycle (warm-started from u; desc.outer_pre_gs is ignored, as
+ * in mg_X_solve): mg_set_shift(h, 1.0 / (theta * dt)) first, which STAYS set; no host synchronisation between the steps;
+ * at the end one mg_X_residual norm and one sum of squares, st->relres = ||rhs - (sigma I + N0)(u')|| / ||rhs|| of the
+ * LAST step (0 when the numerator is 0). bc with every face Neumann is not singular here (sigma > 0): nothing is projected.
+ * mg_X_heat_rhs(h, dt, theta, arr_u, arr_dst) is the assembly launch alone: arr_dst(0) = the step's right-hand side from
+ * arr_u(0) in ONE launch, with the UNSHIFTED operator whatever the handle's shift is; arr_u and the shift are not touched.
+ * mg_set_shift(h, 1/(theta dt)) + mg_X_heat_rhs + mg_X_solve is a step solved to a tolerance.
+ * Arithmetic, in the working dtype T, every operation rounded separately, rdt / omt / rth as for mg_heat_rhs:
+ *   rhs = ((f + rdt*u) - omt*n0) * rth     unknowns;  without a source (rdt*u - omt*n0) * rth
+ *   rhs = u                                Dirichlet nodes, bit for bit
+ *   n0  = the family's residual expression with the shift taken out: vc d*u_i - s with d started from (T)0; bc the sum of
+ *         mg_bc_residual with the unshifted diagonal cd0; fas that sum + G*g(u) (see the families' contracts above).
+ * theta == 1 loads no neighbour: rhs = f + rdt*u on the unknowns, the general expression's value for finite data. For
+ * finite data mg_bc_heat_rhs with mask 0, mg_fas_heat_rhs with gamma 0 and, with theta == 1, mg_vc_heat_rhs and
+ * mg_fas_heat_rhs give mg_heat_rhs's bits. mg_X_set_form(1) selects the plain kernel here too.
+ * MG_ERR_BAD_ARG, with U, RHS and the shift untouched: what mg_heat_step / mg_heat_rhs refuse (same messages, with the
+ * function's name), and what mg_X_cycle refuses (step) or mg_X_residual refuses of the handle (rhs): a sawtooth handle, a
+ * smoother other than Jacobi or red-black, a stage callback, distributed handles, vc without a coefficient. Nothing is
+ * allocated, and no other entry point changes behaviour. */
+int mg_vc_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst);
+int mg_bc_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst);
+int mg_fas_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst);
+int mg_vc_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
+int mg_bc_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
+int mg_fas_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
+
 /* ---- lowest eigenpairs by multigrid-preconditioned LOBPCG ----
  * mg_eig_solve finds the nev smallest eigenpairs of sigma I + A on the interior nodes of level 0, (sigma I + A) x =
  * lambda x with x = 0 on Dirichlet nodes -- the operator of mg_level_coefficients(h, 0): aniso, the current shift

@@ -169,6 +169,7 @@ EXPORTS = [
     "mg_fas_set_reaction", "mg_fas_get_reaction", "mg_fas_set_form", "mg_fas_residual", "mg_fas_smooth", "mg_fas_coarse_rhs", "mg_fas_correct",
     "mg_fas_coarse_solve", "mg_fas_cycle", "mg_fas_solve",
     "mg_set_shift", "mg_get_shift", "mg_heat_set_source", "mg_heat_set_source_device", "mg_heat_step", "mg_heat_rhs",
+    "mg_vc_heat_rhs", "mg_bc_heat_rhs", "mg_fas_heat_rhs", "mg_vc_heat_step", "mg_bc_heat_step", "mg_fas_heat_step",
     "mg_eig_solve", "mg_eig_set_vector", "mg_eig_get_vector", "mg_eig_set_vector_device", "mg_eig_get_vector_device",
     "mg_eig_block", "mg_eig_kernel",
     "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
@@ -271,6 +272,9 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_heat_set_source_device.argtypes = [vp, vp, i, vp]
     L.mg_heat_step.argtypes = [vp, C.c_double, C.c_double, i, i, C.POINTER(MgHeatStats)]
     L.mg_heat_rhs.argtypes = [vp, C.c_double, C.c_double, i, i]
+    for fam in ("vc", "bc", "fas"):
+        getattr(L, f"mg_{fam}_heat_rhs").argtypes = [vp, C.c_double, C.c_double, i, i]
+        getattr(L, f"mg_{fam}_heat_step").argtypes = [vp, C.c_double, C.c_double, i, i, C.POINTER(MgHeatStats)]
     L.mg_eig_solve.argtypes = [vp, i, i, C.c_double, i, dp, dp, dp, i, C.POINTER(i), C.POINTER(MgEigStats)]
     L.mg_eig_set_vector.argtypes = [vp, i, i, vp]
     L.mg_eig_get_vector.argtypes = [vp, i, i, vp]
@@ -752,6 +756,36 @@ class Solver:
     def heat_rhs(self, dt, theta, arr_u=ARR_U, arr_dst=ARR_RHS):
         """mg_heat_rhs: arr_dst(0) = the right-hand side of one theta-scheme step built from arr_u(0)"""
         _check(self.lib.mg_heat_rhs(self.h, dt, theta, arr_u, arr_dst))
+
+    # -- the same steps of u_t = -N0(u) + f on a family's operator (N0 without the shift; f: the handle's one source)
+    def _fam_heat_step(self, fam, dt, theta, nsteps, cycles_per_step) -> MgHeatStats:
+        st = MgHeatStats()
+        _check(getattr(self.lib, f"mg_{fam}_heat_step")(self.h, dt, theta, nsteps, cycles_per_step, C.byref(st)))
+        return st
+
+    def vc_heat_step(self, dt, theta=1.0, nsteps=1, cycles_per_step=1) -> MgHeatStats:
+        """mg_vc_heat_step: mg_heat_step for u_t = div(a grad u) + f with mg_vc_cycle as the step's cycle"""
+        return self._fam_heat_step("vc", dt, theta, nsteps, cycles_per_step)
+
+    def bc_heat_step(self, dt, theta=1.0, nsteps=1, cycles_per_step=1) -> MgHeatStats:
+        """mg_bc_heat_step: mg_heat_step with zero-flux walls on the faces of the mask, mg_bc_cycle as the step's cycle"""
+        return self._fam_heat_step("bc", dt, theta, nsteps, cycles_per_step)
+
+    def fas_heat_step(self, dt, theta=1.0, nsteps=1, cycles_per_step=1) -> MgHeatStats:
+        """mg_fas_heat_step: mg_heat_step for u_t = -(A0 u + gamma g(u)) + f with mg_fas_cycle as the step's cycle"""
+        return self._fam_heat_step("fas", dt, theta, nsteps, cycles_per_step)
+
+    def vc_heat_rhs(self, dt, theta, arr_u=ARR_U, arr_dst=ARR_RHS):
+        """mg_vc_heat_rhs: arr_dst(0) = the right-hand side of one theta step of the unshifted vc operator from arr_u(0)"""
+        _check(self.lib.mg_vc_heat_rhs(self.h, dt, theta, arr_u, arr_dst))
+
+    def bc_heat_rhs(self, dt, theta, arr_u=ARR_U, arr_dst=ARR_RHS):
+        """mg_bc_heat_rhs: the same with the Neumann faces of the mask; Dirichlet nodes take u"""
+        _check(self.lib.mg_bc_heat_rhs(self.h, dt, theta, arr_u, arr_dst))
+
+    def fas_heat_rhs(self, dt, theta, arr_u=ARR_U, arr_dst=ARR_RHS):
+        """mg_fas_heat_rhs: the same with N0(u) = A0 u + gamma g(u)"""
+        _check(self.lib.mg_fas_heat_rhs(self.h, dt, theta, arr_u, arr_dst))
 
     # -- lowest eigenpairs of sigma I + A on level 0 (multigrid-preconditioned LOBPCG)
     def eig_solve(self, m, nev=None, tol=1e-8, maxit=200):

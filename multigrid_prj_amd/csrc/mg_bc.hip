@@ -9,8 +9,9 @@
 //                                  plain form (residual / Jacobi sweep / one red-black colour pass, every shape) and the
 //                                  coarsest-grid solve are mg_opfamily.h's k_op_plain<BcOp<T>, DIM, OP, SAVE> and
 //                                  k_op_coarse<BcOp<T>, DIM>
-//   k_bc_march<T, OP, SAVE>        the residual and the Jacobi sweep on 3-D levels with rows long enough to fill a wave
-//                                  (bc_march_ok, mg_geom.h)
+//   k_bc_march<T, OP, SAVE, SRC, NB>   the residual, the Jacobi sweep and the right-hand side of a theta step (OP_STEP, with or
+//                                  without a source, with the stencil or -- theta == 1 -- without a neighbour loaded:
+//                                  mg_bc_heat_rhs) on 3-D levels with rows long enough to fill a wave (bc_march_ok, mg_geom.h)
 //   k_bc_restrict<T, DIM, WZ>      full weighting with mirrored fine neighbours, coarse Dirichlet nodes injected
 //   k_bc_wsum<T> / k_bc_shift<T>   sum of w v (w = 1/2 per Neumann face the node lies on) / v -= c on every node
 //   k_bc_dirichlet_copy<T>         x = rhs on the Dirichlet nodes
@@ -33,6 +34,8 @@
 //   point solve  the same sum without the diagonal term (offdiag_sum's order), ps = (b - sum) / cd (div_cd: the IEEE quotient)
 //   Jacobi       u' = ps (omega == 1) or u_i + omega * (ps - u_i); Dirichlet nodes: u' = b
 //   red-black    in place, colour (i + j + gz) & 1, colour 0 first; Dirichlet nodes take b with their colour
+//   step         n0 = the residual's sum with the UNSHIFTED diagonal cd0; rhs = ((f + rdt*u_i) - omt*n0) * rth, without a source
+//                (rdt*u_i - omt*n0) * rth; Dirichlet nodes: rhs = u_i (step_value, mg_opfamily.h; tests/step_ref.py)
 //   restriction  restrict_fw_point's expression (x, then y inside the z planes, weights q, hlf, q) with fine indices outside
 //                the grid mirrored; coarse Dirichlet nodes injected
 // With mask 0 every one of these is the existing kernel's expression: the results are the same bits.
@@ -114,7 +117,30 @@ __device__ __forceinline__ T bc_point_solve(const Geom &g, const Coef<T> &c, int
     return ps;
 }
 
-// the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h). The two point functions stay free
+// the operator's value at node (z, y, x) into v -- bc_point_res's sum, c.cd = cd0: the unshifted operator of the time
+// steppers; stencil == false: v is left alone and no neighbour is loaded -> true at a Dirichlet node
+template <typename T, int DIM>
+__device__ __forceinline__ bool bc_point_n0(const Geom &g, const Coef<T> &c, int mask, const T *u, int z, int y, int x, bool stencil, T &v)
+{
+    const int f = bc_faces(g, z, y, x);
+    if (f & ~mask) return true;
+    if (stencil) {
+        const long long i = lidx(g, z, y, x);
+        const BcNb n = bc_neighbours(g, i, f);
+        T sum = 0;
+        if (DIM == 3) sum += c.cz * u[n.zm];
+        sum += c.cy * u[n.ym];
+        sum += c.cx * u[n.xm];
+        sum += c.cd * u[i];
+        sum += c.cx * u[n.xp];
+        sum += c.cy * u[n.yp];
+        if (DIM == 3) sum += c.cz * u[n.zp];
+        v = sum;
+    }
+    return false;
+}
+
+// the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h). The point functions stay free
 // functions because the marching tile calls them too, for the odd last column.
 template <typename T>
 struct BcOp {
@@ -133,16 +159,25 @@ struct BcOp {
     {
         return bc_point_solve<T, DIM>(g, c, mask, omega, damped, u, b, z, y, x);
     }
+
+    template <int DIM>
+    __device__ __forceinline__ bool n0(const Geom &g, const T *u, int z, int y, int x, bool stencil, T &v) const
+    {
+        return bc_point_n0<T, DIM>(g, c, mask, u, z, y, x, stencil, v);
+    }
 };
 
 // ---------------------------------------------------------------- the marching tile (3-D)
-template <typename T, int OP, bool SAVE>
+// OP_STEP: b is the source of the step (not loaded without SRC), st its scalars, c.cd = cd0; out = u on Dirichlet nodes.
+// NB == false (theta == 1, where the operator's value is multiplied by zero): u is streamed through, no neighbour is loaded
+template <typename T, int OP, bool SAVE, bool SRC = true, bool NB = true>
 __global__ __launch_bounds__(64 * MBW) void k_bc_march(Geom g, Coef<T> c, int mask, T omega, const T *__restrict__ u,
                                                        const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
-                                                       int nbx, int nby, int nbz, int zc)
+                                                       int nbx, int nby, int nbz, int zc, StepCoef<T> st)
 {
     constexpr int V = Vec16<T>::n;
-    constexpr bool STORE = OP == OP_JAC || SAVE;
+    constexpr bool STORE = OP != OP_RES || SAVE;
+    constexpr bool LOADB = OP != OP_STEP || SRC;
     typedef typename Vec16<T>::type vec;
     __shared__ double sh[MBW];
 
@@ -186,8 +221,8 @@ __global__ __launch_bounds__(64 * MBW) void k_bc_march(Geom g, Coef<T> c, int ma
     const T *pu = u + (long long)z0 * g.plane;
 #pragma unroll
     for (int r = 0; r < MRY; r++) {
-        uzm[r] = *(const vec *)(pu - g.plane + rowoff[r]);
-        ucc[r] = *(const vec *)(pu + rowoff[r]);
+        uzm[r] = NB ? *(const vec *)(pu - g.plane + rowoff[r]) : (vec)(0);
+        ucc[r] = NB ? *(const vec *)(pu + rowoff[r]) : (vec)(0);
     }
     double acc = 0.;
     for (int z = z0; z < zend; z++, pu += g.plane) {
@@ -195,17 +230,18 @@ __global__ __launch_bounds__(64 * MBW) void k_bc_march(Geom g, Coef<T> c, int ma
         vec bv[MRY];
 #pragma unroll
         for (int r = 0; r < MRY; r++) {
-            uzp[r] = *(const vec *)(pu + g.plane + rowoff[r]);
-            bv[r] = __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r]));
+            if (NB) uzp[r] = *(const vec *)(pu + g.plane + rowoff[r]);
+            else ucc[r] = uzp[r] = __builtin_nontemporal_load((const vec *)(pu + rowoff[r]));
+            bv[r] = LOADB ? __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r])) : (vec)(0);
         }
-        const vec ulo = *(const vec *)(pu + off_lo), uhi = *(const vec *)(pu + off_hi);
+        const vec ulo = NB ? *(const vec *)(pu + off_lo) : (vec)(0), uhi = NB ? *(const vec *)(pu + off_hi) : (vec)(0);
         const int gz = g.gz0 + z;
         const int zface = (gz == 0 ? FZLO : 0) | (gz == g.gnz - 1 ? FZHI : 0);
 #pragma unroll
         for (int r = 0; r < MRY; r++) {
             T uel = 0, uer = 0;
-            if (edge_l) uel = pu[rowoff[r] - 1];
-            if (edge_r) uer = pu[rowoff[r] + V];
+            if (NB && edge_l) uel = pu[rowoff[r] - 1];
+            if (NB && edge_r) uer = pu[rowoff[r] + V];
             const T uxm = lane_from_prev(ucc[r][V - 1], uel), uxp = lane_from_next(ucc[r][0], uer);
             const vec uym0 = (r > 0) ? ucc[r > 0 ? r - 1 : 0] : ulo, uyp0 = (r < MRY - 1) ? ucc[r < MRY - 1 ? r + 1 : 0] : uhi;
             // the mirror in y and z: values the lane holds anyway
@@ -227,11 +263,12 @@ __global__ __launch_bounds__(64 * MBW) void k_bc_march(Geom g, Coef<T> c, int ma
                 sum += c.cz * uzl[e];
                 sum += c.cy * uym[e];
                 sum += c.cx * ul;
-                if (OP == OP_RES) sum += c.cd * ui;
+                if (OP == OP_RES || OP == OP_STEP) sum += c.cd * ui;
                 sum += c.cx * ur;
                 sum += c.cy * uyp[e];
                 sum += c.cz * uzh[e];
                 if (OP == OP_RES) res[e] = dn[e] ? bi - ui : bi - sum;
+                else if (OP == OP_STEP) res[e] = dn[e] ? ui : step_value<T, SRC>(st, ui, bi, NB ? sum : (T)0);
                 else num[e] = bi - sum;
             }
             if (OP == OP_JAC) {
@@ -271,6 +308,12 @@ __global__ __launch_bounds__(64 * MBW) void k_bc_march(Geom g, Coef<T> c, int ma
                                 const T rt = bc_point_res<T, 3>(g, c, mask, u, b, z, yb + r, g.nx - 1);
                                 acc += (double)rt * (double)rt;
                                 tv[0] = rt;
+                            } else if (OP == OP_STEP) {
+                                const long long it = ro + g.nx - 1;
+                                const T ut = u[it];
+                                T n0 = (T)0;
+                                const bool fixed = bc_point_n0<T, 3>(g, c, mask, u, z, yb + r, g.nx - 1, NB, n0);
+                                tv[0] = fixed ? ut : step_value<T, SRC>(st, ut, SRC ? b[it] : (T)0, n0);
                             } else {
                                 tv[0] = bc_point_solve<T, 3>(g, c, mask, omega, damped, u, b, z, yb + r, g.nx - 1);
                             }
@@ -383,8 +426,8 @@ int launch_bc_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int mask,
         const MarchGrid m = march_grid<T>(g);
         if (m.grid <= cap) {
             const dim3 gr(m.grid), bl(64 * MBW);
-            if (r) hipLaunchKernelGGL((k_bc_march<T, OP_RES, true>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
-            else hipLaunchKernelGGL((k_bc_march<T, OP_RES, false>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
+            if (r) hipLaunchKernelGGL((k_bc_march<T, OP_RES, true>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
+            else hipLaunchKernelGGL((k_bc_march<T, OP_RES, false>), gr, bl, 0, s, g, c, mask, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
             return m.grid;
         }
     }
@@ -397,10 +440,27 @@ void launch_bc_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, 
     if (march_takes<T>(g, plain)) {
         const MarchGrid m = march_grid<T>(g);
         hipLaunchKernelGGL((k_bc_march<T, OP_JAC, false>), dim3(m.grid), dim3(64 * MBW), 0, s, g, c, mask, omega, u, b, out,
-                           (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+                           (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
         return;
     }
     plain_jacobi(s, g, BcOp<T>{c, mask}, omega, u, b, out);
+}
+
+template <typename T>
+void launch_bc_heat_rhs(hipStream_t s, const Geom &g, const Coef<T> &c0, int mask, double dt, double theta, const T *u, const T *f, T *out,
+                        bool plain)
+{
+    const StepCoef<T> st = step_coef<T>(dt, theta);
+    if (march_takes<T>(g, plain)) {
+        const MarchGrid m = march_grid<T>(g);
+        const dim3 gr(m.grid), bl(64 * MBW);
+#define MG_BC(SRC, NB) hipLaunchKernelGGL((k_bc_march<T, OP_STEP, true, SRC, NB>), gr, bl, 0, s, g, c0, mask, (T)1, u, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st)
+        if (theta != 1.0) { if (f) MG_BC(true, true); else MG_BC(false, true); }
+        else { if (f) MG_BC(true, false); else MG_BC(false, false); }
+#undef MG_BC
+        return;
+    }
+    plain_step(s, g, BcOp<T>{c0, mask}, st, u, f, out);
 }
 
 template <typename T>
@@ -450,6 +510,7 @@ void launch_bc_dirichlet_copy(hipStream_t s, const Geom &g, int mask, T *x, cons
 #define MG_BC_INST(T)                                                                                                                   \
     template int launch_bc_residual<T>(hipStream_t, const Geom &, const Coef<T> &, int, const T *, const T *, T *, double *, int, bool); \
     template void launch_bc_jacobi<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, const T *, const T *, T *, bool);             \
+    template void launch_bc_heat_rhs<T>(hipStream_t, const Geom &, const Coef<T> &, int, double, double, const T *, const T *, T *, bool); \
     template void launch_bc_rb_colour<T>(hipStream_t, const Geom &, const Coef<T> &, int, int, T *, const T *);                         \
     template void launch_bc_restrict_fw<T>(hipStream_t, const Geom &, const Geom &, int, const T *, T *);                               \
     template void launch_bc_coarse<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, int, T *, T *, const T *, int, double, int,  \

@@ -398,6 +398,21 @@ int mg_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst)
     MG_H(h);
     return guarded([&] { return h->impl->heat_rhs(dt, theta, arr_u, arr_dst); });
 }
+#define MG_FAM_HEAT(fam)                                                                                                         \
+    int mg_##fam##_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst)                                        \
+    {                                                                                                                            \
+        MG_H(h);                                                                                                                 \
+        return guarded([&] { return h->impl->fam##_heat_rhs(dt, theta, arr_u, arr_dst); });                                      \
+    }                                                                                                                            \
+    int mg_##fam##_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)           \
+    {                                                                                                                            \
+        MG_H(h);                                                                                                                 \
+        return guarded([&] { return h->impl->fam##_heat_step(dt, theta, nsteps, cycles_per_step, st); });                        \
+    }
+MG_FAM_HEAT(vc)
+MG_FAM_HEAT(bc)
+MG_FAM_HEAT(fas)
+#undef MG_FAM_HEAT
 int mg_eig_solve(mg_handle h, int m, int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap,
                  int *n_hist, mg_eig_stats *st)
 {

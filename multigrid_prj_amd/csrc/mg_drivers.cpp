@@ -1135,6 +1135,16 @@ struct Solver::VcFam {
         launch_vc_coarse<T>(s.stream_, L.g, L.coef, s.shift_, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.vcptr<T>(l), s.d_.coarse_maxit,
                             s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
     }
+    static void heat_rhs(Solver &s, double dt, double theta, const T *u, const T *f, T *out)
+    {
+        const Level &L = s.lv_[0];
+        if (theta == 1.0) {   // the operator's value is multiplied by zero: mg_heat.hip's stencil-free form, same Dirichlet nodes
+            const double coef0[4] = {L.coef[0], L.coef[1], L.coef[2], L.cd0};
+            launch_heat_rhs<T>(s.stream_, L.g, coef0, dt, theta, u, f, out);
+            return;
+        }
+        launch_vc_heat_rhs<T>(s.stream_, L.g, L.coef, dt, theta, u, s.vcptr<T>(0), f, out, s.vc_plain_);
+    }
     static int down(Solver &s, int l)
     {
         MG_TRY(s.restrict_t<T>(l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
@@ -1175,6 +1185,11 @@ struct Solver::BcFam {
         const Level &L = s.lv_[l];
         launch_bc_coarse<T>(s.stream_, L.g, coef_of<T>(L), s.bc_mask_, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.d_.coarse_maxit,
                             s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
+    }
+    static void heat_rhs(Solver &s, double dt, double theta, const T *u, const T *f, T *out)
+    {
+        const Level &L = s.lv_[0];   // the mask decides which nodes copy u, so theta == 1 has a form of its own in mg_bc.hip
+        launch_bc_heat_rhs<T>(s.stream_, L.g, coef0_of<T>(L), s.bc_mask_, dt, theta, u, f, out, s.bc_plain_);
     }
     static int down(Solver &s, int l)
     {
@@ -1222,6 +1237,16 @@ struct Solver::FasFam {
         launch_fas_coarse<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, (T)s.d_.omega, s.d_.smoother, x, tmp, b,
                              s.d_.coarse_maxit, s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
     }
+    static void heat_rhs(Solver &s, double dt, double theta, const T *u, const T *f, T *out)
+    {
+        const Level &L = s.lv_[0];
+        if (theta == 1.0) {   // as VcFam::heat_rhs: the reaction is multiplied by zero too
+            const double coef0[4] = {L.coef[0], L.coef[1], L.coef[2], L.cd0};
+            launch_heat_rhs<T>(s.stream_, L.g, coef0, dt, theta, u, f, out);
+            return;
+        }
+        launch_fas_heat_rhs<T>(s.stream_, L.g, coef0_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, dt, theta, u, f, out, s.fas_plain_);
+    }
     static int down(Solver &s, int l) { return s.fas_coarse_rhs_t<T>(l); }   // U(l + 1) = E(l + 1) = the injected iterate, RHS(l + 1)
     static int up(Solver &s, int l) { return s.fas_correct_t<T>(l); }
 };
@@ -1250,13 +1275,13 @@ int Solver::set_form(const char *fn, int form, bool *plain)
 }
 
 template <class F>
-int Solver::fam_residual_t(int level, int ax, int ar, int arr_r, bool want_sum)
+int Solver::fam_residual_t(int level, int ax, int ar, int arr_r, bool want_sum, int slot)
 {
     typedef typename F::type T;
     Level &L = lv_[level];
     if (arr_r == MG_ARR_RHS) L.rhs_halo_ok = false;
     const int np = F::residual(*this, level, ptr<T>(ax, level), ptr<T>(ar, level), arr_r >= 0 ? ptr<T>(arr_r, level) : (T *)nullptr);
-    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_FAM_SUM);
+    if (want_sum) launch_reduce_final(stream_, d_partials_, np, d_scal_ + slot);
     MG_HIP(hipGetLastError());
     return MG_OK;
 }
@@ -1424,6 +1449,80 @@ int Solver::fam_solve(const char *fn, double tol, int maxit, double *hist, int h
     if (maxit < 0) { set_last_error(std::string(fn) + ": negative maxit"); return MG_ERR_BAD_ARG; }
     return d_.dtype == MG_F64 ? fam_solve_t<F<double>>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
                               : fam_solve_t<F<float>>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
+}
+
+// ---------------------------------------------------------------- implicit time steps on a family's operator (mg_*_heat_*), DESIGN.md section 21
+// u_t = -N0(u) + f with N0 the family's operator WITHOUT the shift, f the source of mg_heat_set_source: mg_heat_step's loop
+// with the family's right-hand side launch and the family's cycle on (1/(theta dt) I + N0) u' = rhs, warm-started from u.
+template <class F>
+int Solver::fam_heat_rhs_t(double dt, double theta, int arr_u, int arr_dst)
+{
+    typedef typename F::type T;
+    Level &L0 = lv_[0];
+    const T *f = heat_has_f_ ? reinterpret_cast<const T *>(heat_f_) + L0.gh * L0.g.plane : (const T *)nullptr;
+    if (arr_dst == MG_ARR_RHS) L0.rhs_halo_ok = false;
+    F::heat_rhs(*this, dt, theta, ptr<T>(arr_u, 0), f, ptr<T>(arr_dst, 0));
+    MG_HIP(hipGetLastError());
+    return MG_OK;
+}
+
+template <template <typename> class F>
+int Solver::fam_heat_rhs(const char *fn, double dt, double theta, int arr_u, int arr_dst)
+{
+    MG_TRY(heat_check(fn, dt, theta));
+    MG_TRY(fam_check<F>(fn, 0));
+    if (!check_arr(arr_u, 0, fn) || !check_arr(arr_dst, 0, fn)) return MG_ERR_BAD_ARG;
+    if (arr_u == arr_dst) { set_last_error(std::string(fn) + ": arr_dst must differ from arr_u"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? fam_heat_rhs_t<F<double>>(dt, theta, arr_u, arr_dst) : fam_heat_rhs_t<F<float>>(dt, theta, arr_u, arr_dst);
+}
+
+template <class F>
+int Solver::fam_heat_step_t(double dt, double theta, int nsteps, int cycles_per_step)
+{
+    typedef typename F::type T;
+    for (int n = 0; n < nsteps; n++) {
+        MG_TRY(fam_heat_rhs_t<F>(dt, theta, MG_ARR_U, MG_ARR_RHS));
+        for (int c = 0; c < cycles_per_step; c++) MG_TRY(fam_cycle_enqueue_t<F>());
+    }
+    MG_TRY(fam_residual_t<F>(0, MG_ARR_U, MG_ARR_RHS, -1, true, SC_RR));   // next to SC_BB: the two are fetched in one copy
+    return sumsq_t<T>(0, MG_ARR_RHS);
+}
+
+template <template <typename> class F>
+int Solver::fam_heat_step(const char *fn, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
+{
+    MG_TRY(heat_check(fn, dt, theta));
+    MG_TRY(fam_check<F>(fn, FAM_NEED_CYCLE));
+    if (nsteps < 1) { set_last_error(std::string(fn) + ": nsteps must be at least 1"); return MG_ERR_BAD_ARG; }
+    if (cycles_per_step < 1) { set_last_error(std::string(fn) + ": cycles_per_step must be at least 1"); return MG_ERR_BAD_ARG; }
+    MG_TRY(set_shift(1.0 / (theta * dt)));
+    MG_TRY(d_.dtype == MG_F64 ? fam_heat_step_t<F<double>>(dt, theta, nsteps, cycles_per_step)
+                              : fam_heat_step_t<F<float>>(dt, theta, nsteps, cycles_per_step));
+    // the one host synchronisation of the call: ||rhs - (sigma I + N0)(u)|| / ||rhs|| of the last step
+    MG_TRY(fetch_scalars(SC_RR, d_scal_ + SC_RR, 2));   // SC_RR and SC_BB
+    if (st) {
+        st->steps = nsteps;
+        st->cycles = nsteps * cycles_per_step;
+        st->time = (double)nsteps * dt;
+        st->relres = h_scal_[SC_RR] == 0.0 ? 0.0 : std::sqrt(h_scal_[SC_RR] / h_scal_[SC_BB]);
+    }
+    return MG_OK;
+}
+
+int Solver::vc_heat_rhs(double dt, double theta, int arr_u, int arr_dst) { return fam_heat_rhs<VcFam>("mg_vc_heat_rhs", dt, theta, arr_u, arr_dst); }
+int Solver::bc_heat_rhs(double dt, double theta, int arr_u, int arr_dst) { return fam_heat_rhs<BcFam>("mg_bc_heat_rhs", dt, theta, arr_u, arr_dst); }
+int Solver::fas_heat_rhs(double dt, double theta, int arr_u, int arr_dst) { return fam_heat_rhs<FasFam>("mg_fas_heat_rhs", dt, theta, arr_u, arr_dst); }
+int Solver::vc_heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
+{
+    return fam_heat_step<VcFam>("mg_vc_heat_step", dt, theta, nsteps, cycles_per_step, st);
+}
+int Solver::bc_heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
+{
+    return fam_heat_step<BcFam>("mg_bc_heat_step", dt, theta, nsteps, cycles_per_step, st);
+}
+int Solver::fas_heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st)
+{
+    return fam_heat_step<FasFam>("mg_fas_heat_step", dt, theta, nsteps, cycles_per_step, st);
 }
 
 // ---------------------------------------------------------------- what only mg_vc_* has

@@ -7,7 +7,8 @@
 //                                        form (residual / Jacobi sweep / one red-black colour pass, every shape) and the
 //                                        coarsest-grid solve are mg_opfamily.h's k_op_plain<FasOp<T, KIND>, DIM, OP, SAVE> and
 //                                        k_op_coarse<FasOp<T, KIND>, DIM>
-//   k_fas_march<T, KIND, OP, SAVE>       the residual and the Jacobi sweep on 3-D levels with rows long enough to fill a wave
+//   k_fas_march<T, KIND, OP, SAVE, SRC>  the residual, the Jacobi sweep and the right-hand side of a theta step (OP_STEP, with or
+//                                        without a source: mg_fas_heat_rhs) on 3-D levels with rows long enough to fill a wave
 //                                        (fas_march_ok, mg_geom.h): k_bc_march's tile (mg_bc.hip) with one marched field
 //   k_fas_coarse_rhs<T, DIM, WZ, KIND>   the FAS transition l -> l+1 in one launch: U(l+1) = E(l+1) = U(l) injected,
 //                                        RHS(l+1) = R TMP(l) + N_c(U(l) injected), the coarse neighbours read from U(l)
@@ -22,6 +23,8 @@
 //                quotient: one Newton step on the node's own equation); Dirichlet nodes take b. Nothing guards den.
 //   Jacobi       u' = ps (omega == 1) or u_i + omega * (ps - u_i)
 //   red-black    in place, colour (i + j + gz) & 1, colour 0 first; Dirichlet nodes take b with their colour
+//   step         n0 = sum + G*g with the UNSHIFTED diagonal cd0; rhs = ((f + rdt*u_i) - omt*n0) * rth, without a source
+//                (rdt*u_i - omt*n0) * rth; Dirichlet nodes: rhs = u_i (step_value, mg_opfamily.h; tests/step_ref.py)
 // With gamma == 0 num = b - s and den = cd, and the correctly rounded quotient is div_cd's: mg_residual's and mg_smooth's bits.
 #include "mg_opfamily.h"
 
@@ -91,19 +94,35 @@ struct FasOp {
         if (damped) return ui + omega * (ps - ui);
         return ps;
     }
+
+    // the operator's value sum + G*g at an unknown (c.cd = cd0: the unshifted operator of the time steppers)
+    template <int DIM>
+    __device__ __forceinline__ bool n0(const Geom &g, const T *u, int z, int y, int x, bool stencil, T &v) const
+    {
+        if (on_boundary(g, z, y, x)) return true;
+        if (stencil) {
+            const long long i = lidx(g, z, y, x);
+            T gv, gp;
+            fas_react<T, KIND>(u[i], gv, gp);
+            v = full_sum<T, DIM>(u, i, g.pitch, g.plane, c) + G * gv;
+        }
+        return false;
+    }
 };
 
 // ---------------------------------------------------------------- the marching tile (3-D)
 // k_bc_march's tile: a lane owns one aligned 16-byte vector of x, a wave covers 64 vectors of MRY = 2 rows, MBW = 4 waves are
 // stacked in y and the workgroup marches zc planes with the planes z-1, z, z+1 of u in registers. The reaction term is
 // computed from the centre value the lane holds: no load and no branch is added in the interior; Dirichlet nodes are a select.
-template <typename T, int KIND, int OP, bool SAVE>
+// OP_STEP: b is the source of the step (not loaded without SRC), st its scalars, c.cd = cd0; out = u on Dirichlet nodes.
+template <typename T, int KIND, int OP, bool SAVE, bool SRC = true>
 __global__ __launch_bounds__(64 * MBW) void k_fas_march(Geom g, Coef<T> c, T G, T omega, const T *__restrict__ u,
                                                         const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
-                                                        int nbx, int nby, int nbz, int zc)
+                                                        int nbx, int nby, int nbz, int zc, StepCoef<T> st)
 {
     constexpr int V = Vec16<T>::n;
-    constexpr bool STORE = OP == OP_JAC || SAVE;
+    constexpr bool STORE = OP != OP_RES || SAVE;
+    constexpr bool LOADB = OP != OP_STEP || SRC;
     typedef typename Vec16<T>::type vec;
     __shared__ double sh[MBW];
 
@@ -155,7 +174,7 @@ __global__ __launch_bounds__(64 * MBW) void k_fas_march(Geom g, Coef<T> c, T G, 
 #pragma unroll
         for (int r = 0; r < MRY; r++) {
             uzp[r] = *(const vec *)(pu + g.plane + rowoff[r]);
-            bv[r] = __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r]));
+            bv[r] = LOADB ? __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r])) : (vec)(0);
         }
         const vec ulo = *(const vec *)(pu + off_lo), uhi = *(const vec *)(pu + off_hi);
         const int gz = g.gz0 + z;
@@ -179,7 +198,7 @@ __global__ __launch_bounds__(64 * MBW) void k_fas_march(Geom g, Coef<T> c, T G, 
                 sum += c.cz * uzm[r][e];
                 sum += c.cy * uym[e];
                 sum += c.cx * ul;
-                if (OP == OP_RES) sum += c.cd * ui;
+                if (OP == OP_RES || OP == OP_STEP) sum += c.cd * ui;
                 sum += c.cx * ur;
                 sum += c.cy * uyp[e];
                 sum += c.cz * uzp[r][e];
@@ -187,6 +206,10 @@ __global__ __launch_bounds__(64 * MBW) void k_fas_march(Geom g, Coef<T> c, T G, 
                     T gv, gp;
                     fas_react<T, KIND>(ui, gv, gp);
                     res[e] = dn ? bi - ui : bi - (sum + G * gv);
+                } else if (OP == OP_STEP) {
+                    T gv, gp;
+                    fas_react<T, KIND>(ui, gv, gp);
+                    res[e] = dn ? ui : step_value<T, SRC>(st, ui, bi, sum + G * gv);
                 } else {
                     const T ps = fas_newton<T, KIND>(c, G, sum, ui, bi);
                     res[e] = dn ? bi : (damped ? ui + omega * (ps - ui) : ps);
@@ -215,7 +238,9 @@ __global__ __launch_bounds__(64 * MBW) void k_fas_march(Geom g, Coef<T> c, T G, 
                     const long long ro = zo + (rowoff[r] - x0c);
                     if (xs < line_end) {
                         vec tv = (vec)(0);
-                        if (j == 0) {
+                        if (j == 0 && OP == OP_STEP) {
+                            tv[0] = u[ro + g.nx - 1];
+                        } else if (j == 0) {
                             const T bt = b[ro + g.nx - 1];
                             if (OP == OP_RES) {
                                 const T rt = bt - (T)1 * u[ro + g.nx - 1];
@@ -312,7 +337,7 @@ int launch_fas_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int kind
         const MarchGrid m = march_grid<T>(g);
         if (m.grid <= cap) {
             const dim3 gr(m.grid), bl(64 * MBW);
-#define MG_FAS(KIND, SAVE) hipLaunchKernelGGL((k_fas_march<T, KIND, OP_RES, SAVE>), gr, bl, 0, s, g, c, G, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc)
+#define MG_FAS(KIND, SAVE) hipLaunchKernelGGL((k_fas_march<T, KIND, OP_RES, SAVE>), gr, bl, 0, s, g, c, G, (T)1, u, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{})
             if (kind == FAS_CUBIC) { if (r) MG_FAS(FAS_CUBIC, true); else MG_FAS(FAS_CUBIC, false); }
             else { if (r) MG_FAS(FAS_EXP, true); else MG_FAS(FAS_EXP, false); }
 #undef MG_FAS
@@ -329,12 +354,29 @@ void launch_fas_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int kind,
         const MarchGrid m = march_grid<T>(g);
         const dim3 gr(m.grid), bl(64 * MBW);
         if (kind == FAS_CUBIC)
-            hipLaunchKernelGGL((k_fas_march<T, FAS_CUBIC, OP_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+            hipLaunchKernelGGL((k_fas_march<T, FAS_CUBIC, OP_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
         else
-            hipLaunchKernelGGL((k_fas_march<T, FAS_EXP, OP_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+            hipLaunchKernelGGL((k_fas_march<T, FAS_EXP, OP_JAC, false>), gr, bl, 0, s, g, c, G, omega, u, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
         return;
     }
     with_fas_op(kind, c, G, [&](auto op) { plain_jacobi(s, g, op, omega, u, b, out); });
+}
+
+template <typename T>
+void launch_fas_heat_rhs(hipStream_t s, const Geom &g, const Coef<T> &c0, int kind, T G, double dt, double theta, const T *u, const T *f,
+                         T *out, bool plain)
+{
+    const StepCoef<T> st = step_coef<T>(dt, theta);
+    if (march_takes<T>(g, plain)) {
+        const MarchGrid m = march_grid<T>(g);
+        const dim3 gr(m.grid), bl(64 * MBW);
+#define MG_FAS(KIND, SRC) hipLaunchKernelGGL((k_fas_march<T, KIND, OP_STEP, true, SRC>), gr, bl, 0, s, g, c0, G, (T)1, u, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st)
+        if (kind == FAS_CUBIC) { if (f) MG_FAS(FAS_CUBIC, true); else MG_FAS(FAS_CUBIC, false); }
+        else { if (f) MG_FAS(FAS_EXP, true); else MG_FAS(FAS_EXP, false); }
+#undef MG_FAS
+        return;
+    }
+    with_fas_op(kind, c0, G, [&](auto op) { plain_step(s, g, op, st, u, f, out); });
 }
 
 template <typename T>
@@ -375,6 +417,8 @@ void launch_fas_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int kind,
 #define MG_FAS_INST(T)                                                                                                                    \
     template int launch_fas_residual<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, const T *, const T *, T *, double *, int, bool); \
     template void launch_fas_jacobi<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, T, const T *, const T *, T *, bool);           \
+    template void launch_fas_heat_rhs<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, double, double, const T *, const T *, T *,   \
+                                         bool);                                                                                           \
     template void launch_fas_rb_colour<T>(hipStream_t, const Geom &, const Coef<T> &, int, T, int, T *, const T *);                       \
     template void launch_fas_coarse_rhs<T>(hipStream_t, const Geom &, const Geom &, const Coef<T> &, int, T, bool, const T *, const T *,  \
                                            T *, T *, T *);                                                                                \

@@ -314,6 +314,11 @@ int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], doubl
 template <typename T>
 void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, T omega, const T *u, const T *a, const T *b,
                       T *out, bool plain);
+// launch_heat_rhs with the UNSHIFTED operator -div(a grad .) (coef's cd and the handle's shift are not used): out = right-hand
+// side of one theta step from u (and the source f; nullptr: f = 0), u on Dirichlet nodes. out must not alias u, a or f.
+template <typename T>
+void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], double dt, double theta, const T *u, const T *a, const T *f,
+                        T *out, bool plain);
 // one colour pass of red-black Gauss-Seidel, in place
 template <typename T>
 void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int colour, T *u, const T *a, const T *b);
@@ -336,6 +341,11 @@ int launch_bc_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int mask,
 // one Jacobi sweep, out of place (out must not alias u)
 template <typename T>
 void launch_bc_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, T omega, const T *u, const T *b, T *out, bool plain);
+// launch_heat_rhs with Neumann faces; c0: the level's Coef with the UNSHIFTED diagonal cd0. out = u on the Dirichlet nodes of
+// the mask; theta == 1 loads no neighbour. out must not alias u or f.
+template <typename T>
+void launch_bc_heat_rhs(hipStream_t s, const Geom &g, const Coef<T> &c0, int mask, double dt, double theta, const T *u, const T *f, T *out,
+                        bool plain);
 // one colour pass of red-black Gauss-Seidel, in place
 template <typename T>
 void launch_bc_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int mask, int colour, T *u, const T *b);
@@ -366,6 +376,10 @@ int launch_fas_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int kind
 // one Jacobi sweep of linearised point solves, out of place (out must not alias u)
 template <typename T>
 void launch_fas_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, const T *u, const T *b, T *out, bool plain);
+// launch_heat_rhs with N0(u) = A0 u + G g(u); c0: the level's Coef with the UNSHIFTED diagonal cd0. out must not alias u or f.
+template <typename T>
+void launch_fas_heat_rhs(hipStream_t s, const Geom &g, const Coef<T> &c0, int kind, T G, double dt, double theta, const T *u, const T *f,
+                         T *out, bool plain);
 // one colour pass of red-black Gauss-Seidel with the linearised point solve, in place
 template <typename T>
 void launch_fas_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int colour, T *u, const T *b);

@@ -8,9 +8,15 @@
 //     typedef ... type;                                                     the element type T
 //     template <int DIM> T res(g, u, b, z, y, x) const;                     b - L u at one node (Dirichlet nodes: b - u)
 //     template <int DIM> T solve(g, omega, damped, u, b, z, y, x) const;    the point solve (Dirichlet nodes: b)
+//     template <int DIM> bool n0(g, u, z, y, x, stencil, v) const;          true at a Dirichlet node; else v = the operator's
+//                                                                           value at the node (stencil == false: v is left alone
+//                                                                           and no neighbour is loaded). The time steppers build
+//                                                                           the Op with sigma = 0 / cd0: the UNSHIFTED operator
 //
-//   k_op_plain<Op, DIM, OP, SAVE>   OP = residual (stored with SAVE, else norm only) / Jacobi sweep (out of place) / one
-//                                   red-black colour pass (in place): one thread per node, grid-stride, every shape
+//   k_op_plain<Op, DIM, OP, SAVE, SRC>   OP = residual (stored with SAVE, else norm only) / Jacobi sweep (out of place) / one
+//                                   red-black colour pass (in place) / the right-hand side of a theta step (OP_STEP, out of
+//                                   place; SRC: with a source, read where the others read b): one thread per node,
+//                                   grid-stride, every shape
 //   k_op_coarse<Op, DIM>            the Solver::Solve loop of k_coarse_solve (mg_kernels.hip) in one workgroup, with the
 //                                   family's sweep (wg_op_jacobi / wg_op_rbgs) and residual (wg_op_residual_sumsq)
 #pragma once
@@ -23,14 +29,37 @@ namespace mg {
 
 constexpr int OP_THREADS = 256, OP_MAX_BLOCKS = 2048;
 constexpr int MBW = 4, MRY = 2;   // waves per workgroup / rows per wave of the marching tiles
-enum { OP_RES = 0, OP_JAC = 1, OP_RB = 2 };
+enum { OP_RES = 0, OP_JAC = 1, OP_RB = 2, OP_STEP = 3 };
+
+// The scalars of one theta step of u_t = -N0(u) + f (mg_*_heat_rhs), passed to the kernels by value:
+// rdt = (T)(1 / dt), omt = (T)(1 - theta), rth = (T)(1 / theta). The other modes do not look at them.
+template <typename T>
+struct StepCoef {
+    T rdt, omt, rth;
+};
+
+template <typename T>
+StepCoef<T> step_coef(double dt, double theta)
+{
+    return StepCoef<T>{(T)(1.0 / dt), (T)(1.0 - theta), (T)(1.0 / theta)};
+}
+
+// the step's right-hand side at an unknown from u, the source and the unshifted operator value n0 (k_heat_rhs's expression)
+template <typename T, bool SRC>
+__device__ __forceinline__ T step_value(const StepCoef<T> &st, T ui, T fi, T n0)
+{
+    T t = st.rdt * ui;
+    if (SRC) t = fi + t;
+    return (t - st.omt * n0) * st.rth;
+}
 
 // ---------------------------------------------------------------- the plain form
-// out: r (OP_RES with SAVE), u' (OP_JAC, must not alias u) or u itself (OP_RB: the other colour is only read)
-template <typename Op, int DIM, int OP, bool SAVE>
+// out: r (OP_RES with SAVE), u' (OP_JAC, must not alias u), u itself (OP_RB: the other colour is only read) or the step's
+// right-hand side (OP_STEP, must not alias u; b is the source, not read without SRC; theta == 1: no neighbour is loaded)
+template <typename Op, int DIM, int OP, bool SAVE, bool SRC = true>
 __global__ __launch_bounds__(OP_THREADS) void k_op_plain(Geom g, Op op, typename Op::type omega, int colour, const typename Op::type *u,
                                                          const typename Op::type *__restrict__ b, typename Op::type *out,
-                                                         double *__restrict__ partials)
+                                                         double *__restrict__ partials, StepCoef<typename Op::type> st)
 {
     typedef typename Op::type T;
     __shared__ double sh[OP_THREADS / 64];
@@ -50,6 +79,13 @@ __global__ __launch_bounds__(OP_THREADS) void k_op_plain(Geom g, Op op, typename
             const T res = op.template res<DIM>(g, u, b, z, y, x);
             acc += (double)res * (double)res;
             if (SAVE) out[lidx(g, z, y, x)] = res;
+        } else if (OP == OP_STEP) {
+            const long long i = lidx(g, z, y, x);
+            const T ui = u[i];
+            T n0 = (T)0, fi = (T)0;
+            const bool fixed = op.template n0<DIM>(g, u, z, y, x, st.omt != (T)0, n0);
+            if (SRC) fi = __builtin_nontemporal_load(b + i);
+            __builtin_nontemporal_store(fixed ? ui : step_value<T, SRC>(st, ui, fi, n0), out + i);
         } else {
             out[lidx(g, z, y, x)] = op.template solve<DIM>(g, omega, damped, u, b, z, y, x);
         }
@@ -205,7 +241,7 @@ int plain_residual(hipStream_t s, const Geom &g, const Op &op, const typename Op
     typedef typename Op::type T;
     const int nb = plain_grid((long long)g.nx * g.ny * g.nz, cap);
     const dim3 gr(nb), bl(OP_THREADS);
-#define MG_OP(DIM, SAVE) hipLaunchKernelGGL((k_op_plain<Op, DIM, OP_RES, SAVE>), gr, bl, 0, s, g, op, (T)1, 0, u, b, r, partials)
+#define MG_OP(DIM, SAVE) hipLaunchKernelGGL((k_op_plain<Op, DIM, OP_RES, SAVE>), gr, bl, 0, s, g, op, (T)1, 0, u, b, r, partials, StepCoef<T>{})
     if (g.dim == 3) { if (r) MG_OP(3, true); else MG_OP(3, false); }
     else { if (r) MG_OP(2, true); else MG_OP(2, false); }
 #undef MG_OP
@@ -216,9 +252,10 @@ template <typename Op>
 void plain_jacobi(hipStream_t s, const Geom &g, const Op &op, typename Op::type omega, const typename Op::type *u,
                   const typename Op::type *b, typename Op::type *out)
 {
+    typedef typename Op::type T;
     const dim3 gr(plain_grid((long long)g.nx * g.ny * g.nz, OP_MAX_BLOCKS)), bl(OP_THREADS);
-    if (g.dim == 3) hipLaunchKernelGGL((k_op_plain<Op, 3, OP_JAC, false>), gr, bl, 0, s, g, op, omega, 0, u, b, out, (double *)nullptr);
-    else hipLaunchKernelGGL((k_op_plain<Op, 2, OP_JAC, false>), gr, bl, 0, s, g, op, omega, 0, u, b, out, (double *)nullptr);
+    if (g.dim == 3) hipLaunchKernelGGL((k_op_plain<Op, 3, OP_JAC, false>), gr, bl, 0, s, g, op, omega, 0, u, b, out, (double *)nullptr, StepCoef<T>{});
+    else hipLaunchKernelGGL((k_op_plain<Op, 2, OP_JAC, false>), gr, bl, 0, s, g, op, omega, 0, u, b, out, (double *)nullptr, StepCoef<T>{});
 }
 
 template <typename Op>
@@ -226,8 +263,21 @@ void plain_rb_colour(hipStream_t s, const Geom &g, const Op &op, int colour, typ
 {
     typedef typename Op::type T;
     const dim3 gr(plain_grid((long long)((g.nx + 1) / 2) * g.ny * g.nz, OP_MAX_BLOCKS)), bl(OP_THREADS);
-    if (g.dim == 3) hipLaunchKernelGGL((k_op_plain<Op, 3, OP_RB, false>), gr, bl, 0, s, g, op, (T)1, colour, u, b, u, (double *)nullptr);
-    else hipLaunchKernelGGL((k_op_plain<Op, 2, OP_RB, false>), gr, bl, 0, s, g, op, (T)1, colour, u, b, u, (double *)nullptr);
+    if (g.dim == 3) hipLaunchKernelGGL((k_op_plain<Op, 3, OP_RB, false>), gr, bl, 0, s, g, op, (T)1, colour, u, b, u, (double *)nullptr, StepCoef<T>{});
+    else hipLaunchKernelGGL((k_op_plain<Op, 2, OP_RB, false>), gr, bl, 0, s, g, op, (T)1, colour, u, b, u, (double *)nullptr, StepCoef<T>{});
+}
+
+// the step's right-hand side in the plain form; op carries the UNSHIFTED operator, f == nullptr: no source
+template <typename Op>
+void plain_step(hipStream_t s, const Geom &g, const Op &op, const StepCoef<typename Op::type> &st, const typename Op::type *u,
+                const typename Op::type *f, typename Op::type *out)
+{
+    typedef typename Op::type T;
+    const dim3 gr(plain_grid((long long)g.nx * g.ny * g.nz, OP_MAX_BLOCKS)), bl(OP_THREADS);
+#define MG_OP(DIM, SRC) hipLaunchKernelGGL((k_op_plain<Op, DIM, OP_STEP, true, SRC>), gr, bl, 0, s, g, op, (T)1, 0, u, f, out, (double *)nullptr, st)
+    if (g.dim == 3) { if (f) MG_OP(3, true); else MG_OP(3, false); }
+    else { if (f) MG_OP(2, true); else MG_OP(2, false); }
+#undef MG_OP
 }
 
 template <typename Op>

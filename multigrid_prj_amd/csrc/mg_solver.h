@@ -138,6 +138,14 @@ public:
     int heat_set_source_device(const void *dense, int dense_dtype, hipStream_t caller);
     int heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
     int heat_rhs(double dt, double theta, int arr_u, int arr_dst);
+    // the same steps of u_t = -N0(u) + f with N0 the unshifted operator of a family (mg_vc_heat_*, mg_bc_heat_*, mg_fas_heat_*);
+    // f is the one source of the handle
+    int vc_heat_rhs(double dt, double theta, int arr_u, int arr_dst);
+    int bc_heat_rhs(double dt, double theta, int arr_u, int arr_dst);
+    int fas_heat_rhs(double dt, double theta, int arr_u, int arr_dst);
+    int vc_heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
+    int bc_heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
+    int fas_heat_step(double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
     // lowest eigenpairs of sigma I + A on level 0 by multigrid-preconditioned LOBPCG (mg_eig_*); the block of 6 m level-0
     // arrays is allocated on first use and kept until the handle goes
     int eig_solve(int m, int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap, int *n_hist,
@@ -210,6 +218,8 @@ private:
         if (!switches().fast_div) c.win = 0;  // A/B switch: hardware division everywhere
         return c;
     }
+    // the level's UNSHIFTED operator (cd0): what the time steppers apply to u; nothing divides by its diagonal
+    template <typename T> static Coef<T> coef0_of(const Level &L) { return make_coef<T>(L.coef[0], L.coef[1], L.coef[2], L.cd0); }
     // x_zero: the caller knows x == 0 (fresh coarse-level guess): the first Jacobi sweep of a
     // fast-path level then skips reading x (and the caller skips the memset)
     template <typename T> int smooth_t(int level, int smoother, int sweeps, int ax, int ar, bool x_zero = false,
@@ -402,7 +412,7 @@ private:
     enum : unsigned { FAM_NEED_CYCLE = 1u, FAM_NEED_SMOOTHER = 2u };   // what fam_check asks of the descriptor beyond F's own precondition
     template <template <typename> class F> int fam_check(const char *fn, unsigned need);   // driver_begin, F::ready, the cycle / smoother the family drivers run
     int set_form(const char *fn, int form, bool *plain);   // mg_*_set_form
-    template <class F> int fam_residual_t(int level, int ax, int ar, int arr_r, bool want_sum);   // the sum -> d_scal_[SC_FAM_SUM]
+    template <class F> int fam_residual_t(int level, int ax, int ar, int arr_r, bool want_sum, int slot = SC_FAM_SUM);   // the sum -> d_scal_[slot]
     template <class F> int fam_residual_sum_t(int level, int ax, int ar, int arr_r, double *sumsq_r);   // ... and fetched: synchronises
     template <class F> int fam_smooth_t(int level, int smoother, int sweeps, int ax, int ar);
     template <class F> int fam_coarse_t(int level, int ax, int ar);
@@ -417,6 +427,12 @@ private:
     template <template <typename> class F> int fam_cycle(const char *fn, mg_cycle_stats *st);
     template <template <typename> class F>
     int fam_solve(const char *fn, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
+    // mg_<family>_heat_rhs / mg_<family>_heat_step: heat_check, fam_check, then F::heat_rhs (one launch) and the family's cycle
+    template <class F> int fam_heat_rhs_t(double dt, double theta, int arr_u, int arr_dst);
+    template <class F> int fam_heat_step_t(double dt, double theta, int nsteps, int cycles_per_step);   // sums -> SC_RR, SC_BB
+    template <template <typename> class F> int fam_heat_rhs(const char *fn, double dt, double theta, int arr_u, int arr_dst);
+    template <template <typename> class F>
+    int fam_heat_step(const char *fn, double dt, double theta, int nsteps, int cycles_per_step, mg_heat_stats *st);
     // variable-coefficient drivers (mg_vc_*): Level::vc_a of every level, valid once vc_set_ is true
     bool vc_set_ = false, vc_plain_ = false;
     int vc_alloc();

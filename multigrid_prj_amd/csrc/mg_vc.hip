@@ -7,7 +7,8 @@
 //                                  form (residual / Jacobi sweep / one red-black colour pass, every shape) and the
 //                                  coarsest-grid solve are mg_opfamily.h's k_op_plain<VcOp<T>, DIM, OP, SAVE> and
 //                                  k_op_coarse<VcOp<T>, DIM>
-//   k_vc_march<T, OP, SAVE>        the residual and the Jacobi sweep on 3-D levels with rows long enough to fill a wave
+//   k_vc_march<T, OP, SAVE, SRC>   the residual, the Jacobi sweep and the right-hand side of a theta step (OP_STEP, with or
+//                                  without a source: mg_vc_heat_rhs) on 3-D levels with rows long enough to fill a wave
 //                                  (vc_march_ok, mg_geom.h)
 //   k_vc_cg_direction<T, DIM>      k_cg_direction_apply (mg_krylov.hip) with q = L p'
 //
@@ -29,6 +30,8 @@
 //   Jacobi       u' = ps (omega == 1) or u_i + omega * (ps - u_i); Dirichlet nodes: u' = b
 //   red-black    in place, colour (i + j + k) & 1, colour 0 first; Dirichlet nodes take b with their colour
 //   direction    p' = z + beta * p (0 on Dirichlet nodes), q = d * p'_i - s with u = p' (0 on Dirichlet nodes), p'.q in double
+//   step         n0 = d * u_i - s with d started from (T)0 (the UNSHIFTED operator); rhs = ((f + rdt*u_i) - omt*n0) * rth, without a
+//                source (rdt*u_i - omt*n0) * rth; Dirichlet nodes: rhs = u_i (step_value, mg_opfamily.h; tests/step_ref.py)
 #include "mg_opfamily.h"
 
 namespace mg {
@@ -95,16 +98,32 @@ struct VcOp {
         }
         return ps;
     }
+
+    // the operator's value d * u_i - s at an unknown (c.sigma = 0: the unshifted operator of the time steppers)
+    template <int DIM>
+    __device__ __forceinline__ bool n0(const Geom &g, const T *u, int z, int y, int x, bool stencil, T &v) const
+    {
+        if (on_boundary(g, z, y, x)) return true;
+        if (stencil) {
+            const long long i = lidx(g, z, y, x);
+            T s, d;
+            vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, g.pitch, g.plane, c, s, d);
+            v = d * u[i] - s;
+        }
+        return false;
+    }
 };
 
 // ---------------------------------------------------------------- the marching tile (3-D)
-template <typename T, int OP, bool SAVE>
+// OP_STEP: b is the source of the step (not loaded without SRC), st its scalars, c.sigma = 0; out = u on Dirichlet nodes
+template <typename T, int OP, bool SAVE, bool SRC = true>
 __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T omega, const T *__restrict__ u, const T *__restrict__ a,
                                                        const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
-                                                       int nbx, int nby, int nbz, int zc)
+                                                       int nbx, int nby, int nbz, int zc, StepCoef<T> st)
 {
     constexpr int V = Vec16<T>::n;
-    constexpr bool STORE = OP == OP_JAC || SAVE;
+    constexpr bool STORE = OP != OP_RES || SAVE;
+    constexpr bool LOADB = OP != OP_STEP || SRC;
     typedef typename Vec16<T>::type vec;
     __shared__ double sh[MBW];
 
@@ -159,7 +178,7 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
         for (int r = 0; r < MRY; r++) {
             uzp[r] = *(const vec *)(pu + g.plane + rowoff[r]);
             azp[r] = *(const vec *)(pa + g.plane + rowoff[r]);
-            bv[r] = __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r]));
+            bv[r] = LOADB ? __builtin_nontemporal_load((const vec *)(b + zo + rowoff[r])) : (vec)(0);
         }
         const vec ulo = *(const vec *)(pu + off_lo), uhi = *(const vec *)(pu + off_hi);
         const vec alo = *(const vec *)(pa + off_lo), ahi = *(const vec *)(pa + off_hi);
@@ -192,6 +211,8 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                 T v;
                 if (OP == OP_RES) {
                     v = bnd ? bi - ui : bi - (d * ui - s);
+                } else if (OP == OP_STEP) {
+                    v = bnd ? ui : step_value<T, SRC>(st, ui, bi, d * ui - s);
                 } else {
                     const T ps = (bi + s) / d;
                     v = bnd ? bi : (damped ? ui + omega * (ps - ui) : ps);
@@ -213,7 +234,7 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                         if (STORE && e < part) po[e] = res[e];
                 }
                 if (tailwave && lane >= 56) {
-                    // column nx-1 (Dirichlet: r = b - u, u' = b) as one full 128-byte line: value + zero padding
+                    // column nx-1 (Dirichlet: r = b - u, u' = b, the step's rhs = u) as one full 128-byte line: value + zero padding
                     const int j = lane - 56;
                     constexpr int LINE = 128 / (int)sizeof(T);
                     const int xs = g.nx - 1 + V * j;
@@ -221,7 +242,9 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                     const long long ro = zo + (rowoff[r] - x0c);
                     if (xs < line_end) {
                         vec tv = (vec)(0);
-                        if (j == 0) {
+                        if (j == 0 && OP == OP_STEP) {
+                            tv[0] = u[ro + g.nx - 1];
+                        } else if (j == 0) {
                             const T bt = b[ro + g.nx - 1];
                             if (OP == OP_RES) {
                                 const T rt = bt - u[ro + g.nx - 1];
@@ -297,8 +320,8 @@ int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], doubl
         const MarchGrid m = march_grid<T>(g);
         if (m.grid <= cap) {
             const dim3 gr(m.grid), bl(64 * MBW);
-            if (r) hipLaunchKernelGGL((k_vc_march<T, OP_RES, true>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
-            else hipLaunchKernelGGL((k_vc_march<T, OP_RES, false>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc);
+            if (r) hipLaunchKernelGGL((k_vc_march<T, OP_RES, true>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
+            else hipLaunchKernelGGL((k_vc_march<T, OP_RES, false>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
             return m.grid;
         }
     }
@@ -313,10 +336,26 @@ void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double
     if (march_takes<T>(g, plain)) {
         const MarchGrid m = march_grid<T>(g);
         hipLaunchKernelGGL((k_vc_march<T, OP_JAC, false>), dim3(m.grid), dim3(64 * MBW), 0, s, g, c, omega, u, a, b, out,
-                           (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc);
+                           (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
         return;
     }
     plain_jacobi(s, g, VcOp<T>{c, a}, omega, u, b, out);
+}
+
+template <typename T>
+void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], double dt, double theta, const T *u, const T *a, const T *f,
+                        T *out, bool plain)
+{
+    const VcCoef<T> c = vc_coef<T>(coef, 0.0);   // the unshifted operator: d starts from (T)0
+    const StepCoef<T> st = step_coef<T>(dt, theta);
+    if (march_takes<T>(g, plain)) {
+        const MarchGrid m = march_grid<T>(g);
+        const dim3 gr(m.grid), bl(64 * MBW);
+        if (f) hipLaunchKernelGGL((k_vc_march<T, OP_STEP, true, true>), gr, bl, 0, s, g, c, (T)1, u, a, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st);
+        else hipLaunchKernelGGL((k_vc_march<T, OP_STEP, true, false>), gr, bl, 0, s, g, c, (T)1, u, a, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st);
+        return;
+    }
+    plain_step(s, g, VcOp<T>{c, a}, st, u, f, out);
 }
 
 template <typename T>
@@ -348,6 +387,8 @@ int launch_vc_cg_direction(hipStream_t s, const Geom &g, const double coef[4], d
                                        double *, int, bool);                                                                         \
     template void launch_vc_jacobi<T>(hipStream_t, const Geom &, const double[4], double, T, const T *, const T *, const T *, T *,   \
                                       bool);                                                                                         \
+    template void launch_vc_heat_rhs<T>(hipStream_t, const Geom &, const double[4], double, double, const T *, const T *, const T *,  \
+                                        T *, bool);                                                                                  \
     template void launch_vc_rb_colour<T>(hipStream_t, const Geom &, const double[4], double, int, T *, const T *, const T *);         \
     template void launch_vc_coarse<T>(hipStream_t, const Geom &, const double[4], double, T, int, T *, T *, const T *, const T *, int, \
                                       double, int, CoarseOut *);                                                                     \
