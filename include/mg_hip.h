@@ -502,6 +502,47 @@ int mg_bc_project(mg_handle h, int level, int arr, double *mean);
 int mg_bc_cycle(mg_handle h, mg_cycle_stats *st);
 int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
 
+/* Neumann faces of the variable-coefficient operator (extension, no reference counterpart): mg_vc_* with zero-flux walls or
+ * symmetry planes -- insulated walls of a heterogeneous conductor, no-flow boundaries of a porous medium, the all-Neumann
+ * and singular variable-density projection. A SECOND face mask on the handle, independent of mg_bc_set_faces, default 0.
+ * The node classes are those of the block above: a node on at least one face that is not in the mask is a Dirichlet node
+ * (identity row: r = b - u, the sweeps take b), every other node is an unknown, edges and corners between Neumann faces
+ * included. At an unknown the arithmetic is mg_vc_*'s word for word with the MIRRORED index substituted for a missing
+ * neighbour, for a and for u alike; no ghost value is stored or read:
+ *   w_a = (T)(-c_a / 2);  s = 0;  d = (T)sigma;  for the slots z-, y-, x-, x+, y+, z+ (no z in 2-D), q the neighbour or its
+ *   mirror image i+ when i- falls outside through a Neumann face (i- for a missing i+):
+ *       g = w_a * (a_i + a_q);  s = s + g * u_q;  d = d + g                (a mirrored slot counts twice, in s and in d)
+ *   residual r = b - (d * u_i - s), point solve (b + s) / d, Jacobi / damping / red-black colour as for mg_vc_*; the sum of r^2
+ *   over all nodes in double in a fixed order.
+ * With w_i = the product of 1/2 per Neumann face the node lies on (mg_bc_project's weights) diag(w) L is symmetric for any a,
+ * and with every face Neumann and shift 0 the constants span the null space.
+ * COARSE COEFFICIENTS: with a non-zero mask level l + 1 is the MIRRORED full weighting of level l (mg_bc_restrict's
+ * MG_RESTRICT_FULLW with this mask, coarse Dirichlet nodes injected), which keeps min a <= a_coarse <= max a;
+ * mg_vc_set_coefficient* restricts with the current mask and mg_vc_set_faces restricts again from the stored level 0 when a
+ * coefficient is set, so the two may come in either order. With mask 0 everything is mg_vc_*'s kernels and bits as before.
+ * INHOMOGENEOUS FLUX is the caller's business: for an outward normal derivative g on a Neumann face of axis a add
+ * (2 alpha aniso_a / h_a) a_i g to b at that face's nodes, a_i the coefficient AT the wall node (one term per face at an edge
+ * or corner): second-order accurate for any a. (alpha aniso_a / h_a) (a_i + a_i+) g, with the coefficient of the mirrored
+ * slot, is second order only where a has no normal derivative at the wall and first order otherwise.
+ *
+ * mg_vc_set_faces / mg_vc_get_faces: set and read the mask; nothing is allocated; z bits on a 2-D handle and masks outside
+ *   0..63 are MG_ERR_BAD_ARG and leave the mask and the coefficients as they were.
+ * These entry points honour the mask with unchanged signatures: mg_vc_residual, mg_vc_smooth, mg_vc_coarse_solve, mg_vc_cycle
+ *   (V, W, F; the residual goes down by mg_vc_restrict with desc.restriction), mg_vc_solve, mg_vc_heat_rhs, mg_vc_heat_step
+ *   (theta == 1 copies u on the mask's Dirichlet nodes), mg_vc_pcg_solve and mg_vc_direction.
+ * mg_vc_solve, THE SINGULAR CASE (every face of the handle's dimension Neumann, shift 0): as mg_bc_solve -- RHS(0) is projected
+ *   first and stays projected, U(0) is projected after the last cycle.
+ * mg_vc_pcg_solve with a mask: every inner product of the iteration is sum w x y (z.r, z.q, p.q), in which L is self-adjoint;
+ *   the stopping test and the history stay sqrt(sum r^2) / ||b||. In the singular case RHS(0) is projected first, z after
+ *   every preconditioner application and x at the end.
+ * mg_vc_direction with a mask: arr_pn and arr_q are 0 on the mask's Dirichlet nodes, neighbours are mirrored, *pq = sum w pn q.
+ * mg_vc_restrict, mg_vc_project: mg_bc_restrict and mg_bc_project with this mask (no coefficient is needed).
+ * MG_ERR_BAD_ARG as for mg_vc_*. Not combined with mg_fas_*, mg_o4_*, mg_fmg, mg_eig_solve or mg_mixed_solve. */
+int mg_vc_set_faces(mg_handle h, int mask);
+int mg_vc_get_faces(mg_handle h, int *mask);
+int mg_vc_restrict(mg_handle h, int fine_level, int kind, int arr_src, int arr_dst);
+int mg_vc_project(mg_handle h, int level, int arr, double *mean);
+
 /* Nonlinear solves by the full approximation scheme, FAS (extension, no reference counterpart): the semilinear problem
  *     N(u) = (sigma I + A) u + gamma g(u) = f
  * with the handle's constant operator -- alpha, aniso, semi_xy, grids that are not 2^k + 1 and the shift of mg_set_shift keep

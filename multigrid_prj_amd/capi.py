@@ -164,6 +164,7 @@ EXPORTS = [
     "mg_o4_residual", "mg_o4_correct_residual", "mg_o4_solve",
     "mg_vc_set_coefficient", "mg_vc_set_coefficient_device", "mg_vc_get_coefficient", "mg_vc_set_form", "mg_vc_residual", "mg_vc_smooth",
     "mg_vc_coarse_solve", "mg_vc_cycle", "mg_vc_solve", "mg_vc_pcg_solve", "mg_vc_direction",
+    "mg_vc_set_faces", "mg_vc_get_faces", "mg_vc_restrict", "mg_vc_project",
     "mg_bc_set_faces", "mg_bc_get_faces", "mg_bc_set_form", "mg_bc_residual", "mg_bc_smooth", "mg_bc_restrict", "mg_bc_coarse_solve",
     "mg_bc_project", "mg_bc_cycle", "mg_bc_solve",
     "mg_fas_set_reaction", "mg_fas_get_reaction", "mg_fas_set_form", "mg_fas_residual", "mg_fas_smooth", "mg_fas_coarse_rhs", "mg_fas_correct",
@@ -246,6 +247,10 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_vc_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgCycleStats)]
     L.mg_vc_pcg_solve.argtypes = [vp, C.c_double, i, dp, i, C.POINTER(i), C.POINTER(MgKrylovStats)]
     L.mg_vc_direction.argtypes = [vp, C.c_double, i, i, i, i, dp]
+    L.mg_vc_set_faces.argtypes = [vp, i]
+    L.mg_vc_get_faces.argtypes = [vp, C.POINTER(i)]
+    L.mg_vc_restrict.argtypes = [vp, i, i, i, i]
+    L.mg_vc_project.argtypes = [vp, i, i, dp]
     L.mg_bc_set_faces.argtypes = [vp, i]
     L.mg_bc_get_faces.argtypes = [vp, C.POINTER(i)]
     L.mg_bc_set_form.argtypes = [vp, i]
@@ -653,6 +658,23 @@ class Solver:
     def vc_direction(self, beta, arr_z, arr_p, arr_pn, arr_q) -> float:
         """mg_vc_direction: arr_pn = arr_z + beta arr_p, arr_q = L arr_pn (both 0 on Dirichlet nodes) -> sum pn.q"""
         s = C.c_double(0); _check(self.lib.mg_vc_direction(self.h, beta, arr_z, arr_p, arr_pn, arr_q, C.byref(s))); return s.value
+
+    # Neumann faces of the variable-coefficient operator: a face mask of its own (mg_vc_set_faces, include/mg_hip.h)
+    def vc_set_faces(self, mask):
+        """mg_vc_set_faces: the Neumann faces (FACE_* bits) of mg_vc_*, 0 = all Dirichlet; independent of bc_set_faces"""
+        _check(self.lib.mg_vc_set_faces(self.h, int(mask)))
+
+    def vc_get_faces(self) -> int:
+        """mg_vc_get_faces: the mask of vc_set_faces"""
+        m = C.c_int(0); _check(self.lib.mg_vc_get_faces(self.h, C.byref(m))); return m.value
+
+    def vc_restrict(self, fine_level, kind, arr_src, arr_dst):
+        """mg_vc_restrict: bc_restrict with the vc mask"""
+        _check(self.lib.mg_vc_restrict(self.h, fine_level, kind, arr_src, arr_dst))
+
+    def vc_project(self, level, arr) -> float:
+        """mg_vc_project: subtracts the w-weighted mean (the vc mask's weights) from every node and returns it"""
+        m = C.c_double(0); _check(self.lib.mg_vc_project(self.h, level, arr, C.byref(m))); return m.value
 
     # -- Neumann faces: the constant operator with zero-flux walls on the faces of a mask (mg_bc_*, include/mg_hip.h)
     def bc_set_faces(self, mask):

@@ -44,32 +44,7 @@
 namespace mg {
 namespace {
 
-enum { FXLO = 1, FXHI = 2, FYLO = 4, FYHI = 8, FZLO = 16, FZHI = 32 };   // enum mg_face
-
-// the faces node (z, y, x) lies on, as mg_face bits
-__device__ __forceinline__ int bc_faces(const Geom &g, int z, int y, int x)
-{
-    int f = (x == 0 ? FXLO : 0) | (x == g.nx - 1 ? FXHI : 0) | (y == 0 ? FYLO : 0) | (y == g.ny - 1 ? FYHI : 0);
-    if (g.dim == 3) {
-        const int gz = g.gz0 + z;
-        f |= (gz == 0 ? FZLO : 0) | (gz == g.gnz - 1 ? FZHI : 0);
-    }
-    return f;
-}
-
-// element indices of the six neighbours of unknown i on faces f (all of them Neumann): the mirror image where one is missing
-struct BcNb { long long zm, ym, xm, xp, yp, zp; };
-__device__ __forceinline__ BcNb bc_neighbours(const Geom &g, long long i, int f)
-{
-    BcNb n;
-    n.xm = (f & FXLO) ? i + 1 : i - 1;
-    n.xp = (f & FXHI) ? i - 1 : i + 1;
-    n.ym = (f & FYLO) ? i + g.pitch : i - g.pitch;
-    n.yp = (f & FYHI) ? i - g.pitch : i + g.pitch;
-    n.zm = (f & FZLO) ? i + g.plane : i - g.plane;
-    n.zp = (f & FZHI) ? i - g.plane : i + g.plane;
-    return n;
-}
+// the face bits, bc_faces and bc_neighbours are mg_opfamily.h's: mg_vc.hip mirrors with them too
 
 template <typename T, int DIM>
 __device__ __forceinline__ T bc_point_res(const Geom &g, const Coef<T> &c, int mask, const T *u, const T *b, int z, int y, int x)

@@ -311,6 +311,19 @@ int mg_vc_direction(mg_handle h, double beta, int arr_z, int arr_p, int arr_pn, 
     MG_H(h);
     return guarded([&] { return h->impl->vc_direction(beta, arr_z, arr_p, arr_pn, arr_q, pq); });
 }
+int mg_vc_set_faces(mg_handle h, int mask) { MG_H(h); return guarded([&] { return h->impl->vc_set_faces(mask); }); }
+int mg_vc_get_faces(mg_handle h, int *mask)
+{
+    MG_H(h);
+    if (!mask) return bad("mg_vc_get_faces: null output");
+    return h->impl->vc_get_faces(mask);
+}
+int mg_vc_restrict(mg_handle h, int fine_level, int kind, int arr_src, int arr_dst)
+{
+    MG_H(h);
+    return guarded([&] { return h->impl->vc_restrict(fine_level, kind, arr_src, arr_dst); });
+}
+int mg_vc_project(mg_handle h, int level, int arr, double *mean) { MG_H(h); return guarded([&] { return h->impl->vc_project(level, arr, mean); }); }
 int mg_bc_set_faces(mg_handle h, int mask) { MG_H(h); return guarded([&] { return h->impl->bc_set_faces(mask); }); }
 int mg_bc_get_faces(mg_handle h, int *mask)
 {

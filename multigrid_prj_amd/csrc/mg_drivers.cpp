@@ -143,10 +143,14 @@ int Solver::precondition(void **z, void *r, bool vc)
 // The flexible CG iteration of mg_pcg_solve and mg_vc_pcg_solve on level 0. What the two operators do differently comes in:
 // residual_sum(r, v): r = b - A x (r may be null), *v = r.r, fetched (it synchronises); direction_apply(z, p, pn, q): pn = z +
 // beta p, q = A pn, returns the number of partial sums of pn.q; vc: precondition()'s flag.
+// vc_mask != 0: L is self-adjoint in the inner product of the weights w (1/2 per Neumann face of a node), so z.r, z.q and
+// p.q carry them (the direction kernel's partials come weighted); the stopping test stays the plain norm. In the singular case
+// the iteration lives on the complement of the constants: RHS(0) is projected first, z after every cycle, x at the end.
 template <typename T, class ResidualSum, class DirectionApply>
 int Solver::pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply direction_apply, double tol, int maxit, double *hist,
-                       int hist_cap, int *n_hist, mg_krylov_stats *st)
+                       int hist_cap, int *n_hist, mg_krylov_stats *st, int vc_mask, bool singular)
 {
+    if (singular) MG_TRY(bc_project_t<T>(vc_mask, 0, MG_ARR_RHS, nullptr));
     Level &L0 = lv_[0];
     const Geom &g = L0.g;
     auto kp = [&](int k) { return reinterpret_cast<T *>(kry_[k]) + L0.gh * g.plane; };
@@ -160,7 +164,8 @@ int Solver::pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply directi
     MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
     // Dirichlet rows are identity rows carrying the boundary data: x takes b's values there, after which r, z, p and q
     // vanish on the boundary and the iteration lives on the interior, where A is symmetric positive definite
-    launch_cg_boundary_copy<T>(stream_, g, x, b);
+    if (vc_mask) launch_bc_dirichlet_copy<T>(stream_, g, vc_mask, x, b);
+    else launch_cg_boundary_copy<T>(stream_, g, x, b);
     MG_HIP(hipGetLastError());
     double rr0 = 0;
     MG_TRY(residual_sum(kp(KR), &rr0));   // r0 = b - A x0, r0.r0
@@ -176,7 +181,9 @@ int Solver::pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply directi
         MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));   // p_{-1} = 0: p_0 = z_0 + 0 p_{-1} = z_0
         auto direction = [&](int mode) -> int {   // z = M r, gamma, beta, p_{k+1} = z + beta p_k, q = A p_{k+1}, alpha
             MG_TRY(precondition(&kry_[KZ], kry_[KR], vc));
-            int np = launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
+            if (singular) MG_TRY(bc_project_ptr_t<T>(vc_mask, g, kp(KZ), nullptr));   // fetches the mean: a second synchronisation per iteration, in this case only
+            int np = vc_mask ? launch_vc_cg_wdots<T>(stream_, g, vc_mask, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_)
+                             : launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
             launch_cg_tail(stream_, mode, d_cg_part_, np, d_cg_);
             np = direction_apply(kp(KZ), kp(pc), kp(pn), kp(KQ));
             launch_cg_tail(stream_, CG_TAIL_ALPHA, d_cg_part_, np, d_cg_);
@@ -190,7 +197,7 @@ int Solver::pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply directi
             launch_cg_tail(stream_, CG_TAIL_RR, d_cg_part_, np, d_cg_);
             MG_HIP(hipGetLastError());
             MG_HIP(hipMemcpyAsync(h_cg_, d_cg_, sizeof(CgScalars), hipMemcpyDeviceToHost, stream_));
-            MG_HIP(hipStreamSynchronize(stream_));   // the one host synchronisation per iteration: the stopping test
+            MG_HIP(hipStreamSynchronize(stream_));   // the stopping test: the one host synchronisation per iteration (the singular masked case has the projection's too)
             if (h_cg_->bad) { out.status = 2; break; }   // the update was skipped: x is the last iterate
             out.iters = k + 1;
             const double rel = std::sqrt(h_cg_->rr / nb);
@@ -200,6 +207,7 @@ int Solver::pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply directi
             MG_TRY(direction(CG_TAIL_BETA));
         }
     }
+    if (singular) MG_TRY(bc_project_t<T>(vc_mask, 0, MG_ARR_U, nullptr));
     double nr = 0;
     MG_TRY(residual_sum((T *)nullptr, &nr));   // the true residual of the returned x
     out.relres_true = std::sqrt(nr / nb);
@@ -1105,7 +1113,9 @@ int Solver::eig_kernel(int kernel, int nw, int np, const double *coef, const dou
 // prolongation -- those kernels carry the constant stencil in registers.
 //
 // vc (section 18): L = sigma I - div(a grad .) with a nodal coefficient array per level (Level::vc_a; level l + 1 is the
-// full-weighted level l). The kernels are in mg_vc.hip; the transfers are the handle's own.
+// full-weighted level l). The kernels are in mg_vc.hip; the transfers are the handle's own. With a face mask (vc_mask_,
+// section 22) the faces in it are zero-flux walls: the kernels mirror, and the restriction, the projection of the singular
+// case and the Dirichlet copy are mg_bc.hip's with this mask. With mask 0 every launch is the one it was without it.
 template <typename T>
 struct Solver::VcFam {
     typedef T type;
@@ -1117,44 +1127,56 @@ struct Solver::VcFam {
     static int residual(Solver &s, int l, const T *x, const T *b, T *r)
     {
         const Level &L = s.lv_[l];
-        return launch_vc_residual<T>(s.stream_, L.g, L.coef, s.shift_, x, s.vcptr<T>(l), b, r, s.d_partials_, s.o4_partials_cap_, s.vc_plain_);
+        return launch_vc_residual<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, x, s.vcptr<T>(l), b, r, s.d_partials_, s.o4_partials_cap_, s.vc_plain_);
     }
     static void jacobi(Solver &s, int l, const T *x, const T *b, T *out)
     {
         const Level &L = s.lv_[l];
-        launch_vc_jacobi<T>(s.stream_, L.g, L.coef, s.shift_, (T)s.d_.omega, x, s.vcptr<T>(l), b, out, s.vc_plain_);
+        launch_vc_jacobi<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, (T)s.d_.omega, x, s.vcptr<T>(l), b, out, s.vc_plain_);
     }
     static void rb_colour(Solver &s, int l, int colour, T *x, const T *b)
     {
         const Level &L = s.lv_[l];
-        launch_vc_rb_colour<T>(s.stream_, L.g, L.coef, s.shift_, colour, x, s.vcptr<T>(l), b);
+        launch_vc_rb_colour<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, colour, x, s.vcptr<T>(l), b);
     }
     static void coarse(Solver &s, int l, T *x, T *tmp, const T *b)
     {
         const Level &L = s.lv_[l];
-        launch_vc_coarse<T>(s.stream_, L.g, L.coef, s.shift_, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.vcptr<T>(l), s.d_.coarse_maxit,
+        launch_vc_coarse<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.vcptr<T>(l), s.d_.coarse_maxit,
                             s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
     }
     static void heat_rhs(Solver &s, double dt, double theta, const T *u, const T *f, T *out)
     {
         const Level &L = s.lv_[0];
+        if (theta == 1.0 && s.vc_mask_) {   // the operator's value is multiplied by zero and the mask decides which nodes copy u:
+            launch_bc_heat_rhs<T>(s.stream_, L.g, coef0_of<T>(L), s.vc_mask_, dt, theta, u, f, out, s.vc_plain_);   // mg_bc.hip's stencil-free form
+            return;
+        }
         if (theta == 1.0) {   // the operator's value is multiplied by zero: mg_heat.hip's stencil-free form, same Dirichlet nodes
             const double coef0[4] = {L.coef[0], L.coef[1], L.coef[2], L.cd0};
             launch_heat_rhs<T>(s.stream_, L.g, coef0, dt, theta, u, f, out);
             return;
         }
-        launch_vc_heat_rhs<T>(s.stream_, L.g, L.coef, dt, theta, u, s.vcptr<T>(0), f, out, s.vc_plain_);
+        launch_vc_heat_rhs<T>(s.stream_, L.g, L.coef, s.vc_mask_, dt, theta, u, s.vcptr<T>(0), f, out, s.vc_plain_);
     }
     static int down(Solver &s, int l)
     {
-        MG_TRY(s.restrict_t<T>(l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
+        // injecting the residual at coarse nodes of a Neumann face makes the cycle diverge, as in section 19
+        if (s.vc_mask_) MG_TRY(s.bc_restrict_t<T>(s.vc_mask_, l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
+        else MG_TRY(s.restrict_t<T>(l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
         return s.zero_array(MG_ARR_U, l + 1);
     }
     static int up(Solver &s, int l) { return s.prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U); }
-    // mg_vc_solve: nothing to project; U = RHS on the Dirichlet nodes
-    static int solve_begin(Solver &) { return MG_OK; }
-    static int solve_end(Solver &) { return MG_OK; }
-    static void dirichlet_copy(Solver &s) { launch_cg_boundary_copy<T>(s.stream_, s.lv_[0].g, s.ptr<T>(MG_ARR_U, 0), s.ptr<T>(MG_ARR_RHS, 0)); }
+    // mg_vc_solve: U = RHS on the Dirichlet nodes; all faces Neumann and no shift: RHS(0) is projected first, U(0) at the end
+    static int solve_begin(Solver &s) { return s.vc_singular() ? s.bc_project_t<T>(s.vc_mask_, 0, MG_ARR_RHS, nullptr) : MG_OK; }
+    static int solve_end(Solver &s) { return s.vc_singular() ? s.bc_project_t<T>(s.vc_mask_, 0, MG_ARR_U, nullptr) : MG_OK; }
+    static void dirichlet_copy(Solver &s)
+    {
+        T *const x = s.ptr<T>(MG_ARR_U, 0);
+        const T *const b = s.ptr<T>(MG_ARR_RHS, 0);
+        if (s.vc_mask_) launch_bc_dirichlet_copy<T>(s.stream_, s.lv_[0].g, s.vc_mask_, x, b);
+        else launch_cg_boundary_copy<T>(s.stream_, s.lv_[0].g, x, b);
+    }
 };
 
 // bc (section 19): the handle's constant operator with zero-flux walls on the faces of a mask (enum mg_face): nodes that lie
@@ -1193,14 +1215,14 @@ struct Solver::BcFam {
     }
     static int down(Solver &s, int l)
     {
-        MG_TRY(s.bc_restrict_t<T>(l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
+        MG_TRY(s.bc_restrict_t<T>(s.bc_mask_, l, s.d_.restriction, MG_ARR_TMP, MG_ARR_RHS));
         return s.zero_array(MG_ARR_U, l + 1);
     }
     static int up(Solver &s, int l) { return s.prolong_t<T>(l + 1, 1, MG_ARR_U, MG_ARR_U); }
     // mg_bc_solve with all faces Neumann and no shift: the constants are the null space, RHS(0) is projected onto the range
     // first (it stays projected) and U(0) is projected at the end
-    static int solve_begin(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(0, MG_ARR_RHS, nullptr) : MG_OK; }
-    static int solve_end(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(0, MG_ARR_U, nullptr) : MG_OK; }
+    static int solve_begin(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(s.bc_mask_, 0, MG_ARR_RHS, nullptr) : MG_OK; }
+    static int solve_end(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(s.bc_mask_, 0, MG_ARR_U, nullptr) : MG_OK; }
     static void dirichlet_copy(Solver &s)
     {
         launch_bc_dirichlet_copy<T>(s.stream_, s.lv_[0].g, s.bc_mask_, s.ptr<T>(MG_ARR_U, 0), s.ptr<T>(MG_ARR_RHS, 0));
@@ -1536,7 +1558,10 @@ int Solver::vc_alloc()
 template <typename T>
 int Solver::vc_restrict_all_t()
 {
-    for (int l = 0; l + 1 < d_.levels; l++) launch_restrict_fw<T>(stream_, lv_[l].g, lv_[l + 1].g, vcptr<T>(l), vcptr<T>(l + 1));
+    for (int l = 0; l + 1 < d_.levels; l++) {
+        if (vc_mask_) launch_bc_restrict_fw<T>(stream_, lv_[l].g, lv_[l + 1].g, vc_mask_, vcptr<T>(l), vcptr<T>(l + 1));   // keeps a_min <= a_c <= a_max
+        else launch_restrict_fw<T>(stream_, lv_[l].g, lv_[l + 1].g, vcptr<T>(l), vcptr<T>(l + 1));
+    }
     MG_HIP(hipGetLastError());
     return MG_OK;
 }
@@ -1606,9 +1631,9 @@ int Solver::vc_pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_h
         return MG_OK;
     };
     auto direction_apply = [&](const T *z, const T *p, T *pn, T *q) {
-        return launch_vc_cg_direction<T>(stream_, L0.g, L0.coef, shift_, z, p, vcptr<T>(0), pn, q, d_cg_, d_cg_part_);
+        return launch_vc_cg_direction<T>(stream_, L0.g, L0.coef, shift_, vc_mask_, z, p, vcptr<T>(0), pn, q, d_cg_, d_cg_part_);
     };
-    return pcg_body_t<T>(true, residual_sum, direction_apply, tol, maxit, hist, hist_cap, n_hist, st);
+    return pcg_body_t<T>(true, residual_sum, direction_apply, tol, maxit, hist, hist_cap, n_hist, st, vc_mask_, vc_mask_ != 0 && vc_singular());
 }
 
 // the direction kernel alone on level-0 arrays (mg_vc_direction): kernel-level checks and measurements, as mg_pcg_kernel
@@ -1619,8 +1644,8 @@ int Solver::vc_direction_t(double beta, const int *a, double *pq)
     *h_cg_ = CgScalars{};
     h_cg_->alpha = h_cg_->beta = beta;
     MG_HIP(hipMemcpyAsync(d_cg_, h_cg_, sizeof(CgScalars), hipMemcpyHostToDevice, stream_));
-    const int np = launch_vc_cg_direction<T>(stream_, L0.g, L0.coef, shift_, ptr<T>(a[0], 0), ptr<T>(a[1], 0), vcptr<T>(0), ptr<T>(a[2], 0),
-                                             ptr<T>(a[3], 0), d_cg_, d_cg_part_);
+    const int np = launch_vc_cg_direction<T>(stream_, L0.g, L0.coef, shift_, vc_mask_, ptr<T>(a[0], 0), ptr<T>(a[1], 0), vcptr<T>(0),
+                                             ptr<T>(a[2], 0), ptr<T>(a[3], 0), d_cg_, d_cg_part_);
     launch_reduce_final(stream_, d_cg_part_, np, d_cg_dot_);
     MG_HIP(hipGetLastError());
     if (pq) {
@@ -1652,12 +1677,58 @@ int Solver::vc_pcg_solve(double tol, int maxit, double *hist, int hist_cap, int 
                               : vc_pcg_t<float>(tol, maxit, hist, hist_cap, n_hist, st);
 }
 
+// Neumann faces of the variable-coefficient operator (section 22). The mask is handle state like bc_mask_ and independent of
+// it; with a coefficient set, the coarse levels are restricted again from the stored level 0 with the new mask.
+int Solver::face_mask_check(const char *fn, int mask)
+{
+    if (mask < 0 || mask > 63) { set_last_error(std::string(fn) + ": the mask must be a combination of the six MG_FACE_* bits"); return MG_ERR_BAD_ARG; }
+    if (d_.dim == 2 && (mask & (MG_FACE_ZLO | MG_FACE_ZHI))) { set_last_error(std::string(fn) + ": a 2-D handle has no z faces"); return MG_ERR_BAD_ARG; }
+    return MG_OK;
+}
+
+int Solver::vc_set_faces(int mask)
+{
+    MG_TRY(driver_begin("mg_vc_set_faces", REFUSE_DIST));
+    MG_TRY(face_mask_check("mg_vc_set_faces", mask));
+    if (mask == vc_mask_) return MG_OK;
+    const int old = vc_mask_;
+    vc_mask_ = mask;
+    if (vc_set_) {
+        int rc = d_.dtype == MG_F64 ? vc_restrict_all_t<double>() : vc_restrict_all_t<float>();
+        if (rc != MG_OK) {   // back to the mask the call found, and the coarse coefficients that go with it
+            vc_mask_ = old;
+            (void)(d_.dtype == MG_F64 ? vc_restrict_all_t<double>() : vc_restrict_all_t<float>());
+            return rc;
+        }
+    }
+    return MG_OK;
+}
+
+int Solver::vc_get_faces(int *mask) const
+{
+    if (!mask) return MG_ERR_BAD_ARG;
+    *mask = vc_mask_;
+    return MG_OK;
+}
+
+int Solver::vc_restrict(int fine_level, int kind, int arr_src, int arr_dst)
+{
+    MG_TRY(driver_begin("mg_vc_restrict", REFUSE_DIST));   // a transfer: no coefficient is needed
+    return fam_restrict("mg_vc_restrict", vc_mask_, fine_level, kind, arr_src, arr_dst);
+}
+
+int Solver::vc_project(int level, int arr, double *mean)
+{
+    MG_TRY(driver_begin("mg_vc_project", REFUSE_DIST));
+    if (!check_arr(arr, level, "mg_vc_project")) return MG_ERR_BAD_ARG;
+    return d_.dtype == MG_F64 ? bc_project_t<double>(vc_mask_, level, arr, mean) : bc_project_t<float>(vc_mask_, level, arr, mean);
+}
+
 // ---------------------------------------------------------------- what only mg_bc_* has
 int Solver::bc_set_faces(int mask)
 {
     MG_TRY(driver_begin("mg_bc_set_faces", REFUSE_DIST));
-    if (mask < 0 || mask > 63) { set_last_error("mg_bc_set_faces: the mask must be a combination of the six MG_FACE_* bits"); return MG_ERR_BAD_ARG; }
-    if (d_.dim == 2 && (mask & (MG_FACE_ZLO | MG_FACE_ZHI))) { set_last_error("mg_bc_set_faces: a 2-D handle has no z faces"); return MG_ERR_BAD_ARG; }
+    MG_TRY(face_mask_check("mg_bc_set_faces", mask));
     bc_mask_ = mask;
     return MG_OK;
 }
@@ -1670,55 +1741,65 @@ int Solver::bc_get_faces(int *mask) const
 }
 
 template <typename T>
-int Solver::bc_restrict_t(int fl, int kind, int as, int ad)
+int Solver::bc_restrict_t(int mask, int fl, int kind, int as, int ad)
 {
     if (ad == MG_ARR_RHS) lv_[fl + 1].rhs_halo_ok = false;
     if (kind == MG_RESTRICT_FULLW)
-        launch_bc_restrict_fw<T>(stream_, lv_[fl].g, lv_[fl + 1].g, bc_mask_, ptr<T>(as, fl), ptr<T>(ad, fl + 1));
+        launch_bc_restrict_fw<T>(stream_, lv_[fl].g, lv_[fl + 1].g, mask, ptr<T>(as, fl), ptr<T>(ad, fl + 1));
     else
         launch_inject<T>(stream_, lv_[fl].g, lv_[fl + 1].g, ptr<T>(as, fl), ptr<T>(ad, fl + 1));
     MG_HIP(hipGetLastError());
     return MG_OK;
 }
 
+int Solver::fam_restrict(const char *fn, int mask, int fine_level, int kind, int arr_src, int arr_dst)
+{
+    if (fine_level < 0 || fine_level + 1 >= d_.levels || !check_arr(arr_src, fine_level, fn) ||
+        !check_arr(arr_dst, fine_level + 1, fn) || (kind != MG_RESTRICT_INJECT && kind != MG_RESTRICT_FULLW)) {
+        set_last_error(std::string(fn) + ": bad level / array / kind");
+        return MG_ERR_BAD_ARG;
+    }
+    return d_.dtype == MG_F64 ? bc_restrict_t<double>(mask, fine_level, kind, arr_src, arr_dst)
+                              : bc_restrict_t<float>(mask, fine_level, kind, arr_src, arr_dst);
+}
+
 int Solver::bc_restrict(int fine_level, int kind, int arr_src, int arr_dst)
 {
     MG_TRY(fam_check<BcFam>("mg_bc_restrict", 0));
-    if (fine_level < 0 || fine_level + 1 >= d_.levels || !check_arr(arr_src, fine_level, "mg_bc_restrict") ||
-        !check_arr(arr_dst, fine_level + 1, "mg_bc_restrict") || (kind != MG_RESTRICT_INJECT && kind != MG_RESTRICT_FULLW)) {
-        set_last_error("mg_bc_restrict: bad level / array / kind");
-        return MG_ERR_BAD_ARG;
-    }
-    return d_.dtype == MG_F64 ? bc_restrict_t<double>(fine_level, kind, arr_src, arr_dst)
-                              : bc_restrict_t<float>(fine_level, kind, arr_src, arr_dst);
+    return fam_restrict("mg_bc_restrict", bc_mask_, fine_level, kind, arr_src, arr_dst);
 }
 
 // c = (sum w v) / (sum w), v -= (T)c. sum w is the product over the axes of (nodes - half a node per Neumann face): exact in double.
 template <typename T>
-int Solver::bc_project_t(int level, int arr, double *mean)
+int Solver::bc_project_ptr_t(int mask, const Geom &g, T *v, double *mean)
 {
-    Level &L = lv_[level];
-    if (arr == MG_ARR_RHS) L.rhs_halo_ok = false;
-    const Geom &g = L.g;
-    const int np = launch_bc_wsum<T>(stream_, g, bc_mask_, ptr<T>(arr, level), d_partials_, o4_partials_cap_);
+    const int np = launch_bc_wsum<T>(stream_, g, mask, v, d_partials_, o4_partials_cap_);
     launch_reduce_final(stream_, d_partials_, np, d_scal_ + SC_FAM_SUM);
     MG_HIP(hipGetLastError());
     MG_TRY(fetch_scalars(SC_FAM_SUM, d_scal_ + SC_FAM_SUM));
-    auto halves = [&](int lo, int hi) { return 0.5 * (((bc_mask_ & lo) ? 1 : 0) + ((bc_mask_ & hi) ? 1 : 0)); };
+    auto halves = [&](int lo, int hi) { return 0.5 * (((mask & lo) ? 1 : 0) + ((mask & hi) ? 1 : 0)); };
     double sw = ((double)g.nx - halves(MG_FACE_XLO, MG_FACE_XHI)) * ((double)g.ny - halves(MG_FACE_YLO, MG_FACE_YHI));
     if (g.dim == 3) sw *= (double)g.gnz - halves(MG_FACE_ZLO, MG_FACE_ZHI);
     const double c = h_scal_[SC_FAM_SUM] / sw;
-    launch_bc_shift<T>(stream_, g, (T)c, ptr<T>(arr, level));
+    launch_bc_shift<T>(stream_, g, (T)c, v);
     MG_HIP(hipGetLastError());
     if (mean) *mean = c;
     return MG_OK;
+}
+
+template <typename T>
+int Solver::bc_project_t(int mask, int level, int arr, double *mean)
+{
+    Level &L = lv_[level];
+    if (arr == MG_ARR_RHS) L.rhs_halo_ok = false;
+    return bc_project_ptr_t<T>(mask, L.g, ptr<T>(arr, level), mean);
 }
 
 int Solver::bc_project(int level, int arr, double *mean)
 {
     MG_TRY(fam_check<BcFam>("mg_bc_project", 0));
     if (!check_arr(arr, level, "mg_bc_project")) return MG_ERR_BAD_ARG;
-    return d_.dtype == MG_F64 ? bc_project_t<double>(level, arr, mean) : bc_project_t<float>(level, arr, mean);
+    return d_.dtype == MG_F64 ? bc_project_t<double>(bc_mask_, level, arr, mean) : bc_project_t<float>(bc_mask_, level, arr, mean);
 }
 
 int Solver::bc_set_form(int form) { return set_form("mg_bc_set_form", form, &bc_plain_); }

@@ -305,31 +305,37 @@ int launch_o4_correct_residual(hipStream_t s, const Geom &g, const double w[3], 
 
 // ---- variable-coefficient operator (mg_vc.hip, driven by Solver::vc_*) ----
 // coef = {cx, cy, cz, cd} of the level in fp64 (cd is not used: the diagonal is built from a), sigma the handle's shift; a:
-// the level's coefficient array (level-shaped, ghost planes and padding zero). plain: never the marching tile.
+// the level's coefficient array (level-shaped, ghost planes and padding zero). plain: never the marching tile. mask: the
+// Neumann faces (enum mg_face; mg_vc_set_faces): missing neighbours are mirror images, for a and u alike, and the Dirichlet
+// nodes are those on a face outside the mask; 0 launches the kernels a handle without a mask has always run.
 // r = b - L u (r == nullptr: norm only); one partial sum of r^2 per workgroup in `partials` (room for `cap`), returns how many
 template <typename T>
-int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, const T *u, const T *a, const T *b, T *r,
+int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, const T *u, const T *a, const T *b, T *r,
                        double *partials, int cap, bool plain);
 // one Jacobi sweep, out of place (out must not alias u)
 template <typename T>
-void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, T omega, const T *u, const T *a, const T *b,
+void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, const T *u, const T *a, const T *b,
                       T *out, bool plain);
 // launch_heat_rhs with the UNSHIFTED operator -div(a grad .) (coef's cd and the handle's shift are not used): out = right-hand
 // side of one theta step from u (and the source f; nullptr: f = 0), u on Dirichlet nodes. out must not alias u, a or f.
 template <typename T>
-void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], double dt, double theta, const T *u, const T *a, const T *f,
-                        T *out, bool plain);
+void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], int mask, double dt, double theta, const T *u, const T *a,
+                        const T *f, T *out, bool plain);
 // one colour pass of red-black Gauss-Seidel, in place
 template <typename T>
-void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int colour, T *u, const T *a, const T *b);
+void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int colour, T *u, const T *a, const T *b);
 // launch_coarse_solve's loop with the vc sweep (smoother 1: Jacobi, 2: red-black) and the vc residual, one workgroup
 template <typename T>
-void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, T omega, int smoother, T *x, T *tmp,
+void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, int smoother, T *x, T *tmp,
                       const T *rhs, const T *a, int maxit, double tol, int fixed, CoarseOut *d_out);
-// launch_cg_direction_apply with q = L pn; partials of pn.q (at most cg_partials_capacity() / 2), returns how many
+// launch_cg_direction_apply with q = L pn; partials of pn.q (at most cg_partials_capacity() / 2), returns how many. With a
+// mask pn and q are 0 on ITS Dirichlet nodes and the partials are those of sum w pn q, w = 1/2 per Neumann face of the node
 template <typename T>
-int launch_vc_cg_direction(hipStream_t s, const Geom &g, const double coef[4], double sigma, const T *z, const T *p, const T *a, T *pn,
-                           T *q, const CgScalars *sc, double *partials);
+int launch_vc_cg_direction(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, const T *z, const T *p, const T *a,
+                           T *pn, T *q, const CgScalars *sc, double *partials);
+// launch_cg_dots with the weights of the mask: partials of sum w z r, then of sum w z q
+template <typename T>
+int launch_vc_cg_wdots(hipStream_t s, const Geom &g, int mask, const T *z, const T *r, const T *q, const CgScalars *sc, double *partials);
 
 // ---- the constant operator with Neumann faces (mg_bc.hip, driven by Solver::bc_*) ----
 // c: the level's Coef (shift included); mask: the Neumann faces (enum mg_face), 0 = the existing kernels' results bit for

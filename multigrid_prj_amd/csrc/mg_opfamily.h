@@ -31,6 +31,37 @@ constexpr int OP_THREADS = 256, OP_MAX_BLOCKS = 2048;
 constexpr int MBW = 4, MRY = 2;   // waves per workgroup / rows per wave of the marching tiles
 enum { OP_RES = 0, OP_JAC = 1, OP_RB = 2, OP_STEP = 3 };
 
+// ---------------------------------------------------------------- Neumann faces (mg_bc.hip, and mg_vc.hip with a face mask)
+enum { FXLO = 1, FXHI = 2, FYLO = 4, FYHI = 8, FZLO = 16, FZHI = 32 };   // enum mg_face
+
+// the faces node (z, y, x) lies on, as mg_face bits
+__device__ __forceinline__ int bc_faces(const Geom &g, int z, int y, int x)
+{
+    int f = (x == 0 ? FXLO : 0) | (x == g.nx - 1 ? FXHI : 0) | (y == 0 ? FYLO : 0) | (y == g.ny - 1 ? FYHI : 0);
+    if (g.dim == 3) {
+        const int gz = g.gz0 + z;
+        f |= (gz == 0 ? FZLO : 0) | (gz == g.gnz - 1 ? FZHI : 0);
+    }
+    return f;
+}
+
+// element indices of the six neighbours of unknown i on faces f (all of them Neumann): the mirror image where one is missing
+struct BcNb { long long zm, ym, xm, xp, yp, zp; };
+__device__ __forceinline__ BcNb bc_neighbours(const Geom &g, long long i, int f)
+{
+    BcNb n;
+    n.xm = (f & FXLO) ? i + 1 : i - 1;
+    n.xp = (f & FXHI) ? i - 1 : i + 1;
+    n.ym = (f & FYLO) ? i + g.pitch : i - g.pitch;
+    n.yp = (f & FYHI) ? i - g.pitch : i + g.pitch;
+    n.zm = (f & FZLO) ? i + g.plane : i - g.plane;
+    n.zp = (f & FZHI) ? i - g.plane : i + g.plane;
+    return n;
+}
+
+// w = 1/2 per Neumann face the node lies on (nf = 0 .. 3: at most one face per axis)
+__device__ __forceinline__ double bc_weight(int nf) { return nf == 0 ? 1.0 : (nf == 1 ? 0.5 : (nf == 2 ? 0.25 : 0.125)); }
+
 // The scalars of one theta step of u_t = -N0(u) + f (mg_*_heat_rhs), passed to the kernels by value:
 // rdt = (T)(1 / dt), omt = (T)(1 - theta), rth = (T)(1 / theta). The other modes do not look at them.
 template <typename T>

@@ -167,6 +167,12 @@ public:
     int vc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);
     int vc_pcg_solve(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     int vc_direction(double beta, int arr_z, int arr_p, int arr_pn, int arr_q, double *pq);   // the direction kernel alone
+    // Neumann faces of mg_vc_*: a second face mask, independent of bc_set_faces; with a non-zero mask the coarse coefficients
+    // are the MIRRORED full weighting of the stored level 0 (set_faces re-restricts when a coefficient is set)
+    int vc_set_faces(int mask);
+    int vc_get_faces(int *mask) const;
+    int vc_restrict(int fine_level, int kind, int arr_src, int arr_dst);   // mg_bc_restrict with this mask
+    int vc_project(int level, int arr, double *mean);                      // mg_bc_project with this mask
     // the constant operator with Neumann faces (mg_bc_*): a face mask (enum mg_face), nothing allocated
     int bc_set_faces(int mask);
     int bc_get_faces(int *mask) const;
@@ -281,10 +287,13 @@ private:
     // this way keep their ghost planes and padding columns zero: nothing writes them afterwards.
     int alloc_zeroed(void **p, size_t nbytes);
     template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
-    // pcg_t's and vc_pcg_t's iteration; the two callables are the operator's residual with its sum and its direction kernel
+    // pcg_t's and vc_pcg_t's iteration; the two callables are the operator's residual with its sum and its direction kernel.
+    // vc_mask != 0 (mg_vc_pcg_solve on a handle with Neumann faces): the Dirichlet copy and the two dots are the mask's
+    // (launch_bc_dirichlet_copy, launch_vc_cg_wdots); singular (every face in the mask and no shift: the caller decides): RHS(0),
+    // every z and the final x are projected, each projection with a fetch of its mean
     template <typename T, class ResidualSum, class DirectionApply>
     int pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply direction_apply, double tol, int maxit, double *hist, int hist_cap,
-                   int *n_hist, mg_krylov_stats *st);
+                   int *n_hist, mg_krylov_stats *st, int vc_mask = 0, bool singular = false);
     // *z = M r: one mg_solve outer iteration from zero with the buffers *z and r in level 0's U / RHS slots. The cycle may leave
     // its result in the buffer that was TMP: *z is whatever U points at afterwards, and TMP keeps the other buffer.
     // vc: the cycle is mg_vc_cycle's (mg_vc_pcg_solve) and no Gauss-Seidel sweeps come before it
@@ -437,15 +446,21 @@ private:
     bool vc_set_ = false, vc_plain_ = false;
     int vc_alloc();
     template <typename T> T *vcptr(int level) const { return reinterpret_cast<T *>(lv_[level].vc_a) + lv_[level].gh * lv_[level].g.plane; }
-    template <typename T> int vc_restrict_all_t();   // vc_a(l + 1) = full weighting of vc_a(l), every transition
+    template <typename T> int vc_restrict_all_t();   // vc_a(l + 1) = full weighting of vc_a(l) (mirrored with a mask), every transition
+    int vc_mask_ = 0;   // the Neumann faces of mg_vc_* (mg_vc_set_faces), 0 = all Dirichlet
+    bool vc_singular() const { return vc_mask_ == (d_.dim == 3 ? 63 : 15) && shift_ == 0.0; }   // constants are the null space
     template <typename T> int vc_direction_t(double beta, const int *arrs, double *pq);
     template <typename T> int vc_pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     // Neumann-face drivers (mg_bc_*): the mask of Neumann faces, 0 = all Dirichlet
     int bc_mask_ = 0;
     bool bc_plain_ = false;
     bool bc_singular() const { return bc_mask_ == (d_.dim == 3 ? 63 : 15) && shift_ == 0.0; }   // all faces Neumann, no shift: constants are the null space
-    template <typename T> int bc_restrict_t(int fl, int kind, int as, int ad);
-    template <typename T> int bc_project_t(int level, int arr, double *mean);   // synchronises: the mean is fetched
+    // the two below take the mask as an argument: mg_vc_* runs them with its own
+    template <typename T> int bc_restrict_t(int mask, int fl, int kind, int as, int ad);
+    template <typename T> int bc_project_t(int mask, int level, int arr, double *mean);   // synchronises: the mean is fetched
+    template <typename T> int bc_project_ptr_t(int mask, const Geom &g, T *v, double *mean);   // the same on a level-shaped buffer
+    int face_mask_check(const char *fn, int mask);
+    int fam_restrict(const char *fn, int mask, int fine_level, int kind, int arr_src, int arr_dst);
     // full-approximation-scheme drivers (mg_fas_*): the reaction gamma g(u), g of enum mg_fas_kind
     int fas_kind_ = MG_FAS_CUBIC;
     double fas_gamma_ = 0.0;

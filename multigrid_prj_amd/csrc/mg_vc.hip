@@ -11,6 +11,15 @@
 //                                  without a source: mg_vc_heat_rhs) on 3-D levels with rows long enough to fill a wave
 //                                  (vc_march_ok, mg_geom.h)
 //   k_vc_cg_direction<T, DIM>      k_cg_direction_apply (mg_krylov.hip) with q = L p'
+//   k_vcn_cg_direction<T, DIM>     the same with a face mask: mirrored neighbours, Dirichlet nodes by the mask, p'.q weighted
+//   k_vcn_cg_dots<T>               k_cg_dots (mg_krylov.hip) with the weights: sum w z r and sum w z q
+//
+// NEUMANN FACES (mg_vc_set_faces). A face mask (enum mg_face) names the zero-flux faces; the node
+// classes are mg_bc.hip's: a node on at least one face that is not in the mask is a Dirichlet node, every other node is an
+// unknown whose missing neighbour q is the mirror image inside the box, for a and for u alike, so a mirrored slot counts
+// twice in s and in d. Nothing else of the contract below changes. The template flag MIR selects that form; without it
+// (mask 0) every kernel is the code it was before the mask existed, and the launchers pick MIR only for a non-zero mask.
+// w = 1/2 per Neumann face a node lies on makes diag(w) L symmetric: the Krylov dots of a masked handle carry it.
 //
 // The marching tile is k_heat_rhs's (mg_heat.hip) with TWO marched fields: a lane owns one aligned 16-byte vector of x, a
 // wave covers 64 vectors of MRY = 2 rows, MBW = 4 waves are stacked in y and the workgroup marches zc planes with the
@@ -19,6 +28,10 @@
 // other row or two halo rows that hit L1 / L2. b is loaded and r / u' stored non-temporally, the block order is
 // XCD-aware, the odd last column is written as one full 128-byte line as in mg_heat.hip. Ghost planes and padding
 // columns are read (they exist and hold zeros) and what is computed from them is dropped: only Dirichlet nodes touch them.
+// With MIR the mirror is a select between values the lane holds anyway, for both fields, as in k_bc_march: the element at
+// x = 0 takes its right neighbour for the left one, row 0 takes row 1 for the halo row, plane 0 takes uzp / azp for uzm / azm
+// (and likewise at the high ends); no load and no branch is added in the interior. Only the odd last column of a 2^k + 1
+// row is computed from global memory by the plain form's point function, because with an x-hi Neumann face it is an unknown.
 //
 // Arithmetic contract (compiled with -ffp-contract=off; tests/vc_ref.py restates it in numpy), all in T, every operation
 // rounded separately, w_a = (T)(-c_a / 2) with c_a the level's off-diagonal of mg_level_coefficients:
@@ -51,35 +64,66 @@ __device__ __forceinline__ void vc_nb(T w, T ai, T aq, T uq, T &s, T &d)
     d = d + g;
 }
 
-// s and d at element i; uat(q, k) = u at element q, the k-th neighbour in row order (0: z-, 1: y-, 2: x-, 3: x+, 4: y+, 5: z+)
+// s and d at element i with the neighbours n (or their mirror images); uat(q, k) = u at element q, the k-th neighbour in
+// row order (0: z-, 1: y-, 2: x-, 3: x+, 4: y+, 5: z+)
 template <typename T, int DIM, typename F>
-__device__ __forceinline__ void vc_parts(F &&uat, const T *a, long long i, int pitch, long long plane, const VcCoef<T> &c, T &s, T &d)
+__device__ __forceinline__ void vc_parts(F &&uat, const T *a, long long i, const BcNb &n, const VcCoef<T> &c, T &s, T &d)
 {
     const T ai = a[i];
     s = (T)0;
     d = c.sigma;
-    if (DIM == 3) vc_nb<T>(c.wz, ai, a[i - plane], uat(i - plane, 0), s, d);
-    vc_nb<T>(c.wy, ai, a[i - pitch], uat(i - pitch, 1), s, d);
-    vc_nb<T>(c.wx, ai, a[i - 1], uat(i - 1, 2), s, d);
-    vc_nb<T>(c.wx, ai, a[i + 1], uat(i + 1, 3), s, d);
-    vc_nb<T>(c.wy, ai, a[i + pitch], uat(i + pitch, 4), s, d);
-    if (DIM == 3) vc_nb<T>(c.wz, ai, a[i + plane], uat(i + plane, 5), s, d);
+    if (DIM == 3) vc_nb<T>(c.wz, ai, a[n.zm], uat(n.zm, 0), s, d);
+    vc_nb<T>(c.wy, ai, a[n.ym], uat(n.ym, 1), s, d);
+    vc_nb<T>(c.wx, ai, a[n.xm], uat(n.xm, 2), s, d);
+    vc_nb<T>(c.wx, ai, a[n.xp], uat(n.xp, 3), s, d);
+    vc_nb<T>(c.wy, ai, a[n.yp], uat(n.yp, 4), s, d);
+    if (DIM == 3) vc_nb<T>(c.wz, ai, a[n.zp], uat(n.zp, 5), s, d);
 }
 
+__device__ __forceinline__ BcNb vc_straight(const Geom &g, long long i)
+{
+    return BcNb{i - g.plane, i - g.pitch, i - 1, i + 1, i + g.pitch, i + g.plane};
+}
+
+// the mask of a VcOp: no member without MIR, so the mask-0 kernels take the arguments they always took
+template <bool MIR>
+struct VcMask {
+    int mask;
+};
+template <>
+struct VcMask<false> {
+    static constexpr int mask = 0;
+};
+
 // the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h)
-template <typename T>
-struct VcOp {
+template <typename T, bool MIR = false>
+struct VcOp : VcMask<MIR> {
     typedef T type;
     VcCoef<T> c;
     const T *__restrict__ a;
+
+    // true at a Dirichlet node; else n = the neighbours of unknown i, mirrored on the Neumann faces it lies on
+    __device__ __forceinline__ bool fixed(const Geom &g, int z, int y, int x, long long i, BcNb &n) const
+    {
+        if (MIR) {
+            const int f = bc_faces(g, z, y, x);
+            if (f & ~this->mask) return true;
+            n = bc_neighbours(g, i, f);
+            return false;
+        }
+        if (on_boundary(g, z, y, x)) return true;
+        n = vc_straight(g, i);
+        return false;
+    }
 
     template <int DIM>
     __device__ __forceinline__ T res(const Geom &g, const T *u, const T *b, int z, int y, int x) const
     {
         const long long i = lidx(g, z, y, x);
-        if (on_boundary(g, z, y, x)) return b[i] - u[i];
+        BcNb n;
+        if (fixed(g, z, y, x, i, n)) return b[i] - u[i];
         T s, d;
-        vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, g.pitch, g.plane, c, s, d);
+        vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, n, c, s, d);
         return b[i] - (d * u[i] - s);
     }
 
@@ -88,9 +132,10 @@ struct VcOp {
     {
         const long long i = lidx(g, z, y, x);
         const T bi = b[i];
-        if (on_boundary(g, z, y, x)) return bi;
+        BcNb n;
+        if (fixed(g, z, y, x, i, n)) return bi;
         T s, d;
-        vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, g.pitch, g.plane, c, s, d);
+        vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, n, c, s, d);
         const T ps = (bi + s) / d;
         if (damped) {
             const T ui = u[i];
@@ -103,23 +148,35 @@ struct VcOp {
     template <int DIM>
     __device__ __forceinline__ bool n0(const Geom &g, const T *u, int z, int y, int x, bool stencil, T &v) const
     {
-        if (on_boundary(g, z, y, x)) return true;
+        const long long i = lidx(g, z, y, x);
+        BcNb n;
+        if (fixed(g, z, y, x, i, n)) return true;
         if (stencil) {
-            const long long i = lidx(g, z, y, x);
             T s, d;
-            vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, g.pitch, g.plane, c, s, d);
+            vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, n, c, s, d);
             v = d * u[i] - s;
         }
         return false;
     }
 };
 
+template <typename T, bool MIR>
+__host__ __device__ VcOp<T, MIR> vc_op(const VcCoef<T> &c, const T *a, int mask)
+{
+    VcOp<T, MIR> op;
+    op.c = c;
+    op.a = a;
+    if constexpr (MIR) op.mask = mask;
+    return op;
+}
+
 // ---------------------------------------------------------------- the marching tile (3-D)
-// OP_STEP: b is the source of the step (not loaded without SRC), st its scalars, c.sigma = 0; out = u on Dirichlet nodes
-template <typename T, int OP, bool SAVE, bool SRC = true>
+// OP_STEP: b is the source of the step (not loaded without SRC), st its scalars, c.sigma = 0; out = u on Dirichlet nodes.
+// MIR: the faces of `mask` are Neumann (not looked at otherwise)
+template <typename T, int OP, bool SAVE, bool SRC = true, bool MIR = false>
 __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T omega, const T *__restrict__ u, const T *__restrict__ a,
                                                        const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
-                                                       int nbx, int nby, int nbz, int zc, StepCoef<T> st)
+                                                       int nbx, int nby, int nbz, int zc, StepCoef<T> st, int mask)
 {
     constexpr int V = Vec16<T>::n;
     constexpr bool STORE = OP != OP_RES || SAVE;
@@ -201,13 +258,28 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                 const T ul = (e == 0) ? uxm : ucc[r][e > 0 ? e - 1 : 0], al = (e == 0) ? axm : acc_[r][e > 0 ? e - 1 : 0];
                 const T ur = (e == V - 1) ? uxp : ucc[r][e < V - 1 ? e + 1 : 0], ar = (e == V - 1) ? axp : acc_[r][e < V - 1 ? e + 1 : 0];
                 T s = (T)0, d = c.sigma;
-                vc_nb<T>(c.wz, ai, azm[r][e], uzm[r][e], s, d);
-                vc_nb<T>(c.wy, ai, aym[e], uym[e], s, d);
-                vc_nb<T>(c.wx, ai, al, ul, s, d);
-                vc_nb<T>(c.wx, ai, ar, ur, s, d);
-                vc_nb<T>(c.wy, ai, ayp[e], uyp[e], s, d);
-                vc_nb<T>(c.wz, ai, azp[r][e], uzp[r][e], s, d);
-                const bool bnd = rb || (x0 + e == 0) || (x0 + e == g.nx - 1);
+                bool bnd;
+                if constexpr (MIR) {
+                    // the mirror: a select between values the lane holds anyway, element by element; Dirichlet nodes by the mask
+                    const int yf = (yb + r == 0 ? FYLO : 0) | (yb + r == g.ny - 1 ? FYHI : 0);
+                    const int zf = (gz == 0 ? FZLO : 0) | (gz == g.gnz - 1 ? FZHI : 0);
+                    const int xf = (x0 + e == 0 ? FXLO : 0) | (x0 + e == g.nx - 1 ? FXHI : 0);
+                    vc_nb<T>(c.wz, ai, (zf & FZLO) ? azp[r][e] : azm[r][e], (zf & FZLO) ? uzp[r][e] : uzm[r][e], s, d);
+                    vc_nb<T>(c.wy, ai, (yf & FYLO) ? ayp[e] : aym[e], (yf & FYLO) ? uyp[e] : uym[e], s, d);
+                    vc_nb<T>(c.wx, ai, (xf & FXLO) ? ar : al, (xf & FXLO) ? ur : ul, s, d);
+                    vc_nb<T>(c.wx, ai, (xf & FXHI) ? al : ar, (xf & FXHI) ? ul : ur, s, d);
+                    vc_nb<T>(c.wy, ai, (yf & FYHI) ? aym[e] : ayp[e], (yf & FYHI) ? uym[e] : uyp[e], s, d);
+                    vc_nb<T>(c.wz, ai, (zf & FZHI) ? azm[r][e] : azp[r][e], (zf & FZHI) ? uzm[r][e] : uzp[r][e], s, d);
+                    bnd = ((zf | yf | xf) & ~mask) != 0;
+                } else {
+                    vc_nb<T>(c.wz, ai, azm[r][e], uzm[r][e], s, d);
+                    vc_nb<T>(c.wy, ai, aym[e], uym[e], s, d);
+                    vc_nb<T>(c.wx, ai, al, ul, s, d);
+                    vc_nb<T>(c.wx, ai, ar, ur, s, d);
+                    vc_nb<T>(c.wy, ai, ayp[e], uyp[e], s, d);
+                    vc_nb<T>(c.wz, ai, azp[r][e], uzp[r][e], s, d);
+                    bnd = rb || (x0 + e == 0) || (x0 + e == g.nx - 1);
+                }
                 T v;
                 if (OP == OP_RES) {
                     v = bnd ? bi - ui : bi - (d * ui - s);
@@ -234,7 +306,9 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                         if (STORE && e < part) po[e] = res[e];
                 }
                 if (tailwave && lane >= 56) {
-                    // column nx-1 (Dirichlet: r = b - u, u' = b, the step's rhs = u) as one full 128-byte line: value + zero padding
+                    // column nx-1 (Dirichlet: r = b - u, u' = b, the step's rhs = u) as one full 128-byte line: value + zero padding.
+                    // MIR: with an x-hi Neumann face the node is an unknown and the plain form's point function computes it
+                    // (one lane per row; u is never the output array)
                     const int j = lane - 56;
                     constexpr int LINE = 128 / (int)sizeof(T);
                     const int xs = g.nx - 1 + V * j;
@@ -242,7 +316,22 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                     const long long ro = zo + (rowoff[r] - x0c);
                     if (xs < line_end) {
                         vec tv = (vec)(0);
-                        if (j == 0 && OP == OP_STEP) {
+                        if (MIR && j == 0) {
+                            const VcOp<T, true> op = vc_op<T, true>(c, a, mask);
+                            if (OP == OP_RES) {
+                                const T rt = op.template res<3>(g, u, b, z, yb + r, g.nx - 1);
+                                acc += (double)rt * (double)rt;
+                                tv[0] = rt;
+                            } else if (OP == OP_STEP) {
+                                const long long it = ro + g.nx - 1;
+                                const T ut = u[it];
+                                T n0 = (T)0;
+                                const bool fixed = op.template n0<3>(g, u, z, yb + r, g.nx - 1, true, n0);
+                                tv[0] = fixed ? ut : step_value<T, SRC>(st, ut, SRC ? b[it] : (T)0, n0);
+                            } else {
+                                tv[0] = op.template solve<3>(g, omega, damped, u, b, z, yb + r, g.nx - 1);
+                            }
+                        } else if (j == 0 && OP == OP_STEP) {
                             tv[0] = u[ro + g.nx - 1];
                         } else if (j == 0) {
                             const T bt = b[ro + g.nx - 1];
@@ -291,7 +380,7 @@ __global__ __launch_bounds__(OP_THREADS) void k_vc_cg_direction(Geom g, VcCoef<T
                 const int dz = k == 0 ? -1 : (k == 5 ? 1 : 0), dy = k == 1 ? -1 : (k == 4 ? 1 : 0), dx = k == 2 ? -1 : (k == 3 ? 1 : 0);
                 if (on_boundary(g, z + dz, y + dy, x + dx)) return (T)0;
                 return zv[e] + beta * p[e];
-            }, a, i, g.pitch, g.plane, c, s, d);
+            }, a, i, vc_straight(g, i), c, s, d);
             qv = d * pc - s;
             acc += (double)pc * (double)qv;
         }
@@ -300,6 +389,79 @@ __global__ __launch_bounds__(OP_THREADS) void k_vc_cg_direction(Geom g, VcCoef<T
     }
     const double s = block_sum(acc, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// ---------------------------------------------------------------- the same with a face mask; sum w p'.q
+// p' and q are 0 on the Dirichlet nodes of the mask; a mirrored neighbour is the value of the node it mirrors
+template <typename T, int DIM>
+__global__ __launch_bounds__(OP_THREADS) void k_vcn_cg_direction(Geom g, VcCoef<T> c, int mask, const T *__restrict__ zv,
+                                                                 const T *__restrict__ p, const T *__restrict__ a, T *__restrict__ pn,
+                                                                 T *__restrict__ q, const CgScalars *__restrict__ sc,
+                                                                 double *__restrict__ partials)
+{
+    __shared__ double sh[OP_THREADS / 64];
+    if (sc->bad != 0) return;
+    const T beta = (T)sc->beta;
+    const long long nitems = (long long)g.nx * g.ny * g.nz;
+    double acc = 0.;
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
+        const long long row = it / g.nx;
+        const int x = (int)(it - row * g.nx), y = (int)(row % g.ny), z = (int)(row / g.ny);
+        const long long i = lidx(g, z, y, x);
+        const int f = bc_faces(g, z, y, x);
+        T pc = (T)0, qv = (T)0;
+        if (!(f & ~mask)) {
+            pc = zv[i] + beta * p[i];
+            // the coordinates of the six neighbours, mirrored like their indices
+            const int zs[2] = {(f & FZLO) ? z + 1 : z - 1, (f & FZHI) ? z - 1 : z + 1};
+            const int ys[2] = {(f & FYLO) ? y + 1 : y - 1, (f & FYHI) ? y - 1 : y + 1};
+            const int xs[2] = {(f & FXLO) ? x + 1 : x - 1, (f & FXHI) ? x - 1 : x + 1};
+            T s, d;
+            vc_parts<T, DIM>([&](long long e, int k) -> T {
+                const int nz = k == 0 ? zs[0] : (k == 5 ? zs[1] : z), ny = k == 1 ? ys[0] : (k == 4 ? ys[1] : y);
+                const int nx = k == 2 ? xs[0] : (k == 3 ? xs[1] : x);
+                if (bc_faces(g, nz, ny, nx) & ~mask) return (T)0;
+                return zv[e] + beta * p[e];
+            }, a, i, bc_neighbours(g, i, f), c, s, d);
+            qv = d * pc - s;
+            acc += bc_weight(__popc((unsigned)f)) * ((double)pc * (double)qv);   // f lies in the mask here
+        }
+        pn[i] = pc;
+        q[i] = qv;
+    }
+    const double s = block_sum(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// ---------------------------------------------------------------- sum w z.r, sum w z.q (k_cg_dots with the weights of the mask)
+template <typename T>
+__global__ __launch_bounds__(OP_THREADS) void k_vcn_cg_dots(Geom g, int mask, const T *__restrict__ z, const T *__restrict__ r,
+                                                            const T *__restrict__ q, const CgScalars *__restrict__ sc,
+                                                            double *__restrict__ partials)
+{
+    constexpr int V = Vec16<T>::n;
+    typedef typename Vec16<T>::type vec;
+    __shared__ double sh[OP_THREADS / 64];
+    if (sc->bad != 0) return;
+    const long long vpr = g.pitch / V, nitems = vpr * g.ny * g.nz;
+    double zr = 0., zq = 0.;
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
+        const long long row = it / vpr;
+        const int x0 = (int)(it - row * vpr) * V, y = (int)(row % g.ny), zz = (int)(row / g.ny);
+        if (x0 >= g.nx) continue;
+        const long long i = lidx(g, zz, y, x0);
+        const vec zv = *(const vec *)(z + i), rv = *(const vec *)(r + i), qv = *(const vec *)(q + i);
+#pragma unroll
+        for (int e = 0; e < V; e++)
+            if (x0 + e < g.nx) {
+                const double w = bc_weight(__popc((unsigned)(bc_faces(g, zz, y, x0 + e) & mask)));   // a power of two: exact
+                zr += w * ((double)zv[e] * (double)rv[e]);
+                zq += w * ((double)zv[e] * (double)qv[e]);
+            }
+    }
+    const double s0 = block_sum(zr, sh);
+    const double s1 = block_sum(zq, sh);
+    if (threadIdx.x == 0) { partials[blockIdx.x] = s0; partials[gridDim.x + blockIdx.x] = s1; }
 }
 
 // ---------------------------------------------------------------- launchers
@@ -311,8 +473,9 @@ VcCoef<T> vc_coef(const double coef[4], double sigma)
 
 }  // namespace
 
+// mask == 0 launches the instantiations without MIR: the kernels of a handle that never set a mask
 template <typename T>
-int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, const T *u, const T *a, const T *b, T *r,
+int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, const T *u, const T *a, const T *b, T *r,
                        double *partials, int cap, bool plain)
 {
     const VcCoef<T> c = vc_coef<T>(coef, sigma);
@@ -320,80 +483,106 @@ int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], doubl
         const MarchGrid m = march_grid<T>(g);
         if (m.grid <= cap) {
             const dim3 gr(m.grid), bl(64 * MBW);
-            if (r) hipLaunchKernelGGL((k_vc_march<T, OP_RES, true>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
-            else hipLaunchKernelGGL((k_vc_march<T, OP_RES, false>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
+#define MG_VC(SAVE, MIR) hipLaunchKernelGGL((k_vc_march<T, OP_RES, SAVE, true, MIR>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{}, mask)
+            if (mask) { if (r) MG_VC(true, true); else MG_VC(false, true); }
+            else { if (r) MG_VC(true, false); else MG_VC(false, false); }
+#undef MG_VC
             return m.grid;
         }
     }
-    return plain_residual(s, g, VcOp<T>{c, a}, u, b, r, partials, cap);
+    if (mask) return plain_residual(s, g, vc_op<T, true>(c, a, mask), u, b, r, partials, cap);
+    return plain_residual(s, g, vc_op<T, false>(c, a, 0), u, b, r, partials, cap);
 }
 
 template <typename T>
-void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, T omega, const T *u, const T *a, const T *b,
+void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, const T *u, const T *a, const T *b,
                       T *out, bool plain)
 {
     const VcCoef<T> c = vc_coef<T>(coef, sigma);
     if (march_takes<T>(g, plain)) {
         const MarchGrid m = march_grid<T>(g);
-        hipLaunchKernelGGL((k_vc_march<T, OP_JAC, false>), dim3(m.grid), dim3(64 * MBW), 0, s, g, c, omega, u, a, b, out,
-                           (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{});
+        const dim3 gr(m.grid), bl(64 * MBW);
+#define MG_VC(MIR) hipLaunchKernelGGL((k_vc_march<T, OP_JAC, false, true, MIR>), gr, bl, 0, s, g, c, omega, u, a, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{}, mask)
+        if (mask) MG_VC(true); else MG_VC(false);
+#undef MG_VC
         return;
     }
-    plain_jacobi(s, g, VcOp<T>{c, a}, omega, u, b, out);
+    if (mask) plain_jacobi(s, g, vc_op<T, true>(c, a, mask), omega, u, b, out);
+    else plain_jacobi(s, g, vc_op<T, false>(c, a, 0), omega, u, b, out);
 }
 
 template <typename T>
-void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], double dt, double theta, const T *u, const T *a, const T *f,
-                        T *out, bool plain)
+void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], int mask, double dt, double theta, const T *u, const T *a,
+                        const T *f, T *out, bool plain)
 {
     const VcCoef<T> c = vc_coef<T>(coef, 0.0);   // the unshifted operator: d starts from (T)0
     const StepCoef<T> st = step_coef<T>(dt, theta);
     if (march_takes<T>(g, plain)) {
         const MarchGrid m = march_grid<T>(g);
         const dim3 gr(m.grid), bl(64 * MBW);
-        if (f) hipLaunchKernelGGL((k_vc_march<T, OP_STEP, true, true>), gr, bl, 0, s, g, c, (T)1, u, a, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st);
-        else hipLaunchKernelGGL((k_vc_march<T, OP_STEP, true, false>), gr, bl, 0, s, g, c, (T)1, u, a, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st);
+#define MG_VC(SRC, MIR) hipLaunchKernelGGL((k_vc_march<T, OP_STEP, true, SRC, MIR>), gr, bl, 0, s, g, c, (T)1, u, a, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st, mask)
+        if (mask) { if (f) MG_VC(true, true); else MG_VC(false, true); }
+        else { if (f) MG_VC(true, false); else MG_VC(false, false); }
+#undef MG_VC
         return;
     }
-    plain_step(s, g, VcOp<T>{c, a}, st, u, f, out);
+    if (mask) plain_step(s, g, vc_op<T, true>(c, a, mask), st, u, f, out);
+    else plain_step(s, g, vc_op<T, false>(c, a, 0), st, u, f, out);
 }
 
 template <typename T>
-void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int colour, T *u, const T *a, const T *b)
+void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int colour, T *u, const T *a, const T *b)
 {
-    plain_rb_colour(s, g, VcOp<T>{vc_coef<T>(coef, sigma), a}, colour, u, b);
+    if (mask) plain_rb_colour(s, g, vc_op<T, true>(vc_coef<T>(coef, sigma), a, mask), colour, u, b);
+    else plain_rb_colour(s, g, vc_op<T, false>(vc_coef<T>(coef, sigma), a, 0), colour, u, b);
 }
 
 template <typename T>
-void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, T omega, int smoother, T *x, T *tmp,
+void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, int smoother, T *x, T *tmp,
                       const T *rhs, const T *a, int maxit, double tol, int fixed, CoarseOut *d_out)
 {
-    coarse_solve(s, g, VcOp<T>{vc_coef<T>(coef, sigma), a}, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
+    if (mask) coarse_solve(s, g, vc_op<T, true>(vc_coef<T>(coef, sigma), a, mask), omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
+    else coarse_solve(s, g, vc_op<T, false>(vc_coef<T>(coef, sigma), a, 0), omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
 }
 
 template <typename T>
-int launch_vc_cg_direction(hipStream_t s, const Geom &g, const double coef[4], double sigma, const T *z, const T *p, const T *a, T *pn,
-                           T *q, const CgScalars *sc, double *partials)
+int launch_vc_cg_direction(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, const T *z, const T *p, const T *a,
+                           T *pn, T *q, const CgScalars *sc, double *partials)
 {
     const VcCoef<T> c = vc_coef<T>(coef, sigma);
     const int nb = plain_grid((long long)g.nx * g.ny * g.nz, OP_MAX_BLOCKS);
-    if (g.dim == 3) hipLaunchKernelGGL((k_vc_cg_direction<T, 3>), dim3(nb), dim3(OP_THREADS), 0, s, g, c, z, p, a, pn, q, sc, partials);
-    else hipLaunchKernelGGL((k_vc_cg_direction<T, 2>), dim3(nb), dim3(OP_THREADS), 0, s, g, c, z, p, a, pn, q, sc, partials);
+    const dim3 gr(nb), bl(OP_THREADS);
+    if (mask) {
+        if (g.dim == 3) hipLaunchKernelGGL((k_vcn_cg_direction<T, 3>), gr, bl, 0, s, g, c, mask, z, p, a, pn, q, sc, partials);
+        else hipLaunchKernelGGL((k_vcn_cg_direction<T, 2>), gr, bl, 0, s, g, c, mask, z, p, a, pn, q, sc, partials);
+    } else {
+        if (g.dim == 3) hipLaunchKernelGGL((k_vc_cg_direction<T, 3>), gr, bl, 0, s, g, c, z, p, a, pn, q, sc, partials);
+        else hipLaunchKernelGGL((k_vc_cg_direction<T, 2>), gr, bl, 0, s, g, c, z, p, a, pn, q, sc, partials);
+    }
+    return nb;
+}
+
+template <typename T>
+int launch_vc_cg_wdots(hipStream_t s, const Geom &g, int mask, const T *z, const T *r, const T *q, const CgScalars *sc, double *partials)
+{
+    const int nb = plain_grid((long long)(g.pitch / Vec16<T>::n) * g.ny * g.nz, OP_MAX_BLOCKS);
+    hipLaunchKernelGGL((k_vcn_cg_dots<T>), dim3(nb), dim3(OP_THREADS), 0, s, g, mask, z, r, q, sc, partials);
     return nb;
 }
 
 #define MG_VC_INST(T)                                                                                                                  \
-    template int launch_vc_residual<T>(hipStream_t, const Geom &, const double[4], double, const T *, const T *, const T *, T *,      \
+    template int launch_vc_residual<T>(hipStream_t, const Geom &, const double[4], double, int, const T *, const T *, const T *, T *, \
                                        double *, int, bool);                                                                         \
-    template void launch_vc_jacobi<T>(hipStream_t, const Geom &, const double[4], double, T, const T *, const T *, const T *, T *,   \
-                                      bool);                                                                                         \
-    template void launch_vc_heat_rhs<T>(hipStream_t, const Geom &, const double[4], double, double, const T *, const T *, const T *,  \
-                                        T *, bool);                                                                                  \
-    template void launch_vc_rb_colour<T>(hipStream_t, const Geom &, const double[4], double, int, T *, const T *, const T *);         \
-    template void launch_vc_coarse<T>(hipStream_t, const Geom &, const double[4], double, T, int, T *, T *, const T *, const T *, int, \
-                                      double, int, CoarseOut *);                                                                     \
-    template int launch_vc_cg_direction<T>(hipStream_t, const Geom &, const double[4], double, const T *, const T *, const T *, T *,  \
-                                           T *, const CgScalars *, double *);
+    template void launch_vc_jacobi<T>(hipStream_t, const Geom &, const double[4], double, int, T, const T *, const T *, const T *,   \
+                                      T *, bool);                                                                                    \
+    template void launch_vc_heat_rhs<T>(hipStream_t, const Geom &, const double[4], int, double, double, const T *, const T *,        \
+                                        const T *, T *, bool);                                                                       \
+    template void launch_vc_rb_colour<T>(hipStream_t, const Geom &, const double[4], double, int, int, T *, const T *, const T *);    \
+    template void launch_vc_coarse<T>(hipStream_t, const Geom &, const double[4], double, int, T, int, T *, T *, const T *, const T *, \
+                                      int, double, int, CoarseOut *);                                                                \
+    template int launch_vc_cg_direction<T>(hipStream_t, const Geom &, const double[4], double, int, const T *, const T *, const T *,  \
+                                           T *, T *, const CgScalars *, double *);                                                   \
+    template int launch_vc_cg_wdots<T>(hipStream_t, const Geom &, int, const T *, const T *, const T *, const CgScalars *, double *);
 MG_VC_INST(double)
 MG_VC_INST(float)
 #undef MG_VC_INST
