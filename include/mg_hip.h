@@ -808,6 +808,41 @@ int mg_profile_get(mg_handle h, int kind, double *ms, int *launches);
 /* bytes of HBM held by the handle */
 int mg_device_bytes(mg_handle h, size_t *bytes);
 
+/* TEST AND DEBUGGING WINDOW, not a data path: the whole allocation behind one level-shaped array of a single-GPU handle --
+ * (nz + 2 ghost) planes x ny rows x pitch elements, ghost planes and padding columns included -- as the kernels see it.
+ * tests/test_storage_gpu.py holds every kernel entry point to the layout's invariant with it (padding
+ * columns and ghost planes are +0 and stay +0). Neither call launches a kernel, allocates, or changes any state of the
+ * handle that a driver caches; use mg_set_array / mg_get_array (or their _device twins) to move data.
+ *   space                 index                          level     the array
+ *   MG_RAW_LEVEL          enum mg_array                  any       the slot's CURRENT buffer (out-of-place sweeps swap U / TMP)
+ *   MG_RAW_VC             0                              any       the coefficient of mg_vc_set_coefficient
+ *   MG_RAW_KRYLOV         0 .. 4                         0         the buffers of mg_pcg_solve / mg_vc_pcg_solve
+ *   MG_RAW_MIXED          0 = b64, 1 = u64, 2 = its twin 0         fp64 arrays of mg_mixed_*: 8-byte elements, their own pitch
+ *   MG_RAW_EIG            family * MG_EIG_MAX_BLOCK + j  0         column j of an enum mg_eig_family
+ *   MG_RAW_HEAT           0                              0         the source of mg_heat_set_source
+ *   MG_RAW_O4             0 = b4, 1 = u4, 2 = its twin   0         the outer arrays of mg_o4_solve
+ * mg_debug_raw_layout fills *out for any admissible (space, index, level); allocated == 0 when the handle has not made that
+ * array yet (the geometry is the one it will have). Element (z, y, x) of the dense array is element
+ * ((z + ghost) * ny + y) * pitch + x of the allocation.
+ * mg_debug_raw_copy copies the whole allocation host -> device (to_device != 0) or device -> host on the handle's stream
+ * and waits for it. bytes must equal elems * elem_size. An upload into MG_ARR_RHS drops the level's cached halo state as
+ * mg_set_array does; nothing else is touched (mg_mixed_solve's "array was set" flags included).
+ * MG_ERR_BAD_ARG, nothing copied: NULL handle, NULL out / host, distributed handles (dry runs included: their ghost planes
+ * are live halo), an unknown space, index or level, an array that is not allocated (copy), bytes of another size. */
+enum mg_raw_space { MG_RAW_LEVEL = 0, MG_RAW_VC = 1, MG_RAW_KRYLOV = 2, MG_RAW_MIXED = 3, MG_RAW_EIG = 4, MG_RAW_HEAT = 5,
+                    MG_RAW_O4 = 6, MG_RAW_SPACES = 7 };
+typedef struct mg_debug_raw_info {
+    int32_t elem_size;   /* 8 or 4                                        */
+    int32_t nx, ny, nz;  /* dense extents                                 */
+    int32_t pitch;       /* elements per row, >= nx                       */
+    int32_t ghost;       /* ghost planes either side of the nz dense ones */
+    int32_t allocated;   /* 0: the handle has not allocated this array    */
+    int32_t reserved;
+    uint64_t elems;      /* (nz + 2 * ghost) * ny * pitch                 */
+} mg_debug_raw_info;
+int mg_debug_raw_layout(mg_handle h, int space, int index, int level, mg_debug_raw_info *out);
+int mg_debug_raw_copy(mg_handle h, int space, int index, int level, void *host, size_t bytes, int to_device);
+
 /* ---- multi-GPU (z-slab domain decomposition, RCCL halo exchange) ---- */
 #define MG_COMM_ID_BYTES 128
 /* rank 0 creates the RCCL unique id; the caller ships it to the other ranks by any

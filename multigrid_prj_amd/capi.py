@@ -31,6 +31,8 @@ EIG_MAX_BLOCK = 8
 EIG_X, EIG_AX, EIG_W, EIG_AW, EIG_P, EIG_AP = 0, 1, 2, 3, 4, 5
 EIG_K_APPLY_GRAM, EIG_K_COMBINE = 0, 1
 EIG_CONVERGED, EIG_MAXIT, EIG_NOT_FINITE = 0, 1, 2
+# enum mg_raw_space: the arrays mg_debug_raw_* (a test and debugging window, not a data path) can look at
+RAW_LEVEL, RAW_VC, RAW_KRYLOV, RAW_MIXED, RAW_EIG, RAW_HEAT, RAW_O4 = 0, 1, 2, 3, 4, 5, 6
 
 
 class MgError(RuntimeError):
@@ -114,6 +116,13 @@ class MgHeatStats(C.Structure):
     _fields_ = [("steps", C.c_int32), ("cycles", C.c_int32), ("time", C.c_double), ("relres", C.c_double)]
 
 
+class MgDebugRawInfo(C.Structure):
+    """include/mg_hip.h::mg_debug_raw_info (mg_debug_raw_layout)"""
+
+    _fields_ = [("elem_size", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("pitch", C.c_int32),
+                ("ghost", C.c_int32), ("allocated", C.c_int32), ("reserved", C.c_int32), ("elems", C.c_uint64)]
+
+
 class MgEigStats(C.Structure):
     """include/mg_hip.h::mg_eig_stats (mg_eig_solve)"""
 
@@ -173,7 +182,8 @@ EXPORTS = [
     "mg_vc_heat_rhs", "mg_bc_heat_rhs", "mg_fas_heat_rhs", "mg_vc_heat_step", "mg_bc_heat_step", "mg_fas_heat_step",
     "mg_eig_solve", "mg_eig_set_vector", "mg_eig_get_vector", "mg_eig_set_vector_device", "mg_eig_get_vector_device",
     "mg_eig_block", "mg_eig_kernel",
-    "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes", "mg_comm_unique_id", "mg_comm_selftest",
+    "mg_set_stage_callback", "mg_sync", "mg_timer_start", "mg_timer_stop", "mg_profile_begin", "mg_profile_end", "mg_profile_fused", "mg_profile_get", "mg_comm_info", "mg_comm_stats", "mg_device_bytes",
+    "mg_debug_raw_layout", "mg_debug_raw_copy", "mg_comm_unique_id", "mg_comm_selftest",
     "mg_create_distributed", "mg_create_distributed_hostcomm", "mg_create_distributed_dryrun", "mg_plan_slab",
 ]
 
@@ -298,6 +308,8 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     L.mg_comm_info.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(C.c_char_p)]
     L.mg_comm_stats.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.mg_device_bytes.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.mg_debug_raw_layout.argtypes = [vp, i, i, i, C.POINTER(MgDebugRawInfo)]
+    L.mg_debug_raw_copy.argtypes = [vp, i, i, i, vp, C.c_size_t, i]
     L.mg_comm_unique_id.argtypes = [vp]
     L.mg_comm_selftest.argtypes = [C.c_size_t]
     L.mg_create_distributed.argtypes = [C.POINTER(MgDesc), i, i, i, vp, C.POINTER(vp)]
@@ -907,3 +919,23 @@ class Solver:
 
     def device_bytes(self) -> int:
         b = C.c_size_t(0); _check(self.lib.mg_device_bytes(self.h, C.byref(b))); return b.value
+
+    # -- test and debugging window (mg_debug_raw_*): whole allocations, ghost planes and padding columns included
+    def debug_raw_layout(self, space, index=0, level=0) -> MgDebugRawInfo:
+        """mg_debug_raw_layout: element size, extents, pitch, ghost planes and size of one allocation (RAW_* spaces)"""
+        info = MgDebugRawInfo(); _check(self.lib.mg_debug_raw_layout(self.h, space, index, level, C.byref(info))); return info
+
+    def debug_raw_get(self, space, index=0, level=0):
+        """mg_debug_raw_copy, device -> host: the allocation as an array of shape (nz + 2 ghost, ny, pitch)"""
+        info = self.debug_raw_layout(space, index, level)
+        a = np.empty((info.nz + 2 * info.ghost, info.ny, info.pitch), np.float64 if info.elem_size == 8 else np.float32)
+        _check(self.lib.mg_debug_raw_copy(self.h, space, index, level, a.ctypes.data_as(C.c_void_p), a.nbytes, 0)); return a
+
+    def debug_raw_set(self, space, index, level, a):
+        """mg_debug_raw_copy, host -> device: every word of the allocation from an array shaped as debug_raw_get returns it"""
+        info = self.debug_raw_layout(space, index, level)
+        want = (info.nz + 2 * info.ghost, info.ny, info.pitch)
+        a = np.ascontiguousarray(a, np.float64 if info.elem_size == 8 else np.float32)
+        if a.shape != want:
+            raise ValueError(f"expected shape {want}, got {a.shape}")
+        _check(self.lib.mg_debug_raw_copy(self.h, space, index, level, a.ctypes.data_as(C.c_void_p), a.nbytes, 1))

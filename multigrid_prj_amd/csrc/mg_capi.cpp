@@ -502,6 +502,17 @@ int mg_device_bytes(mg_handle h, size_t *bytes)
     return MG_OK;
 }
 
+int mg_debug_raw_layout(mg_handle h, int space, int index, int level, mg_debug_raw_info *out)
+{
+    if (!h || !h->impl) return bad("mg_debug_raw_layout: null handle");
+    return guarded([&] { return h->impl->raw_layout("mg_debug_raw_layout", space, index, level, out); });
+}
+int mg_debug_raw_copy(mg_handle h, int space, int index, int level, void *host, size_t bytes, int to_device)
+{
+    if (!h || !h->impl) return bad("mg_debug_raw_copy: null handle");
+    return guarded([&] { return h->impl->raw_copy(space, index, level, host, bytes, to_device != 0); });
+}
+
 int mg_plan_slab(const mg_desc *desc, int nranks, int rank, int level, int *z0, int *nz,
                  int *first_gathered_level)
 {

@@ -5,9 +5,12 @@
 // pitch = nx rounded up to 128 B so every row starts on a 128-byte line and lane
 // l of a wave reads x = 2l,2l+1 (fp64) / 4l..4l+3 (fp32) with one aligned 16-byte
 // access.  Plane 0 and plane nz+1 are ghost planes (z-halo of the slab
-// decomposition; unused and zero on one GPU); `p` pointers handed to kernels
-// point at local plane 0, i.e. one plane into the allocation.  Padding columns
-// x >= nx are never written and stay zero.
+// decomposition; unused and zero on one GPU, where no kernel writes them); `p`
+// pointers handed to kernels point at local plane 0, i.e. one plane into the
+// allocation.  Padding columns x >= nx stay zero: they are written only with
+// zeros -- by the tail-line stores (mg_device.h), the line store of mg_fmg.hip
+// and the copies into the layout (mg_io.hip, the host staging of mg_set_array).
+// tests/test_storage_gpu.py holds every entry point to both.
 #ifndef MG_GEOM_H
 #define MG_GEOM_H
 

@@ -404,7 +404,9 @@ void launch_fas_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int kind,
 // ---- device-resident array I/O (mg_io.hip, driven by Solver::device_copy) ----
 // padded: local plane 0 of a level-shaped array of geometry g with elements P; dense: the caller's dense device array of
 // g.nx * g.ny * g.nz elements D at any element-aligned address. to_padded: padded = (P)dense, padding columns written as
-// zeros; otherwise dense = (D)padded and no byte outside the dense array is written. Ghost planes are not touched.
+// zeros (the value they hold: mg_geom.h -- padding is only ever written with zeros, here, by the tail-line stores and by the
+// line store of mg_fmg.hip); otherwise dense = (D)padded and no byte outside the dense array is written. Ghost planes are
+// not touched.
 template <typename P, typename D>
 void launch_io_copy(hipStream_t s, const Geom &g, P *padded, D *dense, bool to_padded);
 

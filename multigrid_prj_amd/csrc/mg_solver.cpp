@@ -592,6 +592,87 @@ int Solver::zero_array(int which, int level)
     return MG_OK;
 }
 
+// ---- mg_debug_raw_*: the test and debugging window on a whole allocation ----
+// *out for (space, index, level) and, when asked, the allocation's base (nullptr: not allocated). No HIP call.
+int Solver::raw_layout(const char *fn, int space, int index, int level, mg_debug_raw_info *out, void **dev) const
+{
+    const std::string f = std::string(fn) + ": ";
+    if (nranks_ > 1) {
+        set_last_error(f + "distributed handles are not supported: their ghost planes are live halo (single-GPU handles only)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (!out) { set_last_error(f + "null argument"); return MG_ERR_BAD_ARG; }
+    if (level < 0 || level >= d_.levels) { set_last_error(f + "no such level"); return MG_ERR_BAD_ARG; }
+    if (space != MG_RAW_LEVEL && space != MG_RAW_VC && level != 0) { set_last_error(f + "this space has level 0 only"); return MG_ERR_BAD_ARG; }
+    const Level &L = lv_[level];
+    Geom g = L.g;
+    size_t es = esize();
+    void *base = nullptr;
+    bool ok = false;
+    switch (space) {
+    case MG_RAW_LEVEL:
+        ok = index >= 0 && index < NUM_ARR;
+        if (ok) base = L.base[index];
+        break;
+    case MG_RAW_VC: ok = index == 0; base = L.vc_a; break;
+    case MG_RAW_KRYLOV:
+        ok = index >= 0 && index < NKRY;
+        if (ok) base = kry_[index];
+        break;
+    case MG_RAW_MIXED:   // mixed_alloc's geometry: level 0 with rows of doubles padded to 128 B
+        ok = index >= 0 && index < NMX;
+        if (ok) base = mx_[index];
+        es = sizeof(double);
+        g.pitch = ((g.nx + 15) / 16) * 16;
+        g.plane = (long long)g.ny * g.pitch;
+        break;
+    case MG_RAW_EIG:
+        ok = index >= 0 && index < EIG_FAMILIES * MG_EIG_MAX_BLOCK;
+        if (ok) base = eig_[index / MG_EIG_MAX_BLOCK][index % MG_EIG_MAX_BLOCK];
+        break;
+    case MG_RAW_HEAT: ok = index == 0; base = heat_f_; break;
+    case MG_RAW_O4:
+        ok = index >= 0 && index < NO4;
+        if (ok) base = o4_[index];
+        break;
+    default: set_last_error(f + "unknown space"); return MG_ERR_BAD_ARG;
+    }
+    if (!ok) { set_last_error(f + "no such index in this space"); return MG_ERR_BAD_ARG; }
+    out->elem_size = (int32_t)es;
+    out->nx = g.nx; out->ny = g.ny; out->nz = g.nz;
+    out->pitch = g.pitch;
+    out->ghost = L.gh;
+    out->allocated = base ? 1 : 0;
+    out->reserved = 0;
+    out->elems = (uint64_t)(g.nz + 2 * L.gh) * (uint64_t)g.plane;
+    if (dev) *dev = base;
+    return MG_OK;
+}
+
+int Solver::raw_copy(int space, int index, int level, void *host, size_t bytes, bool to_device)
+{
+    const char *fn = "mg_debug_raw_copy";
+    mg_debug_raw_info info{};
+    void *dev = nullptr;
+    MG_TRY(raw_layout(fn, space, index, level, &info, &dev));
+    if (!host) { set_last_error(std::string(fn) + ": null host pointer"); return MG_ERR_BAD_ARG; }
+    if (!dev) { set_last_error(std::string(fn) + ": the handle has not allocated this array"); return MG_ERR_BAD_ARG; }
+    const size_t want = (size_t)info.elems * (size_t)info.elem_size;
+    if (bytes != want) {
+        set_last_error(std::string(fn) + ": bytes must be the allocation's size, " + std::to_string(want) + " (got " + std::to_string(bytes) + ")");
+        return MG_ERR_BAD_ARG;
+    }
+    MG_HIP(hipSetDevice(device_));
+    if (to_device && space == MG_RAW_LEVEL) {   // stage_rows' invalidations: what an upload can make stale
+        pair_on_comm_level_ = -1;
+        if (index == MG_ARR_RHS) lv_[level].rhs_halo_ok = false;
+    }
+    if (to_device) MG_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream_));
+    else MG_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream_));
+    MG_HIP(hipStreamSynchronize(stream_));
+    return MG_OK;
+}
+
 int Solver::post(const P2POp *ops, int n, hipStream_t s)
 {
     if (n > 0) comm_groups_++;

@@ -205,6 +205,10 @@ public:
     int profile_get(int kind, double *ms, int *launches) const;
     int comm_info(int *rank, int *nranks, int *transport_ranks, const char **transport) const;
     size_t device_bytes() const { return bytes_; }
+    // test and debugging window (mg_debug_raw_*): the whole allocation behind one level-shaped array, ghost planes and
+    // padding columns included; no kernel, no allocation, no driver state
+    int raw_layout(const char *fn, int space, int index, int level, mg_debug_raw_info *out, void **dev = nullptr) const;
+    int raw_copy(int space, int index, int level, void *host, size_t bytes, bool to_device);
     long long comm_groups() const { return comm_groups_; }
     long long comm_bytes_sent() const { return comm_bytes_; }
 
@@ -284,7 +288,9 @@ private:
     int fetch_cycle_stats(mg_cycle_stats *st, bool with_fine = false);
     void fill_cycle_stats(mg_cycle_stats *st, double fine_sumsq_r) const;   // from h_coarse_ as it stands
     // *p = nbytes of zeroed device memory (the memset is queued on stream_), counted in bytes_. Level-shaped arrays made
-    // this way keep their ghost planes and padding columns zero: nothing writes them afterwards.
+    // this way keep their ghost planes and padding columns zero: on a one-GPU level no kernel writes a ghost plane, and the
+    // padding columns are written only with zeros (the tail-line stores of mg_device.h, the line store of mg_fmg.hip).
+    // tests/test_storage_gpu.py holds every entry point to that.
     int alloc_zeroed(void **p, size_t nbytes);
     template <typename T> int pcg_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_krylov_stats *st);
     // pcg_t's and vc_pcg_t's iteration; the two callables are the operator's residual with its sum and its direction kernel.

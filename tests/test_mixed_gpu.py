@@ -8,8 +8,8 @@
   cycles than the fp64 handle needs (one correction of slack);
 * invariance under scaling b by 2^-200 / 2^+200, a dense solve, determinism, isolation, edge cases and refusals.
 
-Not checked here: that the padding columns (x >= nx) of the arrays stay zero -- no entry point of the C ABI reads them;
-the kernels only ever store the first nx elements of a row (masked stores, mg_mixed.hip).
+That the padding columns (x >= nx) and the ghost planes of the arrays, the fp64 ones included, stay zero is checked in
+tests/test_storage_gpu.py (rows mixed-kernel and mixed-solve of tests/storage_table.py), on the whole allocations.
 """
 import math
 import threading

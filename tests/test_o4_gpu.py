@@ -82,10 +82,8 @@ def test_outputs_feed_the_other_kernels(fused, dim, n, dtype):
     """What mg_o4_residual / mg_o4_correct_residual leave in the handle's arrays is what an upload of the same values
     leaves, as far as the other kernels can tell: sweeps and a residual run on the outputs give the bits they give on a
     twin handle whose arrays were uploaded.
-    NOT checked, here or anywhere: that the padding columns (x >= nx) stay zero and the ghost planes untouched. No entry
-    point of the C ABI reads them (tests/test_mixed_gpu.py says the same of its kernels), and the kernels that load them
-    use them only as neighbours of Dirichlet nodes, whose results are masked; the bound checks of mg_o4.hip were read, not
-    measured."""
+    That the padding columns (x >= nx) stay zero and the ghost planes untouched is checked in tests/test_storage_gpu.py
+    (rows o4-residual and o4-correct-residual of tests/storage_table.py), on the whole allocations."""
     rng = np.random.default_rng(n)
     kw = dict(dim=dim, n=n, levels=2, length=1.0, dtype=dtype, cycle=capi.CYCLE_V, smoother=capi.SMOOTH_JACOBI, omega=6.0 / 7.0,
               nu_pre=2, nu_post=2, restriction=capi.RESTRICT_FULLW, outer_pre_gs=0)

@@ -1,0 +1,218 @@
+"""CPU side of the storage checks (tests/storage_table.py, tests/test_storage_gpu.py):
+
+* every function include/mg_hip.h declares has a row in storage_table.ROWS or a reason in storage_table.NO_KERNEL -- an
+  entry point added later without either fails here;
+* the table reaches what it is there for: both dtypes, the tail-line store taken and not taken on an odd n in every row;
+* mg_debug_raw_layout / mg_debug_raw_copy are exported, declared as capi.py registers them, and refuse a NULL handle with a
+  message that names them, without a device;
+* the mask helpers partition the padded layout exactly, on a numpy model of it built from nx, ny, nz, pitch and gh.
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from multigrid_prj_amd import capi
+from tests import storage_table as st
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+
+def header_text():
+    text = open(os.path.join(ROOT, "include", "mg_hip.h")).read()
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def declared_functions():
+    return sorted(set(re.findall(r"\b(mg_[a-z_0-9]+)\s*\(", header_text())))
+
+
+# ---------------------------------------------------------------- coverage of the C ABI
+def test_every_declared_function_has_a_row_or_a_reason():
+    declared = set(declared_functions())
+    assert len(declared) >= 110 and declared == set(capi.EXPORTS)
+    rows = {e for r in st.ROWS for e in r.entries}
+    assert rows <= declared, sorted(rows - declared)
+    assert set(st.NO_KERNEL) <= declared, sorted(set(st.NO_KERNEL) - declared)
+    assert not rows & set(st.NO_KERNEL), sorted(rows & set(st.NO_KERNEL))
+    missing = declared - rows - set(st.NO_KERNEL)
+    assert not missing, f"no row in tests/storage_table.py and no reason in NO_KERNEL: {sorted(missing)}"
+    assert all(isinstance(why, str) and why.strip() for why in st.NO_KERNEL.values())
+    # a driver is left out only as a composition of rows it names
+    for fn, why in st.NO_KERNEL.items():
+        if why.startswith("composition: rows "):
+            named = [w.strip() for w in why[len("composition: rows "):].split(",")]
+            assert named and all(n in st.ROW for n in named), (fn, named)
+
+
+REQUIRED = """mg_smooth mg_residual mg_sumsq mg_restrict mg_prolong mg_correct mg_coarse_solve mg_coarse_solve_ex mg_zero_array
+mg_set_array mg_get_array mg_set_array_device mg_get_array_device mg_cycle mg_solve mg_subcycle mg_fmg mg_fmg_prolong mg_pcg_kernel
+mg_pcg_solve mg_mixed_kernel mg_mixed_solve mg_o4_residual mg_o4_correct_residual mg_heat_rhs mg_heat_step mg_eig_kernel
+mg_vc_set_coefficient mg_vc_residual mg_vc_smooth mg_vc_restrict mg_vc_project mg_vc_coarse_solve mg_vc_cycle mg_vc_direction
+mg_vc_heat_rhs mg_bc_residual mg_bc_smooth mg_bc_restrict mg_bc_project mg_bc_coarse_solve mg_bc_cycle mg_bc_heat_rhs
+mg_fas_residual mg_fas_smooth mg_fas_coarse_rhs mg_fas_correct mg_fas_coarse_solve mg_fas_cycle mg_fas_heat_rhs""".split()
+
+
+def test_the_kernel_launching_functions_have_rows():
+    rows = {e for r in st.ROWS for e in r.entries}
+    assert not set(REQUIRED) - rows, sorted(set(REQUIRED) - rows)
+
+
+def variant_ids(row, case, dtype):
+    return [v["id"] for v in row.variants(case, dtype)]
+
+
+def test_rows_are_well_formed():
+    for r, case, dtype in st.pairs():
+        vs = row_variants = r.variants(case, dtype)
+        assert vs and len({v["id"] for v in vs}) == len(vs), (r.id, case.id)
+        assert all(isinstance(v["desc"], dict) for v in row_variants)
+        assert (case.n - 1) % (1 << (case.levels - 1)) == 0, case.id
+        capi.make_desc(**st.base_desc(case, dtype, **vs[0]["desc"]))
+    assert len({st.pair_id(p) for p in st.pairs()}) == len(st.pairs())
+    for r in st.ROWS:
+        for space, index, why in r.relies_on_zero:   # "file:line -- reason", the file exists
+            m = re.match(r"(\S+):(\d+) -- \S", why)
+            assert m and os.path.exists(os.path.join(ROOT, "multigrid_prj_amd", "csrc", m.group(1))), (r.id, why)
+
+
+def takes_tail(case, dtype):
+    """an odd last column written as one full line: the row is on a vector path (fast path of the base kernels: rows of >= 33,
+    tests/size_table.py; the marching tile: storage_table.march) and one column is left over after the full vectors"""
+    V = 2 if dtype == st.F64 else 4
+    return case.dim == 3 and case.n >= 33 and case.n % V == 1
+
+
+def test_every_row_sees_the_tail_line_store_taken_and_not_taken():
+    """on an odd n each: a case whose level 0 takes a vector path with one column left over, and one that does not (the plain
+    kernels of a short row, or n % 4 == 3 in fp32); rows that admit only the listed special sizes are exempt from the second"""
+    special = {"smooth-wide", "cycle-wide", "subcycle"}
+    for r in st.ROWS:
+        odd = [(c, dt) for c in r.cases for dt in r.dtypes if c.n % 2 == 1]
+        if r.id in ("smooth-wide", "cycle-wide"):
+            assert [takes_tail(c, dt) for c, dt in odd] == [True, True], r.id   # 257 in both precisions: 128 and 64 vectors + 1
+            continue
+        assert any(not takes_tail(c, dt) for c, dt in odd), r.id
+        if r.id not in special and not r.id.endswith("coarse-solve"):   # the coarse solves run one workgroup on a small level
+            assert any(takes_tail(c, dt) for c, dt in odd), r.id
+        assert set(r.dtypes) == {st.F64, st.F32} or r.id.startswith("mixed") or r.id.endswith("-wide"), r.id
+
+
+def test_family_rows_run_every_mask_form_and_reaction():
+    for fam in ("vc", "bc", "fas"):
+        rows = [r for r in st.ROWS if r.id.startswith(fam + "-")]
+        assert len(rows) >= 7, fam
+        for r in rows:
+            vs = r.variants(st.C(3, 65, 2), st.F64)
+            if fam == "fas":
+                assert {v["reaction"][0] for v in vs} == {capi.FAS_CUBIC, capi.FAS_EXP}, r.id
+            else:
+                assert {v["mask"] for v in vs} == {0, 63, 0b011010}, r.id
+            if not r.id.endswith(("restrict", "project", "set-coefficient")):   # plain kernels whatever the form
+                assert {v["form"] for v in vs} == {0, 1}, r.id
+                assert {v["form"] for v in r.variants(st.C(3, 17, 2), st.F64)} == {0}   # no tile to turn off
+
+
+def test_march_gate_is_mg_geom_h():
+    from tests import vcn_ref
+    for n in (9, 17, 33, 34, 35, 65, 67, 129):
+        for dt, es in ((st.F64, 8), (st.F32, 4)):
+            assert st.march(st.C(3, n, 1), dt) == vcn_ref.march_ok(3, n, n, n, es)
+            assert not st.march(st.C(2, n, 1), dt)
+
+
+# ---------------------------------------------------------------- the C ABI of the window
+NEW = {"mg_debug_raw_layout": 5, "mg_debug_raw_copy": 7}
+
+
+def test_new_symbols_are_exported_and_declared():
+    lib = capi.load()
+    text = header_text()
+    for name, nargs in NEW.items():
+        assert name in capi.EXPORTS and hasattr(lib, name), name
+        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
+        assert m, f"{name} is not declared in include/mg_hip.h"
+        assert len(m.group(1).split(",")) == nargs == len(getattr(lib, name).argtypes), name
+    assert re.search(r"typedef\s+struct\s+mg_debug_raw_info\s*\{[^}]*int32_t\s+elem_size;[^}]*int32_t\s+nx,\s*ny,\s*nz;[^}]*int32_t\s+pitch;"
+                     r"[^}]*int32_t\s+ghost;[^}]*int32_t\s+allocated;[^}]*int32_t\s+reserved;[^}]*uint64_t\s+elems;[^}]*\}\s*mg_debug_raw_info\s*;", text)
+    assert C.sizeof(capi.MgDebugRawInfo) == 40
+    m = re.search(r"enum\s+mg_raw_space\s*\{([^}]*)\}", text)
+    values = dict(re.findall(r"(MG_RAW_[A-Z0-9]+)\s*=\s*(\d+)", m.group(1)))
+    want = {"MG_RAW_" + k: getattr(capi, "RAW_" + k) for k in "LEVEL VC KRYLOV MIXED EIG HEAT O4".split()}
+    assert {k: int(v) for k, v in values.items() if k != "MG_RAW_SPACES"} == want
+    assert int(values["MG_RAW_SPACES"]) == len(st.SPACE_INDICES) == len(st.SPACE_NAME)
+
+
+def test_null_handle_is_refused_without_a_device():
+    lib = capi.load()
+    info = capi.MgDebugRawInfo()
+    info.elems = 77
+    buf = (C.c_double * 4)(1.0, 2.0, 3.0, 4.0)
+    for fn, call in (("mg_debug_raw_layout", lambda: lib.mg_debug_raw_layout(None, capi.RAW_LEVEL, 0, 0, C.byref(info))),
+                     ("mg_debug_raw_copy", lambda: lib.mg_debug_raw_copy(None, capi.RAW_LEVEL, 0, 0, buf, 32, 0)),
+                     ("mg_debug_raw_copy", lambda: lib.mg_debug_raw_copy(None, capi.RAW_LEVEL, 0, 0, buf, 32, 1))):
+        assert call() == -4 and lib.mg_last_error().decode().startswith(fn + ": null handle"), fn
+    assert info.elems == 77 and list(buf) == [1.0, 2.0, 3.0, 4.0]
+
+
+# ---------------------------------------------------------------- the padded layout
+def case_layouts():
+    """(dim, n, nz, element size) of every level of every case of the table, pitches as mg_geom.h rounds them"""
+    out = set()
+    for r, case, dtype in st.pairs():
+        semi = case.extra.get("semi_xy", 0)
+        for l in range(case.levels):
+            n = (case.n - 1) // (1 << l) + 1
+            nz = (case.n - 1) // (1 << max(l - semi, 0)) + 1
+            out.add((case.dim, n, nz, 8 if dtype == st.F64 else 4))
+            if r.id.startswith("mixed") and l == 0:
+                out.add((case.dim, n, nz, 8))   # the fp64 arrays beside an fp32 hierarchy
+    return sorted(out)
+
+
+def test_pitch_rounds_rows_up_to_128_bytes():
+    for nx in range(1, 600):
+        for es in (4, 8):
+            p = st.pitch_of(nx, es)
+            assert p >= nx and (p * es) % 128 == 0 and (p - nx) * es < 128
+
+
+@pytest.mark.parametrize("gh", [1, 2])
+def test_masks_partition_the_allocation(gh):
+    lays = case_layouts()
+    assert len(lays) > 30 and {l[3] for l in lays} == {4, 8} and any(l[1] != l[2] and l[0] == 3 for l in lays)
+    for dim, n, nz, es in lays:
+        if n * n * nz > 140 ** 3:
+            nz = 5   # the model of the widest rows needs no more planes than this
+        lay = st.layout_of(dim, n, nz, es, gh)
+        T = np.float64 if es == 8 else np.float32
+        shape = st.raw_shape(lay)
+        assert shape == ((nz if dim == 3 else 1) + 2 * gh, n, st.pitch_of(n, es))
+        # the model: a flat allocation indexed as the kernels index it, element ((z + gh) * ny + y) * pitch + x
+        flat = np.zeros(int(np.prod(shape)), T)
+        z, y, x = np.meshgrid(np.arange(lay.nz), np.arange(lay.ny), np.arange(lay.nx), indexing="ij")
+        flat[(((z + gh) * lay.ny + y) * lay.pitch + x).ravel()] = 1
+        raw = flat.reshape(shape)
+        pad, ghost = st.padding_mask(lay), st.ghost_mask(lay)
+        dense = np.zeros(shape, bool)
+        st.dense_view(dense, lay)[...] = True
+        assert not (pad & ghost).any() and not (pad & dense).any() and not (ghost & dense).any()
+        assert (pad | ghost | dense).all()
+        assert np.array_equal(dense, raw == 1)
+        assert st.dense_view(raw, lay).shape == (lay.nz, lay.ny, lay.nx) and st.dense_view(raw, lay).all()
+        assert int(pad.sum()) == lay.nz * lay.ny * (lay.pitch - lay.nx) and int(ghost.sum()) == 2 * gh * lay.ny * lay.pitch
+        assert st.first_outside_nonzero(raw, lay) == (0, None, None)
+        probe = raw.copy()
+        st.fill_outside(probe, lay, np.nan)
+        assert np.array_equal(np.isnan(probe), pad | ghost)
+        # one planted word each, -0.0 included
+        if lay.pitch > lay.nx:
+            probe = raw.copy()
+            probe[gh + lay.nz - 1, lay.ny - 1, lay.nx] = -0.0
+            assert st.first_outside_nonzero(probe, lay) == (1, "padding", (lay.nz - 1, lay.ny - 1, lay.nx))
+        probe = raw.copy()
+        probe[0, 0, 0] = 2.0
+        probe[-1, lay.ny - 1, lay.pitch - 1] = 2.0
+        assert st.first_outside_nonzero(probe, lay) == (2, "ghost", (-gh, 0, 0))
