@@ -19,6 +19,14 @@
 //   * per plane step: u(p+1) (corrected) -> LDS slot A; first sweep on plane p reads its x/y neighbours from LDS slot
 //     B (u(p), published one step earlier) and the z neighbours from registers; v(p) -> LDS; second sweep on plane p-1
 //     reads v(p-1)'s x/y neighbours from LDS and v(p-2), v(p) from registers; ONE barrier per plane.
+//   * the folding variant (CORR) does not carry its own rows of u(p-1), u(p), v(p-2), v(p-1) from step to step: every one of
+//     them lies in an LDS slot (published for the neighbours) when it is needed and is read back from there with one
+//     16-byte LDS read -- 102 instead of 118 VGPRs in fp64. The registers go to the coarse correction: the raw rows of the
+//     two coarse planes around the current fine plane stay in registers and rotate (the upper plane of odd fine plane 2k+1
+//     is the lower one of planes 2k+2 and 2k+3), so every second step requests ONE coarse plane, a step ahead and together
+//     with the next plane's u rows, instead of every step requesting one or two planes at its top and waiting for them
+//     (125 VGPRs, no scratch). tools/foldcheck.hip pins every variant to k_jacobi2 on the geometries where the rotation is
+//     set up anew (chunk, range and tile starts on even and odd global planes, slab pieces, the two-copies launch).
 // Per-point arithmetic, its order, -ffp-contract=off and the correctly rounded division are those of k_jacobi2 and of
 // two k_sweep3d launches: the output is bit-identical (tests/test_gpu_parity.py compares with the oracle).
 // Geometry conventions (z-slab pieces, ghost planes, the second copy `dup_planes` further up, coarse planes addressed by
@@ -171,6 +179,14 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
             }
         }
     };
+    // the raw rows of ONE coarse plane (the plane loop keeps two of them in registers and rotates them, see there)
+    auto load_rows = [&](const T *base, T (&Rw)[3][NR]) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            if (j == 0 && !lo_grp) continue;
+            load_crow(base, j, Rw[j]);
+        }
+    };
     // z phase: correction rows interpolated onto fine plane P (zero outside the grid)
     auto zfin = [&](int P, const T (&Ra)[3][NR], const T (&Rb)[3][NR], T (&Z)[3][NR]) {
         const int gP = gzo + P;
@@ -309,6 +325,9 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 *(vec *)&su[sl][1 + i0 + r][V + x0] = uc[r];
+                // (CORR: the plane loop takes its own rows of u(p-1) and u(p) out of their LDS slots -- u(z0-2) lies in the other
+                // slot, where only this thread looks before it overwrites it with u(z0))
+                if constexpr (CORR) *(vec *)&su[sl ^ 1][1 + i0 + r][V + x0] = um[r];
                 if (tail) su[sl][1 + i0 + r][V + x0 + V] = ter[r];
                 if (xt == 0) { su[0][1 + i0 + r][V - 1] = 0; su[1][1 + i0 + r][V - 1] = 0; }
             }
@@ -359,19 +378,49 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
     };
     auto fetch = [&](int pu1, int pb) { fetch_u(pu1); fetch_b(pb); };
     fetch(z0, z0 - 1);
+    // CORR: the raw rows of the coarse planes around fine plane p+1 stay in registers and rotate: CA = the lower (or only) coarse
+    // plane under it, CB = the upper one of an odd plane. The CB of odd plane 2k+1 is the CA of planes 2k+2 and 2k+3, so only
+    // every second step loads anything -- one plane, requested between the two sweeps of the step before its use like the
+    // next plane's u rows -- and no step begins by waiting for coarse data. Primed here, wherever a workgroup starts a chunk,
+    // a range or a new tile; the parity is the GLOBAL plane's (gzo + p).
+    T CA[3][NR], CB[3][NR];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+#pragma unroll
+        for (int m = 0; m < NR; m++) { CA[j][m] = 0; CB[j][m] = 0; }
+    }
+    if constexpr (CORR) {
+        load_rows(cplane(z0, 0), CA);
+        if (((gzo + z0) & 1) != 0) load_rows(cplane(z0, 1), CB);
+    }
 
     for (int p = z0 - 1; p <= z1; p++) {
         // ---- this step's operands were requested one step ago (between the two sweeps of the last step)
         vec b[R], hn = nh;
         T vtail[R], ter_n[R], hter_n = nhter;
+        if constexpr (CORR) {
+            // own rows of u(p-1) and u(p): not carried across the second sweep and the barrier (four 16-byte registers, which the
+            // coarse rows take) but read back from the slots they were published in -- u(p-1) before u(p+1) overwrites it below
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                um[r] = *(const vec *)&su[(p + 1) & 1][1 + i0 + r][V + x0];
+                uc[r] = *(const vec *)&su[p & 1][1 + i0 + r][V + x0];
+            }
+        }
 #pragma unroll
         for (int r = 0; r < R; r++) { up[r] = nu[r]; b[r] = nb[r]; ter_n[r] = nter[r]; vtail[r] = nvt[r]; }
-        T Ra[3][NR], Rb[3][NR];
-        if (CORR) raw(p + 1, Ra, Rb);
         // ---- u(p+1) + P e -> LDS slot (p+1)&1 (read by the next step's first sweep)
-        if (CORR) {
+        const bool codd = ((gzo + p + 1) & 1) != 0;   // fine plane p+1 lies between two coarse planes
+        if constexpr (CORR) {
             T Z[3][NR];
-            zfin(p + 1, Ra, Rb, Z);
+            zfin(p + 1, CA, CB, Z);
+            if (codd) {
+#pragma unroll
+                for (int j = 0; j < 3; j++) {
+#pragma unroll
+                    for (int m = 0; m < NR; m++) CA[j][m] = CB[j][m];
+                }
+            }
             correct(Z, up, ter_n, hn, hter_n, true);
         }
         if constexpr (!ZEROU) {
@@ -419,6 +468,8 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
                     for (int e = 0; e < V; e++)
                         if (((x0 + e + Y0 + i0 + r + gzo + p) & 1) != 0) v[r][e] = uc[r][e];  // not red: unchanged
                 }
+                // (CORR: v(p-2), the second sweep's lower z neighbour, out of the slot that v(p) now takes)
+                if constexpr (CORR) vm[r] = *(const vec *)&sv[sc][i0 + r][V + x0];
                 *(vec *)&sv[sc][i0 + r][V + x0] = v[r];
             }
         }
@@ -431,12 +482,20 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
         constexpr bool LATE_B = !CORR && !ZEROU;
         fetch_u(p + 2);
         if (!LATE_B) fetch_b(p + 1);
+        if constexpr (CORR) {
+            // plane p+2 is odd: its upper coarse plane (the lower one is CA already); nothing of it is used after plane z1+1
+            if (!codd && p < z1) load_rows(cplane(p + 2, 1), CB);
+        }
         // ---- second sweep on plane q = p-1, output rows
         const int q = p - 1;
         if (q >= z0 && q < z1) {
             const bool zbq = (gzo + q == 0) || (gzo + q == gzn - 1);
             const int sl = q & 1;
             const long long qo = (long long)q * g.plane;
+            if constexpr (CORR) {   // own rows of v(p-1): read back, not carried through the top of the step and the first sweep
+#pragma unroll
+                for (int r = 0; r < R; r++) vc[r] = *(const vec *)&sv[sl][i0 + r][V + x0];
+            }
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 if (outrow[r]) {
@@ -471,7 +530,10 @@ __global__ __launch_bounds__(TPR * G) void k_pairw(Geom g, Coef<T> c, T omega, c
         if (LATE_B) fetch_b(p + 1);
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < R; r++) { um[r] = uc[r]; uc[r] = up[r]; vm[r] = vc[r]; vc[r] = v[r]; bq[r] = b[r]; }
+        for (int r = 0; r < R; r++) {
+            if constexpr (!CORR) { um[r] = uc[r]; uc[r] = up[r]; vm[r] = vc[r]; vc[r] = v[r]; }   // (CORR: read back from LDS where they are used)
+            bq[r] = b[r];
+        }
     }
     }   // next chunk of this workgroup's range
     if (NORM) {
