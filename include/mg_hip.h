@@ -490,7 +490,7 @@ enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 
  * than Jacobi or red-black (cycle, solve, coarse_solve); an unknown smoother in mg_bc_smooth; distributed handles (dry runs
  * included); bad arrays, levels or masks; NULL handle. No other entry point changes behaviour, and the family allocates
  * nothing. Not combined with mg_vc_*, mg_o4_*, mg_heat_step, mg_fmg, mg_eig_solve, mg_mixed_solve or mg_pcg_solve, which
- * keep treating every face as Dirichlet; mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
+ * keep treating every face as Dirichlet (mg_fas_* reads this mask when its kind carries MG_FAS_ON_FACES, see there); mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
 int mg_bc_set_faces(mg_handle h, int mask);
 int mg_bc_get_faces(mg_handle h, int *mask);
 int mg_bc_set_form(mg_handle h, int form);
@@ -548,7 +548,8 @@ int mg_vc_project(mg_handle h, int level, int arr, double *mean);
  * with the handle's constant operator -- alpha, aniso, semi_xy, grids that are not 2^k + 1 and the shift of mg_set_shift keep
  * their meaning --, all faces Dirichlet, and a pointwise reaction g; gamma is the same on every level. The cycle is the
  * smoothing / restriction / prolongation recursion on the nonlinear problem itself: no global linearisation, no Jacobian. */
-enum mg_fas_kind { MG_FAS_CUBIC = 0 /* g = u^3 */, MG_FAS_EXP = 1 /* g = exp(u) */ };
+enum mg_fas_kind { MG_FAS_CUBIC = 0 /* g = u^3 */, MG_FAS_EXP = 1 /* g = exp(u) */,
+                   MG_FAS_ON_FACES = 256 /* OR-ed into the kind: the linear part is mg_bc_*'s operator */ };
 typedef struct mg_fas_stats {
     int32_t status;   /* 0 converged, 1 hit maxit, 2 a norm that is not finite (it is the last hist entry; U is unspecified) */
     int32_t cycles;   /* cycles done = n_hist - 1                                                                            */
@@ -594,8 +595,32 @@ typedef struct mg_fas_stats {
  * red-black (mg_fas_smooth's argument; the handle's for cycle, solve, coarse_solve); a sawtooth handle or a stage callback
  * installed (cycle, solve); distributed handles (dry runs included); bad arrays or levels and the aliasing mg_vc_residual /
  * mg_vc_smooth reject; negative or non-finite tolerances, maxit < 0; NULL handle. No other entry point changes behaviour, and
- * the family allocates nothing. Not combined with mg_vc_*, mg_bc_*, mg_o4_*, mg_fmg, mg_mixed_solve or mg_heat_step;
- * mg_set_shift(1/dt) + mg_fas_solve is one implicit reaction-diffusion step. */
+ * the family allocates nothing. Not combined with mg_vc_*, mg_o4_*, mg_fmg, mg_mixed_solve or mg_heat_step, and with
+ * mg_bc_* only as described next; mg_set_shift(1/dt) + mg_fas_solve is one implicit reaction-diffusion step.
+ *
+ * NEUMANN FACES. mg_fas_set_reaction(h, MG_FAS_CUBIC | MG_FAS_ON_FACES, gamma) (or MG_FAS_EXP | MG_FAS_ON_FACES) makes the
+ * linear part mg_bc_*'s operator: while the flag is set every mg_fas_* entry point, mg_fas_heat_* included, uses the handle's
+ * current mg_bc_set_faces mask m, read at call time -- the two calls may come in either order and mg_bc_set_faces keeps its
+ * own validation. mg_fas_get_reaction returns the kind with the flag; every other kind value stays refused. The unknowns are
+ * the nodes whose faces all lie in m, u(q) is the neighbour or its mirror image as for mg_bc_*, and with m != 0:
+ *   residual     sum = mg_bc_residual's sum in its order; r = b - (sum + G*g); Dirichlet nodes (a face outside m): r = b - u
+ *   point solve  s = mg_bc_smooth's off-diagonal sum; ps from s as above; Dirichlet nodes take b; damping and colouring as above
+ *   mg_fas_coarse_rhs  uc as above at every coarse node; rc = mg_bc_restrict's mirrored full weighting of TMP(l) (or the
+ *                injection with MG_RESTRICT_INJECT); at a coarse unknown RHS(l+1) = rc + (sum_c + G*g(uc)) with a coarse
+ *                neighbour that leaves the grid replaced by its mirror image in U(l); coarse Dirichlet nodes by m: RHS(l+1) = uc.
+ *                Still one launch. (Injecting the residual at the coarse nodes of a Neumann face makes the cycle diverge.)
+ *   mg_fas_correct  unchanged: the prolongation writes face nodes already
+ *   mg_fas_cycle, mg_fas_coarse_solve  the same recursion and loop over this point operator (V, W and F cycles)
+ *   mg_fas_solve  U = RHS on m's Dirichlet nodes first, then as above
+ *   mg_fas_heat_rhs, mg_fas_heat_step  n0 = the mirrored sum with cd0, plus G*g; m's Dirichlet nodes copy u; theta == 1 is
+ *                mg_bc_heat_rhs's stencil-free form with m
+ * - With the flag clear, or the flag set and mask 0, every mg_fas_* call makes the launches it makes without this feature,
+ *   with the same kernel instantiations: the same bits.
+ * - With gamma == 0 and the flag set, mg_fas_residual, mg_fas_smooth and mg_fas_coarse_solve give mg_bc_*'s bits and
+ *   mg_fas_heat_rhs gives mg_bc_heat_rhs's (num = b - s and den = cd, whose IEEE quotient is mg_bc_smooth's).
+ * - NO PROJECTION is done. With all 2*dim faces in m, shift 0 and gamma == 0 the operator is singular and mg_bc_solve is the
+ *   entry point; with gamma g' > 0 somewhere the problem is regular. The singular case is documented, not refused.
+ * - Nothing is allocated; mg_bc_* and mg_vc_* are unchanged; the refusals are those listed above. */
 int mg_fas_set_reaction(mg_handle h, int kind, double gamma);
 int mg_fas_get_reaction(mg_handle h, int *kind, double *gamma);
 int mg_fas_set_form(mg_handle h, int form);
@@ -673,7 +698,8 @@ int mg_heat_rhs(mg_handle h, double dt, double theta, int arr_u, int arr_dst);
  *   vc    N0(u) = -div(a grad u)          (a of mg_vc_set_coefficient; Dirichlet nodes: the box boundary)
  *   bc    N0(u) = A0 u with mirrored neighbours at the unknowns on the faces of the mask (mg_bc_set_faces; Dirichlet nodes:
  *                 the nodes on a face that is NOT in the mask)
- *   fas   N0(u) = A0 u + gamma g(u)       (mg_fas_set_reaction; Dirichlet nodes: the box boundary)
+ *   fas   N0(u) = A0 u + gamma g(u)       (mg_fas_set_reaction; Dirichlet nodes: the box boundary; with MG_FAS_ON_FACES A0 and
+ *                 the Dirichlet nodes are bc's, by the mg_bc_set_faces mask)
  * f is the source of mg_heat_set_source[_device]: a handle holds ONE source, shared by mg_heat_step and these three
  * steppers. One theta step solves, on the unknowns,
  *     (1/(theta dt)) u' + N0(u') = (f + u/dt - (1 - theta) N0(u)) / theta

@@ -316,31 +316,12 @@ __global__ __launch_bounds__(OP_THREADS) void k_bc_restrict(Geom gf, Geom gc, in
     for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
         const long long row = it / gc.nx;
         const int x = (int)(it - row * gc.nx), y = (int)(row % gc.ny), z = (int)(row / gc.ny);
-        const int gzf = (DIM == 3 && WZ) ? 2 * (gc.gz0 + z) : 0;   // global fine plane
-        const int fz = (DIM == 3) ? (WZ ? gzf - gf.gz0 : z) : 0;
-        const long long fi = lidx(gf, fz, 2 * y, 2 * x);
         T out;
         if (bc_faces(gc, z, y, x) & ~mask) {
-            out = fine[fi];
+            const int fz = (DIM == 3) ? (WZ ? 2 * (gc.gz0 + z) - gf.gz0 : z) : 0;
+            out = fine[lidx(gf, fz, 2 * y, 2 * x)];
         } else {
-            const T q = (T)0.25, hlf = (T)0.5;
-            // offsets of the lower and the upper fine neighbour per axis, mirrored where the index leaves the grid
-            const long long oxl = (2 * x - 1 < 0) ? 1 : -1, oxh = (2 * x + 1 > gf.nx - 1) ? -1 : 1;
-            const long long oyl = (2 * y - 1 < 0) ? gf.pitch : -(long long)gf.pitch, oyh = (2 * y + 1 > gf.ny - 1) ? -(long long)gf.pitch : gf.pitch;
-            const long long ozl = (gzf - 1 < 0) ? gf.plane : -gf.plane, ozh = (gzf + 1 > gf.gnz - 1) ? -gf.plane : gf.plane;
-            const long long oy[3] = {oyl, 0, oyh}, oz[3] = {ozl, 0, ozh};
-            T zacc[3];
-#pragma unroll
-            for (int dz = 0; dz < (WZ ? 3 : 1); dz++) {
-                T yacc[3];
-#pragma unroll
-                for (int dy = 0; dy < 3; dy++) {
-                    const T *p = fine + fi + (WZ ? oz[dz] : 0) + oy[dy];
-                    yacc[dy] = q * p[oxl] + hlf * p[0] + q * p[oxh];
-                }
-                zacc[dz] = q * yacc[0] + hlf * yacc[1] + q * yacc[2];
-            }
-            out = WZ ? q * zacc[0] + hlf * zacc[1] + q * zacc[2] : zacc[0];
+            out = bc_restrict_point<T, DIM, WZ>(gf, gc, fine, z, y, x);   // mg_opfamily.h: the FAS transition calls it too
         }
         coarse[lidx(gc, z, y, x)] = out;
     }

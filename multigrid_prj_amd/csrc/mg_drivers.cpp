@@ -1229,8 +1229,10 @@ struct Solver::BcFam {
     }
 };
 
-// fas (section 20): N(u) = (sigma I + A) u + gamma g(u) with the handle's constant operator, all faces Dirichlet, gamma the
-// same on every level. The cycle is the same recursion on the nonlinear problem itself: the coarse level starts from the
+// fas (section 20): N(u) = (sigma I + A) u + gamma g(u) with the handle's constant operator, gamma the same on every level.
+// All faces are Dirichlet unless the kind carries MG_FAS_ON_FACES (section 23): then the linear part is bc's operator with
+// the handle's mg_bc_set_faces mask, read at call time (fas_mask()), and every launch below takes it; mask 0 is the
+// mask-free launch. The cycle is the same recursion on the nonlinear problem itself: the coarse level starts from the
 // INJECTED iterate (kept in E), its right-hand side is R r + N_c(injected iterate), and the correction is the difference to
 // the kept copy. The kernels are in mg_fas.hip. Nothing is allocated: the state is the kind and gamma.
 template <typename T>
@@ -1240,37 +1242,45 @@ struct Solver::FasFam {
     static int residual(Solver &s, int l, const T *x, const T *b, T *r)
     {
         const Level &L = s.lv_[l];
-        return launch_fas_residual<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, x, b, r, s.d_partials_, s.o4_partials_cap_,
-                                      s.fas_plain_);
+        return launch_fas_residual<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), x, b, r, s.d_partials_,
+                                      s.o4_partials_cap_, s.fas_plain_);
     }
     static void jacobi(Solver &s, int l, const T *x, const T *b, T *out)
     {
         const Level &L = s.lv_[l];
-        launch_fas_jacobi<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, (T)s.d_.omega, x, b, out, s.fas_plain_);
+        launch_fas_jacobi<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), (T)s.d_.omega, x, b, out, s.fas_plain_);
     }
     static void rb_colour(Solver &s, int l, int colour, T *x, const T *b)
     {
         const Level &L = s.lv_[l];
-        launch_fas_rb_colour<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, colour, x, b);
+        launch_fas_rb_colour<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), colour, x, b);
     }
     static void coarse(Solver &s, int l, T *x, T *tmp, const T *b)
     {
         const Level &L = s.lv_[l];
-        launch_fas_coarse<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, (T)s.d_.omega, s.d_.smoother, x, tmp, b,
+        launch_fas_coarse<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), (T)s.d_.omega, s.d_.smoother, x, tmp, b,
                              s.d_.coarse_maxit, s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
     }
     static void heat_rhs(Solver &s, double dt, double theta, const T *u, const T *f, T *out)
     {
         const Level &L = s.lv_[0];
+        if (theta == 1.0 && s.fas_mask()) {   // as VcFam::heat_rhs: the mask decides which nodes copy u, mg_bc.hip's stencil-free form
+            launch_bc_heat_rhs<T>(s.stream_, L.g, coef0_of<T>(L), s.fas_mask(), dt, theta, u, f, out, s.fas_plain_);
+            return;
+        }
         if (theta == 1.0) {   // as VcFam::heat_rhs: the reaction is multiplied by zero too
             const double coef0[4] = {L.coef[0], L.coef[1], L.coef[2], L.cd0};
             launch_heat_rhs<T>(s.stream_, L.g, coef0, dt, theta, u, f, out);
             return;
         }
-        launch_fas_heat_rhs<T>(s.stream_, L.g, coef0_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, dt, theta, u, f, out, s.fas_plain_);
+        launch_fas_heat_rhs<T>(s.stream_, L.g, coef0_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), dt, theta, u, f, out, s.fas_plain_);
     }
     static int down(Solver &s, int l) { return s.fas_coarse_rhs_t<T>(l); }   // U(l + 1) = E(l + 1) = the injected iterate, RHS(l + 1)
-    static int up(Solver &s, int l) { return s.fas_correct_t<T>(l); }
+    static int up(Solver &s, int l) { return s.fas_correct_t<T>(l); }   // P writes face nodes already (mg_bc_cycle)
+    static void dirichlet_copy(Solver &s)   // mg_fas_solve: U = RHS on the Dirichlet nodes
+    {
+        launch_bc_dirichlet_copy<T>(s.stream_, s.lv_[0].g, s.fas_mask(), s.ptr<T>(MG_ARR_U, 0), s.ptr<T>(MG_ARR_RHS, 0));
+    }
 };
 
 template <template <typename> class F>
@@ -1816,16 +1826,21 @@ int Solver::bc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_h
 int Solver::fas_set_reaction(int kind, double gamma)
 {
     MG_TRY(driver_begin("mg_fas_set_reaction", REFUSE_DIST));
-    if (kind != MG_FAS_CUBIC && kind != MG_FAS_EXP) { set_last_error("mg_fas_set_reaction: the kind must be MG_FAS_CUBIC or MG_FAS_EXP"); return MG_ERR_BAD_ARG; }
+    const int base = kind & ~MG_FAS_ON_FACES;
+    if (base != MG_FAS_CUBIC && base != MG_FAS_EXP) {
+        set_last_error("mg_fas_set_reaction: the kind must be MG_FAS_CUBIC or MG_FAS_EXP, alone or OR-ed with MG_FAS_ON_FACES");
+        return MG_ERR_BAD_ARG;
+    }
     if (!std::isfinite(gamma)) { set_last_error("mg_fas_set_reaction: gamma must be finite"); return MG_ERR_BAD_ARG; }
-    fas_kind_ = kind;
+    fas_kind_ = base;
+    fas_faces_ = (kind & MG_FAS_ON_FACES) != 0;
     fas_gamma_ = gamma;
     return MG_OK;
 }
 
 int Solver::fas_get_reaction(int *kind, double *gamma) const
 {
-    if (kind) *kind = fas_kind_;
+    if (kind) *kind = fas_kind_ | (fas_faces_ ? MG_FAS_ON_FACES : 0);
     if (gamma) *gamma = fas_gamma_;
     return MG_OK;
 }
@@ -1835,7 +1850,7 @@ template <typename T>
 int Solver::fas_coarse_rhs_t(int fl)
 {
     lv_[fl + 1].rhs_halo_ok = false;
-    launch_fas_coarse_rhs<T>(stream_, lv_[fl].g, lv_[fl + 1].g, coef_of<T>(lv_[fl + 1]), fas_kind_, (T)fas_gamma_,
+    launch_fas_coarse_rhs<T>(stream_, lv_[fl].g, lv_[fl + 1].g, coef_of<T>(lv_[fl + 1]), fas_kind_, (T)fas_gamma_, fas_mask(),
                              d_.restriction == MG_RESTRICT_INJECT, ptr<T>(MG_ARR_U, fl), ptr<T>(MG_ARR_TMP, fl), ptr<T>(MG_ARR_U, fl + 1),
                              ptr<T>(MG_ARR_E, fl + 1), ptr<T>(MG_ARR_RHS, fl + 1));
     MG_HIP(hipGetLastError());
@@ -1875,7 +1890,7 @@ int Solver::fas_cycle(mg_cycle_stats *st) { return fam_cycle<FasFam>("mg_fas_cyc
 template <typename T>
 int Solver::fas_solve_t(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st)
 {
-    launch_bc_dirichlet_copy<T>(stream_, lv_[0].g, 0, ptr<T>(MG_ARR_U, 0), ptr<T>(MG_ARR_RHS, 0));   // U = RHS on the Dirichlet nodes
+    FasFam<T>::dirichlet_copy(*this);   // U = RHS on the Dirichlet nodes
     MG_HIP(hipGetLastError());
     int nh = 0, status = 1;
     double first = 0, last = 0;

@@ -374,32 +374,35 @@ void launch_bc_dirichlet_copy(hipStream_t s, const Geom &g, int mask, T *x, cons
 
 // ---- the semilinear operator (sigma I + A) u + gamma g(u) of the full approximation scheme (mg_fas.hip, Solver::fas_*) ----
 // c: the level's Coef (shift included); kind: enum mg_fas_kind; G = (T)gamma, 0 = the constant kernels' results bit for bit.
-// plain: never the marching tile.
+// plain: never the marching tile. mask: the Neumann faces (enum mg_face) of MG_FAS_ON_FACES -- the linear part is mg_bc.hip's
+// operator with this mask; 0: all faces Dirichlet, the launches and kernel instantiations of a handle without the flag.
 // r = b - N(u) (r == nullptr: norm only); one partial sum of r^2 per workgroup in `partials` (room for `cap`), returns how many
 template <typename T>
-int launch_fas_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, const T *u, const T *b, T *r, double *partials,
-                        int cap, bool plain);
+int launch_fas_residual(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int mask, const T *u, const T *b, T *r,
+                        double *partials, int cap, bool plain);
 // one Jacobi sweep of linearised point solves, out of place (out must not alias u)
 template <typename T>
-void launch_fas_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, const T *u, const T *b, T *out, bool plain);
+void launch_fas_jacobi(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int mask, T omega, const T *u, const T *b, T *out,
+                       bool plain);
 // launch_heat_rhs with N0(u) = A0 u + G g(u); c0: the level's Coef with the UNSHIFTED diagonal cd0. out must not alias u or f.
 template <typename T>
-void launch_fas_heat_rhs(hipStream_t s, const Geom &g, const Coef<T> &c0, int kind, T G, double dt, double theta, const T *u, const T *f,
-                         T *out, bool plain);
+void launch_fas_heat_rhs(hipStream_t s, const Geom &g, const Coef<T> &c0, int kind, T G, int mask, double dt, double theta, const T *u,
+                         const T *f, T *out, bool plain);
 // one colour pass of red-black Gauss-Seidel with the linearised point solve, in place
 template <typename T>
-void launch_fas_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int colour, T *u, const T *b);
-// the FAS transition: uc = ec = uf injected, rhsc = R rf + N_c(uf injected) (cc: Coef of the coarse level; inject: R is the injection)
+void launch_fas_rb_colour(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int mask, int colour, T *u, const T *b);
+// the FAS transition: uc = ec = uf injected, rhsc = R rf + N_c(uf injected) (cc: Coef of the coarse level; inject: R is the injection;
+// with a mask R is launch_bc_restrict_fw's mirrored full weighting and N_c mirrors its coarse neighbours)
 template <typename T>
-void launch_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const Coef<T> &cc, int kind, T G, bool inject, const T *uf,
-                           const T *rf, T *uc, T *ec, T *rhsc);
+void launch_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const Coef<T> &cc, int kind, T G, int mask, bool inject,
+                           const T *uf, const T *rf, T *uc, T *ec, T *rhsc);
 // e = x - e on every node
 template <typename T>
 void launch_fas_diff(hipStream_t s, const Geom &g, const T *x, T *e);
 // launch_coarse_solve's loop with the nonlinear sweep (smoother 1: Jacobi, 2: red-black) and the nonlinear residual, one workgroup
 template <typename T>
-void launch_fas_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, T omega, int smoother, T *x, T *tmp, const T *rhs,
-                       int maxit, double tol, int fixed, CoarseOut *d_out);
+void launch_fas_coarse(hipStream_t s, const Geom &g, const Coef<T> &c, int kind, T G, int mask, T omega, int smoother, T *x, T *tmp,
+                       const T *rhs, int maxit, double tol, int fixed, CoarseOut *d_out);
 
 // ---- device-resident array I/O (mg_io.hip, driven by Solver::device_copy) ----
 // padded: local plane 0 of a level-shaped array of geometry g with elements P; dense: the caller's dense device array of

@@ -62,6 +62,35 @@ __device__ __forceinline__ BcNb bc_neighbours(const Geom &g, long long i, int f)
 // w = 1/2 per Neumann face the node lies on (nf = 0 .. 3: at most one face per axis)
 __device__ __forceinline__ double bc_weight(int nf) { return nf == 0 ? 1.0 : (nf == 1 ? 0.5 : (nf == 2 ? 0.25 : 0.125)); }
 
+// full weighting at coarse node (z, y, x) with mirrored fine neighbours (k_bc_restrict, and the FAS transition with Neumann
+// faces): restrict_fw_point's expression (x, then y inside the z planes, weights q, hlf, q) with the fine indices that leave
+// the grid mirrored. WZ: weights along z too (3-D standard coarsening); otherwise 9-point weights per plane
+template <typename T, int DIM, bool WZ>
+__device__ __forceinline__ T bc_restrict_point(const Geom &gf, const Geom &gc, const T *__restrict__ fine, int z, int y, int x)
+{
+    const int gzf = (DIM == 3 && WZ) ? 2 * (gc.gz0 + z) : 0;   // global fine plane
+    const int fz = (DIM == 3) ? (WZ ? gzf - gf.gz0 : z) : 0;
+    const long long fi = lidx(gf, fz, 2 * y, 2 * x);
+    const T q = (T)0.25, hlf = (T)0.5;
+    // offsets of the lower and the upper fine neighbour per axis, mirrored where the index leaves the grid
+    const long long oxl = (2 * x - 1 < 0) ? 1 : -1, oxh = (2 * x + 1 > gf.nx - 1) ? -1 : 1;
+    const long long oyl = (2 * y - 1 < 0) ? gf.pitch : -(long long)gf.pitch, oyh = (2 * y + 1 > gf.ny - 1) ? -(long long)gf.pitch : gf.pitch;
+    const long long ozl = (gzf - 1 < 0) ? gf.plane : -gf.plane, ozh = (gzf + 1 > gf.gnz - 1) ? -gf.plane : gf.plane;
+    const long long oy[3] = {oyl, 0, oyh}, oz[3] = {ozl, 0, ozh};
+    T zacc[3];
+#pragma unroll
+    for (int dz = 0; dz < (WZ ? 3 : 1); dz++) {
+        T yacc[3];
+#pragma unroll
+        for (int dy = 0; dy < 3; dy++) {
+            const T *p = fine + fi + (WZ ? oz[dz] : 0) + oy[dy];
+            yacc[dy] = q * p[oxl] + hlf * p[0] + q * p[oxh];
+        }
+        zacc[dz] = q * yacc[0] + hlf * yacc[1] + q * yacc[2];
+    }
+    return WZ ? q * zacc[0] + hlf * zacc[1] + q * zacc[2] : zacc[0];
+}
+
 // The scalars of one theta step of u_t = -N0(u) + f (mg_*_heat_rhs), passed to the kernels by value:
 // rdt = (T)(1 / dt), omt = (T)(1 - theta), rth = (T)(1 / theta). The other modes do not look at them.
 template <typename T>

@@ -1,0 +1,582 @@
+"""The semilinear operator with Neumann faces on the GPU (mg_fas_* with MG_FAS_ON_FACES and the mg_bc_set_faces mask,
+multigrid_prj_amd/csrc/mg_fas.hip) against tests/fasn_ref.py: the flag, the cubic kernels bit for bit
+(plain form and mirrored marching tile), the exp kernels to the accuracy of the device's exp, the transition and the correction
+bit for bit, the two reductions on two handles (mask 0 is the mask-free family, gamma 0 is mg_bc_*), one cycle of each kind
+against long double, the solves of section 23, the time steps, and layout / determinism / isolation."""
+import functools
+import math
+
+import numpy as np
+import pytest
+
+from multigrid_prj_amd import capi
+from tests import fas_ref as fr
+from tests import fasn_ref as fn
+from tests import npref
+from tests import step_ref as sr
+from tests import storage_table as st
+from tests.test_bc_gpu import CASES, case_id, desc_kw, mixed
+from tests.test_fas_gpu import TRANSITIONS
+from tests.test_storage_gpu import Ctx, name as raw_name, snapshot
+
+pytestmark = pytest.mark.gpu
+
+NP = {capi.MG_F64: np.float64, capi.MG_F32: np.float32}
+DTYPES = pytest.mark.parametrize("dtype", [capi.MG_F64, capi.MG_F32], ids=["f64", "f32"])
+U, E, RHS, TMP, RES = capi.ARR_U, capi.ARR_E, capi.ARR_RHS, capi.ARR_TMP, capi.ARR_RES
+JAC, RB = capi.SMOOTH_JACOBI, capi.SMOOTH_RBGS
+INJECT, FULLW = capi.RESTRICT_INJECT, capi.RESTRICT_FULLW
+CUBIC, EXP, ON_FACES = capi.FAS_CUBIC, capi.FAS_EXP, capi.FAS_ON_FACES
+LD = np.longdouble
+
+
+def all_faces(dim):
+    return 63 if dim == 3 else 15
+
+
+def problem_of(s, kw, prec, kind, gamma, mask, sigma=0.0, coefs=None):
+    """the reference of a handle's descriptor in `prec`, with the handle's own level coefficients (shift included)"""
+    P = fn.FASNProblem(kind=kind, gamma=gamma, mask=mask, sigma=sigma, prec=prec, **{k: v for k, v in kw.items() if k != "dtype"})
+    P.use_handle_coefs(coefs if coefs is not None else [s.level_coefficients(l) for l in range(kw["levels"])])
+    return P
+
+
+def is_march(dim, shape, T):
+    return dim == 3 and fr.march_ok(3, shape[2], shape[1], shape[0], np.dtype(T).itemsize)
+
+
+def outside_is_zero(s, case, dtype, tag):
+    """padding columns and ghost planes of every allocation read +0 (mg_debug_raw_*; tests/test_storage_gpu.py's check (a))"""
+    x = Ctx(s, st.Case(case_id(case), *case), dtype)
+    for k, (lay, raw) in snapshot(x).items():
+        count, kind, where = st.first_outside_nonzero(raw, lay)
+        assert count == 0, (tag, raw_name(k), kind, where, count)
+
+
+# ---------------------------------------------------------------- 1. the flag
+def test_the_flag_is_accepted_and_nothing_else_is():
+    with capi.Solver(capi.make_desc(**desc_kw(3, 9, 2, {}, capi.MG_F64))) as s:
+        assert ON_FACES == 256 and s.fas_get_reaction() == (CUBIC, 0.0)
+        for kind in (CUBIC | ON_FACES, EXP | ON_FACES, EXP, CUBIC):
+            s.fas_set_reaction(kind, 1.5)
+            assert s.fas_get_reaction() == (kind, 1.5)
+        s.fas_set_reaction(EXP | ON_FACES, 0.25)
+        s.bc_set_faces(5)   # either order: the mask is read at call time
+        for bad in (258, 2, -1, 512, 256 | 2):
+            with pytest.raises(capi.MgError) as e:
+                s.fas_set_reaction(bad, 1.0)
+            assert e.value.code == -4
+            assert s.fas_get_reaction() == (EXP | ON_FACES, 0.25) and s.bc_get_faces() == 5
+        with pytest.raises(capi.MgError):
+            s.bc_set_faces(64)   # mg_bc_set_faces keeps its own validation
+        assert s.bc_get_faces() == 5
+
+
+# ---------------------------------------------------------------- 2. the cubic kernels, bit for bit
+@DTYPES
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_cubic_kernels_bit_for_bit(case, dtype):
+    """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7) and one red-black sweep on levels 0 and 1, sigma 0 and
+    500, gamma 0.7 and -0.3, masks 0 / all faces / mixed (n = 9: every single face too), standard-normal data; where the marching
+    tile takes the level the plain form is run too (mg_fas_set_form) against the same numbers. The inputs come back unmodified;
+    at 35 and 67 the padding columns and ghost planes read +0 after every flagged call."""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    rng = np.random.default_rng(100 * dim + n)
+    masks = [0, all_faces(dim), mixed(dim)] + ([1 << k for k in range(2 * dim)] if n == 9 else [])
+    layout = n in (35, 67)
+    forms_seen = set()
+    for omega in (1.0, 6.0 / 7.0):
+        kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
+        with capi.Solver(capi.make_desc(**kw)) as s:
+            for sigma in (0.0, 500.0):
+                s.set_shift(sigma)
+                for gamma in (0.7, -0.3):
+                    s.fas_set_reaction(CUBIC | ON_FACES, gamma)
+                    for mask in masks:
+                        s.bc_set_faces(mask)
+                        P = problem_of(s, kw, T, fr.CUBIC, gamma, mask, sigma)
+                        for l in range(min(levels, 2)):
+                            shape = s.level_shape(l)
+                            u, b, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
+                            jac_ref = P.jacobi(u, b, l)
+                            assert jac_ref.dtype == T
+                            first = omega == 1.0   # the residual and the red-black sweep do not depend on omega
+                            if first:
+                                r_ref, rb_ref = P.residual(u, b, l), P.rbgs(u, b, l)
+                                assert r_ref.dtype == T and rb_ref.dtype == T
+                            march = is_march(dim, shape, T)
+                            for form in ((0, 1) if march else (0,)):
+                                s.fas_set_form(form)
+                                forms_seen.add("march" if march and form == 0 else "plain")
+                                tag = (l, sigma, omega, gamma, mask, form)
+                                chk = (lambda: outside_is_zero(s, case, dtype, tag)) if layout and mask else (lambda: None)
+                                s.set_array(RHS, l, b)
+                                if first:
+                                    s.set_array(E, l, u); s.set_array(TMP, l, other)   # RES exists on level 0 only
+                                    ss = s.fas_residual(l, E, RHS, TMP); chk()
+                                    got = s.get_array(TMP, l)
+                                    assert np.array_equal(got, r_ref), (tag, int((got != r_ref).sum()))
+                                    assert ss == pytest.approx(npref.fsum_sq(r_ref), rel=1e-13) and s.fas_residual(l, E, RHS, -1) == ss
+                                    chk()
+                                    assert np.array_equal(s.get_array(E, l), u) and np.array_equal(s.get_array(RHS, l), b)
+                                    s.set_array(U, l, u)
+                                    s.fas_smooth(l, RB, 1, U, RHS); chk()
+                                    got = s.get_array(U, l)
+                                    assert np.array_equal(got, rb_ref), (tag, int((got != rb_ref).sum()))
+                                s.set_array(U, l, u)
+                                s.fas_smooth(l, JAC, 1, U, RHS); chk()
+                                got = s.get_array(U, l)
+                                assert np.array_equal(got, jac_ref), (tag, int((got != jac_ref).sum()))
+                                assert np.array_equal(s.get_array(RHS, l), b)
+                            s.fas_set_form(0)
+    want = {"march", "plain"} if dim == 3 and fr.march_side(3, n, np.dtype(T).itemsize) else {"plain"}
+    assert forms_seen == want
+
+
+# ---------------------------------------------------------------- 3. the exp kind
+@DTYPES
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 67, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)})],
+                         ids=case_id)
+def test_exp_kernels_within_8_eps(case, dtype):
+    """the same launches with g = exp(u), u uniform in [-2, 2], all faces and the mixed mask, within 8 eps_T x magnitude:
+    |b| + |A||u| + |G||g| for the residual, (|b| + |A - D||u| + |G|(|g| + |gp u|)) / |den| for the point solves, the neighbours of
+    the magnitudes mirrored as the operator's. The device's exp is specified to 1 ulp and the reference's is rounded once."""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    eps = float(np.finfo(T).eps)
+    rng = np.random.default_rng(7 * n + dim)
+    worst = {"residual": 0.0, "jacobi": 0.0, "rb": 0.0}
+    for omega in (1.0, 6.0 / 7.0):
+        kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
+        with capi.Solver(capi.make_desc(**kw)) as s:
+            for sigma, gamma in ((0.0, 0.7), (500.0, -0.3)):
+                s.set_shift(sigma); s.fas_set_reaction(EXP | ON_FACES, gamma)
+                for mask in (all_faces(dim), mixed(dim)):
+                    s.bc_set_faces(mask)
+                    P = problem_of(s, kw, T, fr.EXP, gamma, mask, sigma)
+                    for l in range(min(levels, 2)):
+                        shape = s.level_shape(l)
+                        u = rng.uniform(-2.0, 2.0, shape).astype(T)
+                        b = rng.standard_normal(shape).astype(T)
+                        mag_r, mag_ps = P.residual_mag(u, b, l).astype(np.float64), P.point_solve_mag(u, b, l).astype(np.float64)
+                        for form in ((0, 1) if is_march(dim, shape, T) else (0,)):
+                            s.fas_set_form(form)
+                            s.set_array(RHS, l, b)
+                            if omega == 1.0:
+                                s.set_array(E, l, u)
+                                s.fas_residual(l, E, RHS, TMP)
+                                d = abs(s.get_array(TMP, l).astype(np.float64) - P.residual(u, b, l).astype(np.float64)) / mag_r
+                                worst["residual"] = max(worst["residual"], float(d.max()) / eps)
+                                s.set_array(U, l, u); s.fas_smooth(l, RB, 1, U, RHS)
+                                d = abs(s.get_array(U, l).astype(np.float64) - P.rbgs(u, b, l).astype(np.float64)) / mag_ps
+                                worst["rb"] = max(worst["rb"], float(d.max()) / eps)
+                            s.set_array(U, l, u); s.fas_smooth(l, JAC, 1, U, RHS)
+                            d = abs(s.get_array(U, l).astype(np.float64) - P.jacobi(u, b, l).astype(np.float64)) / mag_ps
+                            worst["jacobi"] = max(worst["jacobi"], float(d.max()) / eps)
+                        s.fas_set_form(0)
+    print(f"{case_id(case)} {T.__name__}: largest error in units of eps x magnitude: {worst}")
+    assert max(worst.values()) <= 8.0
+
+
+# ---------------------------------------------------------------- 4. the transition and the correction, bit for bit
+@DTYPES
+@pytest.mark.parametrize("which", ["all", "mixed"])
+@pytest.mark.parametrize("restriction", [FULLW, INJECT], ids=["fullw", "inject"])
+@pytest.mark.parametrize("case", TRANSITIONS, ids=case_id)
+def test_coarse_rhs_and_correct_bit_for_bit(case, restriction, which, dtype):
+    """mg_fas_coarse_rhs: U, E and RHS of level 1 from U and TMP of level 0 (mirrored weighting, mirrored coarse neighbours, the
+    mask's coarse Dirichlet nodes); mg_fas_correct: E(1) = U(1) - E(1), U(0) += P E(1). Every other array is unchanged."""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    mask = all_faces(dim) if which == "all" else mixed(dim)
+    kw = desc_kw(dim, n, levels, extra, dtype, restriction=restriction)
+    rng = np.random.default_rng(n + dim)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.set_shift(500.0); s.bc_set_faces(mask); s.fas_set_reaction(CUBIC | ON_FACES, 0.7)
+        P = problem_of(s, kw, T, fr.CUBIC, 0.7, mask, 500.0)
+        fs, cs = s.level_shape(0), s.level_shape(1)
+        fine = {a: rng.standard_normal(fs).astype(T) for a in (U, E, RHS, TMP, RES)}
+        coarse = {a: rng.standard_normal(cs).astype(T) for a in (U, E, RHS, TMP)}
+        for a, v in fine.items():
+            s.set_array(a, 0, v)
+        for a, v in coarse.items():
+            s.set_array(a, 1, v)
+        uc0, rhs = P.coarse_rhs(fine[U], fine[TMP], 0)
+        assert uc0.dtype == T and rhs.dtype == T
+        s.fas_coarse_rhs(0)
+        assert np.array_equal(s.get_array(U, 1), uc0) and np.array_equal(s.get_array(E, 1), uc0)
+        got = s.get_array(RHS, 1)
+        assert np.array_equal(got, rhs), int((got != rhs).sum())
+        for a, v in fine.items():
+            assert np.array_equal(s.get_array(a, 0), v), a
+        assert np.array_equal(s.get_array(TMP, 1), coarse[TMP])
+        if n == 35:
+            outside_is_zero(s, case, dtype, "coarse_rhs")
+        # the correction: a coarse iterate that differs from the kept copy at the unknowns only, as after any coarse solve
+        unknown = ~P.dirichlet(cs)
+        uc = np.where(unknown, rng.standard_normal(cs).astype(T), uc0)
+        s.set_array(U, 1, uc)
+        s.fas_correct(0)
+        assert np.array_equal(s.get_array(E, 1), uc - uc0)
+        got, want = s.get_array(U, 0), P.correct(fine[U], uc, uc0, 0)
+        assert want.dtype == T and np.array_equal(got, want), int((got != want).sum())
+        for a in (E, RHS, TMP, RES):
+            assert np.array_equal(s.get_array(a, 0), fine[a]), a
+        assert np.array_equal(s.get_array(U, 1), uc) and np.array_equal(s.get_array(RHS, 1), rhs)
+        assert np.array_equal(s.get_array(TMP, 1), coarse[TMP])
+        if n == 35:
+            outside_is_zero(s, case, dtype, "correct")
+
+
+# ---------------------------------------------------------------- 5. the two reductions, on two handles
+EQ_CASES = [(3, 17, 2, {}), (3, 35, 2, {}), (3, 65, 2, {}), (2, 130, 1, {})]
+
+
+@DTYPES
+@pytest.mark.parametrize("kind", [CUBIC, EXP], ids=["cubic", "exp"])
+@pytest.mark.parametrize("case", EQ_CASES, ids=case_id)
+def test_flag_with_mask_zero_is_the_mask_free_family(case, kind, dtype):
+    """flag set and mask 0 against flag clear: residual, smooth, mg_fas_coarse_rhs, one mg_fas_cycle, mg_fas_heat_rhs -- the same
+    launches, the same bits, the partial sums included"""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    kw = desc_kw(dim, n, levels, extra, dtype, omega=6.0 / 7.0, coarse_maxit=3)
+    rng = np.random.default_rng(n)
+    with capi.Solver(capi.make_desc(**kw)) as a, capi.Solver(capi.make_desc(**kw)) as c:
+        a.fas_set_reaction(kind | ON_FACES, 0.7); c.fas_set_reaction(kind, 0.7)
+        assert a.bc_get_faces() == 0
+        shape = a.level_shape(0)
+        u = rng.uniform(-1.5, 1.5, shape).astype(T)
+        b, f = rng.standard_normal(shape).astype(T), rng.standard_normal(shape).astype(T)
+        out = []
+        for h in (a, c):
+            o = []
+            h.set_shift(10.0)
+            for form in ((0, 1) if is_march(dim, shape, T) else (0,)):
+                h.fas_set_form(form)
+                h.set_array(E, 0, u); h.set_array(RHS, 0, b)
+                o += [h.fas_residual(0, E, RHS, TMP), h.get_array(TMP, 0)]
+                for sm in (JAC, RB):
+                    h.set_array(U, 0, u); h.fas_smooth(0, sm, 1, U, RHS); o.append(h.get_array(U, 0))
+                for src in (f, None):
+                    h.heat_set_source(src)
+                    for theta in (1.0, 0.5):
+                        h.set_array(U, 0, u); h.fas_heat_rhs(1e-3, theta, U, TMP); o.append(h.get_array(TMP, 0))
+            h.fas_set_form(0)
+            if levels > 1:
+                h.set_array(U, 0, u); h.set_array(TMP, 0, b)
+                h.fas_coarse_rhs(0)
+                o += [h.get_array(x, 1) for x in (U, E, RHS)]
+            h.set_solution(u); h.set_rhs(b)
+            h.fas_cycle()
+            o.append(h.get_solution())
+            out.append(o)
+        for k, (x, y) in enumerate(zip(*out)):
+            assert np.array_equal(x, y), k
+
+
+@DTYPES
+@pytest.mark.parametrize("which", ["mixed", "all-sigma10"])
+@pytest.mark.parametrize("kind", [CUBIC, EXP], ids=["cubic", "exp"])
+@pytest.mark.parametrize("case", EQ_CASES, ids=case_id)
+def test_flag_with_gamma_zero_is_mg_bc(case, kind, which, dtype):
+    """flag set and gamma 0 against mg_bc_residual, mg_bc_smooth, mg_bc_coarse_solve (fixed sweeps) and mg_bc_heat_rhs: num = b - s,
+    den = cd, and the IEEE quotient is div_cd's"""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    mask, sigma = (mixed(dim), 0.0) if which == "mixed" else (all_faces(dim), 10.0)
+    kw = desc_kw(dim, n, levels, extra, dtype, omega=6.0 / 7.0, coarse_maxit=3)
+    rng = np.random.default_rng(n + 1)
+    with capi.Solver(capi.make_desc(**kw)) as a, capi.Solver(capi.make_desc(**kw)) as c:
+        a.fas_set_reaction(kind | ON_FACES, 0.0)
+        shape, cshape = a.level_shape(0), a.level_shape(levels - 1)
+        u, b, f = (rng.standard_normal(shape).astype(T) for _ in range(3))
+        uc, bc = (rng.standard_normal(cshape).astype(T) for _ in range(2))
+        out = []
+        for h, fam in ((a, "fas"), (c, "bc")):
+            call = lambda what, *args: getattr(h, f"{fam}_{what}")(*args)
+            o = []
+            h.bc_set_faces(mask); h.set_shift(sigma)
+            for form in ((0, 1) if is_march(dim, shape, T) else (0,)):
+                call("set_form", form)
+                h.set_array(E, 0, u); h.set_array(RHS, 0, b)
+                ss = call("residual", 0, E, RHS, TMP)
+                o += [h.get_array(TMP, 0)]
+                assert ss == pytest.approx(npref.fsum_sq(o[-1]), rel=1e-13)
+                for sm in (JAC, RB):
+                    h.set_array(U, 0, u); call("smooth", 0, sm, 1, U, RHS); o.append(h.get_array(U, 0))
+                for src in (f, None):
+                    h.heat_set_source(src)
+                    for theta in (1.0, 0.5):
+                        h.set_array(U, 0, u); call("heat_rhs", 1e-3, theta, U, TMP); o.append(h.get_array(TMP, 0))
+            call("set_form", 0)
+            if int(np.prod(cshape)) <= 32768:   # the one-workgroup coarse solve
+                h.set_array(U, levels - 1, uc); h.set_array(RHS, levels - 1, bc)
+                stc = call("coarse_solve", levels - 1, U, RHS)
+                o += [h.get_array(U, levels - 1), np.array([stc.coarse_iters, stc.coarse_flag, stc.coarse_relres])]
+            out.append(o)
+        for k, (x, y) in enumerate(zip(*out)):
+            assert np.array_equal(x, y), k
+
+
+# ---------------------------------------------------------------- 6. one cycle of each kind
+CYCLE_KINDS = {
+    "v-rb": dict(cycle=capi.CYCLE_V, smoother=RB), "w-rb": dict(cycle=capi.CYCLE_W, smoother=RB), "f-rb": dict(cycle=capi.CYCLE_F, smoother=RB),
+    "v-jacobi": dict(cycle=capi.CYCLE_V, smoother=JAC, omega=6.0 / 7.0),
+}
+CYCLE_REACTIONS = {"cubic": (CUBIC, 50.0, 0.0), "exp": (EXP, 20.0, 10.0)}   # kind, gamma, sigma: gamma g' > 0 on standard-normal data
+
+
+@functools.lru_cache(maxsize=None)
+def cycle_inputs(n):
+    """u0, b with float32 values: exact in both working dtypes, so the long-double reference is shared"""
+    rng = np.random.default_rng(n)
+    return rng.standard_normal((n, n, n)).astype(np.float32), rng.standard_normal((n, n, n)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def cycle_reference(n, levels, kind, reaction, mask, prec, coefs):
+    """coefs: mg_level_coefficients of every level (doubles, shift included) -- the contract casts THOSE to T"""
+    rk, gamma, sigma = CYCLE_REACTIONS[reaction]
+    kw = desc_kw(3, n, levels, {}, capi.MG_F64, **CYCLE_KINDS[kind])
+    u0, b = cycle_inputs(n)
+    P = problem_of(None, kw, prec, rk, gamma, mask, sigma, coefs)
+    return P.vcycle(P.as_prec(u0), P.as_prec(b), kw["coarse_maxit"])
+
+
+@DTYPES
+@pytest.mark.parametrize("which", ["all", "mixed"])
+@pytest.mark.parametrize("reaction", list(CYCLE_REACTIONS))
+@pytest.mark.parametrize("kind", list(CYCLE_KINDS))
+@pytest.mark.parametrize("n,levels", [(17, 3), (35, 2)])
+def test_one_cycle_against_long_double(n, levels, kind, reaction, which, dtype):
+    """mg_fas_cycle with the flag (V, W, F with red-black, V with Jacobi 6/7; V(2,2), 6 coarse sweeps) against the long-double
+    reference cycle on the handle's level coefficients. The GPU's distance to it may be at most 4 x the distance of fasn_ref run
+    in the working dtype: both round the same arithmetic (tests/test_fas_gpu.py's rule)."""
+    T = NP[dtype]
+    rk, gamma, sigma = CYCLE_REACTIONS[reaction]
+    mask = 63 if which == "all" else mixed(3)
+    u0, b = (a.astype(T) for a in cycle_inputs(n))
+    kw = desc_kw(3, n, levels, {}, dtype, **CYCLE_KINDS[kind])
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        s.set_shift(sigma); s.bc_set_faces(mask); s.fas_set_reaction(rk | ON_FACES, gamma); s.set_solution(u0); s.set_rhs(b)
+        coefs = tuple(s.level_coefficients(l) for l in range(levels))
+        u_T, u_LD = (cycle_reference(n, levels, kind, reaction, mask, p, coefs) for p in (T, LD))
+        tol = 4 * float(abs(u_T.astype(LD) - u_LD).max())
+        st_ = s.fas_cycle()
+        got = s.get_solution().astype(LD)
+        err = float(abs(got - u_LD).max())
+        print(f"n={n} {kind} {reaction} {which} {T.__name__}: |gpu - ld| = {err:.3e}, |fasn_ref in T - ld| = {tol / 4:.3e}")
+        assert err <= tol
+        assert np.array_equal(s.get_array(RHS, 0), b)
+        visits = {capi.CYCLE_V: 1, capi.CYCLE_W: 2 ** (levels - 2), capi.CYCLE_F: levels - 1}[kw["cycle"]]
+        assert st_.coarse_iters == visits * kw["coarse_maxit"] and st_.coarse_flag == 0
+
+
+# ---------------------------------------------------------------- 7. the solves (n = 33, 4 levels, red-black V(2,2), FULLW, 50 coarse sweeps)
+def table_desc(dtype, n=33, levels=4):
+    return dict(dim=3, n=n, levels=levels, length=1.0, alpha=1.0, dtype=dtype, cycle=capi.CYCLE_V, smoother=RB, nu_pre=2, nu_post=2,
+                restriction=FULLW, outer_pre_gs=0, coarse_mode=capi.COARSE_FIXED, coarse_maxit=fn.TABLE_COARSE_SWEEPS)
+
+
+@functools.lru_cache(maxsize=None)
+def row_reference(name, prec, cycles):
+    P = fn.table_problem(name, prec=prec)
+    b = fn.noise(P, P.shape(0), fn.TABLE[name][2]).astype(prec)
+    _, hist, status = P.solve_history(np.zeros_like(b), b, cycles, fn.TABLE_COARSE_SWEEPS)
+    return b, hist, status
+
+
+@pytest.mark.parametrize("name", fn.GPU_ROWS)
+def test_solve_history_follows_the_reference(name):
+    """fp64, 20 cycles with no tolerance: the factors of cycles 6 .. 10 match fasn_ref's to 5 %, and the entries match to 1e-6
+    relative while they are above 1e3 x the floor the float64 reference itself reaches"""
+    b, ref, _ = row_reference(name, np.float64, 20)
+    floor = float(ref.min())
+    kind, gamma, _, mask, _, _ = fn.TABLE[name]
+    with capi.Solver(capi.make_desc(**table_desc(capi.MG_F64))) as s:
+        s.fas_set_reaction(kind | ON_FACES, gamma); s.bc_set_faces(mask); s.set_rhs(b); s.set_solution(np.zeros_like(b))
+        hist, st_ = s.fas_solve(0.0, 0.0, 20)
+        print("gpu", hist, "reference", ref)
+        assert len(hist) == 21 and st_.status == 1 and st_.cycles == 20 and st_.norm0 == hist[0] and st_.norm == hist[-1]
+        assert fn.factors(hist)[5:10] == pytest.approx(fn.factors(ref)[5:10], rel=0.05)
+        above = ref > 1e3 * floor
+        assert above.sum() >= 8 and hist[above] == pytest.approx(ref[above], rel=1e-6)
+        assert np.array_equal(s.get_array(RHS, 0), b)
+
+
+@pytest.mark.parametrize("name", fn.GPU_ROWS)
+def test_fp32_reaches_the_reference_floor(name):
+    """fp32: the same solve stalls at a floor; the GPU gets within 10 x the floor fasn_ref reaches in float32 (computed here)"""
+    b, ref, _ = row_reference(name, np.float32, 20)
+    floor = float(ref.min())
+    kind, gamma, _, mask, _, _ = fn.TABLE[name]
+    with capi.Solver(capi.make_desc(**table_desc(capi.MG_F32))) as s:
+        s.fas_set_reaction(kind | ON_FACES, gamma); s.bc_set_faces(mask); s.set_rhs(b); s.set_solution(np.zeros_like(b))
+        hist, st_ = s.fas_solve(0.0, 0.0, 20)
+        print(f"{name}: float32 floor of the reference {floor:.3e}, gpu {hist.min():.3e}")
+        assert len(hist) == 21 and st_.status == 1 and hist.min() <= 10 * floor
+
+
+@functools.lru_cache(maxsize=None)
+def manufactured_reference(name, n):
+    kind, gamma, mask, f, u = fn.manufactured(name, n)
+    P = fn.problem(kind, gamma, mask, n=n, levels=fn.levels_for(n))
+    x, _, status = P.solve_history(np.zeros_like(f), f, 30, fn.TABLE_COARSE_SWEEPS, rtol=1e-12)
+    assert status == 0
+    return float(abs(x - u).max())
+
+
+@pytest.mark.parametrize("name", list(fn.MANUFACTURED))
+def test_manufactured_errors_match_the_reference(name):
+    """n = 17 and 33, solved to rtol 1e-12 within 30 cycles: status 0 and max errors within 1 % of fasn_ref's"""
+    for n in (17, 33):
+        kind, gamma, mask, f, u = fn.manufactured(name, n)
+        with capi.Solver(capi.make_desc(**table_desc(capi.MG_F64, n, fn.levels_for(n)))) as s:
+            s.bc_set_faces(mask); s.fas_set_reaction(kind | ON_FACES, gamma); s.set_rhs(f); s.set_solution(np.zeros_like(f))
+            hist, st_ = s.fas_solve(1e-12, 0.0, 30)
+            err = float(abs(s.get_solution() - u).max())
+            want = manufactured_reference(name, n)
+            print(f"{name} n={n}: gpu {err:.4e}, reference {want:.4e}, {len(hist) - 1} cycles")
+            assert st_.status == 0 and err == pytest.approx(want, rel=0.01)
+
+
+# ---------------------------------------------------------------- 8. the steps
+@DTYPES
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 67, 2, {}), (2, 130, 1, {})], ids=case_id)
+def test_heat_rhs_against_step_ref(case, dtype):
+    """mg_fas_heat_rhs with the flag against step_ref's expression on fasn_ref's operator: cubic bit for bit, exp within 8 eps x
+    magnitude; tile and plain form, theta 1 and 0.5, with and without a source, all faces and the mixed mask; a handle shift is
+    ignored and kept. At 35 and 67 the padding columns and ghost planes read +0 after every call."""
+    dim, n, levels, extra = case
+    T = NP[dtype]
+    eps = float(np.finfo(T).eps)
+    kw = desc_kw(dim, n, levels, extra, dtype)
+    rng = np.random.default_rng(1000 * dim + n)
+    forms_seen, worst_exp = set(), 0.0
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        shape = s.level_shape(0)
+        coefs0 = [s.level_coefficients(l) for l in range(levels)]   # the unshifted operator
+        f = (10.0 * rng.standard_normal(shape)).astype(T)
+        other = rng.standard_normal(shape).astype(T)
+        s.set_shift(123.0)
+        tile = is_march(dim, shape, T)
+        for rk, gamma in ((CUBIC, 0.7), (EXP, -0.3)):
+            s.fas_set_reaction(rk | ON_FACES, gamma)
+            u = (rng.uniform(-2.0, 2.0, shape) if rk == EXP else rng.standard_normal(shape)).astype(T)
+            for mask in (all_faces(dim), mixed(dim)):
+                s.bc_set_faces(mask)
+                P = problem_of(s, kw, T, rk, gamma, mask, 0.0, coefs0)
+                for src in (True, False):
+                    s.heat_set_source(f if src else None)
+                    for theta, dt, (au, ad) in ((1.0, 1e-3, (U, RHS)), (0.5, 2e-3, (E, TMP))):
+                        want = sr.step_rhs(P, u, f if src else None, dt, theta)
+                        assert want.dtype == T
+                        for form in ((0, 1) if tile else (0,)):
+                            s.fas_set_form(form)
+                            forms_seen.add("tile" if form == 0 and tile else "plain")
+                            s.set_array(au, 0, u); s.set_array(ad, 0, other)
+                            s.fas_heat_rhs(dt, theta, au, ad)
+                            got = s.get_array(ad, 0)
+                            tag = (rk, mask, src, theta, form)
+                            if rk == EXP and theta != 1.0:
+                                mag = sr.step_rhs_mag(P, u, f if src else None, dt, theta).astype(np.float64)
+                                d = float((abs(got.astype(np.float64) - want.astype(np.float64)) / mag).max()) / eps
+                                worst_exp = max(worst_exp, d)
+                                assert d <= 8.0, (tag, d)
+                                fx = sr.fixed_nodes(P, shape)
+                                assert np.array_equal(got[fx], u[fx]), tag
+                            else:
+                                assert np.array_equal(got, want), (tag, int((got != want).sum()))
+                            assert np.array_equal(s.get_array(au, 0), u), tag
+                            assert s.get_shift() == 123.0
+                            if n in (35, 67):
+                                outside_is_zero(s, case, dtype, tag)
+                        s.fas_set_form(0)
+    print(f"{case_id(case)} {T.__name__}: exp, largest error in units of eps x magnitude: {worst_exp:.3f}")
+    assert forms_seen == ({"tile", "plain"} if tile else {"plain"})
+
+
+@functools.lru_cache(maxsize=None)
+def step_reference(theta):
+    """the float64 reference step of tests/test_fasn_cpu.py item 6 -> the number of cycles after which its relative residual is
+    below 1e-10 (taken from the reference, not from the GPU)"""
+    n, dt, gamma = 17, 1e-3, 1e3
+    u0, f = fn.step_case(n)
+    P0 = fn.problem(fr.CUBIC, gamma, 63, n=n, levels=fn.levels_for(n))
+    Ps = fn.problem(fr.CUBIC, gamma, 63, sigma=sr.shift_of(dt, theta), n=n, levels=fn.levels_for(n))
+    b = sr.step_rhs(P0, u0, f, dt, theta)
+    nb, u, cycles = float(np.sqrt(np.sum(b * b))), u0.copy(), 0
+    while Ps.norm(u, b) > 1e-11 * nb:   # a decade below the 1e-10 the test asks of the GPU
+        u = Ps.vcycle(u, b, fn.TABLE_COARSE_SWEEPS); cycles += 1
+        assert cycles < 40
+    return cycles
+
+
+@pytest.mark.parametrize("theta", [1.0, 0.5])
+def test_heat_step_conserves_on_an_insulated_box(theta):
+    """tests/test_fasn_cpu.py's identity through mg_fas_heat_step (fp64, n = 17, all faces Neumann, cubic gamma 1e3, dt 1e-3):
+    sum w (u1 - u0)/dt = sum w f - gamma (theta sum w g(u1) + (1 - theta) sum w g(u0)) to ||w|| x the final residual norm plus
+    64 eps x the magnitudes of the terms"""
+    n, dt, gamma = 17, 1e-3, 1e3
+    u0, f = fn.step_case(n)
+    cycles = step_reference(theta)
+    P0 = fn.problem(fr.CUBIC, gamma, 63, n=n, levels=fn.levels_for(n))
+    with capi.Solver(capi.make_desc(**table_desc(capi.MG_F64, n, fn.levels_for(n)))) as s:
+        s.bc_set_faces(63); s.fas_set_reaction(CUBIC | ON_FACES, gamma); s.heat_set_source(f); s.set_solution(u0)
+        st_ = s.fas_heat_step(dt, theta, 1, cycles)
+        print(f"theta {theta}: {cycles} cycles, relres {st_.relres:.3e}")
+        assert st_.steps == 1 and st_.cycles == cycles and st_.relres < 1e-10
+        assert s.get_shift() == sr.shift_of(dt, theta)
+        u1 = s.get_solution()
+        resnorm = math.sqrt(s.fas_residual(0, U, RHS, -1))
+        diff, bound, mag = fn.step_identity(P0, u0, u1, f, dt, theta, resnorm)
+        print(f"identity off by {diff:.3e} (relative {abs(diff) / mag:.1e}), bound {bound:.3e}")
+        assert abs(diff) <= bound
+
+
+# ---------------------------------------------------------------- 9. determinism and isolation
+@DTYPES
+def test_memory_determinism_and_isolation(dtype):
+    T = NP[dtype]
+    kw = desc_kw(3, 33, 4, {}, dtype, smoother=JAC, omega=6.0 / 7.0)
+    rng = np.random.default_rng(8)
+    with capi.Solver(capi.make_desc(**kw)) as s, capi.Solver(capi.make_desc(**kw)) as fresh:
+        shape = s.level_shape(0)
+        b = rng.standard_normal(shape).astype(T)
+        before = s.device_bytes()
+        assert before == fresh.device_bytes()
+        fresh.set_rhs(b); fresh.set_solution(b)
+        untouched = [fresh.get_array(a, l) for l in range(4) for a in (U, E, RHS, TMP)]
+        runs = []
+        for k in range(2):
+            out = []
+            for kind, gamma, mask in ((CUBIC, 50.0, 63), (EXP, 20.0, mixed(3))):
+                s.set_shift(10.0)
+                s.bc_set_faces(mask); s.fas_set_reaction(kind | ON_FACES, gamma)
+                s.set_rhs(b); s.set_solution(np.zeros_like(b))
+                hist, _ = s.fas_solve(0.0, 0.0, 3)
+                out += [hist, s.get_solution(), s.get_array(RHS, 0)]
+                s.set_array(E, 0, b); s.fas_residual(0, E, RHS, RES); s.fas_smooth(0, RB, 1, E, RHS); s.fas_residual(0, U, RHS, TMP)
+                s.fas_coarse_rhs(0); s.fas_correct(0); s.fas_coarse_solve(3, U, RHS); s.fas_cycle()
+                out.append(s.get_solution())
+                s.fas_heat_rhs(1e-3, 0.5, U, TMP); out.append(s.get_array(TMP, 0))   # no source: mg_heat_set_source would allocate
+                hs = s.fas_heat_step(1e-3, 0.5, 2, 2); out += [s.get_solution(), np.array([hs.relres])]
+                assert s.device_bytes() == before   # no mg_fas_* call allocates
+            runs.append(out)
+        for x, y in zip(*runs):
+            assert np.array_equal(x, y)   # two runs give the same bits
+        for got, want in zip([fresh.get_array(a, l) for l in range(4) for a in (U, E, RHS, TMP)], untouched):
+            assert np.array_equal(got, want)   # a second handle is untouched
+        # a handle that ran the flagged family gives mg_cycle / mg_solve results bit-identical to a fresh handle
+        s.set_shift(0.0)
+        outs = []
+        for h in (fresh, s):
+            h.set_rhs(b); h.set_solution(np.zeros_like(b))
+            h.cycle(); u1 = h.get_solution()
+            hist, _ = h.solve(0.0, 2)
+            outs.append((u1, hist, h.get_solution()))
+        for x, y in zip(*outs):
+            assert np.array_equal(x, y)
+        assert s.device_bytes() == fresh.device_bytes() == before
