@@ -549,7 +549,9 @@ int mg_vc_project(mg_handle h, int level, int arr, double *mean);
  * their meaning --, all faces Dirichlet, and a pointwise reaction g; gamma is the same on every level. The cycle is the
  * smoothing / restriction / prolongation recursion on the nonlinear problem itself: no global linearisation, no Jacobian. */
 enum mg_fas_kind { MG_FAS_CUBIC = 0 /* g = u^3 */, MG_FAS_EXP = 1 /* g = exp(u) */,
-                   MG_FAS_ON_FACES = 256 /* OR-ed into the kind: the linear part is mg_bc_*'s operator */ };
+                   MG_FAS_ON_FACES = 256 /* OR-ed into the kind: the linear part is mg_bc_*'s operator */,
+                   /* 512 is skipped on purpose: it has always been a refused kind value that callers and the suite rely on */
+                   MG_FAS_ON_COEFFICIENT = 1024 /* OR-ed into the kind: the linear part is mg_vc_*'s operator (not with 256) */ };
 typedef struct mg_fas_stats {
     int32_t status;   /* 0 converged, 1 hit maxit, 2 a norm that is not finite (it is the last hist entry; U is unspecified) */
     int32_t cycles;   /* cycles done = n_hist - 1                                                                            */
@@ -620,7 +622,39 @@ typedef struct mg_fas_stats {
  *   mg_fas_heat_rhs gives mg_bc_heat_rhs's (num = b - s and den = cd, whose IEEE quotient is mg_bc_smooth's).
  * - NO PROJECTION is done. With all 2*dim faces in m, shift 0 and gamma == 0 the operator is singular and mg_bc_solve is the
  *   entry point; with gamma g' > 0 somewhere the problem is regular. The singular case is documented, not refused.
- * - Nothing is allocated; mg_bc_* and mg_vc_* are unchanged; the refusals are those listed above. */
+ * - Nothing is allocated; mg_bc_* and mg_vc_* are unchanged; the refusals are those listed above.
+ *
+ * VARIABLE COEFFICIENT. mg_fas_set_reaction(h, MG_FAS_CUBIC | MG_FAS_ON_COEFFICIENT, gamma) (or MG_FAS_EXP | ...) makes the
+ * linear part mg_vc_*'s operator: sigma u - div(a(x) grad u) + gamma g(u) = f. While the flag is set every mg_fas_* entry
+ * point -- residual, smooth, coarse_rhs, correct, coarse_solve, cycle (V, W, F), solve, heat_rhs, heat_step -- uses the
+ * handle's coefficient hierarchy (mg_vc_set_coefficient*), the shift of mg_set_shift and the handle's mg_vc_set_faces mask
+ * m, all read at call time: the calls may come in any order. mg_bc_set_faces is not looked at. MG_FAS_ON_COEFFICIENT is
+ * 1024, not 512: 512 has always been a refused kind value and stays one. The valid kinds are 0 and 1, alone or OR-ed with
+ * exactly one of 256 and 1024; every other value, 256 | 1024 included, is MG_ERR_BAD_ARG and changes nothing.
+ * mg_fas_get_reaction returns the kind with the flag. While the flag is set an mg_fas_* compute call on a handle with no
+ * coefficient set is MG_ERR_BAD_ARG with mg_vc_*'s "no coefficient set" message.
+ * Arithmetic in T, every operation rounded separately; s and d are mg_vc_*'s (d started from (T)sigma, neighbour order z-,
+ * y-, x-, x+, y+, z+, w_a of the level; with a mask the mirrored index is used for a and u alike), G = (T)gamma, g and gp as
+ * above:
+ *   residual     r = b - ((d*u_i - s) + G*g) at unknowns; Dirichlet nodes (a face outside m): r = b - u; the sum of r^2 over
+ *                all nodes in double, fixed order
+ *   point solve  num = (b + s) - G*(g - gp*u_i); den = d + G*gp; ps = num / den; Dirichlet nodes take b; Jacobi damping and
+ *                red-black colouring as mg_vc_*. Nothing guards den.
+ *   mg_fas_coarse_rhs  still one launch: uc = U(l) injected into U(l+1) and E(l+1); rc = mg_bc_restrict's mirrored full
+ *                weighting with m (plain full weighting for m == 0, the injection with MG_RESTRICT_INJECT); at a coarse
+ *                unknown RHS(l+1) = rc + ((d_c*uc - s_c) + G*g(uc)) with s_c, d_c from level l+1's coefficient array at the
+ *                coarse node and its coarse neighbours and level l+1's w_a, the u neighbours read from U(l) at distance 2
+ *                (z: 1 on a semi transition); on a face in m a neighbour that leaves the grid, for a or for u, is its
+ *                mirror image; coarse Dirichlet nodes: RHS(l+1) = uc
+ *   mg_fas_correct  unchanged
+ *   mg_fas_solve  U = RHS on m's Dirichlet nodes first, then as above
+ *   mg_fas_heat_rhs, mg_fas_heat_step  n0 = (d0*u_i - s) + G*g with d0 started from (T)0; Dirichlet nodes copy u; theta == 1
+ *                takes the stencil-free launches mg_vc_heat_rhs takes
+ * - With gamma == 0 and the flag set, mg_fas_residual, mg_fas_smooth, mg_fas_coarse_solve and mg_fas_heat_rhs give
+ *   mg_vc_residual's, mg_vc_smooth's, mg_vc_coarse_solve's and mg_vc_heat_rhs's bits, for mask 0 and non-zero masks
+ *   (num = b + s, den = d). With the flag clear every call gives the bits it gave before the flag existed.
+ * - NO PROJECTION is done: all faces in m, shift 0 and gamma == 0 is singular, and mg_vc_solve is the entry point for it.
+ * - Nothing is allocated; mg_vc_* and mg_bc_* are unchanged; mg_fas_set_form(1) selects the plain kernels here too. */
 int mg_fas_set_reaction(mg_handle h, int kind, double gamma);
 int mg_fas_get_reaction(mg_handle h, int *kind, double *gamma);
 int mg_fas_set_form(mg_handle h, int form);

@@ -19,6 +19,7 @@ RESTRICT_INJECT, RESTRICT_FULLW = 0, 1
 FACE_XLO, FACE_XHI, FACE_YLO, FACE_YHI, FACE_ZLO, FACE_ZHI = 1, 2, 4, 8, 16, 32   # enum mg_face: the Neumann faces of mg_bc_*
 FAS_CUBIC, FAS_EXP = 0, 1   # enum mg_fas_kind: the reaction g of mg_fas_* (u^3, exp(u))
 FAS_ON_FACES = 256          # OR-ed into the kind: the linear part is mg_bc_*'s operator with the mg_bc_set_faces mask
+FAS_ON_COEFFICIENT = 1024   # OR-ed into the kind (not with 256; 512 stays refused): the linear part is mg_vc_*'s operator
 COARSE_TOL, COARSE_FIXED = 0, 1
 ARR_U, ARR_E, ARR_RHS, ARR_TMP, ARR_RES = 0, 1, 2, 3, 4
 MG_COMM_ID_BYTES = 128
@@ -729,8 +730,10 @@ class Solver:
 
     # -- nonlinear solves by the full approximation scheme: (sigma I + A) u + gamma g(u) = f (mg_fas_*, include/mg_hip.h)
     def fas_set_reaction(self, kind, gamma):
-        """mg_fas_set_reaction: g = u^3 (FAS_CUBIC) or exp(u) (FAS_EXP), alone or OR-ed with FAS_ON_FACES (Neumann faces by
-        bc_set_faces), and its factor gamma"""
+        """mg_fas_set_reaction: g = u^3 (FAS_CUBIC) or exp(u) (FAS_EXP) and its factor gamma. The kind alone: the handle's constant
+        operator, all faces Dirichlet; OR-ed with FAS_ON_FACES: Neumann faces by bc_set_faces; OR-ed with FAS_ON_COEFFICIENT:
+        sigma u - div(a grad u) + gamma g(u) with the coefficient of vc_set_coefficient, the shift and the faces of vc_set_faces,
+        all read at call time (a compute call without a coefficient raises MgError -4). The two flags exclude each other."""
         _check(self.lib.mg_fas_set_reaction(self.h, int(kind), float(gamma)))
 
     def fas_get_reaction(self):

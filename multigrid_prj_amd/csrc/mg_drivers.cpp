@@ -1127,23 +1127,23 @@ struct Solver::VcFam {
     static int residual(Solver &s, int l, const T *x, const T *b, T *r)
     {
         const Level &L = s.lv_[l];
-        return launch_vc_residual<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, x, s.vcptr<T>(l), b, r, s.d_partials_, s.o4_partials_cap_, s.vc_plain_);
+        return launch_vc_residual<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, FAS_LINEAR, (T)0, x, s.vcptr<T>(l), b, r, s.d_partials_, s.o4_partials_cap_, s.vc_plain_);
     }
     static void jacobi(Solver &s, int l, const T *x, const T *b, T *out)
     {
         const Level &L = s.lv_[l];
-        launch_vc_jacobi<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, (T)s.d_.omega, x, s.vcptr<T>(l), b, out, s.vc_plain_);
+        launch_vc_jacobi<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, FAS_LINEAR, (T)0, (T)s.d_.omega, x, s.vcptr<T>(l), b, out, s.vc_plain_);
     }
     static void rb_colour(Solver &s, int l, int colour, T *x, const T *b)
     {
         const Level &L = s.lv_[l];
-        launch_vc_rb_colour<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, colour, x, s.vcptr<T>(l), b);
+        launch_vc_rb_colour<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, FAS_LINEAR, (T)0, colour, x, s.vcptr<T>(l), b);
     }
     static void coarse(Solver &s, int l, T *x, T *tmp, const T *b)
     {
         const Level &L = s.lv_[l];
-        launch_vc_coarse<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.vcptr<T>(l), s.d_.coarse_maxit,
-                            s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
+        launch_vc_coarse<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, FAS_LINEAR, (T)0, (T)s.d_.omega, s.d_.smoother, x, tmp, b, s.vcptr<T>(l),
+                            s.d_.coarse_maxit, s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
     }
     static void heat_rhs(Solver &s, double dt, double theta, const T *u, const T *f, T *out)
     {
@@ -1157,7 +1157,7 @@ struct Solver::VcFam {
             launch_heat_rhs<T>(s.stream_, L.g, coef0, dt, theta, u, f, out);
             return;
         }
-        launch_vc_heat_rhs<T>(s.stream_, L.g, L.coef, s.vc_mask_, dt, theta, u, s.vcptr<T>(0), f, out, s.vc_plain_);
+        launch_vc_heat_rhs<T>(s.stream_, L.g, L.coef, s.vc_mask_, FAS_LINEAR, (T)0, dt, theta, u, s.vcptr<T>(0), f, out, s.vc_plain_);
     }
     static int down(Solver &s, int l)
     {
@@ -1232,32 +1232,51 @@ struct Solver::BcFam {
 // fas (section 20): N(u) = (sigma I + A) u + gamma g(u) with the handle's constant operator, gamma the same on every level.
 // All faces are Dirichlet unless the kind carries MG_FAS_ON_FACES (section 23): then the linear part is bc's operator with
 // the handle's mg_bc_set_faces mask, read at call time (fas_mask()), and every launch below takes it; mask 0 is the
-// mask-free launch. The cycle is the same recursion on the nonlinear problem itself: the coarse level starts from the
+// mask-free launch. With MG_FAS_ON_COEFFICIENT (section 24, fas_coef_) the linear part is vc's operator instead: the launches
+// are mg_vc.hip's with the reaction, the level's coefficient array, the shift and the mg_vc_set_faces mask, and ready() asks
+// for a coefficient as VcFam's does. The cycle is the same recursion on the nonlinear problem itself: the coarse level starts from the
 // INJECTED iterate (kept in E), its right-hand side is R r + N_c(injected iterate), and the correction is the difference to
 // the kept copy. The kernels are in mg_fas.hip. Nothing is allocated: the state is the kind and gamma.
 template <typename T>
 struct Solver::FasFam {
     typedef T type;
-    static int ready(Solver &, const char *) { return MG_OK; }
+    static int ready(Solver &s, const char *fn) { return s.fas_coef_ ? VcFam<T>::ready(s, fn) : MG_OK; }
     static int residual(Solver &s, int l, const T *x, const T *b, T *r)
     {
         const Level &L = s.lv_[l];
+        if (s.fas_coef_)
+            return launch_vc_residual<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, s.fas_kind_, (T)s.fas_gamma_, x, s.vcptr<T>(l), b, r,
+                                         s.d_partials_, s.o4_partials_cap_, s.fas_plain_);
         return launch_fas_residual<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), x, b, r, s.d_partials_,
                                       s.o4_partials_cap_, s.fas_plain_);
     }
     static void jacobi(Solver &s, int l, const T *x, const T *b, T *out)
     {
         const Level &L = s.lv_[l];
+        if (s.fas_coef_) {
+            launch_vc_jacobi<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, s.fas_kind_, (T)s.fas_gamma_, (T)s.d_.omega, x, s.vcptr<T>(l), b, out,
+                                s.fas_plain_);
+            return;
+        }
         launch_fas_jacobi<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), (T)s.d_.omega, x, b, out, s.fas_plain_);
     }
     static void rb_colour(Solver &s, int l, int colour, T *x, const T *b)
     {
         const Level &L = s.lv_[l];
+        if (s.fas_coef_) {
+            launch_vc_rb_colour<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, s.fas_kind_, (T)s.fas_gamma_, colour, x, s.vcptr<T>(l), b);
+            return;
+        }
         launch_fas_rb_colour<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), colour, x, b);
     }
     static void coarse(Solver &s, int l, T *x, T *tmp, const T *b)
     {
         const Level &L = s.lv_[l];
+        if (s.fas_coef_) {
+            launch_vc_coarse<T>(s.stream_, L.g, L.coef, s.shift_, s.vc_mask_, s.fas_kind_, (T)s.fas_gamma_, (T)s.d_.omega, s.d_.smoother, x, tmp, b,
+                                s.vcptr<T>(l), s.d_.coarse_maxit, s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
+            return;
+        }
         launch_fas_coarse<T>(s.stream_, L.g, coef_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), (T)s.d_.omega, s.d_.smoother, x, tmp, b,
                              s.d_.coarse_maxit, s.d_.coarse_tol, s.d_.coarse_mode == MG_COARSE_FIXED ? 1 : 0, s.d_coarse_);
     }
@@ -1271,6 +1290,10 @@ struct Solver::FasFam {
         if (theta == 1.0) {   // as VcFam::heat_rhs: the reaction is multiplied by zero too
             const double coef0[4] = {L.coef[0], L.coef[1], L.coef[2], L.cd0};
             launch_heat_rhs<T>(s.stream_, L.g, coef0, dt, theta, u, f, out);
+            return;
+        }
+        if (s.fas_coef_) {
+            launch_vc_heat_rhs<T>(s.stream_, L.g, L.coef, s.vc_mask_, s.fas_kind_, (T)s.fas_gamma_, dt, theta, u, s.vcptr<T>(0), f, out, s.fas_plain_);
             return;
         }
         launch_fas_heat_rhs<T>(s.stream_, L.g, coef0_of<T>(L), s.fas_kind_, (T)s.fas_gamma_, s.fas_mask(), dt, theta, u, f, out, s.fas_plain_);
@@ -1826,21 +1849,24 @@ int Solver::bc_solve(double tol, int maxit, double *hist, int hist_cap, int *n_h
 int Solver::fas_set_reaction(int kind, double gamma)
 {
     MG_TRY(driver_begin("mg_fas_set_reaction", REFUSE_DIST));
-    const int base = kind & ~MG_FAS_ON_FACES;
-    if (base != MG_FAS_CUBIC && base != MG_FAS_EXP) {
-        set_last_error("mg_fas_set_reaction: the kind must be MG_FAS_CUBIC or MG_FAS_EXP, alone or OR-ed with MG_FAS_ON_FACES");
+    const int flags = MG_FAS_ON_FACES | MG_FAS_ON_COEFFICIENT;
+    const int base = kind & ~flags;
+    if ((base != MG_FAS_CUBIC && base != MG_FAS_EXP) || (kind & flags) == flags) {
+        set_last_error("mg_fas_set_reaction: the kind must be MG_FAS_CUBIC or MG_FAS_EXP, alone or OR-ed with one of MG_FAS_ON_FACES and "
+                       "MG_FAS_ON_COEFFICIENT");
         return MG_ERR_BAD_ARG;
     }
     if (!std::isfinite(gamma)) { set_last_error("mg_fas_set_reaction: gamma must be finite"); return MG_ERR_BAD_ARG; }
     fas_kind_ = base;
     fas_faces_ = (kind & MG_FAS_ON_FACES) != 0;
+    fas_coef_ = (kind & MG_FAS_ON_COEFFICIENT) != 0;
     fas_gamma_ = gamma;
     return MG_OK;
 }
 
 int Solver::fas_get_reaction(int *kind, double *gamma) const
 {
-    if (kind) *kind = fas_kind_ | (fas_faces_ ? MG_FAS_ON_FACES : 0);
+    if (kind) *kind = fas_kind_ | (fas_faces_ ? MG_FAS_ON_FACES : 0) | (fas_coef_ ? MG_FAS_ON_COEFFICIENT : 0);
     if (gamma) *gamma = fas_gamma_;
     return MG_OK;
 }
@@ -1850,9 +1876,14 @@ template <typename T>
 int Solver::fas_coarse_rhs_t(int fl)
 {
     lv_[fl + 1].rhs_halo_ok = false;
-    launch_fas_coarse_rhs<T>(stream_, lv_[fl].g, lv_[fl + 1].g, coef_of<T>(lv_[fl + 1]), fas_kind_, (T)fas_gamma_, fas_mask(),
-                             d_.restriction == MG_RESTRICT_INJECT, ptr<T>(MG_ARR_U, fl), ptr<T>(MG_ARR_TMP, fl), ptr<T>(MG_ARR_U, fl + 1),
-                             ptr<T>(MG_ARR_E, fl + 1), ptr<T>(MG_ARR_RHS, fl + 1));
+    if (fas_coef_)
+        launch_vc_fas_coarse_rhs<T>(stream_, lv_[fl].g, lv_[fl + 1].g, lv_[fl + 1].coef, shift_, vc_mask_, fas_kind_, (T)fas_gamma_,
+                                    d_.restriction == MG_RESTRICT_INJECT, ptr<T>(MG_ARR_U, fl), ptr<T>(MG_ARR_TMP, fl), vcptr<T>(fl + 1),
+                                    ptr<T>(MG_ARR_U, fl + 1), ptr<T>(MG_ARR_E, fl + 1), ptr<T>(MG_ARR_RHS, fl + 1));
+    else
+        launch_fas_coarse_rhs<T>(stream_, lv_[fl].g, lv_[fl + 1].g, coef_of<T>(lv_[fl + 1]), fas_kind_, (T)fas_gamma_, fas_mask(),
+                                 d_.restriction == MG_RESTRICT_INJECT, ptr<T>(MG_ARR_U, fl), ptr<T>(MG_ARR_TMP, fl), ptr<T>(MG_ARR_U, fl + 1),
+                                 ptr<T>(MG_ARR_E, fl + 1), ptr<T>(MG_ARR_RHS, fl + 1));
     MG_HIP(hipGetLastError());
     return MG_OK;
 }

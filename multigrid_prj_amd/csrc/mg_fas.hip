@@ -3,6 +3,8 @@
 // handle's constant operator (alpha, aniso, semi_xy, odd sizes, the shift of mg_set_shift), all faces Dirichlet -- or, with
 // MG_FAS_ON_FACES and a non-zero mg_bc_set_faces mask, mg_bc.hip's operator with Neumann faces (section 23); the reaction
 // g is pointwise, so every kernel is the 7-point stream of the constant operator plus a few flops on the centre value.
+// With MG_FAS_ON_COEFFICIENT the linear part is mg_vc_*'s operator instead and the launches are mg_vc.hip's (section 24): of
+// this file only k_fas_diff runs then.
 //
 //   FasOp<T, KIND>                       the point operator (Coef and G): res<DIM> and solve<DIM> of the contract below. The plain
 //                                        form (residual / Jacobi sweep / one red-black colour pass, every shape) and the
@@ -38,33 +40,12 @@
 namespace mg {
 namespace {
 
-enum { FAS_CUBIC = 0, FAS_EXP = 1 };   // enum mg_fas_kind
-
-__device__ __forceinline__ double fas_exp(double x) { return exp(x); }
-__device__ __forceinline__ float fas_exp(float x) { return expf(x); }
-
-// g(u) and g'(u)
-template <typename T, int KIND>
-__device__ __forceinline__ void fas_react(T u, T &gv, T &gp)
-{
-    if (KIND == FAS_CUBIC) {
-        const T q = u * u;
-        gv = q * u;
-        gp = (T)3 * q;
-    } else {
-        gv = gp = fas_exp(u);
-    }
-}
-
-// the point solve from the off-diagonal sum s, the centre value and the right-hand side
+// the point solve from the off-diagonal sum s, the centre value and the right-hand side (fas_react and the Newton step:
+// mg_opfamily.h, shared with mg_vc.hip)
 template <typename T, int KIND>
 __device__ __forceinline__ T fas_newton(const Coef<T> &c, T G, T s, T ui, T bi)
 {
-    T gv, gp;
-    fas_react<T, KIND>(ui, gv, gp);
-    const T num = (bi - s) - G * (gv - gp * ui);
-    const T den = c.cd + G * gp;
-    return num / den;
+    return fas_newton_point<T, KIND>(G, bi - s, c.cd, ui);
 }
 
 // the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h)

@@ -308,26 +308,39 @@ int launch_o4_correct_residual(hipStream_t s, const Geom &g, const double w[3], 
 // the level's coefficient array (level-shaped, ghost planes and padding zero). plain: never the marching tile. mask: the
 // Neumann faces (enum mg_face; mg_vc_set_faces): missing neighbours are mirror images, for a and u alike, and the Dirichlet
 // nodes are those on a face outside the mask; 0 launches the kernels a handle without a mask has always run.
+// react, G: the pointwise reaction G g(u) added to the operator (MG_FAS_ON_COEFFICIENT: mg_fas_* on this operator) -- react =
+// FAS_CUBIC / FAS_EXP (enum mg_fas_kind), or FAS_LINEAR: no reaction (G is not looked at), the launches and instantiations
+// of mg_vc_*. With a reaction the point solve is one Newton step on the node's own equation (mg_fas.hip's contract).
+enum { FAS_LINEAR = -1, FAS_CUBIC = 0, FAS_EXP = 1 };
 // r = b - L u (r == nullptr: norm only); one partial sum of r^2 per workgroup in `partials` (room for `cap`), returns how many
 template <typename T>
-int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, const T *u, const T *a, const T *b, T *r,
-                       double *partials, int cap, bool plain);
+int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, const T *u, const T *a,
+                       const T *b, T *r, double *partials, int cap, bool plain);
 // one Jacobi sweep, out of place (out must not alias u)
 template <typename T>
-void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, const T *u, const T *a, const T *b,
-                      T *out, bool plain);
+void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, T omega, const T *u,
+                      const T *a, const T *b, T *out, bool plain);
 // launch_heat_rhs with the UNSHIFTED operator -div(a grad .) (coef's cd and the handle's shift are not used): out = right-hand
 // side of one theta step from u (and the source f; nullptr: f = 0), u on Dirichlet nodes. out must not alias u, a or f.
 template <typename T>
-void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], int mask, double dt, double theta, const T *u, const T *a,
-                        const T *f, T *out, bool plain);
+void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], int mask, int react, T G, double dt, double theta, const T *u,
+                        const T *a, const T *f, T *out, bool plain);
 // one colour pass of red-black Gauss-Seidel, in place
 template <typename T>
-void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int colour, T *u, const T *a, const T *b);
+void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, int colour, T *u,
+                         const T *a, const T *b);
 // launch_coarse_solve's loop with the vc sweep (smoother 1: Jacobi, 2: red-black) and the vc residual, one workgroup
 template <typename T>
-void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, int smoother, T *x, T *tmp,
-                      const T *rhs, const T *a, int maxit, double tol, int fixed, CoarseOut *d_out);
+void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, T omega, int smoother,
+                      T *x, T *tmp, const T *rhs, const T *a, int maxit, double tol, int fixed, CoarseOut *d_out);
+// the FAS transition on this operator (launch_fas_coarse_rhs with the coarse level's coefficient array ac and its coef): uc = ec
+// = uf injected, rhsc = R rf + ((d_c uc - s_c) + G g(uc)) with s_c, d_c from ac at the coarse node and its coarse neighbours and
+// the u neighbours read from uf at distance 2 (z: 1 on a semi transition), mirrored for a and u alike on the faces of the mask;
+// R is the mirrored full weighting with a mask, full weighting without, or the injection; coarse Dirichlet nodes: uc.
+// react is FAS_CUBIC or FAS_EXP.
+template <typename T>
+void launch_vc_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const double coefc[4], double sigma, int mask, int react, T G,
+                              bool inject, const T *uf, const T *rf, const T *ac, T *uc, T *ec, T *rhsc);
 // launch_cg_direction_apply with q = L pn; partials of pn.q (at most cg_partials_capacity() / 2), returns how many. With a
 // mask pn and q are 0 on ITS Dirichlet nodes and the partials are those of sum w pn q, w = 1/2 per Neumann face of the node
 template <typename T>

@@ -1,6 +1,7 @@
 // mg_opfamily.h -- what the kernel files of the operator families share (mg_vc.hip, mg_bc.hip, mg_fas.hip; drivers: the
 // fam_* templates of mg_drivers.cpp): the plain form, the one-workgroup coarsest-grid solve and the launch planners, written
-// once over an operator functor. The marching tiles are each family's own and stay in its file.
+// once over an operator functor, and the pointwise reaction of mg_fas_* (fas_react, fas_newton_point), which mg_fas.hip and --
+// with MG_FAS_ON_COEFFICIENT -- mg_vc.hip add to their linear parts. The marching tiles are each family's own and stay in its file.
 //
 // An Op is a trivially copyable struct passed to the kernel by value. It carries what the family's point operator needs
 // besides u and b (vc: VcCoef and the coefficient array a; bc: Coef and the face mask; fas: Coef and gamma, the reaction kind
@@ -111,6 +112,37 @@ __device__ __forceinline__ T step_value(const StepCoef<T> &st, T ui, T fi, T n0)
     T t = st.rdt * ui;
     if (SRC) t = fi + t;
     return (t - st.omt * n0) * st.rth;
+}
+
+// ---------------------------------------------------------------- the pointwise reaction (mg_fas.hip, and mg_vc.hip with MG_FAS_ON_COEFFICIENT)
+// enum mg_fas_kind (FAS_CUBIC, FAS_EXP: mg_kernels.h); FAS_LINEAR = no reaction: every use below folds away at compile time
+__device__ __forceinline__ double fas_exp(double x) { return exp(x); }
+__device__ __forceinline__ float fas_exp(float x) { return expf(x); }
+
+// g(u) and g'(u)
+template <typename T, int KIND>
+__device__ __forceinline__ void fas_react(T u, T &gv, T &gp)
+{
+    if (KIND == FAS_CUBIC) {
+        const T q = u * u;
+        gv = q * u;
+        gp = (T)3 * q;
+    } else {
+        gv = gp = fas_exp(u);
+    }
+}
+
+// the point solve with the reaction: one Newton step around ui on the node's own equation lin_den * v + G g(v) = lin_num, from
+// the numerator and the denominator of the LINEAR point solve (fas: b - s and cd; vc: b + s and d); the IEEE quotient, nothing
+// guards den
+template <typename T, int KIND>
+__device__ __forceinline__ T fas_newton_point(T G, T lin_num, T lin_den, T ui)
+{
+    T gv, gp;
+    fas_react<T, KIND>(ui, gv, gp);
+    const T num = lin_num - G * (gv - gp * ui);
+    const T den = lin_den + G * gp;
+    return num / den;
 }
 
 // ---------------------------------------------------------------- the plain form

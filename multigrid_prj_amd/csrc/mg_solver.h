@@ -472,7 +472,8 @@ private:
     double fas_gamma_ = 0.0;
     bool fas_plain_ = false;
     bool fas_faces_ = false;   // MG_FAS_ON_FACES: the linear part is mg_bc_*'s operator with bc_mask_, read at call time
-    int fas_mask() const { return fas_faces_ ? bc_mask_ : 0; }
+    bool fas_coef_ = false;    // MG_FAS_ON_COEFFICIENT: the linear part is mg_vc_*'s operator (vc_a, shift_) with vc_mask_, read at call time
+    int fas_mask() const { return fas_coef_ ? vc_mask_ : (fas_faces_ ? bc_mask_ : 0); }
     template <typename T> int fas_coarse_rhs_t(int fl);
     template <typename T> int fas_correct_t(int fl);
     template <typename T> int fas_solve_t(double rtol, double atol, int maxit, double *hist, int hist_cap, int *n_hist, mg_fas_stats *st);

@@ -3,13 +3,14 @@
 // transfers do not depend on the operator, so only the smoother, the residual, the coarsest-grid solve and the Krylov
 // direction kernel live here.
 //
-//   VcOp<T>                        the point operator (VcCoef and a): res<DIM> and solve<DIM> of the contract below. The plain
+//   VcOp<T, MIR, KIND>             the point operator (VcCoef and a): res<DIM> and solve<DIM> of the contract below. The plain
 //                                  form (residual / Jacobi sweep / one red-black colour pass, every shape) and the
 //                                  coarsest-grid solve are mg_opfamily.h's k_op_plain<VcOp<T>, DIM, OP, SAVE> and
 //                                  k_op_coarse<VcOp<T>, DIM>
-//   k_vc_march<T, OP, SAVE, SRC>   the residual, the Jacobi sweep and the right-hand side of a theta step (OP_STEP, with or
+//   k_vc_march<T, OP, SAVE, SRC, MIR, KIND>  the residual, the Jacobi sweep and the right-hand side of a theta step (OP_STEP, with or
 //                                  without a source: mg_vc_heat_rhs) on 3-D levels with rows long enough to fill a wave
 //                                  (vc_march_ok, mg_geom.h)
+//   k_vc_fas_coarse_rhs<T, DIM, WZ, KIND, MIR>  the FAS transition on this operator (see REACTION)
 //   k_vc_cg_direction<T, DIM>      k_cg_direction_apply (mg_krylov.hip) with q = L p'
 //   k_vcn_cg_direction<T, DIM>     the same with a face mask: mirrored neighbours, Dirichlet nodes by the mask, p'.q weighted
 //   k_vcn_cg_dots<T>               k_cg_dots (mg_krylov.hip) with the weights: sum w z r and sum w z q
@@ -20,6 +21,12 @@
 // twice in s and in d. Nothing else of the contract below changes. The template flag MIR selects that form; without it
 // (mask 0) every kernel is the code it was before the mask existed, and the launchers pick MIR only for a non-zero mask.
 // w = 1/2 per Neumann face a node lies on makes diag(w) L symmetric: the Krylov dots of a masked handle carry it.
+//
+// REACTION (MG_FAS_ON_COEFFICIENT): mg_fas_* on this operator, N(u) = L u + G g(u). VcOp and k_vc_march carry
+// the reaction as the template parameter KIND (FAS_CUBIC, FAS_EXP; fas_react and fas_newton_point of mg_opfamily.h): residual
+// r = b - ((d * u_i - s) + G * g), point solve num = (b + s) - G * (g - gp * u_i), den = d + G * gp, ps = num / den, step n0 =
+// (d0 * u_i - s) + G * g. With KIND = FAS_LINEAR (the default: mg_vc_*) VcReact is empty and every such expression folds to the
+// one of the contract below: the same kernels, arguments and registers as without the parameter. tests/fasvc_ref.py restates it.
 //
 // The marching tile is k_heat_rhs's (mg_heat.hip) with TWO marched fields: a lane owns one aligned 16-byte vector of x, a
 // wave covers 64 vectors of MRY = 2 rows, MBW = 4 waves are stacked in y and the workgroup marches zc planes with the
@@ -95,9 +102,43 @@ struct VcMask<false> {
     static constexpr int mask = 0;
 };
 
-// the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h)
-template <typename T, bool MIR = false>
-struct VcOp : VcMask<MIR> {
+// the reaction of a VcOp / of the tile: G = (T)gamma of MG_FAS_ON_COEFFICIENT; no member with FAS_LINEAR, so the kernels of
+// mg_vc_* take the arguments they always took
+template <typename T, int KIND>
+struct VcReact {
+    static constexpr int kind = KIND;
+    T G;
+};
+template <typename T>
+struct VcReact<T, FAS_LINEAR> {
+    static constexpr int kind = FAS_LINEAR;
+};
+
+// the operator's value (d * u_i - s) + G * g(u_i) from the linear part lin = d * u_i - s; FAS_LINEAR: lin itself
+template <typename T, int KIND>
+__device__ __forceinline__ T vc_value(const VcReact<T, KIND> &rx, T lin, T ui)
+{
+    if constexpr (KIND == FAS_LINEAR) {
+        return lin;
+    } else {
+        T gv, gp;
+        fas_react<T, KIND>(ui, gv, gp);
+        return lin + rx.G * gv;
+    }
+}
+
+// the point solve from num = b + s and d; FAS_LINEAR: their IEEE quotient, else one Newton step (fas_newton_point)
+template <typename T, int KIND>
+__device__ __forceinline__ T vc_point(const VcReact<T, KIND> &rx, T num, T d, T ui)
+{
+    if constexpr (KIND == FAS_LINEAR) return num / d;
+    else return fas_newton_point<T, KIND>(rx.G, num, d, ui);
+}
+
+// the point operator of the plain form and of the coarsest-grid solve (mg_opfamily.h); KIND: the reaction of
+// MG_FAS_ON_COEFFICIENT, FAS_LINEAR (mg_vc_*) folds it away
+template <typename T, bool MIR = false, int KIND = FAS_LINEAR>
+struct VcOp : VcMask<MIR>, VcReact<T, KIND> {
     typedef T type;
     VcCoef<T> c;
     const T *__restrict__ a;
@@ -124,7 +165,7 @@ struct VcOp : VcMask<MIR> {
         if (fixed(g, z, y, x, i, n)) return b[i] - u[i];
         T s, d;
         vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, n, c, s, d);
-        return b[i] - (d * u[i] - s);
+        return b[i] - vc_value<T, KIND>(*this, d * u[i] - s, u[i]);
     }
 
     template <int DIM>
@@ -136,15 +177,21 @@ struct VcOp : VcMask<MIR> {
         if (fixed(g, z, y, x, i, n)) return bi;
         T s, d;
         vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, n, c, s, d);
-        const T ps = (bi + s) / d;
-        if (damped) {
+        if constexpr (KIND == FAS_LINEAR) {
+            const T ps = (bi + s) / d;
+            if (damped) {
+                const T ui = u[i];
+                return ui + omega * (ps - ui);
+            }
+            return ps;
+        } else {
             const T ui = u[i];
-            return ui + omega * (ps - ui);
+            const T ps = vc_point<T, KIND>(*this, bi + s, d, ui);
+            return damped ? ui + omega * (ps - ui) : ps;
         }
-        return ps;
     }
 
-    // the operator's value d * u_i - s at an unknown (c.sigma = 0: the unshifted operator of the time steppers)
+    // the operator's value (d * u_i - s) + G * g at an unknown (c.sigma = 0: the unshifted operator of the time steppers)
     template <int DIM>
     __device__ __forceinline__ bool n0(const Geom &g, const T *u, int z, int y, int x, bool stencil, T &v) const
     {
@@ -154,29 +201,31 @@ struct VcOp : VcMask<MIR> {
         if (stencil) {
             T s, d;
             vc_parts<T, DIM>([&](long long q, int) { return u[q]; }, a, i, n, c, s, d);
-            v = d * u[i] - s;
+            v = vc_value<T, KIND>(*this, d * u[i] - s, u[i]);
         }
         return false;
     }
 };
 
-template <typename T, bool MIR>
-__host__ __device__ VcOp<T, MIR> vc_op(const VcCoef<T> &c, const T *a, int mask)
+template <typename T, bool MIR, int KIND = FAS_LINEAR>
+__host__ __device__ VcOp<T, MIR, KIND> vc_op(const VcCoef<T> &c, const T *a, int mask, const VcReact<T, KIND> &rx = VcReact<T, KIND>{})
 {
-    VcOp<T, MIR> op;
+    VcOp<T, MIR, KIND> op;
     op.c = c;
     op.a = a;
     if constexpr (MIR) op.mask = mask;
+    if constexpr (KIND != FAS_LINEAR) op.G = rx.G;
     return op;
 }
 
 // ---------------------------------------------------------------- the marching tile (3-D)
 // OP_STEP: b is the source of the step (not loaded without SRC), st its scalars, c.sigma = 0; out = u on Dirichlet nodes.
-// MIR: the faces of `mask` are Neumann (not looked at otherwise)
-template <typename T, int OP, bool SAVE, bool SRC = true, bool MIR = false>
+// MIR: the faces of `mask` are Neumann (not looked at otherwise). KIND: the reaction rx.G * g(u) of MG_FAS_ON_COEFFICIENT, from the
+// centre value the lane holds (no load and no branch is added); FAS_LINEAR: rx is empty and the tile is the code it was
+template <typename T, int OP, bool SAVE, bool SRC = true, bool MIR = false, int KIND = FAS_LINEAR>
 __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T omega, const T *__restrict__ u, const T *__restrict__ a,
                                                        const T *__restrict__ b, T *__restrict__ out, double *__restrict__ partials,
-                                                       int nbx, int nby, int nbz, int zc, StepCoef<T> st, int mask)
+                                                       int nbx, int nby, int nbz, int zc, StepCoef<T> st, int mask, VcReact<T, KIND> rx)
 {
     constexpr int V = Vec16<T>::n;
     constexpr bool STORE = OP != OP_RES || SAVE;
@@ -282,11 +331,11 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                 }
                 T v;
                 if (OP == OP_RES) {
-                    v = bnd ? bi - ui : bi - (d * ui - s);
+                    v = bnd ? bi - ui : bi - vc_value<T, KIND>(rx, d * ui - s, ui);
                 } else if (OP == OP_STEP) {
-                    v = bnd ? ui : step_value<T, SRC>(st, ui, bi, d * ui - s);
+                    v = bnd ? ui : step_value<T, SRC>(st, ui, bi, vc_value<T, KIND>(rx, d * ui - s, ui));
                 } else {
-                    const T ps = (bi + s) / d;
+                    const T ps = vc_point<T, KIND>(rx, bi + s, d, ui);
                     v = bnd ? bi : (damped ? ui + omega * (ps - ui) : ps);
                 }
                 res[e] = v;
@@ -317,7 +366,7 @@ __global__ __launch_bounds__(64 * MBW) void k_vc_march(Geom g, VcCoef<T> c, T om
                     if (xs < line_end) {
                         vec tv = (vec)(0);
                         if (MIR && j == 0) {
-                            const VcOp<T, true> op = vc_op<T, true>(c, a, mask);
+                            const VcOp<T, true, KIND> op = vc_op<T, true, KIND>(c, a, mask, rx);
                             if (OP == OP_RES) {
                                 const T rt = op.template res<3>(g, u, b, z, yb + r, g.nx - 1);
                                 acc += (double)rt * (double)rt;
@@ -464,6 +513,45 @@ __global__ __launch_bounds__(OP_THREADS) void k_vcn_cg_dots(Geom g, int mask, co
     if (threadIdx.x == 0) { partials[blockIdx.x] = s0; partials[gridDim.x + blockIdx.x] = s1; }
 }
 
+// ---------------------------------------------------------------- the FAS transition l -> l+1 on this operator
+// k_fas_coarse_rhs (mg_fas.hip) with the coarse level's coefficient array: uf = U(l), rf = TMP(l) (the residual of level l), ac =
+// vc_a(l+1), cc = the VcCoef of level l+1; per coarse node uc = uf at the even fine node -> uco and eco; rhsc = rc + ((d_c*uc -
+// s_c) + G*g(uc)) with vc_parts over ac at the coarse node and its coarse neighbours and the u neighbours read from uf at
+// distance 2 (z: 1 on a semi transition); coarse Dirichlet nodes: rhsc = uc. MIR: the Dirichlet nodes are those on a face
+// outside the mask, rc is bc_restrict_point and a neighbour that leaves the grid, for a or for u, is its mirror image.
+template <typename T, int DIM, bool WZ, int KIND, bool MIR>
+__global__ __launch_bounds__(OP_THREADS) void k_vc_fas_coarse_rhs(Geom gf, Geom gc, VcCoef<T> cc, T G, int inject, const T *__restrict__ uf,
+                                                                   const T *__restrict__ rf, const T *__restrict__ ac, T *__restrict__ uco,
+                                                                   T *__restrict__ eco, T *__restrict__ rhsc, int mask)
+{
+    const long long nitems = (long long)gc.nx * gc.ny * gc.nz;
+    for (long long it = (long long)blockIdx.x * OP_THREADS + threadIdx.x; it < nitems; it += (long long)gridDim.x * OP_THREADS) {
+        const long long row = it / gc.nx;
+        const int x = (int)(it - row * gc.nx), y = (int)(row % gc.ny), z = (int)(row / gc.ny);
+        const int fz = (DIM == 3) ? (WZ ? 2 * (gc.gz0 + z) - gf.gz0 : z) : 0;
+        const long long fi = lidx(gf, fz, 2 * y, 2 * x), ci = lidx(gc, z, y, x);
+        const T uc = uf[fi];
+        T rhs;
+        const int cf = MIR ? bc_faces(gc, z, y, x) : 0;
+        if (MIR ? (cf & ~mask) != 0 : on_boundary(gc, z, y, x)) {
+            rhs = uc;
+        } else {
+            const T rc = inject ? rf[fi]
+                                : (MIR ? bc_restrict_point<T, DIM, WZ>(gf, gc, rf, z, y, x) : restrict_fw_point<T, DIM, WZ>(gf, gc, rf, z, y, x));
+            const long long sy = 2 * (long long)gf.pitch, sz = WZ ? 2 * gf.plane : gf.plane;
+            // the coarse neighbours in uf, in vc_parts' order; on a Neumann face the one that leaves the grid is its mirror image
+            const long long off[6] = {(cf & FZLO) ? sz : -sz, (cf & FYLO) ? sy : -sy, (cf & FXLO) ? 2 : -2,
+                                      (cf & FXHI) ? -2 : 2,   (cf & FYHI) ? -sy : sy, (cf & FZHI) ? -sz : sz};
+            T sc, dc;
+            vc_parts<T, DIM>([&](long long, int k) { return uf[fi + off[k]]; }, ac, ci, bc_neighbours(gc, ci, cf), cc, sc, dc);
+            rhs = rc + vc_value<T, KIND>(VcReact<T, KIND>{G}, dc * uc - sc, uc);
+        }
+        uco[ci] = uc;
+        eco[ci] = uc;
+        rhsc[ci] = rhs;
+    }
+}
+
 // ---------------------------------------------------------------- launchers
 template <typename T>
 VcCoef<T> vc_coef(const double coef[4], double sigma)
@@ -471,78 +559,125 @@ VcCoef<T> vc_coef(const double coef[4], double sigma)
     return VcCoef<T>{(T)(-coef[0] / 2.0), (T)(-coef[1] / 2.0), (T)(-coef[2] / 2.0), (T)sigma};
 }
 
+// launch(rx) with rx = the VcReact of `react`: the kernels and the point operator take KIND from its type
+template <typename T, typename Launch>
+auto with_vc_react(int react, T G, Launch &&launch)
+{
+    if (react == FAS_CUBIC) return launch(VcReact<T, FAS_CUBIC>{G});
+    if (react == FAS_EXP) return launch(VcReact<T, FAS_EXP>{G});
+    return launch(VcReact<T, FAS_LINEAR>{});
+}
+
+// launch(op) with the point operator of the mask and of rx
+template <typename T, int KIND, typename Launch>
+auto with_vc_op(const VcCoef<T> &c, const T *a, int mask, const VcReact<T, KIND> &rx, Launch &&launch)
+{
+    if (mask) return launch(vc_op<T, true, KIND>(c, a, mask, rx));
+    return launch(vc_op<T, false, KIND>(c, a, 0, rx));
+}
+
 }  // namespace
 
-// mask == 0 launches the instantiations without MIR: the kernels of a handle that never set a mask
+// mask == 0 launches the instantiations without MIR, react == FAS_LINEAR those without a reaction: the kernels of mg_vc_*.
+// Every (reaction, element type, mirrored) combination runs the tile where march_takes: each has no scratch and beat the plain
+// form in profiles/fasvc_times.log
 template <typename T>
-int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, const T *u, const T *a, const T *b, T *r,
-                       double *partials, int cap, bool plain)
+int launch_vc_residual(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, const T *u, const T *a,
+                       const T *b, T *r, double *partials, int cap, bool plain)
 {
     const VcCoef<T> c = vc_coef<T>(coef, sigma);
-    if (march_takes<T>(g, plain)) {
-        const MarchGrid m = march_grid<T>(g);
-        if (m.grid <= cap) {
-            const dim3 gr(m.grid), bl(64 * MBW);
-#define MG_VC(SAVE, MIR) hipLaunchKernelGGL((k_vc_march<T, OP_RES, SAVE, true, MIR>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{}, mask)
-            if (mask) { if (r) MG_VC(true, true); else MG_VC(false, true); }
-            else { if (r) MG_VC(true, false); else MG_VC(false, false); }
+    return with_vc_react<T>(react, G, [&](auto rx) {
+        constexpr int KIND = decltype(rx)::kind;
+        if (march_takes<T>(g, plain)) {
+            const MarchGrid m = march_grid<T>(g);
+            if (m.grid <= cap) {
+                const dim3 gr(m.grid), bl(64 * MBW);
+#define MG_VC(SAVE, MIR) hipLaunchKernelGGL((k_vc_march<T, OP_RES, SAVE, true, MIR, KIND>), gr, bl, 0, s, g, c, (T)1, u, a, b, r, partials, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{}, mask, rx)
+                if (mask) { if (r) MG_VC(true, true); else MG_VC(false, true); }
+                else { if (r) MG_VC(true, false); else MG_VC(false, false); }
 #undef MG_VC
-            return m.grid;
+                return m.grid;
+            }
         }
-    }
-    if (mask) return plain_residual(s, g, vc_op<T, true>(c, a, mask), u, b, r, partials, cap);
-    return plain_residual(s, g, vc_op<T, false>(c, a, 0), u, b, r, partials, cap);
+        return with_vc_op<T, KIND>(c, a, mask, rx, [&](auto op) { return plain_residual(s, g, op, u, b, r, partials, cap); });
+    });
 }
 
 template <typename T>
-void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, const T *u, const T *a, const T *b,
-                      T *out, bool plain)
+void launch_vc_jacobi(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, T omega, const T *u,
+                      const T *a, const T *b, T *out, bool plain)
 {
     const VcCoef<T> c = vc_coef<T>(coef, sigma);
-    if (march_takes<T>(g, plain)) {
-        const MarchGrid m = march_grid<T>(g);
-        const dim3 gr(m.grid), bl(64 * MBW);
-#define MG_VC(MIR) hipLaunchKernelGGL((k_vc_march<T, OP_JAC, false, true, MIR>), gr, bl, 0, s, g, c, omega, u, a, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{}, mask)
-        if (mask) MG_VC(true); else MG_VC(false);
+    with_vc_react<T>(react, G, [&](auto rx) {
+        constexpr int KIND = decltype(rx)::kind;
+        if (march_takes<T>(g, plain)) {
+            const MarchGrid m = march_grid<T>(g);
+            const dim3 gr(m.grid), bl(64 * MBW);
+#define MG_VC(MIR) hipLaunchKernelGGL((k_vc_march<T, OP_JAC, false, true, MIR, KIND>), gr, bl, 0, s, g, c, omega, u, a, b, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, StepCoef<T>{}, mask, rx)
+            if (mask) MG_VC(true); else MG_VC(false);
 #undef MG_VC
-        return;
-    }
-    if (mask) plain_jacobi(s, g, vc_op<T, true>(c, a, mask), omega, u, b, out);
-    else plain_jacobi(s, g, vc_op<T, false>(c, a, 0), omega, u, b, out);
+            return;
+        }
+        with_vc_op<T, KIND>(c, a, mask, rx, [&](auto op) { plain_jacobi(s, g, op, omega, u, b, out); });
+    });
 }
 
 template <typename T>
-void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], int mask, double dt, double theta, const T *u, const T *a,
-                        const T *f, T *out, bool plain)
+void launch_vc_heat_rhs(hipStream_t s, const Geom &g, const double coef[4], int mask, int react, T G, double dt, double theta, const T *u,
+                        const T *a, const T *f, T *out, bool plain)
 {
     const VcCoef<T> c = vc_coef<T>(coef, 0.0);   // the unshifted operator: d starts from (T)0
     const StepCoef<T> st = step_coef<T>(dt, theta);
-    if (march_takes<T>(g, plain)) {
-        const MarchGrid m = march_grid<T>(g);
-        const dim3 gr(m.grid), bl(64 * MBW);
-#define MG_VC(SRC, MIR) hipLaunchKernelGGL((k_vc_march<T, OP_STEP, true, SRC, MIR>), gr, bl, 0, s, g, c, (T)1, u, a, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st, mask)
-        if (mask) { if (f) MG_VC(true, true); else MG_VC(false, true); }
-        else { if (f) MG_VC(true, false); else MG_VC(false, false); }
+    with_vc_react<T>(react, G, [&](auto rx) {
+        constexpr int KIND = decltype(rx)::kind;
+        if (march_takes<T>(g, plain)) {
+            const MarchGrid m = march_grid<T>(g);
+            const dim3 gr(m.grid), bl(64 * MBW);
+#define MG_VC(SRC, MIR) hipLaunchKernelGGL((k_vc_march<T, OP_STEP, true, SRC, MIR, KIND>), gr, bl, 0, s, g, c, (T)1, u, a, f, out, (double *)nullptr, m.nbx, m.nby, m.nbz, m.zc, st, mask, rx)
+            if (mask) { if (f) MG_VC(true, true); else MG_VC(false, true); }
+            else { if (f) MG_VC(true, false); else MG_VC(false, false); }
 #undef MG_VC
-        return;
-    }
-    if (mask) plain_step(s, g, vc_op<T, true>(c, a, mask), st, u, f, out);
-    else plain_step(s, g, vc_op<T, false>(c, a, 0), st, u, f, out);
+            return;
+        }
+        with_vc_op<T, KIND>(c, a, mask, rx, [&](auto op) { plain_step(s, g, op, st, u, f, out); });
+    });
 }
 
 template <typename T>
-void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int colour, T *u, const T *a, const T *b)
+void launch_vc_rb_colour(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, int colour, T *u,
+                         const T *a, const T *b)
 {
-    if (mask) plain_rb_colour(s, g, vc_op<T, true>(vc_coef<T>(coef, sigma), a, mask), colour, u, b);
-    else plain_rb_colour(s, g, vc_op<T, false>(vc_coef<T>(coef, sigma), a, 0), colour, u, b);
+    with_vc_react<T>(react, G, [&](auto rx) {
+        with_vc_op<T, decltype(rx)::kind>(vc_coef<T>(coef, sigma), a, mask, rx, [&](auto op) { plain_rb_colour(s, g, op, colour, u, b); });
+    });
 }
 
 template <typename T>
-void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, T omega, int smoother, T *x, T *tmp,
-                      const T *rhs, const T *a, int maxit, double tol, int fixed, CoarseOut *d_out)
+void launch_vc_coarse(hipStream_t s, const Geom &g, const double coef[4], double sigma, int mask, int react, T G, T omega, int smoother,
+                      T *x, T *tmp, const T *rhs, const T *a, int maxit, double tol, int fixed, CoarseOut *d_out)
 {
-    if (mask) coarse_solve(s, g, vc_op<T, true>(vc_coef<T>(coef, sigma), a, mask), omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
-    else coarse_solve(s, g, vc_op<T, false>(vc_coef<T>(coef, sigma), a, 0), omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out);
+    with_vc_react<T>(react, G, [&](auto rx) {
+        with_vc_op<T, decltype(rx)::kind>(vc_coef<T>(coef, sigma), a, mask, rx,
+                                          [&](auto op) { coarse_solve(s, g, op, omega, smoother, x, tmp, rhs, maxit, tol, fixed, d_out); });
+    });
+}
+
+template <typename T>
+void launch_vc_fas_coarse_rhs(hipStream_t s, const Geom &gf, const Geom &gc, const double coefc[4], double sigma, int mask, int react, T G,
+                              bool inject, const T *uf, const T *rf, const T *ac, T *uc, T *ec, T *rhsc)
+{
+    const VcCoef<T> cc = vc_coef<T>(coefc, sigma);
+    const dim3 gr(plain_grid((long long)gc.nx * gc.ny * gc.nz, OP_MAX_BLOCKS)), bl(OP_THREADS);
+    const int inj = inject ? 1 : 0;
+#define MG_VC(DIM, WZ, KIND, MIR) hipLaunchKernelGGL((k_vc_fas_coarse_rhs<T, DIM, WZ, KIND, MIR>), gr, bl, 0, s, gf, gc, cc, G, inj, uf, rf, ac, uc, ec, rhsc, mask)
+#define MG_VC_M(DIM, WZ, KIND) if (mask) MG_VC(DIM, WZ, KIND, true); else MG_VC(DIM, WZ, KIND, false);
+#define MG_VC_K(DIM, WZ) if (react == FAS_CUBIC) { MG_VC_M(DIM, WZ, FAS_CUBIC) } else { MG_VC_M(DIM, WZ, FAS_EXP) }
+    if (gc.dim == 3 && is_semi_transition(gf, gc)) { MG_VC_K(3, false) }
+    else if (gc.dim == 3) { MG_VC_K(3, true) }
+    else { MG_VC_K(2, false) }
+#undef MG_VC_K
+#undef MG_VC_M
+#undef MG_VC
 }
 
 template <typename T>
@@ -571,15 +706,18 @@ int launch_vc_cg_wdots(hipStream_t s, const Geom &g, int mask, const T *z, const
 }
 
 #define MG_VC_INST(T)                                                                                                                  \
-    template int launch_vc_residual<T>(hipStream_t, const Geom &, const double[4], double, int, const T *, const T *, const T *, T *, \
-                                       double *, int, bool);                                                                         \
-    template void launch_vc_jacobi<T>(hipStream_t, const Geom &, const double[4], double, int, T, const T *, const T *, const T *,   \
-                                      T *, bool);                                                                                    \
-    template void launch_vc_heat_rhs<T>(hipStream_t, const Geom &, const double[4], int, double, double, const T *, const T *,        \
+    template int launch_vc_residual<T>(hipStream_t, const Geom &, const double[4], double, int, int, T, const T *, const T *, const T *, \
+                                       T *, double *, int, bool);                                                                    \
+    template void launch_vc_jacobi<T>(hipStream_t, const Geom &, const double[4], double, int, int, T, T, const T *, const T *,       \
+                                      const T *, T *, bool);                                                                         \
+    template void launch_vc_heat_rhs<T>(hipStream_t, const Geom &, const double[4], int, int, T, double, double, const T *, const T *, \
                                         const T *, T *, bool);                                                                       \
-    template void launch_vc_rb_colour<T>(hipStream_t, const Geom &, const double[4], double, int, int, T *, const T *, const T *);    \
-    template void launch_vc_coarse<T>(hipStream_t, const Geom &, const double[4], double, int, T, int, T *, T *, const T *, const T *, \
-                                      int, double, int, CoarseOut *);                                                                \
+    template void launch_vc_rb_colour<T>(hipStream_t, const Geom &, const double[4], double, int, int, T, int, T *, const T *,        \
+                                         const T *);                                                                                 \
+    template void launch_vc_coarse<T>(hipStream_t, const Geom &, const double[4], double, int, int, T, T, int, T *, T *, const T *,   \
+                                      const T *, int, double, int, CoarseOut *);                                                     \
+    template void launch_vc_fas_coarse_rhs<T>(hipStream_t, const Geom &, const Geom &, const double[4], double, int, int, T, bool,    \
+                                              const T *, const T *, const T *, T *, T *, T *);                                       \
     template int launch_vc_cg_direction<T>(hipStream_t, const Geom &, const double[4], double, int, const T *, const T *, const T *,  \
                                            T *, T *, const CgScalars *, double *);                                                   \
     template int launch_vc_cg_wdots<T>(hipStream_t, const Geom &, int, const T *, const T *, const T *, const CgScalars *, double *);
