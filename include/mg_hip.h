@@ -490,7 +490,8 @@ enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 
  * than Jacobi or red-black (cycle, solve, coarse_solve); an unknown smoother in mg_bc_smooth; distributed handles (dry runs
  * included); bad arrays, levels or masks; NULL handle. No other entry point changes behaviour, and the family allocates
  * nothing. Not combined with mg_vc_*, mg_o4_*, mg_heat_step, mg_fmg, mg_eig_solve, mg_mixed_solve or mg_pcg_solve, which
- * keep treating every face as Dirichlet (mg_fas_* reads this mask when its kind carries MG_FAS_ON_FACES, see there); mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
+ * keep treating every face as Dirichlet (mg_fas_* reads this mask when its kind carries MG_FAS_ON_FACES, mg_eig_solve after
+ * MG_EIG_OPERATOR(MG_EIG_ON_FACES) OR-ed into its m, see there); mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
 int mg_bc_set_faces(mg_handle h, int mask);
 int mg_bc_get_faces(mg_handle h, int *mask);
 int mg_bc_set_form(mg_handle h, int form);
@@ -537,7 +538,8 @@ int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, 
  *   every preconditioner application and x at the end.
  * mg_vc_direction with a mask: arr_pn and arr_q are 0 on the mask's Dirichlet nodes, neighbours are mirrored, *pq = sum w pn q.
  * mg_vc_restrict, mg_vc_project: mg_bc_restrict and mg_bc_project with this mask (no coefficient is needed).
- * MG_ERR_BAD_ARG as for mg_vc_*. Not combined with mg_fas_*, mg_o4_*, mg_fmg, mg_eig_solve or mg_mixed_solve. */
+ * MG_ERR_BAD_ARG as for mg_vc_*. Not combined with mg_fas_*, mg_o4_*, mg_fmg or mg_mixed_solve (mg_fas_* with
+ * MG_FAS_ON_COEFFICIENT and mg_eig_solve with MG_EIG_ON_COEFFICIENT read this mask, see there). */
 int mg_vc_set_faces(mg_handle h, int mask);
 int mg_vc_get_faces(mg_handle h, int *mask);
 int mg_vc_restrict(mg_handle h, int fine_level, int kind, int arr_src, int arr_dst);
@@ -801,7 +803,31 @@ int mg_fas_heat_step(mg_handle h, double dt, double theta, int nsteps, int cycle
  * MG_ERR_BAD_ARG with nothing touched: m outside [1, MG_EIG_MAX_BLOCK], nev outside [1, m], m above the number of
  * interior nodes, tol not positive and finite, maxit < 0, a bad history buffer, NULL lambda / relres, distributed handles
  * (dry runs included), a stage callback installed, an unknown family, j outside the block, NULL handle. The device
- * variants follow every rule of mg_set_array_device. */
+ * variants follow every rule of mg_set_array_device.
+ *
+ * THE OPERATOR FAMILIES. The operator of a call is OR-ed into an argument it already has, as
+ * MG_FAS_ON_* is into the kind of mg_fas_set_reaction: mg_eig_solve(h, m | MG_EIG_OPERATOR(op), ...) and
+ * mg_eig_kernel(h, kernel | MG_EIG_OPERATOR(op), ...), op an enum mg_eig_operator. There is no entry point of its own and
+ * the handle keeps nothing: every call names its operator, and everything the choice stands for is read at that call:
+ *   MG_EIG_ON_CONSTANT     the default, everything above;
+ *   MG_EIG_ON_FACES        mg_bc_*'s operator: the constant stencil of level 0 with the current shift and the faces of
+ *                          mg_bc_set_faces Neumann (mask 0: MG_EIG_ON_CONSTANT, bit for bit);
+ *   MG_EIG_ON_COEFFICIENT  mg_vc_*'s operator sigma u - div(a grad u): the coefficient of mg_vc_set_coefficient, the shift and
+ *                          the faces of mg_vc_set_faces.
+ * Node classes are mg_bc_*'s: a node on a face outside the mask is a Dirichlet node, x = 0 there; every other node is an
+ * unknown whose missing neighbours are mirror images. With Neumann faces L is not symmetric but diag(w) L is, w = 1/2 per
+ * Neumann face a node lies on, and L x = lambda x is solved in that inner product: G = S^T diag(w) S, H = S^T diag(w) L S,
+ * relres_j = ||R_j||_w / (|theta_j| ||X_j||_w), the returned X is w-orthonormal (X^T diag(w) X = I). The preconditioner is
+ * one cycle of the family (mg_bc_cycle / mg_vc_cycle from zero, as in mg_vc_pcg_solve; no Gauss-Seidel sweeps before it).
+ * Everything else -- the host dense step, soft locking, restarts, the exit by a fresh apply -- is as above. The block may
+ * be kept across a change of operator, mask, shift or coefficient: a solve first zeroes X on the Dirichlet nodes of its
+ * operator and recomputes A X, and uses no P in its first iteration. mg_eig_kernel honours the operator too: A is the
+ * family's operator and G, H and sums carry w.
+ * MG_ERR_BAD_ARG with nothing touched, beside the list above (m is checked against the unknowns of the mask): an unknown
+ * op (bits 8 and up of m / kernel other than 0, 1, 2), MG_EIG_ON_COEFFICIENT without a coefficient, what the family's cycle refuses (a cycle that is not
+ * V / W / F, a smoother other than MG_SMOOTH_JACOBI / MG_SMOOTH_RBGS), distributed handles, and the singular case: every
+ * face of the box in the mask and shift == 0 -- the operator then has the eigenvalue 0 and relres divides by |theta|; set a
+ * positive shift and subtract it from the eigenvalues. */
 #define MG_EIG_MAX_BLOCK 8
 enum mg_eig_family { MG_EIG_X = 0, MG_EIG_AX = 1, MG_EIG_W = 2, MG_EIG_AW = 3, MG_EIG_P = 4, MG_EIG_AP = 5 };
 typedef struct mg_eig_stats {
@@ -819,6 +845,8 @@ int mg_eig_get_vector(mg_handle h, int family, int j, void *host);
 int mg_eig_set_vector_device(mg_handle h, int family, int j, const void *dev, int dtype, void *stream);
 int mg_eig_get_vector_device(mg_handle h, int family, int j, void *dev, int dtype, void *stream);
 int mg_eig_block(mg_handle h, int *m);   /* block size currently allocated, 0: none */
+enum mg_eig_operator { MG_EIG_ON_CONSTANT = 0 /* the default */, MG_EIG_ON_FACES = 1, MG_EIG_ON_COEFFICIENT = 2 };
+#define MG_EIG_OPERATOR(op) ((op) << 8)   /* OR-ed into mg_eig_solve's m (<= MG_EIG_MAX_BLOCK) or mg_eig_kernel's kernel */
 
 /* Kernel-level check of the two block kernels of mg_eig.hip on the handle's block of m = mg_eig_block columns.
  * APPLY_GRAM: the first nw W columns and np P columns (np = 0 or nw) are active. AW_j = A W_j (row order of the
@@ -829,7 +857,10 @@ int mg_eig_block(mg_handle h, int *m);   /* block size currently allocated, 0: n
  *             X' = S Cx, AX' = AS Cx, P' = [W, P] Cp, AP' = [AW, AP] Cp; each element starts at 0.0 in double, adds
  *             (double) S_i * C_ij in the column order of S with every product and sum rounded, and is rounded once to T.
  *             R into the W family's first m columns: r = ax' - (T) theta_j * x', in T. sums[j] = sum r_j^2 (m doubles).
- * MG_ERR_BAD_ARG: no block, nw outside [0, m], np not 0 or nw, a NULL output, distributed handles. */
+ * With kernel | MG_EIG_OPERATOR(op): A is the family's operator (Dirichlet nodes and mirrors by its mask), every product of G and H
+ * and every r^2 of sums carries the node's weight w; the arrays COMBINE writes are the same bits whatever the operator.
+ * MG_ERR_BAD_ARG: no block, nw outside [0, m], np not 0 or nw, a NULL output, distributed handles, MG_EIG_ON_COEFFICIENT
+ * without a coefficient. */
 enum mg_eig_kernel_kind { MG_EIG_K_APPLY_GRAM = 0, MG_EIG_K_COMBINE = 1 };
 int mg_eig_kernel(mg_handle h, int kernel, int nw, int np, const double *coef, const double *theta,
                   double *G, double *H, double *sums);

@@ -33,6 +33,13 @@ EIG_MAX_BLOCK = 8
 EIG_X, EIG_AX, EIG_W, EIG_AW, EIG_P, EIG_AP = 0, 1, 2, 3, 4, 5
 EIG_K_APPLY_GRAM, EIG_K_COMBINE = 0, 1
 EIG_CONVERGED, EIG_MAXIT, EIG_NOT_FINITE = 0, 1, 2
+EIG_ON_CONSTANT, EIG_ON_FACES, EIG_ON_COEFFICIENT = 0, 1, 2   # enum mg_eig_operator
+
+
+def eig_operator(op):
+    """include/mg_hip.h::MG_EIG_OPERATOR: what is OR-ed into mg_eig_solve's m or mg_eig_kernel's kernel"""
+    return op << 8
+
 # enum mg_raw_space: the arrays mg_debug_raw_* (a test and debugging window, not a data path) can look at
 RAW_LEVEL, RAW_VC, RAW_KRYLOV, RAW_MIXED, RAW_EIG, RAW_HEAT, RAW_O4 = 0, 1, 2, 3, 4, 5, 6
 
@@ -827,14 +834,16 @@ class Solver:
         _check(self.lib.mg_fas_heat_rhs(self.h, dt, theta, arr_u, arr_dst))
 
     # -- lowest eigenpairs of sigma I + A on level 0 (multigrid-preconditioned LOBPCG)
-    def eig_solve(self, m, nev=None, tol=1e-8, maxit=200):
+    def eig_solve(self, m, nev=None, tol=1e-8, maxit=200, op=None):
         """mg_eig_solve: the nev (default m) smallest eigenpairs on a block of m vectors, warm-started from the X columns the
-        handle holds -> (lambda[m], relres[m], hist, MgEigStats); the vectors come from eig_get_vector(EIG_X, j)"""
+        handle holds -> (lambda[m], relres[m], hist, MgEigStats); the vectors come from eig_get_vector(EIG_X, j).
+        op: the operator of this call (EIG_ON_*; default: the one of eig_set_operator), OR-ed into m as MG_EIG_OPERATOR does"""
         nev = m if nev is None else nev
+        marg = m | eig_operator(self._eig_op if op is None else op)
         cap = max(maxit, 0) + 1
         lam = (C.c_double * max(m, 1))(); rel = (C.c_double * max(m, 1))()
         hist = (C.c_double * cap)(); nh = C.c_int(0); st = MgEigStats()
-        _check(self.lib.mg_eig_solve(self.h, m, nev, tol, maxit, lam, rel, hist, cap, C.byref(nh), C.byref(st)))
+        _check(self.lib.mg_eig_solve(self.h, marg, nev, tol, maxit, lam, rel, hist, cap, C.byref(nh), C.byref(st)))
         return np.array(lam[:m]), np.array(rel[:m]), np.array(hist[:min(nh.value, cap)]), st
 
     def eig_set_vector(self, family, j, a):
@@ -857,20 +866,35 @@ class Solver:
         """mg_eig_block: the block size currently allocated, 0: none"""
         m = C.c_int(0); _check(self.lib.mg_eig_block(self.h, C.byref(m))); return m.value
 
-    def eig_kernel_gram(self, nw, np_):
-        """mg_eig_kernel(EIG_K_APPLY_GRAM): AW = A W on the first nw W columns, then (G, H) over [X, W, P]"""
+    _eig_op = EIG_ON_CONSTANT
+
+    def eig_set_operator(self, op):
+        """The operator eig_solve / eig_kernel_* pass on when they are given none: EIG_ON_CONSTANT (default), EIG_ON_FACES
+        (mg_bc_*'s operator) or EIG_ON_COEFFICIENT (mg_vc_*'s). One integer kept by THIS OBJECT -- the C interface has no
+        setter, every mg_eig_solve / mg_eig_kernel call names its operator (MG_EIG_OPERATOR); the mask, the shift and the
+        coefficient are read by the library at that call"""
+        if op not in (EIG_ON_CONSTANT, EIG_ON_FACES, EIG_ON_COEFFICIENT):
+            raise MgError(-4, "eig_set_operator: the operator must be EIG_ON_CONSTANT, EIG_ON_FACES or EIG_ON_COEFFICIENT")
+        self._eig_op = op
+
+    def eig_get_operator(self) -> int:
+        return self._eig_op
+
+    def eig_kernel_gram(self, nw, np_, op=None):
+        """mg_eig_kernel(EIG_K_APPLY_GRAM): AW = A W on the first nw W columns, then (G, H) over [X, W, P]; op as in eig_solve"""
         s = self.eig_block() + nw + np_
         G = np.zeros((s, s)); H = np.zeros((s, s)); dp = C.POINTER(C.c_double)
-        _check(self.lib.mg_eig_kernel(self.h, EIG_K_APPLY_GRAM, nw, np_, None, None, G.ctypes.data_as(dp), H.ctypes.data_as(dp), None))
+        _check(self.lib.mg_eig_kernel(self.h, EIG_K_APPLY_GRAM | eig_operator(self._eig_op if op is None else op), nw, np_, None, None, G.ctypes.data_as(dp), H.ctypes.data_as(dp), None))
         return G, H
 
-    def eig_kernel_combine(self, nw, np_, cx, cp, theta):
-        """mg_eig_kernel(EIG_K_COMBINE): the in-place block update with Cx (s x m), Cp ((nw + np) x nw), theta (m) -> sums r^2"""
+    def eig_kernel_combine(self, nw, np_, cx, cp, theta, op=None):
+        """mg_eig_kernel(EIG_K_COMBINE): the in-place block update with Cx (s x m), Cp ((nw + np) x nw), theta (m) -> sums r^2
+        (weighted with an operator family); op as in eig_solve"""
         m = self.eig_block(); dp = C.POINTER(C.c_double)
         coef = np.concatenate([np.ascontiguousarray(cx, np.float64).ravel(), np.ascontiguousarray(cp, np.float64).ravel()])
         th = np.ascontiguousarray(theta, np.float64); sums = np.zeros(m)
         assert coef.size == (m + nw + np_) * m + (nw + np_) * nw and th.size == m
-        _check(self.lib.mg_eig_kernel(self.h, EIG_K_COMBINE, nw, np_, coef.ctypes.data_as(dp), th.ctypes.data_as(dp), None, None,
+        _check(self.lib.mg_eig_kernel(self.h, EIG_K_COMBINE | eig_operator(self._eig_op if op is None else op), nw, np_, coef.ctypes.data_as(dp), th.ctypes.data_as(dp), None, None,
                                       sums.ctypes.data_as(dp)))
         return sums
 

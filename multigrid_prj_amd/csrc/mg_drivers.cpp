@@ -126,14 +126,14 @@ int Solver::krylov_alloc()
 // z = M r: the cycle code works on level 0's U / RHS slots, so z and r take them for the duration (pointer swap, no copy).
 // The cycle may itself leave its result in the array that was TMP (out-of-place sweeps swap U / TMP): whatever U points
 // at afterwards is z, and TMP keeps the other buffer.
-int Solver::precondition(void **z, void *r, bool vc)
+int Solver::precondition(void **z, void *r, Precond fam)
 {
     Level &L0 = lv_[0];
     void *const x_base = L0.base[MG_ARR_U], *const b_base = L0.base[MG_ARR_RHS];
     MG_HIP(hipMemsetAsync(*z, 0, L0.alloc_elems * esize(), stream_));
     L0.base[MG_ARR_U] = *z;
     L0.base[MG_ARR_RHS] = r;
-    const int rc = vc ? fam_cycle_enqueue<VcFam>() : outer_iteration_enqueue();
+    const int rc = fam == PRE_VC ? fam_cycle_enqueue<VcFam>() : (fam == PRE_BC ? fam_cycle_enqueue<BcFam>() : outer_iteration_enqueue());
     *z = L0.base[MG_ARR_U];
     L0.base[MG_ARR_U] = x_base;
     L0.base[MG_ARR_RHS] = b_base;
@@ -180,7 +180,7 @@ int Solver::pcg_body_t(bool vc, ResidualSum residual_sum, DirectionApply directi
         int pc = KP0, pn = KP1;   // p ping-pongs: another workgroup may still read p_k at a neighbour while p_{k+1} is written
         MG_HIP(hipMemsetAsync(kry_[pc], 0, L0.alloc_elems * esize(), stream_));   // p_{-1} = 0: p_0 = z_0 + 0 p_{-1} = z_0
         auto direction = [&](int mode) -> int {   // z = M r, gamma, beta, p_{k+1} = z + beta p_k, q = A p_{k+1}, alpha
-            MG_TRY(precondition(&kry_[KZ], kry_[KR], vc));
+            MG_TRY(precondition(&kry_[KZ], kry_[KR], vc ? PRE_VC : PRE_CONSTANT));
             if (singular) MG_TRY(bc_project_ptr_t<T>(vc_mask, g, kp(KZ), nullptr));   // fetches the mean: a second synchronisation per iteration, in this case only
             int np = vc_mask ? launch_vc_cg_wdots<T>(stream_, g, vc_mask, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_)
                              : launch_cg_dots<T>(stream_, g, kp(KZ), kp(KR), kp(KQ), d_cg_, d_cg_part_);
@@ -846,6 +846,7 @@ int Solver::eig_gram_t(int mode, int nw, int np, double *G, double *H)
     const Level &L0 = lv_[0];
     const Geom &g = L0.g;
     const Coef<T> c = coef_of<T>(L0);
+    const EigOp<T> op = eig_op_t<T>();
     const int m = eig_m_;
     auto col = [&](int fam, int j) { return reinterpret_cast<T *>(eig_[fam][j]) + L0.gh * g.plane; };
     // S and AS in column order; `interior`: the column is read as 0 on Dirichlet nodes (what the apply is about to make of it)
@@ -881,7 +882,7 @@ int Solver::eig_gram_t(int mode, int nw, int np, double *G, double *H)
                 for (int r = a.na; r < EIG_GRAM_ROWS; r++) a.row[r] = a.row[0];
                 for (int j = nb; j < EIG_GRAM_COLS; j++) { a.col[j] = a.col[0]; a.acol[j] = a.acol[0]; }
                 a.col_interior = interior[c0] ? 1 : 0;
-                nblocks = launch_eig_gram<T>(stream_, g, c, a, applied[c0] && r0 == 0, d_eig_part_ + (size_t)nt * TILE * EIG_MAX_BLOCKS);
+                nblocks = launch_eig_gram<T>(stream_, g, c, op, a, applied[c0] && r0 == 0, d_eig_part_ + (size_t)nt * TILE * EIG_MAX_BLOCKS);
                 tiles[nt++] = Tile{r0, a.na, c0, nb};
             }
         }
@@ -914,6 +915,9 @@ int Solver::eig_combine_t(int nw, int np, const double *coef, const double *thet
     auto col = [&](int fam, int j) { return reinterpret_cast<T *>(eig_[fam][j]) + L0.gh * g.plane; };
     EigCombineArgs<T> a{};
     a.m = m; a.nw = nw; a.np = np;
+    const EigOp<T> op = eig_op_t<T>();
+    a.mask = op.mask;
+    a.weighted = op.kind != EIG_OP_CONSTANT && op.mask != 0;   // mask 0: every weight is 1
     int k = 0;
     for (int j = 0; j < m; j++, k++) { a.s[k] = col(MG_EIG_X, j); a.as[k] = col(MG_EIG_AX, j); }
     for (int j = 0; j < nw; j++, k++) { a.s[k] = col(MG_EIG_W, j); a.as[k] = col(MG_EIG_AW, j); }
@@ -945,12 +949,14 @@ int Solver::eig_t(int nev, double tol, int maxit, double *lambda, double *relres
     double G[SMAX * SMAX], H[SMAX * SMAX], C[SMAX * MG_EIG_MAX_BLOCK + 2 * MG_EIG_MAX_BLOCK * MG_EIG_MAX_BLOCK];
     double theta[MG_EIG_MAX_BLOCK], sums[MG_EIG_MAX_BLOCK], rel[MG_EIG_MAX_BLOCK];
     int nh = 0;
+    const int opk = eig_op_t<T>().kind;
+    const Precond pre = opk == EIG_OP_COEFFICIENT ? PRE_VC : (opk == EIG_OP_FACES ? PRE_BC : PRE_CONSTANT);
     // Rayleigh-Ritz on X alone from a fresh A X (X need not be orthonormal): X, AX rotated, theta, R in the W family, rel
     auto ritz_x = [&]() -> int {
         MG_TRY(eig_gram_t<T>(EIG_GRAM_X, 0, 0, G, H));
         if (dense_rayleigh_ritz(m, m, G, H, DENSE_PIVOT_MIN, theta, C) != DENSE_OK) return 1;
         MG_TRY(eig_combine_t<T>(0, 0, C, theta, sums));
-        for (int j = 0; j < m; j++) rel[j] = std::sqrt(sums[j]) / std::fabs(theta[j]);   // ||x_j|| = 1
+        for (int j = 0; j < m; j++) rel[j] = std::sqrt(sums[j]) / std::fabs(theta[j]);   // ||x_j|| = 1 (in the operator's inner product)
         return MG_OK;
     };
     auto all_finite = [&]() {
@@ -990,7 +996,7 @@ int Solver::eig_t(int nev, double tol, int maxit, double *lambda, double *relres
         // result is W column k and the buffer R_k lay in (a finished or locked column's: act[k] >= k) is the free AW column
         for (int k = 0; k < nw; k++) {
             void *z = eig_[MG_EIG_AW][k];
-            MG_TRY(precondition(&z, eig_[MG_EIG_W][act[k]]));
+            MG_TRY(precondition(&z, eig_[MG_EIG_W][act[k]], pre));
             eig_[MG_EIG_AW][k] = eig_[MG_EIG_W][k];
             eig_[MG_EIG_W][k] = z;
             out.cycles++;
@@ -1041,18 +1047,71 @@ int Solver::eig_t(int nev, double tol, int maxit, double *lambda, double *relres
     return MG_OK;
 }
 
+// The operator of mg_eig_*  comes with every call, OR-ed into mg_eig_solve's m and mg_eig_kernel's kernel
+// (MG_EIG_OPERATOR); which kernels and which cycle that means is decided from the handle's state at that call, so the mask, the
+// shift and the coefficient may change between two calls.
+int Solver::eig_take_operator(const char *fn, int *m_or_kernel)
+{
+    const int v = *m_or_kernel, op = v >= 0 ? v >> 8 : 0;
+    if (op != MG_EIG_ON_CONSTANT && op != MG_EIG_ON_FACES && op != MG_EIG_ON_COEFFICIENT) {
+        set_last_error(std::string(fn) + ": the operator OR-ed in must be MG_EIG_OPERATOR of MG_EIG_ON_CONSTANT, MG_EIG_ON_FACES or MG_EIG_ON_COEFFICIENT");
+        return MG_ERR_BAD_ARG;
+    }
+    if (v >= 0) *m_or_kernel = v & 0xff;
+    eig_op_ = op;
+    return MG_OK;
+}
+
+template <typename T>
+EigOp<T> Solver::eig_op_t() const
+{
+    EigOp<T> op{};
+    op.kind = EIG_OP_CONSTANT;
+    if (eig_op_ == MG_EIG_ON_FACES && bc_mask_ != 0) {
+        op.kind = EIG_OP_FACES;
+        op.mask = bc_mask_;
+    } else if (eig_op_ == MG_EIG_ON_COEFFICIENT) {
+        const Level &L0 = lv_[0];
+        op.kind = EIG_OP_COEFFICIENT;
+        op.mask = vc_mask_;
+        op.wx = (T)(-L0.coef[0] / 2.0); op.wy = (T)(-L0.coef[1] / 2.0); op.wz = (T)(-L0.coef[2] / 2.0);   // mg_vc.hip's vc_coef
+        op.sigma = (T)shift_;
+        op.a = vcptr<T>(0);
+    }
+    return op;
+}
+
+int Solver::eig_op_check(const char *fn, bool cycle)
+{
+    const unsigned need = cycle ? FAM_NEED_CYCLE : 0u;
+    if (eig_op_ == MG_EIG_ON_COEFFICIENT) return fam_check<VcFam>(fn, need);
+    if (eig_op_ == MG_EIG_ON_FACES && bc_mask_ != 0) return fam_check<BcFam>(fn, need);
+    return MG_OK;
+}
+
 int Solver::eig_solve(int m, int nev, double tol, int maxit, double *lambda, double *relres, double *hist, int hist_cap,
                       int *n_hist, mg_eig_stats *st)
 {
+    MG_TRY(eig_take_operator("mg_eig_solve", &m));
     const Geom &g = lv_[0].g;
-    const long long interior = (long long)(g.nx - 2) * (g.ny - 2) * (g.dim == 3 ? g.gnz - 2 : 1);
-    if (m < 1 || m > MG_EIG_MAX_BLOCK || nev < 1 || nev > m || m > interior || !(tol > 0.0) || !std::isfinite(tol) || maxit < 0 ||
+    const int mask = eig_op_ == MG_EIG_ON_COEFFICIENT ? vc_mask_ : (eig_op_ == MG_EIG_ON_FACES ? bc_mask_ : 0);
+    // the unknowns of the mask: an axis loses a node per Dirichlet face
+    auto axis = [&](int n, int lo, int hi) { return (long long)n - ((mask & lo) ? 0 : 1) - ((mask & hi) ? 0 : 1); };
+    const long long unknowns = axis(g.nx, MG_FACE_XLO, MG_FACE_XHI) * axis(g.ny, MG_FACE_YLO, MG_FACE_YHI) *
+                               (g.dim == 3 ? axis(g.gnz, MG_FACE_ZLO, MG_FACE_ZHI) : 1);
+    if (m < 1 || m > MG_EIG_MAX_BLOCK || nev < 1 || nev > m || m > unknowns || !(tol > 0.0) || !std::isfinite(tol) || maxit < 0 ||
         !lambda || !relres) {
-        set_last_error("mg_eig_solve: need 1 <= nev <= m <= min(MG_EIG_MAX_BLOCK, interior nodes), a positive finite tol, maxit >= 0 and "
-                       "lambda / relres arrays");
+        set_last_error("mg_eig_solve: need 1 <= nev <= m <= min(MG_EIG_MAX_BLOCK, unknowns of the operator), a positive finite tol, "
+                       "maxit >= 0 and lambda / relres arrays");
         return MG_ERR_BAD_ARG;
     }
     MG_TRY(driver_begin("mg_eig_solve", REFUSE_DIST | REFUSE_STAGE_CB));
+    MG_TRY(eig_op_check("mg_eig_solve", true));
+    if (mask == (d_.dim == 3 ? 63 : 15) && shift_ == 0.0) {
+        set_last_error("mg_eig_solve: every face is Neumann and the shift is 0, so the operator has the eigenvalue 0 and relres divides "
+                       "by it: set a positive shift (mg_set_shift) and subtract it from the eigenvalues");
+        return MG_ERR_BAD_ARG;
+    }
     MG_TRY(eig_resize(m));
     return d_.dtype == MG_F64 ? eig_t<double>(nev, tol, maxit, lambda, relres, hist, hist_cap, n_hist, st)
                               : eig_t<float>(nev, tol, maxit, lambda, relres, hist, hist_cap, n_hist, st);
@@ -1095,12 +1154,14 @@ int Solver::eig_vector_device(int family, int j, void *dense, int dense_dtype, b
 int Solver::eig_kernel(int kernel, int nw, int np, const double *coef, const double *theta, double *G, double *H, double *sums)
 {
     MG_TRY(driver_begin("mg_eig_kernel", REFUSE_DIST));
+    MG_TRY(eig_take_operator("mg_eig_kernel", &kernel));
     const bool gram = kernel == MG_EIG_K_APPLY_GRAM;
     if ((!gram && kernel != MG_EIG_K_COMBINE) || eig_m_ == 0 || nw < 0 || nw > eig_m_ || (np != 0 && np != nw) ||
         (gram ? (!G || !H) : (!coef || !theta || !sums))) {
         set_last_error("mg_eig_kernel: unknown kernel, no block (mg_eig_block), nw outside [0, m], np not 0 or nw, or a null argument");
         return MG_ERR_BAD_ARG;
     }
+    MG_TRY(eig_op_check("mg_eig_kernel", false));
     if (gram) return d_.dtype == MG_F64 ? eig_gram_t<double>(EIG_GRAM_FULL, nw, np, G, H) : eig_gram_t<float>(EIG_GRAM_FULL, nw, np, G, H);
     return d_.dtype == MG_F64 ? eig_combine_t<double>(nw, np, coef, theta, sums) : eig_combine_t<float>(nw, np, coef, theta, sums);
 }

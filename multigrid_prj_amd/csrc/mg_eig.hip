@@ -28,8 +28,18 @@
 //   S C    each element starts at 0.0 in double and adds (double) S_i * C_ij for i in the column order of S, every product
 //            and sum rounded separately, rounded once to T
 //   R      r = ax' - (T) theta_j * x' in T from the rounded x', ax'; sums of r^2 in double
-#include "mg_kernels.h"
-#include "mg_device.h"
+//
+// The operator families (enum mg_eig_operator; OPK below). With EIG_OP_FACES the stencil is the constant
+// one and the faces of a mask are Neumann, with EIG_OP_COEFFICIENT it is mg_vc.hip's with the same kind of mask. Node classes
+// are mg_bc.hip's: a node on a face outside the mask is a Dirichlet node, every other node is an unknown whose missing
+// neighbours are mirror images. y and z are uniform over an item, so their mirrors are a select between two ADDRESSES before
+// the load; the x mirrors are selects between values the lane holds. L is self-adjoint in the inner product of the weights w
+// (1/2 per face of the mask a node lies on, bc_weight), so every product of both Gram halves and every r^2 of the combine
+// carries w -- a power of two, the scaling is exact. tests/eigop_ref.py restates:
+//   FACES        the sum of A w above with the mirrored value in the slot of the missing neighbour
+//   COEFFICIENT  s = 0, d = (T)sigma; per slot z-, y-, x-, x+, y+, z+: g = w_a * (a_i + a_q), s = s + g * b_q, d = d + g with
+//                w_a = (T)(-c_a / 2); L b = d * b_i - s (k_vcn_cg_direction's q); a is mirrored like b and never zeroed
+#include "mg_opfamily.h"
 
 namespace mg {
 
@@ -129,9 +139,18 @@ __device__ __forceinline__ void flush(int n, double *__restrict__ partials, doub
 // for; the rows are read by both halves at about the same time and the second read is served by the caches.
 constexpr int GRAM_ITEMS = EIG_THREADS / 2;
 
-template <typename T, int DIM, bool APPLY>
-__global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(Geom g, Coef<T> c, EigGramArgs<T> a, double *__restrict__ partials)
+// the mg_face bits of a row, a (global) plane and a column: bc_faces (mg_opfamily.h) axis by axis
+__device__ __forceinline__ int y_faces(const Geom &g, int y) { return (y == 0 ? FYLO : 0) | (y == g.ny - 1 ? FYHI : 0); }
+__device__ __forceinline__ int z_faces(const Geom &g, int gz) { return g.dim == 3 ? (gz == 0 ? FZLO : 0) | (gz == g.gnz - 1 ? FZHI : 0) : 0; }
+__device__ __forceinline__ int x_faces(const Geom &g, int x) { return (x == 0 ? FXLO : 0) | (x == g.nx - 1 ? FXHI : 0); }
+
+// OPK: the operator. EIG_OP_CONSTANT does not look at op and is the code it was before the families came. The others take
+// the Dirichlet flags and the weights from op.mask; their apply loads the y / z neighbours from mirrored addresses, and with
+// EIG_OP_COEFFICIENT the seven vectors of a once per item: the six g and d of the contract are shared by the tile's columns.
+template <typename T, int DIM, bool APPLY, int OPK = EIG_OP_CONSTANT>
+__global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(Geom g, Coef<T> c, EigGramArgs<T> a, double *__restrict__ partials, EigOp<T> op)
 {
+    constexpr bool FAM = OPK != EIG_OP_CONSTANT;
     constexpr int V = Vec16<T>::n;
     constexpr int NA = EIG_GRAM_ROWS, NB = EIG_GRAM_COLS;
     __shared__ double sh[2 * NA * NB][EIG_WAVES];
@@ -148,10 +167,22 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(Geom g, Coef<T> c, Eig
         const int valid = g.nx - t.x0;
         if (valid <= 0) continue;
         const long long i = (long long)t.z * g.plane + (long long)t.y * g.pitch + t.x0;
-        const bool rb = row_is_boundary(g, t.z, t.y);
-        bool dir[V];   // the element is a Dirichlet node
+        const int frow = FAM ? y_faces(g, t.y) | z_faces(g, g.gz0 + t.z) : 0;   // the y and z faces the row lies on
+        const bool rb = FAM ? (frow & ~op.mask) != 0 : row_is_boundary(g, t.z, t.y);
+        bool dir[V];   // the element is a Dirichlet node (or a padding column)
+        [[maybe_unused]] T wgt[V];
+        [[maybe_unused]] bool any_dir = false;
 #pragma unroll
-        for (int e = 0; e < V; e++) dir[e] = rb || t.x0 + e == 0 || t.x0 + e >= g.nx - 1;
+        for (int e = 0; e < V; e++) {
+            if constexpr (FAM) {
+                const int fx = x_faces(g, t.x0 + e);
+                dir[e] = rb || (fx & ~op.mask) != 0 || t.x0 + e >= g.nx;
+                wgt[e] = (T)bc_weight(__popc((unsigned)((frow | fx) & op.mask)));
+                any_dir |= dir[e] && e < valid;
+            } else {
+                dir[e] = rb || t.x0 + e == 0 || t.x0 + e >= g.nx - 1;
+            }
+        }
         // Every load of the item is issued before anything waits for one: no branch stands between them. The launcher points
         // the unused rows and columns at used ones, and a level-shaped array has a ghost plane either side, so the stencil's
         // neighbours of a Dirichlet node are addressable too; what must count as zero is zeroed by selects afterwards.
@@ -169,7 +200,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(Geom g, Coef<T> c, Eig
                     for (int e = 0; e < V; e++) cv[j][e] = dir[e] ? (T)0 : cv[j][e];
             }
             // b := 0 on its Dirichlet nodes: only vectors that hold one are written (every reader takes them masked)
-            if (APPLY && (rb || t.x0 == 0 || t.x0 + V >= g.nx - 1)) {
+            if (APPLY && (FAM ? any_dir : (rb || t.x0 == 0 || t.x0 + V >= g.nx - 1))) {
 #pragma unroll
                 for (int j = 0; j < NB; j++)
                     if (j < a.nb) vstore_masked(a.col[j] + i, cv[j], valid);
@@ -177,6 +208,104 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(Geom g, Coef<T> c, Eig
         } else if (!APPLY) {
 #pragma unroll
             for (int j = 0; j < NB; j++) vload(a.acol[j] + i, cv[j]);
+        } else if constexpr (FAM) {
+            T pc[NB][V], ps[NB][V], pn[NB][V], pd[NB][V], pu[NB][V], pl[NB], pr[NB];
+            [[maybe_unused]] T ac[V], as[V], an[V], ad[V], au[V], al, ar;
+            const int gz = g.gz0 + t.z;
+            // the rows of the y / z neighbours, mirrored on the faces the row lies on (in the mask or not: a row on a Dirichlet
+            // face is dropped below, and the mirrored row always lies inside the level)
+            const int ys = (frow & FYLO) ? t.y + 1 : t.y - 1, yn = (frow & FYHI) ? t.y - 1 : t.y + 1;
+            const int zd = (frow & FZLO) ? gz + 1 : gz - 1, zu = (frow & FZHI) ? gz - 1 : gz + 1;
+            const long long is = i + (long long)(ys - t.y) * g.pitch, in = i + (long long)(yn - t.y) * g.pitch;
+            const long long id = i + (long long)(zd - gz) * g.plane, iu = i + (long long)(zu - gz) * g.plane;
+#pragma unroll
+            for (int j = 0; j < NB; j++) {
+                const T *const b = a.col[j];
+                vload(b + i, pc[j]);
+                vload(b + is, ps[j]);
+                vload(b + in, pn[j]);
+                if (DIM == 3) { vload(b + id, pd[j]); vload(b + iu, pu[j]); }
+                pl[j] = b[i - 1];
+                pr[j] = b[i + V];
+            }
+            if constexpr (OPK == EIG_OP_COEFFICIENT) {
+                vload(op.a + i, ac);
+                vload(op.a + is, as);
+                vload(op.a + in, an);
+                if (DIM == 3) { vload(op.a + id, ad); vload(op.a + iu, au); }
+                al = op.a[i - 1];
+                ar = op.a[i + V];
+            }
+            // a neighbour row counts as zero when it lies on a Dirichlet face
+            const bool south0 = (y_faces(g, ys) & ~op.mask) != 0, north0 = (y_faces(g, yn) & ~op.mask) != 0;
+            const bool down0 = (z_faces(g, zd) & ~op.mask) != 0, up0 = (z_faces(g, zu) & ~op.mask) != 0;
+            // the elements beyond the vector's ends count when their column is an unknown's
+            const bool l_in = t.x0 >= 1 && (t.x0 > 1 || (op.mask & FXLO)), r_in = t.x0 + V < g.nx - 1 || (t.x0 + V == g.nx - 1 && (op.mask & FXHI));
+            // the six g and d of mg_vc.hip's contract per element, shared by the columns
+            [[maybe_unused]] T gq[6][V], dd[V];
+            if constexpr (OPK == EIG_OP_COEFFICIENT) {
+#pragma unroll
+                for (int e = 0; e < V; e++) {
+                    const int xx = t.x0 + e;
+                    const T aw = e == 0 ? al : ac[e - 1 < 0 ? 0 : e - 1];
+                    const T axm = xx == 0 ? ac[1] : aw;
+                    const T axp = xx == g.nx - 1 ? aw : (e == V - 1 ? ar : ac[e + 1 > V - 1 ? V - 1 : e + 1]);
+                    T d = op.sigma;
+                    if (DIM == 3) { gq[0][e] = op.wz * (ac[e] + ad[e]); d = d + gq[0][e]; }
+                    gq[1][e] = op.wy * (ac[e] + as[e]); d = d + gq[1][e];
+                    gq[2][e] = op.wx * (ac[e] + axm); d = d + gq[2][e];
+                    gq[3][e] = op.wx * (ac[e] + axp); d = d + gq[3][e];
+                    gq[4][e] = op.wy * (ac[e] + an[e]); d = d + gq[4][e];
+                    if (DIM == 3) { gq[5][e] = op.wz * (ac[e] + au[e]); d = d + gq[5][e]; }
+                    dd[e] = d;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NB; j++) {
+#pragma unroll
+                for (int e = 0; e < V; e++) {
+                    const int xx = t.x0 + e;
+                    const bool xd = (x_faces(g, xx) & ~op.mask) != 0 || xx >= g.nx;   // a Dirichlet (or padding) column
+                    pc[j][e] = xd ? (T)0 : pc[j][e];
+                    ps[j][e] = south0 ? (T)0 : ps[j][e];
+                    pn[j][e] = north0 ? (T)0 : pn[j][e];
+                    if (DIM == 3) {
+                        pd[j][e] = down0 ? (T)0 : pd[j][e];
+                        pu[j][e] = up0 ? (T)0 : pu[j][e];
+                    }
+                }
+                const T wl = l_in ? pl[j] : (T)0;
+                const T er = r_in ? pr[j] : (T)0;
+#pragma unroll
+                for (int e = 0; e < V; e++) {
+                    const int xx = t.x0 + e;
+                    // x = 0 takes its right neighbour for the left one; x = nx - 1 its left one, which is pl when the node is
+                    // alone in its vector and pc[e - 1] when it lies inside one
+                    const T lw = e == 0 ? wl : pc[j][e - 1 < 0 ? 0 : e - 1];
+                    const T w = xx == 0 ? pc[j][1] : lw;
+                    const T ea = xx == g.nx - 1 ? lw : (e == V - 1 ? er : pc[j][e + 1 > V - 1 ? V - 1 : e + 1]);
+                    T s = 0;
+                    if constexpr (OPK == EIG_OP_COEFFICIENT) {
+                        if (DIM == 3) s = s + gq[0][e] * pd[j][e];
+                        s = s + gq[1][e] * ps[j][e];
+                        s = s + gq[2][e] * w;
+                        s = s + gq[3][e] * ea;
+                        s = s + gq[4][e] * pn[j][e];
+                        if (DIM == 3) s = s + gq[5][e] * pu[j][e];
+                        s = dd[e] * pc[j][e] - s;
+                    } else {
+                        if (DIM == 3) s += c.cz * pd[j][e];
+                        s += c.cy * ps[j][e];
+                        s += c.cx * w;
+                        s += c.cd * pc[j][e];
+                        s += c.cx * ea;
+                        s += c.cy * pn[j][e];
+                        if (DIM == 3) s += c.cz * pu[j][e];
+                    }
+                    cv[j][e] = dir[e] ? (T)0 : s;
+                }
+                if (j < a.nb) vstore_masked(a.acol[j] + i, cv[j], valid);
+            }
         } else {
             T pc[NB][V], ps[NB][V], pn[NB][V], pd[NB][V], pu[NB][V], pl[NB], pr[NB];
             const int gz = g.gz0 + t.z;
@@ -225,6 +354,12 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(Geom g, Coef<T> c, Eig
                 if (j < a.nb) vstore_masked(a.acol[j] + i, cv[j], valid);
             }
         }
+        if constexpr (FAM) {   // after the store of A b: both halves weigh their products
+#pragma unroll
+            for (int j = 0; j < NB; j++)
+#pragma unroll
+                for (int e = 0; e < V; e++) cv[j][e] = cv[j][e] * wgt[e];
+        }
 #pragma unroll
         for (int r = 0; r < NA; r++) {
             const bool rin = (a.row_interior >> r) & 1u;
@@ -258,7 +393,8 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_gram(Geom g, Coef<T> c, Eig
 
 // ---------------------------------------------------------------- combine + residual
 // MB: columns held as accumulators (the block size rounded up to 4 or 8)
-template <typename T, int MB>
+// WGT: the sums of r^2 carry the weights of a.mask; the arrays are written as without it
+template <typename T, int MB, bool WGT = false>
 __global__ __launch_bounds__(EIG_THREADS) void k_eig_combine(Geom g, EigCombineArgs<T> a, const double *__restrict__ coef,
                                                              const double *__restrict__ theta, double *__restrict__ partials)
 {
@@ -276,6 +412,12 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_combine(Geom g, EigCombineA
         const int valid = g.nx - t.x0;
         if (valid <= 0) continue;
         const long long i = (long long)t.z * g.plane + (long long)t.y * g.pitch + t.x0;
+        [[maybe_unused]] double wgt[V];
+        if constexpr (WGT) {
+            const int frow = y_faces(g, t.y) | z_faces(g, g.gz0 + t.z);
+#pragma unroll
+            for (int e = 0; e < V; e++) wgt[e] = bc_weight(__popc((unsigned)((frow | x_faces(g, t.x0 + e)) & a.mask)));
+        }
         double x[MB][V], ax[MB][V], p[MB][V], ap[MB][V];
 #pragma unroll
         for (int j = 0; j < MB; j++)
@@ -319,7 +461,8 @@ __global__ __launch_bounds__(EIG_THREADS) void k_eig_combine(Geom g, EigCombineA
                 xv[e] = (T)x[j][e];
                 axv[e] = (T)ax[j][e];
                 rv[e] = axv[e] - th * xv[e];
-                if (e < valid) rr[j] += (double)rv[e] * (double)rv[e];
+                if constexpr (WGT) { if (e < valid) rr[j] += wgt[e] * ((double)rv[e] * (double)rv[e]); }
+                else if (e < valid) rr[j] += (double)rv[e] * (double)rv[e];
             }
             vstore_masked(a.x[j] + i, xv, valid);
             vstore_masked(a.ax[j] + i, axv, valid);
@@ -381,19 +524,31 @@ int eig_grid(const Geom &g, int per_item)
     return (int)std::min<long long>(EIG_MAX_BLOCKS, std::max<long long>(1, (items + EIG_THREADS - 1) / EIG_THREADS));
 }
 
+template <typename T, int OPK>
+void eig_gram_launch(hipStream_t s, int nb, const Geom &g, const Coef<T> &c, const EigOp<T> &op, const EigGramArgs<T> &a, bool apply,
+                     double *partials)
+{
+    if (apply) {
+        if (g.dim == 3) hipLaunchKernelGGL((k_eig_gram<T, 3, true, OPK>), dim3(nb), dim3(EIG_THREADS), 0, s, g, c, a, partials, op);
+        else hipLaunchKernelGGL((k_eig_gram<T, 2, true, OPK>), dim3(nb), dim3(EIG_THREADS), 0, s, g, c, a, partials, op);
+    } else {
+        // DIM is not looked at, and the operator only decides the Dirichlet flags and the weights: FACES' instantiation serves COEFFICIENT
+        constexpr int K = OPK == EIG_OP_COEFFICIENT ? EIG_OP_FACES : OPK;
+        hipLaunchKernelGGL((k_eig_gram<T, 2, false, K>), dim3(nb), dim3(EIG_THREADS), 0, s, g, c, a, partials, op);
+    }
+}
+
 }  // namespace
 
 template <typename T>
-int launch_eig_gram(hipStream_t s, const Geom &g, const Coef<T> &c, const EigGramArgs<T> &a, bool apply, double *partials)
+int launch_eig_gram(hipStream_t s, const Geom &g, const Coef<T> &c, const EigOp<T> &op, const EigGramArgs<T> &a, bool apply,
+                    double *partials)
 {
     const long long items = (long long)(g.pitch / Vec16<T>::n) * g.ny * g.nz;
     const int nb = (int)std::min<long long>(EIG_MAX_BLOCKS, std::max<long long>(1, (items + GRAM_ITEMS - 1) / GRAM_ITEMS));
-    if (apply) {
-        if (g.dim == 3) hipLaunchKernelGGL((k_eig_gram<T, 3, true>), dim3(nb), dim3(EIG_THREADS), 0, s, g, c, a, partials);
-        else hipLaunchKernelGGL((k_eig_gram<T, 2, true>), dim3(nb), dim3(EIG_THREADS), 0, s, g, c, a, partials);
-    } else {
-        hipLaunchKernelGGL((k_eig_gram<T, 2, false>), dim3(nb), dim3(EIG_THREADS), 0, s, g, c, a, partials);   // DIM is not looked at
-    }
+    if (op.kind == EIG_OP_CONSTANT) eig_gram_launch<T, EIG_OP_CONSTANT>(s, nb, g, c, op, a, apply, partials);
+    else if (op.kind == EIG_OP_FACES) eig_gram_launch<T, EIG_OP_FACES>(s, nb, g, c, op, a, apply, partials);
+    else eig_gram_launch<T, EIG_OP_COEFFICIENT>(s, nb, g, c, op, a, apply, partials);
     return nb;
 }
 
@@ -402,8 +557,10 @@ int launch_eig_combine(hipStream_t s, const Geom &g, const EigCombineArgs<T> &a,
                        double *partials)
 {
     const int nb = eig_grid(g, Vec16<T>::n);
-    if (a.m <= 4) hipLaunchKernelGGL((k_eig_combine<T, 4>), dim3(nb), dim3(EIG_THREADS), 0, s, g, a, coef, theta, partials);
-    else hipLaunchKernelGGL((k_eig_combine<T, 8>), dim3(nb), dim3(EIG_THREADS), 0, s, g, a, coef, theta, partials);
+#define MG_EIG_COMBINE(MB, WGT) hipLaunchKernelGGL((k_eig_combine<T, MB, WGT>), dim3(nb), dim3(EIG_THREADS), 0, s, g, a, coef, theta, partials)
+    if (a.weighted) { if (a.m <= 4) MG_EIG_COMBINE(4, true); else MG_EIG_COMBINE(8, true); }
+    else { if (a.m <= 4) MG_EIG_COMBINE(4, false); else MG_EIG_COMBINE(8, false); }
+#undef MG_EIG_COMBINE
     return nb;
 }
 
@@ -419,7 +576,8 @@ void launch_eig_fill(hipStream_t s, const Geom &g, T *x, int column)
 }
 
 #define MG_EIG_INST(T)                                                                                                        \
-    template int launch_eig_gram<T>(hipStream_t, const Geom &, const Coef<T> &, const EigGramArgs<T> &, bool, double *);      \
+    template int launch_eig_gram<T>(hipStream_t, const Geom &, const Coef<T> &, const EigOp<T> &, const EigGramArgs<T> &, bool, \
+                                    double *);                                                                                \
     template int launch_eig_combine<T>(hipStream_t, const Geom &, const EigCombineArgs<T> &, const double *, const double *,  \
                                        double *);                                                                             \
     template void launch_eig_fill<T>(hipStream_t, const Geom &, T *, int);

@@ -238,17 +238,32 @@ struct EigGramArgs {
     unsigned row_interior;             // bit r: row r is read as 0 on Dirichlet nodes whatever it holds there (the W family)
     int col_interior;                  // the same for the columns of a launch without the apply
 };
+// The operator of the block kernels (enum mg_eig_operator, MG_EIG_OPERATOR): EIG_OP_CONSTANT is the handle's constant stencil with every face
+// Dirichlet and looks at nothing else here. EIG_OP_FACES: the constant stencil with the faces of `mask` Neumann (mg_bc.hip's
+// node classes and mirrors). EIG_OP_COEFFICIENT: mg_vc.hip's operator from the level-0 coefficient array a with w_a =
+// (T)(-c_a / 2), sigma = (T)shift and the faces of `mask`. With the last two every product of a Gram sum and every r^2 of
+// the combine carries the node's weight (1/2 per face of the mask it lies on).
+enum { EIG_OP_CONSTANT = 0, EIG_OP_FACES = 1, EIG_OP_COEFFICIENT = 2 };
+template <typename T>
+struct EigOp {
+    int kind, mask;
+    T wx, wy, wz, sigma;
+    const T *a;
+};
 // One tile: partials[(r * EIG_GRAM_COLS + j) * nblocks + block] of row[r] . col[j], and EIG_GRAM_ROWS * EIG_GRAM_COLS
 // entries further on the same of row[r] . acol[j]. apply: acol[j] = A col[j] is made (and stored) instead of read.
 // Every array is level-shaped with a ghost plane either side (the apply reads the neighbours of boundary nodes too and
 // zeroes them afterwards). Returns nblocks.
 template <typename T>
-int launch_eig_gram(hipStream_t s, const Geom &g, const Coef<T> &c, const EigGramArgs<T> &a, bool apply, double *partials);
+int launch_eig_gram(hipStream_t s, const Geom &g, const Coef<T> &c, const EigOp<T> &op, const EigGramArgs<T> &a, bool apply,
+                    double *partials);
 template <typename T>
 struct EigCombineArgs {
     const T *s[3 * EIG_MAX_COLS], *as[3 * EIG_MAX_COLS];   // S = [X, W, P] and AS = [AX, AW, AP] in column order
     T *x[EIG_MAX_COLS], *ax[EIG_MAX_COLS], *r[EIG_MAX_COLS], *p[EIG_MAX_COLS], *ap[EIG_MAX_COLS];   // outputs (they alias inputs)
     int m, nw, np;
+    int mask;   // weighted: the sums of r^2 carry the weights of this face mask (the arrays are the same bits either way)
+    bool weighted;
 };
 // x_j = S Cx, ax_j = AS Cx (j < m), p_j = [W, P] Cp, ap_j = [AW, AP] Cp (j < nw), r_j = ax_j - theta_j x_j; coef (device) =
 // Cx (s x m) followed by Cp ((nw + np) x nw), row-major; partials[j * nblocks + block] of r_j^2. Returns nblocks.

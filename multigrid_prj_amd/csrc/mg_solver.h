@@ -302,8 +302,10 @@ private:
                    int *n_hist, mg_krylov_stats *st, int vc_mask = 0, bool singular = false);
     // *z = M r: one mg_solve outer iteration from zero with the buffers *z and r in level 0's U / RHS slots. The cycle may leave
     // its result in the buffer that was TMP: *z is whatever U points at afterwards, and TMP keeps the other buffer.
-    // vc: the cycle is mg_vc_cycle's (mg_vc_pcg_solve) and no Gauss-Seidel sweeps come before it
-    int precondition(void **z, void *r, bool vc = false);
+    // PRE_VC / PRE_BC: the cycle is mg_vc_cycle's (mg_vc_pcg_solve, mg_eig_solve on the coefficient) / mg_bc_cycle's
+    // (mg_eig_solve on the faces) and no Gauss-Seidel sweeps come before it
+    enum Precond { PRE_CONSTANT = 0, PRE_VC = 1, PRE_BC = 2 };
+    int precondition(void **z, void *r, Precond fam = PRE_CONSTANT);
     template <typename T> int pcg_kernel_t(int kernel, double scalar, const int *arrs, double *dots);
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
     int mixed_check(const char *fn, unsigned refuse = REFUSE_DIST);      // MG_F32, then driver_begin(fn, refuse)
@@ -484,6 +486,15 @@ private:
     void *eig_[EIG_FAMILIES][MG_EIG_MAX_BLOCK] = {};
     int eig_m_ = 0;
     double *d_eig_part_ = nullptr, *d_eig_out_ = nullptr, *d_eig_coef_ = nullptr, *h_eig_ = nullptr;
+    int eig_op_ = MG_EIG_ON_CONSTANT;   // the operator of the eig_solve / eig_kernel call in progress (enum mg_eig_operator): taken
+                                        // from the call's m / kernel argument (MG_EIG_OPERATOR) at its entry, nothing keeps it between calls
+    // m_or_kernel = value | MG_EIG_OPERATOR(op) -> value, eig_op_ = op; an unknown op is refused
+    int eig_take_operator(const char *fn, int *m_or_kernel);
+    // the operator as the block kernels take it, from the handle's state NOW: MG_EIG_ON_FACES with mask 0 is the constant one
+    template <typename T> EigOp<T> eig_op_t() const;
+    // what eig_solve and eig_kernel refuse because of the operator: the family's own precondition (cycle: and what its cycle
+    // asks of the descriptor)
+    int eig_op_check(const char *fn, bool cycle);
     int eig_check(const char *fn, int family, int j, bool may_grow);   // driver_begin + the family / column rules
     int eig_resize(int m);
     // G, H (s x s, s = m or m + nw + np) of the block. EIG_GRAM_X: S = [X], AX = A X made on the way (X := 0 on Dirichlet
