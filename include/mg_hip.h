@@ -322,6 +322,44 @@ enum mg_mixed_kernel_kind { MG_MIXED_K_RESIDUAL = 0, MG_MIXED_K_CORRECT_RESIDUAL
 int mg_mixed_kernel(mg_handle h, int kernel, double scale_in, double scale_out,
                     int arr_e32, int arr_r32, double *sumsq_r);
 
+/* THE VARIABLE-COEFFICIENT OPERATOR in mg_mixed_solve and mg_mixed_kernel. No new entry point: flags OR-ed into arguments the
+ * two calls already have.
+ *   mg_mixed_solve(h, tol, maxit, count | MG_MIXED_OPERATOR(MG_MIXED_ON_COEFFICIENT) [| MG_MIXED_INNER_PCG], ...)
+ *   mg_mixed_kernel(h, kernel | MG_MIXED_OPERATOR(MG_MIXED_ON_COEFFICIENT), scale_in, scale_out, arr_e32, arr_r32, &sumsq)
+ * count (bits 0 .. 15, 1 .. 65535) is the number of cycles -- with MG_MIXED_INNER_PCG of CG iterations -- per correction. With
+ * no bit above 15 set every value below 65536 does what it always did, bit for bit.
+ * The operator is mg_vc_*'s as the handle holds it AT THE CALL: L = sigma I - div(a grad .) with the coefficient of
+ * mg_vc_set_coefficient[_device] on this MG_F32 handle, sigma = mg_get_shift and the Neumann faces of mg_vc_set_faces; the
+ * handle keeps nothing new. u64 / b64 are the arrays of mg_mixed_set_*. The fp64 operator uses a = (double) of the handle's
+ * fp32 level-0 coefficient: every fp32 value is exact in fp64, so this is a well-defined system -- the user's field rounded
+ * to fp32, a relative perturbation of at most 6e-8, none for piecewise-constant fields with representable values. No fp64
+ * copy of a is stored and the residual pass reads 4 bytes per node for it, not 8.
+ * Arithmetic (fp64, no contraction, every operation rounded separately), c_a from mg_level_coefficients(h, 0), w_a = -c_a / 2:
+ *   u' = u + (double)e / s_in at the mask's unknowns; u' = u on its Dirichlet nodes (nodes on at least one face that is not
+ *        in the mask; e is not looked at there)
+ *   s = 0, d = sigma; for the neighbours q (or their mirror images through a Neumann face) z-, y-, x-, x+, y+, z+ (no z in 2-D):
+ *        g = w_a * (a_i + a_q);  s = s + g * u'_q;  d = d + g
+ *   r = b - (d * u'_i - s) at unknowns, r = 0 on Dirichlet nodes; r32 = (float)(s_out * r), round to nearest even; the sum of
+ *        r^2 (unscaled) in double, per-workgroup partials added in a fixed order: two runs give the same bits
+ * (a power-of-two s_in with a normal reciprocal multiplies by the reciprocal, any other divides). mg_vc_set_form chooses the
+ * marching tile (mask 0 on 3-D levels with at least 16 fp64 vectors per row) or the one-thread-per-node form, as for every vc
+ * kernel; a non-zero mask always takes the latter (a mirrored tile measured slower). Same bits either way.
+ * The solve is mg_mixed_solve's loop with: u64 = b64 on the mask's Dirichlet nodes; the inner solve from U32(0) = 0 is count
+ * mg_vc_cycle (desc.outer_pre_gs ignored, as in mg_vc_solve) or, with MG_MIXED_INNER_PCG, count iterations of mg_vc_pcg_solve's
+ * weighted flexible CG with tolerance 0 (it allocates the Krylov arrays on first use; a breakdown ends the inner solve early
+ * and the iterate it holds is the correction; it synchronises once per iteration). stats.cycles counts the cycles run, a CG
+ * iteration as one. In the singular case (every face Neumann, shift 0) b64 is projected first with mg_vc_project's weights
+ * and STAYS projected, hist is relative to the projected b, u64 is projected after the last correction and stats.relres is
+ * evaluated once more on the projected u64 (it is the residual of the u64 returned; the last hist entry is the one before
+ * the projection and agrees with it to rounding).
+ * MG_ERR_BAD_ARG with u64 untouched and nothing allocated: any other bit above 15, operator value 1 (kept for a faces-only
+ * operator) or 3, MG_MIXED_INNER_PCG without MG_MIXED_ON_COEFFICIENT, count == 0, no coefficient set, whatever mg_vc_cycle /
+ * mg_vc_pcg_solve refuse (sawtooth, a smoother other than Jacobi or red-black, a stage callback, distributed handles) and
+ * everything mg_mixed_solve / mg_mixed_kernel refuse without the flags. */
+enum mg_mixed_operator { MG_MIXED_ON_CONSTANT = 0 /* default */, MG_MIXED_ON_COEFFICIENT = 2 };  /* 1: kept for a faces-only operator, refused */
+#define MG_MIXED_OPERATOR(op) ((op) << 16)   /* OR-ed into mg_mixed_solve's inner_cycles or mg_mixed_kernel's kernel */
+#define MG_MIXED_INNER_PCG    (1 << 20)      /* mg_mixed_solve only, only with MG_MIXED_ON_COEFFICIENT */
+
 /* Fourth-order accurate solves by defect correction (extension, no reference counterpart). The residual is evaluated with
  * the fourth-order operator sigma I + A4 of level 0, the correction equation (sigma I + A2) e = r is solved approximately by
  * the handle's own second-order cycles, u += e (Trottenberg et al., Multigrid, section 5.4.1). The fixed point solves the
@@ -491,7 +529,9 @@ enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 
  * included); bad arrays, levels or masks; NULL handle. No other entry point changes behaviour, and the family allocates
  * nothing. Not combined with mg_vc_*, mg_o4_*, mg_heat_step, mg_fmg, mg_eig_solve, mg_mixed_solve or mg_pcg_solve, which
  * keep treating every face as Dirichlet (mg_fas_* reads this mask when its kind carries MG_FAS_ON_FACES, mg_eig_solve after
- * MG_EIG_OPERATOR(MG_EIG_ON_FACES) OR-ed into its m, see there); mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
+ * MG_EIG_OPERATOR(MG_EIG_ON_FACES) OR-ed into its m, see there). mg_mixed_solve has no faces-only operator (value 1 of
+ * mg_mixed_operator is refused): its Neumann faces are mg_vc_set_faces' with MG_MIXED_ON_COEFFICIENT, and a == 1 there is
+ * this family's operator; mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
 int mg_bc_set_faces(mg_handle h, int mask);
 int mg_bc_get_faces(mg_handle h, int *mask);
 int mg_bc_set_form(mg_handle h, int form);
@@ -538,8 +578,9 @@ int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, 
  *   every preconditioner application and x at the end.
  * mg_vc_direction with a mask: arr_pn and arr_q are 0 on the mask's Dirichlet nodes, neighbours are mirrored, *pq = sum w pn q.
  * mg_vc_restrict, mg_vc_project: mg_bc_restrict and mg_bc_project with this mask (no coefficient is needed).
- * MG_ERR_BAD_ARG as for mg_vc_*. Not combined with mg_fas_*, mg_o4_*, mg_fmg or mg_mixed_solve (mg_fas_* with
- * MG_FAS_ON_COEFFICIENT and mg_eig_solve with MG_EIG_ON_COEFFICIENT read this mask, see there). */
+ * MG_ERR_BAD_ARG as for mg_vc_*. Not combined with mg_fas_*, mg_o4_* or mg_fmg (mg_fas_* with MG_FAS_ON_COEFFICIENT,
+ * mg_eig_solve with MG_EIG_ON_COEFFICIENT and, on an MG_F32 handle, mg_mixed_solve / mg_mixed_kernel with
+ * MG_MIXED_OPERATOR(MG_MIXED_ON_COEFFICIENT) read the coefficient, the shift and this mask at the call, see there). */
 int mg_vc_set_faces(mg_handle h, int mask);
 int mg_vc_get_faces(mg_handle h, int *mask);
 int mg_vc_restrict(mg_handle h, int fine_level, int kind, int arr_src, int arr_dst);

@@ -28,6 +28,8 @@ PCG_K_UPDATE, PCG_K_DOTS, PCG_K_DIRECTION = 0, 1, 2
 PCG_CONVERGED, PCG_MAXIT, PCG_BREAKDOWN = 0, 1, 2
 MIXED_K_RESIDUAL, MIXED_K_CORRECT_RESIDUAL = 0, 1
 MIXED_CONVERGED, MIXED_MAXIT, MIXED_NOT_FINITE = 0, 1, 2
+MIXED_ON_CONSTANT, MIXED_ON_COEFFICIENT = 0, 2   # enum mg_mixed_operator (1 is kept for a faces-only operator and refused)
+MIXED_INNER_PCG = 1 << 20                        # OR-ed into mg_mixed_solve's inner_cycles, only with MIXED_ON_COEFFICIENT
 O4_CONVERGED, O4_MAXIT, O4_NOT_FINITE = 0, 1, 2
 EIG_MAX_BLOCK = 8
 EIG_X, EIG_AX, EIG_W, EIG_AW, EIG_P, EIG_AP = 0, 1, 2, 3, 4, 5
@@ -39,6 +41,10 @@ EIG_ON_CONSTANT, EIG_ON_FACES, EIG_ON_COEFFICIENT = 0, 1, 2   # enum mg_eig_oper
 def eig_operator(op):
     """include/mg_hip.h::MG_EIG_OPERATOR: what is OR-ed into mg_eig_solve's m or mg_eig_kernel's kernel"""
     return op << 8
+
+def mixed_operator(op):
+    """include/mg_hip.h::MG_MIXED_OPERATOR: what is OR-ed into mg_mixed_solve's inner_cycles or mg_mixed_kernel's kernel"""
+    return op << 16
 
 # enum mg_raw_space: the arrays mg_debug_raw_* (a test and debugging window, not a data path) can look at
 RAW_LEVEL, RAW_VC, RAW_KRYLOV, RAW_MIXED, RAW_EIG, RAW_HEAT, RAW_O4 = 0, 1, 2, 3, 4, 5, 6
@@ -591,18 +597,22 @@ class Solver:
         ptr, dt = device_view(out, self.level_shape(0), writable=True)
         _check(self.lib.mg_mixed_get_solution_device(self.h, ptr, dt, stream or None))
 
-    def mixed_solve(self, tol=1e-11, maxit=100, inner_cycles=4):
+    def mixed_solve(self, tol=1e-11, maxit=100, inner_cycles=4, op=MIXED_ON_CONSTANT, inner_pcg=False):
         """mg_mixed_solve: fp64 defect correction over the fp32 cycles of this (MG_F32) handle, `maxit` corrections of
-        `inner_cycles` cycles at most -> (hist, MgMixedStats); hist[k] = the true fp64 ||b - A u_k|| / ||b||"""
+        `inner_cycles` cycles at most -> (hist, MgMixedStats); hist[k] = the true fp64 ||b - A u_k|| / ||b||.
+        op=MIXED_ON_COEFFICIENT: on mg_vc_*'s operator as the handle holds it (coefficient, shift, vc_set_faces mask);
+        inner_pcg: `inner_cycles` iterations of vc_pcg_solve's CG per correction instead of cycles. Both are OR-ed into
+        inner_cycles as MG_MIXED_OPERATOR / MG_MIXED_INNER_PCG do; the defaults pass inner_cycles as it is"""
         cap = max(maxit, 0) + 1
         hist = (C.c_double * cap)(); nh = C.c_int(0); st = MgMixedStats()
-        _check(self.lib.mg_mixed_solve(self.h, tol, maxit, inner_cycles, hist, cap, C.byref(nh), C.byref(st)))
+        arg = inner_cycles | mixed_operator(op) | (MIXED_INNER_PCG if inner_pcg else 0)
+        _check(self.lib.mg_mixed_solve(self.h, tol, maxit, arg, hist, cap, C.byref(nh), C.byref(st)))
         return np.array(hist[:min(nh.value, cap)]), st
 
-    def mixed_kernel(self, kernel, scale_in, scale_out, arr_e32, arr_r32) -> float:
-        """mg_mixed_kernel: one of the two fp64-in / fp32-out kernels of mixed_solve (MIXED_K_*) -> sum r^2"""
+    def mixed_kernel(self, kernel, scale_in, scale_out, arr_e32, arr_r32, op=MIXED_ON_CONSTANT) -> float:
+        """mg_mixed_kernel: one of the two fp64-in / fp32-out kernels of mixed_solve (MIXED_K_*) -> sum r^2; op as in mixed_solve"""
         s = C.c_double(0)
-        _check(self.lib.mg_mixed_kernel(self.h, kernel, scale_in, scale_out, arr_e32, arr_r32, C.byref(s))); return s.value
+        _check(self.lib.mg_mixed_kernel(self.h, kernel | mixed_operator(op), scale_in, scale_out, arr_e32, arr_r32, C.byref(s))); return s.value
 
     # -- fourth-order defect correction on level 0
     def o4_residual(self, arr_u, arr_b, arr_r=-1) -> float:

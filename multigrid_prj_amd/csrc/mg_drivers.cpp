@@ -473,10 +473,25 @@ int Solver::mixed_solve(double tol, int maxit, int inner_cycles, double *hist, i
 {
     MG_TRY(mixed_check("mg_mixed_solve", REFUSE_DIST | REFUSE_STAGE_CB));
     if (inner_cycles < 1) { set_last_error("mg_mixed_solve: inner_cycles must be at least 1"); return MG_ERR_BAD_ARG; }
+    // bits 0 .. 15: the count; MG_MIXED_OPERATOR in bits 16, 17; MG_MIXED_INNER_PCG; no other bit
+    const unsigned flags = (unsigned)inner_cycles;
+    const int mx_op = (int)((flags >> 16) & 3u);
+    const bool inner_pcg = (flags & (unsigned)MG_MIXED_INNER_PCG) != 0;
+    inner_cycles = (int)(flags & 0xffffu);
+    if ((flags & ~(0xffffu | (3u << 16) | (unsigned)MG_MIXED_INNER_PCG)) || (mx_op != MG_MIXED_ON_CONSTANT && mx_op != MG_MIXED_ON_COEFFICIENT)) {
+        set_last_error("mg_mixed_solve: unknown bits above the count (MG_MIXED_OPERATOR(MG_MIXED_ON_COEFFICIENT) and MG_MIXED_INNER_PCG are the only ones)");
+        return MG_ERR_BAD_ARG;
+    }
+    if (inner_pcg && mx_op != MG_MIXED_ON_COEFFICIENT) { set_last_error("mg_mixed_solve: MG_MIXED_INNER_PCG needs MG_MIXED_ON_COEFFICIENT"); return MG_ERR_BAD_ARG; }
+    if (inner_cycles < 1) { set_last_error("mg_mixed_solve: the count (bits 0 .. 15) must be at least 1"); return MG_ERR_BAD_ARG; }
     if (maxit < 0) { set_last_error("mg_mixed_solve: negative maxit"); return MG_ERR_BAD_ARG; }
     if (!mx_has_b_ || !mx_has_u_) {
         set_last_error("mg_mixed_solve: call mg_mixed_set_rhs and mg_mixed_set_solution first");
         return MG_ERR_BAD_ARG;
+    }
+    if (mx_op == MG_MIXED_ON_COEFFICIENT) {
+        MG_TRY(fam_check<VcFam>("mg_mixed_solve", FAM_NEED_CYCLE));   // a coefficient, V / W / F, Jacobi or red-black
+        return mixed_solve_vc(tol, maxit, inner_cycles, inner_pcg, hist, hist_cap, n_hist, st);
     }
     Level &L0 = lv_[0];
     const Geom &g32 = L0.g;
@@ -533,9 +548,91 @@ int Solver::mixed_solve(double tol, int maxit, int inner_cycles, double *hist, i
     return MG_OK;
 }
 
+// The same loop on mg_vc_*'s operator (MG_MIXED_ON_COEFFICIENT; kernels: mg_vc_mixed.hip): the operator is the handle's as it
+// stands at the call -- the fp32 level-0 coefficient read as fp64, shift_, vc_mask_, the form of mg_vc_set_form -- and nothing
+// new is kept. The Dirichlet nodes are the mask's; in the singular case (every face Neumann, no shift) b64 is projected first
+// with mg_vc_project's weights and stays projected, u64 is projected after the last correction, and relres is evaluated once
+// more on the projected u64, so that it is the residual of what is returned. The inner solve from U32(0) = 0 is `count` vc
+// cycles, or -- inner_pcg -- `count` iterations of mg_vc_pcg_solve's weighted flexible CG with tolerance 0 (a breakdown ends
+// it early; the iterate it holds is the correction). One fused launch and one host synchronisation per correction, plus the
+// CG's own in that mode.
+int Solver::mixed_solve_vc(double tol, int maxit, int count, bool inner_pcg, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st)
+{
+    if (inner_pcg) MG_TRY(krylov_alloc());
+    Level &L0 = lv_[0];
+    const Geom &g32 = L0.g;
+    const bool singular = vc_singular();
+    double *const b = mxptr(MXB);
+    mg_mixed_stats out{0, 0, 0, 0, 0.0};
+    int nh = 0;
+    auto record = [&](double rel) { if (hist && nh < hist_cap) hist[nh] = rel; nh++; out.relres = rel; };
+    auto fetch_sum = [&](double *partials, int np, double *v) -> int {   // the fixed-order sum of the partials; synchronises
+        launch_reduce_final(stream_, partials, np, d_mx_sum_);
+        MG_HIP(hipGetLastError());
+        MG_TRY(fetch_scalars(SC_MX_SUM, d_mx_sum_));
+        *v = h_scal_[SC_MX_SUM];
+        return MG_OK;
+    };
+    // e32 == nullptr: the residual of u64 alone; -> sum r^2
+    auto residual = [&](const float *e32, double s_in, double s_out, double *v) -> int {
+        L0.rhs_halo_ok = false;
+        const int np = launch_vc_mixed(stream_, g64_, g32, L0.coef, shift_, vc_mask_, mxptr(MXU), e32, vcptr<float>(0), b, mxptr(MXU2),
+                                       ptr<float>(MG_ARR_RHS, 0), s_in, s_out, d_partials_, o4_partials_cap_, vc_plain_);
+        return fetch_sum(d_partials_, np, v);
+    };
+
+    if (singular) MG_TRY(bc_project_ptr_t<double>(vc_mask_, g64_, b, nullptr));
+    if (vc_mask_) launch_bc_dirichlet_copy<double>(stream_, g64_, vc_mask_, mxptr(MXU), b);
+    else launch_cg_boundary_copy<double>(stream_, g64_, mxptr(MXU), b);
+    double bb = 0, rr = 0;
+    MG_TRY(fetch_sum(d_mx_part_, launch_mixed_sumsq(stream_, g64_, b, d_mx_part_), &bb));
+    double s = mixed_scale(bb);   // the scale RHS32(0) currently carries
+    MG_TRY(residual(nullptr, 1.0, s, &rr));
+    auto relres = [&](double v) { return v == 0.0 ? 0.0 : std::sqrt(v / bb); };
+    record(relres(rr));
+    if (!std::isfinite(rr) || !std::isfinite(out.relres)) {
+        out.status = 2;
+    } else if (rr == 0.0) {
+        out.status = 0;   // nothing to do: u solves the system
+    } else {
+        for (int k = 0;; k++) {
+            if (k > 0 && out.relres <= tol) { out.status = 0; break; }
+            if (k == maxit) { out.status = 1; break; }
+            MG_HIP(hipMemsetAsync(L0.base[MG_ARR_U], 0, L0.alloc_elems * esize(), stream_));
+            if (inner_pcg) {
+                mg_krylov_stats ks{0, 0, 0.0, 0.0};
+                MG_TRY(vc_pcg_t<float>(0.0, count, nullptr, 0, nullptr, &ks));
+                out.cycles += ks.iters;
+            } else {
+                for (int c = 0; c < count; c++) MG_TRY(fam_cycle_enqueue_t<VcFam<float>>());
+                out.cycles += count;
+            }
+            const double s_next = mixed_scale(rr);   // from the PREVIOUS residual: known before the launch
+            double rr_new = 0;
+            MG_TRY(residual(ptr<float>(MG_ARR_U, 0), s, s_next, &rr_new));   // the one host synchronisation per correction
+            record(relres(rr_new));
+            if (!std::isfinite(rr_new) || !std::isfinite(out.relres)) { out.status = 2; break; }   // not taken: u64 stays the last iterate
+            std::swap(mx_[MXU], mx_[MXU2]);
+            out.outer = k + 1;
+            rr = rr_new;
+            s = s_next;
+        }
+    }
+    if (singular && out.status != 2) {
+        MG_TRY(bc_project_ptr_t<double>(vc_mask_, g64_, mxptr(MXU), nullptr));
+        MG_TRY(residual(nullptr, 1.0, mixed_scale(rr), &rr));   // of the u64 returned
+        out.relres = relres(rr);
+    }
+    if (n_hist) *n_hist = nh;
+    if (st) *st = out;
+    return MG_OK;
+}
+
 int Solver::mixed_kernel(int kernel, double scale_in, double scale_out, int arr_e32, int arr_r32, double *sumsq_r)
 {
     MG_TRY(mixed_check("mg_mixed_kernel"));
+    const int mx_op = kernel >= 0 ? (kernel >> 16) : 0;   // MG_MIXED_OPERATOR; any other bit above the kind fails the test below
+    if (mx_op == MG_MIXED_ON_COEFFICIENT) kernel &= 0xffff;
     if (kernel != MG_MIXED_K_RESIDUAL && kernel != MG_MIXED_K_CORRECT_RESIDUAL) { set_last_error("mg_mixed_kernel: unknown kernel"); return MG_ERR_BAD_ARG; }
     const bool corr = kernel == MG_MIXED_K_CORRECT_RESIDUAL;
     if (!check_arr(arr_r32, 0, "mg_mixed_kernel") || (corr && !check_arr(arr_e32, 0, "mg_mixed_kernel"))) return MG_ERR_BAD_ARG;
@@ -546,14 +643,21 @@ int Solver::mixed_kernel(int kernel, double scale_in, double scale_out, int arr_
         return MG_ERR_BAD_ARG;
     }
     Level &L0 = lv_[0];
+    if (mx_op == MG_MIXED_ON_COEFFICIENT) MG_TRY(fam_check<VcFam>("mg_mixed_kernel", 0));   // a coefficient
     if (arr_r32 == MG_ARR_RHS) L0.rhs_halo_ok = false;
     int np = 0;
-    if (corr)
+    double *part = d_mx_part_;
+    if (mx_op == MG_MIXED_ON_COEFFICIENT) {   // mg_vc_*'s operator as it stands: coefficient, shift, mask, form (mg_vc_mixed.hip)
+        part = d_partials_;
+        np = launch_vc_mixed(stream_, g64_, L0.g, L0.coef, shift_, vc_mask_, mxptr(MXU), corr ? ptr<float>(arr_e32, 0) : (const float *)nullptr,
+                             vcptr<float>(0), mxptr(MXB), mxptr(MXU2), ptr<float>(arr_r32, 0), scale_in, scale_out, d_partials_,
+                             o4_partials_cap_, vc_plain_);
+    } else if (corr)
         np = launch_mixed_correct_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), ptr<float>(arr_e32, 0), mxptr(MXB), mxptr(MXU2),
                                            ptr<float>(arr_r32, 0), scale_in, scale_out, d_mx_part_);
     else
         np = launch_mixed_residual(stream_, g64_, L0.g, L0.coef, mxptr(MXU), mxptr(MXB), ptr<float>(arr_r32, 0), scale_out, d_mx_part_);
-    launch_reduce_final(stream_, d_mx_part_, np, d_mx_sum_);
+    launch_reduce_final(stream_, part, np, d_mx_sum_);
     MG_HIP(hipGetLastError());
     MG_TRY(fetch_scalars(SC_MX_SUM, d_mx_sum_));
     if (corr) std::swap(mx_[MXU], mx_[MXU2]);

@@ -310,6 +310,8 @@ inline bool o4_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return
 inline bool vc_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return march_ok(dim, nx, ny, nz, elem_size); }
 inline bool bc_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return march_ok(dim, nx, ny, nz, elem_size); }
 inline bool fas_march_ok(int dim, int nx, int ny, int nz, int elem_size) { return march_ok(dim, nx, ny, nz, elem_size); }
+// mg_vc_mixed.hip: the fp64 arrays decide (a lane owns one 16-byte vector of doubles), whatever the handle's element size
+inline bool vc_mixed_march_ok(int dim, int nx, int ny, int nz) { return march_ok(dim, nx, ny, nz, 8); }
 
 struct CoarseOut {
     int iters;

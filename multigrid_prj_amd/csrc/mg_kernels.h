@@ -297,6 +297,17 @@ int launch_mixed_correct_residual(hipStream_t s, const Geom &g64, const Geom &g3
 // partials of v^2 over all nodes
 int launch_mixed_sumsq(hipStream_t s, const Geom &g64, const double *v, double *partials);
 
+// ---- the same two kernels on mg_vc_*'s operator (mg_vc_mixed.hip; MG_MIXED_ON_COEFFICIENT) ----
+// coef = the level's mg_level_coefficients, sigma the shift, mask the Neumann faces, a32 the handle's fp32 level-0 coefficient
+// (its fp64 image is the operator's). e32 == nullptr: the first residual, r32 = (float)(scale_out * (b - L u)), 0 on the mask's
+// Dirichlet nodes; otherwise u_out = u + (double)e32 / scale_in at the mask's unknowns (u on its Dirichlet nodes; u_out must not
+// alias u) and the same residual of u_out. The marching tile where vc_mixed_march_takes and its grid fits `cap` partial sums,
+// the plain form (one thread per node) otherwise. -> the number of partial sums left in `partials`.
+bool vc_mixed_march_takes(const Geom &g64, bool plain);
+int launch_vc_mixed(hipStream_t s, const Geom &g64, const Geom &g32, const double coef[4], double sigma, int mask, const double *u,
+                    const float *e32, const float *a32, const double *b, double *u_out, float *r32, double scale_in, double scale_out,
+                    double *partials, int cap, bool plain);
+
 // ---- implicit heat-equation stepper on level 0 (mg_heat.hip, driven by Solver::heat_step) ----
 // out = right-hand side of one theta-scheme step built from u (and the source f; nullptr: f = 0): on interior nodes
 // ((f + u / dt) - (1 - theta) A0 u) / theta with coef0 = {cx, cy, cz, cd0}, the UNSHIFTED operator of the level in fp64

@@ -310,6 +310,7 @@ private:
     template <typename T> int fmg_t(int cycles_per_level, mg_fmg_stats *st);
     int mixed_check(const char *fn, unsigned refuse = REFUSE_DIST);      // MG_F32, then driver_begin(fn, refuse)
     int mixed_alloc();
+    int mixed_solve_vc(double tol, int maxit, int count, bool inner_pcg, double *hist, int hist_cap, int *n_hist, mg_mixed_stats *st);   // MG_MIXED_ON_COEFFICIENT
     // U(0) = 0, then inner_cycles outer iterations of mg_solve on RHS(0): the approximate solve of the correction equation
     // of mixed_solve and o4_solve; no synchronisation
     int correction_cycles(int inner_cycles);

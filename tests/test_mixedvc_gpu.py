@@ -1,0 +1,412 @@
+"""mg_mixed_solve / mg_mixed_kernel on the variable-coefficient operator (MG_MIXED_OPERATOR(MG_MIXED_ON_COEFFICIENT),
+MG_MIXED_INNER_PCG; include/mg_hip.h, multigrid_prj_amd/csrc/mg_vc_mixed.hip).
+
+1. the two kernels, tile and plain form, against the fp64 contract restated in numpy (tests/vcn_ref.py's VCNProblem in float64 on
+   a = (double)a32), bit for bit; their sums of squares against long-double sums;
+2. the whole solve against an independent numpy loop (tests/mixedvc_ref.py): corrections, the true residual, the history;
+3. what it is for: fp64 residuals where the fp32 handle's own mg_vc_solve stalls, and CG as the inner solver where cycles stall;
+4. contracts: scaling, a == 1 against the constant kernel, unflagged calls unchanged, determinism, refusals, edge cases.
+
+That padding columns and ghost planes stay zero and are not relied on is tests/test_mixedvc_storage_gpu.py's.
+"""
+import functools
+import math
+
+import numpy as np
+import pytest
+
+from multigrid_prj_amd import capi
+from tests import mixedvc_ref as mr
+from tests import npref
+from tests import vcn_ref as vn
+
+pytestmark = pytest.mark.gpu
+
+U, E, RHS, TMP, RES = capi.ARR_U, capi.ARR_E, capi.ARR_RHS, capi.ARR_TMP, capi.ARR_RES
+COEF = capi.MIXED_ON_COEFFICIENT
+KRES, KCORR = capi.MIXED_K_RESIDUAL, capi.MIXED_K_CORRECT_RESIDUAL
+LD = np.longdouble
+
+
+def ld_sumsq(a):
+    a = a.astype(LD)
+    return float(np.sum(a * a))
+
+
+def b64_of(s):
+    """b64 as the handle holds it (the dense part of the raw allocation)"""
+    raw = s.debug_raw_get(capi.RAW_MIXED, 0, 0)
+    shape = s.level_shape(0)
+    dense = raw[1:-1, :, :shape[-1]]
+    return dense[0].copy() if len(shape) == 2 else dense.copy()
+
+
+# ---------------------------------------------------------------- 1. the kernels, bit for bit
+# 2-D (always plain) 17 and 97; 3-D 17: plain only; 33: the smallest tile, exactly 16 fp64 vectors plus the odd column; 65; 129: more
+# than one block along x (65 vectors: the second block holds the last full vector and writes the tail lines)
+KSHAPES = [(2, 17), (2, 97), (3, 17), (3, 33), (3, 65), (3, 129)]
+
+
+def masks(dim):
+    return (0, vn.all_faces(dim), vn.MIXED if dim == 3 else 0b1010)
+
+
+@pytest.mark.parametrize("mi", [0, 1, 2], ids=["mask0", "all-neumann", "mixed"])
+@pytest.mark.parametrize("dim,n", KSHAPES)
+def test_kernels_bit_for_bit(dim, n, mi):
+    """r32 and u64' equal the numpy contract, sum r^2 a long-double sum to rel 1e-13, for the first residual and the fused
+    correction + residual (a power-of-two scale_in, then one that is none), shift 0 and 10, both forms where the tile takes the
+    shape; u64 (by the residual kernel), b64, e32 and the coefficient are unchanged; e on Dirichlet nodes is not looked at"""
+    mask = masks(dim)[mi]
+    rng = np.random.default_rng(100 * n + 10 * dim + mi)
+    kw = dict(dim=dim, n=n, levels=2, length=1.0, alpha=1.3, smoother=capi.SMOOTH_RBGS, cycle=capi.CYCLE_V)
+    forms = (0, 1) if vn.march_ok(dim, n, n, n if dim == 3 else 1, 8) else (0,)
+    assert (len(forms) == 2) == (dim == 3 and n >= 33)
+    with capi.Solver(capi.make_desc(dtype=capi.MG_F32, **kw)) as s:
+        shape = s.level_shape(0)
+        a32 = np.exp(rng.standard_normal(shape)).astype(np.float32)
+        u0 = rng.standard_normal(shape)
+        b = rng.standard_normal(shape) * 1e3
+        e32 = rng.standard_normal(shape).astype(np.float32)
+        s.vc_set_coefficient(a32); s.vc_set_faces(mask)
+        s.mixed_set_rhs(b)
+        s.set_array(E, 0, e32)
+        for sigma in (0.0, 10.0):
+            s.set_shift(sigma)
+            P = vn.VCNProblem(mask=mask, sigma=sigma, prec=np.float64, **kw)
+            P.use_handle_coefs([s.level_coefficients(l) for l in range(2)])
+            P.set_a(a32.astype(np.float64))
+            dm = P.dirichlet(shape)
+            # the references, once for both forms
+            steps = [(None, 2.0 ** 5), (2.0 ** -7, 2.0 ** 5), (0.37, 3.0)]   # (scale_in or None = residual only, scale_out)
+            refs, u = [], u0
+            for s_in, s_out in steps:
+                if s_in is not None:
+                    u = mr.correct64(P, u, e32, s_in)
+                r = mr.residual64(P, u, b)
+                refs.append((u, (np.float64(s_out) * r).astype(np.float32), ld_sumsq(r)))
+            for form in forms:
+                s.vc_set_form(form)
+                s.mixed_set_solution(u0)
+                for (s_in, s_out), (u_ref, r32_ref, ss_ref) in zip(steps, refs):
+                    if s_in is None:
+                        ss = s.mixed_kernel(KRES, 1.0, s_out, E, TMP, op=COEF)
+                        got = s.get_array(TMP, 0)
+                    else:
+                        ss = s.mixed_kernel(KCORR, s_in, s_out, E, RES, op=COEF)
+                        got = s.get_array(RES, 0)
+                    tag = f"sigma={sigma} form={form} s_in={s_in}"
+                    got_u = s.mixed_get_solution()
+                    assert np.array_equal(got_u, u_ref), tag
+                    assert np.array_equal(got_u[dm], u0[dm]), tag
+                    assert np.array_equal(got, r32_ref), tag
+                    assert not got[dm].any(), tag
+                    np.testing.assert_allclose(ss, ss_ref, rtol=1e-13, err_msg=tag)
+                    assert np.array_equal(s.get_array(E, 0), e32) and np.array_equal(b64_of(s), b), tag
+                assert np.array_equal(s.vc_get_coefficient(0), a32)
+            # e on the Dirichlet nodes is not looked at: NaN there changes nothing (the last form, this shift)
+            if dm.any():
+                e_nan = e32.copy()
+                e_nan[dm] = np.nan
+                s.set_array(E, 0, e_nan)
+                s.mixed_set_solution(u0)
+                s.mixed_kernel(KCORR, 2.0 ** -7, 2.0 ** 5, E, RES, op=COEF)
+                assert np.array_equal(s.mixed_get_solution(), refs[1][0])
+                s.set_array(E, 0, e32)
+        s.vc_set_form(0); s.set_shift(0.0)
+
+
+# ---------------------------------------------------------------- 2. the solve against an independent loop
+# vcn_ref.convergence_problem / test_vcn_gpu.conv_desc: 33^3, 4 levels, red-black V(2,2), full weighting, 50 fixed coarse sweeps,
+# standard-normal b (seed 1). (field, faces, count, inner CG, tol, corrections of the reference)
+ROWS = {
+    "smooth-yhi-2cyc": ("smooth", "only-y-hi-dirichlet", 2, False, 3e-11, 12),
+    "smooth-mixed-2cyc": ("smooth", "mixed", 2, False, 1e-11, 10),
+    "smooth-singular-2cyc": ("smooth", "all-neumann-singular", 2, False, 1e-11, 9),
+    "aligned-yhi-8cg": ("aligned", "only-y-hi-dirichlet", 8, True, 1e-8, 6),
+    "offgrid-singular-8cg": ("offgrid", "all-neumann-singular", 8, True, 1e-10, 4),
+}
+MAXIT = 40
+EXACT = ("smooth-yhi-2cyc", "smooth-mixed-2cyc")   # cycles as inner solver, no projection: the GPU reproduces the numpy loop bit for bit
+
+
+def conv_kw():
+    return dict(dim=3, n=33, levels=4, length=1.0, alpha=1.0, dtype=capi.MG_F32, cycle=capi.CYCLE_V, smoother=capi.SMOOTH_RBGS, nu_pre=2,
+                nu_post=2, restriction=capi.RESTRICT_FULLW, outer_pre_gs=0, coarse_mode=capi.COARSE_FIXED, coarse_maxit=50)
+
+
+def field32(field):
+    return vn.FIELDS[field](33).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(row):
+    """the numpy loop with float32 inner solves (the reference) and with float64 ones (for the spread) -> (b, u, hist, b as left,
+    corrections, relres, spread); spread = the largest relative deviation between the two histories while the reference is above 1e-9"""
+    field, faces, count, pcg, tol, _ = ROWS[row]
+    mask, sigma = vn.FACES[faces]
+    b = vn.convergence_rhs((33, 33, 33))
+    out = {}
+    for prec in (np.float32, np.float64):
+        P64, Pin = mr.problems(field32(field), mask, sigma, prec)
+        out[prec] = mr.mixed_loop(P64, Pin, b, np.zeros_like(b), count, pcg, tol, MAXIT)
+    h32, h64 = out[np.float32][1], out[np.float64][1]
+    m = min(len(h32), len(h64))
+    above = h32[:m] > 1e-9
+    spread = float(np.max(np.abs(h32[:m][above] - h64[:m][above]) / h32[:m][above]))
+    for a in out[np.float32][:3]:
+        a.setflags(write=False)
+    return (b,) + out[np.float32] + (spread,)
+
+
+def conv_solver(field, faces):
+    mask, sigma = vn.FACES[faces]
+    s = capi.Solver(capi.make_desc(**conv_kw()))
+    s.set_shift(sigma); s.vc_set_coefficient(field32(field)); s.vc_set_faces(mask)
+    return s
+
+
+@pytest.mark.parametrize("row", list(ROWS))
+def test_solve_against_the_numpy_loop(row):
+    """status 0 within the reference's corrections + 1; stats.relres is the numpy fp64 residual of the u64 returned to rel 1e-12;
+    hist follows the reference entry by entry, while the reference is above 1e-9, to three times the spread between the reference
+    with float32 and with float64 inner solves (computed here: 1.0e-4, 6.0e-5, 8.6e-5 for the cycle rows, 5.3e-3, 3.5e-3 for
+    the CG rows -- swapping the whole inner arithmetic bounds what another fp32 rounding order can do). The deviation the GPU
+    shows is printed. Measured on an MI355X: 1.2e-16, 2.1e-16, 1.6e-16 for the cycle rows -- the GPU's fp32
+    vc cycle is bit-identical to numpy's on these settings, so the two non-singular cycle rows also assert u64 bit for bit
+    (the singular row's projection sums in another order) -- and 2.4e-3, 4.5e-3 for the CG rows, whose dots are summed in
+    another order."""
+    field, faces, count, pcg, tol, ncorr = ROWS[row]
+    b, u_ref, ref, b_ref, outer_ref, relres_ref, spread = reference(row)
+    assert outer_ref == ncorr and ref[-1] <= tol < ref[-2]   # the table above
+    mask, sigma = vn.FACES[faces]
+    P64, _ = mr.problems(field32(field), mask, sigma)
+    w = P64.node_weights(b.shape)
+    with conv_solver(field, faces) as s:
+        s.mixed_set_rhs(b); s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(tol, MAXIT, count, op=COEF, inner_pcg=pcg)
+        u = s.mixed_get_solution()
+        m = min(len(hist), len(ref))
+        above = ref[:m] > 1e-9
+        dev = float(np.max(np.abs(hist[:m][above] - ref[:m][above]) / ref[:m][above]))
+        same = np.array_equal(u, u_ref)
+        print(f"{row}: gpu {st.outer} corrections, {st.cycles} cycles, relres {st.relres:.3e}; reference {outer_ref}, {relres_ref:.3e}; "
+              f"history deviation {dev:.2e}, spread {spread:.2e}, u64 bit-identical: {same}")
+        print("gpu", hist, "reference", ref)
+        assert st.status == capi.MIXED_CONVERGED and st.outer <= ncorr + 1 and len(hist) == st.outer + 1
+        assert st.cycles == st.outer * count
+        b_left = b64_of(s)
+        true = math.sqrt(npref.fsum_sq(mr.residual64(P64, u, b_left)) / npref.fsum_sq(b_left))
+        assert st.relres == pytest.approx(true, rel=1e-12) and st.relres <= tol
+        assert P64.singular() or hist[-1] == st.relres   # singular: evaluated once more, on the projected u64
+        assert dev <= 3 * spread
+        if row in EXACT:
+            assert same   # hist itself differs in the last bit: the norms are summed in another order
+        if P64.singular():
+            assert abs((w * u).sum()) <= 1e-12 * (w * abs(u)).sum()
+            assert abs(b_left - b_ref).max() <= 4 * np.finfo(np.float64).eps * abs(b).max()   # b64 comes back projected
+            assert abs((w * b_left).sum()) <= 1e-12 * (w * abs(b_left)).sum()
+        else:
+            dm = P64.dirichlet(b.shape)
+            assert np.array_equal(b_left, b) and np.array_equal(u[dm], b[dm])
+        assert np.array_equal(s.vc_get_coefficient(0), field32(field))
+
+
+# ---------------------------------------------------------------- 3. what it is for
+@functools.lru_cache(maxsize=None)
+def fp32_floor(faces):
+    P = vn.convergence_problem("smooth", faces, prec=np.float32)
+    P.set_a(field32("smooth"))
+    b = vn.convergence_rhs(P.shape(0)).astype(np.float32)
+    return float(P.solve_history(np.zeros_like(b), b, 24, 50)[1].min())
+
+
+@pytest.mark.parametrize("faces", ["only-y-hi-dirichlet", "all-neumann-singular"])
+def test_fp64_residual_where_the_fp32_solve_stalls(faces):
+    """the fp32 handle's own mg_vc_solve stalls above 1e-7, at the floor vcn_ref reaches in float32 (computed here: 3.4e-5 and
+    5.2e-7); the mixed solve on the same handle passes 1e-11"""
+    floor = fp32_floor(faces)
+    b = vn.convergence_rhs((33, 33, 33))
+    with conv_solver("smooth", faces) as s:
+        s.set_rhs(b.astype(np.float32)); s.set_solution(np.zeros(b.shape, np.float32))
+        h32, _ = s.vc_solve(0.0, 24)
+        s.mixed_set_rhs(b); s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(1e-11, MAXIT, 2, op=COEF)
+        print(f"{faces}: float32 floor of the reference {floor:.3e}, mg_vc_solve {h32.min():.3e}; mixed {st.relres:.3e} in {st.outer} corrections")
+        assert floor > 1e-7 and h32.min() > 1e-7 and floor / 10 <= h32.min() <= 10 * floor
+        assert st.status == capi.MIXED_CONVERGED and st.relres <= 1e-11
+
+
+def test_cg_inner_solver_where_cycles_stall():
+    """the aligned jump of 1000: 14 corrections of 2 cycles stay above 0.5 (the numpy loop is at 0.68); 8 CG iterations per
+    correction converge to 1e-8"""
+    b = vn.convergence_rhs((33, 33, 33))
+    with conv_solver("aligned", "only-y-hi-dirichlet") as s:
+        s.mixed_set_rhs(b); s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(0.0, 14, 2, op=COEF)
+        print("cycles alone after 14 corrections of 2:", hist[-1])
+        assert st.status == capi.MIXED_MAXIT and st.outer == 14 and st.cycles == 28 and hist[-1] > 0.5
+        s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(1e-8, MAXIT, 8, op=COEF, inner_pcg=True)
+        assert st.status == capi.MIXED_CONVERGED and st.relres <= 1e-8 and st.outer <= 7
+
+
+# ---------------------------------------------------------------- 4. contracts
+def test_scaling_b_by_powers_of_two_changes_no_digit():
+    b = vn.convergence_rhs((33, 33, 33))
+    with conv_solver("smooth", "mixed") as s:
+        runs = []
+        for p in (0, -200, 200):
+            s.mixed_set_rhs(np.ldexp(b, p)); s.mixed_set_solution(np.zeros_like(b))
+            hist, st = s.mixed_solve(0.0, 5, 2, op=COEF)
+            runs.append((hist, np.ldexp(s.mixed_get_solution(), -p)))
+        for hist, u in runs[1:]:
+            assert np.array_equal(hist, runs[0][0]) and np.array_equal(u, runs[0][1])
+        assert runs[0][0][-1] < 1e-5 * runs[0][0][0]
+
+
+@pytest.mark.parametrize("dim,n", [(2, 33), (3, 17), (3, 33)])
+def test_unit_coefficient_is_the_constant_operator(dim, n):
+    """mask 0, a == 1: the constant mg_mixed_kernel's residual to rounding. The operation order differs (2 w (u_i - u_q) summed
+    against c u_q summed), so not bit for bit: each of the 2 * dim + 1 products and sums of either form rounds once, relative to
+    terms bounded by |d| max|u| -- 8 eps64 |d| max|u| covers both, plus half an ulp of the fp32 result each"""
+    rng = np.random.default_rng(n + dim)
+    kw = dict(dim=dim, n=n, levels=2, length=1.0, alpha=1.0, dtype=capi.MG_F32, smoother=capi.SMOOTH_RBGS, cycle=capi.CYCLE_V)
+    with capi.Solver(capi.make_desc(**kw)) as s:
+        shape = s.level_shape(0)
+        u, b = rng.standard_normal(shape), rng.standard_normal(shape)
+        s.vc_set_coefficient(np.ones(shape, np.float32)); s.vc_set_faces(0)
+        s.mixed_set_rhs(b); s.mixed_set_solution(u)
+        ss_c = s.mixed_kernel(KRES, 1.0, 1.0, E, TMP)
+        r_c = s.get_array(TMP, 0).astype(np.float64)
+        ss_v = s.mixed_kernel(KRES, 1.0, 1.0, E, RES, op=COEF)
+        r_v = s.get_array(RES, 0).astype(np.float64)
+        d = abs(s.level_coefficients(0)[3])
+        bound = 8 * np.finfo(np.float64).eps * d * abs(u).max() + np.finfo(np.float32).eps * abs(r_c)
+        print("largest difference", abs(r_v - r_c).max(), "bound", bound.min())
+        assert (abs(r_v - r_c) <= bound).all()
+        assert ss_v == pytest.approx(ss_c, rel=1e-12)
+
+
+def test_unflagged_calls_keep_their_bits_and_runs_repeat():
+    """a constant-operator mg_mixed_solve gives the same bits before and after flagged calls on the same handle; two flagged runs
+    give the same bits (cycles and CG)"""
+    b = vn.convergence_rhs((33, 33, 33))
+    with conv_solver("smooth", "mixed") as s:
+        def constant():
+            s.mixed_set_rhs(b); s.mixed_set_solution(np.zeros_like(b))
+            hist, st = s.mixed_solve(0.0, 3, 2)
+            ss = s.mixed_kernel(KCORR, 4.0, 2.0, U, RES)
+            return hist, s.mixed_get_solution(), ss, s.get_array(RES, 0)
+
+        def flagged(pcg):
+            s.mixed_set_rhs(b); s.mixed_set_solution(np.zeros_like(b))
+            hist, st = s.mixed_solve(0.0, 3, 2, op=COEF, inner_pcg=pcg)
+            return hist, s.mixed_get_solution()
+
+        before = constant()
+        runs = [flagged(False), flagged(True), flagged(False), flagged(True)]
+        after = constant()
+        assert all(np.array_equal(x, y) for x, y in zip(before, after))
+        assert all(np.array_equal(x, y) for x, y in zip(runs[0], runs[2])) and all(np.array_equal(x, y) for x, y in zip(runs[1], runs[3]))
+        assert not np.array_equal(runs[0][0], before[0])   # another operator
+
+
+def refused(call, word=""):
+    with pytest.raises(capi.MgError) as e:
+        call()
+    assert e.value.code == -4 and word in str(e.value), str(e.value)
+
+
+def test_refusals_leave_everything_untouched():
+    rng = np.random.default_rng(9)
+    base = dict(dim=3, n=17, levels=3, length=1.0, alpha=1.0, dtype=capi.MG_F32, cycle=capi.CYCLE_V, smoother=capi.SMOOTH_RBGS,
+                coarse_mode=capi.COARSE_FIXED, coarse_maxit=6)
+    lib = capi.load()
+    op = capi.mixed_operator(COEF)
+
+    def raw_solve(s, arg):
+        st = capi.MgMixedStats()
+        return capi._check(lib.mg_mixed_solve(s.h, 1e-8, 3, arg, None, 0, None, st))
+
+    def raw_kernel(s, k):
+        return capi._check(lib.mg_mixed_kernel(s.h, k, 1.0, 1.0, E, RES, None))
+
+    with capi.Solver(capi.make_desc(**base)) as s:
+        shape = s.level_shape(0)
+        u0, b = rng.standard_normal(shape), rng.standard_normal(shape)
+        s.mixed_set_rhs(b); s.mixed_set_solution(u0)
+        before = s.device_bytes()
+        refused(lambda: s.mixed_solve(1e-8, 3, 2, op=COEF), "no coefficient")
+        refused(lambda: s.mixed_kernel(KRES, 1.0, 1.0, E, RES, op=COEF), "no coefficient")
+        assert s.device_bytes() == before
+        a32 = np.exp(rng.standard_normal(shape)).astype(np.float32)
+        s.vc_set_coefficient(a32); s.vc_set_faces(vn.MIXED)
+        coefs = [s.vc_get_coefficient(l) for l in range(3)]
+        before = s.device_bytes()
+        for arg in (2 | (1 << 18), 2 | (1 << 19), 2 | (1 << 21), 2 | (1 << 30), 2 | op | (1 << 18), 2 | capi.mixed_operator(1),
+                    2 | capi.mixed_operator(3), 2 | capi.MIXED_INNER_PCG, 2 | capi.mixed_operator(1) | capi.MIXED_INNER_PCG,
+                    op, op | capi.MIXED_INNER_PCG, 0, -1):
+            refused(lambda: raw_solve(s, arg))
+        for k in (KRES | capi.mixed_operator(1), KRES | capi.mixed_operator(3), KRES | op | capi.MIXED_INNER_PCG, KCORR | (1 << 18), 2 | op):
+            refused(lambda: raw_kernel(s, k))
+        refused(lambda: s.mixed_solve(1e-8, -1, 2, op=COEF), "maxit")
+        s.set_stage_callback(lambda *a: None)
+        refused(lambda: s.mixed_solve(1e-8, 3, 2, op=COEF), "stage callback")
+        refused(lambda: s.mixed_solve(1e-8, 3, 2, op=COEF, inner_pcg=True), "stage callback")
+        s.set_stage_callback(None)
+        assert np.array_equal(s.mixed_get_solution(), u0) and np.array_equal(b64_of(s), b) and s.device_bytes() == before
+        assert all(np.array_equal(s.vc_get_coefficient(l), coefs[l]) for l in range(3))
+        # the Krylov arrays come with the first CG run, as in mg_vc_pcg_solve, and only then
+        s.mixed_solve(1e-8, 1, 2, op=COEF)
+        assert s.device_bytes() == before
+        s.mixed_solve(1e-8, 1, 2, op=COEF, inner_pcg=True)
+        assert s.device_bytes() > before
+    for more, word in ((dict(cycle=capi.CYCLE_SAWTOOTH), "sawtooth"), (dict(smoother=capi.SMOOTH_GS_LEX), "smoother"),
+                       (dict(smoother=capi.SMOOTH_ZEBRA_Y), "smoother")):
+        with capi.Solver(capi.make_desc(**dict(base, **more))) as s:
+            u0 = rng.standard_normal(s.level_shape(0))
+            s.mixed_set_rhs(u0); s.mixed_set_solution(u0)
+            s.vc_set_coefficient(np.ones(s.level_shape(0), np.float32))
+            before = s.device_bytes()
+            refused(lambda: s.mixed_solve(1e-8, 3, 2, op=COEF), word)
+            refused(lambda: s.mixed_solve(1e-8, 3, 2, op=COEF, inner_pcg=True), word)
+            assert np.array_equal(s.mixed_get_solution(), u0) and s.device_bytes() == before
+    with capi.Solver(capi.make_desc(**dict(base, dtype=capi.MG_F64))) as s:   # the cycles run in fp32
+        s.vc_set_coefficient(np.ones(s.level_shape(0)))
+        refused(lambda: s.mixed_solve(1e-8, 3, 2, op=COEF), "MG_F32")
+        refused(lambda: s.mixed_kernel(KRES, 1.0, 1.0, E, RES, op=COEF), "MG_F32")
+    with capi.Solver(capi.make_desc(**base), device=0, rank=0, nranks=2, dry=True) as s:
+        before = s.device_bytes()
+        refused(lambda: s.mixed_solve(1e-8, 3, 2, op=COEF), "distributed")
+        refused(lambda: s.mixed_kernel(KRES, 1.0, 1.0, E, RES, op=COEF), "distributed")
+        assert s.device_bytes() == before
+
+
+@pytest.mark.parametrize("faces", ["mixed", "all-neumann-singular"])
+def test_edge_cases_take_no_correction(faces):
+    """b = 0 and a first iterate that already solves the system: status 0, no correction, no cycle; maxit = 0: no correction
+    either, with the status mg_mixed_solve has always given it (MIXED_MAXIT while the residual is not zero)"""
+    b = vn.convergence_rhs((33, 33, 33))
+    mask, sigma = vn.FACES[faces]
+    P64, _ = mr.problems(field32("smooth"), mask, sigma)
+    with conv_solver("smooth", faces) as s:
+        s.mixed_set_rhs(np.zeros_like(b)); s.mixed_set_solution(np.zeros_like(b))
+        for pcg in (False, True):
+            hist, st = s.mixed_solve(1e-8, 5, 2, op=COEF, inner_pcg=pcg)
+            assert (st.status, st.outer, st.cycles, st.relres) == (0, 0, 0, 0.0) and list(hist) == [0.0]
+            assert not s.mixed_get_solution().any()
+        s.mixed_set_rhs(b); s.mixed_set_solution(np.zeros_like(b))
+        hist, st = s.mixed_solve(1e-8, 0, 2, op=COEF)
+        assert (st.status, st.outer, st.cycles) == (capi.MIXED_MAXIT, 0, 0) and len(hist) == 1 and hist[0] > 0
+        # u solves the system exactly: b = L u evaluated by the contract itself, so the residual is exactly zero
+        if not P64.singular():
+            rng = np.random.default_rng(3)
+            u = np.round(rng.standard_normal(b.shape) * 8) / 8            # few bits: every product and sum below is exact
+            s.vc_set_coefficient(np.ones(b.shape, np.float32))
+            P1, _ = mr.problems(np.ones(b.shape, np.float32), mask, sigma)
+            bu = P1.apply_A(u, 0)
+            assert not mr.residual64(P1, u, bu).any()
+            s.mixed_set_rhs(bu); s.mixed_set_solution(u)
+            hist, st = s.mixed_solve(1e-8, 5, 2, op=COEF)
+            assert (st.status, st.outer, st.cycles, st.relres) == (0, 0, 0, 0.0) and np.array_equal(s.mixed_get_solution(), u)
