@@ -229,6 +229,50 @@ int mg_fmg(mg_handle h, int cycles_per_level, mg_fmg_stats *st);
  * (arr_bnd < 0: they are interpolated like every other node). Single-GPU handles only; arr_dst != arr_bnd. */
 int mg_fmg_prolong(mg_handle h, int coarse_level, int arr_src, int arr_dst, int arr_bnd);
 
+/* NESTED ITERATION ON THE OPERATOR FAMILIES (mg_bc_*, mg_vc_*, mg_fas_*, declared further down). No new entry point: a flag
+ * OR-ed into arguments the two calls already have.
+ *   mg_fmg(h, count | MG_FMG_OPERATOR(op), &st)
+ *   mg_fmg_prolong(h, coarse_level | MG_FMG_OPERATOR(op), arr_src, arr_dst, arr_bnd)
+ * count and coarse_level are bits 0 .. 15 (count 1 .. 65535). With no bit above 15 set both calls do what they always did, bit
+ * for bit (MG_FMG_ON_CONSTANT is 0). The operator is the family's AS THE HANDLE HOLDS IT AT THE CALL; the handle keeps nothing new:
+ *   MG_FMG_ON_FACES        mg_bc_*'s operator, the Neumann faces of mg_bc_set_faces
+ *   MG_FMG_ON_COEFFICIENT  mg_vc_*'s operator: the coefficient, the shift, the Neumann faces of mg_vc_set_faces
+ *   MG_FMG_ON_REACTION     mg_fas_*'s operator exactly as mg_fas_set_reaction left it: its MG_FAS_ON_FACES / MG_FAS_ON_COEFFICIENT
+ *                          flags decide the linear part and which mask applies, as in every mg_fas_* call
+ * The pass is mg_fmg's with the family's launches:
+ *   1. singular case only (linear families, every face Neumann, shift 0): RHS(0) is projected with the family's weights, as
+ *      mg_<family>_solve does, and stays projected
+ *   2. RHS(l+1) = R RHS(l): the family's restriction (desc.restriction; mirrored full weighting at the Neumann faces, Dirichlet
+ *      data injected on the mask's Dirichlet nodes)
+ *   3. U(L-1) = 0 at the unknowns, RHS(L-1) on the mask's Dirichlet nodes; the family's coarsest-grid solve, one workgroup or
+ *      chip-wide sweeps as in its cycle; stats.coarse_* are this solve's
+ *   4. for l = L-2 .. 0: U(l) = Pi_mask U(l+1) at the unknowns, RHS(l) on the Dirichlet nodes (one launch), then count cycles of
+ *      the descriptor's kind started on level l
+ *   5. singular case: U(0) is projected
+ *   6. one residual: stats.relres = ||b - L u|| / ||b||, for mg_fas_*'s operator ||f - N(u)|| / ||f||
+ * For mg_fas_* the restricted f is the coarse right-hand side: these are the coarse PROBLEMS, not coarse corrections, so there
+ * is no tau term; the cycles started on level l then overwrite RHS / U / E of the levels below it as usual. No host
+ * synchronisation before the last residual (the two projections of the singular case synchronise, as in mg_<family>_solve).
+ * RHS(0) is unchanged (projected in the singular case); the incoming U(0) is ignored; nothing is allocated.
+ * Pi_mask, per coarsened axis: at an end whose face is in the mask the coarse row is extended by its mirror image, c[-1] =
+ * c[1] and c[nc] = c[nc-2], and the odd node next to that end takes the cubic rule on the extended row; the one-sided rule
+ * stays at an end whose face is Dirichlet. The nodes of a Neumann face are interpolated like every other unknown. Fine nodes on
+ * at least one face that is not in the mask take arr_bnd; with arr_bnd < 0 they are interpolated too. Each 1-D pass is
+ * ((wb b + wc c) - (a + d)) * 2^-k with every operation rounded separately, along x, then y, then z, for either kernel form
+ * (the streaming 3-D kernel or the gather kernel, MG_FMG_FAST): the same bits, and with mask 0 the bits of the unflagged call.
+ * MG_ERR_BAD_ARG with U untouched: any other bit above 15, count == 0, MG_FMG_ON_COEFFICIENT (or MG_FMG_ON_REACTION on a
+ * reaction with MG_FAS_ON_COEFFICIENT) with no coefficient set, whatever the family's cycle refuses (MG_CYCLE_SAWTOOTH, a
+ * smoother other than Jacobi or red-black, a stage callback, distributed handles) -- mg_fmg_prolong with a flag asks for a
+ * single-GPU handle and the coefficient only -- and everything the unflagged calls refuse.
+ * The FMG property ||u_fmg - u_h|| <= ||u_h - u*|| (max norm; u_h the discrete solution, u* a smooth solution compatible with
+ * the mask) with ONE red-black V(2,2) per level is tested on 33^3 / 4 levels for: mg_bc_* with x-lo and with all faces but y-hi
+ * Neumann (and a 2-D 65^2 case), mg_vc_* with a smooth factor-100 coefficient and x-lo, mg_fas_* cubic (gamma 1e3) and exp,
+ * each plain, MG_FAS_ON_FACES and MG_FAS_ON_COEFFICIENT with both masks. One listed case was dropped: mg_vc_* with all faces
+ * but y-hi Neumann, whose float64 reference pass reaches 1.21 x the discretisation error with one cycle per level (two cycles
+ * per level are below it); the pass itself is compared with the reference on that case like on the others. */
+enum mg_fmg_operator { MG_FMG_ON_CONSTANT = 0 /* default */, MG_FMG_ON_FACES = 1, MG_FMG_ON_COEFFICIENT = 2, MG_FMG_ON_REACTION = 3 };
+#define MG_FMG_OPERATOR(op) ((op) << 16)   /* OR-ed into mg_fmg's cycles_per_level or mg_fmg_prolong's coarse_level */
+
 /* W- and F-cycles (extension, mg_desc.h: MG_CYCLE_W, MG_CYCLE_F). With L = desc.levels, one cycle of kind V, W or F started
  * on level l is
  *     cyc(l, kind):
@@ -529,7 +573,7 @@ enum mg_face { MG_FACE_XLO = 1, MG_FACE_XHI = 2, MG_FACE_YLO = 4, MG_FACE_YHI = 
  * included); bad arrays, levels or masks; NULL handle. No other entry point changes behaviour, and the family allocates
  * nothing. Not combined with mg_vc_*, mg_o4_*, mg_heat_step, mg_fmg, mg_eig_solve, mg_mixed_solve or mg_pcg_solve, which
  * keep treating every face as Dirichlet (mg_fas_* reads this mask when its kind carries MG_FAS_ON_FACES, mg_eig_solve after
- * MG_EIG_OPERATOR(MG_EIG_ON_FACES) OR-ed into its m, see there). mg_mixed_solve has no faces-only operator (value 1 of
+ * MG_EIG_OPERATOR(MG_EIG_ON_FACES) OR-ed into its m, mg_fmg / mg_fmg_prolong after MG_FMG_OPERATOR(MG_FMG_ON_FACES), see there). mg_mixed_solve has no faces-only operator (value 1 of
  * mg_mixed_operator is refused): its Neumann faces are mg_vc_set_faces' with MG_MIXED_ON_COEFFICIENT, and a == 1 there is
  * this family's operator; mg_set_shift + mg_bc_solve is the implicit step with insulated walls. */
 int mg_bc_set_faces(mg_handle h, int mask);
@@ -580,7 +624,8 @@ int mg_bc_solve(mg_handle h, double tol, int maxit, double *hist, int hist_cap, 
  * mg_vc_restrict, mg_vc_project: mg_bc_restrict and mg_bc_project with this mask (no coefficient is needed).
  * MG_ERR_BAD_ARG as for mg_vc_*. Not combined with mg_fas_*, mg_o4_* or mg_fmg (mg_fas_* with MG_FAS_ON_COEFFICIENT,
  * mg_eig_solve with MG_EIG_ON_COEFFICIENT and, on an MG_F32 handle, mg_mixed_solve / mg_mixed_kernel with
- * MG_MIXED_OPERATOR(MG_MIXED_ON_COEFFICIENT) read the coefficient, the shift and this mask at the call, see there). */
+ * MG_MIXED_OPERATOR(MG_MIXED_ON_COEFFICIENT) read the coefficient, the shift and this mask at the call, see there; so does mg_fmg
+ * with MG_FMG_OPERATOR(MG_FMG_ON_COEFFICIENT)). */
 int mg_vc_set_faces(mg_handle h, int mask);
 int mg_vc_get_faces(mg_handle h, int *mask);
 int mg_vc_restrict(mg_handle h, int fine_level, int kind, int arr_src, int arr_dst);
@@ -640,7 +685,8 @@ typedef struct mg_fas_stats {
  * red-black (mg_fas_smooth's argument; the handle's for cycle, solve, coarse_solve); a sawtooth handle or a stage callback
  * installed (cycle, solve); distributed handles (dry runs included); bad arrays or levels and the aliasing mg_vc_residual /
  * mg_vc_smooth reject; negative or non-finite tolerances, maxit < 0; NULL handle. No other entry point changes behaviour, and
- * the family allocates nothing. Not combined with mg_vc_*, mg_o4_*, mg_fmg, mg_mixed_solve or mg_heat_step, and with
+ * the family allocates nothing. Not combined with mg_vc_*, mg_o4_*, mg_fmg (unless MG_FMG_OPERATOR(MG_FMG_ON_REACTION) is
+ * OR-ed into its count, see there), mg_mixed_solve or mg_heat_step, and with
  * mg_bc_* only as described next; mg_set_shift(1/dt) + mg_fas_solve is one implicit reaction-diffusion step.
  *
  * NEUMANN FACES. mg_fas_set_reaction(h, MG_FAS_CUBIC | MG_FAS_ON_FACES, gamma) (or MG_FAS_EXP | MG_FAS_ON_FACES) makes the

@@ -46,6 +46,13 @@ def mixed_operator(op):
     """include/mg_hip.h::MG_MIXED_OPERATOR: what is OR-ed into mg_mixed_solve's inner_cycles or mg_mixed_kernel's kernel"""
     return op << 16
 
+FMG_ON_CONSTANT, FMG_ON_FACES, FMG_ON_COEFFICIENT, FMG_ON_REACTION = 0, 1, 2, 3   # enum mg_fmg_operator
+
+
+def fmg_operator(op):
+    """include/mg_hip.h::MG_FMG_OPERATOR: what is OR-ed into mg_fmg's cycles_per_level or mg_fmg_prolong's coarse_level"""
+    return op << 16
+
 # enum mg_raw_space: the arrays mg_debug_raw_* (a test and debugging window, not a data path) can look at
 RAW_LEVEL, RAW_VC, RAW_KRYLOV, RAW_MIXED, RAW_EIG, RAW_HEAT, RAW_O4 = 0, 1, 2, 3, 4, 5, 6
 
@@ -546,18 +553,21 @@ class Solver:
         _check(self.lib.mg_pcg_kernel(self.h, kernel, scalar, a, dots))
         return dots[0], dots[1]
 
-    def fmg(self, cycles_per_level=1):
+    def fmg(self, cycles_per_level=1, op=None):
         """mg_fmg: full multigrid (nested iteration) from the coarsest grid up, cubic interpolation of the solution and
         cycles_per_level cycles of the descriptor's kind (V, W or F) per level; U(0) holds the iterate on return (its incoming content is ignored)
-        -> MgFmgStats"""
+        -> MgFmgStats. op (FMG_ON_*): the pass on a family's operator as the handle holds it at the call -- FMG_ON_FACES
+        mg_bc_*'s, FMG_ON_COEFFICIENT mg_vc_*'s, FMG_ON_REACTION mg_fas_*'s -- OR-ed into cycles_per_level as MG_FMG_OPERATOR
+        does; None passes cycles_per_level as it is"""
         st = MgFmgStats()
-        _check(self.lib.mg_fmg(self.h, cycles_per_level, C.byref(st)))
+        _check(self.lib.mg_fmg(self.h, cycles_per_level if op is None else cycles_per_level | fmg_operator(op), C.byref(st)))
         return st
 
-    def fmg_prolong(self, coarse_level, arr_src, arr_dst, arr_bnd=-1):
+    def fmg_prolong(self, coarse_level, arr_src, arr_dst, arr_bnd=-1, op=None):
         """mg_fmg_prolong: arr_dst(coarse_level - 1) = Pi arr_src(coarse_level), the FMG (cubic) interpolation; fine
-        Dirichlet nodes from arr_bnd (< 0: interpolated too)"""
-        _check(self.lib.mg_fmg_prolong(self.h, coarse_level, arr_src, arr_dst, arr_bnd))
+        Dirichlet nodes from arr_bnd (< 0: interpolated too). op (FMG_ON_*): mirrored at the Neumann faces of that family's
+        mask, arr_bnd on the mask's Dirichlet nodes; OR-ed into coarse_level as MG_FMG_OPERATOR does"""
+        _check(self.lib.mg_fmg_prolong(self.h, coarse_level if op is None else coarse_level | fmg_operator(op), arr_src, arr_dst, arr_bnd))
 
     def subcycle(self, level, kind, path=0) -> MgCycleStats:
         """mg_subcycle: one cyc(level, kind) (CYCLE_V / _W / _F) on U(level), RHS(level) from the U it holds; path 0: launch

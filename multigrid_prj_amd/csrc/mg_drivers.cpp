@@ -320,8 +320,25 @@ int Solver::fmg_t(int cycles_per_level, mg_fmg_stats *st)
     return MG_OK;
 }
 
+// bits 16 and up of mg_fmg's count / mg_fmg_prolong's level: MG_FMG_OPERATOR(op); anything but the four operators is refused
+static int fmg_operator_of(const char *fn, int arg, int *op)
+{
+    if (arg < 0 || (arg >> 16) > MG_FMG_ON_REACTION) {
+        set_last_error(std::string(fn) + ": bits 16 and up must be MG_FMG_OPERATOR(op) with op an enum mg_fmg_operator");
+        return MG_ERR_BAD_ARG;
+    }
+    *op = arg >> 16;
+    return MG_OK;
+}
+
 int Solver::fmg(int cycles_per_level, mg_fmg_stats *st)
 {
+    if (cycles_per_level >> 16) {   // flagged (or negative): the pass on a family's operator
+        int op = 0;
+        MG_TRY(fmg_operator_of("mg_fmg", cycles_per_level, &op));
+        const int count = cycles_per_level & 0xffff;
+        return op == MG_FMG_ON_FACES ? fam_fmg<BcFam>(count, st) : (op == MG_FMG_ON_COEFFICIENT ? fam_fmg<VcFam>(count, st) : fam_fmg<FasFam>(count, st));
+    }
     MG_TRY(driver_begin("mg_fmg", REFUSE_DIST | REFUSE_STAGE_CB));
     if (!is_vwf(d_.cycle)) {
         set_last_error("mg_fmg: the descriptor's cycle must be MG_CYCLE_V (the levels of a sawtooth cycle hold errors, not solutions)");
@@ -366,7 +383,21 @@ int Solver::subcycle(int level, int kind, int path, mg_cycle_stats *st)
 
 int Solver::fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)
 {
+    if (coarse_level >> 16) {   // flagged (or negative): the interpolation by a family's mask
+        int op = 0;
+        MG_TRY(fmg_operator_of("mg_fmg_prolong", coarse_level, &op));
+        const int cl = coarse_level & 0xffff;
+        return op == MG_FMG_ON_FACES ? fam_fmg_prolong<BcFam>(cl, arr_src, arr_dst, arr_bnd)
+                                     : (op == MG_FMG_ON_COEFFICIENT ? fam_fmg_prolong<VcFam>(cl, arr_src, arr_dst, arr_bnd)
+                                                                    : fam_fmg_prolong<FasFam>(cl, arr_src, arr_dst, arr_bnd));
+    }
     MG_TRY(driver_begin("mg_fmg_prolong", REFUSE_DIST));
+    return fmg_prolong_mask(0, coarse_level, arr_src, arr_dst, arr_bnd);
+}
+
+// the argument checks and the launch; mask: the Neumann faces (0: the mask-free launch)
+int Solver::fmg_prolong_mask(int mask, int coarse_level, int arr_src, int arr_dst, int arr_bnd)
+{
     if (coarse_level < 1 || coarse_level >= d_.levels || !check_arr(arr_src, coarse_level, "mg_fmg_prolong") ||
         !check_arr(arr_dst, coarse_level - 1, "mg_fmg_prolong") || (arr_bnd >= 0 && !check_arr(arr_bnd, coarse_level - 1, "mg_fmg_prolong"))) {
         set_last_error("mg_fmg_prolong: bad level / array");
@@ -377,10 +408,10 @@ int Solver::fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)
     if (arr_dst == MG_ARR_RHS) lv_[fl].rhs_halo_ok = false;
     if (d_.dtype == MG_F64)
         launch_fmg_prolong<double>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<double>(arr_src, coarse_level), ptr<double>(arr_dst, fl),
-                                   arr_bnd >= 0 ? ptr<double>(arr_bnd, fl) : (double *)nullptr);
+                                   arr_bnd >= 0 ? ptr<double>(arr_bnd, fl) : (double *)nullptr, mask);
     else
         launch_fmg_prolong<float>(stream_, lv_[coarse_level].g, lv_[fl].g, ptr<float>(arr_src, coarse_level), ptr<float>(arr_dst, fl),
-                                  arr_bnd >= 0 ? ptr<float>(arr_bnd, fl) : (float *)nullptr);
+                                  arr_bnd >= 0 ? ptr<float>(arr_bnd, fl) : (float *)nullptr, mask);
     MG_HIP(hipGetLastError());
     return MG_OK;
 }
@@ -1335,6 +1366,12 @@ struct Solver::VcFam {
     // mg_vc_solve: U = RHS on the Dirichlet nodes; all faces Neumann and no shift: RHS(0) is projected first, U(0) at the end
     static int solve_begin(Solver &s) { return s.vc_singular() ? s.bc_project_t<T>(s.vc_mask_, 0, MG_ARR_RHS, nullptr) : MG_OK; }
     static int solve_end(Solver &s) { return s.vc_singular() ? s.bc_project_t<T>(s.vc_mask_, 0, MG_ARR_U, nullptr) : MG_OK; }
+    // mg_fmg on this operator: the mask of the interpolation, and RHS(l + 1) = R RHS(l) with the restriction down() uses
+    static int mask(const Solver &s) { return s.vc_mask_; }
+    static int restrict_rhs(Solver &s, int l)
+    {
+        return s.vc_mask_ ? s.bc_restrict_t<T>(s.vc_mask_, l, s.d_.restriction, MG_ARR_RHS, MG_ARR_RHS) : s.restrict_t<T>(l, s.d_.restriction, MG_ARR_RHS, MG_ARR_RHS);
+    }
     static void dirichlet_copy(Solver &s)
     {
         T *const x = s.ptr<T>(MG_ARR_U, 0);
@@ -1388,6 +1425,8 @@ struct Solver::BcFam {
     // first (it stays projected) and U(0) is projected at the end
     static int solve_begin(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(s.bc_mask_, 0, MG_ARR_RHS, nullptr) : MG_OK; }
     static int solve_end(Solver &s) { return s.bc_singular() ? s.bc_project_t<T>(s.bc_mask_, 0, MG_ARR_U, nullptr) : MG_OK; }
+    static int mask(const Solver &s) { return s.bc_mask_; }
+    static int restrict_rhs(Solver &s, int l) { return s.bc_restrict_t<T>(s.bc_mask_, l, s.d_.restriction, MG_ARR_RHS, MG_ARR_RHS); }
     static void dirichlet_copy(Solver &s)
     {
         launch_bc_dirichlet_copy<T>(s.stream_, s.lv_[0].g, s.bc_mask_, s.ptr<T>(MG_ARR_U, 0), s.ptr<T>(MG_ARR_RHS, 0));
@@ -1465,6 +1504,13 @@ struct Solver::FasFam {
     }
     static int down(Solver &s, int l) { return s.fas_coarse_rhs_t<T>(l); }   // U(l + 1) = E(l + 1) = the injected iterate, RHS(l + 1)
     static int up(Solver &s, int l) { return s.fas_correct_t<T>(l); }   // P writes face nodes already (mg_bc_cycle)
+    // no projection: the nonlinear problem has no null space to take out (mg_fas_solve does none either)
+    static int solve_begin(Solver &) { return MG_OK; }
+    static int solve_end(Solver &) { return MG_OK; }
+    // mg_fmg on this operator: f goes down by the weighting mg_fas_coarse_rhs gives the residual (mirrored by the mask, the
+    // coarse Dirichlet nodes injected); no tau term -- these are the coarse problems
+    static int mask(const Solver &s) { return s.fas_mask(); }
+    static int restrict_rhs(Solver &s, int l) { return s.bc_restrict_t<T>(s.fas_mask(), l, s.d_.restriction, MG_ARR_RHS, MG_ARR_RHS); }
     static void dirichlet_copy(Solver &s)   // mg_fas_solve: U = RHS on the Dirichlet nodes
     {
         launch_bc_dirichlet_copy<T>(s.stream_, s.lv_[0].g, s.fas_mask(), s.ptr<T>(MG_ARR_U, 0), s.ptr<T>(MG_ARR_RHS, 0));
@@ -1669,6 +1715,66 @@ int Solver::fam_solve(const char *fn, double tol, int maxit, double *hist, int h
     if (maxit < 0) { set_last_error(std::string(fn) + ": negative maxit"); return MG_ERR_BAD_ARG; }
     return d_.dtype == MG_F64 ? fam_solve_t<F<double>>(tol, maxit, hist, hist_cap, n_hist, per_cycle)
                               : fam_solve_t<F<float>>(tol, maxit, hist, hist_cap, n_hist, per_cycle);
+}
+
+// ---------------------------------------------------------------- nested iteration on a family's operator (mg_fmg with MG_FMG_OPERATOR), DESIGN.md section 27
+// fmg_t's pass with the family's launches: RHS goes down by the family's restriction, the coarsest level is solved as the
+// cycle solves it, and per level U(l) = Pi_mask U(l + 1) (mg_fmg.hip with the family's mask: mirrored at the Neumann faces,
+// RHS(l) on the mask's Dirichlet nodes) followed by count cycles started on level l. fam_cycle_rec_t started on level l only
+// overwrites the levels below l, which the pass has finished with. In the singular case (linear families, every face Neumann,
+// no shift) RHS(0) is projected first and U(0) last, as in fam_solve_t -- the projections are the only host synchronisations
+// before the residual at the end.
+template <class F>
+int Solver::fam_fmg_t(int count, mg_fmg_stats *st)
+{
+    typedef typename F::type T;
+    const int L = d_.levels, mask = F::mask(*this);
+    MG_TRY(F::solve_begin(*this));
+    for (int l = 0; l + 1 < L; l++) MG_TRY(F::restrict_rhs(*this, l));
+    MG_TRY(zero_array(MG_ARR_U, L - 1));
+    launch_bc_dirichlet_copy<T>(stream_, lv_[L - 1].g, mask, ptr<T>(MG_ARR_U, L - 1), ptr<T>(MG_ARR_RHS, L - 1));
+    MG_HIP(hipGetLastError());
+    MG_TRY(fam_cycle_rec_t<F>(L - 1, MG_CYCLE_V));   // the coarsest-grid solve: one workgroup or chip-wide sweeps, as in a cycle
+    MG_HIP(hipMemcpyAsync(h_coarse_, d_coarse_, sizeof(CoarseOut), hipMemcpyDeviceToHost, stream_));   // of this first, true coarse solve
+    for (int l = L - 2; l >= 0; l--) {
+        launch_fmg_prolong<T>(stream_, lv_[l + 1].g, lv_[l].g, ptr<T>(MG_ARR_U, l + 1), ptr<T>(MG_ARR_U, l), ptr<T>(MG_ARR_RHS, l), mask);
+        MG_HIP(hipGetLastError());
+        for (int k = 0; k < count; k++) {
+            if (d_.cycle == MG_CYCLE_V) { MG_TRY(fam_cycle_rec_t<F>(l, MG_CYCLE_V)); continue; }
+            MG_TRY(stats_begin());   // W and F: as fam_cycle_enqueue_t
+            const int rc = fam_cycle_rec_t<F>(l, d_.cycle);
+            acc_stats_ = false;
+            MG_TRY(rc);
+            MG_TRY(stats_end());
+        }
+    }
+    MG_TRY(F::solve_end(*this));
+    double nb = 0, nr = 0;
+    MG_TRY(sumsq(0, MG_ARR_RHS, &nb));
+    MG_TRY(fam_residual_sum_t<F>(0, MG_ARR_U, MG_ARR_RHS, -1, &nr));   // synchronises: h_coarse_ is valid from here
+    if (st) {
+        st->levels = L;
+        st->cycles_per_level = count;
+        st->coarse_iters = h_coarse_->iters;
+        st->coarse_flag = h_coarse_->flag;
+        st->relres = std::sqrt(nr / nb);
+    }
+    return MG_OK;
+}
+
+template <template <typename> class F>
+int Solver::fam_fmg(int count, mg_fmg_stats *st)
+{
+    MG_TRY(fam_check<F>("mg_fmg", FAM_NEED_CYCLE));
+    if (count < 1) { set_last_error("mg_fmg: cycles_per_level (bits 0 .. 15) must be at least 1"); return MG_ERR_BAD_ARG; }
+    return d_.dtype == MG_F64 ? fam_fmg_t<F<double>>(count, st) : fam_fmg_t<F<float>>(count, st);
+}
+
+template <template <typename> class F>
+int Solver::fam_fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd)
+{
+    MG_TRY(fam_check<F>("mg_fmg_prolong", 0));   // single-GPU handles, and a coefficient where the family's mask goes with one
+    return fmg_prolong_mask(F<double>::mask(*this), coarse_level, arr_src, arr_dst, arr_bnd);
 }
 
 // ---------------------------------------------------------------- implicit time steps on a family's operator (mg_*_heat_*), DESIGN.md section 21

@@ -281,7 +281,10 @@ void launch_eig_fill(hipStream_t s, const Geom &g, T *x, int column);
 // bnd != nullptr: fine Dirichlet nodes = bnd[node] instead, in the same launch. Whole (undistributed) levels only.
 template <typename T> bool fmg_prolong_fast_ok(const Geom &gc, const Geom &gf);   // the streaming 3-D form runs (else the gather kernel)
 template <typename T>
-void launch_fmg_prolong(hipStream_t s, const Geom &gc, const Geom &gf, const T *coarse, T *fine, const T *bnd);
+void launch_fmg_prolong(hipStream_t s, const Geom &gc, const Geom &gf, const T *coarse, T *fine, const T *bnd, int mask = 0);
+// mask (enum mg_face) != 0: the faces in it are Neumann faces -- the coarse rows are mirrored there, the odd node next to such
+// an end takes the cubic rule, and bnd goes to the fine nodes on at least one face that is not in the mask. mask 0 launches
+// the mask-free instantiations: the same code, registers and bits as before the mask existed.
 
 // ---- mixed-precision defect correction on level 0 (mg_mixed.hip, driven by Solver::mixed_solve) ----
 // g64 / g32: the fp64 and the fp32 geometry of level 0 (same extents, different pitches); coef = {cx, cy, cz, cd} in fp64.

@@ -112,6 +112,7 @@ public:
     int fmg(int cycles_per_level, mg_fmg_stats *st);
     // arr_dst(l) = Pi arr_src(l + 1), Dirichlet nodes from arr_bnd(l) (< 0: interpolated too) (mg_fmg_prolong)
     int fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd);
+    int fmg_prolong_mask(int mask, int coarse_level, int arr_src, int arr_dst, int arr_bnd);   // its checks and launch, by a face mask
     // one cyc(level, kind) on U(level), RHS(level): launch by launch (path 0) or by the LDS kernel rooted there (path 1)
     int subcycle(int level, int kind, int path, mg_cycle_stats *st);
     // root level the handle's cycles hand to the LDS kernel, -1: none
@@ -437,6 +438,10 @@ private:
     template <class F> int fam_cycle_rec_t(int l, int kind);
     template <class F> int fam_cycle_enqueue_t();
     template <class F> int fam_solve_t(double tol, int maxit, double *hist, int hist_cap, int *n_hist, mg_cycle_stats *per_cycle);   // vc, bc
+    // nested iteration on the family's operator (mg_fmg with MG_FMG_OPERATOR): the mirrored FMG interpolation by F::mask
+    template <class F> int fam_fmg_t(int count, mg_fmg_stats *st);
+    template <template <typename> class F> int fam_fmg(int count, mg_fmg_stats *st);   // fam_check, then by the handle's dtype
+    template <template <typename> class F> int fam_fmg_prolong(int coarse_level, int arr_src, int arr_dst, int arr_bnd);
     template <template <typename> class F> int fam_cycle_enqueue();   // by the handle's dtype
     // the public mg_<family>_<fn>: fam_check, the argument checks (messages start with fn), then the template by dtype
     template <template <typename> class F> int fam_residual(const char *fn, int level, int arr_x, int arr_rhs, int arr_r, double *sumsq_r);
