@@ -22,10 +22,14 @@ word in an array of the row's written set, which check (a) reports):
   mg_krylov.hip        pcg_kernel[*], pcg_solve          mg_mixed.hip   mixed_kernel[*], mixed_solve (fp32 handles)
   mg_io.hip            set_array_device, get_array_device
   mg_eig.hip           eig-gram, eig-combine
-  mg_heat.hip          heat_rhs, heat_step (tail): 33, 35 fp64; 65, 67 both
-  mg_o4.hip            o4_residual, o4_correct_residual (tail): 33, 35 fp64; 65 both; 67 fp64
+  mg_heat.hip          heat_rhs, heat_step (tail): 33, 35 fp64; 65, 67 both; the two non-isotropic family cases below on level 0
+  mg_o4.hip            o4_residual, o4_correct_residual (tail): 33, 35 fp64; 65 both; 67 fp64; the same two cases on level 0
   mg_vc.hip            vc_* rows, form 0 (marching tile, mirrored with a mask; tail): 33, 35 fp64; 65 both; 67 fp64 (fp32:
-                       67 % 4 == 3, the partial last vector); form 1 and n = 9, 17, 2-D: the plain kernels
+                       67 % 4 == 3, the partial last vector); form 1 and n = 9, 17, 2-D: the plain kernels.
+                       3d67L2-semi_xy1 (tests/tile_cases.py's s67): the cycle rows run the fp64 tile on level 1, 34 x 34 x 67 --
+                       an even row (no tail line) on a level with nz != nx, under checks (a) and (b); the restrict, coarse-rhs
+                       and correct rows cross the semi-coarsened transition. 3d65L2-aniso1.0_2.5_0.3 (a65): every row's tile
+                       with pairwise distinct axis coefficients; the cycle rows run the fp64 tile on level 1 (33^3, tail) too
   mg_bc.hip, mg_fas.hip  bc_* / fas_* rows, the same cases and forms
 An odd n that takes NO tail-line store: 9 and 17 (plain kernels) in every row, 35 and 67 in fp32 (n % 4 == 3).
 """
@@ -114,12 +118,16 @@ Case = namedtuple("Case", "id dim n levels extra")
 
 
 def C(dim, n, levels, **extra):
-    return Case(f"{dim}d{n}L{levels}" + "".join(f"-{k}{v}" for k, v in extra.items()), dim, n, levels, extra)
+    word = lambda v: "_".join(str(x) for x in v) if isinstance(v, tuple) else str(v)   # aniso=(1.0, 2.5, 0.3) -> aniso1.0_2.5_0.3
+    return Case(f"{dim}d{n}L{levels}" + "".join(f"-{k}{word(v)}" for k, v in extra.items()), dim, n, levels, extra)
 
 
 # operator families (tests/test_bc_gpu.py CASES, vcn_ref.march_ok): 9, 17 plain; 33, 34, 35 the fp64 marching tile (2^k + 1,
 # an even row, an odd row that is not 2^k + 1); 65, 67 the tile in both precisions (67: a partial last fp32 vector)
 FAM3 = [C(3, 9, 2), C(3, 17, 2), C(3, 33, 2), C(3, 34, 1), C(3, 35, 2), C(3, 65, 2), C(3, 67, 2)]
+# ... all isotropic cubes. tests/tile_cases.py's s67 and a65: the tile's stores on a level with nz != nx (34 x 34 x 67, level 1 of
+# the family cycle rows) and with pairwise distinct axis coefficients. march() below is about level 0, a cube in both
+FAM3 += [C(3, 67, 2, semi_xy=1), C(3, 65, 2, aniso=(1.0, 2.5, 0.3))]
 D2 = [C(2, 17, 2), C(2, 130, 1), C(2, 129, 2)]
 FAM = FAM3 + D2
 FAM_2LEVEL = [c for c in FAM if c.levels >= 2]
@@ -391,6 +399,7 @@ def fam_masks(dim):
 
 
 def march(case, dtype):
+    """level 0 (a cube) takes the marching tile; not for the levels of a semi-coarsened hierarchy"""
     return case.dim == 3 and case.n // (16 // (8 if dtype == F64 else 4)) >= 16 and case.n >= 7
 
 

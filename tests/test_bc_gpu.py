@@ -10,6 +10,7 @@ import pytest
 from multigrid_prj_amd import capi
 from tests import npref
 from tests import bc_ref as br
+from tests import tile_cases as tc
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +28,11 @@ CASES = [
     (2, 17, 2, {}), (2, 130, 1, {}),
     (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}), (3, 17, 3, {"semi_xy": 1}),
 ]
-
-
-def case_id(c):
-    dim, n, levels, extra = c
-    return f"{dim}d{n}" + "".join("-" + k for k in extra)
+# ... on all of which the tile sees a cube with cx == cy == cz (the last two are plain). tests/tile_cases.py: a33, a65 put it on
+# pairwise distinct axis coefficients, sa65, s67, s129 on a level with nz != nx (sa65: both at once; s67: an even row, 34 x 34 x 67;
+# s129: the fp32 tile, level 1 only)
+CASES += tc.CASES
+case_id = tc.case_id
 
 
 def mixed(dim):
@@ -62,13 +63,15 @@ def sumsq(r):
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_kernels_bit_for_bit(case, dtype):
     """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7), one red-black sweep and mg_bc_restrict (both kinds) on
-    levels 0 and 1, sigma 0 and 500, masks 0 / all faces / mixed (n = 9: every single face too); where the marching tile takes
-    the level the plain form is run too (mg_bc_set_form) against the same numbers. The inputs come back unmodified."""
+    the case's levels to check (0 and 1; s129: 1), sigma 0 and 500, masks 0 / all faces / mixed (n = 9: every single face too);
+    where the marching tile takes the level the plain form is run too (mg_bc_set_form) against the same numbers. The inputs come
+    back unmodified. The tile on distinct axis coefficients: a33, a65, sa65; on nz != nx: sa65, s67 (an even row), s129 (fp32)."""
     dim, n, levels, extra = case
     T = NP[dtype]
     rng = np.random.default_rng(100 * dim + n)
     masks = [0, br.all_faces(dim), mixed(dim)] + ([1 << k for k in range(2 * dim)] if n == 9 else [])
-    forms_seen = set()
+    check = tc.levels_to_check(case)
+    forms_seen = {l: set() for l in check}
     for omega in (1.0, 6.0 / 7.0):
         kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
         with capi.Solver(capi.make_desc(**kw)) as s:
@@ -78,8 +81,9 @@ def test_kernels_bit_for_bit(case, dtype):
                     s.bc_set_faces(mask)
                     assert s.bc_get_faces() == mask
                     P = problem_of(s, kw, T, mask, sigma)
-                    for l in range(min(levels, 2)):
+                    for l in check:
                         shape = s.level_shape(l)
+                        assert tuple(shape) == tc.level_shape(case, l)
                         u, b, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
                         jac_ref = P.jacobi(u, b, l)
                         assert jac_ref.dtype == T
@@ -90,7 +94,7 @@ def test_kernels_bit_for_bit(case, dtype):
                         march = dim == 3 and br.march_ok(3, shape[2], shape[1], shape[0], np.dtype(T).itemsize)
                         for form in ((0, 1) if march else (0,)):
                             s.bc_set_form(form)
-                            forms_seen.add("march" if march and form == 0 else "plain")
+                            forms_seen[l].add("march" if march and form == 0 else "plain")
                             tag = (l, sigma, omega, mask, form)
                             s.set_array(RHS, l, b)
                             if first:
@@ -119,16 +123,16 @@ def test_kernels_bit_for_bit(case, dtype):
                                 got = s.get_array(TMP, l + 1)
                                 assert np.array_equal(got, ref), (l, mask, kind, int((got != ref).sum()))
                             assert np.array_equal(s.get_array(E, l), u)
-    want = {"march", "plain"} if dim == 3 and br.march_side(3, n, np.dtype(T).itemsize) else {"plain"}
-    assert forms_seen == want
+    assert forms_seen == {l: tc.want_forms(case, l, np.dtype(T).itemsize) for l in check}   # per level: a semi level is no cube
 
 
 # ---------------------------------------------------------------- 2. mask 0 is the existing entry points
 @DTYPES
-@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 65, 2, {}), (2, 130, 1, {})], ids=case_id)
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 65, 2, {}), (2, 130, 1, {}), tc.A65, tc.SA65], ids=case_id)
 def test_mask_zero_equals_the_existing_entry_points(case, dtype):
     """mg_bc_residual / mg_bc_smooth / mg_bc_restrict(FULLW) with mask 0 against mg_residual / mg_smooth / mg_restrict(FULLW) on
-    the same random arrays, bit for bit, with and without a shift"""
+    the same random arrays, bit for bit, with and without a shift. a65 and sa65 pin the tile to mg_jacobi_fast.hip's kernels on an
+    operator with distinct axis coefficients (sa65: on a 33 x 33 x 65 level too)"""
     dim, n, levels, extra = case
     T = NP[dtype]
     kw = desc_kw(dim, n, levels, extra, dtype, omega=6.0 / 7.0)
@@ -219,47 +223,57 @@ CYCLE_KINDS = {
 CYCLE_SETTINGS = {"mixed": (mixed(3), 0.0), "all": (63, 10.0)}
 
 
+# (n, levels, extra) x kind x setting; sa65 (tests/tile_cases.py): a V(2,2) cycle whose Jacobi sweeps and residuals go through
+# the tile inside the driver's dispatch on 65^3 and on 33 x 33 x 65, both with pairwise distinct axis coefficients
+CYCLE_GRIDS = {"17-3": (17, 3, {}), "33-4": (33, 4, {}), "sa65": tc.SA65[1:]}
+CYCLE_PARAMS = [pytest.param(g, kind, setting, id=f"{g}-{kind}-{setting}") for g in ("17-3", "33-4") for kind in CYCLE_KINDS for setting in CYCLE_SETTINGS]
+CYCLE_PARAMS += [pytest.param("sa65", kind, "mixed", id=f"sa65-{kind}-mixed") for kind in ("v-rb", "v-jacobi")]
+
+
 @functools.lru_cache(maxsize=None)
-def cycle_inputs(n):
+def cycle_inputs(shape):
     """u0, b with float32 values: exact in both working dtypes, so the long-double reference is shared"""
-    rng = np.random.default_rng(n)
-    return rng.standard_normal((n, n, n)).astype(np.float32), rng.standard_normal((n, n, n)).astype(np.float32)
+    rng = np.random.default_rng(shape[-1])
+    return rng.standard_normal(shape).astype(np.float32), rng.standard_normal(shape).astype(np.float32)
 
 
 @functools.lru_cache(maxsize=None)
-def cycle_reference(n, levels, kind, setting, prec, coefs):
+def cycle_reference(grid, kind, setting, prec, coefs):
     """coefs: mg_level_coefficients of every level (doubles, shift included) -- the contract casts THOSE to T, and in fp32 the
     cast diagonal is not exactly -2 x the sum of the cast off-diagonals, which a reference with coefficients of its own
     would not see (n = 17, V red-black, mixed: 8.6e-8 from long double with its own float32 coefficients, 7.2e-7 with these)"""
     mask, sigma = CYCLE_SETTINGS[setting]
-    kw = desc_kw(3, n, levels, {}, capi.MG_F64, **CYCLE_KINDS[kind])
-    u0, b = cycle_inputs(n)
+    n, levels, extra = CYCLE_GRIDS[grid]
+    kw = desc_kw(3, n, levels, extra, capi.MG_F64, **CYCLE_KINDS[kind])
+    u0, b = cycle_inputs((n, n, n))
     P = br.BCProblem(mask=mask, sigma=sigma, prec=prec, **{k: v for k, v in kw.items() if k != "dtype"})
     P.use_handle_coefs(coefs)
     return P.vcycle(P.as_prec(u0), P.as_prec(b), kw["coarse_maxit"])
 
 
 @DTYPES
-@pytest.mark.parametrize("setting", list(CYCLE_SETTINGS))
-@pytest.mark.parametrize("kind", list(CYCLE_KINDS))
-@pytest.mark.parametrize("n,levels", [(17, 3), (33, 4)])
-def test_one_cycle_against_long_double(n, levels, kind, setting, dtype):
+@pytest.mark.parametrize("grid,kind,setting", CYCLE_PARAMS)
+def test_one_cycle_against_long_double(grid, kind, setting, dtype):
     """mg_bc_cycle (V, W, F; red-black and Jacobi 6/7, V(2,2), 6 coarse sweeps) against the long-double reference cycle on the
     handle's level coefficients. Tolerance, as test_vc_gpu.py builds it: 4 x the largest difference between bc_ref run in the
-    working dtype and in long double on the same input -- computed here, from the reference alone."""
+    working dtype and in long double on the same input -- computed here, from the reference alone. sa65 (V red-black and V
+    Jacobi, the mixed mask): the tile on distinct axis coefficients and on nz != nx inside the driver. That difference on sa65,
+    from the reference alone on the CPU (max |u| = 4.5): V red-black fp64 8.3e-16, fp32 3.7e-07; V Jacobi fp64 6.8e-16, fp32
+    3.0e-07 -- under one eps_T x max |u|, as at 17 and 33: the rule stays about rounding on this hierarchy."""
     T = NP[dtype]
     mask, sigma = CYCLE_SETTINGS[setting]
-    u0, b = (a.astype(T) for a in cycle_inputs(n))
-    kw = desc_kw(3, n, levels, {}, dtype, **CYCLE_KINDS[kind])
+    n, levels, extra = CYCLE_GRIDS[grid]
+    u0, b = (a.astype(T) for a in cycle_inputs((n, n, n)))
+    kw = desc_kw(3, n, levels, extra, dtype, **CYCLE_KINDS[kind])
     with capi.Solver(capi.make_desc(**kw)) as s:
         s.set_shift(sigma); s.bc_set_faces(mask); s.set_solution(u0); s.set_rhs(b)
         coefs = tuple(s.level_coefficients(l) for l in range(levels))
-        u_T, u_LD = cycle_reference(n, levels, kind, setting, T, coefs), cycle_reference(n, levels, kind, setting, LD, coefs)
+        u_T, u_LD = cycle_reference(grid, kind, setting, T, coefs), cycle_reference(grid, kind, setting, LD, coefs)
         tol = 4 * float(abs(u_T.astype(LD) - u_LD).max())
         st = s.bc_cycle()
         got = s.get_solution().astype(LD)
         err = float(abs(got - u_LD).max())
-        print(f"n={n} {kind} {setting} {T.__name__}: |gpu - ld| = {err:.3e}, tolerance = {tol:.3e}")
+        print(f"{grid} {kind} {setting} {T.__name__}: |gpu - ld| = {err:.3e}, tolerance = {tol:.3e}")
         assert err <= tol
         assert np.array_equal(s.get_array(RHS, 0), b)
         visits = {capi.CYCLE_V: 1, capi.CYCLE_W: 2 ** (levels - 2), capi.CYCLE_F: levels - 1}[kw["cycle"]]

@@ -10,6 +10,7 @@ import pytest
 from multigrid_prj_amd import capi
 from tests import npref
 from tests import fas_ref as fr
+from tests import tile_cases as tc
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +29,11 @@ CASES = [
     (2, 17, 2, {}), (2, 130, 1, {}),
     (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}), (3, 17, 3, {"semi_xy": 1}),
 ]
-
-
-def case_id(c):
-    dim, n, levels, extra = c
-    return f"{dim}d{n}" + "".join("-" + k for k in extra)
+# ... on all of which the tile sees a cube with cx == cy == cz (the last two are plain). tests/tile_cases.py: a33, a65 put it on
+# pairwise distinct axis coefficients, sa65, s67, s129 on a level with nz != nx (sa65: both at once; s67: an even row, 34 x 34 x 67;
+# s129: the fp32 tile, level 1 only)
+CASES += tc.CASES
+case_id = tc.case_id
 
 
 def desc_kw(dim, n, levels, extra, dtype, **more):
@@ -61,13 +62,15 @@ def is_march(dim, shape, T):
 @DTYPES
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_cubic_kernels_bit_for_bit(case, dtype):
-    """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7) and one red-black sweep on levels 0 and 1, sigma 0 and
-    500, gamma 0.7 and -0.3, standard-normal data (den = cd + 3 G u^2 keeps its sign); where the marching tile takes the level
-    the plain form is run too (mg_fas_set_form) against the same numbers. The inputs come back unmodified."""
+    """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7) and one red-black sweep on the case's levels to check
+    (0 and 1; s129: 1), sigma 0 and 500, gamma 0.7 and -0.3, standard-normal data (den = cd + 3 G u^2 keeps its sign); where the
+    marching tile takes the level the plain form is run too (mg_fas_set_form) against the same numbers. The inputs come back
+    unmodified. The tile on distinct axis coefficients: a33, a65, sa65; on nz != nx: sa65, s67 (an even row), s129 (fp32)."""
     dim, n, levels, extra = case
     T = NP[dtype]
     rng = np.random.default_rng(100 * dim + n)
-    forms_seen = set()
+    check = tc.levels_to_check(case)
+    forms_seen = {l: set() for l in check}
     for omega in (1.0, 6.0 / 7.0):
         kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
         with capi.Solver(capi.make_desc(**kw)) as s:
@@ -77,8 +80,9 @@ def test_cubic_kernels_bit_for_bit(case, dtype):
                     s.fas_set_reaction(CUBIC, gamma)
                     assert s.fas_get_reaction() == (CUBIC, gamma)
                     P = problem_of(s, kw, T, fr.CUBIC, gamma, sigma)
-                    for l in range(min(levels, 2)):
+                    for l in check:
                         shape = s.level_shape(l)
+                        assert tuple(shape) == tc.level_shape(case, l)
                         u, b, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
                         jac_ref = P.jacobi(u, b, l)
                         assert jac_ref.dtype == T
@@ -89,7 +93,7 @@ def test_cubic_kernels_bit_for_bit(case, dtype):
                         march = is_march(dim, shape, T)
                         for form in ((0, 1) if march else (0,)):
                             s.fas_set_form(form)
-                            forms_seen.add("march" if march and form == 0 else "plain")
+                            forms_seen[l].add("march" if march and form == 0 else "plain")
                             tag = (l, sigma, omega, gamma, form)
                             s.set_array(RHS, l, b)
                             if first:
@@ -109,17 +113,17 @@ def test_cubic_kernels_bit_for_bit(case, dtype):
                             assert np.array_equal(got, jac_ref), (tag, int((got != jac_ref).sum()))
                             assert np.array_equal(s.get_array(RHS, l), b)
                         s.fas_set_form(0)
-    want = {"march", "plain"} if dim == 3 and fr.march_side(3, n, np.dtype(T).itemsize) else {"plain"}
-    assert forms_seen == want
+    assert forms_seen == {l: tc.want_forms(case, l, np.dtype(T).itemsize) for l in check}   # per level: a semi level is no cube
 
 
 # ---------------------------------------------------------------- 2. gamma = 0 is the existing entry points
 @DTYPES
 @pytest.mark.parametrize("kind", [CUBIC, EXP], ids=["cubic", "exp"])
-@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 65, 2, {}), (2, 130, 1, {})], ids=case_id)
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 65, 2, {}), (2, 130, 1, {}), tc.A65, tc.SA65], ids=case_id)
 def test_gamma_zero_equals_the_existing_entry_points(case, kind, dtype):
     """mg_fas_residual / mg_fas_smooth with gamma = 0 against mg_residual / mg_smooth on the same random arrays, bit for bit, with
-    and without a shift: num = b - s, den = cd, and the IEEE quotient is div_cd's"""
+    and without a shift: num = b - s, den = cd, and the IEEE quotient is div_cd's. a65 and sa65 pin the tile to
+    mg_jacobi_fast.hip's kernels on an operator with distinct axis coefficients (sa65: on a 33 x 33 x 65 level too)"""
     dim, n, levels, extra = case
     T = NP[dtype]
     kw = desc_kw(dim, n, levels, extra, dtype, omega=6.0 / 7.0)
@@ -149,12 +153,13 @@ def test_gamma_zero_equals_the_existing_entry_points(case, kind, dtype):
 
 # ---------------------------------------------------------------- 3. the exp kind
 @DTYPES
-@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 67, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)})],
-                         ids=case_id)
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 67, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}),
+                                  tc.A65, tc.SA65], ids=case_id)
 def test_exp_kernels_within_8_eps(case, dtype):
     """the same launches with g = exp(u), u uniform in [-2, 2], within 8 eps_T x magnitude: |b| + |A||u| + |G||g| for the residual,
     (|b| + |A - D||u| + |G|(|g| + |gp u|)) / |den| for the point solves. The device's exp is specified to 1 ulp and the
-    reference's is rounded once, so g differs by at most 1.5 ulp; every other operation is the same in the same order."""
+    reference's is rounded once, so g differs by at most 1.5 ulp; every other operation is the same in the same order. a65 and
+    sa65: the exp tile on distinct axis coefficients (an exchanged pair is an error of order 1, not of 8 eps) and on nz != nx."""
     dim, n, levels, extra = case
     T = NP[dtype]
     eps = float(np.finfo(T).eps)
@@ -297,6 +302,13 @@ CYCLE_KINDS = {
 CYCLE_REACTIONS = {"cubic": (CUBIC, 50.0, 0.0), "exp": (EXP, 20.0, 10.0)}   # kind, gamma, sigma: gamma g' > 0 on standard-normal data
 
 
+# (n, levels, extra) x kind x reaction; sa65 (tests/tile_cases.py): a V(2,2) cycle whose Jacobi sweeps and residuals go through
+# the tile inside the driver's dispatch on 65^3 and on 33 x 33 x 65, both with pairwise distinct axis coefficients
+CYCLE_GRIDS = {"17-3": (17, 3, {}), "35-2": (35, 2, {}), "sa65": tc.SA65[1:]}
+CYCLE_PARAMS = [pytest.param(g, kind, r, id=f"{g}-{kind}-{r}") for g in ("17-3", "35-2") for kind in CYCLE_KINDS for r in CYCLE_REACTIONS]
+CYCLE_PARAMS += [pytest.param("sa65", kind, "cubic", id=f"sa65-{kind}-cubic") for kind in ("v-rb", "v-jacobi")]
+
+
 @functools.lru_cache(maxsize=None)
 def cycle_inputs(n):
     """u0, b with float32 values: exact in both working dtypes, so the long-double reference is shared"""
@@ -305,10 +317,11 @@ def cycle_inputs(n):
 
 
 @functools.lru_cache(maxsize=None)
-def cycle_reference(n, levels, kind, reaction, prec, coefs):
+def cycle_reference(grid, kind, reaction, prec, coefs):
     """coefs: mg_level_coefficients of every level (doubles, shift included) -- the contract casts THOSE to T"""
     rk, gamma, sigma = CYCLE_REACTIONS[reaction]
-    kw = desc_kw(3, n, levels, {}, capi.MG_F64, **CYCLE_KINDS[kind])
+    n, levels, extra = CYCLE_GRIDS[grid]
+    kw = desc_kw(3, n, levels, extra, capi.MG_F64, **CYCLE_KINDS[kind])
     u0, b = cycle_inputs(n)
     P = fr.FASProblem(kind=rk, gamma=gamma, sigma=sigma, prec=prec, **{k: v for k, v in kw.items() if k != "dtype"})
     P.use_handle_coefs(coefs)
@@ -316,26 +329,28 @@ def cycle_reference(n, levels, kind, reaction, prec, coefs):
 
 
 @DTYPES
-@pytest.mark.parametrize("reaction", list(CYCLE_REACTIONS))
-@pytest.mark.parametrize("kind", list(CYCLE_KINDS))
-@pytest.mark.parametrize("n,levels", [(17, 3), (35, 2)])
-def test_one_cycle_against_long_double(n, levels, kind, reaction, dtype):
+@pytest.mark.parametrize("grid,kind,reaction", CYCLE_PARAMS)
+def test_one_cycle_against_long_double(grid, kind, reaction, dtype):
     """mg_fas_cycle (V, W, F; red-black and Jacobi 6/7, V(2,2), 6 coarse sweeps) against the long-double reference cycle on the
     handle's level coefficients. The GPU's distance to it may be at most 4 x the distance of fas_ref run in the working dtype:
-    both round the same arithmetic; the factor covers summation-order differences in the prolongation and the norms."""
+    both round the same arithmetic; the factor covers summation-order differences in the prolongation and the norms. sa65 (V
+    red-black and V Jacobi, cubic): the tile on distinct axis coefficients and on nz != nx inside the driver. fas_ref's
+    distance on sa65, from the reference alone on the CPU (max |u| = 4.5): V red-black fp64 4.3e-16, fp32 3.0e-07; V Jacobi fp64
+    3.5e-16, fp32 2.3e-07 -- about half an eps_T x max |u|: the rule stays about rounding on this hierarchy."""
     T = NP[dtype]
     rk, gamma, sigma = CYCLE_REACTIONS[reaction]
+    n, levels, extra = CYCLE_GRIDS[grid]
     u0, b = (a.astype(T) for a in cycle_inputs(n))
-    kw = desc_kw(3, n, levels, {}, dtype, **CYCLE_KINDS[kind])
+    kw = desc_kw(3, n, levels, extra, dtype, **CYCLE_KINDS[kind])
     with capi.Solver(capi.make_desc(**kw)) as s:
         s.set_shift(sigma); s.fas_set_reaction(rk, gamma); s.set_solution(u0); s.set_rhs(b)
         coefs = tuple(s.level_coefficients(l) for l in range(levels))
-        u_T, u_LD = cycle_reference(n, levels, kind, reaction, T, coefs), cycle_reference(n, levels, kind, reaction, LD, coefs)
+        u_T, u_LD = cycle_reference(grid, kind, reaction, T, coefs), cycle_reference(grid, kind, reaction, LD, coefs)
         tol = 4 * float(abs(u_T.astype(LD) - u_LD).max())
         st = s.fas_cycle()
         got = s.get_solution().astype(LD)
         err = float(abs(got - u_LD).max())
-        print(f"n={n} {kind} {reaction} {T.__name__}: |gpu - ld| = {err:.3e}, |fas_ref in T - ld| = {tol / 4:.3e}")
+        print(f"{grid} {kind} {reaction} {T.__name__}: |gpu - ld| = {err:.3e}, |fas_ref in T - ld| = {tol / 4:.3e}")
         assert err <= tol
         assert np.array_equal(s.get_array(RHS, 0), b)
         visits = {capi.CYCLE_V: 1, capi.CYCLE_W: 2 ** (levels - 2), capi.CYCLE_F: levels - 1}[kw["cycle"]]

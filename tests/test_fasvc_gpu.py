@@ -16,6 +16,7 @@ from tests import fasvc_ref as fv
 from tests import npref
 from tests import step_ref as sr
 from tests import storage_table as st
+from tests import tile_cases as tc
 from tests.test_fas_gpu import TRANSITIONS, refused
 from tests.test_storage_gpu import Ctx, name as raw_name, snapshot
 from tests.test_vcn_gpu import CASES, case_id, desc_kw, mixed
@@ -118,13 +119,16 @@ def test_cubic_kernels_bit_for_bit(case, dtype):
     """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7) and one red-black sweep on levels 0 and 1, sigma 0 and
     500, gamma 0.7 and -0.3, masks 0 / all faces / mixed (n = 9: every single face too), standard-normal data, a uniform in
     [0.5, 2]; where the marching tile takes the level the plain form is run too (mg_fas_set_form) against the same numbers. The
-    inputs come back unmodified; at 35 and 67 the padding columns and ghost planes read +0 after every flagged call."""
+    inputs come back unmodified; at 35 and 67 the padding columns and ghost planes read +0 after every flagged call. The levels
+    are the case's levels to check (tests/tile_cases.py; 0 and 1, s129: 1). The tile on distinct axis coefficients: a33, a65,
+    sa65; on nz != nx: sa65, s67 (an even row), s129 (fp32)."""
     dim, n, levels, extra = case
     T = NP[dtype]
     rng = np.random.default_rng(100 * dim + n)
     masks = [0, all_faces(dim), mixed(dim)] + ([1 << k for k in range(2 * dim)] if n == 9 else [])
     layout = n in (35, 67)
-    forms_seen = set()
+    check = tc.levels_to_check(case)
+    forms_seen = {l: set() for l in check}
     for omega in (1.0, 6.0 / 7.0):
         kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
         with capi.Solver(capi.make_desc(**kw)) as s:
@@ -137,8 +141,9 @@ def test_cubic_kernels_bit_for_bit(case, dtype):
                     for mask in masks:
                         s.vc_set_faces(mask)
                         P = problem_of(s, kw, T, fr.CUBIC, gamma, mask, sigma, a0)
-                        for l in range(min(levels, 2)):
+                        for l in check:
                             shape = s.level_shape(l)
+                            assert tuple(shape) == tc.level_shape(case, l)
                             u, b, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
                             jac_ref = P.jacobi(u, b, l)
                             assert jac_ref.dtype == T
@@ -149,7 +154,7 @@ def test_cubic_kernels_bit_for_bit(case, dtype):
                             march = is_march(dim, shape, T)
                             for form in ((0, 1) if march else (0,)):
                                 s.fas_set_form(form)
-                                forms_seen.add("march" if march and form == 0 else "plain")
+                                forms_seen[l].add("march" if march and form == 0 else "plain")
                                 tag = (l, sigma, omega, gamma, mask, form)
                                 chk = (lambda: outside_is_zero(s, case, dtype, tag)) if layout else (lambda: None)
                                 s.set_array(RHS, l, b)
@@ -172,17 +177,17 @@ def test_cubic_kernels_bit_for_bit(case, dtype):
                                 assert np.array_equal(s.get_array(RHS, l), b)
                                 assert np.array_equal(s.vc_get_coefficient(l), P.a[l])
                             s.fas_set_form(0)
-    want = {"march", "plain"} if dim == 3 and fr.march_side(3, n, np.dtype(T).itemsize) else {"plain"}
-    assert forms_seen == want
+    assert forms_seen == {l: tc.want_forms(case, l, np.dtype(T).itemsize) for l in check}   # per level: a semi level is no cube
 
 
 # ---------------------------------------------------------------- 3. the exp kind
 @DTYPES
-@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 67, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)})],
-                         ids=case_id)
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 35, 2, {}), (3, 67, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}),
+                                  tc.A65, tc.SA65], ids=case_id)
 def test_exp_kernels_within_8_eps(case, dtype):
     """the same launches with g = exp(u), u uniform in [-2, 2], masks 0, all faces and mixed, within 8 eps_T x magnitude
-    (fasvc_ref's residual_mag / point_solve_mag). The device's exp is specified to 1 ulp and the reference's is rounded once."""
+    (fasvc_ref's residual_mag / point_solve_mag). The device's exp is specified to 1 ulp and the reference's is rounded once. a65
+    and sa65: the exp tile on distinct axis coefficients (an exchanged pair is an error of order 1, not of 8 eps) and on nz != nx."""
     dim, n, levels, extra = case
     T = NP[dtype]
     eps = float(np.finfo(T).eps)
@@ -379,6 +384,14 @@ CYCLE_KINDS = {
 CYCLE_REACTIONS = {"cubic": (CUBIC, 50.0, 0.0), "exp": (EXP, 20.0, 10.0)}   # kind, gamma, sigma: gamma g' > 0 on standard-normal data
 
 
+# (n, levels, extra) x kind x reaction x mask; sa65 (tests/tile_cases.py): a V(2,2) cycle whose Jacobi sweeps and residuals go through
+# the tile inside the driver's dispatch on 65^3 and on 33 x 33 x 65, both with pairwise distinct axis coefficients
+CYCLE_GRIDS = {"17-3": (17, 3, {}), "35-2": (35, 2, {}), "sa65": tc.SA65[1:]}
+CYCLE_PARAMS = [pytest.param(g, kind, r, w, id=f"{g}-{kind}-{r}-{w}") for g in ("17-3", "35-2") for kind in CYCLE_KINDS for r in CYCLE_REACTIONS
+                for w in ("all", "mixed")]
+CYCLE_PARAMS += [pytest.param("sa65", kind, "cubic", "mixed", id=f"sa65-{kind}-cubic-mixed") for kind in ("v-rb", "v-jacobi")]
+
+
 @functools.lru_cache(maxsize=None)
 def cycle_inputs(n):
     """u0, b, a with float32 values: exact in both working dtypes, so the long-double reference is shared"""
@@ -388,40 +401,42 @@ def cycle_inputs(n):
 
 
 @functools.lru_cache(maxsize=None)
-def cycle_reference(n, levels, kind, reaction, mask, prec, coefs):
+def cycle_reference(grid, kind, reaction, mask, prec, coefs):
     """coefs: mg_level_coefficients of every level (doubles) -- the contract casts THOSE to T. The coefficient hierarchy of the
     long-double reference is built in long double from the same level-0 values."""
     rk, gamma, sigma = CYCLE_REACTIONS[reaction]
-    kw = desc_kw(3, n, levels, {}, capi.MG_F64, **CYCLE_KINDS[kind])
+    n, levels, extra = CYCLE_GRIDS[grid]
+    kw = desc_kw(3, n, levels, extra, capi.MG_F64, **CYCLE_KINDS[kind])
     u0, b, a0 = cycle_inputs(n)
     P = problem_of(None, kw, prec, rk, gamma, mask, sigma, a0, coefs)
     return P.vcycle(P.as_prec(u0), P.as_prec(b), kw["coarse_maxit"])
 
 
 @DTYPES
-@pytest.mark.parametrize("which", ["all", "mixed"])
-@pytest.mark.parametrize("reaction", list(CYCLE_REACTIONS))
-@pytest.mark.parametrize("kind", list(CYCLE_KINDS))
-@pytest.mark.parametrize("n,levels", [(17, 3), (35, 2)])
-def test_one_cycle_against_long_double(n, levels, kind, reaction, which, dtype):
+@pytest.mark.parametrize("grid,kind,reaction,which", CYCLE_PARAMS)
+def test_one_cycle_against_long_double(grid, kind, reaction, which, dtype):
     """mg_fas_cycle with the flag (V, W, F with red-black, V with Jacobi 6/7; V(2,2), 6 coarse sweeps) against the long-double
     reference cycle on the handle's level coefficients. The GPU's distance to it may be at most 4 x the distance of fasvc_ref run
-    in the working dtype: both round the same arithmetic (tests/test_fasn_gpu.py's rule)."""
+    in the working dtype: both round the same arithmetic (tests/test_fasn_gpu.py's rule). sa65 (V red-black and V Jacobi, cubic, the
+    mixed mask): the tile on distinct axis coefficients and on nz != nx inside the driver. fasvc_ref's distance on sa65, from the
+    reference alone on the CPU (max |u| = 4.5): V red-black fp64 6.1e-16, fp32 4.1e-07; V Jacobi fp64 5.3e-16, fp32 4.1e-07 -- under
+    one eps_T x max |u|: the rule stays about rounding on this hierarchy."""
     T = NP[dtype]
     rk, gamma, sigma = CYCLE_REACTIONS[reaction]
+    n, levels, extra = CYCLE_GRIDS[grid]
     mask = 63 if which == "all" else mixed(3)
     u0, b, a0 = (x.astype(T) for x in cycle_inputs(n))
-    kw = desc_kw(3, n, levels, {}, dtype, **CYCLE_KINDS[kind])
+    kw = desc_kw(3, n, levels, extra, dtype, **CYCLE_KINDS[kind])
     with capi.Solver(capi.make_desc(**kw)) as s:
         s.set_shift(sigma); s.vc_set_faces(mask); s.vc_set_coefficient(a0); s.fas_set_reaction(rk | ON_COEF, gamma)
         s.set_solution(u0); s.set_rhs(b)
         coefs = tuple(s.level_coefficients(l) for l in range(levels))
-        u_T, u_LD = (cycle_reference(n, levels, kind, reaction, mask, p, coefs) for p in (T, LD))
+        u_T, u_LD = (cycle_reference(grid, kind, reaction, mask, p, coefs) for p in (T, LD))
         tol = 4 * float(abs(u_T.astype(LD) - u_LD).max())
         st_ = s.fas_cycle()
         got = s.get_solution().astype(LD)
         err = float(abs(got - u_LD).max())
-        print(f"n={n} {kind} {reaction} {which} {T.__name__}: |gpu - ld| = {err:.3e}, |fasvc_ref in T - ld| = {tol / 4:.3e}")
+        print(f"{grid} {kind} {reaction} {which} {T.__name__}: |gpu - ld| = {err:.3e}, |fasvc_ref in T - ld| = {tol / 4:.3e}")
         assert err <= tol
         assert np.array_equal(s.get_array(RHS, 0), b)
         visits = {capi.CYCLE_V: 1, capi.CYCLE_W: 2 ** (levels - 2), capi.CYCLE_F: levels - 1}[kw["cycle"]]

@@ -18,6 +18,7 @@ import pytest
 from multigrid_prj_amd import capi
 from tests import mixedvc_ref as mr
 from tests import npref
+from tests import tile_cases as tc
 from tests import vcn_ref as vn
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +45,8 @@ def b64_of(s):
 # ---------------------------------------------------------------- 1. the kernels, bit for bit
 # 2-D (always plain) 17 and 97; 3-D 17: plain only; 33: the smallest tile, exactly 16 fp64 vectors plus the odd column; 65; 129: more
 # than one block along x (65 vectors: the second block holds the last full vector and writes the tail lines)
-KSHAPES = [(2, 17), (2, 97), (3, 17), (3, 33), (3, 65), (3, 129)]
+# (dim, n, extra); the anisotropic 33 and 65 (tests/tile_cases.py's ANISO): the fused fp64 tile with pairwise distinct axis weights
+KSHAPES = [(2, 17, {}), (2, 97, {}), (3, 17, {}), (3, 33, {}), (3, 65, {}), (3, 129, {}), (3, 33, {"aniso": tc.ANISO}), (3, 65, {"aniso": tc.ANISO})]
 
 
 def masks(dim):
@@ -52,14 +54,15 @@ def masks(dim):
 
 
 @pytest.mark.parametrize("mi", [0, 1, 2], ids=["mask0", "all-neumann", "mixed"])
-@pytest.mark.parametrize("dim,n", KSHAPES)
-def test_kernels_bit_for_bit(dim, n, mi):
+@pytest.mark.parametrize("dim,n,extra", KSHAPES, ids=[f"{d}-{n}" + "".join("-" + k for k in e) for d, n, e in KSHAPES])
+def test_kernels_bit_for_bit(dim, n, extra, mi):
     """r32 and u64' equal the numpy contract, sum r^2 a long-double sum to rel 1e-13, for the first residual and the fused
     correction + residual (a power-of-two scale_in, then one that is none), shift 0 and 10, both forms where the tile takes the
-    shape; u64 (by the residual kernel), b64, e32 and the coefficient are unchanged; e on Dirichlet nodes is not looked at"""
+    shape; u64 (by the residual kernel), b64, e32 and the coefficient are unchanged; e on Dirichlet nodes is not looked at. The
+    3-33-aniso and 3-65-aniso shapes run the tile with pairwise distinct axis weights"""
     mask = masks(dim)[mi]
     rng = np.random.default_rng(100 * n + 10 * dim + mi)
-    kw = dict(dim=dim, n=n, levels=2, length=1.0, alpha=1.3, smoother=capi.SMOOTH_RBGS, cycle=capi.CYCLE_V)
+    kw = dict(dim=dim, n=n, levels=2, length=1.0, alpha=1.3, smoother=capi.SMOOTH_RBGS, cycle=capi.CYCLE_V, **extra)
     forms = (0, 1) if vn.march_ok(dim, n, n, n if dim == 3 else 1, 8) else (0,)
     assert (len(forms) == 2) == (dim == 3 and n >= 33)
     with capi.Solver(capi.make_desc(dtype=capi.MG_F32, **kw)) as s:

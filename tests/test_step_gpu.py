@@ -14,6 +14,7 @@ from tests import fas_ref as fr
 from tests import heat_ref as hr
 from tests import npref
 from tests import step_ref as sr
+from tests import tile_cases as tc
 from tests import vc_ref as vr
 from tests.test_independent_reference import check_max, cycle_bound, sweep_scale
 
@@ -28,14 +29,18 @@ MIXED = capi.FACE_XLO | capi.FACE_YHI | capi.FACE_ZLO | capi.FACE_ZHI   # in 2-D
 
 # the shapes of tests/test_vc_gpu.py's CASES: 9, 17 plain; 33, 35 tile in fp64 (35: odd last column, not 2^k + 1), 34 an even
 # row; 65, 67 tile in both dtypes (67: a partial last vector in fp32); 2-D always plain
-SHAPES = [(3, 9, 2), (3, 17, 2), (3, 33, 2), (3, 35, 2), (3, 34, 1), (3, 65, 2), (3, 67, 2), (2, 17, 2), (2, 130, 1)]
+SHAPES = [(3, 9, 2, {}), (3, 17, 2, {}), (3, 33, 2, {}), (3, 35, 2, {}), (3, 34, 1, {}), (3, 65, 2, {}), (3, 67, 2, {}), (2, 17, 2, {}),
+          (2, 130, 1, {})]
+# ... all with cx == cy == cz. tests/tile_cases.py's a33 (fp64) and a65 (both dtypes) put the OP_STEP tile, its no-neighbour
+# theta == 1 form included, on pairwise distinct axis coefficients (the right-hand side is level 0 only: no semi-coarsened case)
+SHAPES += [tc.A33, tc.A65]
 # family settings: name -> (family, its parameter)
 FAMS = {"vc": ("vc", None), "bc0": ("bc", 0), "bc-all": ("bc", 63), "bc-mixed": ("bc", MIXED), "cubic": ("fas", (fr.CUBIC, 50.0)),
         "exp": ("fas", (fr.EXP, 20.0))}
 
 
 def shape_id(c):
-    return f"{c[0]}d{c[1]}"
+    return tc.case_id(c) if len(c) == 4 and c[3] else f"{c[0]}d{c[1]}"
 
 
 def desc_kw(dim, n, levels, dtype, **more):
@@ -96,11 +101,12 @@ def is_tile(dim, n, T):
 @pytest.mark.parametrize("case", SHAPES, ids=shape_id)
 def test_rhs_kernel_bit_for_bit(case, dtype):
     """every family, theta 1 / 0.5 / 0.75, with and without a source, tile and plain form, a handle shift that must be
-    ignored and kept; cubic, vc and bc bit for bit, exp within 8 eps x magnitude (the device's exp is specified to 1 ulp)"""
-    dim, n, levels = case
+    ignored and kept; cubic, vc and bc bit for bit, exp within 8 eps x magnitude (the device's exp is specified to 1 ulp). a33
+    and a65: the tile with pairwise distinct axis coefficients, in every family setting"""
+    dim, n, levels, extra = case
     T = NP[dtype]
     eps = float(np.finfo(T).eps)
-    kw = desc_kw(dim, n, levels, dtype)
+    kw = desc_kw(dim, n, levels, dtype, **extra)
     rng = np.random.default_rng(1000 * dim + n)
     forms_seen, worst_exp = set(), 0.0
     with capi.Solver(capi.make_desc(**kw)) as s:

@@ -116,11 +116,33 @@ def test_family_rows_run_every_mask_form_and_reaction():
 
 
 def test_march_gate_is_mg_geom_h():
+    from tests import tile_cases as tc
     from tests import vcn_ref
     for n in (9, 17, 33, 34, 35, 65, 67, 129):
         for dt, es in ((st.F64, 8), (st.F32, 4)):
             assert st.march(st.C(3, n, 1), dt) == vcn_ref.march_ok(3, n, n, n, es)
             assert not st.march(st.C(2, n, 1), dt)
+    # every case of FAM3, the non-isotropic ones included, has a cubic level 0, which is what st.march is about
+    assert {c.n for c in st.FAM3} == {9, 17, 33, 34, 35, 65, 67}
+    for c in st.FAM3:
+        case = (c.dim, c.n, c.levels, c.extra)
+        assert tc.level_shape(case, 0) == (c.n, c.n, c.n)
+        for dt, es in ((st.F64, 8), (st.F32, 4)):
+            assert st.march(c, dt) == tc.takes_tile(case, 0, es) == vcn_ref.march_ok(3, c.n, c.n, c.n, es), (c.id, es)
+
+
+def test_family_cases_reach_a_non_cubic_tile_level_and_distinct_coefficients():
+    """FAM3's two non-isotropic cases are tests/tile_cases.py's s67 and a65: the family cycle rows run the fp64 tile on
+    34 x 34 x 67 (an even row, nz != nx), and every family row runs it on pairwise distinct axis coefficients"""
+    from tests import tile_cases as tc
+    extra = [c for c in st.FAM3 if c.extra]
+    assert [(c.dim, c.n, c.levels, c.extra) for c in extra] == [tc.S67, tc.A65]
+    assert [c.id for c in extra] == ["3d67L2-semi_xy1", "3d65L2-aniso1.0_2.5_0.3"]
+    assert all(re.fullmatch(r"[A-Za-z0-9_.\-]+", c.id) for c in st.FAM)   # a valid pytest id without escapes
+    assert tc.level_shape(tc.S67, 1) == (67, 34, 34) and tc.takes_tile(tc.S67, 1, 8) and not tc.takes_tile(tc.S67, 1, 4)
+    assert len(set(tc.level_coefs(tc.A65, 0))) == 3 and tc.takes_tile(tc.A65, 0, 8) and tc.takes_tile(tc.A65, 0, 4)
+    for fam in ("vc", "bc", "fas"):
+        assert all(c in st.ROW[f"{fam}-cycle"].cases and c in st.ROW[f"{fam}-residual"].cases for c in extra)
 
 
 # ---------------------------------------------------------------- the C ABI of the window

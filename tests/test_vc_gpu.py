@@ -10,6 +10,7 @@ import torch
 
 from multigrid_prj_amd import capi
 from tests import npref
+from tests import tile_cases as tc
 from tests import vc_ref as vr
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +28,11 @@ CASES = [
     (2, 17, 2, {}), (2, 130, 1, {}),
     (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}), (3, 17, 3, {"semi_xy": 1}),
 ]
-
-
-def case_id(c):
-    dim, n, levels, extra = c
-    return f"{dim}d{n}" + "".join("-" + k for k in extra)
+# ... on all of which the tile sees a cube with wx == wy == wz (the last two are plain). tests/tile_cases.py: a33, a65 put it on
+# pairwise distinct axis coefficients, sa65, s67, s129 on a level with nz != nx (sa65: both at once; s67: an even row, 34 x 34 x 67;
+# s129: the fp32 tile, level 1 only)
+CASES += tc.CASES
+case_id = tc.case_id
 
 
 def desc_kw(dim, n, levels, extra, dtype, **more):
@@ -60,12 +61,15 @@ def sumsq(r):
 @DTYPES
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_kernels_bit_for_bit(case, dtype):
-    """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7) and one red-black sweep on levels 0 and 1, sigma 0
-    and 500; where the marching tile takes the level the plain form is run too (mg_vc_set_form) against the same numbers"""
+    """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7) and one red-black sweep on the case's levels to check
+    (0 and 1; s129: 1), sigma 0 and 500; where the marching tile takes the level the plain form is run too (mg_vc_set_form)
+    against the same numbers. The tile on distinct axis coefficients: a33, a65, sa65; on nz != nx: sa65, s67 (an even row), s129
+    (fp32)."""
     dim, n, levels, extra = case
     T = NP[dtype]
     rng = np.random.default_rng(100 * dim + n)
-    forms_seen = set()
+    check = tc.levels_to_check(case)
+    forms_seen = {l: set() for l in check}
     for omega in (1.0, 6.0 / 7.0):
         kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
         with capi.Solver(capi.make_desc(**kw)) as s:
@@ -74,15 +78,16 @@ def test_kernels_bit_for_bit(case, dtype):
                 s.set_shift(sigma)
                 P = problem_of(s, kw, T, sigma)
                 P.a = [s.vc_get_coefficient(l) for l in range(levels)]
-                for l in range(min(levels, 2)):
+                for l in check:
                     shape = s.level_shape(l)
+                    assert tuple(shape) == tc.level_shape(case, l)
                     u, b, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
                     r_ref, jac_ref, rb_ref = P.residual(u, b, l), P.jacobi(u, b, l), P.rbgs(u, b, l)
                     assert r_ref.dtype == T and jac_ref.dtype == T and rb_ref.dtype == T
                     march = dim == 3 and vr.march_side(3, shape[-1], np.dtype(T).itemsize) and min(shape) >= 7
                     for form in ((0, 1) if march else (0,)):
                         s.vc_set_form(form)
-                        forms_seen.add("march" if march and form == 0 else "plain")
+                        forms_seen[l].add("march" if march and form == 0 else "plain")
                         tag = (l, sigma, omega, form)
                         s.set_array(E, l, u); s.set_array(RHS, l, b); s.set_array(TMP, l, other)   # RES exists on level 0 only
                         ss = s.vc_residual(l, E, RHS, TMP)
@@ -101,8 +106,7 @@ def test_kernels_bit_for_bit(case, dtype):
                         assert np.array_equal(s.get_array(RHS, l), b)
                         assert np.array_equal(s.vc_get_coefficient(l), P.a[l])
                     s.vc_set_form(0)
-    want = {"march", "plain"} if dim == 3 and vr.march_side(3, n, np.dtype(T).itemsize) else {"plain"}
-    assert forms_seen == want
+    assert forms_seen == {l: tc.want_forms(case, l, np.dtype(T).itemsize) for l in check}   # per level: a semi level is no cube
 
 
 @DTYPES
@@ -171,11 +175,12 @@ def test_device_set_equals_host_set(src, dtype):
 
 # ---------------------------------------------------------------- 3. a == 1 is the constant operator
 @DTYPES
-@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 33, 2, {}), (3, 65, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)})],
-                         ids=case_id)
+@pytest.mark.parametrize("case", [(3, 17, 2, {}), (3, 33, 2, {}), (3, 65, 2, {}), (2, 130, 1, {}), (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}),
+                                  tc.A65, tc.SA65], ids=case_id)
 def test_unit_coefficient_agrees_with_the_constant_kernels(case, dtype):
     """vc_residual / one vc_smooth sweep against mg_residual / mg_smooth within 8 eps_T of npref's rounding magnitudes
-    (apply_A(absolute=True), point_solve_mag): what tests/test_independent_reference.py holds the constant kernels to"""
+    (apply_A(absolute=True), point_solve_mag): what tests/test_independent_reference.py holds the constant kernels to. a65 and
+    sa65: the tile against the constant kernels with distinct axis coefficients (sa65: on a 33 x 33 x 65 level too)"""
     dim, n, levels, extra = case
     T = NP[dtype]
     eps = float(np.finfo(T).eps)
@@ -249,13 +254,20 @@ def test_coarse_solve_to_tolerance(dim, n, smoother, omega, dtype):
 
 # ---------------------------------------------------------------- 5. one cycle
 CYCLE_KINDS = {"v22-rb": dict(cycle=capi.CYCLE_V, smoother=RB, nu_pre=2, nu_post=2),
-               "w11-jacobi": dict(cycle=capi.CYCLE_W, smoother=JAC, omega=6.0 / 7.0, nu_pre=1, nu_post=1)}
+               "w11-jacobi": dict(cycle=capi.CYCLE_W, smoother=JAC, omega=6.0 / 7.0, nu_pre=1, nu_post=1),
+               "v22-jacobi": dict(cycle=capi.CYCLE_V, smoother=JAC, omega=6.0 / 7.0, nu_pre=2, nu_post=2)}
+# (n, levels, extra) x kind; sa65 (tests/tile_cases.py): V(2,2) cycles whose Jacobi sweeps and residuals go through the tile inside
+# the driver's dispatch on 65^3 and on 33 x 33 x 65, both with pairwise distinct axis weights
+CYCLE_GRIDS = {"17-3": (17, 3, {}), "33-4": (33, 4, {}), "sa65": tc.SA65[1:]}
+CYCLE_PARAMS = [pytest.param(g, kind, id=f"{g}-{kind}") for g in ("17-3", "33-4") for kind in ("v22-rb", "w11-jacobi")]
+CYCLE_PARAMS += [pytest.param("sa65", kind, id=f"sa65-{kind}") for kind in ("v22-rb", "v22-jacobi")]
 
 
 @functools.lru_cache(maxsize=None)
-def cycle_references(n, levels, kind, dtype):
+def cycle_references(grid, kind, dtype):
     """one cycle from the same u, b, a by vc_ref in the working dtype and in long double -> (u_T, u_LD, the inputs)"""
-    kw = desc_kw(3, n, levels, {}, dtype, **CYCLE_KINDS[kind])
+    n, levels, extra = CYCLE_GRIDS[grid]
+    kw = desc_kw(3, n, levels, extra, dtype, **CYCLE_KINDS[kind])
     T = NP[dtype]
     rng = np.random.default_rng(n)
     shape = (n, n, n)
@@ -269,22 +281,24 @@ def cycle_references(n, levels, kind, dtype):
 
 
 @DTYPES
-@pytest.mark.parametrize("kind", list(CYCLE_KINDS))
-@pytest.mark.parametrize("n,levels", [(17, 3), (33, 4)])
-def test_one_cycle_against_long_double(n, levels, kind, dtype):
+@pytest.mark.parametrize("grid,kind", CYCLE_PARAMS)
+def test_one_cycle_against_long_double(grid, kind, dtype):
     """mg_vc_cycle against the long-double reference cycle. Tolerance: 4 x the largest difference between vc_ref run in the
     working dtype and in long double on the same input (computed here, from the reference alone). That difference, measured
     on the CPU (max norm; u, b standard normal, a = exp(N(0,1))):
         n = 17  V(2,2) red-black   fp64 4.2e-16   fp32 2.2e-07      W(1,1) Jacobi 6/7   fp64 6.9e-16   fp32 2.4e-07
-        n = 33  V(2,2) red-black   fp64 1.1e-15   fp32 4.0e-07      W(1,1) Jacobi 6/7   fp64 7.5e-16   fp32 4.0e-07"""
-    u_T, u_LD, (a0, u0, b), kw = cycle_references(n, levels, kind, dtype)
+        n = 33  V(2,2) red-black   fp64 1.1e-15   fp32 4.0e-07      W(1,1) Jacobi 6/7   fp64 7.5e-16   fp32 4.0e-07
+        sa65    V(2,2) red-black   fp64 1.5e-15   fp32 7.1e-07      V(2,2) Jacobi 6/7   fp64 1.4e-15   fp32 6.7e-07   (max |u| 4.5)
+    sa65 (65^3 over 33 x 33 x 65, aniso (1, 2.5, 0.3)): the tile on distinct axis weights and on nz != nx inside the driver."""
+    n, levels, _ = CYCLE_GRIDS[grid]
+    u_T, u_LD, (a0, u0, b), kw = cycle_references(grid, kind, dtype)
     tol = 4 * float(abs(u_T.astype(LD) - u_LD).max())
     with capi.Solver(capi.make_desc(**kw)) as s:
         s.vc_set_coefficient(a0); s.set_solution(u0); s.set_rhs(b)
         st = s.vc_cycle()
         got = s.get_solution().astype(LD)
         err = float(abs(got - u_LD).max())
-        print(f"n={n} {kind} {NP[dtype].__name__}: |gpu - ld| = {err:.3e}, tolerance = {tol:.3e}")
+        print(f"{grid} {kind} {NP[dtype].__name__}: |gpu - ld| = {err:.3e}, tolerance = {tol:.3e}")
         assert err <= tol
         assert np.array_equal(s.get_array(RHS, 0), b)
         visits = 1 if kw["cycle"] == capi.CYCLE_V else 2 ** (levels - 2)

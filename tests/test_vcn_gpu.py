@@ -12,6 +12,7 @@ import pytest
 from multigrid_prj_amd import capi
 from tests import heat_ref as hr
 from tests import npref
+from tests import tile_cases as tc
 from tests import vc_ref as vr
 from tests import vcn_ref as vn
 
@@ -31,11 +32,11 @@ CASES = [
     (2, 17, 2, {}), (2, 130, 1, {}),
     (3, 17, 2, {"aniso": (1.0, 30.0, 0.05)}), (3, 17, 3, {"semi_xy": 1}),
 ]
-
-
-def case_id(c):
-    dim, n, levels, extra = c
-    return f"{dim}d{n}" + "".join("-" + k for k in extra)
+# ... on all of which the tile sees a cube with wx == wy == wz (the last two are plain). tests/tile_cases.py: a33, a65 put it on
+# pairwise distinct axis coefficients, sa65, s67, s129 on a level with nz != nx (sa65: both at once; s67: an even row, 34 x 34 x 67;
+# s129: the fp32 tile, level 1 only)
+CASES += tc.CASES
+case_id = tc.case_id
 
 
 def mixed(dim):
@@ -73,14 +74,16 @@ def sumsq(r):
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_kernels_bit_for_bit(case, dtype):
     """residual (saved and norm only), one Jacobi sweep (omega 1 and 6/7), one red-black sweep, mg_vc_restrict (both kinds) and the
-    level-1 coefficient on levels 0 and 1, sigma 0 and 500, masks 0 / all faces / mixed (n = 9: every single face too); where
-    the marching tile takes the level the plain form is run too (mg_vc_set_form) against the same numbers. The inputs come
-    back unmodified."""
+    level-1 coefficient on the case's levels to check (0 and 1; s129: 1), sigma 0 and 500, masks 0 / all faces / mixed (n = 9:
+    every single face too); where the marching tile takes the level the plain form is run too (mg_vc_set_form) against the same
+    numbers. The inputs come back unmodified. The mirrored tile on distinct axis coefficients: a33, a65, sa65; on nz != nx (the
+    z-face test against another extent than x's): sa65, s67 (an even row), s129 (fp32)."""
     dim, n, levels, extra = case
     T = NP[dtype]
     rng = np.random.default_rng(100 * dim + n)
     masks = [0, vn.all_faces(dim), mixed(dim)] + ([1 << k for k in range(2 * dim)] if n == 9 else [])
-    forms_seen = set()
+    check = tc.levels_to_check(case)
+    forms_seen = {l: set() for l in check}
     for omega in (1.0, 6.0 / 7.0):
         kw = desc_kw(dim, n, levels, extra, dtype, omega=omega)
         with capi.Solver(capi.make_desc(**kw)) as s:
@@ -96,8 +99,9 @@ def test_kernels_bit_for_bit(case, dtype):
                     for l in range(levels):   # the mirrored full weighting of the coefficient
                         got = s.vc_get_coefficient(l)
                         assert np.array_equal(got, P.a[l]), (l, mask, int((got != P.a[l]).sum()))
-                    for l in range(min(levels, 2)):
+                    for l in check:
                         shape = s.level_shape(l)
+                        assert tuple(shape) == tc.level_shape(case, l)
                         u, b, other = (rng.standard_normal(shape).astype(T) for _ in range(3))
                         jac_ref = P.jacobi(u, b, l)
                         assert jac_ref.dtype == T
@@ -108,7 +112,7 @@ def test_kernels_bit_for_bit(case, dtype):
                         march = dim == 3 and vn.march_ok(3, shape[2], shape[1], shape[0], np.dtype(T).itemsize)
                         for form in ((0, 1) if march else (0,)):
                             s.vc_set_form(form)
-                            forms_seen.add("march" if march and form == 0 else "plain")
+                            forms_seen[l].add("march" if march and form == 0 else "plain")
                             tag = (l, sigma, omega, mask, form)
                             s.set_array(RHS, l, b)
                             if first:
@@ -138,8 +142,7 @@ def test_kernels_bit_for_bit(case, dtype):
                                 got = s.get_array(TMP, l + 1)
                                 assert np.array_equal(got, ref), (l, mask, kind, int((got != ref).sum()))
                             assert np.array_equal(s.get_array(E, l), u)
-    want = {"march", "plain"} if dim == 3 and vn.march_side(3, n, np.dtype(T).itemsize) else {"plain"}
-    assert forms_seen == want
+    assert forms_seen == {l: tc.want_forms(case, l, np.dtype(T).itemsize) for l in check}   # per level: a semi level is no cube
 
 
 # ---------------------------------------------------------------- 2. back to mask 0
@@ -239,6 +242,13 @@ CYCLE_KINDS = {
 CYCLE_SETTINGS = {"mixed": (vn.MIXED, 0.0), "all": (63, 10.0)}
 
 
+# (n, levels, extra) x kind x setting; sa65 (tests/tile_cases.py): a V(2,2) cycle whose Jacobi sweeps and residuals go through
+# the mirrored tile inside the driver's dispatch on 65^3 and on 33 x 33 x 65, both with pairwise distinct axis coefficients
+CYCLE_GRIDS = {"17-3": (17, 3, {}), "33-4": (33, 4, {}), "sa65": tc.SA65[1:]}
+CYCLE_PARAMS = [pytest.param(g, kind, setting, id=f"{g}-{kind}-{setting}") for g in ("17-3", "33-4") for kind in CYCLE_KINDS for setting in CYCLE_SETTINGS]
+CYCLE_PARAMS += [pytest.param("sa65", kind, "mixed", id=f"sa65-{kind}-mixed") for kind in ("v-rb", "v-jacobi")]
+
+
 @functools.lru_cache(maxsize=None)
 def cycle_inputs(n):
     """a0, u0, b with float32 values: exact in both working dtypes, so the long-double reference is shared"""
@@ -248,11 +258,12 @@ def cycle_inputs(n):
 
 
 @functools.lru_cache(maxsize=None)
-def cycle_reference(n, levels, kind, setting, prec, coefs):
+def cycle_reference(grid, kind, setting, prec, coefs):
     """coefs: mg_level_coefficients of every level (the doubles the contract casts to T); the coefficient hierarchy is
     vcn_ref's own in `prec` from the shared level 0"""
     mask, sigma = CYCLE_SETTINGS[setting]
-    kw = desc_kw(3, n, levels, {}, capi.MG_F64, **CYCLE_KINDS[kind])
+    n, levels, extra = CYCLE_GRIDS[grid]
+    kw = desc_kw(3, n, levels, extra, capi.MG_F64, **CYCLE_KINDS[kind])
     a0, u0, b = cycle_inputs(n)
     P = vn.VCNProblem(mask=mask, sigma=sigma, prec=prec, **{k: v for k, v in kw.items() if k != "dtype"})
     P.use_handle_coefs(coefs)
@@ -261,26 +272,28 @@ def cycle_reference(n, levels, kind, setting, prec, coefs):
 
 
 @DTYPES
-@pytest.mark.parametrize("setting", list(CYCLE_SETTINGS))
-@pytest.mark.parametrize("kind", list(CYCLE_KINDS))
-@pytest.mark.parametrize("n,levels", [(17, 3), (33, 4)])
-def test_one_cycle_against_long_double(n, levels, kind, setting, dtype):
+@pytest.mark.parametrize("grid,kind,setting", CYCLE_PARAMS)
+def test_one_cycle_against_long_double(grid, kind, setting, dtype):
     """mg_vc_cycle (V, W, F; red-black and Jacobi 6/7, V(2,2), 6 coarse sweeps) with a mask against the long-double reference
     cycle on the handle's level coefficients. Tolerance, as tests/test_vc_gpu.py builds it: 4 x the largest difference between
-    vcn_ref run in the working dtype and in long double on the same input -- computed here, from the reference alone."""
+    vcn_ref run in the working dtype and in long double on the same input -- computed here, from the reference alone. sa65 (V
+    red-black and V Jacobi, the mixed mask): the mirrored tile on distinct axis coefficients and on nz != nx inside the driver.
+    That difference on sa65, from the reference alone on the CPU (max |u| = 4.5): V red-black fp64 1.3e-15, fp32 8.5e-07; V Jacobi
+    fp64 1.4e-15, fp32 7.5e-07 -- about 1.5 eps_T x max |u|, as at 33: the rule stays about rounding on this hierarchy."""
     T = NP[dtype]
     mask, sigma = CYCLE_SETTINGS[setting]
+    n, levels, extra = CYCLE_GRIDS[grid]
     a0, u0, b = (a.astype(T) for a in cycle_inputs(n))
-    kw = desc_kw(3, n, levels, {}, dtype, **CYCLE_KINDS[kind])
+    kw = desc_kw(3, n, levels, extra, dtype, **CYCLE_KINDS[kind])
     with capi.Solver(capi.make_desc(**kw)) as s:
         coefs = tuple(s.level_coefficients(l) for l in range(levels))   # before the shift: vcn_ref adds sigma itself
         s.set_shift(sigma); s.vc_set_faces(mask); s.vc_set_coefficient(a0); s.set_solution(u0); s.set_rhs(b)
-        u_T, u_LD = cycle_reference(n, levels, kind, setting, T, coefs), cycle_reference(n, levels, kind, setting, LD, coefs)
+        u_T, u_LD = cycle_reference(grid, kind, setting, T, coefs), cycle_reference(grid, kind, setting, LD, coefs)
         tol = 4 * float(abs(u_T.astype(LD) - u_LD).max())
         st = s.vc_cycle()
         got = s.get_solution().astype(LD)
         err = float(abs(got - u_LD).max())
-        print(f"n={n} {kind} {setting} {T.__name__}: |gpu - ld| = {err:.3e}, tolerance = {tol:.3e}")
+        print(f"{grid} {kind} {setting} {T.__name__}: |gpu - ld| = {err:.3e}, tolerance = {tol:.3e}")
         assert err <= tol
         assert np.array_equal(s.get_array(RHS, 0), b)
         visits = {capi.CYCLE_V: 1, capi.CYCLE_W: 2 ** (levels - 2), capi.CYCLE_F: levels - 1}[kw["cycle"]]
